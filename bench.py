@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of ARMOUR's constraint callback on MI355X: planning iters/s (fused eval_g + eval_jac_g).
 
-    python bench.py --gpus N --steps K --warmup W [--repeats R] [--batch B] [--obstacles O] [--time-steps T]
+    python bench.py --gpus N --steps K --warmup W [--repeats R] [--batch B] [--obstacles O] [--time-steps T] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (RT/NLPclass.cu:272-396: eval_g + eval_jac_g at a fresh k) over this
 rank's batch of planning problems; one kernel launch per step, inputs (reach-set tables from
@@ -375,6 +375,37 @@ class Timed:
         return worst
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(dirname, tm, rank, world, seed=0):
+    """--dump-outputs DIR: what the last timed step handed its caller, g [B, m] and jac [B, m, n] in float64, as DIR/g.npy and
+    DIR/jac.npy (rank r of a multi-rank run: g_rank<r>.npy, jac_rank<r>.npy).  Above DUMP_LIMIT_BYTES a fixed sample (seeded,
+    so the same for every run with the same arguments) of problems, and if one problem is still too large of constraint rows,
+    is written instead; the sampled indices go to problems.npy / rows.npy (float64) next to the arrays."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    g, jac = tm.d_g.cpu().numpy(), tm.d_jac.cpu().numpy()
+    B, m, n = jac.shape
+    budget = DUMP_LIMIT_BYTES // world - 2 * 8 * (B + m)           # (room for the index files)
+    rng = np.random.default_rng(seed)
+    files = {}
+    if g.nbytes + jac.nbytes > budget:
+        rows = np.arange(m)
+        if 8 * m * (n + 1) > budget:
+            rows = np.sort(rng.choice(m, budget // (8 * (n + 1)), replace=False))
+            files["rows"] = rows.astype(np.float64)
+        probs = np.arange(B)
+        if 8 * len(rows) * (n + 1) * B > budget:
+            probs = np.sort(rng.choice(B, max(1, budget // (8 * len(rows) * (n + 1))), replace=False))
+            files["problems"] = probs.astype(np.float64)
+        g, jac = g[probs][:, rows], jac[probs][:, rows]
+    files["g"], files["jac"] = g, jac
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def summarise(nlp, wall, ev, K, world, extra=None, traffic_name=None):
     """Three byte counts per launch, each divided by the HIP-event launch time:
       algorithmic  the reference formulation's bytes (1440 B per collision row + PZ tables + outputs) -- the yardstick
@@ -678,6 +709,8 @@ def main():
     ap.add_argument("--rank-devices", default="", metavar="D0,D1,...", help="development / tests: device ordinal of every rank (default: rank r on device r); "
                     "several ranks on one device need --dist-backend gloo (RCCL refuses two ranks on one GPU)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend of the barrier and the MAX reduction (nccl = RCCL)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write g and jac of the last timed step as DIR/*.npy "
+                    "(float64, at most 64 MB in all: a seeded sample of a larger output); same arguments, same inputs")
     args = ap.parse_args()
     for kv in args.set_option:
         OPTIONS.append((int(kv.split("=")[0]), float(kv.split("=")[1])))
@@ -773,6 +806,8 @@ def main():
     if os.environ.get("BENCH_PROBE_POINTS") and rank == 0:
         probe_early["after_graph_built"] = sync_probe()
     wall, ev = tm.run(R)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tm, rank, world)
     if os.environ.get("BENCH_PROBE_POINTS") and rank == 0:
         probe_early["after_timed_run"] = sync_probe()
     if not args.no_check and not args.no_sync_probe:

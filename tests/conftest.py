@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -25,6 +28,20 @@ def pytest_collection_modifyitems(config, items):
         for item in items:
             if item.get_closest_marker("gpu") and not item.get_closest_marker("timeout"):
                 item.add_marker(pytest.mark.timeout(300, method="thread"))
+
+
+@pytest.fixture
+def socket_dir(tmp_path):
+    """A buffer directory for `armour_main --serve <dir>`, whose <dir>/armour.sock must fit an AF_UNIX address (107 bytes):
+    tmp_path when it is short enough, else a fresh short directory under /tmp (a deep pytest base directory overflows it)."""
+    if len(str(tmp_path / "armour.sock")) < 100:
+        yield tmp_path
+        return
+    d = tempfile.mkdtemp(prefix="armour-", dir="/tmp" if os.access("/tmp", os.W_OK) else None)
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.fixture(scope="session")

@@ -184,7 +184,7 @@ def test_desired_trajectory_matches_the_matlab_bernstein_formulation():
     assert np.array_equal(hq, q0) and not hqd.any()
 
 
-def test_resident_planner_protocol_without_a_gpu(tmp_path):
+def test_resident_planner_protocol_without_a_gpu(socket_dir):
     """The socket protocol of `armour_main --serve` (armour_amd/csrc/cli_common.h), with no handles created up front so
     that it runs on a CPU-only host: requests reach the resident process, failures come back as the reference's
     conventions (-1 in the .out file, non-zero exit code), `--quit` ends it and removes the socket."""
@@ -196,31 +196,31 @@ def test_resident_planner_protocol_without_a_gpu(tmp_path):
     exe, exe2 = os.path.join(bindir, "armour_main"), os.path.join(bindir, "armtd_main")
     if not (os.path.exists(exe) and os.path.exists(exe2)):
         pytest.skip("executables not built (make -C armour_amd/csrc)")
-    daemon = subprocess.Popen([exe, "--serve", str(tmp_path), "0", "0"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    daemon = subprocess.Popen([exe, "--serve", str(socket_dir), "0", "0"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     try:
         t0 = time.time()
-        while not os.path.exists(tmp_path / "armour.sock"):
+        while not os.path.exists(socket_dir / "armour.sock"):
             assert daemon.poll() is None and time.time() - t0 < 30
             time.sleep(0.01)
         for binary, out in ((exe, "armour.out"), (exe2, "armtd.out")):
-            r = subprocess.run([binary, str(tmp_path)], capture_output=True, text=True, timeout=60)
-            assert r.returncode == 1 and open(tmp_path / out).read().split() == ["-1"]
+            r = subprocess.run([binary, str(socket_dir)], capture_output=True, text=True, timeout=60)
+            assert r.returncode == 1 and open(socket_dir / out).read().split() == ["-1"]
             assert r.stdout == "" and r.stderr == ""          # the iteration ran in the resident process, not here
-        assert subprocess.run([exe, "--quit", str(tmp_path)], timeout=60).returncode == 0
-        assert daemon.wait(timeout=30) == 0 and not os.path.exists(tmp_path / "armour.sock")
+        assert subprocess.run([exe, "--quit", str(socket_dir)], timeout=60).returncode == 0
+        assert daemon.wait(timeout=30) == 0 and not os.path.exists(socket_dir / "armour.sock")
         log = daemon.stdout.read()
         assert log.count("Error reading input files") == 2 and "listening" in log
         # nobody listening any more: the executable runs the iteration itself (and reports the missing input)
-        r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=60)
+        r = subprocess.run([exe, str(socket_dir)], capture_output=True, text=True, timeout=60)
         assert r.returncode == 1 and "Error reading input files" in r.stderr
-        assert subprocess.run([exe, "--quit", str(tmp_path)], timeout=60).returncode == 1
+        assert subprocess.run([exe, "--quit", str(socket_dir)], timeout=60).returncode == 1
     finally:
         if daemon.poll() is None:
             daemon.kill()
             daemon.wait()
 
 
-def test_resident_planner_survives_thousands_of_iterations_and_dies_with_its_front_end(tmp_path):
+def test_resident_planner_survives_thousands_of_iterations_and_dies_with_its_front_end(socket_dir):
     """Two findings of the round-1 review, on a CPU-only host (no handles: every iteration fails fast with the reference's
     "-1" convention, which is all this needs).  (1) file_protocol.ResidentPlanner used to hand the planner a pipe nobody
     read: after ~64 KB of per-iteration "HIP & C++: ..." lines it blocked in fflush and every forwarding armour_main hung.
@@ -235,30 +235,30 @@ def test_resident_planner_survives_thousands_of_iterations_and_dies_with_its_fro
     exe = os.path.join(bindir, "armour_main")
     if not os.path.exists(exe):
         pytest.skip("executables not built (make -C armour_amd/csrc)")
-    with fp.ResidentPlanner(tmp_path, 0, 0) as rp:
+    with fp.ResidentPlanner(socket_dir, 0, 0) as rp:
         for i in range(1500):
-            r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=30)
+            r = subprocess.run([exe, str(socket_dir)], capture_output=True, text=True, timeout=30)
             assert r.returncode == 1 and r.stdout == "" and r.stderr == "", (i, r.stderr)
         log = rp.log()
         assert log.count("Error reading input files") == 1500 and len(log) > 65536
-    assert not os.path.exists(tmp_path / "armour.sock")
+    assert not os.path.exists(socket_dir / "armour.sock")
     # (2) SIGKILL the front end: the worker must go away by itself
-    rp = fp.ResidentPlanner(tmp_path, 0, 0)
-    assert subprocess.run([exe, str(tmp_path)], capture_output=True, timeout=30).returncode == 1      # served
+    rp = fp.ResidentPlanner(socket_dir, 0, 0)
+    assert subprocess.run([exe, str(socket_dir)], capture_output=True, timeout=30).returncode == 1      # served
     rp.proc.send_signal(signal.SIGKILL)
     rp.proc.wait()
     t0 = time.time()
     while True:
         # once the worker is gone nobody answers on the socket and the executable runs the iteration itself (stderr non-empty)
-        r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=30)
+        r = subprocess.run([exe, str(socket_dir)], capture_output=True, text=True, timeout=30)
         if r.stderr:
             break
         assert time.time() - t0 < 20, "the worker outlived its front end"
         time.sleep(0.05)
     # SIGTERM to the front end is relayed: clean shutdown, socket removed, exit code 0
-    rp = fp.ResidentPlanner(tmp_path, 0, 0)
+    rp = fp.ResidentPlanner(socket_dir, 0, 0)
     rp.proc.send_signal(signal.SIGTERM)
-    assert rp.proc.wait(timeout=30) == 0 and not os.path.exists(tmp_path / "armour.sock")
+    assert rp.proc.wait(timeout=30) == 0 and not os.path.exists(socket_dir / "armour.sock")
 
 
 def test_output_files_are_formatted_as_the_reference_formats_them(tmp_path):

@@ -287,29 +287,31 @@ def test_device_against_the_scene_goldens(T):
     nlp.close()
 
 
-REF_SCENARIOS = "/root/reference/kinova_src/kinova_simulator_interfaces/kinova_scenarios/get_kinova_scenario_info.m"
-REF_SCENES = "/root/reference/kinova_src/saved_worlds/random"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_SCENARIOS), reason="the reference checkout is only present in the build container")
 def test_fixtures_are_the_references_own_numbers():
-    """Where the reference checkout exists (this container, not the GPU box): the committed CSVs are byte for byte the reference's files, and start / goal of
-    every hard scenario in the JSON table are the (uncommented) MATLAB statements of get_kinova_scenario_info.m, read as text and evaluated."""
-    import re
+    """The committed CSVs are byte for byte the reference's saved worlds, and start / goal of every hard scenario in the JSON table are
+    the (uncommented) MATLAB statements of get_kinova_scenario_info.m evaluated -- both as recorded in tests/golden/reference_inputs.json."""
+    import sys
     from armour_amd.scenes import SCENE_DIR
-    names = sorted(f for f in os.listdir(REF_SCENES) if f.endswith(".csv"))
-    assert len(names) == 100
-    for f in names:
-        assert open(os.path.join(REF_SCENES, f), "rb").read() == open(os.path.join(SCENE_DIR, f), "rb").read(), f
-    text = open(REF_SCENARIOS).read()
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_reference_fixtures as mrf
+    rec = mrf.load(mrf.INPUTS)
+    digests = rec["saved_worlds_sha256"]
+    assert len(digests) == 100 and sorted(f for f in os.listdir(SCENE_DIR) if f.endswith(".csv")) == sorted(digests)
+    for f, want in digests.items():
+        assert hashlib.sha256(open(os.path.join(SCENE_DIR, f), "rb").read()).hexdigest() == want, f
     with open(os.path.join(SCENE_DIR, "hard_scenarios.json")) as fh:
         table = {s["scenario"]: s for s in json.load(fh)["scenarios"]}
-    blocks = re.split(r"\n\s*case (\d) %", text)
-    for k in range(1, len(blocks), 2):
-        case, body = int(blocks[k]), blocks[k + 1]
+    assert sorted(table) == sorted(int(c) for c in rec["hard_scenarios"])
+    for case, sc in rec["hard_scenarios"].items():
         for field in ("start", "goal"):
-            m = [ln for ln in body.splitlines() if re.match(rf"\s*{field} = \[", ln)]     # (commented alternatives start with %)
-            vec = re.search(r"\[(.*?)\]", m[0]).group(1)
-            vals = [float(eval(x.strip(), {"pi": np.pi})) for x in re.split(r"[;,]", vec) if x.strip()]
-            assert np.allclose(vals, table[case][field], rtol=0, atol=1e-15), (case, field)
+            assert np.allclose(sc[field], table[int(case)][field], rtol=0, atol=1e-15), (case, field)
     assert len(table) == 7
+
+
+@pytest.mark.skipif(not os.path.exists("/root/reference/kinova_src"), reason="reference checkout not present")
+def test_recorded_inputs_are_the_reference_files():
+    """Where the reference checkout exists: its saved worlds and scenario script give exactly the recorded digests and numbers."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_reference_fixtures as mrf
+    assert mrf.load(mrf.INPUTS) == json.loads(json.dumps(mrf.inputs_from_reference()))

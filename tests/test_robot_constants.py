@@ -1,7 +1,7 @@
 """The product's robot presets (include/armour_robot_kinova.h, include/armour_robot_fetch.h, hand-written) against the
 oracle's (oracle/robot_tables.hpp, GENERATED from the reference headers by oracle/gen_robot_tables.py) -- field by field,
-exact -- and, where /root/reference exists (the build container), both against a fresh parse of
-RT/KinovaWithoutGripperInfo.h, RT/KinovaInfo.h, CMP/FetchInfo.h and RT/Parameters.h.  Closes the round-1 hole where the
+exact -- and both against the numbers of RT/KinovaWithoutGripperInfo.h, RT/KinovaInfo.h, CMP/FetchInfo.h and
+RT/Parameters.h recorded in tests/golden/reference_constants.json (checked against a fresh parse where the reference exists).  Closes the round-1 hole where the
 oracle included the product's own constant header."""
 import ctypes as C
 import os
@@ -45,22 +45,38 @@ def test_default_parameters_equal():
         assert bytes(planner.default_params(T)) == bytes(cpu_oracle.default_params(T))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/kinova_src"), reason="reference checkout not present (GPU box)")
+def _recorded():
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_reference_fixtures as mrf
+    return mrf
+
+
 def test_both_against_the_reference_headers():
+    """Against the reference headers as recorded in tests/golden/reference_constants.json (make_reference_fixtures.py)."""
     import gen_robot_tables as g
-    robots = {name: g.robot_from_header(name) for name in PRESETS}
-    assert open(os.path.join(ROOT, "oracle", "robot_tables.hpp")).read() == g.emit_header(robots), "re-run oracle/gen_robot_tables.py"
+    mrf = _recorded()
+    rec = mrf.load(mrf.CONSTANTS)
+    robots, p = rec["robots"], rec["params"]
+    assert list(robots) == list(PRESETS)
+    assert open(os.path.join(ROOT, "oracle", "robot_tables.hpp")).read() == g.emit_header(robots, p), "re-run oracle/gen_robot_tables.py"
     for name, ref in robots.items():
         assert g.diff(ref, g.robot_from_struct(_product(name))) == [], name
         assert g.diff(ref, g.robot_from_struct(_oracle(name))) == [], name
     # the only mixed-axis chain of the reference
     assert robots["fetch"]["axes"] == [3, 2, 1, 2, 1, 2, 1, 0, 0] and robots["fetch"]["num_joints"] == 9
-    p = g.params_from_reference()
     from armour_amd import planner
     d = planner.default_params(p["num_time_steps_reference"])
     assert list(d.k_range) == p["k_range"] and d.duration == p["duration"] and d.simplify_threshold == p["simplify_threshold"]
     assert d.t_plan == p["t_plan"] and d.cost_scale == p["cost_scale"]
     assert d.collision_violation_threshold == p["collision_violation_threshold"] and d.torque_violation_threshold == p["torque_violation_threshold"]
+
+
+@pytest.mark.skipif(not os.path.exists("/root/reference/kinova_src"), reason="reference checkout not present")
+def test_recorded_constants_are_the_reference_headers():
+    """Where the reference checkout exists: a fresh parse of its headers gives exactly the recorded numbers."""
+    import json
+    mrf = _recorded()
+    assert mrf.load(mrf.CONSTANTS) == json.loads(json.dumps(mrf.constants_from_reference()))
 
 
 def test_per_link_uncertainty_overrides_the_scalar():
