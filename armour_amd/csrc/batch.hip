@@ -180,17 +180,17 @@ extern "C" int armour_batch_set_problems(ArmourBatch* bt, int32_t B, int32_t O, 
     const int n = bt->n;
     // ONE reach-set kernel for all slots of a problem set (every slot used to choose from its own shard, so the 18 + 17
     // problems of a batch of 35 over two slots were built by two different kernels, whose radii differ to 1e-12).  With the option left
-    // automatic the batch takes the kernel the SMALLEST shard would take (armour_p1_build's rule: time-vectorised from B_shard * T >= 50 *
-    // ARMOUR_OPT_P1_TV_MIN_GROUPS on) -- deciding from the whole batch instead would put shards of a few problems on the time-vectorised
-    // kernel, three times slower there.  Tables still depend on the NUMBER of slots within the stated 1e-12; a caller that needs them
-    // bit-identical for every device count pins ARMOUR_OPT_P1_BUILD to 1 or 2 (include/armour_hip.h).
+    // automatic the batch takes the kernel the SMALLEST shard would take (armour_p1_auto_kernel) -- deciding from the whole batch instead would
+    // put shards of a few problems on the time-vectorised kernel, three times slower there.  Tables still depend on the NUMBER of slots within
+    // the stated 1e-12; a caller that needs them bit-identical for every device count pins ARMOUR_OPT_P1_BUILD to 1 or 2 (include/armour_hip.h).
     if (bt->user_build == 0) {
         int smallest = B;
         for (int d = 0; d < G; d++)
             if (bt->first[d + 1] > bt->first[d]) smallest = std::min(smallest, bt->first[d + 1] - bt->first[d]);
         double min_groups = 31.0;   // (= kTuning's default; the option always exists, this is only the value if the query failed)
         (void)armour_get_option(bt->slot[0], ARMOUR_OPT_P1_TV_MIN_GROUPS, &min_groups);
-        const int build = (long long)smallest * bt->T >= 50ll * (long long)min_groups ? 2 : 1;
+        // (fk_only false, as this rule has always been: the lone handle's rule holds forward-kinematics-only modes to 5/3 the threshold)
+        const int build = armour_p1_auto_kernel(smallest, bt->T, (int)min_groups, false);
         for (ArmourPlanner* h : bt->slot) (void)armour_set_option(h, ARMOUR_OPT_P1_BUILD, build);
     }
     const int rc = on_every_slot(bt, [&](int d) {

@@ -253,6 +253,15 @@ int armour_bounds_launch(ArmourPlanner* h, const double* d_torque_radius);   // 
 int armour_p1_build(ArmourPlanner* h, const double* obstacles);  // h->mode selects the ARMOUR or the ARMTD chain
 void armour_p1_free(ArmourPlanner* h);
 int armour_p1_full_planes(ArmourPlanner* h, double* d_full);
+
+// The reach-set kernel ARMOUR_OPT_P1_BUILD = 0 takes for B problems of T time steps (ARMOUR_P1_KERNEL_*).  min_groups, ARMOUR_OPT_P1_TV_MIN_GROUPS, default 31:
+// below this the per-step kernel is faster (re-measured at the end of round 4, B problems of 100 steps, per-step against time-vectorised: 14: 5.84 / 6.35 ms, 16: 7.49 / 6.64 -- the per-step kernel steps up with every 768 items -- 18: 8.04 / 6.66; round 3: 36, profiles/r03_p1_breakeven.txt)
+// (the break-even is one of WORK: the per-step kernel's time grows with B * T, a chain's latency hardly depends on the lanes in use -- 64 problems of 20 time steps are faster step by step -- so the threshold counts groups of 50 time steps' worth of items)
+// fk_only: comparison mode, or ARMOUR without input constraints -- every item a forward-kinematics item, its chain a fifth of the RNEA chain: the per-step kernel stays ahead up to B = 30 there, so 60 groups (2.97 against 2.59 ms at B = 32, 2.40 against 2.57 at B = 28)
+inline int armour_p1_auto_kernel(int B, int T, int min_groups, bool fk_only) {
+    return (long long)B * T >= 50ll * (fk_only ? min_groups * 5 / 3 : min_groups) ? ARMOUR_P1_KERNEL_TIME_VECTORISED : ARMOUR_P1_KERNEL_PER_STEP;
+}
+
 int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, const int* cnt, const uint64_t* const* keys,
                           const double* const* coef, const double* cen, const double* ind, const double* ind2, const double* consts,
                           int r, int out_cap, uint64_t* out_keys, double* out_coef, double* out_misc);

@@ -1809,7 +1809,6 @@ TvArenaPool g_tv_pool[kMaxPoolDevices];
 struct P1Work {
     unsigned char* arena = nullptr;
     size_t arena_total = 0;
-    int waves = 0;
     unsigned* d_status = nullptr;
     double* d_link_gens = nullptr; size_t gens_cap = 0;
     double* d_torque_radius = nullptr; size_t tr_cap = 0;
@@ -1830,25 +1829,22 @@ struct P1Work {
 #ifndef P1_TV_LAUNCH
 #define P1_TV_LAUNCH armour_p1_tv_launch_g64
 #endif
+// Set a reach-set kernel's dynamic-LDS size, then launch it: `blocks` blocks of `nw` waves (the caller holds g_p1_launch_mu)
+static hipError_t p1_launch(void (*kernel)(P1Cfg), int nw, int blocks, size_t smem, hipStream_t stream, const P1Cfg& cf) {
+    if (const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(WAVE * nw), smem, stream, cf);
+    return hipGetLastError();
+}
+
 __attribute__((visibility("hidden"))) hipError_t P1_TV_LAUNCH(int nw_launch, int nw, int blocks, size_t smem, hipStream_t stream, const void* cfg) {
     const P1Cfg& cf = *static_cast<const P1Cfg*>(cfg);
-    hipError_t e = hipSuccess;
     if (nw_launch == 8) {
-        if constexpr (kTvDedicatedHelpers) {
-            if ((e = hipFuncSetAttribute((const void*)tvchain::armour_p1_tv_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) != hipSuccess) return e;
-            hipLaunchKernelGGL(tvchain::armour_p1_tv_kernel<8>, dim3(blocks), dim3(WAVE * 8), smem, stream, cf);
-        }
-    } else if (nw == 4) {
-        if ((e = hipFuncSetAttribute((const void*)tvchain::armour_p1_tv_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) != hipSuccess) return e;
-        hipLaunchKernelGGL(tvchain::armour_p1_tv_kernel<4>, dim3(blocks), dim3(WAVE * 4), smem, stream, cf);
-    } else if (nw == kRoles) {
-        if ((e = hipFuncSetAttribute((const void*)tvchain::armour_p1_tv_kernel<kRoles>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) != hipSuccess) return e;
-        hipLaunchKernelGGL(tvchain::armour_p1_tv_kernel<kRoles>, dim3(blocks), dim3(WAVE * kRoles), smem, stream, cf);
-    } else {
-        if ((e = hipFuncSetAttribute((const void*)tvchain::armour_p1_tv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)) != hipSuccess) return e;
-        hipLaunchKernelGGL(tvchain::armour_p1_tv_kernel<1>, dim3(blocks), dim3(WAVE), smem, stream, cf);
+        if constexpr (kTvDedicatedHelpers) return p1_launch(tvchain::armour_p1_tv_kernel<8>, 8, blocks, smem, stream, cf);
+        return hipGetLastError();
     }
-    return hipGetLastError();
+    if (nw == 4) return p1_launch(tvchain::armour_p1_tv_kernel<4>, 4, blocks, smem, stream, cf);
+    if (nw == kRoles) return p1_launch(tvchain::armour_p1_tv_kernel<kRoles>, kRoles, blocks, smem, stream, cf);
+    return p1_launch(tvchain::armour_p1_tv_kernel<1>, 1, blocks, smem, stream, cf);
 }
 
 #ifndef P1_TV_VARIANT
@@ -1887,16 +1883,20 @@ void armour_p1_free(ArmourPlanner* h) {
     h->p1 = nullptr;
 }
 
+// a device buffer of at least `need` elements (`fresh`, if given: set when it was allocated anew)
 template <class Tp>
-static int grow(Tp** p, size_t* cap, size_t need) {
+static int grow(Tp** p, size_t* cap, size_t need, bool* fresh = nullptr) {
     if (need <= *cap && *p) return ARMOUR_OK;
     if (*p) (void)hipFree(*p);
     *p = nullptr;
     HIPCHK(hipMalloc((void**)p, (need ? need : 1) * sizeof(Tp)));
     *cap = need;
+    if (fresh) *fresh = true;
     return ARMOUR_OK;
 }
 
+// the centres / radii a block keeps in LDS (p1_shared_lds)
+static size_t ci_doubles(const Layout& L) { return (size_t)L.nV * 9 + kNS * 3 + kNM * 27 + (size_t)L.nJM * 27 + (size_t)L.nJV * 9 + (size_t)L.nJS * 3; }
 
 // test hook (include/armour_hip.h: armour_debug_pz_op)
 int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, const int* cnt, const uint64_t* const* keys,
@@ -1907,8 +1907,7 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
     int cap_raw = 64;
     while (cap_raw < h->lim.raw_terms) cap_raw <<= 1;
     const Layout L = make_layout(J, n, h->lim.work_monomials, 1);
-    const size_t ci_doubles = (size_t)L.nV * 9 + kNS * 3 + kNM * 27 + (size_t)L.nJM * 27 + (size_t)L.nJV * 9 + (size_t)L.nJS * 3;
-    const size_t smem = p1_wave_lds(cap_raw, cap_raw) + p1_shared_lds(ci_doubles);
+    const size_t smem = p1_wave_lds(cap_raw, cap_raw) + p1_shared_lds(ci_doubles(L));
     HIPCHK(hipFuncSetAttribute((const void*)armour_p1_pzop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     unsigned char* arena = nullptr;
     HIPCHK(hipMalloc((void**)&arena, L.total));
@@ -1986,6 +1985,386 @@ static void armour_margin_from_words(ArmourPlanner* h, const unsigned long long*
     }
 }
 
+// The P1Cfg fields every launch of a reach-set kernel shares, for sort buffers of `cap` entries; each launch path sets its arena and its own fields
+static P1Cfg p1_cfg_base(const ArmourPlanner* h, const P1Work* wk, int cap) {
+    P1Cfg cf;
+    memset(&cf, 0, sizeof(cf));
+    cf.B = h->B; cf.T = h->T; cf.J = h->J; cf.n = h->n; cf.O = h->O;
+    cf.capW = h->lim.work_monomials; cf.capRaw = cap; cf.capKey = key_cap(cap); cf.capL = h->lim.link_monomials; cf.capT = h->lim.torque_monomials;
+    cf.rb = h->robot; cf.pr = h->params; cf.ub = h->ub;
+    cf.bez = h->d_bez;
+    cf.mode = h->mode; cf.fk_only = h->no_torque() ? 1 : 0; cf.jrs = h->d_jrs;
+    cf.link_count = h->d_link_count; cf.link_center = h->d_link_center; cf.link_indep = h->d_link_indep;
+    cf.link_keys = h->d_link_keys; cf.link_coeff = h->d_link_coeff;
+    cf.tq_count = h->d_tq_count; cf.tq_center = h->d_tq_center; cf.tq_indep = h->d_tq_indep;
+    cf.tq_keys = h->d_tq_keys; cf.tq_coeff = h->d_tq_coeff;
+    cf.link_gens = wk->d_link_gens; cf.torque_radius = wk->d_torque_radius; cf.status = wk->d_status;
+    cf.margin = wk->d_margin;
+    return cf;
+}
+
+// a build's error from the status words, other than a capacity flag of the sort buffers
+static int p1_status_error(const unsigned* st) {
+    if (st[ST_ERR] & (unsigned)ERR_PAIR) {   // not a capacity limit: two waves that share an operator lost each other (psync), their barriers went off
+        armour_set_error("reach-set build: a pair of waves lost its barrier (flags 0x%x) -- an internal synchronisation error, not a capacity limit; "
+                         "ARMOUR_OPT_P1_STEP_PAIRS = 0 builds without paired waves", st[ST_ERR]);
+        return ARMOUR_EDEVICE;
+    }
+    if (st[ST_ERR] & ~(unsigned)ERR_RAW_OVERFLOW) {
+        armour_set_error("[dbg word3=%u] reach-set build overflow (flags 0x%x: 2=work_monomials, 4=link/torque_monomials, 8=link generators); max raw terms %u, max monomials %u",
+                         st[3], st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
+        return ARMOUR_ECAPACITY;
+    }
+    return ARMOUR_OK;
+}
+
+// ---- the per-step kernel: a launch is planned (plan_step_launch), queued (queue_step_launch) and, after the caller's wait, read (finish_step_launch)
+// LDS of a per-step block of `nw` waves (1, kRoles or 4) with sort buffers of `cap` entries
+static size_t step_lds_bytes(const ArmourPlanner* h, int cap, int nw = 1) {
+    const Layout L = make_layout(h->J, h->n, h->lim.work_monomials, nw);
+    return (size_t)(nw == 4 ? 3 : nw) * p1_wave_lds(key_cap(cap), cap) + (nw == 4 ? p1_wave_lds(kFkCapKey, kFkCapRaw) : 0) + p1_shared_lds(ci_doubles(L));
+}
+
+// one-wave blocks a CU holds at a time with sort buffers of `cap` entries
+static int step_waves_per_cu(const ArmourPlanner* h, int cap) {
+    const int max_waves_env = std::min(h->tune(ARMOUR_OPT_P1_MAX_WAVES_PER_CU), 4 * P1_WAVES_PER_SIMD);
+    return std::max(1, std::min(max_waves_env, (int)((size_t)160 * 1024 / step_lds_bytes(h, cap))));
+}
+
+// One launch of the per-step kernel over `n_items` work items (items == nullptr: all of them) with sort buffers of `cap` entries; with `collect` the items that overflow them are listed in wk->d_retry instead of failing the launch
+struct StepPlan {
+    int cap, n_items; const int* items; bool collect;
+    int nw, per_cu, waves; size_t smem;   // `waves` blocks of nw waves and smem bytes of LDS, per_cu of them per CU
+    bool phase_log;                       // ARMOUR_P1_TRACE: the four-wave blocks log their phase clocks (wk->d_phase holds 1024 blocks)
+    bool split; int fk_items;             // the forward kinematics of every item as an item of its own
+    bool two_cu; int helper0;             // a time step on two CUs: block k builds item k, block helper0 + k helps it
+};
+
+static int plan_step_launch(const ArmourPlanner* h, int cus, int cap, const int* d_items, int n_items, bool collect, StepPlan* p) {
+    // few items (at most one per CU): three waves per item, the roles of a time step run concurrently (latency);
+    // otherwise one wave per item and as many items per CU as the LDS holds (throughput)
+    const int nw_env = h->tune(ARMOUR_OPT_P1_STEP_WAVES);   // (0: automatic)
+    // (round 3) ... FOUR waves when the block's LDS holds the fourth wave's small sort buffers as well: the forward kinematics,
+    // the omega recursion and the constant cross products of the linear acceleration leave the three recursion waves for a wave
+    // of their own (run_rnea_free, the choreography of the time-vectorised kernel's four-wave blocks) and no item is issued twice
+    const int free_env0 = h->tune(ARMOUR_OPT_P1_STEP_FREE);
+    const bool fits4 = free_env0 && step_lds_bytes(h, cap, 4) <= (size_t)160 * 1024;
+    // Four-wave blocks take an item in 1.17 ms, one per CU at a time; one-wave blocks in 2.7 ms, waves_per_cu of them per CU.  With more
+    // items than CUs the blocks loop, and what decides is the number of rounds either shape needs (measured, B problems of 100 steps,
+    // four waves against one: B = 3..5 2.3-2.6 against 2.8-3.1 ms, 6..7 3.5-3.7 against 3.2-3.5, 8..10 4.4-4.8 against 5.2-5.7,
+    // 12 6.0 either way, 14..15 7.0 against 6.3: profiles/r03_p1_four_waves.txt; re-measured at the end of round 3 with both shapes faster:
+    // a round of four-wave items 1.0 ms, of one-wave items 2.6 ms -- B = 11 5.07 against 5.27, 16 7.16 against 7.70, 14 6.2 against 5.7)
+    const int waves_per_cu = step_waves_per_cu(h, cap);
+    const long long r4 = (n_items + cus - 1) / cus, r1 = (n_items + (long long)cus * waves_per_cu - 1) / ((long long)cus * waves_per_cu);
+    const bool multi = h->no_torque() ? false  // forward kinematics only: a single role
+                       : nw_env ? nw_env >= 3
+                       : collect ? false
+                       : fits4 ? r4 <= 5 && 100 * r4 < 258 * r1   // (round 4, after the merge-path sorts and the item queue, B problems of 100 steps, four waves | one: 5: 2.22 | 2.66, 8: 3.73 | 3.76, 10: 4.03 | 4.46, 12: 4.83 | 4.94, 13: 5.63 | 5.04, 15: 5.90 | 5.28 -- from the sixth round on the one-wave blocks' throughput wins)
+                               : (n_items <= cus && step_lds_bytes(h, cap, kRoles) <= (size_t)160 * 1024);
+    const bool four = multi && free_env0 && (nw_env ? nw_env == 4 : fits4);
+    const int nw = four ? 4 : multi ? kRoles : 1;
+    const size_t smem = step_lds_bytes(h, cap, nw);
+    if (smem > (size_t)160 * 1024) { armour_set_error("raw_terms=%d does not fit the 160 KiB LDS", cap); return ARMOUR_EINVAL; }
+    const int per_cu = multi ? 1 : waves_per_cu;
+    // with at least as many idle CUs as items, the forward kinematics of every item runs as an item of its own
+    const int split_env = h->tune(ARMOUR_OPT_P1_STEP_SPLIT_FK);   // (-1: automatic)
+    const bool split = split_env >= 0 ? (split_env != 0 && multi) : (multi && n_items <= cus);   // (round 4: also when the two kinds of items together are more than the blocks -- the blocks draw the RNEA items first and fill up with the forward kinematics: B = 2 1.095 -> 1.081 ms)
+    const int fk_items = split ? n_items : 0;
+    // A time step on two CUs (p1_free.inc.h): every item gets a helper block on a CU of its own, which also runs the item's forward kinematics.
+    // Block k builds item k, block helper0 + k helps it; helper0 a multiple of 8 puts the two on one XCD (checked on the device, item by item).
+    const int helper0 = (n_items + 7) & ~7;
+    const bool two_cu = four && split && !collect && !d_items && h->tune(ARMOUR_OPT_P1_STEP_TWO_CU) && !h->p1_two_cu_off && h->mode == ARMOUR_MODE_ARMOUR && helper0 + n_items <= cus * per_cu
+                        && h->tune(ARMOUR_OPT_P1_STEP_FREE) && h->tune(ARMOUR_OPT_P1_STEP_AUX3);   // (the choreography it changes is the free-running one with the w_aux recursion on the fourth wave)
+    const int waves = two_cu ? helper0 + n_items : std::min(n_items + fk_items, cus * per_cu);
+    *p = StepPlan{cap, n_items, d_items, collect, nw, per_cu, waves, smem, armour_trace_p1() && nw == 4 && waves <= 1024, split, fk_items, two_cu, helper0};
+    return ARMOUR_OK;
+}
+
+// The launch and the copy of its status words into the page-locked block `st_pin` (a copy into pageable memory would wait by itself), queued and NOT waited for: the caller queues more behind it, waits once and calls finish_step_launch
+static int queue_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, unsigned* st_pin) {
+    const Layout L = make_layout(h->J, h->n, h->lim.work_monomials, p.nw);
+    int rc;
+    if ((rc = grow(&wk->arena, &wk->arena_total, (size_t)p.waves * L.total)) != ARMOUR_OK) return rc;
+    P1Cfg cf = p1_cfg_base(h, wk, p.cap);
+    cf.arena_bytes = L.total; cf.arena = wk->arena;
+    cf.free_running = h->tune(ARMOUR_OPT_P1_STEP_FREE);   // (0 = a barrier per joint)
+    if (!p.items) HIPCHK(hipMemsetAsync(wk->d_margin, 0, (size_t)h->B * sizeof(unsigned long long), h->stream));   // (a launch over ALL items starts the margins afresh; the second pass over a few overflowed items adds to them)
+    cf.items = p.items; cf.n_items = p.n_items; cf.fk_items = p.fk_items;
+    cf.tv_aux_on_fk_wave = h->tune(ARMOUR_OPT_P1_STEP_AUX3);   // (four-wave blocks: the w_aux recursion next to omega on the fourth wave)
+    cf.step_pairs = h->tune(ARMOUR_OPT_P1_STEP_PAIRS) == 2 || (h->tune(ARMOUR_OPT_P1_STEP_PAIRS) == 1 && p.n_items + p.fk_items <= p.waves);   // (1: with a block per item only -- after the merge-path sorts the pairs are worth 1 % to a lone problem and cost 2 % when the blocks loop: B = 4 1.95 against 1.99 ms, 8: 3.73 against 3.82; 2: always)
+    cf.queue_order = h->tune(ARMOUR_OPT_P1_STEP_QUEUE);
+    cf.queue = cf.queue_order != 0 && p.n_items + p.fk_items > p.waves ? wk->d_status + ST_WORDS + 60 : nullptr;   // (with a block per item there is nothing to draw: B = 1 1.044 against 1.069 ms.  The word: one of the status block that the profile counters of development builds do not reach)
+    if (cf.queue) HIPCHK(hipMemsetAsync(cf.queue, 0, sizeof(unsigned), h->stream));
+    cf.tail_cross = p.split ? h->tune(ARMOUR_OPT_P1_STEP_TAIL_CROSS) : 0;   // (with its forward kinematics to do the fourth wave has no time to spare)
+    cf.retry_list = p.collect ? wk->d_retry + 1 : nullptr; cf.retry_count = reinterpret_cast<unsigned*>(wk->d_retry);
+    if (p.phase_log) {
+        if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
+        HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
+        cf.phase_log = wk->d_phase;
+    }
+    cf.two_cu = p.two_cu ? h->tune(ARMOUR_OPT_P1_STEP_TWO_CU) : 0; cf.helper0 = p.helper0;
+    cf.lean_back = h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 1; cf.late_jrs = (h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 2) == 0;   // (development: + 2 builds every joint before the roles begin)
+    if (p.two_cu) {
+        bool clear = false;
+        if ((rc = grow(&wk->d_xch, &wk->xch_cap, (size_t)p.n_items * kXchBytes, &clear)) != ARMOUR_OK) return rc;
+        if (++wk->xch_epoch >= (1 << 23)) { wk->xch_epoch = 1; clear = true; }
+        if (clear) HIPCHK(hipMemsetAsync(wk->d_xch, 0, wk->xch_cap, h->stream));
+        cf.xch = wk->d_xch; cf.xch_epoch = wk->xch_epoch;
+    }
+    HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
+    if (p.collect) HIPCHK(hipMemsetAsync(wk->d_retry, 0, sizeof(int), h->stream));
+    HIPCHK(hipEventRecord(wk->ev0, h->stream));
+    {
+        std::lock_guard<std::mutex> lk(g_p1_launch_mu);
+        if (p.nw == 4) HIPCHK(p1_launch(armour_p1_chain_kernel<4>, 4, p.waves, p.smem, h->stream, cf));
+        else if (p.nw == kRoles) HIPCHK(p1_launch(armour_p1_chain_kernel<kRoles>, kRoles, p.waves, p.smem, h->stream, cf));
+        else HIPCHK(p1_launch(armour_p1_chain_kernel<1>, 1, p.waves, p.smem, h->stream, cf));
+    }
+    HIPCHK(hipEventRecord(wk->ev1, h->stream));
+    HIPCHK(hipMemcpyAsync(st_pin, wk->d_status, ST_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    armour_build_stamp("launch-queued");
+    return ARMOUR_OK;
+}
+
+// ARMOUR_P1_TRACE, per-step kernel: where the blocks' time went (wave 0 of each): median / max over the main blocks, then over the helpers
+static int report_step_phases(const P1Work* wk, const StepPlan& p) {
+    std::vector<long long> ph((size_t)p.waves * 8);
+    HIPCHK(hipMemcpy(ph.data(), wk->d_phase, ph.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    const char* names[5] = {"JRS", "decision", "forward pass", "backward pass", "tables"};
+    for (int grp = 0; grp < (p.two_cu ? 2 : 1); grp++) {
+        const int b0 = grp == 0 ? 0 : p.helper0, b1 = grp == 0 ? p.n_items : p.helper0 + p.n_items;
+        fprintf(stderr, "[P1 phases, %s blocks, cycles median / max]", grp == 0 ? "main" : "helper");
+        for (int k = 0; k < 5; k++) {
+            std::vector<long long> d;
+            for (int bl = b0; bl < b1 && bl < p.waves; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[k + 1] > 0 && r[k] > 0) d.push_back(r[k + 1] - r[k]); }
+            if (d.empty()) continue;
+            std::sort(d.begin(), d.end());
+            fprintf(stderr, " %s %lld / %lld", names[k], d[d.size() / 2], d.back());
+        }
+        std::vector<long long> tot;
+        for (int bl = b0; bl < b1 && bl < p.waves; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[5] > 0) tot.push_back(r[5] - r[0]); }
+        if (!tot.empty()) { std::sort(tot.begin(), tot.end()); fprintf(stderr, " | item %lld / %lld", tot[tot.size() / 2], tot.back()); }
+        int local = 0, xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int bl = b0; bl < b1 && bl < p.waves; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[6] == 2) { local++; fprintf(stderr, " [block %d on XCD %lld: one CU]", bl, r[7]); } xcd[r[7] & 7]++; }
+        fprintf(stderr, " | %d of %d on their own; blocks per XCD %d %d %d %d %d %d %d %d\n", local, b1 - b0, xcd[0], xcd[1], xcd[2], xcd[3], xcd[4], xcd[5], xcd[6], xcd[7]);
+    }
+    return ARMOUR_OK;
+}
+
+// After the caller's wait: the launch's status words into `st`, its device time onto *total_ms, build_info, the ARMOUR_P1_TRACE lines
+static int finish_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, const unsigned* st_pin, unsigned* st, float* total_ms) {
+    memcpy(st, st_pin, ST_WORDS * sizeof(unsigned));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
+    *total_ms += ms;
+    h->build_info[0] = ARMOUR_P1_KERNEL_PER_STEP; h->build_info[1] = p.nw; h->build_info[2] = p.cap; h->build_info[3]++;
+#ifdef P1_PROFILE
+    unsigned long long pr[PR_WORDS];
+    HIPCHK(hipMemcpy(pr, wk->d_status + ST_WORDS, sizeof(pr), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[P1 profile, wave 0] cycles: fill %llu sort %llu emit %llu abs_sum %llu total %llu | simplify calls %llu (N<=64: %llu) raw terms %llu\n",
+            pr[PR_FILL], pr[PR_SORT], pr[PR_EMIT], pr[PR_ABS], pr[PR_TOTAL], pr[PR_CALLS], pr[PR_SMALL], pr[PR_TERMS]);
+    fprintf(stderr, "[P1 profile, wave 0] whole-call cycles: N<=64 %llu | 64<N<=512: %llu in %llu calls (%llu terms) | N>512: %llu in %llu calls (%llu terms)\n",
+            pr[PR_CYC64], pr[PR_CYC512], pr[PR_N512], pr[PR_TERMS512], pr[PR_CYCBIG], pr[PR_NBIG], pr[PR_TERMSBIG]);
+#endif
+    if (const int rc = p.phase_log ? report_step_phases(wk, p) : ARMOUR_OK; rc != ARMOUR_OK) return rc;
+    if (armour_trace_p1()) fprintf(stderr, "[P1] %d items, cap_raw %d: %d blocks of %d wave(s)%s (%d per CU, %zu B LDS), %.2f ms, flags 0x%x, max raw terms %u, max monomials %u\n", p.n_items, p.cap, p.waves, p.nw, p.two_cu ? ", two CUs per item" : "", p.per_cu, p.smem, ms, st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
+    return ARMOUR_OK;
+}
+
+// The one way off two CUs per time step: a time step lost its helper block (ERR_HELPER: the caller builds again) or its helper started too late (ERR_HELPER_LATE, `late`: good tables,
+// built late -- some main block waited 1.5 ms for a helper that had not started: a shared device, fewer CUs than reported).  The handle stays on one CU per step; armour_set_option switches two CUs on again.
+static void p1_leave_two_cu(ArmourPlanner* h, unsigned st_err, bool late) {
+    if (armour_trace_p1()) fprintf(stderr, late ? "[P1] a helper block started too late for its item (flags 0x%x): one CU per time step from the next build on\n"
+                                                : "[P1] a helper block's results did not arrive (flags 0x%x): building again on one CU per time step\n", st_err);
+    h->p1_two_cu_off = true;
+    h->tuning[ARMOUR_OPT_P1_STEP_TWO_CU - ARMOUR_OPT_FIRST_TUNING] = 0;
+}
+
+// The status words of a pass of the retry loop: *again when the pass is queued once more -- a lost helper, or sort buffers below 16384 entries that overflowed (doubled, and the next build of this handle starts there) -- otherwise the build's error, if any
+static int step_pass_verdict(ArmourPlanner* h, unsigned* st, int* cap_raw, bool* again) {
+    if ((st[ST_ERR] & (unsigned)ERR_HELPER) && !h->p1_two_cu_off) { p1_leave_two_cu(h, st[ST_ERR], false); *again = true; return ARMOUR_OK; }
+    if (st[ST_ERR] & (unsigned)ERR_HELPER_LATE) { p1_leave_two_cu(h, st[ST_ERR], true); st[ST_ERR] &= ~(unsigned)ERR_HELPER_LATE; }
+    if (st[ST_ERR] & ERR_RAW_OVERFLOW) {
+        if (*cap_raw < 16384) { *cap_raw <<= 1; h->p1_step_cap_hint = *cap_raw; *again = true; return ARMOUR_OK; }
+        armour_set_error("a PZ product produced more than %d raw terms (raise ArmourLimits.raw_terms)", *cap_raw);
+        return ARMOUR_ECAPACITY;
+    }
+    return p1_status_error(st);
+}
+
+// ---- the half-space kernels, queued behind the reach sets
+static int queue_planes(ArmourPlanner* h, P1Work* wk) {
+    const int B = h->B, T = h->T, J = h->J, O = h->O, Q = J * T * O;
+    HIPCHK(hipEventRecord(wk->ev2, h->stream));
+    const int nbx = (Q + 63) / 64, nbc = (Q + 255) / 256;
+    // [B][nbx][4] per-wave masks of the planes kernel | [B][nbc] per-block masks of the class pre-pass | [B] its result | [B] planes a sampled row needs
+    const size_t part_words = (size_t)B * nbx * 4, pre_words = (size_t)B * nbc;
+    if (const int rc = grow(&wk->d_skip_part, &wk->skip_part_cap, part_words + pre_words + 2 * (size_t)B); rc != ARMOUR_OK) return rc;
+    unsigned long long* d_pre_part = wk->d_skip_part + part_words;
+    unsigned long long* d_pre = d_pre_part + pre_words;
+    unsigned long long* d_live = d_pre + B;
+    // The table holds what the fused evaluation reads and nothing else (planes_of_group): ARMOUR_OPT_P1_FULL_PLANES = 1 builds
+    // the full one.  d = A.c is stored for the small launches that read it; batches of >= 8 problems or >= 32 768 rows recompute it (armour_make_tables).
+    const int full_env = h->tune(ARMOUR_OPT_P1_FULL_PLANES);
+    const bool lean = !full_env;
+    // (round 4, one box, interleaved: configs[4] -- one problem, 90 000 rows, a 60 MB table -- 13.1 us with d recomputed against 15.8 stored;
+    //  configs[1] -- 14 000 rows, L2-resident -- 5.05 against 5.02: the launch that streams its table from beyond L2 wants the fewer bytes)
+    const int store_d = (B >= 8 || (long long)B * Q >= ARMOUR_RECOMPUTE_D_ROWS) ? 0 : 1;
+    if (lean) {
+        hipLaunchKernelGGL(armour_p1_plane_class_kernel, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
+        hipLaunchKernelGGL(armour_p1_plane_sample_kernel, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
+        hipLaunchKernelGGL(armour_p1_planes_kernel<true>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_pre, d_live, store_d);
+    } else {
+        hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, nullptr, nullptr, 1);
+    }
+    hipLaunchKernelGGL(armour_p1_skip_reduce_kernel, dim3(B), dim3(256), 0, h->stream, wk->d_skip_part, nbx * 4, h->d_plane_skip);
+    h->ll_shared = 1; h->d_from_center = 1;
+    h->planes_lean = lean ? 1 : 0; h->planes_have_d = (!lean || store_d) ? 1 : 0;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(wk->ev3, h->stream));
+    return ARMOUR_OK;
+}
+
+// ARMOUR_P1_TRACE, time-vectorised kernel: when each block's (last) item began and ended -- the spread between the groups
+static int report_tv_phases(const long long* d_phase, int blocks, int G, int rnea_items) {
+    std::vector<long long> ph((size_t)blocks * 8);
+    HIPCHK(hipMemcpy(ph.data(), d_phase, ph.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    std::vector<std::vector<long long>> byg((size_t)G), fw((size_t)G), bw((size_t)G);
+    for (int bl = 0; bl < blocks; bl++) {
+        const long long* r = &ph[(size_t)bl * 8];
+        if (!(r[5] > r[0] && r[0] > 0 && r[6] < (long long)rnea_items)) continue;
+        const size_t g2 = (size_t)(r[6] % G);
+        byg[g2].push_back(r[5] - r[0]);
+        if (r[3] > r[0] && r[4] > r[3]) { fw[g2].push_back(r[3] - r[0]); bw[g2].push_back(r[4] - r[3]); }
+    }
+    fprintf(stderr, "[P1 tv phases, cycles of a block's item by group of time steps, median / max]");
+    for (int g2 = 0; g2 < G; g2++) {
+        auto& d = byg[(size_t)g2];
+        if (d.empty()) continue;
+        std::sort(d.begin(), d.end());
+        fprintf(stderr, " group %d: %lld / %lld (%zu)", g2, d[d.size() / 2], d.back(), d.size());
+        auto& f = fw[(size_t)g2]; auto& bk = bw[(size_t)g2];
+        if (!f.empty()) { std::sort(f.begin(), f.end()); std::sort(bk.begin(), bk.end()); fprintf(stderr, " [JRS + forward %lld / %lld, backward %lld / %lld]", f[f.size() / 2], f.back(), bk[bk.size() / 2], bk.back()); }
+    }
+    fprintf(stderr, "\n");
+    return ARMOUR_OK;
+}
+
+// ---- Time-vectorised build (p1_tv.inc.h): one wave per (problem, group of <= 64 time steps), the symbolic work of an
+// operator done once per group.  Batches only: a single problem has two groups, i.e. two waves, and is faster step by step
+// (DESIGN.md 4.2).  *built stays false when the per-step kernel is to build the batch: any capacity flag, no shape that fits.
+static int build_time_vectorised(ArmourPlanner* h, P1Work* wk, int cus, float* total_ms, bool* built) {
+    const int B = h->B, T = h->T, J = h->J, n = h->n;
+    const bool armtd = h->no_torque();  // comparison mode, or ARMOUR without input constraints: forward kinematics only -- every item is a forward-kinematics item
+    const int G = (T + 63) / 64, LG = (T + G - 1) / G, groups = B * G;
+    // rows of 50 doubles when a group's time steps fit them (T = 100: two groups of 50), of 64 otherwise (the reference's T = 128): pz_tv.h, TV_GROW
+    static_assert(tv::GR == 64, "this unit holds the kernel with full-width rows");
+    const int tv_rows_env = h->tune(ARMOUR_OPT_P1_TV_ROW_WIDTH);   // (0 automatic | 50 | 64)
+    const int gr = (tv_rows_env == 64 || LG > kTvNarrowRows) ? 64 : kTvNarrowRows;
+    const int capTv = h->lim.work_monomials;
+    // Block shapes, in the order tried: (a) while there is at most one group per CU, three waves per group -- the roles of
+    // run_rnea run concurrently, as in the per-step kernel's small launches: the latency of ONE chain is what such a batch pays;
+    // (b) one wave per group with sort buffers of 4096 entries (the union raw-term counts seen are <= 2.4 k), several waves per
+    // CU, the forward kinematics of every group as a work item of its own while slots are free; (c) the same with 8192 entries.
+    // A product that overflows the sort buffers sends the launch to the next shape; any other flag to the per-step path.
+    const int tv_free_env = h->tune(ARMOUR_OPT_P1_TV_FREE);          // (0 = a barrier per joint)
+    const int tv_nw_env = h->tune(ARMOUR_OPT_P1_TV_WAVES);            // (0 automatic | 1 | 3 | 4 | 8)
+    const int tv_split_env = h->tune(ARMOUR_OPT_P1_TV_SPLIT_FK);      // (-1 automatic)
+    const int tv_ded_env = h->tune(ARMOUR_OPT_P1_TV_DEDICATED);       // (0 = no eight-wave blocks)
+    struct Shape { int nw, cap; };
+    // (8: four role waves + four dedicated helper waves, two waves per SIMD -- only in a build whose operators fit 256 registers)
+    const Shape shapes[5] = {{8, 4096}, {4, 4096}, {kRoles, 4096}, {1, 4096}, {1, 8192}};
+    TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices];
+    std::unique_lock<std::mutex> pool_lk(pool.mu);   // held until the last launch of this build has finished
+    // ARMOUR_OPT_P1_KEEP_WORK_MEMORY = 0: released at the end of the build -- on every way out: success, an error return, and when the build
+    // falls through to the per-step kernel (a cap below one block, a capacity flag): nothing of the time-vectorised build outlives it then.
+    struct PoolRelease {
+        TvArenaPool& p; bool keep;
+        ~PoolRelease() { if (p.ptr && !keep) { (void)hipFree(p.ptr); p.ptr = nullptr; p.bytes = 0; } }
+    } pool_release{pool, h->opt_p1_keep_work != 0};
+    if (pool.ptr && h->opt_p1_work_mb > 0 && pool.bytes > (size_t)(h->opt_p1_work_mb * 1048576.0)) {   // a kept arena larger than this handle's cap: give it back first
+        (void)hipFree(pool.ptr);
+        pool.ptr = nullptr; pool.bytes = 0;
+    }
+    for (int si = tv_nw_env > 0 ? 0 : std::min(h->p1_tv_shape_hint, 4); si < 5 && !*built; si++) {   // (a forced block shape searches from the beginning)
+        const int nw_launch = shapes[si].nw, cap = shapes[si].cap;
+        if (nw_launch == 8 && (!kTvDedicatedHelpers || !tv_ded_env || !tv_free_env)) continue;
+        const int nw = nw_launch == 8 ? 4 : nw_launch;   // the waves that play roles
+        const int nhelp = nw_launch == 8 ? 4 : 0;
+        const bool multi = nw > 1;   // (a): the roles of the RNEA on three waves, with four the forward kinematics on a wave of its own
+        // (multi-wave blocks also when there are more groups than CUs: the blocks loop over the groups.  Measured against one wave per group,
+        //  two or three groups per CU at a time -- B = 160: 18.1 against 23.1 ms, 256: 20.0 against 24.1, 384: 29.7 against 43.9, 512: 38.8 against
+        //  47.2 (profiles/r03_p1_breakeven.txt) -- the shared walks are what the one-wave shape lacks)
+        if (multi && (armtd || tv_nw_env == 1)) continue;
+        if (multi && tv_nw_env > 1 && tv_nw_env != nw_launch) continue;
+        if (!multi && tv_nw_env > 1 && si == 3) continue;
+        // (Until the return-address guard of pz_wave.h -- PZ_KEEP_RETURN_ADDRESS -- the ONE-WAVE blocks had to stay on the 64-double rows: their
+        //  kernel ended in a memory-aperture violation with narrower rows, in every launch.  tv::mul<3,3,3,3> -- whose staged-operand walks only the
+        //  one-wave blocks' large staging area reaches -- is 150 KB long in the narrow-row unit, the compiler relaxed two of its branches through
+        //  s[30:31] without saving the return address, and the function returned into its own middle: DESIGN.md 7, profiles/r05_tv_one_wave_narrow_rows.txt.)
+        const tvchain::TLayout TL = tvchain::make_tlayout(J, n, capTv, nw, nhelp, gr);
+        // blocks per CU by LDS; the staging area takes what is left
+        const size_t fixed = (nw == 4 ? 3 * tvchain::tv_lds_fixed(cap) + tvchain::tv_lds_fixed_fk() : (size_t)nw * tvchain::tv_lds_fixed(cap)) + tvchain::tv_lds_shared();
+        const int per_cu = multi ? 1 : std::max(1, std::min(4, (int)((size_t)160 * 1024 / (fixed + 24 * 1024))));
+        if (fixed + 512 * (multi ? 37 + 2 * (nw - 1) : 16) + 256 > (size_t)160 * 1024 / per_cu) continue;
+        const int stage_total = (int)(((size_t)160 * 1024 / per_cu - fixed - 256) / 512);
+        // several waves: wave 1 first gets the 37 rows a joint rotation needs, the rest is shared out evenly
+        const int stage_rows = !multi ? stage_total : std::min(stage_total - 2 * (nw - 1), std::max(stage_total / nw, 37));
+        const int stage_other = !multi ? 0 : (stage_total - stage_rows) / (nw - 1);
+        const size_t smem = tvchain::tv_lds_bytes(cap, stage_rows, stage_other, nw);
+        const int slots = std::min(512, cus * per_cu);
+        const bool split = armtd ? true : multi ? false : (tv_split_env >= 0 ? tv_split_env != 0 : 2 * groups <= slots);
+        const int fk_items = split ? groups : 0, rnea_items = armtd ? 0 : groups;
+        int blocks = std::min(rnea_items + fk_items, slots);
+        if (h->opt_p1_work_mb > 0) {   // ARMOUR_OPT_P1_WORK_MEMORY_MB: fewer blocks, looping over the groups
+            const double max_blocks = h->opt_p1_work_mb * 1048576.0 / (double)TL.total;
+            if (max_blocks < 1.0) continue;   // (not even one block of this shape: the next shape, in the end the per-step kernel)
+            blocks = (int)std::min((double)blocks, max_blocks);
+        }
+        // (not grow(): an arena the device cannot give ends the shape search -- the per-step kernel builds the batch -- instead of the build)
+        if ((size_t)blocks * TL.total > pool.bytes) {
+            if (pool.ptr) (void)hipFree(pool.ptr);
+            pool.ptr = nullptr; pool.bytes = 0;
+            if (hipMalloc((void**)&pool.ptr, (size_t)blocks * TL.total) != hipSuccess) { (void)hipGetLastError(); pool.ptr = nullptr; break; }
+            pool.bytes = (size_t)blocks * TL.total;
+        }
+        P1Cfg cf = p1_cfg_base(h, wk, cap);
+        cf.arena_bytes = TL.total; cf.arena = pool.ptr;
+        HIPCHK(hipMemsetAsync(wk->d_margin, 0, (size_t)B * sizeof(unsigned long long), h->stream));
+        cf.n_items = rnea_items; cf.fk_items = fk_items; cf.tv_groups = G; cf.tv_lanes = LG; cf.tv_cap = capTv; cf.tv_stage_rows = stage_rows; cf.tv_stage_rows_other = stage_other; cf.tv_free_running = tv_free_env;
+        cf.tv_walk_helpers = h->tune(ARMOUR_OPT_P1_TV_HELPERS);   // (0 = every walk on its own wave)
+        cf.tv_help_min = h->tune(ARMOUR_OPT_P1_TV_HELP_MIN); cf.tv_help_n = h->tune(ARMOUR_OPT_P1_TV_HELP_N); cf.tv_help_shift = h->tune(ARMOUR_OPT_P1_TV_HELP_SHIFT);
+        cf.tv_aux_on_fk_wave = h->tune(ARMOUR_OPT_P1_TV_AUX3);
+        cf.tail_cross = h->tune(ARMOUR_OPT_P1_TV_TAIL_CROSS);
+        if (armour_trace_p1() && blocks <= 1024) {   // when each block's (last) item began and ended: the spread between the groups
+            if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
+            HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
+            cf.phase_log = wk->d_phase;
+        }
+        unsigned st[ST_WORDS];
+        HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
+        HIPCHK(hipEventRecord(wk->ev0, h->stream));
+        {
+            std::lock_guard<std::mutex> lk(g_p1_launch_mu);
+            HIPCHK(gr == 64 ? armour_p1_tv_launch_g64(nw_launch, nw, blocks, smem, h->stream, &cf) : armour_p1_tv_launch_g50(nw_launch, nw, blocks, smem, h->stream, &cf));
+        }
+        HIPCHK(hipEventRecord(wk->ev1, h->stream));
+        HIPCHK(hipMemcpyAsync(st, wk->d_status, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(p1_wait_stream(h->stream));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
+        *total_ms += ms;
+        h->build_info[0] = ARMOUR_P1_KERNEL_TIME_VECTORISED; h->build_info[1] = nw_launch; h->build_info[2] = cap; h->build_info[3]++;
+        if (const int rc = cf.phase_log ? report_tv_phases(cf.phase_log, blocks, G, rnea_items) : ARMOUR_OK; rc != ARMOUR_OK) return rc;
+        if (armour_trace_p1()) fprintf(stderr, "[P1 tv] %d groups of <= %d steps%s, sort cap %d: %d blocks of %d wave(s) (%d per CU, %zu B LDS, %d / %d staging rows, %.1f MB arena each, rows of %d), %.2f ms, flags 0x%x, max raw terms %u, max monomials %u\n", groups, LG, fk_items ? " (+ as many forward-kinematics items)" : "", cap, blocks, nw_launch, per_cu, smem, stage_rows, stage_other, TL.total / 1048576.0, gr, ms, st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
+        if (st[ST_ERR] == 0) { *built = true; h->p1_tv_shape_hint = si; }
+        else if (!(st[ST_ERR] == (unsigned)ERR_RAW_OVERFLOW)) break;  // only the sort buffers can be helped by the next shape
+    }
+    return ARMOUR_OK;   // (pool_release: every launch above has been waited for)
+}
+
 int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     if (!h->p1) {
         P1Work* nw = new P1Work();
@@ -2009,6 +2388,7 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
 
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->device));
+    const int cus = prop.multiProcessorCount;
     if (h->p1_hint_B != B || h->p1_hint_T != T || h->p1_hint_O != O || ++h->p1_hint_builds >= 64) {
         h->p1_step_cap_hint = 0; h->p1_tv_shape_hint = 0; h->p1_hint_builds = 0;
         h->p1_hint_B = B; h->p1_hint_T = T; h->p1_hint_O = O;
@@ -2016,368 +2396,36 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     int cap_raw = 64;
     while (cap_raw < h->lim.raw_terms || cap_raw < h->p1_step_cap_hint) cap_raw <<= 1;   // (the hint: what the last build of this handle ended up with)
     if ((rc = grow(&wk->d_retry, &wk->retry_cap, (size_t)1 + (size_t)B * T)) != ARMOUR_OK) return rc;
-    const Layout L1 = make_layout(J, n, h->lim.work_monomials, 1), L3 = make_layout(J, n, h->lim.work_monomials, kRoles), L4 = make_layout(J, n, h->lim.work_monomials, 4);
+    const Layout L4 = make_layout(J, n, h->lim.work_monomials, 4);
     if (L4.idJS + L4.nJS > kMaxSlots) { armour_set_error("slot table too small"); return ARMOUR_EINVAL; }
-    auto ci_doubles = [&](const Layout& L) { return (size_t)L.nV * 9 + kNS * 3 + kNM * 27 + (size_t)L.nJM * 27 + (size_t)L.nJV * 9 + (size_t)L.nJS * 3; };
-    auto lds_bytes = [&](int cap, int nw = 1) {
-        return (size_t)(nw == 4 ? 3 : nw) * p1_wave_lds(key_cap(cap), cap) + (nw == 4 ? p1_wave_lds(kFkCapKey, kFkCapRaw) : 0) + p1_shared_lds(ci_doubles(nw == 1 ? L1 : nw == kRoles ? L3 : L4));
-    };
-    const int max_waves_env = std::min(h->tune(ARMOUR_OPT_P1_MAX_WAVES_PER_CU), 4 * P1_WAVES_PER_SIMD);
-    auto waves_per_cu = [&](int cap) { return std::max(1, std::min(max_waves_env, (int)((size_t)160 * 1024 / lds_bytes(cap)))); };
     float total_ms = 0;
     h->build_info[0] = h->build_info[1] = h->build_info[2] = h->build_info[3] = 0;
     unsigned st[ST_WORDS];
-    // one launch of the chain kernel over `n_items` work items (d_items == nullptr: all of them) with sort buffers of `cap`
-    // entries; with `collect` the items that overflow them are listed in wk->d_retry instead of failing the launch
-    // (`defer`: the launch is queued and NOT waited for -- the caller queues the half-space kernels and the read-back behind it, waits once and
-    //  calls launch_done(); the status words then come back through a page-locked block, a copy into pageable memory would wait by itself)
-    unsigned* st_pin = reinterpret_cast<unsigned*>(armour_handle_pinned(h, 9, 64));
+    unsigned* st_pin = reinterpret_cast<unsigned*>(armour_handle_pinned(h, 9, 64));   // (the status words of the per-step kernel come back through it)
     if (!st_pin) { armour_set_error("page-locked status block"); return ARMOUR_EDEVICE; }
-    std::function<int()> launch_done = [] { return ARMOUR_OK; };
-    auto launch = [&](int cap, const int* d_items, int n_items, bool collect, bool defer = false) -> int {
-        // few items (at most one per CU): three waves per item, the roles of a time step run concurrently (latency);
-        // otherwise one wave per item and as many items per CU as the LDS holds (throughput)
-        const int nw_env = h->tune(ARMOUR_OPT_P1_STEP_WAVES);   // (0: automatic)
-        const int cf_two_cu_env = h->tune(ARMOUR_OPT_P1_STEP_TWO_CU);
-        // (round 3) ... FOUR waves when the block's LDS holds the fourth wave's small sort buffers as well: the forward kinematics,
-        // the omega recursion and the constant cross products of the linear acceleration leave the three recursion waves for a wave
-        // of their own (run_rnea_free, the choreography of the time-vectorised kernel's four-wave blocks) and no item is issued twice
-        const int free_env0 = h->tune(ARMOUR_OPT_P1_STEP_FREE);
-        const bool fits4 = free_env0 && lds_bytes(cap, 4) <= (size_t)160 * 1024;
-        // Four-wave blocks take an item in 1.17 ms, one per CU at a time; one-wave blocks in 2.7 ms, waves_per_cu of them per CU.  With more
-        // items than CUs the blocks loop, and what decides is the number of rounds either shape needs (measured, B problems of 100 steps,
-        // four waves against one: B = 3..5 2.3-2.6 against 2.8-3.1 ms, 6..7 3.5-3.7 against 3.2-3.5, 8..10 4.4-4.8 against 5.2-5.7,
-        // 12 6.0 either way, 14..15 7.0 against 6.3: profiles/r03_p1_four_waves.txt; re-measured at the end of round 3 with both shapes faster:
-        // a round of four-wave items 1.0 ms, of one-wave items 2.6 ms -- B = 11 5.07 against 5.27, 16 7.16 against 7.70, 14 6.2 against 5.7)
-        const int cus = prop.multiProcessorCount;
-        const long long r4 = (n_items + cus - 1) / cus, r1 = (n_items + (long long)cus * waves_per_cu(cap) - 1) / ((long long)cus * waves_per_cu(cap));
-        const bool multi = h->no_torque() ? false  // forward kinematics only: a single role
-                           : nw_env ? nw_env >= 3
-                           : collect ? false
-                           : fits4 ? r4 <= 5 && 100 * r4 < 258 * r1   // (round 4, after the merge-path sorts and the item queue, B problems of 100 steps, four waves | one: 5: 2.22 | 2.66, 8: 3.73 | 3.76, 10: 4.03 | 4.46, 12: 4.83 | 4.94, 13: 5.63 | 5.04, 15: 5.90 | 5.28 -- from the sixth round on the one-wave blocks' throughput wins)
-                                   : (n_items <= cus && lds_bytes(cap, kRoles) <= (size_t)160 * 1024);
-        const bool four = multi && free_env0 && (nw_env ? nw_env == 4 : fits4);
-        const bool three = multi && !four;
-        const int nw = four ? 4 : three ? kRoles : 1;
-        const Layout& L = four ? L4 : three ? L3 : L1;
-        const size_t smem = lds_bytes(cap, nw);
-        if (smem > (size_t)160 * 1024) { armour_set_error("raw_terms=%d does not fit the 160 KiB LDS", cap); return ARMOUR_EINVAL; }
-        const int per_cu = multi ? 1 : waves_per_cu(cap);
-        // with at least as many idle CUs as items, the forward kinematics of every item runs as an item of its own
-        const int split_env = h->tune(ARMOUR_OPT_P1_STEP_SPLIT_FK);   // (-1: automatic)
-        const bool split = split_env >= 0 ? (split_env != 0 && multi) : (multi && n_items <= prop.multiProcessorCount);   // (round 4: also when the two kinds of items together are more than the blocks -- the blocks draw the RNEA items first and fill up with the forward kinematics: B = 2 1.095 -> 1.081 ms)
-        const int fk_items = split ? n_items : 0;
-        // A time step on two CUs (p1_free.inc.h): every item gets a helper block on a CU of its own, which also runs the item's forward kinematics.
-        // Block k builds item k, block helper0 + k helps it; helper0 a multiple of 8 puts the two on one XCD (checked on the device, item by item).
-        const int helper0 = (n_items + 7) & ~7;
-        const bool two_cu = four && split && !collect && !d_items && cf_two_cu_env && !h->p1_two_cu_off && h->mode == ARMOUR_MODE_ARMOUR && helper0 + n_items <= prop.multiProcessorCount * per_cu
-                            && h->tune(ARMOUR_OPT_P1_STEP_FREE) && h->tune(ARMOUR_OPT_P1_STEP_AUX3);   // (the choreography it changes is the free-running one with the w_aux recursion on the fourth wave)
-        const int waves = two_cu ? helper0 + n_items : std::min(n_items + fk_items, prop.multiProcessorCount * per_cu);
-        if ((size_t)waves * L.total > wk->arena_total) {
-            if (wk->arena) (void)hipFree(wk->arena);
-            wk->arena = nullptr;
-            HIPCHK(hipMalloc((void**)&wk->arena, (size_t)waves * L.total));
-            wk->arena_total = (size_t)waves * L.total;
-        }
-        P1Cfg cf;
-        memset(&cf, 0, sizeof(cf));
-        cf.B = B; cf.T = T; cf.J = J; cf.n = n; cf.O = O;
-        cf.capW = h->lim.work_monomials; cf.capRaw = cap; cf.capKey = key_cap(cap); cf.capL = h->lim.link_monomials; cf.capT = h->lim.torque_monomials;
-        cf.arena_bytes = L.total; cf.arena = wk->arena;
-        const int free_env = h->tune(ARMOUR_OPT_P1_STEP_FREE);   // (0 = a barrier per joint)
-        cf.free_running = free_env;
-        cf.rb = h->robot; cf.pr = h->params; cf.ub = h->ub;
-        cf.bez = h->d_bez;
-        cf.mode = h->mode; cf.fk_only = h->no_torque() ? 1 : 0; cf.jrs = h->d_jrs;
-        cf.link_count = h->d_link_count; cf.link_center = h->d_link_center; cf.link_indep = h->d_link_indep;
-        cf.link_keys = h->d_link_keys; cf.link_coeff = h->d_link_coeff;
-        cf.tq_count = h->d_tq_count; cf.tq_center = h->d_tq_center; cf.tq_indep = h->d_tq_indep;
-        cf.tq_keys = h->d_tq_keys; cf.tq_coeff = h->d_tq_coeff;
-        cf.link_gens = wk->d_link_gens; cf.torque_radius = wk->d_torque_radius; cf.status = wk->d_status;
-        cf.margin = wk->d_margin;
-        if (!d_items) HIPCHK(hipMemsetAsync(wk->d_margin, 0, (size_t)B * sizeof(unsigned long long), h->stream));   // (a launch over ALL items starts the margins afresh; the second pass over a few overflowed items adds to them)
-        cf.items = d_items; cf.n_items = n_items; cf.fk_items = fk_items;
-        const int aux3_env = h->tune(ARMOUR_OPT_P1_STEP_AUX3);
-        cf.tv_aux_on_fk_wave = aux3_env;   // (four-wave blocks: the w_aux recursion next to omega on the fourth wave)
-        cf.step_pairs = h->tune(ARMOUR_OPT_P1_STEP_PAIRS) == 2 || (h->tune(ARMOUR_OPT_P1_STEP_PAIRS) == 1 && n_items + fk_items <= waves);   // (1: with a block per item only -- after the merge-path sorts the pairs are worth 1 % to a lone problem and cost 2 % when the blocks loop: B = 4 1.95 against 1.99 ms, 8: 3.73 against 3.82; 2: always)
-        cf.queue_order = h->tune(ARMOUR_OPT_P1_STEP_QUEUE);
-        cf.queue = cf.queue_order != 0 && n_items + fk_items > waves ? wk->d_status + ST_WORDS + 60 : nullptr;   // (with a block per item there is nothing to draw: B = 1 1.044 against 1.069 ms.  The word: one of the status block that the profile counters of development builds do not reach)
-        if (cf.queue) HIPCHK(hipMemsetAsync(cf.queue, 0, sizeof(unsigned), h->stream));
-        cf.tail_cross = split ? h->tune(ARMOUR_OPT_P1_STEP_TAIL_CROSS) : 0;   // (with its forward kinematics to do the fourth wave has no time to spare)
-        cf.retry_list = collect ? wk->d_retry + 1 : nullptr; cf.retry_count = reinterpret_cast<unsigned*>(wk->d_retry);
-        int phase_blocks = 0;
-        if (armour_trace_p1() && nw == 4 && waves <= 1024) {
-            if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
-            HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
-            cf.phase_log = wk->d_phase; phase_blocks = waves;
-        }
-        cf.two_cu = two_cu ? cf_two_cu_env : 0; cf.helper0 = helper0;
-        cf.lean_back = h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 1; cf.late_jrs = (h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 2) == 0;   // (development: + 2 builds every joint before the roles begin)
-        if (two_cu) {
-            const size_t need = (size_t)n_items * kXchBytes;
-            bool clear = false;
-            if (need > wk->xch_cap) {
-                if (wk->d_xch) (void)hipFree(wk->d_xch);
-                wk->d_xch = nullptr; wk->xch_cap = 0;
-                HIPCHK(hipMalloc((void**)&wk->d_xch, need));
-                wk->xch_cap = need; clear = true;
-            }
-            if (++wk->xch_epoch >= (1 << 23)) { wk->xch_epoch = 1; clear = true; }
-            if (clear) HIPCHK(hipMemsetAsync(wk->d_xch, 0, wk->xch_cap, h->stream));
-            cf.xch = wk->d_xch; cf.xch_epoch = wk->xch_epoch;
-        }
-        HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
-        if (collect) HIPCHK(hipMemsetAsync(wk->d_retry, 0, sizeof(int), h->stream));
-        HIPCHK(hipEventRecord(wk->ev0, h->stream));
-        {
-            std::lock_guard<std::mutex> lk(g_p1_launch_mu);
-            if (four) HIPCHK(hipFuncSetAttribute((const void*)armour_p1_chain_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            else if (three) HIPCHK(hipFuncSetAttribute((const void*)armour_p1_chain_kernel<kRoles>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            else HIPCHK(hipFuncSetAttribute((const void*)armour_p1_chain_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            if (four) hipLaunchKernelGGL(armour_p1_chain_kernel<4>, dim3(waves), dim3(WAVE * 4), smem, h->stream, cf);
-            else if (three) hipLaunchKernelGGL(armour_p1_chain_kernel<kRoles>, dim3(waves), dim3(WAVE * kRoles), smem, h->stream, cf);
-            else hipLaunchKernelGGL(armour_p1_chain_kernel<1>, dim3(waves), dim3(WAVE), smem, h->stream, cf);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipEventRecord(wk->ev1, h->stream));
-        HIPCHK(hipMemcpyAsync(st_pin, wk->d_status, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-        armour_build_stamp("launch-queued");
-        launch_done = [&, cap, n_items, waves, nw, two_cu, per_cu, smem, helper0, phase_blocks]() -> int {
-        memcpy(st, st_pin, sizeof(st));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
-        total_ms += ms;
-        h->build_info[0] = ARMOUR_P1_KERNEL_PER_STEP; h->build_info[1] = nw; h->build_info[2] = cap; h->build_info[3]++;
-#ifdef P1_PROFILE
-        {
-            unsigned long long pr[PR_WORDS];
-            HIPCHK(hipMemcpy(pr, wk->d_status + ST_WORDS, sizeof(pr), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[P1 profile, wave 0] cycles: fill %llu sort %llu emit %llu abs_sum %llu total %llu | simplify calls %llu (N<=64: %llu) raw terms %llu\n",
-                    pr[PR_FILL], pr[PR_SORT], pr[PR_EMIT], pr[PR_ABS], pr[PR_TOTAL], pr[PR_CALLS], pr[PR_SMALL], pr[PR_TERMS]);
-            fprintf(stderr, "[P1 profile, wave 0] whole-call cycles: N<=64 %llu | 64<N<=512: %llu in %llu calls (%llu terms) | N>512: %llu in %llu calls (%llu terms)\n",
-                    pr[PR_CYC64], pr[PR_CYC512], pr[PR_N512], pr[PR_TERMS512], pr[PR_CYCBIG], pr[PR_NBIG], pr[PR_TERMSBIG]);
-        }
-#endif
-        if (armour_trace_p1() && nw == 4 && wk->d_phase && phase_blocks > 0) {   // where the blocks' time went (wave 0 of each): median / max over the main blocks, then over the helpers
-            std::vector<long long> ph((size_t)phase_blocks * 8);
-            HIPCHK(hipMemcpy(ph.data(), wk->d_phase, ph.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            const char* names[5] = {"JRS", "decision", "forward pass", "backward pass", "tables"};
-            for (int grp = 0; grp < (two_cu ? 2 : 1); grp++) {
-                const int b0 = grp == 0 ? 0 : helper0, b1 = grp == 0 ? n_items : helper0 + n_items;
-                fprintf(stderr, "[P1 phases, %s blocks, cycles median / max]", grp == 0 ? "main" : "helper");
-                for (int k = 0; k < 5; k++) {
-                    std::vector<long long> d;
-                    for (int bl = b0; bl < b1 && bl < phase_blocks; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[k + 1] > 0 && r[k] > 0) d.push_back(r[k + 1] - r[k]); }
-                    if (d.empty()) continue;
-                    std::sort(d.begin(), d.end());
-                    fprintf(stderr, " %s %lld / %lld", names[k], d[d.size() / 2], d.back());
-                }
-                std::vector<long long> tot;
-                long long first = 0, last = 0;
-                for (int bl = b0; bl < b1 && bl < phase_blocks; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[5] > 0) { tot.push_back(r[5] - r[0]); if (!first || r[0] < first) first = r[0]; if (r[5] > last) last = r[5]; } }
-                if (!tot.empty()) { std::sort(tot.begin(), tot.end()); fprintf(stderr, " | item %lld / %lld", tot[tot.size() / 2], tot.back()); }
-                int local = 0, xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int bl = b0; bl < b1 && bl < phase_blocks; bl++) { const long long* r = &ph[(size_t)bl * 8]; if (r[6] == 2) { local++; fprintf(stderr, " [block %d on XCD %lld: one CU]", bl, r[7]); } xcd[r[7] & 7]++; }
-                fprintf(stderr, " | %d of %d on their own; blocks per XCD %d %d %d %d %d %d %d %d\n", local, b1 - b0, xcd[0], xcd[1], xcd[2], xcd[3], xcd[4], xcd[5], xcd[6], xcd[7]);
-            }
-        }
-        if (armour_trace_p1()) fprintf(stderr, "[P1] %d items, cap_raw %d: %d blocks of %d wave(s)%s (%d per CU, %zu B LDS), %.2f ms, flags 0x%x, max raw terms %u, max monomials %u\n", n_items, cap, waves, nw, two_cu ? ", two CUs per item" : "", per_cu, smem, ms, st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
-        return ARMOUR_OK;
-        };
-        if (defer) return ARMOUR_OK;
-        HIPCHK(p1_wait_stream(h->stream));
-        armour_build_stamp("reach-set-kernel-waited");
-        return launch_done();
-    };
-    auto other_errors = [&]() -> int {
-        if (st[ST_ERR] & (unsigned)ERR_PAIR) {   // not a capacity limit: two waves that share an operator lost each other (psync), their barriers went off
-            armour_set_error("reach-set build: a pair of waves lost its barrier (flags 0x%x) -- an internal synchronisation error, not a capacity limit; "
-                             "ARMOUR_OPT_P1_STEP_PAIRS = 0 builds without paired waves", st[ST_ERR]);
-            return ARMOUR_EDEVICE;
-        }
-        if (st[ST_ERR] & ~(unsigned)ERR_RAW_OVERFLOW) {
-            armour_set_error("[dbg word3=%u] reach-set build overflow (flags 0x%x: 2=work_monomials, 4=link/torque_monomials, 8=link generators); max raw terms %u, max monomials %u",
-                             st[3], st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
-            return ARMOUR_ECAPACITY;
-        }
-        return ARMOUR_OK;
-    };
-    // Batches with more items than three waves per CU hold run a first pass with 2048-entry sort buffers -- 32 KB of LDS
-    // per wave, so FOUR waves per CU -- and list the few items that overflow them; those alone are rebuilt with the full
-    // buffers.  Small batches gain nothing from the fourth wave and go straight to the full buffers.
     if (h->no_torque()) {  // no torque tables in these modes: empty PZs, zero radius (RT/armour_main.cu:172-175: the radius stays zero)
         HIPCHK(hipMemsetAsync(h->d_tq_count, 0, (size_t)B * n * T * sizeof(int), h->stream));
         HIPCHK(hipMemsetAsync(wk->d_torque_radius, 0, (size_t)B * n * T * sizeof(double), h->stream));
     }
-    // ---- Time-vectorised build (p1_tv.inc.h): one wave per (problem, group of <= 64 time steps), the symbolic work of an
-    // operator done once per group.  Batches only: a single problem has two groups, i.e. two waves, and is faster step by step
-    // (DESIGN.md 4.2).  Any capacity flag sends the whole batch down the per-step path below.
+    const int kernel = h->opt_p1_build ? h->opt_p1_build : armour_p1_auto_kernel(B, T, h->tune(ARMOUR_OPT_P1_TV_MIN_GROUPS), h->no_torque());   // (ARMOUR_OPT_P1_BUILD, include/armour_hip.h: a handle can be held to one of the two kernels)
     bool built = false;
-    const int tv_min_groups = h->tune(ARMOUR_OPT_P1_TV_MIN_GROUPS);  // default 31: below this the per-step kernel is faster (re-measured at the end of round 4, B problems of 100 steps, per-step against time-vectorised: 14: 5.84 / 6.35 ms, 16: 7.49 / 6.64 -- the per-step kernel steps up with every 768 items -- 18: 8.04 / 6.66; round 3: 36, profiles/r03_p1_breakeven.txt)
-    const bool armtd = h->no_torque();  // comparison mode, or ARMOUR without input constraints: forward kinematics only -- every item is a forward-kinematics item
-    // (its chain is a fifth of the RNEA chain: the per-step kernel stays ahead up to B = 30 there)
-    // (the break-even is one of WORK: the per-step kernel's time grows with B * T, a chain's latency hardly depends on the lanes in
-    //  use -- 64 problems of 20 time steps are faster step by step -- so the threshold counts groups of 50 time steps' worth of items)
-    // (ARMOUR_OPT_P1_BUILD, include/armour_hip.h: a handle can be held to one of the two kernels)
-    const bool want_tv = h->opt_p1_build == 1 ? false : h->opt_p1_build == 2 ? true
-                         : (long long)B * T >= 50ll * (armtd ? tv_min_groups * 5 / 3 : tv_min_groups);   // (comparison mode: 60 groups -- 2.97 against 2.59 ms at B = 32, 2.40 against 2.57 at B = 28)
-    if (want_tv) {
-        const int G = (T + 63) / 64, LG = (T + G - 1) / G, groups = B * G;
-        // rows of 50 doubles when a group's time steps fit them (T = 100: two groups of 50), of 64 otherwise (the reference's T = 128): pz_tv.h, TV_GROW
-        static_assert(tv::GR == 64, "this unit holds the kernel with full-width rows");
-        const int tv_rows_env = h->tune(ARMOUR_OPT_P1_TV_ROW_WIDTH);   // (0 automatic | 50 | 64)
-        const int gr_multi = (tv_rows_env == 64 || LG > kTvNarrowRows) ? 64 : kTvNarrowRows;
-        const int capTv = h->lim.work_monomials;
-        // Block shapes, in the order tried: (a) while there is at most one group per CU, three waves per group -- the roles of
-        // run_rnea run concurrently, as in the per-step kernel's small launches: the latency of ONE chain is what such a batch pays;
-        // (b) one wave per group with sort buffers of 4096 entries (the union raw-term counts seen are <= 2.4 k), several waves per
-        // CU, the forward kinematics of every group as a work item of its own while slots are free; (c) the same with 8192 entries.
-        // A product that overflows the sort buffers sends the launch to the next shape; any other flag to the per-step path.
-        const int tv_free_env = h->tune(ARMOUR_OPT_P1_TV_FREE);          // (0 = a barrier per joint)
-        const int tv_nw_env = h->tune(ARMOUR_OPT_P1_TV_WAVES);            // (0 automatic | 1 | 3 | 4 | 8)
-        const int tv_split_env = h->tune(ARMOUR_OPT_P1_TV_SPLIT_FK);      // (-1 automatic)
-        const int tv_ded_env = h->tune(ARMOUR_OPT_P1_TV_DEDICATED);       // (0 = no eight-wave blocks)
-        const int tv_shift_env = h->tune(ARMOUR_OPT_P1_TV_HELP_SHIFT);
-        struct Shape { int nw, cap; };
-        // (8: four role waves + four dedicated helper waves, two waves per SIMD -- only in a build whose operators fit 256 registers)
-        const Shape shapes[5] = {{8, 4096}, {4, 4096}, {kRoles, 4096}, {1, 4096}, {1, 8192}};
-        TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices];
-        std::unique_lock<std::mutex> pool_lk(pool.mu);   // held until the last launch of this build has finished
-        // ARMOUR_OPT_P1_KEEP_WORK_MEMORY = 0: released at the end of the build -- on every way out: success, an error return, and when the build
-        // falls through to the per-step kernel (a cap below one block, a capacity flag): nothing of the time-vectorised build outlives it then.
-        struct PoolRelease {
-            TvArenaPool& p; bool keep;
-            ~PoolRelease() { if (p.ptr && !keep) { (void)hipFree(p.ptr); p.ptr = nullptr; p.bytes = 0; } }
-        } pool_release{pool, h->opt_p1_keep_work != 0};
-        if (pool.ptr && h->opt_p1_work_mb > 0 && pool.bytes > (size_t)(h->opt_p1_work_mb * 1048576.0)) {   // a kept arena larger than this handle's cap: give it back first
-            (void)hipFree(pool.ptr);
-            pool.ptr = nullptr; pool.bytes = 0;
-        }
-        for (int si = tv_nw_env > 0 ? 0 : std::min(h->p1_tv_shape_hint, 4); si < 5 && !built; si++) {   // (a forced block shape searches from the beginning)
-            const int nw_launch = shapes[si].nw, cap = shapes[si].cap;
-            if (nw_launch == 8 && (!kTvDedicatedHelpers || !tv_ded_env || !tv_free_env)) continue;
-            const int nw = nw_launch == 8 ? 4 : nw_launch;   // the waves that play roles
-            const int nhelp = nw_launch == 8 ? 4 : 0;
-            const bool multi = nw > 1;   // (a): the roles of the RNEA on three waves, with four the forward kinematics on a wave of its own
-            // (multi-wave blocks also when there are more groups than CUs: the blocks loop over the groups.  Measured against one wave per group,
-            //  two or three groups per CU at a time -- B = 160: 18.1 against 23.1 ms, 256: 20.0 against 24.1, 384: 29.7 against 43.9, 512: 38.8 against
-            //  47.2 (profiles/r03_p1_breakeven.txt) -- the shared walks are what the one-wave shape lacks)
-            if (multi && (armtd || tv_nw_env == 1)) continue;
-            if (multi && tv_nw_env > 1 && tv_nw_env != nw_launch) continue;
-            if (!multi && tv_nw_env > 1 && si == 3) continue;
-            // (Until the return-address guard of pz_wave.h -- PZ_KEEP_RETURN_ADDRESS -- the ONE-WAVE blocks had to stay on the 64-double rows: their
-            //  kernel ended in a memory-aperture violation with narrower rows, in every launch.  tv::mul<3,3,3,3> -- whose staged-operand walks only the
-            //  one-wave blocks' large staging area reaches -- is 150 KB long in the narrow-row unit, the compiler relaxed two of its branches through
-            //  s[30:31] without saving the return address, and the function returned into its own middle: DESIGN.md 7, profiles/r05_tv_one_wave_narrow_rows.txt.)
-            const int gr = gr_multi;
-            const tvchain::TLayout TL = tvchain::make_tlayout(J, n, capTv, nw, nhelp, gr);
-            // blocks per CU by LDS; the staging area takes what is left
-            const size_t fixed = (nw == 4 ? 3 * tvchain::tv_lds_fixed(cap) + tvchain::tv_lds_fixed_fk() : (size_t)nw * tvchain::tv_lds_fixed(cap)) + tvchain::tv_lds_shared();
-            const int per_cu = multi ? 1 : std::max(1, std::min(4, (int)((size_t)160 * 1024 / (fixed + 24 * 1024))));
-            if (fixed + 512 * (multi ? 37 + 2 * (nw - 1) : 16) + 256 > (size_t)160 * 1024 / per_cu) continue;
-            const int stage_total = (int)(((size_t)160 * 1024 / per_cu - fixed - 256) / 512);
-            // several waves: wave 1 first gets the 37 rows a joint rotation needs, the rest is shared out evenly
-            const int stage_rows = !multi ? stage_total : std::min(stage_total - 2 * (nw - 1), std::max(stage_total / nw, 37));
-            const int stage_other = !multi ? 0 : (stage_total - stage_rows) / (nw - 1);
-            const size_t smem = tvchain::tv_lds_bytes(cap, stage_rows, stage_other, nw);
-            const int slots = std::min(512, prop.multiProcessorCount * per_cu);
-            const bool split = armtd ? true : multi ? false : (tv_split_env >= 0 ? tv_split_env != 0 : 2 * groups <= slots);
-            const int fk_items = split ? groups : 0, rnea_items = armtd ? 0 : groups;
-            int blocks = std::min(rnea_items + fk_items, slots);
-            if (h->opt_p1_work_mb > 0) {   // ARMOUR_OPT_P1_WORK_MEMORY_MB: fewer blocks, looping over the groups
-                const double max_blocks = h->opt_p1_work_mb * 1048576.0 / (double)TL.total;
-                if (max_blocks < 1.0) continue;   // (not even one block of this shape: the next shape, in the end the per-step kernel)
-                blocks = (int)std::min((double)blocks, max_blocks);
-            }
-            if ((size_t)blocks * TL.total > pool.bytes) {
-                if (pool.ptr) (void)hipFree(pool.ptr);
-                pool.ptr = nullptr; pool.bytes = 0;
-                if (hipMalloc((void**)&pool.ptr, (size_t)blocks * TL.total) != hipSuccess) { (void)hipGetLastError(); pool.ptr = nullptr; break; }
-                pool.bytes = (size_t)blocks * TL.total;
-            }
-            P1Cfg cf;
-            memset(&cf, 0, sizeof(cf));
-            cf.B = B; cf.T = T; cf.J = J; cf.n = n; cf.O = O;
-            cf.capW = capTv; cf.capRaw = cap; cf.capKey = key_cap(cap); cf.capL = h->lim.link_monomials; cf.capT = h->lim.torque_monomials;
-            cf.arena_bytes = TL.total; cf.arena = pool.ptr;
-            cf.rb = h->robot; cf.pr = h->params; cf.ub = h->ub;
-            cf.bez = h->d_bez;
-            cf.mode = h->mode; cf.fk_only = h->no_torque() ? 1 : 0; cf.jrs = h->d_jrs;
-            cf.link_count = h->d_link_count; cf.link_center = h->d_link_center; cf.link_indep = h->d_link_indep;
-            cf.link_keys = h->d_link_keys; cf.link_coeff = h->d_link_coeff;
-            cf.tq_count = h->d_tq_count; cf.tq_center = h->d_tq_center; cf.tq_indep = h->d_tq_indep;
-            cf.tq_keys = h->d_tq_keys; cf.tq_coeff = h->d_tq_coeff;
-            cf.link_gens = wk->d_link_gens; cf.torque_radius = wk->d_torque_radius; cf.status = wk->d_status;
-            cf.margin = wk->d_margin;
-            HIPCHK(hipMemsetAsync(wk->d_margin, 0, (size_t)B * sizeof(unsigned long long), h->stream));
-            cf.n_items = rnea_items; cf.fk_items = fk_items; cf.tv_groups = G; cf.tv_lanes = LG; cf.tv_cap = capTv; cf.tv_stage_rows = stage_rows; cf.tv_stage_rows_other = stage_other; cf.tv_free_running = tv_free_env;
-            const int tv_help_env = h->tune(ARMOUR_OPT_P1_TV_HELPERS);   // (0 = every walk on its own wave)
-            cf.tv_walk_helpers = tv_help_env;
-            const int tv_help_min_env = h->tune(ARMOUR_OPT_P1_TV_HELP_MIN);
-            const int tv_help_n_env = h->tune(ARMOUR_OPT_P1_TV_HELP_N);
-            cf.tv_help_min = tv_help_min_env; cf.tv_help_n = tv_help_n_env; cf.tv_help_shift = tv_shift_env;
-            const int tv_aux3_env = h->tune(ARMOUR_OPT_P1_TV_AUX3);
-            cf.tv_aux_on_fk_wave = tv_aux3_env;
-            cf.tail_cross = h->tune(ARMOUR_OPT_P1_TV_TAIL_CROSS);
-            if (armour_trace_p1() && blocks <= 1024) {   // when each block's (last) item began and ended: the spread between the groups
-                if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
-                HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
-                cf.phase_log = wk->d_phase;
-            }
-            HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
-            HIPCHK(hipEventRecord(wk->ev0, h->stream));
-            {
-                std::lock_guard<std::mutex> lk(g_p1_launch_mu);
-                HIPCHK(gr == 64 ? armour_p1_tv_launch_g64(nw_launch, nw, blocks, smem, h->stream, &cf) : armour_p1_tv_launch_g50(nw_launch, nw, blocks, smem, h->stream, &cf));
-            }
-            HIPCHK(hipEventRecord(wk->ev1, h->stream));
-            HIPCHK(hipMemcpyAsync(st, wk->d_status, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(p1_wait_stream(h->stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
-            total_ms += ms;
-            h->build_info[0] = ARMOUR_P1_KERNEL_TIME_VECTORISED; h->build_info[1] = nw_launch; h->build_info[2] = cap; h->build_info[3]++;
-            if (cf.phase_log) {
-                std::vector<long long> ph((size_t)blocks * 8);
-                HIPCHK(hipMemcpy(ph.data(), cf.phase_log, ph.size() * sizeof(long long), hipMemcpyDeviceToHost));
-                std::vector<std::vector<long long>> byg((size_t)G);
-                std::vector<std::vector<long long>> fw((size_t)G), bw((size_t)G);
-                for (int bl = 0; bl < blocks; bl++) {
-                    const long long* r = &ph[(size_t)bl * 8];
-                    if (!(r[5] > r[0] && r[0] > 0 && r[6] < (long long)rnea_items)) continue;
-                    const size_t g2 = (size_t)(r[6] % G);
-                    byg[g2].push_back(r[5] - r[0]);
-                    if (r[3] > r[0] && r[4] > r[3]) { fw[g2].push_back(r[3] - r[0]); bw[g2].push_back(r[4] - r[3]); }
-                }
-                fprintf(stderr, "[P1 tv phases, cycles of a block's item by group of time steps, median / max]");
-                for (int g2 = 0; g2 < G; g2++) {
-                    auto& d = byg[(size_t)g2];
-                    if (d.empty()) continue;
-                    std::sort(d.begin(), d.end());
-                    fprintf(stderr, " group %d: %lld / %lld (%zu)", g2, d[d.size() / 2], d.back(), d.size());
-                    auto& f = fw[(size_t)g2]; auto& bk = bw[(size_t)g2];
-                    if (!f.empty()) { std::sort(f.begin(), f.end()); std::sort(bk.begin(), bk.end()); fprintf(stderr, " [JRS + forward %lld / %lld, backward %lld / %lld]", f[f.size() / 2], f.back(), bk[bk.size() / 2], bk.back()); }
-                }
-                fprintf(stderr, "\n");
-            }
-            if (armour_trace_p1()) fprintf(stderr, "[P1 tv] %d groups of <= %d steps%s, sort cap %d: %d blocks of %d wave(s) (%d per CU, %zu B LDS, %d / %d staging rows, %.1f MB arena each, rows of %d), %.2f ms, flags 0x%x, max raw terms %u, max monomials %u\n", groups, LG, fk_items ? " (+ as many forward-kinematics items)" : "", cap, blocks, nw_launch, per_cu, smem, stage_rows, stage_other, TL.total / 1048576.0, gr, ms, st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
-            if (st[ST_ERR] == 0) { built = true; h->p1_tv_shape_hint = si; }
-            else if (!(st[ST_ERR] == (unsigned)ERR_RAW_OVERFLOW)) break;  // only the sort buffers can be helped by the next shape
-        }
-        // (pool_release, at the end of this scope: every launch above has been waited for)
-    }
+    if (kernel == ARMOUR_P1_KERNEL_TIME_VECTORISED && (rc = build_time_vectorised(h, wk, cus, &total_ms, &built)) != ARMOUR_OK) return rc;
+    // Batches with more items than three waves per CU hold run a first pass with 2048-entry sort buffers -- 32 KB of LDS
+    // per wave, so FOUR waves per CU -- and list the few items that overflow them; those alone are rebuilt with the full
+    // buffers.  Small batches gain nothing from the fourth wave and go straight to the full buffers.
     const int kFirstPassCap = 2048;
     const int* d_items = nullptr;
     int n_items = built ? 0 : B * T;
+    StepPlan plan{};
     // (the second pass costs at least one item's latency, ~4 ms: worth it from about 16 items per CU)
     const int two_pass_env = h->tune(ARMOUR_OPT_P1_TWO_PASS);
-    if (!built && two_pass_env && cap_raw > kFirstPassCap && waves_per_cu(kFirstPassCap) > waves_per_cu(cap_raw) && B * T >= 16 * prop.multiProcessorCount) {
-        if ((rc = launch(kFirstPassCap, nullptr, B * T, true)) != ARMOUR_OK) return rc;
-        if ((rc = other_errors()) != ARMOUR_OK) return rc;
-        int nretry = 0;
-        HIPCHK(hipMemcpy(&nretry, wk->d_retry, sizeof(int), hipMemcpyDeviceToHost));
+    if (!built && two_pass_env && cap_raw > kFirstPassCap && step_waves_per_cu(h, kFirstPassCap) > step_waves_per_cu(h, cap_raw) && B * T >= 16 * cus) {
+        if ((rc = plan_step_launch(h, cus, kFirstPassCap, nullptr, B * T, true, &plan)) != ARMOUR_OK || (rc = queue_step_launch(h, wk, plan, st_pin)) != ARMOUR_OK) return rc;
+        HIPCHK(p1_wait_stream(h->stream));
+        armour_build_stamp("reach-set-kernel-waited");
+        if ((rc = finish_step_launch(h, wk, plan, st_pin, st, &total_ms)) != ARMOUR_OK || (rc = p1_status_error(st)) != ARMOUR_OK) return rc;
+        HIPCHK(hipMemcpy(&n_items, wk->d_retry, sizeof(int), hipMemcpyDeviceToHost));
         d_items = wk->d_retry + 1;
-        n_items = nretry;
     }
     // The per-step kernel is queued and NOT waited for: the half-space kernels, the bounds kernel and the read-back of everything the host keeps go
     // into the stream behind it, and ONE wait ends the build (round 6: the wait for the kernel's status words in between cost the launch latency
@@ -2387,93 +2435,37 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     const size_t off_lg = n_tr * sizeof(double), off_lc = off_lg + n_lg * sizeof(double), off_tc = off_lc + n_lc * sizeof(int),
                  off_ps = (off_tc + n_tc * sizeof(int) + 7) & ~(size_t)7, off_mg = off_ps + (size_t)B * sizeof(unsigned long long), rb_bytes = off_mg + (size_t)B * sizeof(unsigned long long);
     unsigned char* rb = rb_bytes <= ((size_t)4 << 20) ? reinterpret_cast<unsigned char*>(armour_handle_pinned(h, 8, rb_bytes)) : nullptr;
-    for (;;) {
-    const bool chain = n_items > 0;
-    if (chain && (rc = launch(cap_raw, d_items, n_items, false, true)) != ARMOUR_OK) return rc;
-    if (O > 0) {
-        const int Q = J * T * O;
-        HIPCHK(hipEventRecord(wk->ev2, h->stream));
-        const int nbx = (Q + 63) / 64, nbc = (Q + 255) / 256;
-        // [B][nbx][4] per-wave masks of the planes kernel | [B][nbc] per-block masks of the class pre-pass | [B] its result | [B] planes a sampled row needs
-        const size_t part_words = (size_t)B * nbx * 4, pre_words = (size_t)B * nbc;
-        if (part_words + pre_words + 2 * (size_t)B > wk->skip_part_cap) {
-            if (wk->d_skip_part) (void)hipFree(wk->d_skip_part);
-            wk->d_skip_part = nullptr; wk->skip_part_cap = 0;
-            HIPCHK(hipMalloc((void**)&wk->d_skip_part, (part_words + pre_words + 2 * (size_t)B) * sizeof(unsigned long long)));
-            wk->skip_part_cap = part_words + pre_words + 2 * (size_t)B;
+    for (bool again = true; again;) {   // again: step_pass_verdict
+        const bool chain = n_items > 0;
+        if (chain && ((rc = plan_step_launch(h, cus, cap_raw, d_items, n_items, false, &plan)) != ARMOUR_OK || (rc = queue_step_launch(h, wk, plan, st_pin)) != ARMOUR_OK)) return rc;
+        if (O > 0 && (rc = queue_planes(h, wk)) != ARMOUR_OK) return rc;
+        // the constraint bounds of this problem set (torque limits -+ the radii just built, collision and joint-limit constants: RT/NLPclass.cu:87-165),
+        // filled on the device behind the build's kernels: the first armour_solve / armour_eval_violations of the set finds them there
+        if (h->d_bounds && (rc = armour_bounds_launch(h, wk->d_torque_radius)) != ARMOUR_OK) return rc;
+        // What the host keeps of a build -- torque radii, link generators, the monomial counts behind the table statistics, the plane masks -- comes
+        // back through ONE page-locked block, queued behind the half-space kernels and waited for once (five blocking copies from pageable memory
+        // and a wait of their own before: 0.1 ms of a lone problem's 1.2 ms call).  Large batches keep the plain copies.
+        if (rb) {
+            HIPCHK(hipMemcpyAsync(rb, wk->d_torque_radius, n_tr * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(rb + off_lg, wk->d_link_gens, n_lg * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(rb + off_lc, h->d_link_count, n_lc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(rb + off_tc, h->d_tq_count, n_tc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            if (O > 0) HIPCHK(hipMemcpyAsync(rb + off_ps, h->d_plane_skip, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(rb + off_mg, wk->d_margin, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         }
-        unsigned long long* d_pre_part = wk->d_skip_part + part_words;
-        unsigned long long* d_pre = d_pre_part + pre_words;
-        unsigned long long* d_live = d_pre + B;
-        // The table holds what the fused evaluation reads and nothing else (planes_of_group): ARMOUR_OPT_P1_FULL_PLANES = 1 builds
-        // the full one.  d = A.c is stored for the small launches that read it; batches of >= 8 problems or >= 32 768 rows recompute it (armour_make_tables).
-        const int full_env = h->tune(ARMOUR_OPT_P1_FULL_PLANES);
-        const bool lean = !full_env;
-        // (round 4, one box, interleaved: configs[4] -- one problem, 90 000 rows, a 60 MB table -- 13.1 us with d recomputed against 15.8 stored;
-        //  configs[1] -- 14 000 rows, L2-resident -- 5.05 against 5.02: the launch that streams its table from beyond L2 wants the fewer bytes)
-        const int store_d = (B >= 8 || (long long)B * Q >= ARMOUR_RECOMPUTE_D_ROWS) ? 0 : 1;
-        if (lean) {
-            hipLaunchKernelGGL(armour_p1_plane_class_kernel, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
-            hipLaunchKernelGGL(armour_p1_plane_sample_kernel, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
-            hipLaunchKernelGGL(armour_p1_planes_kernel<true>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
-                               wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_pre, d_live, store_d);
-        } else {
-            hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
-                               wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, nullptr, nullptr, 1);
+        // (unconditional: the bounds kernel above and the blocking copies below are ordered against h->stream -- a non-blocking stream -- by this
+        //  wait alone; with O == 0 and a batch beyond the page-locked block it used to be skipped: ADVICE r5)
+        armour_build_stamp("planes+bounds+readback-queued");
+        HIPCHK(p1_wait_stream(h->stream));
+        armour_build_stamp("planes-waited");
+        again = false;
+        if (chain && ((rc = finish_step_launch(h, wk, plan, st_pin, st, &total_ms)) != ARMOUR_OK || (rc = step_pass_verdict(h, st, &cap_raw, &again)) != ARMOUR_OK)) return rc;
+        if (!again && O > 0) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, wk->ev2, wk->ev3));
+            total_ms += ms;
+            h->planes_ms = ms;
         }
-        hipLaunchKernelGGL(armour_p1_skip_reduce_kernel, dim3(B), dim3(256), 0, h->stream, wk->d_skip_part, nbx * 4, h->d_plane_skip);
-        h->ll_shared = 1; h->d_from_center = 1;
-        h->planes_lean = lean ? 1 : 0; h->planes_have_d = (!lean || store_d) ? 1 : 0;
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(wk->ev3, h->stream));
-    }
-    // the constraint bounds of this problem set (torque limits -+ the radii just built, collision and joint-limit constants: RT/NLPclass.cu:87-165),
-    // filled on the device behind the build's kernels: the first armour_solve / armour_eval_violations of the set finds them there
-    if (h->d_bounds) { const int rcb = armour_bounds_launch(h, wk->d_torque_radius); if (rcb != ARMOUR_OK) return rcb; }
-    // What the host keeps of a build -- torque radii, link generators, the monomial counts behind the table statistics, the plane masks -- comes
-    // back through ONE page-locked block, queued behind the half-space kernels and waited for once (five blocking copies from pageable memory
-    // and a wait of their own before: 0.1 ms of a lone problem's 1.2 ms call).  Large batches keep the plain copies.
-    if (rb) {
-        HIPCHK(hipMemcpyAsync(rb, wk->d_torque_radius, n_tr * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(rb + off_lg, wk->d_link_gens, n_lg * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(rb + off_lc, h->d_link_count, n_lc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(rb + off_tc, h->d_tq_count, n_tc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (O > 0) HIPCHK(hipMemcpyAsync(rb + off_ps, h->d_plane_skip, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(rb + off_mg, wk->d_margin, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    }
-    // (unconditional: the bounds kernel above and the blocking copies below are ordered against h->stream -- a non-blocking stream -- by this
-    //  wait alone; with O == 0 and a batch beyond the page-locked block it used to be skipped: ADVICE r5)
-    armour_build_stamp("planes+bounds+readback-queued");
-    HIPCHK(p1_wait_stream(h->stream));
-    armour_build_stamp("planes-waited");
-    if (chain) {
-        if ((rc = launch_done()) != ARMOUR_OK) return rc;
-        if ((st[ST_ERR] & (unsigned)ERR_HELPER) && !h->p1_two_cu_off) {   // a time step on two CUs lost its helper: again on one CU per step, and this handle stays there
-            if (armour_trace_p1()) fprintf(stderr, "[P1] a helper block's results did not arrive (flags 0x%x): building again on one CU per time step\n", st[ST_ERR]);
-            h->p1_two_cu_off = true;
-            h->tuning[ARMOUR_OPT_P1_STEP_TWO_CU - ARMOUR_OPT_FIRST_TUNING] = 0;   // (armour_get_option shows it; armour_set_option switches it on again)
-            continue;
-        }
-        if (st[ST_ERR] & (unsigned)ERR_HELPER_LATE) {   // good tables, built late: some main block waited 1.5 ms for a helper that had not started (a shared device, fewer CUs than reported)
-            if (armour_trace_p1()) fprintf(stderr, "[P1] a helper block started too late for its item (flags 0x%x): one CU per time step from the next build on\n", st[ST_ERR]);
-            h->p1_two_cu_off = true;
-            h->tuning[ARMOUR_OPT_P1_STEP_TWO_CU - ARMOUR_OPT_FIRST_TUNING] = 0;
-            st[ST_ERR] &= ~(unsigned)ERR_HELPER_LATE;
-        }
-        if (st[ST_ERR] & ERR_RAW_OVERFLOW) {
-            if (cap_raw < 16384) { cap_raw <<= 1; h->p1_step_cap_hint = cap_raw; continue; }  // retry with larger LDS sort buffers (and start there next time)
-            armour_set_error("a PZ product produced more than %d raw terms (raise ArmourLimits.raw_terms)", cap_raw);
-            return ARMOUR_ECAPACITY;
-        }
-        if ((rc = other_errors()) != ARMOUR_OK) return rc;
-    }
-    if (O > 0) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, wk->ev2, wk->ev3));
-        total_ms += ms;
-        h->planes_ms = ms;
-    }
-    break;
     }
     h->build_ms = total_ms;  // device time of every launch of this build, retries included
 
