@@ -503,26 +503,11 @@ struct Chain {
         mul<1, 1, 1, 1>(w, o, a, b);
         return o;
     }
-    __device__ PZ crossComp(const PZ& a, int a1, int a2, const PZ& b, int b1, int b2) {  // a[a1]*b[b1] - a[a2]*b[b2]
-        PZ t1 = mulSS(elem(w, a, a1), elem(w, b, b1));
-        PZ t2 = mulSS(elem(w, a, a2), elem(w, b, b2));
-        PZ r = comb2(view(w, t1), 1.0, view(w, t2), -1.0);
-        freeSs(t1); freeSs(t2);
-        return r;
-    }
     __device__ PZ crossPzPz(const PZ& a, const PZ& b) {  // RT/PZsparse.cu:1134-1151
-#ifdef P1_COMPOSED_CROSS  // the reference's composition out of 1x1 operators (10 passes); kept for A/B runs
-        PZ r0 = crossComp(a, 1, 2, b, 2, 1);
-        PZ r1 = crossComp(a, 2, 0, b, 0, 2);
-        PZ r2 = crossComp(a, 0, 1, b, 1, 0);
-        PZ o = stack(r0, r1, r2);
-        freeSs(r0); freeSs(r1); freeSs(r2);
-        return o;
-#else
+        // The reference composes it out of 1x1 operators (10 passes; that form is a build switch in p1_reach.hip at commit e68a297).
         PZ o = allocV();
         cross_pzpz(w, o, view(w, a), view(w, b));  // the same three simplify() stages in one pass (pz_wave.h)
         return o;
-#endif
     }
     __device__ PZ mulMV(const PZ& A, const PZ& v) {
         PZ o = allocV();

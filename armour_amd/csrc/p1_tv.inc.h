@@ -696,12 +696,7 @@ __global__ __launch_bounds__(64 * NW) P1_TV_OCC void armour_p1_tv_kernel(P1Cfg c
         // place in a row is its own while the rows have one for it, the shadowed lane's otherwise (the same value to the same address, from two
         // lanes; shadowing the LAST step put fifteen lanes on one address: B = 24 6.65 -> 6.84 ms) (pz_tv.h)
         const int sl = lane % nl;
-#ifdef TV_FORCE_ROW_PLACES   // development: lanes beyond this share the shadowed lane's place although the rows are wider
-        constexpr int kRowPlaces = TV_FORCE_ROW_PLACES;
-#else
-        constexpr int kRowPlaces = tv::GR;
-#endif
-        c.w.active = true; c.w.live = lane < nl; c.w.rl = lane < kRowPlaces ? lane : sl;
+        c.w.active = true; c.w.live = lane < nl; c.w.rl = lane < tv::GR ? lane : sl;
         const int t_lane = t0 + sl;
         c.w.w.mabs = __builtin_inf();   // this item's prune margin (pz_tv.h mtrk; reduced over the lanes -- the group's time steps -- below)
         if constexpr (NW == 8) {
@@ -720,7 +715,7 @@ __global__ __launch_bounds__(64 * NW) P1_TV_OCC void armour_p1_tv_kernel(P1Cfg c
         if (cf.phase_log != nullptr && threadIdx.x == 0) { cf.phase_log[(size_t)blockIdx.x * 8 + 0] = clock64(); cf.phase_log[(size_t)blockIdx.x * 8 + 6] = it; }   // (ARMOUR_P1_TRACE: when this block's item began and ended)
 #ifdef TV_PROFILE
         const long long tvp_start = clock64();
-        c.w.c_wait = c.w.c_sort = c.w.c_walk = c.w.c_cc = c.w.n_raw = c.w.n_calls = c.w.n_emit = 0;
+        c.w.c_wait = c.w.c_sort = c.w.c_walk = c.w.n_raw = c.w.n_calls = c.w.n_emit = 0;
         c.w.c_hwait = c.w.n_shared = c.w.n_shared_terms = 0;
         for (int q = 0; q < 8; q++) { c.w.c_fn[q] = 0; c.w.n_fn[q] = 0; }
         for (int q = 0; q < 3; q++) { c.w.c_type[q] = 0; c.w.n_type[q] = 0; }
@@ -759,13 +754,10 @@ __global__ __launch_bounds__(64 * NW) P1_TV_OCC void armour_p1_tv_kernel(P1Cfg c
         if constexpr (NW == 8) tv::hj_post_ctl(c.w, tv::HK_EXIT);
 #ifdef TV_PROFILE
         if (lane == 0 && blockIdx.x == 0) printf("[tv item %d wave %d] walks by type: mul %lld cycles / %lld raw, cross %lld / %lld, sums %lld / %lld\n", it, c.wid, c.w.c_type[0], c.w.n_type[0], c.w.c_type[1], c.w.n_type[1], c.w.c_type[2], c.w.n_type[2]);
-#ifdef TV_PROFILE_FULL
-        if (threadIdx.x == 0 && blockIdx.x == 0) printf("[tv item %d] walk: load phase %lld, wait for the loads %lld, process phase %lld, chunk prologue %lld cycles, %lld batches, %lld terms\n", it, tv::g_tvprof[0], tv::g_tvprof[4], tv::g_tvprof[1], tv::g_tvprof[2], tv::g_tvprof[3], tv::g_tvprof[5]);
-#endif
         if (lane == 0 && blockIdx.x == 0) printf("[tv item %d wave %d] whole calls (cycles / calls): sorted product %lld / %lld, constant-left product %lld / %lld, cross %lld / %lld, sums %lld / %lld, constant cross %lld / %lld, helper service %lld / %lld, set+transpose %lld / %lld, link tables %lld / %lld\n", it, c.wid,
                                                  c.w.c_fn[0], c.w.n_fn[0], c.w.c_fn[1], c.w.n_fn[1], c.w.c_fn[2], c.w.n_fn[2], c.w.c_fn[3], c.w.n_fn[3], c.w.c_fn[4], c.w.n_fn[4], c.w.c_fn[5], c.w.n_fn[5], c.w.c_fn[6], c.w.n_fn[6], c.w.c_fn[7], c.w.n_fn[7]);
         if (lane == 0 && blockIdx.x == 0) printf("[tv item %d wave %d] shared walks: %lld jobs, %lld raw terms; waited %lld cycles on the helper channel\n", it, c.wid, c.w.n_shared, c.w.n_shared_terms, c.w.c_hwait);
-        if (lane == 0 && blockIdx.x == 0) printf("[tv item %d wave %d] total %lld cycles (waited %lld, %lld of it in the forward pass; forward done at %lld): sort %lld walk %lld cross_const %lld | %lld sorted operator calls, %lld raw terms, %lld emitted\n", it, c.wid, (long long)clock64() - tvp_start, c.w.c_wait, c.w.c_wait_fwd, c.w.c_fwd - tvp_start, c.w.c_sort, c.w.c_walk, c.w.c_cc, c.w.n_calls, c.w.n_raw, c.w.n_emit);
+        if (lane == 0 && blockIdx.x == 0) printf("[tv item %d wave %d] total %lld cycles (waited %lld, %lld of it in the forward pass; forward done at %lld): sort %lld walk %lld | %lld sorted operator calls, %lld raw terms, %lld emitted\n", it, c.wid, (long long)clock64() - tvp_start, c.w.c_wait, c.w.c_wait_fwd, c.w.c_fwd - tvp_start, c.w.c_sort, c.w.c_walk, c.w.n_calls, c.w.n_raw, c.w.n_emit);
 #endif
     }
 #ifdef TV_PROFILE

@@ -22,12 +22,9 @@
 #define P2_SL (3 * (1 + ARMOUR_MAX_FACTORS))   // doubles of one sliced link monomial / one sliced link PZ: x[3], dx[ARMOUR_MAX_FACTORS][3] (24; 27 in the 8-factor build)
 #define P2_TQW (1 + ARMOUR_MAX_FACTORS)        // doubles of one sliced torque monomial: value and ARMOUR_MAX_FACTORS partials (8; 9)
 
-#ifndef P2_DFC_WAVES
-#define P2_DFC_WAVES 3
-#endif
 // batched one-point launches (DFC) are occupancy-bound: hold the kernel to the 168 VGPRs of 3 waves per SIMD (4 was measured:
 // 128 VGPRs + 120 B/lane of scratch, twice as slow)
-#define P2_WPE(DFC, MULTI) ((DFC) && !(MULTI) ? P2_DFC_WAVES : 1)
+#define P2_WPE(DFC, MULTI) ((DFC) && !(MULTI) ? 3 : 1)
 
 namespace p2 {
 

@@ -30,9 +30,6 @@ using pzw::WAVE;
 using pzw::Wave;
 
 #define TV_NOINLINE __attribute__((noinline))
-#if defined(TV_PROFILE_FULL) && !defined(TV_PROFILE)
-#define TV_PROFILE   // -DTV_PROFILE: per-wave stamps and waits only; -DTV_PROFILE_FULL: also cycles per operator type (slows the walks)
-#endif
 
 struct TPZ {
     GLB_AS pzkey_t* keys;
@@ -62,7 +59,7 @@ struct TW {
     int hmin = 192;        // walks with fewer sorted terms stay on one wave (two hand-overs cost more than half of such a walk)
     bool hded = false;     // the channel belongs to a DEDICATED helper wave (eight-wave blocks, below): it serves whatever is posted, nothing is counted
 #ifdef TV_PROFILE  // development: cycles in the sorts, in the walks, raw terms walked, operator calls
-    long long c_sort = 0, c_walk = 0, c_cc = 0, n_raw = 0, n_calls = 0, n_emit = 0, c_wait = 0, c_fwd = 0, c_wait_fwd = 0, c_hwait = 0, n_shared = 0, n_shared_terms = 0;
+    long long c_sort = 0, c_walk = 0, n_raw = 0, n_calls = 0, n_emit = 0, c_wait = 0, c_fwd = 0, c_wait_fwd = 0, c_hwait = 0, n_shared = 0, n_shared_terms = 0;
     long long c_type[3] = {0, 0, 0}, n_type[3] = {0, 0, 0};  // walk cycles / raw terms of mul, cross, sums
     long long c_fn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, n_fn[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // whole-call cycles / calls: 0 sorted product, 1 product with a constant left operand, 2 cross, 3 sum, 4 constant cross, 5 helper service, 6 set / transpose, 7 link tables
 #endif
@@ -203,9 +200,7 @@ struct Out {
 // sum records that sum again); when the context ends the minimum is folded into the wave's register (TW::w.mabs, which lives as long as the work
 // item), and the kernel reduces it over the lanes -- the group's time steps -- into the problem's word when the item ends (p1_tv.inc.h).
 __device__ inline void mtrk(double& m, double thr_sq, double s) {
-#ifndef PZW_NO_MARGIN   // (development: the build without the tracking, for its cost -- profiles/r06_prune_margin.txt)
-    m = fmin(m, fabs(s - thr_sq));
-#endif
+    m = fmin(m, fabs(s - thr_sq));  // (its cost: profiles/r06_prune_margin.txt)
 }
 template <class CX>
 __device__ inline void mfold(TW& t, const CX& cx) { t.w.mabs = fmin(t.w.mabs, cx.mabs); }
@@ -236,12 +231,6 @@ __device__ inline bool verdict(double thr, double thr_sq, bool active, double* a
 //     void add(const Regs&, bool first)          -- accumulate it (first: start a new sum)
 //     void close(pzkey_t key)                   -- the run of equal keys is complete: verdict + emit
 // Loads run U terms ahead of their use.
-#ifdef TV_PROFILE_FULL
-__device__ long long g_tvprof[8];  // (round 3's in-walk stamps: load phase, process phase, chunk prologue, batches -- no longer filled: the walk is pipelined)
-#endif
-#ifndef TV_WALK_PIPELINE
-#define TV_WALK_PIPELINE 1   // development: 0 = round 3's form (a batch of U terms is loaded, waited for and processed before the next is asked for)
-#endif
 // the serial part of a batch of HB terms whose loads have been issued: products (PB at a time, term-innermost), then run logic, sums, verdicts
 template <int HB, class P>
 __device__ inline void walk_consume(P& pol, const typename P::Regs* regs, pzkey_t key_v, int l0, int n, bool& have, pzkey_t& cur) {
@@ -304,49 +293,40 @@ __device__ inline void walk_sorted(int lane, int N_, const KeyAt& keyat, const I
     bool have = false;
     pzkey_t cur = 0;
     if (N0 >= N) return;
-    if constexpr (TV_WALK_PIPELINE && U % 2 == 0) {
-        // Two half-batches in flight alternately (round 4): while one half's terms are processed the other half's rows are on their
-        // way -- round 3 asked for U terms' rows, waited for them, processed them, and only then asked for the next U: a walk waits
-        // for rows, and during the processing nothing was in flight.  The same registers as before (U terms' rows);
-        // every load is unconditional with a clamped term index, so that the compiler's vmcnt for a half is the exact number of
-        // loads issued after it.  The pipeline runs ACROSS the 64-term chunks: the next chunk's keys and descriptors are worked out
-        // while the current chunk's first loads are in flight, and the half that follows a chunk's last half is the next chunk's first
-        // (picked with selects on the wave-uniform condition -- a branch would make the load count path-dependent).
-        // (Measured against it, one box, B = 128: a ring of FOUR quarter-batches -- three in flight -- 9.28 against 9.12 ms: the products of a
-        //  quarter interleave less; larger batches, U = 24 / 12: 9.57 against 9.06, the rows no longer fit the registers.)
-        constexpr int HB = U / 2;
-        typename P::Regs ra[HB], rb[HB];
-        WalkChunk<P> c = walk_chunk(pol, lane, N0, N, keyat, idxat);
-        walk_issue<HB>(pol, c, 0, ra);
-        for (int base = N0; base < N; base += WAVE) {
-            const bool more = base + WAVE < N;
-            WalkChunk<P> nx = c;
-            if (more) nx = walk_chunk(pol, lane, base + WAVE, N, keyat, idxat);   // (wave-uniform; no row load inside)
-            for (int l0 = 0; l0 < c.n; l0 += U) {
-                walk_issue<HB>(pol, c, l0 + HB, rb);
-                walk_consume<HB>(pol, ra, c.key_v, l0, c.n, have, cur);
-                {   // the next first half: this chunk's, or -- behind its last half -- the next chunk's
-                    const bool here = l0 + U < c.n;
-                    WalkChunk<P> w2;
-                    w2.n = here ? c.n : nx.n;
-                    w2.idx_v = here ? c.idx_v : nx.idx_v;
-                    w2.key_v = 0;
-                    w2.dv = P::select_desc(here, c.dv, nx.dv);
-                    walk_issue<HB>(pol, w2, here ? l0 + U : 0, ra);
-                }
-                walk_consume<HB>(pol, rb, c.key_v, l0 + HB, c.n, have, cur);
+    static_assert(U % 2 == 0, "the walk alternates two half-batches");
+    // Two half-batches in flight alternately (round 4): while one half's terms are processed the other half's rows are on their
+    // way -- round 3 asked for U terms' rows, waited for them, processed them, and only then asked for the next U: a walk waits
+    // for rows, and during the processing nothing was in flight.  The same registers as before (U terms' rows);
+    // every load is unconditional with a clamped term index, so that the compiler's vmcnt for a half is the exact number of
+    // loads issued after it.  The pipeline runs ACROSS the 64-term chunks: the next chunk's keys and descriptors are worked out
+    // while the current chunk's first loads are in flight, and the half that follows a chunk's last half is the next chunk's first
+    // (picked with selects on the wave-uniform condition -- a branch would make the load count path-dependent).
+    // (Measured against it, one box, B = 128: a ring of FOUR quarter-batches -- three in flight -- 9.28 against 9.12 ms: the products of a
+    //  quarter interleave less; larger batches, U = 24 / 12: 9.57 against 9.06, the rows no longer fit the registers.)
+    // (Round 3's form is a build switch in pz_tv.h at commit e68a297.)
+    constexpr int HB = U / 2;
+    typename P::Regs ra[HB], rb[HB];
+    WalkChunk<P> c = walk_chunk(pol, lane, N0, N, keyat, idxat);
+    walk_issue<HB>(pol, c, 0, ra);
+    for (int base = N0; base < N; base += WAVE) {
+        const bool more = base + WAVE < N;
+        WalkChunk<P> nx = c;
+        if (more) nx = walk_chunk(pol, lane, base + WAVE, N, keyat, idxat);   // (wave-uniform; no row load inside)
+        for (int l0 = 0; l0 < c.n; l0 += U) {
+            walk_issue<HB>(pol, c, l0 + HB, rb);
+            walk_consume<HB>(pol, ra, c.key_v, l0, c.n, have, cur);
+            {   // the next first half: this chunk's, or -- behind its last half -- the next chunk's
+                const bool here = l0 + U < c.n;
+                WalkChunk<P> w2;
+                w2.n = here ? c.n : nx.n;
+                w2.idx_v = here ? c.idx_v : nx.idx_v;
+                w2.key_v = 0;
+                w2.dv = P::select_desc(here, c.dv, nx.dv);
+                walk_issue<HB>(pol, w2, here ? l0 + U : 0, ra);
             }
-            c = nx;
+            walk_consume<HB>(pol, rb, c.key_v, l0 + HB, c.n, have, cur);
         }
-    } else {
-        for (int base = N0; base < N; base += WAVE) {
-            const WalkChunk<P> c = walk_chunk(pol, lane, base, N, keyat, idxat);
-            for (int l0 = 0; l0 < c.n; l0 += U) {
-                typename P::Regs regs[U];
-                walk_issue<U>(pol, c, l0, regs);
-                walk_consume<U>(pol, regs, c.key_v, l0, c.n, have, cur);
-            }
-        }
+        c = nx;
     }
     if (have) pol.close(cur);
 }
@@ -1447,9 +1427,6 @@ __device__ TV_NOINLINE void cross_const(TW& t, const TPZ& out, const TView& a_, 
     WSYNC();
     Out<3> o;
     o.init(out, rl);
-#ifdef TV_PROFILE_FULL
-    const long long cc0__ = clock64();
-#endif
     // a dedicated helper takes the upper part of a's monomials (the key list is a's: no sort, the split is one of the list)
     const bool shared = t.hch != nullptr && t.hded && 2 * a.cnt >= t.hmin;
     int S = a.cnt;
@@ -1477,9 +1454,6 @@ __device__ TV_NOINLINE void cross_const(TW& t, const TPZ& out, const TView& a_, 
         for (int c = 0; c < 3; c++) { ra1[c] += hdr[(size_t)c * GR + rl]; ra2[c] += hdr[(size_t)(3 + c) * GR + rl]; o.asum[c] += hdr[(size_t)(6 + c) * GR + rl]; }
         o.n += nh;
     }
-#ifdef TV_PROFILE_FULL
-    t.c_cc += clock64() - cc0__;
-#endif
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         st_hdr(out, H_CEN, c, rl, cen[c]);

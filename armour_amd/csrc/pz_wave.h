@@ -36,11 +36,7 @@
 // narrow rows, whose mul<3,3,3,3> is the first shipped function to cross the limit).  Declaring s30 / s31 clobbered at the entry makes the
 // compiler keep the return address elsewhere (a lane of a VGPR, as in functions that call), so that the scavenged pair is free to use.
 // tools/check_long_branches.py verifies on every P1 object that no function relaxes a branch through an unsaved s[30:31].
-#ifdef PZ_NO_RETURN_ADDRESS_GUARD   // (forensic builds only: the objects of rounds 1-4 as they were, for tools/check_long_branches.py to look at)
-#define PZ_KEEP_RETURN_ADDRESS()
-#else
 #define PZ_KEEP_RETURN_ADDRESS() asm volatile("; return address kept out of s[30:31] (pz_wave.h)" ::: "s30", "s31")
-#endif
 
 namespace pzw {
 
@@ -73,7 +69,7 @@ enum { PR_FILL = 0, PR_SORT = 1, PR_EMIT = 2, PR_ABS = 3, PR_CALLS = 4, PR_TERMS
 enum { ERR_RAW_OVERFLOW = 1, ERR_SLOT_OVERFLOW = 2, ERR_TABLE_OVERFLOW = 4, ERR_LINK_GENS = 8, ERR_PAIR = 32, ERR_DBG_BOUNDS = 128,
        ERR_HELPER = 256 /* a time step on two CUs (p1_free.inc.h): the helper block's results did not arrive -- the host builds again on one CU per step */,
        ERR_HELPER_LATE = 512 /* not an error: a main block gave up waiting for its helper to START (the device is shared, or holds fewer CUs than it reports) and built its item alone -- the tables are good, the handle goes back to one CU per step */ };
-// -DDBG_BOUNDS (root-cause tooling, tools/dev/gpu_fault_hunt.py): every LDS / arena index of the product merge and of the reduce
+// -DDBG_BOUNDS (`make checked`, tests/test_codegen_fences.py): every LDS / arena index of the product merge and of the reduce
 // pass is range-checked BEFORE the access; a violation is recorded (flag 128, lstat[3] = code * 2^20 + the offending value's
 // low 20 bits, first one wins) and the index clamped to 0, so that a genuine out-of-range index shows up as a report
 // instead of a memory fault.
@@ -176,29 +172,12 @@ __device__ inline View elem(const Wave& w, const PZ& p, int r) { return View{p.k
 // Sum over the 64 lanes, returned in every lane.  Data-parallel-primitive moves inside the VALU (quad permutes, row
 // mirrors, row broadcasts) instead of six rounds of cross-lane shuffles through the LDS crossbar, which cost ~3 k cycles
 // per product operator in abs_sum alone (tools/dev/gpu_pzop_cost.py).  Fixed summation tree: the same result in every launch shape.
-#ifdef NO_DPP  /* development: the same data movement through ds_bpermute instead of DPP moves */
-template <int CTRL, int ROW_MASK>
-__device__ inline double dpp_take(double v) {
-    const int lane = (int)(threadIdx.x & 63), row = lane >> 4, li = lane & 15;
-    int src = lane; bool valid = true;
-    if (CTRL == 0xB1) src = lane ^ 1;
-    else if (CTRL == 0x4E) src = lane ^ 2;
-    else if (CTRL == 0x141) src = (lane & ~7) | (7 - (lane & 7));
-    else if (CTRL == 0x140) src = (lane & ~15) | (15 - li);
-    else if (CTRL == 0x142) { src = row * 16 - 1; valid = row > 0; }
-    else if (CTRL == 0x143) { src = 31; valid = row >= 2; }
-    else if (CTRL == 0x130) { src = lane + 1; valid = lane < 63; }
-    const double g = __shfl(v, valid ? src : lane, 64);
-    return (valid && ((ROW_MASK >> row) & 1)) ? g : 0.0;
-}
-#else
 template <int CTRL, int ROW_MASK>
 __device__ inline double dpp_take(double v) {  // the value of the lane selected by CTRL; 0.0 where no lane is selected / the row is masked
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-#endif
 __device__ inline double wave_sum(double v) {
     v += dpp_take<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
     v += dpp_take<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
@@ -233,9 +212,7 @@ __device__ inline bool norm_le(const double* acc, const Wave& w) {
 // ---- prune margin: the verdicts of simplify() with their distance to the threshold recorded (Wave::mabs) ----
 // s = the squared norm the verdict was taken on (1x1: v * v, whose root IS |v|)
 __device__ inline void mtrack(Wave& w, double s) {
-#ifndef PZW_NO_MARGIN   // (development: the build without the tracking, for its cost -- profiles/r06_prune_margin.txt)
-    w.mabs = fmin(w.mabs, fabs(s - w.thr_sq));
-#endif
+    w.mabs = fmin(w.mabs, fabs(s - w.thr_sq));  // (its cost: profiles/r06_prune_margin.txt)
 }
 __device__ inline bool norm1_le_t(Wave& w, double v) { mtrack(w, v * v); return fabs(v) <= w.thr; }
 template <int SZ>
@@ -249,9 +226,6 @@ __device__ inline bool norm_le_t(const double* acc, Wave& w) {
 }
 // fold this operator's tracker into the wave's LDS row (every lane its own place: no reduction here)
 __device__ inline void mflush(const Wave& w) {
-#ifdef PZW_NO_MARGIN
-    return;
-#endif
     if (w.mg == nullptr) return;
     w.mg[w.lane] = fmin(w.mg[w.lane], w.mabs);
 }
@@ -408,25 +382,6 @@ __device__ inline int sort_terms(Wave& w, int N, const Eval& ev, bool& indirect)
         } else if (ev.try_merge(w, N, indirect)) {
             // the operands' sorted runs were merged: either skey / sidx hold the sorted keys and the permutation like the
             // bitonic path leaves them, or (`indirect`) sidx holds the permutation and the keys come from the LDS staging
-#ifdef DBG_CHECK_MERGE
-            {
-                int bad = 0;
-                for (int p = w.lane; p < N; p += WAVE) {
-                    const pzkey_t kp = indirect ? ev.key_lds(w, w.sidx[p]) : w.skey[p];
-                    if (p > 0 && (indirect ? ev.key_lds(w, w.sidx[p - 1]) : w.skey[p - 1]) > kp) bad = 1;
-                    if (p > 0 && (indirect ? ev.key_lds(w, w.sidx[p - 1]) : w.skey[p - 1]) == kp && w.sidx[p - 1] > w.sidx[p]) bad |= 4;
-                    if (kp != ev.key(w.sidx[p])) bad |= 2;
-                }
-                {
-                    const unsigned long long any = __ballot(bad != 0);
-                    if (any != 0ull && !(w.lstat[ST_ERR] & 64)) {
-                        int bits = 0;
-                        for (int b = 1; b <= 4; b <<= 1) if (__ballot((bad & b) != 0) != 0ull) bits |= b;
-                        if (w.lane == 0) { w.lstat[ST_ERR] |= 64; w.lstat[3] = (N & 0xffff) | (bits << 16) | ((indirect ? 1 : 0) << 20) | (__popcll(any) << 24); }
-                    }
-                }
-            }
-#endif
         } else {
             const int P = next_pow2(N);
             if (w.half == 0) {   // (a pair: the first wave alone -- the network is the path of last resort)
@@ -694,16 +649,12 @@ struct LinEval {
     __device__ inline bool try_merge(Wave& w, int N, bool& indirect) const {
         if (!can_merge(w, N)) return false;
         indirect = true;
-#ifdef DBG_NO_MERGE_LIN
-        return false;
-#endif
         PROF_T0
         const int nl = w.nl;   // (cooperating lanes: one wave's, or a pair's)
-#ifndef LIN_MERGE_BY_SEARCH
         // Merge path (round 4): the NS sorted runs are merged pairwise in ceil(log2 NS) levels between the two halves of the sort buffers, as
         // a product's runs are (MulEval::tree_merge) -- a lane fills consecutive places of a level with one diagonal search and a two-finger
-        // merge -- instead of NS - 1 binary searches for every term (-DLIN_MERGE_BY_SEARCH: that form, also taken when the buffers cannot
-        // hold two copies).  Ties go to the earlier run, which is generation order: the same order, and the keys come out sorted in skey.
+        // merge -- instead of NS - 1 binary searches for every term (that form, below, is taken when the buffers cannot hold two copies).
+        // Ties go to the earlier run, which is generation order: the same order, and the keys come out sorted in skey.
         if (2 * N <= w.cap_key && 2 * N <= w.cap_raw) {
             constexpr int LV = NS <= 2 ? 1 : 2;   // (NS <= 4)
             static_assert(NS <= 4, "merge levels");
@@ -743,7 +694,7 @@ struct LinEval {
             PROF_ADD(PR_SORT) PROF_ADD(PR_S_LINMERGE)
             return true;
         }
-#endif
+        // fall-back: rank every term by binary searches in the other runs
         for (int i0 = w.lane2; i0 < N; i0 += 4 * nl) {   // (four keys per lane and pass in flight: see MulEval::tree_merge)
             pzkey_t kk[4];
 #pragma unroll
@@ -1074,20 +1025,10 @@ struct MulEval {
         return sp;
     }
     __device__ inline bool try_merge(Wave& w, int N, bool& indirect) const {
-#ifdef DBG_NO_MERGE_MUL
-        return false;
-#endif
-#ifndef DBG_NO_TREE
         if (can_tree(w, N)) { indirect = false; tree_merge(w, N); return true; }
-#endif
-#ifdef DBG_NO_RANK
-        return false;
-#endif
         if (!can_rank(w)) {   // too long for the tree's two buffers and too many runs to rank
-#ifndef DBG_NO_SPLIT
             const Split sp = split_of(w, N);
             if (sp.ok) { indirect = false; split_merge(w, N, sp); return true; }
-#endif
             return false;     // ... and no split that fits: the bitonic network
         }
         indirect = true;
@@ -1095,12 +1036,9 @@ struct MulEval {
     }
     // The raw terms in generation order ARE a concatenation of sorted runs: for a fixed term i of a (centre first), the
     // keys KA[i] + KB[j] rise with j.  Merge those runs pairwise, level by level, between the two halves of the sort
-    // buffers: an element's place in the merged pair is its offset in its own run plus the number of the sibling run's
-    // elements that go before it -- ONE binary search per element and level (ties: the earlier run first, which is
-    // generation order), log2(#runs) levels.  Against the bitonic network this replaces (72 % of a 40 x 40 cross product,
-    // tools/dev/gpu_pzop_cost.py) that is ~50 search steps per element instead of 66 compare-exchange stages, and against the
-    // one-search-per-run ranking below it is log2 instead of linear in the number of runs.  Eight elements per lane are
-    // searched together, branch-free with a wave-uniform step count, so that their LDS reads overlap.
+    // buffers (ties: the earlier run first, which is generation order), log2(#runs) levels.  This replaces the bitonic network
+    // (72 % of a 40 x 40 cross product, tools/dev/gpu_pzop_cost.py), and against the one-search-per-run ranking below it is
+    // log2 instead of linear in the number of runs.
     // The runs are taken along the SHORTER operand (fewer runs = fewer levels): a's terms when a is the shorter one -- the
     // generation order itself -- and otherwise b's terms, with the raw terms laid out b-major for the merge and their
     // generation index carried as the payload.  Equal keys must come out in generation order (a-major): between two runs
@@ -1146,17 +1084,13 @@ struct MulEval {
             }
         }
         psync(w);
-        [[maybe_unused]] constexpr int U = 8;
         for (int lv = 0; lv < levels; lv++) {
             const int rl = d1 << lv;  // run r of this level holds the positions q with q + 1 in [r*rl, (r+1)*rl)
-            [[maybe_unused]] int top = 1;
-            while (top * 2 <= rl) top *= 2;
             const LDS_AS pzkey_t* K = kb[cur];
             const LDS_AS uint16_t* V = vb[cur];
             LDS_AS pzkey_t* Ko = kb[cur ^ 1];
             LDS_AS uint16_t* Vo = vb[cur ^ 1];
-#ifndef TREE_MERGE_BY_SEARCH
-            // Merge path (round 4; -DTREE_MERGE_BY_SEARCH builds the rounds 2-3 form below, one binary search per element and level).  Every
+            // Merge path (round 4; the rounds 2-3 form, one binary search per element and level, is in pz_wave.h at commit e68a297).  Every
             // lane produces E CONSECUTIVE places of the level's output: one search along the diagonal of its first place -- how many of the
             // places before it come from the pair's first run -- and then a serial two-finger merge of E elements, one key read per element.
             // The search form spent 11 steps of ~8 instructions on every element at every level; this spends them once per lane and level.
@@ -1176,51 +1110,6 @@ struct MulEval {
                     c = c9;
                 }
             }
-#else
-            for (int p0 = w.lane2; p0 < N; p0 += nl * U) {
-                int ss[U], len[U], cnt[U], dst[U];
-                pzkey_t tg[U], ky[U];
-                bool ok[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const int p = p0 + nl * u;
-                    ok[u] = p < N;
-                    const int pc = ok[u] ? p : 0;
-                    const int r = (int)(((unsigned long long)(pc + 1) * magic) >> 32) >> lv;
-                    const int s0 = max(r * rl - 1, 0);
-                    const int rs = r ^ 1;
-                    const int sb = max(rs * rl - 1, 0), se = min((rs + 1) * rl - 1, N);
-                    len[u] = max(se - sb, 0);  // 0: the last run of an odd count has no sibling
-                    ss[u] = len[u] > 0 ? sb : 0;
-                    ky[u] = K[BIDX(w, pc, N, 1)];
-                    // count the sibling's keys below ky -- and its equal key too if the sibling's term goes first on a tie
-                    tg[u] = ky[u] + (pzkey_t)(((r & 1) != 0) == by_a ? 1 : 0);
-                    cnt[u] = 0;
-                    dst[u] = min(s0, sb) + (pc - s0);
-                }
-                for (int step = top; step > 0; step >>= 1) {
-                    pzkey_t v[U];
-#pragma unroll
-                    for (int u = 0; u < U; u++) v[u] = K[BIDX(w, ss[u] + max(min(cnt[u] + step, len[u]), 1) - 1, N, 2)];
-#pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        const int take = (int)(cnt[u] + step <= len[u]) & (int)(v[u] < tg[u]);  // (no short circuit: a branch would serialise the reads)
-#ifdef TREE_MERGE_SELECT_FORM  /* the value-identical rewrite that faulted in round 1; kept for the root-cause tooling only:
-                                  a bit mask over the product shapes (1: 3x3*3x1, 2: 3x3*3x3, 4: 1x1*1x1 incl. cross, 8: 1x1*3x1) */
-                        if constexpr ((((TREE_MERGE_SELECT_FORM) >> (SH::ASZ == 9 ? (SH::BSZ == 3 ? 0 : 1) : (SH::BSZ == 1 ? 2 : 3))) & 1) != 0)
-                            cnt[u] = take ? cnt[u] + step : cnt[u];
-                        else
-                            cnt[u] += take ? step : 0;
-#else
-                        cnt[u] += take ? step : 0;
-#endif
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; u++)
-                    if (ok[u]) { const int o__ = BIDX(w, dst[u] + cnt[u], N, 3); Ko[o__] = ky[u]; Vo[o__] = V[BIDX(w, p0 + nl * u, N, 4)]; }
-            }
-#endif
             psync(w);
             cur ^= 1;
         }
@@ -1299,9 +1188,6 @@ struct MulEval {
         const bool a_short = a.cnt <= b.cnt;
         const int ns = (a_short ? a.cnt : b.cnt) + 1, nl = (a_short ? b.cnt : a.cnt) + 1;
         if (!can_rank(w)) return false;
-#ifdef DBG_NO_MERGE_MUL
-        return false;
-#endif
         PROF_T0
         const GLB_AS pzkey_t* lk = a_short ? b.keys : a.keys;
         const GLB_AS pzkey_t* sk = a_short ? a.keys : b.keys;

@@ -293,7 +293,8 @@ struct Leader {
     long long t_start;
     // the problem's constants, staged once (global loads from a single lane cost ~1 us each)
     double bz[3 * NV], qdes[NV];
-    // QP state and temporaries (thread 0 works on them with run-time indices: LDS, not scratch)
+    // QP state and temporaries (thread 0 works on them with run-time indices: LDS, not scratch).  u, An, M, Lc, Lci, rhs, r, bp, up, A, q,
+    // p, added, chol_rows, act, exc and rs were the block-wide QP's, which is gone; they stay so that the kernel's LDS layout is unchanged.
     double qx[NV], u[NV + 1], An[NV][NV], np[NV];
     double M[NV * NV], Lc[NV][NV], Lci[NV], invHd[NV], rhs[NV], r[NV], z[NV];   // Lci[i] = 1 / Lc[i][i], invHd[j] = 1 / Hd[j] (solver.hip spd_solve)
     double bp, up, max_mult, sigma;
@@ -305,324 +306,6 @@ struct Leader {
     int scan[1024];
 };
 
-// QP rows: [0, ncand) the gathered candidates (b = v - sigma * max(v, 0)), then 2n bound rows  x_l <= x + d <= x_u
-__device__ inline void qp_row(const SolveArgs& a, const Leader& L, const SolveRow* cand, int i, double* arow, double& brow) {
-    if (i < L.ncand) {
-        const SolveRow& r = cand[i];
-#pragma unroll
-        for (int j = 0; j < NV; j++) arow[j] = r.a[j];
-        const double v = r.v;
-        brow = v - (v > 0 ? L.sigma * v : 0.0);
-    } else {
-        const int e = i - L.ncand, j = e >> 1;
-        const double sg = (e & 1) == 0 ? 1.0 : -1.0;
-#pragma unroll
-        for (int jj = 0; jj < NV; jj++) arow[jj] = jj == j ? sg : 0.0;    // (no run-time register index: that would be scratch)
-        brow = (e & 1) == 0 ? -1.0 - L.x[j] : -(1.0 - L.x[j]);            // r.b = xl[j] - s.x[j];  r2.b = -(xu[j] - s.x[j])
-    }
-}
-
-// Goldfarb-Idnani for  min 1/2 d'Gd + g0'd  s.t.  a_i'd >= b_i,  G = diag(Hd) > 0: solve_qp of solver.hip, same arithmetic, arranged
-// for a GPU block.  All 256 threads call it; results in L.qx / L.max_mult / L.feasible.
-//   * the search for the most violated row uses the whole block; with at most 256 rows every thread keeps its row in registers
-//     across the steps, and the active / excluded flags live in LDS while they fit;
-//   * the step runs on wave 0, all 64 lanes in lockstep on the same LDS state (redundant, hence free).  The loops with a division
-//     per term -- M = N'G^-1 N, N'G^-1 np and z -- are dealt one entry per lane, each entry summed in the host form's order;
-//   * the Cholesky factor of M and the two triangular solves run in registers (fully unrolled, guarded by the active count) and
-//     the factor is extended row by row as rows enter the active set: row i of the factor depends on rows <= i of M only, so the
-//     numbers are those of the from-scratch factorisation the host form does at every step.
-template <int WPS>   // (one copy per compiled occupancy, see leader_step)
-__device__ inline void solve_qp_device(const SolveArgs& a, Leader& L, const SolveRow* cand, unsigned char* is_active_g, unsigned char* excluded_g,
-                                       int max_iter = kQpMaxSteps) {
-    const int n = a.tb.n, tid = threadIdx.x;
-    const int mrows = L.ncand + 2 * n;
-    unsigned char* is_active = mrows <= kFlagsInLds ? L.act : is_active_g;
-    unsigned char* excluded = mrows <= kFlagsInLds ? L.exc : excluded_g;
-    if (tid == 0) {
-        for (int j = 0; j < NV; j++) { L.invHd[j] = 1.0 / L.Hd[j]; L.qx[j] = j < n ? -L.gradf[j] * L.invHd[j] : 0.0; }
-        L.q = 0; L.qp_iter = 0; L.feasible = 1; L.max_mult = 0; L.stop = 0; L.chol_rows = 0;
-    }
-    for (int i = tid; i < mrows; i += 256) { is_active[i] = 0; excluded[i] = 0; }
-    const bool one_row = mrows <= 256;
-    double my_a[NV], my_b = 0.0;
-#pragma unroll
-    for (int j = 0; j < NV; j++) my_a[j] = 0.0;
-    if (one_row && tid < mrows) qp_row(a, L, cand, tid, my_a, my_b);
-    __syncthreads();
-    // wave 0's QP state (the same values in all of its lanes): iterate, multipliers, active count, valid rows of the Cholesky factor
-    double qx[NV], u[NV + 1];
-#pragma unroll
-    for (int j = 0; j < NV; j++) { qx[j] = j < n ? L.qx[j] : 0.0; u[j] = 0.0; }
-    u[NV] = 0.0;
-    int q = 0, cv = 0;
-    long long* qst = a.stamps ? a.stamps + (size_t)(blockIdx.x / a.nb + a.b0) * 64 + 44 : nullptr;   // ARMOUR_SOLVE_TIMING: ticks per part of the QP step, summed over the steps
-    long long q_t = qst ? wall_clock64() : 0;
-#define QP_LAP(slot) if (qst && tid == 0) { const long long n__ = wall_clock64(); qst[slot] += n__ - q_t; q_t = n__; }
-    for (;;) {
-        // most violated inactive row: smallest s = a_i'x - b_i below -1e-10, the first such row on ties
-        double best = -1e-10;
-        int bi = -1;
-        if (one_row) {
-            if (tid < mrows && !is_active[tid] && !excluded[tid]) {
-                double s = -my_b;
-#pragma unroll
-                for (int j = 0; j < NV; j++) if (j < n) s += my_a[j] * L.qx[j];
-                if (s < best) { best = s; bi = tid; }
-            }
-        } else {
-            for (int i = tid; i < mrows; i += 256) {
-                if (is_active[i] || excluded[i]) continue;
-                double ar[NV], br;
-                qp_row(a, L, cand, i, ar, br);
-                double s = -br;
-#pragma unroll
-                for (int j = 0; j < NV; j++) if (j < n) s += ar[j] * L.qx[j];   // (unrolled: `ar` stays in registers)
-                if (s < best) { best = s; bi = i; }
-            }
-        }
-        // lexicographic (value, index) minimum: the sequential scan keeps the FIRST row attaining the minimum.
-        // Inside each wave by shuffles, then the four waves' results through LDS: two barriers instead of nine.
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(best, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (oi >= 0 && (bi < 0 || o < best || (o == best && oi < bi))) { best = o; bi = oi; }
-        }
-        if ((tid & 63) == 0) { L.rs[tid >> 6] = best; L.ri[tid >> 6] = bi; }
-        __syncthreads();
-        {
-            best = L.rs[0]; bi = L.ri[0];
-#pragma unroll
-            for (int w2 = 1; w2 < 4; w2++) {
-                const double o = L.rs[w2];
-                const int oi = L.ri[w2];
-                if (oi >= 0 && (bi < 0 || o < best || (o == best && oi < bi))) { best = o; bi = oi; }
-            }
-        }
-        const int p = bi;
-        __syncthreads();
-        QP_LAP(0)
-        if (p < 0) break;
-        if (one_row && tid == p) {   // the entering row's normal and right-hand side: from the thread that holds them
-#pragma unroll
-            for (int j = 0; j < NV; j++) L.np[j] = my_a[j];
-            L.bp = my_b;
-        }
-        __syncthreads();
-        QP_LAP(1)
-        if (tid < 64) {
-            // Wave 0, all lanes in lockstep.  The small vectors (entering normal, iterate, multipliers, z, r) live in REGISTERS, the same
-            // values in every lane; LDS carries only what lanes exchange (M, rhs, the z entries) and what the other waves read (qx, flags).
-            // (With everything in LDS a step was a chain of ~150 dependent LDS round trips: 6 us.)
-            L.p = p;
-            if (++L.qp_iter > max_iter) { L.feasible = 0; L.stop = 1; }
-            else {
-                if (!one_row) {
-                    double npr0[NV], bpr;
-                    qp_row(a, L, cand, p, npr0, bpr);
-#pragma unroll
-                    for (int j = 0; j < NV; j++) L.np[j] = npr0[j];
-                    L.bp = bpr;
-                    WAVE_LDS_SYNC();
-                }
-                double npr[NV], ih[NV];
-#pragma unroll
-                for (int j = 0; j < NV; j++) { npr[j] = L.np[j]; ih[j] = L.invHd[j]; }
-                const double bp = L.bp;
-                double up = 0.0;
-                bool added = false;
-                for (int guard = 0; guard < 4 * NV + 8 && !added; guard++) {
-                    // r = N* np,  z = G^-1 (np - N r)
-                    double rr[NV];
-#pragma unroll
-                    for (int i = 0; i < NV; i++) rr[i] = 0.0;
-                    WAVE_LDS_SYNC();
-                    if (q > 0) {
-                        if (tid < NV * NV) {
-                            const int i = tid / NV, k = tid - i * NV;
-                            if (i < q && k <= i) {
-                                double s = 0;
-#pragma unroll
-                                for (int j = 0; j < NV; j++) if (j < n) s += L.An[i][j] * L.An[k][j] * ih[j];
-                                L.M[i * NV + k] = s; L.M[k * NV + i] = s;
-                            }
-                        } else if (tid < NV * NV + NV) {
-                            const int i = tid - NV * NV;
-                            if (i < q) {
-                                double s = 0;
-#pragma unroll
-                                for (int j = 0; j < NV; j++) if (j < n) s += L.An[i][j] * npr[j] * ih[j];
-                                L.rhs[i] = s;
-                            }
-                        }
-                        WAVE_LDS_SYNC();
-                        QP_LAP(2)
-                        // Cholesky M = Lc Lc' (spd_solve of solver.hip), rows [cv, q) new, in registers
-                        double Lr[NV][NV], Li[NV];
-#pragma unroll
-                        for (int i = 0; i < NV; i++) {
-                            Li[i] = i < cv ? L.Lci[i] : 0.0;
-#pragma unroll
-                            for (int k = 0; k <= i; k++) Lr[i][k] = i < cv ? L.Lc[i][k] : 0.0;
-                        }
-                        bool spd = true;
-#pragma unroll
-                        for (int i = 0; i < NV; i++) {
-                            if (i >= cv && i < q && spd) {
-#pragma unroll
-                                for (int jj = 0; jj <= i; jj++) {
-                                    if (spd) {
-                                        double s = L.M[i * NV + jj];
-#pragma unroll
-                                        for (int k = 0; k < jj; k++) s -= Lr[i][k] * Lr[jj][k];
-                                        if (jj == i) {
-                                            if (s <= 1e-14 * fabs(L.M[i * NV + i]) || s <= 0) spd = false;
-                                            else { Lr[i][i] = sqrt(s); Li[i] = 1.0 / Lr[i][i]; }
-                                        } else {
-                                            Lr[i][jj] = s * Li[jj];
-                                        }
-                                    }
-                                }
-                                if (spd) {
-#pragma unroll
-                                    for (int k = 0; k <= i; k++) L.Lc[i][k] = Lr[i][k];
-                                    L.Lci[i] = Li[i];
-                                    cv = i + 1;
-                                }
-                            }
-                        }
-                        if (!spd) { excluded[p] = 1; break; }  // dependent active set: skip this row
-                        double tt[NV];
-#pragma unroll
-                        for (int i = 0; i < NV; i++) {
-                            tt[i] = 0.0;
-                            if (i < q) {
-                                double s = L.rhs[i];
-#pragma unroll
-                                for (int k = 0; k < i; k++) s -= Lr[i][k] * tt[k];
-                                tt[i] = s * Li[i];
-                            }
-                        }
-#pragma unroll
-                        for (int i = NV - 1; i >= 0; i--) {
-                            if (i < q) {
-                                double s = tt[i];
-#pragma unroll
-                                for (int k = i + 1; k < NV; k++) if (k < q) s -= Lr[k][i] * rr[k];
-                                rr[i] = s * Li[i];
-                            }
-                        }
-                    }
-                    QP_LAP(3)
-                    // z: lane j forms entry j (np_j - sum_i An[i][j] r_i in row order, times 1/Hd_j), then every lane takes all of them
-                    double zmine = 0.0;
-                    {
-                        const int j = tid < NV ? tid : 0;
-                        double s = 0.0;
-#pragma unroll
-                        for (int jj = 0; jj < NV; jj++) if (jj == j) s = npr[jj];
-#pragma unroll
-                        for (int i = 0; i < NV; i++) if (i < q) s -= L.An[i][j] * rr[i];
-                        double ihj = 0.0;
-#pragma unroll
-                        for (int jj = 0; jj < NV; jj++) if (jj == j) ihj = ih[jj];
-                        zmine = s * ihj;
-                    }
-                    double z[NV];
-#pragma unroll
-                    for (int j = 0; j < NV; j++) z[j] = j < n ? __shfl(zmine, j, 64) : 0.0;
-                    double zz = 0, znp = 0;
-#pragma unroll
-                    for (int j = 0; j < NV; j++) if (j < n) { zz += z[j] * z[j]; znp += z[j] * npr[j]; }
-                    // step lengths
-                    double t1 = kInf;
-                    int l = -1;
-#pragma unroll
-                    for (int i = 0; i < NV; i++)
-                        if (i < q && rr[i] > 1e-14) { const double ur = u[i] / rr[i]; if (ur < t1) { t1 = ur; l = i; } }
-                    double sp = -bp;
-#pragma unroll
-                    for (int j = 0; j < NV; j++) if (j < n) sp += npr[j] * qx[j];
-                    double t2 = kInf;
-                    if (zz > 1e-24 && znp > 1e-16) t2 = -sp / znp;
-                    if (t2 < 0) t2 = 0;
-                    const double t = t1 < t2 ? t1 : t2;
-                    if (t >= kInf) { L.feasible = 0; break; }
-                    QP_LAP(4)
-                    const bool dual_only = t2 >= kInf;
-                    if (!dual_only) {
-#pragma unroll
-                        for (int j = 0; j < NV; j++) if (j < n) qx[j] += t * z[j];
-                    }
-#pragma unroll
-                    for (int i = 0; i < NV; i++) if (i < q) u[i] -= t * rr[i];
-                    up += t;
-                    if (!dual_only && t == t2) {  // full step: the row becomes active
-                        if (q >= n) { L.feasible = 0; break; }
-#pragma unroll
-                        for (int i = 0; i < NV; i++) if (i == q) u[i] = up;
-                        if (tid < NV) L.An[q][tid] = L.np[tid];
-                        if (tid == 0) { L.A[q] = p; is_active[p] = 1; }
-                        q++;
-                        added = true;
-                    } else {        // dual step only, or a partial step: drop the blocking row (and try again)
-                        if (tid == 0) is_active[L.A[l]] = 0;
-                        WAVE_LDS_SYNC();
-                        for (int i = l; i < q - 1; i++) {   // (rare; rows move up one by one, every lane a column)
-                            if (tid < NV) L.An[i][tid] = L.An[i + 1][tid];
-                            if (tid == 0) L.A[i] = L.A[i + 1];
-                            WAVE_LDS_SYNC();
-                        }
-#pragma unroll
-                        for (int i = 0; i < NV; i++) if (i >= l && i < q - 1) u[i] = u[i + 1];
-                        q--;
-                        if (cv > l) cv = l;
-                    }
-                }
-                if (tid < NV) L.qx[tid] = 0.0;
-#pragma unroll
-                for (int j = 0; j < NV; j++) if (tid == j) L.qx[j] = qx[j];
-                L.added = added ? 1 : 0;
-                if (!L.feasible) L.stop = 1;
-                else if (!added && !excluded[p]) excluded[p] = 1;  // could not make progress on this row
-            }
-        }
-        QP_LAP(5)
-        __threadfence_block();
-        __syncthreads();
-        QP_LAP(6)
-        if (L.stop) break;
-    }
-#undef QP_LAP
-    if (tid == 0) {
-        L.q = q; L.chol_rows = cv;
-#pragma unroll
-        for (int i = 0; i < NV; i++) L.u[i] = u[i];
-    }
-    __syncthreads();
-    if (tid == 0)
-        for (int i = 0; i < L.q; i++) if (L.u[i] > L.max_mult) L.max_mult = L.u[i];
-    // excluded rows that remain violated mean the linearisation is inconsistent
-    int viol = 0;
-    if (L.feasible)
-        for (int i = tid; i < mrows; i += 256) {
-            double ar[NV], br;   // (every row, active ones included)
-            qp_row(a, L, cand, i, ar, br);
-            double s = -br;
-#pragma unroll
-            for (int j = 0; j < NV; j++) if (j < n) s += ar[j] * L.qx[j];   // (unrolled: `ar` stays in registers)
-            if (s < -1e-7) viol = 1;
-        }
-    L.ri[tid] = viol;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (tid < s2) L.ri[tid] |= L.ri[tid + s2];
-        __syncthreads();
-    }
-    if (tid == 0 && L.ri[0]) L.feasible = 0;
-    __syncthreads();
-}
-
 __device__ inline int ld_lds_int(const int* p) { return *reinterpret_cast<const volatile int*>(p); }
 // ---- the four elastic attempts of one QP side by side, one per wave ------------------------------------------------------------------
 // solver.hip tries sigma = 0, 0.5, 0.9, 0.99 one after the other and keeps the first attempt that is feasible; the attempts share nothing but
@@ -631,8 +314,12 @@ __device__ inline int ld_lds_int(const int* p) { return *reinterpret_cast<const 
 // matters instead of the sum (an infeasible problem pays all four at every SQP iteration -- after the row culling that was what a batch waited
 // for).  A wave that finishes feasible tells the attempts above it to stop.  Inside an attempt nothing crosses waves: the search for the most
 // violated row runs on the wave's 64 lanes (with at most 64 * kRegRows rows every lane keeps its rows in registers across the steps; more: it
-// reads them four at a time), the step is the lockstep code of solve_qp_device on the wave's own LDS state, and there is no block barrier
-// until all four are done.
+// reads them four at a time), the step runs on the wave's own LDS state, and there is no block barrier until all four are done.
+// An attempt is solve_qp of solver.hip for  min 1/2 d'Gd + g0'd  s.t.  a_i'd >= b_i,  G = diag(Hd) > 0, with the same arithmetic: the loops
+// with a division per term -- M = N'G^-1 N, N'G^-1 np and z -- are dealt one entry per lane, each entry summed in the host form's order; the
+// Cholesky factor of M is extended row by row as rows enter the active set (row i of the factor depends on rows <= i of M only, so the
+// numbers are those of the from-scratch factorisation the host form does at every step).  (The rounds 2-4 form, the attempts one after the
+// other on the whole block, is in solver_device.hip at commit e68a297.)
 struct QpWave {
     double qx[NV], An[NV][NV], np[NV], M[NV * NV], Lc[NV][NV], Lci[NV], rhs[NV];
     double bp, max_mult;
@@ -644,7 +331,7 @@ struct QpShared {
     int first_ok;     // lowest attempt that has finished feasible so far (4: none)
 };
 __device__ inline double attempt_sigma(int attempt) { return attempt == 0 ? 0.0 : attempt == 1 ? 0.5 : attempt == 2 ? 0.9 : 0.99; }
-// QP row i of the attempt with elasticity sigma (qp_row with the attempt's own sigma)
+// QP rows: [0, ncand) the gathered candidates (b = v - sigma * max(v, 0)), then 2n bound rows  x_l <= x + d <= x_u
 __device__ inline void qp_row_s(const SolveArgs& a, const Leader& L, const SolveRow* cand, int i, double sigma, double* arow, double& brow) {
     if (i < L.ncand) {
         const SolveRow& r = cand[i];
@@ -1107,16 +794,6 @@ __device__ __forceinline__ int leader_step(const SolveArgs& a, Leader& L, QpShar
             LSTAMP(1);
             // QP with the elastic retries of solver.hip (sigma = fraction of the violation a row may keep): the four attempts side by side,
             // one per wave, the lowest feasible one taken (solve_qp_wave)
-#ifdef SOLVE_QP_SEQUENTIAL   // (development: the attempts one after the other on the whole block, rounds 2-4; WITHOUT round 6's box-clipped first try, so not the host form's iterates any more)
-            for (int attempt = 0; attempt < 4; attempt++) {
-                if (tid == 0) L.sigma = attempt_sigma(attempt);
-                __syncthreads();
-                solve_qp_device<WPS>(a, L, cand, flags_g, flags_g + (a.cap_rows + 2 * NV));
-                if (L.feasible) break;
-                __syncthreads();
-            }
-            __syncthreads();
-#else
             if (tid == 0) {
                 QS.first_ok = 4;
                 for (int j = 0; j < NV; j++) L.invHd[j] = 1.0 / L.Hd[j];
@@ -1151,7 +828,6 @@ __device__ __forceinline__ int leader_step(const SolveArgs& a, Leader& L, QpShar
                 }
             }
             __syncthreads();
-#endif
             LSTAMP(2);
             if (tid == 0 && a.stamps) { if (L.it == 0) { a.stamps[(size_t)b * 64 + 40] = L.qp_iter; a.stamps[(size_t)b * 64 + 41] = L.ncand; } a.stamps[(size_t)b * 64 + 42] += L.qp_iter; a.stamps[(size_t)b * 64 + 43] += 1; }
             if (tid == 0) {
