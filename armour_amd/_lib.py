@@ -121,6 +121,7 @@ EXPORTS = [
     "armour_batch_partition", "armour_batch_create", "armour_batch_destroy", "armour_batch_set_option", "armour_batch_set_problems",
     "armour_batch_get_sizes", "armour_batch_get_bounds", "armour_batch_eval_g_jac", "armour_batch_eval_violations", "armour_batch_solve",
     "armour_batch_get_build_ms", "armour_batch_get_build_info",
+    "armour_roadmap_create", "armour_roadmap_destroy", "armour_roadmap_get_sizes", "armour_roadmap_check", "armour_roadmap_plan",
 ]
 
 _lib = None
@@ -239,6 +240,13 @@ def load():
     L.armour_batch_solve.argtypes = [vp, C.POINTER(ArmourSolveOptions), C.POINTER(ArmourSolveResult)]
     L.armour_batch_get_build_ms.argtypes = [vp, dp, dp]
     L.armour_batch_get_build_info.argtypes = [vp, ip]
+    u8p = C.POINTER(C.c_uint8)
+    L.armour_roadmap_create.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, C.c_int32, ip, u8p, C.c_double, C.c_int32, C.POINTER(vp)]
+    L.armour_roadmap_destroy.argtypes = [vp]
+    L.armour_roadmap_destroy.restype = None
+    L.armour_roadmap_get_sizes.argtypes = [vp, ip, ip, C.POINTER(C.c_int64)]
+    L.armour_roadmap_check.argtypes = [vp, C.c_int32, C.c_int32, dp, u8p, u8p, dp, dp]
+    L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
     _lib = L
     return L
 

@@ -1,0 +1,528 @@
+// Roadmap high-level planner (include/armour_hip.h, armour_roadmap_*): node and edge verdicts of a joint-space roadmap against W worlds
+// in one launch, and the host-side search over one world's free graph.  The rule itself (forward kinematics, the 15-plane separation
+// test of a link box and an obstacle, the enlarged midpoint boxes of an edge) is written once below as __host__ __device__ code: the
+// kernel runs it per work item, armour_roadmap_plan runs it on the host for the few edges that join start and goal to the roadmap.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <queue>
+#include <vector>
+
+#include "common.h"
+
+namespace {
+
+constexpr int RM_BLOCK = 256;                 // four waves; a block serves one world (its obstacles are staged in LDS)
+constexpr int RM_OBS_STRIDE = 27;             // doubles per staged obstacle: Z[12], then 3 x {m[3], |m.g_rest|, |m|} of the obstacle pairs
+constexpr double RM_DEGENERATE = 1e-18;       // a normal m = a x b is skipped when |m|^2 <= RM_DEGENERATE |a|^2 |b|^2
+constexpr double RM_PI = 3.141592653589793;
+constexpr double RM_TWO_PI = 6.283185307179586;
+
+// The robot as the rule reads it: frames, link boxes and the displacement bounds rho (passed by value as a kernel argument, ~2.3 KB).
+struct RmRobot {
+    int J, n;
+    int axis[ARMOUR_MAX_JOINTS];                      // signed 1..3, 0 = fixed
+    int cont[ARMOUR_MAX_FACTORS];
+    double T0[ARMOUR_MAX_JOINTS][9];                  // rpy(rots_l), row-major
+    double trans[ARMOUR_MAX_JOINTS][3];
+    double c[ARMOUR_MAX_JOINTS][3], h[ARMOUR_MAX_JOINTS][3];
+    double rho[ARMOUR_MAX_FACTORS][ARMOUR_MAX_JOINTS];  // rho[j][l], j actuated, l >= j (0 otherwise)
+};
+
+__host__ __device__ inline double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__host__ __device__ inline void cross3(const double* a, const double* b, double* m) {
+    m[0] = a[1] * b[2] - a[2] * b[1];
+    m[1] = a[2] * b[0] - a[0] * b[2];
+    m[2] = a[0] * b[1] - a[1] * b[0];
+}
+// C = A B (3x3 row-major), sums left to right -- the order tests/test_roadmap.py restates
+__host__ __device__ inline void matmul3(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+__host__ __device__ inline double wrap_diff(double a, double b) {
+    const double d = b - a;
+    return d - RM_TWO_PI * floor((d + RM_PI) / RM_TWO_PI);
+}
+
+// Obstacle-only part of the rule: the three obstacle x obstacle normals (unnormalised), their |m . g_rest| and |m| (|m| = 0: skipped).
+__host__ __device__ inline void obstacle_normals(const double* Z, double* out /* [15] */) {
+    const double* g[3] = {Z + 3, Z + 6, Z + 9};
+    const int pa[3] = {0, 0, 1}, pb[3] = {1, 2, 2}, rest[3] = {2, 1, 0};
+    for (int p = 0; p < 3; p++) {
+        double* o = out + 5 * p;
+        cross3(g[pa[p]], g[pb[p]], o);
+        const double m2 = dot3(o, o);
+        if (m2 <= RM_DEGENERATE * (dot3(g[pa[p]], g[pa[p]]) * dot3(g[pb[p]], g[pb[p]]))) {
+            o[0] = o[1] = o[2] = o[3] = o[4] = 0.0;
+        } else {
+            o[3] = fabs(dot3(o, g[rest[p]]));
+            o[4] = sqrt(m2);
+        }
+    }
+}
+
+// One link box (centre x, unit axes u[k] = column k of R, half-sizes s) against one staged obstacle.  full = false: true as soon as
+// one plane separates (value > 0; the sign of the numerator is the sign of the value).  full = true: *value = the pair's clearance.
+__host__ __device__ inline bool pair_separated(const double* x, const double (*u)[3], const double* s, const double* ob, bool full,
+                                               double* value) {
+    const double* Z = ob;
+    const double* g[3] = {Z + 3, Z + 6, Z + 9};
+    double d[3] = {x[0] - Z[0], x[1] - Z[1], x[2] - Z[2]};
+    double best = -INFINITY;
+    // obstacle x obstacle
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const double* m = ob + 12 + 5 * p;
+        if (m[4] == 0.0) continue;
+        const double num = fabs(dot3(m, d)) - (m[3] + ((s[0] * fabs(dot3(m, u[0])) + s[1] * fabs(dot3(m, u[1]))) + s[2] * fabs(dot3(m, u[2]))));
+        if (!full) {
+            if (num > 0.0) return true;
+        } else {
+            best = fmax(best, num / m[4]);
+        }
+    }
+    // link x link: the normal is the third axis
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double num = fabs(dot3(u[k], d)) - (((fabs(dot3(u[k], g[0])) + fabs(dot3(u[k], g[1]))) + fabs(dot3(u[k], g[2]))) + s[k]);
+        if (!full) {
+            if (num > 0.0) return true;
+        } else {
+            best = fmax(best, num);
+        }
+    }
+    // obstacle x link
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double ga2 = dot3(g[a], g[a]);
+        const int a1 = a == 0 ? 1 : 0, a2 = a == 2 ? 1 : 2;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            double m[3];
+            cross3(g[a], u[k], m);
+            const double m2 = dot3(m, m);
+            if (m2 <= RM_DEGENERATE * ga2) continue;
+            const int k1 = k == 0 ? 1 : 0, k2 = k == 2 ? 1 : 2;
+            const double num = fabs(dot3(m, d)) - ((fabs(dot3(m, g[a1])) + fabs(dot3(m, g[a2]))) + (s[k1] * fabs(dot3(m, u[k1])) + s[k2] * fabs(dot3(m, u[k2]))));
+            if (!full) {
+                if (num > 0.0) return true;
+            } else {
+                best = fmax(best, num / sqrt(m2));
+            }
+        }
+    }
+    if (full) *value = best;
+    return best > 0.0;
+}
+
+// The rule for one configuration q with per-link enlargement r[l] (all zero for a node) against O staged obstacles (stride
+// RM_OBS_STRIDE); q and r are consumed (shifted).  full = false: returns at the first colliding pair.  full = true: *clearance = min over pairs of the pair clearance.
+__host__ __device__ inline bool config_free(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], const double* obs, int O, bool full,
+                                            double* clearance) {
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+    double cl = INFINITY;
+    bool free_ = true;
+    for (int l = 0; l < rb.J; l++) {
+        double t[3], A[9];
+        for (int i = 0; i < 3; i++) t[i] = (R[3 * i] * rb.trans[l][0] + R[3 * i + 1] * rb.trans[l][1]) + R[3 * i + 2] * rb.trans[l][2];
+        for (int i = 0; i < 3; i++) p[i] = p[i] + t[i];
+        matmul3(R, rb.T0[l], A);
+        const int ax = rb.axis[l];
+        if (ax != 0 && l < rb.n) {
+            const double ql = q[0], c = cos(ql), sn = ax > 0 ? sin(ql) : -sin(ql);
+            const int e = ax > 0 ? ax : -ax;
+            // Rot about x / y / z: {1,0,0; 0,c,-s; 0,s,c}, {c,0,s; 0,1,0; -s,0,c}, {c,-s,0; s,c,0; 0,0,1}
+            const double Q[9] = {e == 1 ? 1.0 : c,          e == 3 ? -sn : 0.0,       e == 2 ? sn : 0.0,
+                                 e == 3 ? sn : 0.0,         e == 2 ? 1.0 : c,         e == 1 ? -sn : 0.0,
+                                 e == 2 ? -sn : 0.0,        e == 1 ? sn : 0.0,        e == 3 ? 1.0 : c};
+            matmul3(A, Q, R);
+        } else {
+            for (int i = 0; i < 9; i++) R[i] = A[i];
+        }
+        double x[3], u[3][3], s[3];
+        const double rl = r[0];
+        // shift q and r down one joint: link l always reads entry 0, so neither array is indexed at run time (no scratch memory)
+#pragma unroll
+        for (int j = 0; j + 1 < ARMOUR_MAX_FACTORS; j++) q[j] = q[j + 1];
+#pragma unroll
+        for (int j = 0; j + 1 < ARMOUR_MAX_JOINTS; j++) r[j] = r[j + 1];
+        for (int i = 0; i < 3; i++) x[i] = p[i] + ((R[3 * i] * rb.c[l][0] + R[3 * i + 1] * rb.c[l][1]) + R[3 * i + 2] * rb.c[l][2]);
+        for (int k = 0; k < 3; k++) {
+            u[k][0] = R[k]; u[k][1] = R[3 + k]; u[k][2] = R[6 + k];
+            s[k] = rb.h[l][k] + rl;
+        }
+        for (int o = 0; o < O; o++) {
+            double v;
+            const bool sep = pair_separated(x, u, s, obs + (size_t)o * RM_OBS_STRIDE, full, &v);
+            if (!full) {
+                if (!sep) return false;
+            } else {
+                cl = fmin(cl, v);
+                free_ = free_ && sep;
+            }
+        }
+    }
+    if (full) *clearance = cl;
+    return free_;
+}
+
+// Sub-segment s of S of the edge a -> b: midpoint configuration and per-link enlargement.
+__host__ __device__ inline void edge_sample(const RmRobot& rb, const double* a, const double* b, int64_t s, int64_t S, double (&q)[ARMOUR_MAX_FACTORS],
+                                            double (&r)[ARMOUR_MAX_JOINTS]) {
+    double D[ARMOUR_MAX_FACTORS];
+    const double t = (double)(2 * s + 1) / (double)(2 * S);
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
+        D[j] = j < rb.n ? (rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j]) : 0.0;
+        q[j] = j < rb.n ? a[j] + t * D[j] : 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < ARMOUR_MAX_FACTORS && j <= l; j++) acc = j < rb.n ? acc + rb.rho[j][l] * fabs(D[j]) : acc;
+        r[l] = acc / (double)(2 * S);
+    }
+}
+
+__host__ __device__ inline int64_t edge_segments(const RmRobot& rb, const double* a, const double* b, double edge_step) {
+    double mx = 0.0;
+    for (int j = 0; j < rb.n; j++) mx = fmax(mx, fabs(rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j]));
+    const double S = ceil(mx / edge_step);
+    return S < 1.0 ? 1 : (int64_t)S;
+}
+
+// One launch: grid (ceil((N + M) / RM_BLOCK), W); item i < N is node i, item N + k is edge sub-segment k (edge sample_edge[k],
+// sub-segment k - edge_off[e]).  edge_free must hold 1 on entry; a colliding sub-segment stores 0 (no atomics: every writer writes 0).
+__global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int32_t N, int64_t M, const double* __restrict__ nodes,
+                                                                  const int32_t* __restrict__ edges, const int64_t* __restrict__ edge_off,
+                                                                  const int32_t* __restrict__ sample_edge, const double* __restrict__ obstacles,
+                                                                  int32_t O, int32_t E, uint8_t* __restrict__ node_free,
+                                                                  uint8_t* __restrict__ edge_free, double* __restrict__ clearance) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+    const int w = blockIdx.y;
+    const double* Zw = obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES;
+    for (int i = threadIdx.x; i < O * ARMOUR_OBS_DOUBLES; i += RM_BLOCK)
+        s_obs[(i / ARMOUR_OBS_DOUBLES) * RM_OBS_STRIDE + i % ARMOUR_OBS_DOUBLES] = Zw[i];
+    for (int o = threadIdx.x; o < O; o += RM_BLOCK) obstacle_normals(Zw + (size_t)o * ARMOUR_OBS_DOUBLES, s_obs + (size_t)o * RM_OBS_STRIDE + 12);
+    __syncthreads();
+    const int64_t item = (int64_t)blockIdx.x * RM_BLOCK + threadIdx.x;
+    if (item >= (int64_t)N + M) return;
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+    const bool is_node = item < N;
+    int e = 0;
+    if (is_node) {
+#pragma unroll
+        for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? nodes[(size_t)item * rb.n + j] : 0.0;
+#pragma unroll
+        for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
+    } else {
+        const int64_t k = item - N;
+        e = sample_edge[k];
+        const int64_t s = k - edge_off[e], S = edge_off[e + 1] - edge_off[e];
+        const int a = edges[2 * e], b = edges[2 * e + 1];
+        edge_sample(rb, nodes + (size_t)a * rb.n, nodes + (size_t)b * rb.n, s, S, q, r);
+    }
+    const bool full = is_node && clearance != nullptr;   // node clearance: no early exit
+    double cl;
+    const bool ok = config_free(rb, q, r, s_obs, O, full, &cl);
+    if (is_node) {
+        node_free[(size_t)w * N + item] = ok ? 1 : 0;
+        if (full) clearance[(size_t)w * N + item] = cl;
+    } else if (!ok) {
+        edge_free[(size_t)w * E + e] = 0;
+    }
+}
+
+void fill_rm_robot(const ArmourRobot* robot, const uint8_t* continuous, RmRobot* rb) {
+    std::memset(rb, 0, sizeof(*rb));
+    rb->J = robot->num_joints;
+    rb->n = robot->num_factors;
+    for (int l = 0; l < rb->J; l++) {
+        rb->axis[l] = robot->axes[l];
+        // rpy(roll, pitch, yaw), the product of armour_amd/robot_geometry.py rpy_matrix
+        const double cr = cos(robot->rots[3 * l]), sr = sin(robot->rots[3 * l]), cp = cos(robot->rots[3 * l + 1]), sp = sin(robot->rots[3 * l + 1]),
+                     cy = cos(robot->rots[3 * l + 2]), sy = sin(robot->rots[3 * l + 2]);
+        const double T0[9] = {cp * cy, -cp * sy, sp,
+                              cr * sy + cy * sp * sr, cr * cy - sp * sr * sy, -cp * sr,
+                              sr * sy - cr * cy * sp, cy * sr + cr * sp * sy, cp * cr};
+        std::memcpy(rb->T0[l], T0, sizeof(T0));
+        for (int i = 0; i < 3; i++) {
+            rb->trans[l][i] = robot->trans[3 * l + i];
+            rb->c[l][i] = robot->link_zonotope_center[3 * l + i];
+            rb->h[l][i] = robot->link_zonotope_generators[3 * l + i];
+        }
+    }
+    for (int j = 0; j < rb->n; j++) rb->cont[j] = continuous ? (continuous[j] != 0) : (robot->continuous[j] != 0);
+    for (int j = 0; j < rb->n; j++)
+        for (int l = j; l < rb->J; l++) {
+            double acc = 0.0;
+            for (int i = j + 1; i <= l; i++) acc += std::sqrt(dot3(rb->trans[i], rb->trans[i]));
+            rb->rho[j][l] = acc + std::sqrt(dot3(rb->c[l], rb->c[l])) + std::sqrt(dot3(rb->h[l], rb->h[l]));
+        }
+}
+
+double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
+    double acc = 0.0;
+    for (int j = 0; j < rb.n; j++) {
+        const double d = rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j];
+        acc += d * d;
+    }
+    return std::sqrt(acc);
+}
+
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t grow(size_t count) {
+        if (count <= n && p) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
+        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+};
+
+}  // namespace
+
+struct ArmourRoadmap {
+    int device = 0;
+    RmRobot rb;
+    int32_t N = 0, E = 0;
+    int64_t M = 0;
+    double edge_step = 0.0;
+    std::vector<double> nodes;           // [N][n]
+    std::vector<int32_t> edges;          // [E][2]
+    DevBuf<double> d_nodes, d_obs, d_clear;
+    DevBuf<int32_t> d_edges, d_sample_edge;
+    DevBuf<int64_t> d_edge_off;
+    DevBuf<uint8_t> d_node_free, d_edge_free;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the last check, on the host
+    int32_t W = -1, O = 0;
+    std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them
+    std::vector<uint8_t> node_free, edge_free;
+    ~ArmourRoadmap() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
+                                     const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
+    if (!robot || !out || (N > 0 && !nodes) || (E > 0 && !edges)) { armour_set_error("armour_roadmap_create: null argument"); return ARMOUR_EINVAL; }
+    *out = nullptr;
+    if (robot->num_factors < 1 || robot->num_factors > ARMOUR_MAX_FACTORS || robot->num_joints < robot->num_factors || robot->num_joints > ARMOUR_MAX_JOINTS) {
+        armour_set_error("armour_roadmap_create: robot has %d joints, %d factors", robot->num_joints, robot->num_factors);
+        return ARMOUR_EINVAL;
+    }
+    if (N < 0 || E < 0 || !(edge_step > 0.0) || !std::isfinite(edge_step)) {
+        armour_set_error("armour_roadmap_create: N = %d, E = %d, edge_step = %g", N, E, edge_step);
+        return ARMOUR_EINVAL;
+    }
+    const int n = robot->num_factors;
+    for (int64_t i = 0; i < (int64_t)N * n; i++)
+        if (!std::isfinite(nodes[i])) { armour_set_error("armour_roadmap_create: node %lld is not finite", (long long)(i / n)); return ARMOUR_EINVAL; }
+    for (int64_t i = 0; i < 2 * (int64_t)E; i++)
+        if (edges[i] < 0 || edges[i] >= N) { armour_set_error("armour_roadmap_create: edge %lld names node %d of %d", (long long)(i / 2), edges[i], N); return ARMOUR_EINVAL; }
+    ArmourRoadmap* rm = new (std::nothrow) ArmourRoadmap();
+    if (!rm) { armour_set_error("armour_roadmap_create: out of host memory"); return ARMOUR_EDEVICE; }
+    std::unique_ptr<ArmourRoadmap> guard(rm);
+    fill_rm_robot(robot, continuous, &rm->rb);
+    rm->device = device;
+    rm->N = N;
+    rm->E = E;
+    rm->edge_step = edge_step;
+    rm->nodes.assign(nodes, nodes + (size_t)N * n);
+    rm->edges.assign(edges, edges + (size_t)2 * E);
+    std::vector<int64_t> off((size_t)E + 1, 0);
+    for (int e = 0; e < E; e++) {
+        off[e + 1] = off[e] + edge_segments(rm->rb, &rm->nodes[(size_t)edges[2 * e] * n], &rm->nodes[(size_t)edges[2 * e + 1] * n], edge_step);
+        if (off[e + 1] + N > INT32_MAX) {
+            armour_set_error("armour_roadmap_create: more than 2^31 - 1 nodes + edge sub-segments (edge_step %g too small)", edge_step);
+            return ARMOUR_ECAPACITY;
+        }
+    }
+    rm->M = off[E];
+    std::vector<int32_t> sample_edge((size_t)rm->M);
+    for (int e = 0; e < E; e++)
+        for (int64_t k = off[e]; k < off[e + 1]; k++) sample_edge[(size_t)k] = e;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&rm->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&rm->ev0));
+    HIPCHK(hipEventCreate(&rm->ev1));
+    HIPCHK(rm->d_nodes.grow(rm->nodes.size()));
+    HIPCHK(rm->d_edges.grow(rm->edges.size()));
+    HIPCHK(rm->d_edge_off.grow(off.size()));
+    HIPCHK(rm->d_sample_edge.grow(sample_edge.size()));
+    if (!rm->nodes.empty()) HIPCHK(hipMemcpy(rm->d_nodes.p, rm->nodes.data(), rm->nodes.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!rm->edges.empty()) HIPCHK(hipMemcpy(rm->d_edges.p, rm->edges.data(), rm->edges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rm->d_edge_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!sample_edge.empty()) HIPCHK(hipMemcpy(rm->d_sample_edge.p, sample_edge.data(), sample_edge.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    *out = guard.release();
+    return ARMOUR_OK;
+}
+
+extern "C" void armour_roadmap_destroy(ArmourRoadmap* rm) {
+    if (!rm) return;
+    (void)hipSetDevice(rm->device);
+    delete rm;
+}
+
+extern "C" int armour_roadmap_get_sizes(const ArmourRoadmap* rm, int32_t* N, int32_t* E, int64_t* edge_samples) {
+    if (!rm) { armour_set_error("armour_roadmap_get_sizes: null handle"); return ARMOUR_EINVAL; }
+    if (N) *N = rm->N;
+    if (E) *E = rm->E;
+    if (edge_samples) *edge_samples = rm->M;
+    return ARMOUR_OK;
+}
+
+extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
+                                    double* node_clearance, double* ms) {
+    if (!rm) { armour_set_error("armour_roadmap_check: null handle"); return ARMOUR_EINVAL; }
+    if (W < 0 || W > 65535 || O < 0 || O > ARMOUR_ROADMAP_MAX_OBSTACLES || (W > 0 && O > 0 && !obstacles)) {
+        armour_set_error("armour_roadmap_check: W = %d (0..65535), O = %d (0..%d)", W, O, ARMOUR_ROADMAP_MAX_OBSTACLES);
+        return ARMOUR_EINVAL;
+    }
+    const size_t nobs = (size_t)W * O * ARMOUR_OBS_DOUBLES;
+    for (size_t i = 0; i < nobs; i++)
+        if (!std::isfinite(obstacles[i])) { armour_set_error("armour_roadmap_check: obstacle %zu is not finite", i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
+    HIPCHK(hipSetDevice(rm->device));
+    const size_t WN = (size_t)W * rm->N, WE = (size_t)W * rm->E;
+    HIPCHK(rm->d_obs.grow(nobs));
+    HIPCHK(rm->d_node_free.grow(WN));
+    HIPCHK(rm->d_edge_free.grow(WE));
+    if (node_clearance) HIPCHK(rm->d_clear.grow(WN));
+    if (nobs) HIPCHK(hipMemcpyAsync(rm->d_obs.p, obstacles, nobs * sizeof(double), hipMemcpyHostToDevice, rm->stream));
+    if (WE) HIPCHK(hipMemsetAsync(rm->d_edge_free.p, 1, WE, rm->stream));
+    const int64_t items = (int64_t)rm->N + rm->M;
+    HIPCHK(hipEventRecord(rm->ev0, rm->stream));
+    if (W > 0 && items > 0) {
+        const dim3 grid((unsigned)((items + RM_BLOCK - 1) / RM_BLOCK), (unsigned)W);
+        const size_t lds = (size_t)O * RM_OBS_STRIDE * sizeof(double);
+        hipLaunchKernelGGL(roadmap_check_kernel, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes.p, rm->d_edges.p,
+                           rm->d_edge_off.p, rm->d_sample_edge.p, rm->d_obs.p, O, rm->E, rm->d_node_free.p, rm->d_edge_free.p,
+                           node_clearance ? rm->d_clear.p : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(rm->ev1, rm->stream));
+    rm->node_free.resize(WN);
+    rm->edge_free.resize(WE);
+    if (WN) HIPCHK(hipMemcpyAsync(rm->node_free.data(), rm->d_node_free.p, WN, hipMemcpyDeviceToHost, rm->stream));
+    if (WE) HIPCHK(hipMemcpyAsync(rm->edge_free.data(), rm->d_edge_free.p, WE, hipMemcpyDeviceToHost, rm->stream));
+    if (node_clearance && WN) HIPCHK(hipMemcpyAsync(node_clearance, rm->d_clear.p, WN * sizeof(double), hipMemcpyDeviceToHost, rm->stream));
+    HIPCHK(hipStreamSynchronize(rm->stream));
+    if (ms) {
+        float f = 0.f;
+        HIPCHK(hipEventElapsedTime(&f, rm->ev0, rm->ev1));
+        *ms = f;
+    }
+    if (node_free && WN) std::memcpy(node_free, rm->node_free.data(), WN);
+    if (edge_free && WE) std::memcpy(edge_free, rm->edge_free.data(), WE);
+    // the obstacles as the kernel staged them, for the host checks of armour_roadmap_plan
+    rm->obs.assign((size_t)W * O * RM_OBS_STRIDE, 0.0);
+    for (size_t o = 0; o < (size_t)W * O; o++) {
+        std::memcpy(&rm->obs[o * RM_OBS_STRIDE], obstacles + o * ARMOUR_OBS_DOUBLES, ARMOUR_OBS_DOUBLES * sizeof(double));
+        obstacle_normals(obstacles + o * ARMOUR_OBS_DOUBLES, &rm->obs[o * RM_OBS_STRIDE + 12]);
+    }
+    rm->W = W;
+    rm->O = O;
+    return ARMOUR_OK;
+}
+
+// the edge rule on the host, for an edge that is not in the roadmap
+static bool host_edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b) {
+    const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+    for (int64_t s = 0; s < S; s++) {
+        edge_sample(rm->rb, a, b, s, S, q, r);
+        if (!config_free(rm->rb, q, r, obs, rm->O, false, nullptr)) return false;
+    }
+    return true;
+}
+
+extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
+                                   int32_t max_points, double* path, int32_t* points) {
+    if (!rm || !q_start || !q_goal || !points || max_points < 0 || (max_points > 0 && !path) || connect_k < 0) {
+        armour_set_error("armour_roadmap_plan: bad argument");
+        return ARMOUR_EINVAL;
+    }
+    *points = 0;
+    if (rm->W < 0) { armour_set_error("armour_roadmap_plan: no armour_roadmap_check yet"); return ARMOUR_ESTATE; }
+    if (w < 0 || w >= rm->W) { armour_set_error("armour_roadmap_plan: world %d of %d", w, rm->W); return ARMOUR_EINVAL; }
+    const int n = rm->rb.n, N = rm->N;
+    for (int j = 0; j < n; j++)
+        if (!std::isfinite(q_start[j]) || !std::isfinite(q_goal[j])) { armour_set_error("armour_roadmap_plan: start / goal not finite"); return ARMOUR_EINVAL; }
+    const double* obs = rm->obs.data() + (size_t)w * rm->O * RM_OBS_STRIDE;
+    const uint8_t* nf = rm->node_free.data() + (size_t)w * N;
+    const uint8_t* ef = rm->edge_free.data() + (size_t)w * rm->E;
+    auto node = [&](int i) -> const double* { return i == N ? q_start : i == N + 1 ? q_goal : &rm->nodes[(size_t)i * n]; };
+    auto emit = [&](const std::vector<int>& seq) -> int {
+        *points = (int32_t)seq.size();
+        if ((int)seq.size() > max_points) {
+            armour_set_error("armour_roadmap_plan: path of %d points, room for %d", (int)seq.size(), max_points);
+            return ARMOUR_ECAPACITY;
+        }
+        for (size_t i = 0; i < seq.size(); i++) std::memcpy(path + i * n, node(seq[i]), n * sizeof(double));
+        return ARMOUR_OK;
+    };
+    if (host_edge_free(rm, obs, q_start, q_goal)) return emit({N, N + 1});
+    // graph: roadmap nodes 0..N-1, start N, goal N+1
+    std::vector<std::vector<std::pair<int, double>>> adj((size_t)N + 2);
+    for (int e = 0; e < rm->E; e++) {
+        if (!ef[e]) continue;
+        const int a = rm->edges[2 * e], b = rm->edges[2 * e + 1];
+        const double len = wrapped_distance(rm->rb, node(a), node(b));
+        adj[a].push_back({b, len});
+        adj[b].push_back({a, len});
+    }
+    for (int end = N; end <= N + 1; end++) {
+        std::vector<std::pair<double, int>> cand;
+        for (int i = 0; i < N; i++)
+            if (nf[i]) cand.push_back({wrapped_distance(rm->rb, node(end), node(i)), i});
+        const size_t k = std::min<size_t>((size_t)connect_k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + k, cand.end());
+        for (size_t c = 0; c < k; c++) {
+            const int i = cand[c].second;
+            if (host_edge_free(rm, obs, node(end), node(i))) {
+                adj[end].push_back({i, cand[c].first});
+                adj[i].push_back({end, cand[c].first});
+            }
+        }
+    }
+    // A* from start to goal; the heuristic (wrapped distance to the goal) is a metric lower bound of every path's length
+    const int s = N, g = N + 1;
+    std::vector<double> dist((size_t)N + 2, INFINITY);
+    std::vector<int> prev((size_t)N + 2, -1);
+    std::vector<char> done((size_t)N + 2, 0);
+    using Ent = std::pair<double, int>;
+    std::priority_queue<Ent, std::vector<Ent>, std::greater<Ent>> open;
+    dist[s] = 0.0;
+    open.push({wrapped_distance(rm->rb, node(s), node(g)), s});
+    while (!open.empty()) {
+        const int v = open.top().second;
+        open.pop();
+        if (done[v]) continue;
+        done[v] = 1;
+        if (v == g) break;
+        for (const auto& nb : adj[v]) {
+            const double d = dist[v] + nb.second;
+            if (d < dist[nb.first]) {
+                dist[nb.first] = d;
+                prev[nb.first] = v;
+                open.push({d + wrapped_distance(rm->rb, node(nb.first), node(g)), nb.first});
+            }
+        }
+    }
+    if (!done[g]) return ARMOUR_OK;   // *points = 0: no path
+    std::vector<int> seq;
+    for (int v = g; v != -1; v = prev[v]) seq.push_back(v);
+    std::reverse(seq.begin(), seq.end());
+    return emit(seq);
+}

@@ -1,0 +1,160 @@
+"""Roadmap high-level planner: a joint-space roadmap checked against worlds' obstacles on the MI355X (include/armour_hip.h,
+armour_roadmap_*), and waypoints through its free graph.
+
+The reference ships this as a prebuilt CUDA binary without source (kinova_samplebased_HLP_realtime/collision_checker: a roadmap of joint
+configurations + an adjacency list in, node feasibility / link_c / the collision-free adjacency out, then a graph search in MATLAB).  Here:
+
+    rm = Roadmap(robot, *uniform_roadmap(20000, 0.3, 16, seed=0, lb=lb, ub=ub, continuous=cont), continuous=cont)
+    v = rm.check(obstacles)                 # [W,O,12] -> node_free [W,N], edge_free [W,E] (+ node_clearance), one launch
+    path = rm.plan(w, q_start, q_goal)      # host A* over world w's free graph, [P,n] (None: no path)
+    hlp = RoadmapHLP(rm, goal); q_des = hlp.get_waypoint(q_cur, lookahead)
+
+The node and edge rules (exact node test, conservative edge test with enlarged boxes) are stated in include/armour_hip.h and DESIGN.md.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .scenes import angdiff, straight_line_waypoint
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def wrapped_diff(a, b, continuous):
+    """b - a, wrapped to [-pi, pi) on continuous joints (the library's formula: d - 2 pi floor((d + pi) / (2 pi)))."""
+    d = np.asarray(b, dtype=np.float64) - np.asarray(a, dtype=np.float64)
+    w = d - 2 * np.pi * np.floor((d + np.pi) / (2 * np.pi))
+    return np.where(np.asarray(continuous, dtype=bool), w, d)
+
+
+def uniform_roadmap(N, radius, k_max, seed, lb, ub, continuous):
+    """N seeded uniform samples within [lb, ub] ([-pi, pi] on continuous joints) and the edges to neighbours within `radius` by wrapped
+    joint distance: every node proposes its k_max nearest such neighbours and the edge set is the union of the proposals (so a node can
+    end up with more than k_max edges).  Returns (nodes [N,n], edges [E,2] int32 with i < j, sorted).  The analogue of the reference's
+    joint_positions_uniform_hardware_dense_rand.csv / adj_matrix_..._range0p3.txt."""
+    cont = np.asarray(continuous, dtype=bool)
+    lo = np.where(cont, -np.pi, np.asarray(lb, dtype=np.float64))
+    hi = np.where(cont, np.pi, np.asarray(ub, dtype=np.float64))
+    rng = np.random.default_rng(seed)
+    nodes = lo + (hi - lo) * rng.random((int(N), cont.size))
+    pairs = []
+    chunk = max(1, 4_000_000 // max(1, int(N)))
+    for i0 in range(0, int(N), chunk):
+        blk = nodes[i0:i0 + chunk]
+        d = wrapped_diff(blk[:, None, :], nodes[None, :, :], cont)
+        dist = np.sqrt((d * d).sum(-1))
+        dist[np.arange(blk.shape[0]), i0 + np.arange(blk.shape[0])] = np.inf
+        k = min(int(k_max), int(N) - 1)
+        if k <= 0:
+            break
+        near = np.argpartition(dist, k - 1, axis=1)[:, :k] if k < int(N) else np.argsort(dist, axis=1)
+        rows = np.repeat(np.arange(i0, i0 + blk.shape[0]), near.shape[1])
+        cols = near.ravel()
+        keep = dist[rows - i0, cols] <= radius
+        pairs.append(np.stack([rows[keep], cols[keep]], axis=1))
+    if not pairs:
+        return nodes, np.zeros((0, 2), dtype=np.int32)
+    e = np.sort(np.concatenate(pairs), axis=1)
+    e = np.unique(e, axis=0)
+    return nodes, np.ascontiguousarray(e, dtype=np.int32)
+
+
+class Roadmap:
+    """A roadmap on one device: nodes [N,n], edges [E,2], the edge rule's step (radians per sub-segment)."""
+
+    def __init__(self, robot, nodes, edges, continuous=None, edge_step=0.05, device=0):
+        self.L = _lib.load()
+        self.robot = robot
+        self.n = robot.num_factors
+        self.nodes = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1, self.n)
+        self.edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        self.continuous = np.array([robot.continuous[j] for j in range(self.n)], dtype=np.uint8) if continuous is None \
+            else np.ascontiguousarray(continuous, dtype=np.uint8).reshape(self.n)
+        self.edge_step = float(edge_step)
+        h = C.c_void_p()
+        check(self.L.armour_roadmap_create(C.byref(robot), self.nodes.shape[0], _dp(self.nodes), self.edges.shape[0],
+                                           self.edges.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           self.continuous.ctypes.data_as(C.POINTER(C.c_uint8)), self.edge_step, device, C.byref(h)))
+        self.h = h
+        N, E, M = C.c_int32(), C.c_int32(), C.c_int64()
+        check(self.L.armour_roadmap_get_sizes(self.h, C.byref(N), C.byref(E), C.byref(M)))
+        self.N, self.E, self.edge_samples = N.value, E.value, M.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.armour_roadmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, obstacles, clearance=False):
+        """obstacles [W,O,12] (or [O,12]: W = 1) -> dict node_free [W,N] bool, edge_free [W,E] bool, ms (device time of the launch),
+        and node_clearance [W,N] when `clearance`."""
+        obs = np.asarray(obstacles, dtype=np.float64)
+        obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+        W, O = obs.shape[0], obs.shape[1]
+        nf = np.zeros((W, self.N), dtype=np.uint8)
+        ef = np.zeros((W, self.E), dtype=np.uint8)
+        cl = np.zeros((W, self.N)) if clearance else None
+        ms = C.c_double()
+        u8 = C.POINTER(C.c_uint8)
+        check(self.L.armour_roadmap_check(self.h, W, O, _dp(obs) if obs.size else None, nf.ctypes.data_as(u8), ef.ctypes.data_as(u8),
+                                          _dp(cl) if clearance else None, C.byref(ms)))
+        out = dict(node_free=nf.astype(bool), edge_free=ef.astype(bool), ms=ms.value)
+        if clearance:
+            out["node_clearance"] = cl
+        return out
+
+    def plan(self, w, start, goal, connect_k=8, max_points=None):
+        """Path [P,n] from start to goal through world w's free graph of the last check (start and goal included), None if none."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(self.n)
+        g = np.ascontiguousarray(goal, dtype=np.float64).reshape(self.n)
+        cap = self.N + 2 if max_points is None else int(max_points)
+        path = np.zeros((cap, self.n))
+        pts = C.c_int32()
+        check(self.L.armour_roadmap_plan(self.h, int(w), _dp(s), _dp(g), int(connect_k), cap, _dp(path), C.byref(pts)))
+        return path[:pts.value].copy() if pts.value else None
+
+
+def waypoint_along(path, q_cur, lookahead, continuous):
+    """The point at arc length `lookahead` from q_cur along the polyline q_cur -> path[1] -> ... (segments wrapped on continuous joints),
+    continued along the last segment past the goal (no clipping, as robot_arm_straight_line_HLP.get_waypoint)."""
+    pts = [np.asarray(q_cur, dtype=np.float64)] + [np.asarray(p, dtype=np.float64) for p in path[1:]]
+    cont = np.asarray(continuous, dtype=bool)
+    rest = float(lookahead)
+    p = pts[0]
+    for i in range(1, len(pts)):
+        d = pts[i] - p                                   # the straight-line rule's arithmetic (scenes.angdiff on continuous joints)
+        d[cont] = angdiff(p[cont], pts[i][cont])
+        L = np.linalg.norm(d)
+        if L == 0.0:
+            continue
+        if rest <= L or i == len(pts) - 1:
+            return p + rest * d / L
+        rest -= L
+        p = p + d
+    return p.copy()
+
+
+class RoadmapHLP:
+    """High-level planner over a checked Roadmap: get_waypoint(q_cur, lookahead) plans q_cur -> goal in world `world` of the last check
+    and returns the point `lookahead` along the path.  A direct free edge gives the straight-line rule's point; with no path it falls
+    back to scenes.straight_line_waypoint, as the reference's HLPs do."""
+
+    def __init__(self, roadmap, goal, world=0, connect_k=8):
+        self.roadmap, self.goal, self.world, self.connect_k = roadmap, np.asarray(goal, dtype=np.float64), int(world), int(connect_k)
+        self.path = None
+
+    def get_waypoint(self, q_cur, lookahead):
+        self.path = self.roadmap.plan(self.world, q_cur, self.goal, connect_k=self.connect_k)
+        if self.path is None:
+            return straight_line_waypoint(q_cur, self.goal, lookahead)
+        return waypoint_along(self.path, q_cur, lookahead, self.roadmap.continuous.astype(bool))

@@ -449,6 +449,63 @@ int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, const doubl
                              const uint64_t* torque_keys, const double* torque_coeffs, int32_t cap_t,
                              const double* A, const double* d, const double* delta, const double* torque_radius);
 
+/* ---- roadmap high-level planner: a joint-space roadmap checked against worlds' obstacles on the device ---- */
+/* What the reference's sample-based HLP does with its prebuilt collision_checker (kinova_samplebased_HLP_realtime): node feasibility,
+ * node clearance and the collision-free subset of a roadmap's edges, per world; then a search of the free graph for waypoints.
+ *
+ * Geometry.  Link l (all num_joints links, fixed trailing ones included) at configuration q is the box
+ *   p_l(q) + R_l(q) (c_l + diag(h_l) beta),  |beta|_inf <= 1,
+ * c_l = link_zonotope_center[l], h_l = link_zonotope_generators[l], and the frames of armour_amd/robot_geometry.py link_frames:
+ *   p_l = p_{l-1} + R_{l-1} trans_l,  R_l = R_{l-1} rpy(rots_l) Rot(axes_l, q_l)   (Rot = identity on a fixed joint).
+ * An obstacle is the usual 12 numbers Z = [c g1 g2 g3].
+ *
+ * Node rule (exact).  For a (link, obstacle) pair, d = (p_l + R_l c_l) - c, the 6 generators are g1..g3 and h_lk u_k (u_k = column k
+ * of R_l), and the 15 plane normals are the cross products of generator pairs (RT/CollisionChecking.cu polytope_PH, applied to a static
+ * box).  For a normal m from the pair (a, b), with the other four generators "rest":
+ *   value(m) = (|m.d| - sum over rest of |m.g|) / |m|          (positive: this plane separates the two)
+ * A link x link pair's normal is the third axis u_k itself (R_l is a rotation), its value |u_k.d| - sum_a |u_k.g_a| - h_lk.
+ * A normal is DEGENERATE and skipped when |m|^2 <= 1e-18 |a|^2 |b|^2 (the sine of the pair's angle <= 1e-9; for an obstacle x link
+ * pair |u_k| = 1 is used): it is rounding noise, or zero for a zero generator.  A zonotope's facets in 3-D are spanned by generator
+ * pairs, so the test is exact up to the facets of the skipped, nearly parallel pairs (a sliver of relative width <= 1e-9).
+ *   pair clearance = max over the used planes of value;  node clearance = min over (link, obstacle) of pair clearance
+ *   (+inf with no obstacle).  The node is FREE iff its clearance > 0.  This is -link_c of the reference (there link_c <= 0 is safe).
+ * A node's verdict does not depend on the order of links or obstacles.
+ *
+ * Edge rule (conservative).  Edge (a, b) is the joint-space segment q(t) = a + t D, t in [0, 1], D = b - a, wrapped on continuous
+ * joints: D_j = d - 2 pi floor((d + pi) / (2 pi)), d = b_j - a_j.  It is cut into S = max(1, ceil(max_j |D_j| / edge_step))
+ * sub-segments; sub-segment s is checked at its midpoint q(t_s), t_s = (2s + 1) / (2S), with every half-size of link l enlarged by
+ *   r_l = (sum over actuated j <= l of rho_{j,l} |D_j|) / (2S),   rho_{j,l} = sum_{i=j+1..l} |trans_i| + |c_l| + |h_l|.
+ * rho_{j,l} bounds the distance from joint j's origin p_j to any point of link l's box, for every configuration (triangle inequality
+ * along the chain).  Soundness: inside sub-segment s every joint is within |D_j|/(2S) of its midpoint value.  Moving the joints there
+ * one at a time, turning joint j by theta turns every point of link l >= j about an axis through p_j, which moves it by at most
+ * rho_{j,l} theta; so every point of link l anywhere on the sub-segment is within r_l of the midpoint box, i.e. inside the box with
+ * half-sizes h_l + r_l.  The edge is FREE iff every enlarged box of every sub-segment is separated (value > 0) from every obstacle,
+ * so no configuration on a free edge collides, and a free edge has free endpoints.
+ *
+ * Device.  armour_roadmap_check runs ONE launch for W worlds: a work item is (world, node) or (world, edge sub-segment); the
+ * sub-segment offsets depend only on the roadmap, robot and edge_step and are built at create time.  fp64 throughout.
+ * Handles are not thread-safe; calls on one handle are synchronous. */
+typedef struct ArmourRoadmap ArmourRoadmap;
+#define ARMOUR_ROADMAP_MAX_OBSTACLES 256   /* 216 B of LDS each: 55 KB per block at the cap */
+/* nodes [N][n] (n = robot->num_factors), edges [E][2] node indices, continuous [n] (1 = wrapped; NULL: robot->continuous),
+ * edge_step > 0 in radians.  ARMOUR_EINVAL on a bad argument, ARMOUR_ECAPACITY when N + (edge sub-segments) exceeds 2^31 - 1. */
+int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
+                          const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out);
+void armour_roadmap_destroy(ArmourRoadmap* rm);
+/* N, E and the total number of edge sub-segments (any pointer may be NULL) */
+int armour_roadmap_get_sizes(const ArmourRoadmap* rm, int32_t* N, int32_t* E, int64_t* edge_samples);
+/* obstacles [W][O][12], O <= ARMOUR_ROADMAP_MAX_OBSTACLES (pad worlds with fewer boxes with far-away ones).  Outputs, each may be NULL:
+ * node_free [W][N] (0/1), edge_free [W][E] (0/1), node_clearance [W][N] (computed only when requested), ms = device time of the
+ * launch.  The handle keeps every world's verdicts and obstacles for armour_roadmap_plan. */
+int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
+                         double* node_clearance, double* ms);
+/* Host search over world w of the last check: the direct start -> goal edge if it is free; else start and goal are joined to their
+ * connect_k nearest free nodes (wrapped joint distance) by edges checked with the edge rule, and A* runs over the free edges with
+ * wrapped-distance weights.  path [max_points][n] = start, nodes..., goal; *points = 0 when there is no path.  ARMOUR_ESTATE before
+ * a check; ARMOUR_ECAPACITY (with *points = the length needed) when max_points is too small. */
+int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
+                        int32_t max_points, double* path, int32_t* points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,77 @@
+"""Throughput of the roadmap check (armour_roadmap_check) and of the host search (armour_roadmap_plan); prints ONE JSON line.
+
+    python tools/roadmap_bench.py [--nodes 20000] [--radius 0.3] [--k-max 16] [--edge-step 0.05] [--reps 10] [--graph-radius 1.5]
+
+Roadmap: armour_amd.roadmap.uniform_roadmap on the Kinova without gripper.  Worlds: the 107 reference worlds (scenes.reference_worlds,
+O padded with scenes.FAR_BOX), all at once (W = 107) and the first alone (W = 1).  Per row: work items (nodes + edge sub-segments) x W,
+kernel ms (median of `reps` launches, the ms of armour_roadmap_check), checks/s = items x W / kernel time, and the upper bound on
+plane tests per launch (items x W x links x O x 15; the early exit at the first colliding pair does fewer).  With 7 joints a radius of
+0.3 joins almost no pair of 20 000 uniform samples, so a second roadmap with --graph-radius is measured as well; its plan_ms is the
+median host time of armour_roadmap_plan between random free start / goal nodes of world 0."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def measure(robot, nodes, edges, cont, obs, edge_step, reps):
+    from armour_amd.roadmap import Roadmap
+    rm = Roadmap(robot, nodes, edges, continuous=cont, edge_step=edge_step)
+    J, O = robot.num_joints, obs.shape[1]
+    rows = {}
+    for W in (obs.shape[0], 1):
+        rm.check(obs[:W])                                   # warm-up (module load, buffers)
+        ms = sorted(rm.check(obs[:W])["ms"] for _ in range(reps))
+        kms = ms[len(ms) // 2]
+        items = (rm.N + rm.edge_samples) * W
+        rows["W=%d" % W] = dict(kernel_ms=round(kms, 4), kernel_ms_min=round(ms[0], 4), items=items,
+                                checks_per_s=round(items / (kms * 1e-3)), plane_tests_max=items * J * O * 15)
+    v = rm.check(obs)
+    free = np.flatnonzero(v["node_free"][0])
+    rng = np.random.default_rng(0)
+    plan_ms, found = [], 0
+    for _ in range(20 if free.size >= 2 else 0):
+        a, b = rng.choice(free, 2, replace=False)
+        t0 = time.perf_counter()
+        p = rm.plan(0, nodes[a], nodes[b], connect_k=8)
+        plan_ms.append((time.perf_counter() - t0) * 1e3)
+        found += p is not None
+    out = dict(N=rm.N, E=rm.E, edge_samples=rm.edge_samples, O=O, links=J, **rows)
+    if plan_ms:
+        out.update(plan_ms=round(float(np.median(plan_ms)), 3), plans_found=f"{found}/{len(plan_ms)}")
+    rm.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=20000)
+    ap.add_argument("--radius", type=float, default=0.3)
+    ap.add_argument("--graph-radius", type=float, default=1.5)
+    ap.add_argument("--k-max", type=int, default=16)
+    ap.add_argument("--edge-step", type=float, default=0.05)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    from armour_amd.planner import kinova_robot
+    from armour_amd.roadmap import uniform_roadmap
+    from armour_amd.scenes import as_batch, reference_worlds
+    robot = kinova_robot()
+    n = robot.num_factors
+    cont = np.array(robot.continuous[:n]).astype(bool)
+    lb, ub = np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n])
+    obs = np.ascontiguousarray(as_batch(reference_worlds())["obstacles"])
+    res = dict(tool="roadmap_bench", robot="kinova_gen3_no_gripper", worlds=obs.shape[0], edge_step=a.edge_step)
+    for key, radius in (("radius_%g" % a.radius, a.radius), ("radius_%g" % a.graph_radius, a.graph_radius)):
+        nodes, edges = uniform_roadmap(a.nodes, radius, a.k_max, 0, lb, ub, cont)
+        res[key] = measure(robot, nodes, edges, cont.astype(np.uint8), obs, a.edge_step, a.reps)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
