@@ -13,6 +13,7 @@
 #include "bezier.h"
 #include "cacc.h"
 #include "common.h"
+#include "solver_common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -517,27 +518,28 @@ int armour_checked_collision_rows(const ArmourPlanner* h) {
     return h->mode == ARMOUR_MODE_ARMTD ? (h->n - 1 < h->J ? h->n - 1 : h->J) * h->T * h->O : h->Q;
 }
 
-static double wrap_to_pi(double a) {
-    const double pi = 3.14159265358979323846;
-    while (a < -pi) a += 2 * pi;
-    while (a > pi) a -= 2 * pi;
-    return a;
+// joint i's coefficients of problem b for the plan point (solver_common.h slv::plan_point)
+static void plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]) {
+    const double D = h->params.duration;
+    const bool armtd = h->mode == ARMOUR_MODE_ARMTD;  // CMP/NLPclass.cu:183-243
+    c[0] = h->h_q0[ix];
+    c[1] = armtd ? h->h_qd0[ix] : h->h_qd0[ix] * D;
+    c[2] = armtd ? h->h_krange[ix] : h->h_qdd0[ix] * D * D;
 }
 
 extern "C" int armour_eval_f(ArmourPlanner* h, const double* k, double* f) {
     NEED_READY(h);
     const int n = h->n;
-    const double D = h->params.duration;
     for (int b = 0; b < h->B; b++) {
         double obj = 0;
-        for (int pass = 0; pass < 2; pass++)  // continuous joints first, as RT/NLPclass.cu:225-231 sums them
+        for (int pass = 0; pass < 2; pass++)  // continuous joints first (solver_common.h)
             for (int i = 0; i < n; i++) {
                 if ((h->robot.continuous[i] != 0) != (pass == 0)) continue;
                 const size_t ix = (size_t)b * n + i;
-                const double qp = h->mode == ARMOUR_MODE_ARMTD  // CMP/NLPclass.cu:183-212
-                                      ? cacc::q_plan(h->h_q0[ix], h->h_qd0[ix], h->h_krange[ix], k[ix])
-                                      : bez::q_des(h->h_q0[ix], h->h_qd0[ix] * D, h->h_qdd0[ix] * D * D, h->params.k_range[i] * k[ix], h->params.t_plan);
-                const double e = h->robot.continuous[i] ? wrap_to_pi(h->h_qdes[ix] - qp) : (h->h_qdes[ix] - qp);
+                double c[3];
+                plan_coeffs(h, ix, c);
+                const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], h->params.t_plan);
+                const double e = h->robot.continuous[i] ? slv::wrap_to_pi(h->h_qdes[ix] - qp) : (h->h_qdes[ix] - qp);
                 obj += e * e;
             }
         f[b] = obj * h->params.cost_scale;
@@ -548,15 +550,15 @@ extern "C" int armour_eval_f(ArmourPlanner* h, const double* k, double* f) {
 extern "C" int armour_eval_grad_f(ArmourPlanner* h, const double* k, double* grad_f) {
     NEED_READY(h);
     const int n = h->n;
-    const double D = h->params.duration, tp = h->params.t_plan;
+    const double tp = h->params.t_plan;
     for (int b = 0; b < h->B; b++)
         for (int i = 0; i < n; i++) {
             const size_t ix = (size_t)b * n + i;
-            const bool armtd = h->mode == ARMOUR_MODE_ARMTD;  // CMP/NLPclass.cu:217-243
-            const double qp = armtd ? cacc::q_plan(h->h_q0[ix], h->h_qd0[ix], h->h_krange[ix], k[ix])
-                                    : bez::q_des(h->h_q0[ix], h->h_qd0[ix] * D, h->h_qdd0[ix] * D * D, h->params.k_range[i] * k[ix], tp);
-            const double dk = armtd ? cacc::q_plan_dk(h->h_krange[ix]) : (tp * tp * tp) * (6 * tp * tp - 15 * tp + 10) * h->params.k_range[i];
-            const double e = h->robot.continuous[i] ? wrap_to_pi(qp - h->h_qdes[ix]) : (qp - h->h_qdes[ix]);
+            double c[3];
+            plan_coeffs(h, ix, c);
+            const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], tp);
+            const double dk = slv::plan_dk(h->mode, c[2], h->params.k_range[i], tp);
+            const double e = h->robot.continuous[i] ? slv::wrap_to_pi(qp - h->h_qdes[ix]) : (qp - h->h_qdes[ix]);
             grad_f[ix] = 2 * e * dk * h->params.cost_scale;
         }
     return ARMOUR_OK;
@@ -666,9 +668,7 @@ extern "C" int armour_eval_g_jac_device_multi(ArmourPlanner* h, const double* d_
                             points, bn, bm, bm * h->n);
 }
 
-static int spin_on_stream(hipStream_t st) {
-    // spin on the stream instead of sleeping in hipStreamSynchronize: the whole call is tens of microseconds and an
-    // interrupt-driven wake-up would dominate it
+int armour_spin_on_stream(hipStream_t st) {
     for (;;) {
         const hipError_t q = hipStreamQuery(st);
         if (q == hipSuccess) return ARMOUR_OK;
@@ -693,7 +693,7 @@ extern "C" int armour_eval_g_jac(ArmourPlanner* h, const double* k, double* g, d
     if (all_pinned && pinned_mode == 1) {
         int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), k, g, jac, h->stream);
         if (rc != ARMOUR_OK) return rc;
-        return spin_on_stream(h->stream);
+        return armour_spin_on_stream(h->stream);
     }
     const double* k_dev = h->d_k;
     if (all_pinned && pinned_mode == 2) k_dev = k;
@@ -702,11 +702,11 @@ extern "C" int armour_eval_g_jac(ArmourPlanner* h, const double* k, double* g, d
     if (rc != ARMOUR_OK) return rc;
     if (g && jac && jac == g + bm) {   // the caller's g and jac are one block (as the device copies are): one transfer instead of two
         HIPCHK(hipMemcpyAsync(g, h->d_g, bm * (1 + (size_t)h->n) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        return spin_on_stream(h->stream);
+        return armour_spin_on_stream(h->stream);
     }
     if (g) HIPCHK(hipMemcpyAsync(g, h->d_g, bm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (jac) HIPCHK(hipMemcpyAsync(jac, h->d_jac, bm * h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    return spin_on_stream(h->stream);
+    return armour_spin_on_stream(h->stream);
 }
 
 extern "C" int armour_check_feasible(ArmourPlanner* h, const double* g, int32_t* feasible) {
@@ -961,7 +961,7 @@ extern "C" int armour_eval_violations(ArmourPlanner* h, const double* k, ArmourV
     int rc = eval_violations_device_impl(h, h->d_k, h->d_viol, h->stream, in_box);
     if (rc != ARMOUR_OK) return rc;
     HIPCHK(hipMemcpyAsync(hv, h->d_viol, (size_t)h->B * sizeof(ArmourViolation), hipMemcpyDeviceToHost, h->stream));
-    rc = spin_on_stream(h->stream);
+    rc = armour_spin_on_stream(h->stream);
     if (rc != ARMOUR_OK) return rc;
     memcpy(out, hv, (size_t)h->B * sizeof(ArmourViolation));
     return ARMOUR_OK;

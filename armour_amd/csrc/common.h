@@ -62,6 +62,21 @@ __host__ __device__ inline size_t armour_plane_ll_index(int JT, int lt, int pll,
         }                                                                                                \
     } while (0)
 
+// a device buffer of at least `need` elements (`fresh`, if given: set when it was allocated anew)
+template <class Tp>
+inline int grow(Tp** p, size_t* cap, size_t need, bool* fresh = nullptr) {
+    if (need <= *cap && *p) return ARMOUR_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    HIPCHK(hipMalloc((void**)p, (need ? need : 1) * sizeof(Tp)));
+    *cap = need;
+    if (fresh) *fresh = true;
+    return ARMOUR_OK;
+}
+
+// spin on hipStreamQuery instead of sleeping in hipStreamSynchronize: the calls that wait are tens of microseconds (api.hip)
+int armour_spin_on_stream(hipStream_t st);
+
 // Reach-set tables of B problems as the P2 kernel reads them (all device pointers).
 //
 // Final link / torque PZs hold only k-dependent monomials (key < 2^(2n)); keys are stored as u32.

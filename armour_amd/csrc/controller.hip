@@ -244,16 +244,6 @@ struct CtlCache {
 };
 thread_local CtlCache g_ctl;
 
-// spin on the stream instead of sleeping in hipStreamSynchronize: a small call is tens of microseconds and an
-// interrupt-driven wake-up would dominate it (same reasoning as armour_eval_g_jac)
-int ctl_wait(hipStream_t st) {
-    for (;;) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) return ARMOUR_OK;
-        if (q != hipErrorNotReady) { armour_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return ARMOUR_EDEVICE; }
-    }
-}
-
 constexpr int kSplitMaxStates = kSplitStates * 256;   // up to one four-wave block per CU
 constexpr size_t kStagedDoubles = (size_t)1 << 20;  // calls up to this many input doubles go through the page-locked buffer
 
@@ -336,7 +326,7 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
     int st = 0;
     if (staged) {
         HIPCHK(hipMemcpyAsync(c.h_pin + 5 * bn, d_out, (3 * bn + 1) * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-        if (ctl_wait(c.stream) != ARMOUR_OK) return ARMOUR_EDEVICE;
+        if (armour_spin_on_stream(c.stream) != ARMOUR_OK) return ARMOUR_EDEVICE;
         for (int k = 0; k < 3; k++) memcpy(out[k], c.h_pin + (5 + (size_t)k) * bn, bn * sizeof(double));
         memcpy(&st, c.h_pin + 8 * bn, sizeof(int));
     } else {

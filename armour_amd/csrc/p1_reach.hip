@@ -1868,18 +1868,6 @@ void armour_p1_free(ArmourPlanner* h) {
     h->p1 = nullptr;
 }
 
-// a device buffer of at least `need` elements (`fresh`, if given: set when it was allocated anew)
-template <class Tp>
-static int grow(Tp** p, size_t* cap, size_t need, bool* fresh = nullptr) {
-    if (need <= *cap && *p) return ARMOUR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    HIPCHK(hipMalloc((void**)p, (need ? need : 1) * sizeof(Tp)));
-    *cap = need;
-    if (fresh) *fresh = true;
-    return ARMOUR_OK;
-}
-
 // the centres / radii a block keeps in LDS (p1_shared_lds)
 static size_t ci_doubles(const Layout& L) { return (size_t)L.nV * 9 + kNS * 3 + kNM * 27 + (size_t)L.nJM * 27 + (size_t)L.nJV * 9 + (size_t)L.nJS * 3; }
 

@@ -1,13 +1,38 @@
 // Pieces shared by the two forms of armour_solve (solver.hip: QPs on the host; solver_device.hip: the whole SQP iterate
-// in one persistent kernel): the candidate-row record, the row filter, and the fixed-point violation sum.
+// in one persistent kernel): the cost's per-joint rule (also api.hip's armour_eval_f / _grad_f), the candidate-row record,
+// the row filter, and the fixed-point violation sum.
 #pragma once
 #include <cmath>
 
+#include "bezier.h"
+#include "cacc.h"
 #include "common.h"
 
 namespace slv {
 
 constexpr int NV = ARMOUR_MAX_FACTORS;
+
+// ---- the cost f = cost_scale * sum_i e_i^2, e_i = q_des_i - plan point of joint i (RT/NLPclass.cu:207-267, ARMTD mode CMP/NLPclass.cu:183-243) ----
+// Both forms of the solver and armour_eval_f / _grad_f use this arithmetic: the forms agree bit for bit only while they share it.  A continuous
+// joint's error is wrapped to [-pi, pi], and the sum takes the continuous joints first, then the others (RT/NLPclass.cu:225-231).
+__host__ __device__ inline double wrap_to_pi(double a) {  // RT/NLPclass.cu:6-15
+    const double pi = 3.14159265358979323846;
+    while (a < -pi) a += 2 * pi;
+    while (a > pi) a -= 2 * pi;
+    return a;
+}
+// c0, c1, c2 = q0, qd0 * duration, qdd0 * duration^2; ARMTD mode: q0, qd0 and the problem's own k_range_i (k_range_i is then not read).
+// (solver_device.hip writes these two out in its own plan_point / plan_dk)
+__host__ __device__ inline double plan_point(int mode, double c0, double c1, double c2, double k_range_i, double k, double tp) {
+    return mode == ARMOUR_MODE_ARMTD ? cacc::q_plan(c0, c1, c2, k) : bez::q_des(c0, c1, c2, k_range_i * k, tp);
+}
+__host__ __device__ inline double plan_dk(int mode, double c2, double k_range_i, double tp) {  // d plan_point / dk
+    return mode == ARMOUR_MODE_ARMTD ? cacc::q_plan_dk(c2) : (tp * tp * tp) * (6 * tp * tp - 15 * tp + 10) * k_range_i;
+}
+__host__ __device__ inline double hess_diag(double cost_scale, double dk) {  // the cost's constant Hessian entry, floored: G stays positive definite
+    const double Hd = 2.0 * cost_scale * dk * dk;
+    return Hd < 1e-12 ? 1e-12 : Hd;
+}
 
 // One inequality a'd >= v of the QP as the scan hands it over: row `idx` of g, side 0 = upper bound (a = -J_i,
 // v = g_i - hi_i), side 1 = lower bound (a = J_i, v = lo_i - g_i).  v > 0 means violated at the linearisation point.

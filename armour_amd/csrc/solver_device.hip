@@ -85,19 +85,15 @@ __device__ inline void tile_info(const SolveArgs& a, int t, int& role, int& r0, 
     else { role = nbc + nbt; r0 = row0 + a.tb.Q; r1 = a.tb.m; }
 }
 
-__device__ inline double wrap_to_pi_dev(double x) {  // RT/NLPclass.cu:6-15
-    const double pi = 3.14159265358979323846;
-    while (x < -pi) x += 2 * pi;
-    while (x > pi) x -= 2 * pi;
-    return x;
-}
-// eval_f / eval_grad_f (RT/NLPclass.cu:207-267, CMP/NLPclass.cu:183-243): the expressions of api.hip armour_eval_f / _grad_f
+// eval_f / eval_grad_f: the per-joint rule of solver_common.h on this problem's coefficients (bz: [3][n], common.h P2Tables::bez).
+// plan_point and plan_dk repeat slv::plan_point / slv::plan_dk expression for expression instead of calling them: those read every operand
+// before the mode test, and this kernel's instructions then come out scheduled differently.  Change them together.
 __device__ inline double plan_point(const SolveArgs& a, const double* bz, int i, double k) {
     const int n = a.tb.n;
     return a.tb.mode == ARMOUR_MODE_ARMTD ? cacc::q_plan(bz[i], bz[n + i], bz[2 * n + i], k)
                                           : bez::q_des(bz[i], bz[n + i], bz[2 * n + i], a.tb.k_range[i] * k, a.t_plan);
 }
-// eval_f from the joints' squared errors, added in armour_eval_f's order (continuous joints first)
+// eval_f from the joints' squared errors, added in the order of solver_common.h (continuous joints first)
 __device__ inline double cost_sum(const SolveArgs& a, const double* sq) {
     double obj = 0;
     for (int pass = 0; pass < 2; pass++)
@@ -746,9 +742,9 @@ __device__ __forceinline__ int leader_step(const SolveArgs& a, Leader& L, QpShar
     if (tid < n) {   // the squared error of each joint (eval_f) and eval_grad_f at that point
         const bool cont = (a.continuous_mask >> tid) & 1;
         const double qp = plan_point(a, L.bz, tid, pt[tid]);
-        const double eg = cont ? wrap_to_pi_dev(qp - L.qdes[tid]) : (qp - L.qdes[tid]);
+        const double eg = cont ? wrap_to_pi(qp - L.qdes[tid]) : (qp - L.qdes[tid]);
         L.np[tid] = 2 * eg * plan_dk(a, L.bz, tid) * a.cost_scale;   // (np / z double as scratch between QPs)
-        const double e = cont ? wrap_to_pi_dev(L.qdes[tid] - qp) : (L.qdes[tid] - qp);
+        const double e = cont ? wrap_to_pi(L.qdes[tid] - qp) : (L.qdes[tid] - qp);
         L.z[tid] = e * e;
     }
     __syncthreads();
@@ -934,8 +930,7 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(WPS, W
             double Hd = 1e-12;
             if (j < n) {
                 const double dk = plan_dk(a, L.bz, j);
-                Hd = 2.0 * a.cost_scale * dk * dk;   // constant diagonal Hessian of the cost
-                if (Hd < 1e-12) Hd = 1e-12;
+                Hd = hess_diag(a.cost_scale, dk);   // constant diagonal Hessian of the cost (dk first: the order of the loads shapes this kernel's schedule)
             }
             L.Hd[j] = Hd;
         }
