@@ -61,6 +61,24 @@ class ArmourSolveResult(C.Structure):
                 ("iterations", C.c_int32), ("evaluations", C.c_int32), ("status", C.c_int32), ("time_ms", C.c_double)]
 
 
+class ArmourTrackOptions(C.Structure):
+    _fields_ = [("controller", C.c_int32), ("record_every", C.c_int32), ("steps_per_launch", C.c_int32), ("reserved0", C.c_int32),
+                ("Kr", C.c_double * MAXF), ("alpha", C.c_double), ("V_max", C.c_double), ("r_norm_threshold", C.c_double),
+                ("model_uncertainty", C.c_double), ("dt", C.c_double), ("t0", C.c_double), ("t1", C.c_double), ("duration", C.c_double),
+                ("reserved", C.c_double * 4)]
+
+
+class ArmourTrackResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("steps", C.c_int32), ("limit_flags", C.c_int32), ("reserved", C.c_int32),
+                ("t_end", C.c_double), ("q", C.c_double * MAXF), ("qd", C.c_double * MAXF),
+                ("max_pos_error", C.c_double), ("max_vel_error", C.c_double), ("max_V", C.c_double), ("max_robust_input", C.c_double),
+                ("max_torque_ratio", C.c_double), ("first_violation_t", C.c_double)]
+
+
+TRACK_CTL_ROBUST, TRACK_CTL_NOMINAL, TRACK_CTL_NONE = 0, 1, 2   # ARMOUR_TRACK_CTL_*
+TRACK_LIMIT_TORQUE, TRACK_LIMIT_POSITION, TRACK_LIMIT_SPEED = 1, 2, 4   # ARMOUR_TRACK_LIMIT_*
+
+
 class ArmourViolation(C.Structure):
     _fields_ = [("l1_violation", C.c_double), ("worst", C.c_double), ("worst_row", C.c_int32), ("n_violated", C.c_int32),
                 ("n_outside_slack", C.c_int32), ("feasible", C.c_int32)]
@@ -122,6 +140,7 @@ EXPORTS = [
     "armour_batch_get_sizes", "armour_batch_get_bounds", "armour_batch_eval_g_jac", "armour_batch_eval_violations", "armour_batch_solve",
     "armour_batch_get_build_ms", "armour_batch_get_build_info",
     "armour_roadmap_create", "armour_roadmap_destroy", "armour_roadmap_get_sizes", "armour_roadmap_check", "armour_roadmap_plan",
+    "armour_track_options_default", "armour_track", "armour_track_auto_steps",
 ]
 
 _lib = None
@@ -247,6 +266,11 @@ def load():
     L.armour_roadmap_get_sizes.argtypes = [vp, ip, ip, C.POINTER(C.c_int64)]
     L.armour_roadmap_check.argtypes = [vp, C.c_int32, C.c_int32, dp, u8p, u8p, dp, dp]
     L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
+    L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
+    L.armour_track_options_default.restype = None
+    L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,
+                               C.POINTER(ArmourTrackResult), dp, dp]
+    L.armour_track_auto_steps.argtypes = [C.c_int32]
     _lib = L
     return L
 

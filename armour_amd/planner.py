@@ -274,6 +274,7 @@ class ArmourNLP:
                 raise ValueError(f"expected shape ({B},{self.n}), got {a.shape}")
         self._obs = obs
         check(self.L.armour_set_problems(self.h, B, O, _dp(q0), _dp(qd0), _dp(qdd0), _dp(q_des), _dp(obs) if O else None))
+        self.problem = dict(q0=q0.copy(), qd0=qd0.copy(), qdd0=qdd0.copy(), q_des=q_des.copy())   # (for armour_amd.tracking.simulate_plans)
         self._after_set(B, O)
         return self
 
@@ -292,6 +293,7 @@ class ArmourNLP:
             if a.shape != (B, self.n):
                 raise ValueError(f"expected shape ({B},{self.n}), got {a.shape}")
         self._obs = obs
+        self.problem = None   # (a constant-acceleration plan: nothing for armour_amd.tracking.simulate_plans)
         check(self.L.armour_set_problems_armtd(self.h, B, O, _dp(q0), _dp(qd0), _dp(q_des), _dp(jrs), _dp(k_range), _dp(obs) if O else None))
         self._after_set(B, O)
         return self

@@ -1,0 +1,164 @@
+"""Closed-loop tracking on the device: the planner's Bezier plan executed by an arm with uncertain masses and inertias under the
+tracking controller (armour_track, include/armour_hip.h).
+
+    res = simulate_tracking(robot, q0, qd0, qdd0, k, k_range, duration, ...)   # B rollouts, numpy in / numpy out
+    s_m, s_I = plant_samples(robot, B, uncertainty, rng)                       # true plants within +-uncertainty
+    runs = simulate_plans(nlp, nlp.solve(), samples=8, rng=rng)                # every feasible plan of an ArmourNLP
+    summary = compare_robust_controller(levels, samples, seed)                 # kinova_compare_robust_controller.m
+
+The reference integrates one rollout at a time with ode15s and the controller MEX in the right-hand side
+(KSI/uarmtd_agent.m:280-293, :360-405); here every rollout is a device lane running fixed-step RK4, all arithmetic in libarmour_hip.so.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import ArmourTrackOptions, ArmourTrackResult, check
+from .planner import kinova_robot
+
+CONTROLLERS = {"robust": _lib.TRACK_CTL_ROBUST, "nominal": _lib.TRACK_CTL_NOMINAL, "none": _lib.TRACK_CTL_NONE}
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def ultimate_bound(robot, V_max=None, Kr=None):
+    """(ub, qe, qde) of KSI/uarmtd_robust_CBF_LLC.m:36-40: ub = sqrt(2 V_max / M_min), qe = ub / min(Kr), qde = 2 ub."""
+    V_max = robot.V_m if V_max is None else V_max
+    kr = robot.K if Kr is None else float(np.min(Kr))
+    ub = float(np.sqrt(2 * V_max / robot.M_min))
+    return ub, ub / kr, 2 * ub
+
+
+def default_options(robot):
+    opt = ArmourTrackOptions()
+    _lib.load().armour_track_options_default(C.byref(robot), C.byref(opt))
+    return opt
+
+
+@dataclass
+class TrackResult:
+    """Per rollout ([B] / [B, n]): status (0 reached t1, 1 nominal torque outside the interval torque, 2 non-finite state), steps,
+    limit_flags (bit 0 torque, 1 position, 2 speed), t_end, the last node's q / qd, the running maxima, first_violation_t (NaN: none);
+    trace [B, nodes, 3, n] (q, qd, u per recorded node) or None; device_ms of the call."""
+    status: np.ndarray
+    steps: np.ndarray
+    limit_flags: np.ndarray
+    t_end: np.ndarray
+    q: np.ndarray
+    qd: np.ndarray
+    max_pos_error: np.ndarray
+    max_vel_error: np.ndarray
+    max_V: np.ndarray
+    max_robust_input: np.ndarray
+    max_torque_ratio: np.ndarray
+    first_violation_t: np.ndarray
+    trace: np.ndarray
+    device_ms: float
+
+
+def simulate_tracking(robot, q0, qd0, qdd0, k, k_range, duration, t0=0.0, t1=None, dt=1e-3, controller="robust", z0=None,
+                      mass_scale=None, inertia_scale=None, Kr=None, alpha=None, V_max=None, r_norm_threshold=None, model_uncertainty=None,
+                      record_every=0, steps_per_launch=0):
+    """B rollouts of armour_track.  q0 / qd0 / qdd0 / k: [B, n] (or [n]); k_range: [n]; z0: [B, 2n] actual (q, qd) at t0 or None (on the
+    reference); mass_scale / inertia_scale: [B, n] or None.  Controller constants default to armour_track_options_default (the robot's)."""
+    L = _lib.load()
+    robot = robot if robot is not None else kinova_robot()
+    n = robot.num_factors
+    q0, qd0, qdd0, k = [np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (q0, qd0, qdd0, k)]
+    B = q0.shape[0]
+    for a in (q0, qd0, qdd0, k):
+        if a.shape != (B, n):
+            raise ValueError(f"expected shape ({B},{n}), got {a.shape}")
+    k_range = np.ascontiguousarray(np.broadcast_to(np.asarray(k_range, dtype=np.float64), (n,)))
+    z0 = None if z0 is None else np.ascontiguousarray(np.asarray(z0, dtype=np.float64).reshape(B, 2 * n))
+    sm = None if mass_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mass_scale, dtype=np.float64), (B, n)))
+    sI = None if inertia_scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(inertia_scale, dtype=np.float64), (B, n)))
+    opt = default_options(robot)
+    opt.controller = CONTROLLERS[controller] if isinstance(controller, str) else int(controller)
+    opt.record_every, opt.steps_per_launch = int(record_every), int(steps_per_launch)
+    if Kr is not None:
+        kr = np.broadcast_to(np.asarray(Kr, dtype=np.float64), (n,))
+        for i in range(n):
+            opt.Kr[i] = kr[i]
+    for name, val in (("alpha", alpha), ("V_max", V_max), ("r_norm_threshold", r_norm_threshold), ("model_uncertainty", model_uncertainty)):
+        if val is not None:
+            setattr(opt, name, float(val))
+    opt.dt, opt.t0, opt.duration = float(dt), float(t0), float(duration)
+    opt.t1 = float(duration if t1 is None else t1)
+    N = int(np.ceil((opt.t1 - opt.t0) / opt.dt - 1e-9)) if opt.dt > 0 and opt.t1 > opt.t0 else 0
+    trace = np.zeros((B, N // record_every + 1, 3, n)) if record_every > 0 and N > 0 else None
+    res = (ArmourTrackResult * B)()
+    ms = C.c_double(0.0)
+    check(L.armour_track(C.byref(robot), C.byref(opt), B, _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range), _dp(z0), _dp(sm), _dp(sI),
+                         res, _dp(trace), C.byref(ms)))
+    f = lambda name: np.array([getattr(r, name) for r in res])
+    return TrackResult(status=f("status"), steps=f("steps"), limit_flags=f("limit_flags"), t_end=f("t_end"),
+                       q=np.array([r.q[:n] for r in res]), qd=np.array([r.qd[:n] for r in res]),
+                       max_pos_error=f("max_pos_error"), max_vel_error=f("max_vel_error"), max_V=f("max_V"),
+                       max_robust_input=f("max_robust_input"), max_torque_ratio=f("max_torque_ratio"),
+                       first_violation_t=f("first_violation_t"), trace=trace, device_ms=ms.value)
+
+
+def plant_samples(robot, B, uncertainty, rng):
+    """Per-body mass and inertia scales of B true plants, uniform in [-uncertainty, +uncertainty] and drawn independently: ([B, n], [B, n])."""
+    n = robot.num_factors
+    return rng.uniform(-uncertainty, uncertainty, (B, n)), rng.uniform(-uncertainty, uncertainty, (B, n))
+
+
+def simulate_plans(nlp, solve_results, samples, rng, uncertainty=None, **kw):
+    """Execute every feasible plan of an ArmourNLP (the problems of its last set_parameters, the k_opt of `solve_results`) over
+    [0, duration] on `samples` true plants each within +-uncertainty (default: the robot's mass_uncertainty), with the robot's
+    controller constants.  Returns dict(problems [P] indices of the simulated problems, skipped [..] the infeasible ones,
+    result: TrackResult over P * samples rollouts, problem-major)."""
+    prob = getattr(nlp, "problem", None)
+    if prob is None:
+        raise ValueError("simulate_plans needs an ArmourNLP after set_parameters")
+    robot, params = nlp.robot, nlp.params
+    n = robot.num_factors
+    eps = robot.mass_uncertainty if uncertainty is None else uncertainty
+    feasible = [b for b, r in enumerate(solve_results) if r["feasible"]]
+    skipped = [b for b, r in enumerate(solve_results) if not r["feasible"]]
+    if not feasible:
+        return dict(problems=[], skipped=skipped, result=None)
+    idx = np.repeat(np.array(feasible), samples)
+    k = np.stack([solve_results[b]["k_opt"] for b in idx])
+    sm, sI = plant_samples(robot, len(idx), eps, rng)
+    res = simulate_tracking(robot, prob["q0"][idx], prob["qd0"][idx], prob["qdd0"][idx], k, np.array(params.k_range[:n]), params.duration,
+                            mass_scale=sm, inertia_scale=sI, **kw)
+    return dict(problems=feasible, skipped=skipped, result=res)
+
+
+def compare_robust_controller(levels=(0.0, 0.05, 0.1, 0.15, 0.2, 0.25, 0.3), samples=100, seed=0, T=2.5, dt=1e-3, robot=None, **kw):
+    """The workload of kinova_src/scripts/kinova_compare_robust_controller.m for the ARMOUR controller: per uncertainty level, `samples`
+    random starts q0, qd0 in U[-pi/2, pi/2]; the reference starts 0.025 pi / 0.05 pi away in position / velocity along random unit
+    directions and comes to rest at q = 0 at T; the true plant has 1.01 x the nominal masses and inertias (load_robot_params'
+    true_mass_range); the controller's model_uncertainty is the level.  Returns dict(levels, median_max_v [levels] -- the summary
+    script's median over samples of max |v| --, max_v [levels, samples], status [levels, samples], result: [TrackResult per level])."""
+    robot = robot if robot is not None else kinova_robot()
+    n = robot.num_factors
+    rng = np.random.default_rng(seed)
+    out = dict(levels=np.asarray(levels, dtype=np.float64), median_max_v=[], max_v=[], status=[], result=[])
+
+    def unit(shape):
+        d = rng.uniform(-1, 1, shape)
+        return d / np.linalg.norm(d, axis=1, keepdims=True)
+
+    for level in levels:
+        q0 = rng.uniform(-np.pi / 2, np.pi / 2, (samples, n))
+        qd0 = rng.uniform(-np.pi / 2, np.pi / 2, (samples, n))
+        traj_q0 = q0 + 0.025 * np.pi * unit((samples, n))
+        traj_qd0 = qd0 + 0.05 * np.pi * unit((samples, n))
+        k_range = np.ones(n)
+        res = simulate_tracking(robot, traj_q0, traj_qd0, np.zeros((samples, n)), -traj_q0 / k_range, k_range, T, dt=dt,
+                                z0=np.concatenate([q0, qd0], axis=1), mass_scale=np.full((samples, n), 0.01),
+                                inertia_scale=np.full((samples, n), 0.01), model_uncertainty=level, **kw)
+        out["max_v"].append(res.max_robust_input)
+        out["median_max_v"].append(float(np.median(res.max_robust_input)))
+        out["status"].append(res.status)
+        out["result"].append(res)
+    out["max_v"], out["status"], out["median_max_v"] = np.array(out["max_v"]), np.array(out["status"]), np.array(out["median_max_v"])
+    return out

@@ -331,6 +331,68 @@ int armour_robust_controller(const ArmourRobot* robot, double model_uncertainty,
  * beyond, 0 always one lane per state, 1 always the latency kernel. */
 int armour_controller_set_kernel(int32_t which);
 
+/* ---- closed-loop tracking: the plan executed by an uncertain arm under the controller (tracking.hip) ---- */
+/* uarmtd_agent.dynamics + uarmtd_agent.integrator with its low-level controller in the right-hand side (KSI/uarmtd_agent.m:280-293,
+ * :360-405; KSI/uarmtd_robust_CBF_LLC.m:160-170) for B independent rollouts on the device, fp64 throughout.  Rollout b follows the
+ * degree-5 Bezier reference of armour_desired_trajectory (q0[b], qd0[b], qdd0[b], end q0 + k_range .* k[b], `duration`) from t0 to t1.
+ *   Integrator   classical RK4 on z = (q, qd), N = ceil((t1 - t0) / dt - 1e-9) steps of h = (t1 - t0) / N (not ode15s: a fixed
+ *                step, so a rollout's bits depend on nothing but its own inputs); node k is at t0 + k h, node N at t1.
+ *   Controller   ARMOUR_TRACK_CTL_ROBUST: RobustController::update, ARMOUR method, with opt->Kr .. model_uncertainty -- the arithmetic of
+ *                armour_robust_controller;  _NOMINAL: u = the nominal passivity RNEA torque, v = 0 (KSI/uarmtd_nominal_passivity_LLC.m);
+ *                _NONE: u = 0, the passive plant.
+ *   Plant        qdd = M_true(q)^-1 (u - h_true(q, qd)), the controller's own nominal model (CoM frames) with link i's mass scaled by
+ *                (1 + mass_scale[b][i]) and its CoM-frame inertia by (1 + inertia_scale[b][i]); M_true carries the armature on its diagonal
+ *                (the reference's transmision_inertia), h_true = passivity RNEA (q, qd, qd, 0) with gravity.  Unlike uarmtd_agent, h_true
+ *                includes the model's joint damping (zero on the Kinova presets).
+ *   Monitors     at every node, from the first RK4 stage: |wrap(q_des - q)|, |qd_des - qd|, V_true = 1/2 r' M_true r
+ *                (r = (qd_des - qd) + Kr .* wrap(q_des - q), the reference's true_V), |v|, |u_i| / torque_limits[i]; limit crossings as the
+ *                reference's input_check / joint_limit_check (KSI/uarmtd_agent.m:517-590): |u_i| > torque_limits[i] (bit 0),
+ *                q_i outside [state_limits_lb, state_limits_ub] (bit 1), |qd_i| > speed_limits[i] (bit 2).
+ *   Stops        status 1: the robust update found the nominal torque outside the interval torque (the reference throws); status 2: a
+ *                non-finite state.  The result then holds the state at the last node reached (t_end, steps).
+ * Compare the maxima with the ultimate bound of the controller (KSI/uarmtd_robust_CBF_LLC.m:36-40):
+ *   ub = sqrt(2 V_max / robot->M_min),  qe = ub / min(Kr)  (position),  qde = 2 ub  (velocity);  V stays <= V_max.
+ * Work is chunked: every launch advances each live rollout by at most steps_per_launch steps and the host launches until all reach t1;
+ * results are bit-identical for every steps_per_launch.  Arrays are host pointers, rollout-major: q0 / qd0 / qdd0 / k [B][n],
+ * k_range [n], z0 [B][2n] (q then qd at t0; NULL: on the reference), mass_scale / inertia_scale [B][n] (NULL: zeros), results [B],
+ * trace [B][N / record_every + 1][3n] (q, qd, u at nodes 0, r, 2r, ...; nodes after a stop are NaN; NULL or record_every = 0: none).
+ * ms (may be NULL): device time of the whole call.  ARMOUR_EINVAL on bad arguments (checked before the device is touched). */
+#define ARMOUR_TRACK_CTL_ROBUST 0
+#define ARMOUR_TRACK_CTL_NOMINAL 1
+#define ARMOUR_TRACK_CTL_NONE 2
+#define ARMOUR_TRACK_LIMIT_TORQUE 1
+#define ARMOUR_TRACK_LIMIT_POSITION 2
+#define ARMOUR_TRACK_LIMIT_SPEED 4
+typedef struct ArmourTrackOptions {
+    int32_t controller;        /* ARMOUR_TRACK_CTL_* */
+    int32_t record_every;      /* trace every this many steps; 0 = no trace */
+    int32_t steps_per_launch;  /* 0 = automatic (about 15 ms of device time per launch) */
+    int32_t reserved0;
+    double Kr[ARMOUR_MAX_FACTORS];
+    double alpha, V_max, r_norm_threshold, model_uncertainty;   /* as armour_robust_controller */
+    double dt, t0, t1, duration;                                /* 0 <= t0 < t1 <= duration; dt > 0 */
+    double reserved[4];
+} ArmourTrackOptions;
+typedef struct ArmourTrackResult {
+    int32_t status;            /* 0 reached t1, 1 nominal torque outside the interval torque, 2 non-finite state */
+    int32_t steps;             /* steps taken */
+    int32_t limit_flags;       /* ARMOUR_TRACK_LIMIT_* crossed at some node */
+    int32_t reserved;
+    double t_end, q[ARMOUR_MAX_FACTORS], qd[ARMOUR_MAX_FACTORS];   /* the last node reached */
+    double max_pos_error, max_vel_error, max_V, max_robust_input, max_torque_ratio;
+    double first_violation_t;  /* the first node with a limit crossing; NaN: none */
+} ArmourTrackResult;
+/* Kr = robot->K on every joint, alpha = robot->alpha, V_max = robot->V_m, r_norm_threshold = 0, model_uncertainty = robot->mass_uncertainty
+ * (KSI/uarmtd_robust_CBF_LLC.m:6-9 as the planner's robot constants set them), controller ROBUST, dt = 1e-3, t0 = 0, t1 = duration = 1,
+ * no trace, automatic steps per launch. */
+void armour_track_options_default(const ArmourRobot* robot, ArmourTrackOptions* opt);
+int armour_track(const ArmourRobot* robot, const ArmourTrackOptions* opt, int32_t B, const double* q0, const double* qd0, const double* qdd0,
+                 const double* k, const double* k_range, const double* z0, const double* mass_scale, const double* inertia_scale,
+                 ArmourTrackResult* results, double* trace, double* ms);
+/* the steps per launch armour_track takes for `controller` when opt->steps_per_launch = 0 (about 15 ms of device time per launch at the
+ * per-step cost measured on the MI355X, tracking.hip); ARMOUR_EINVAL for an unknown controller */
+int armour_track_auto_steps(int32_t controller);
+
 /* ---- NLP solve of the planning iteration ---- */
 /* Replaces IpoptApplication::OptimizeTNLP + armtd_NLP::finalize_solution (RT/armour_main.cu:237-304,
  * RT/NLPclass.cu:422-538) for all B problems of the handle at once: SQP on the device callbacks, start x = 0,

@@ -9,7 +9,9 @@ and fails the build when
   * a kernel reports a dynamic stack (an indirect or recursive call survived), or
   * a kernel's scratch frame exceeds the bound below (a callee's frame the kernel would address through generic pointers).
 
-    check_controller_codegen.py <remarks file>
+    check_controller_codegen.py <remarks file> [--kernels name,name,...]
+
+--kernels names the kernels the object must hold (default: the controller's two; the tracking simulator's object passes its own).
 """
 import re
 import sys
@@ -35,10 +37,16 @@ def parse(text):
 
 
 def main(argv):
-    fns = parse(open(argv[1]).read())
+    args = argv[1:]
+    kernels = KERNELS
+    if "--kernels" in args:
+        i = args.index("--kernels")
+        kernels = tuple(x for x in args[i + 1].split(",") if x)
+        del args[i:i + 2]
+    fns = parse(open(args[0]).read())
     bad, seen = [], []
     for name, r in fns.items():
-        kernel = next((k for k in KERNELS if k in name and (k != "armour_controller_kernel" or "split" not in name)), None)
+        kernel = next((k for k in kernels if k in name and (k != "armour_controller_kernel" or "split" not in name)), None)
         if kernel is None:
             bad.append(f"{name}: a device function of its own (the controller's halves must be inlined into the kernels)")
             continue
@@ -48,8 +56,8 @@ def main(argv):
         scratch = int(r.get("ScratchSize [bytes/lane]", "0"))
         if scratch > MAX_SCRATCH_BYTES:
             bad.append(f"{name}: {scratch} B of scratch per lane (> {MAX_SCRATCH_BYTES})")
-    if sorted(set(seen)) != sorted(KERNELS):
-        print(f"check_controller_codegen: expected the kernels {KERNELS}, found {seen} in {argv[1]}", file=sys.stderr)
+    if sorted(set(seen)) != sorted(kernels):
+        print(f"check_controller_codegen: expected the kernels {kernels}, found {seen} in {args[0]}", file=sys.stderr)
         return 2
     if bad:
         print("check_controller_codegen:\n  " + "\n  ".join(bad), file=sys.stderr)
