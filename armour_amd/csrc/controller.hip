@@ -167,6 +167,11 @@ struct CtlCache {
 };
 thread_local CtlCache g_ctl;
 
+bool finite_all(const double* x, size_t count) {
+    for (size_t i = 0; i < count; i++) if (!std::isfinite(x[i])) return false;
+    return true;
+}
+
 constexpr int kSplitMaxStates = kSplitStates * 256;   // up to one four-wave block per CU
 constexpr size_t kStagedDoubles = (size_t)1 << 20;  // calls up to this many input doubles go through the page-locked buffer
 
@@ -184,6 +189,16 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
                                         double r_norm_threshold, int32_t B, const double* q, const double* qd, const double* q_des,
                                         const double* qd_des, const double* qdd_des, double* u, double* tau, double* v) {
     if (!robot || !Kr || !q || !qd || !q_des || !qd_des || !qdd_des || !u || !tau || !v || B < 1) { armour_set_error("null or empty argument"); return ARMOUR_EINVAL; }
+    // ---- arguments, before the device is touched (a non-finite state in a kernel is ~10^4 operations on NaN at best)
+    const int nf = robot->num_factors;
+    if (nf < 1 || nf > ARMOUR_MAX_FACTORS) { armour_set_error("armour_robust_controller: num_factors out of range"); return ARMOUR_EINVAL; }
+    if (!finite_all(Kr, nf) || !std::isfinite(alpha) || !std::isfinite(V_max) || !std::isfinite(r_norm_threshold) || !(model_uncertainty >= 0) ||
+        !std::isfinite(model_uncertainty)) {
+        armour_set_error("armour_robust_controller: non-finite controller constant, or a model uncertainty that is negative or non-finite");
+        return ARMOUR_EINVAL;
+    }
+    for (const double* x : {q, qd, q_des, qd_des, qdd_des})
+        if (!finite_all(x, (size_t)B * nf)) { armour_set_error("armour_robust_controller: non-finite state or reference"); return ARMOUR_EINVAL; }
     CtlCache& c = g_ctl;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
@@ -196,7 +211,6 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
     }
     if (!c.stream) HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     if (!c.d_args) HIPCHK(hipMalloc((void**)&c.d_args, sizeof(CtlArgs)));
-    const int nf = robot->num_factors;
     bool same = c.have_model && memcmp(&c.rb, robot, sizeof(ArmourRobot)) == 0 && c.eps == model_uncertainty && c.alpha == alpha && c.V_max == V_max &&
                 c.r_thr == r_norm_threshold;
     for (int i = 0; same && i < nf; i++) same = c.Kr[i] == Kr[i];

@@ -228,9 +228,13 @@ CTL_HD CTL_FLATTEN void pass_rnea(const Model<S>& md, const double* q, const dou
     rnea_dynamics(md, k, qd, qda, qdd, apply_friction, apply_gravity, tau);
 }
 
-CTL_HD double clamp_angle(double x) {  // robust_controller.hpp:11-16
+// The reference's loop (robust_controller.hpp:11-16) for |x| <= 64 pi: at most 32 steps, its bits.  Beyond that the loop does not end in
+// useful time (1.6e9 steps at 1e10) or at all (the step rounds away from ~1e16 on; +-inf), so fmod -- exact -- brings x within one step
+// first: x mod 2 pi up to |x| * 3.9e-17 (the distance of the double 2 pi from 2 pi, once per turn), under an ulp of x.  +-inf and NaN give NaN.
+CTL_HD double clamp_angle(double x) {
     const double pi = 3.14159265358979323846;
     double r = x;
+    if (!(fabs(r) <= 64 * pi)) r = fmod(r, 2 * pi);
     while (r >= pi) r -= 2 * pi;
     while (r < -pi) r += 2 * pi;
     return r;

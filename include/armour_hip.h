@@ -322,7 +322,9 @@ int armour_desired_trajectory(int32_t n, const double* q0, const double* qd0, co
  * masses and inertias within +-model_uncertainty bounds the model error, v = robust input from the control barrier
  * condition on V = 1/2 r'M r <= V_max, u = tau - v.  One device thread per state.  All pointers are host pointers,
  * [B][n] row-major with n = robot->num_factors; Kr: [n] (diagonal gain).  ARMOUR_ESTATE if a nominal torque leaves its
- * interval (the reference throws). */
+ * interval (the reference throws).  ARMOUR_EINVAL, before the device is touched, for a non-finite entry of q .. qdd_des or Kr, a
+ * non-finite alpha, V_max or r_norm_threshold, and a model_uncertainty that is negative or non-finite.  q_des - q is wrapped to
+ * [-pi, pi) by the reference's loop up to 64 pi and by fmod first beyond: a bounded number of steps for every double. */
 int armour_robust_controller(const ArmourRobot* robot, double model_uncertainty, const double* Kr, double alpha, double V_max,
                              double r_norm_threshold, int32_t B, const double* q, const double* qd, const double* q_des,
                              const double* qd_des, const double* qdd_des, double* u, double* tau, double* v);

@@ -180,14 +180,31 @@ void rnea(const Model<S>& md, const double* q, const double* qd, const double* q
     }
 }
 
-double wrap(double x) { const double pi = 3.14159265358979323846; while (x >= pi) x -= 2 * pi; while (x < -pi) x += 2 * pi; return x; }
+/* the reference's loop up to 64 pi (at most 32 steps); beyond, std::fmod first (exact), so that every double takes a bounded number of
+ * steps: x mod 2 pi to under an ulp of x; NaN for +-inf and NaN.  The same rule as the product's clamp_angle, stated again. */
+double wrap(double x) {
+    const double pi = 3.14159265358979323846;
+    if (!(std::fabs(x) <= 64 * pi)) x = std::fmod(x, 2 * pi);
+    while (x >= pi) x -= 2 * pi;
+    while (x < -pi) x += 2 * pi;
+    return x;
+}
 }  // namespace
 
 extern "C" {
 /* [u, tau, v] of RobustController::update (ARMOUR method) for one state; also the interval torque [n][2].  Returns 1 if
  * the nominal torque lies inside the interval torque (the reference throws otherwise). */
+int oracle_robust_controller_detail(const ArmourRobot* rb, double eps, const double* Kr, double alpha, double V_max, double r_thr, const double* q, const double* q_d,
+                                    const double* qd, const double* qd_d, const double* qd_dd, double* u, double* tau, double* v, double* tau_interval, double* detail);
 int oracle_robust_controller(const ArmourRobot* rb, double eps, const double* Kr, double alpha, double V_max, double r_thr, const double* q, const double* q_d,
                              const double* qd, const double* qd_d, const double* qd_dd, double* u, double* tau, double* v, double* tau_interval) {
+    return oracle_robust_controller_detail(rb, eps, Kr, alpha, V_max, r_thr, q, q_d, qd, qd_d, qd_dd, u, tau, v, tau_interval, nullptr);
+}
+/* the same, and the two quantities its discrete decisions hang on, for tests that must stay clear of them -- detail[0] = |r|,
+ * detail[1] = lambda before max(0, .) (NaN when |r| is not above the threshold), detail[2] = |alpha h / |r|| + sqrt(bound^2): the size of
+ * the two terms whose difference detail[1] is */
+int oracle_robust_controller_detail(const ArmourRobot* rb, double eps, const double* Kr, double alpha, double V_max, double r_thr, const double* q, const double* q_d,
+                                    const double* qd, const double* qd_d, const double* qd_dd, double* u, double* tau, double* v, double* tau_interval, double* detail) {
     Model<double> md; Model<Interval> im;
     build(*rb, eps, md, im);
     const int n = md.n;
@@ -211,6 +228,7 @@ int oracle_robust_controller(const ArmourRobot* rb, double eps, const double* Kr
     double rn = 0;
     for (int i = 0; i < n; i++) rn += r[i] * r[i];
     rn = std::sqrt(rn);
+    if (detail) { detail[0] = rn; detail[1] = NAN; detail[2] = NAN; }
     if (rn > r_thr) {
         Interval Mr[NJ];
         rnea<Interval>(im, q, z, z, r, false, false, Mr);
@@ -218,6 +236,7 @@ int oracle_robust_controller(const ArmourRobot* rb, double eps, const double* Kr
         for (int i = 0; i < n; i++) V = V + (0.5 * r[i]) * Mr[i];
         const double h = -V.hi + V_max;
         const double lam = std::fmax(0.0, -alpha * h / rn + std::sqrt(b2));
+        if (detail) { detail[1] = -alpha * h / rn + std::sqrt(b2); detail[2] = std::fabs(alpha * h / rn) + std::sqrt(b2); }
         for (int i = 0; i < n; i++) v[i] = -lam * r[i] / rn;
     }
     for (int i = 0; i < n; i++) u[i] = tau[i] - v[i];

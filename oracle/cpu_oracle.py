@@ -300,17 +300,18 @@ def pz_op(op, operands, consts=None, r=0, threshold=5e-4, out_cap=1 << 16):
 
 def robust_controller(Kr, alpha, V_max, r_thr, q, qd, q_des, qd_des, qdd_des, eps=0.03, robot=None):
     """CPU restatement of the reference's kinova_controller MEX for ONE state (controller_oracle.cpp).
-    Returns dict(u, tau, v, tau_interval [n,2], inside)."""
+    Returns dict(u, tau, v, tau_interval [n,2], inside) and what the discrete decisions hang on: r_norm, lambda_raw (lambda before
+    max(0, .); NaN when r_norm is not above the threshold) and lambda_scale (the size of the two terms whose difference lambda_raw is)."""
     L = lib()
     rb = robot if robot is not None else kinova_robot()
     n = rb.num_factors
     a = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (q, qd, q_des, qd_des, qdd_des)]
     kr = np.ascontiguousarray(np.broadcast_to(np.asarray(Kr, dtype=np.float64).ravel(), (n,)))
-    u, tau, v, ti = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((n, 2))
-    L.oracle_robust_controller.restype = C.c_int
-    ok = L.oracle_robust_controller(C.byref(rb), C.c_double(eps), _dp(kr), C.c_double(alpha), C.c_double(V_max), C.c_double(r_thr),
-                                    *[_dp(x) for x in a], _dp(u), _dp(tau), _dp(v), _dp(ti))
-    return dict(u=u, tau=tau, v=v, tau_interval=ti, inside=bool(ok))
+    u, tau, v, ti, detail = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros((n, 2)), np.zeros(3)
+    L.oracle_robust_controller_detail.restype = C.c_int
+    ok = L.oracle_robust_controller_detail(C.byref(rb), C.c_double(eps), _dp(kr), C.c_double(alpha), C.c_double(V_max), C.c_double(r_thr),
+                                           *[_dp(x) for x in a], _dp(u), _dp(tau), _dp(v), _dp(ti), _dp(detail))
+    return dict(u=u, tau=tau, v=v, tau_interval=ti, inside=bool(ok), r_norm=detail[0], lambda_raw=detail[1], lambda_scale=detail[2])
 
 
 def pass_rnea_scaled(s_m, s_I, q, qd, qda, qdd, gravity=True, robot=None):

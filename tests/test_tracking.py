@@ -5,6 +5,7 @@ The device is checked against a host restatement written here: the same RK4 and 
 (oracle.cpu_oracle.robust_controller), the plant's M columns and bias from oracle.cpu_oracle.pass_rnea_scaled.  The restatement is
 itself held by two invariants (exact tracking under the nominal controller, fourth-order energy convergence of the passive plant)."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
@@ -20,12 +21,17 @@ def _robot():
 
 
 def _wrap(x):
+    """clamp_angle's rule (controller_core.h): the reference's loop up to 64 pi, fmod first beyond, NaN for inf / NaN -- bounded for every double."""
     x = np.array(x, dtype=np.float64)
     for i in range(x.size):
-        while x.flat[i] >= np.pi:
-            x.flat[i] -= 2 * np.pi
-        while x.flat[i] < -np.pi:
-            x.flat[i] += 2 * np.pi
+        r = float(x.flat[i])
+        if not abs(r) <= 64 * math.pi:
+            r = math.fmod(r, 2 * math.pi) if math.isfinite(r) else math.nan
+        while r >= math.pi:
+            r -= 2 * math.pi
+        while r < -math.pi:
+            r += 2 * math.pi
+        x.flat[i] = r
     return x
 
 
