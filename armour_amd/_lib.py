@@ -141,6 +141,7 @@ EXPORTS = [
     "armour_batch_get_build_ms", "armour_batch_get_build_info",
     "armour_roadmap_create", "armour_roadmap_destroy", "armour_roadmap_get_sizes", "armour_roadmap_check", "armour_roadmap_plan",
     "armour_track_options_default", "armour_track", "armour_track_auto_steps",
+    "armour_path_audit", "armour_path_audit_host", "armour_path_audit_items",
 ]
 
 _lib = None
@@ -271,6 +272,10 @@ def load():
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,
                                C.POINTER(ArmourTrackResult), dp, dp]
     L.armour_track_auto_steps.argtypes = [C.c_int32]
+    audit = [C.POINTER(ArmourRobot), C.c_int32, C.c_int32, dp, C.c_int32, ip, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp, C.c_double, ip, dp, dp]
+    L.armour_path_audit.argtypes = audit + [dp]
+    L.armour_path_audit_host.argtypes = audit
+    L.armour_path_audit_items.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, dp, dp, dp, dp, C.c_double, dp, dp, C.c_double, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

@@ -1,0 +1,77 @@
+"""Path audit: executed pieces of Bezier plans checked against worlds' obstacles on the MI355X (include/armour_hip.h, armour_path_audit).
+
+    res = audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02)
+    res.verdict        # [P]: 0 proved free, 1 proved hit, 2 undecided (NOT a finding: the audit at this step could not prove the piece free)
+    res.t_hit          # [P]: the first colliding sample time of a verdict-1 piece, NaN otherwise
+    res.clearance      # [P]: the minimum sample clearance (with clearance=True)
+
+`host=True` runs the library's host restatement of the same rule (no GPU needed; for tests).  The rule, its bound and the proof sketch are
+stated in include/armour_hip.h and DESIGN.md.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+FREE, HIT, UNDECIDED = 0, 1, 2
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+@dataclass
+class AuditResult:
+    verdict: np.ndarray
+    t_hit: np.ndarray
+    clearance: np.ndarray   # None unless requested
+    ms: float               # device time of the launch (0 on the host)
+
+
+def _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb):
+    n = robot.num_factors
+    q0, qd0, qdd0, k = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, n)) for a in (q0, qd0, qdd0, k)]
+    P = q0.shape[0]
+    for a in (qd0, qdd0, k):
+        if a.shape != (P, n):
+            raise ValueError(f"expected shape ({P},{n}), got {a.shape}")
+    k_range = np.ascontiguousarray(np.broadcast_to(np.asarray(k_range, dtype=np.float64), (n,)))
+    ta = np.ascontiguousarray(np.broadcast_to(np.asarray(ta, dtype=np.float64), (P,)))
+    tb = np.ascontiguousarray(np.broadcast_to(np.asarray(tb, dtype=np.float64), (P,)))
+    return P, n, q0, qd0, qdd0, k, k_range, ta, tb
+
+
+def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, clearance=False, host=False):
+    """P pieces in one call.  obstacles [W,O,12] (or [O,12]: W = 1); world_of_piece [P]; q0 / qd0 / qdd0 / k [P,n]; k_range [n]; ta / tb [P] or
+    scalars; tube [P,n], [n] or None (zeros): the per-joint radius about the plan that is audited with it."""
+    L = _lib.load()
+    P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)
+    obs = np.asarray(obstacles, dtype=np.float64)
+    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+    W, O = obs.shape[0], obs.shape[1]
+    wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
+    tube = None if tube is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tube, dtype=np.float64), (P, n)))
+    verdict = np.zeros(P, dtype=np.int32)
+    t_hit = np.zeros(P)
+    cl = np.zeros(P) if clearance else None
+    ip = C.POINTER(C.c_int32)
+    args = [C.byref(robot), W, O, _dp(obs) if obs.size else None, P, wp.ctypes.data_as(ip), _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range),
+            float(duration), _dp(ta), _dp(tb), _dp(tube), float(step), verdict.ctypes.data_as(ip), _dp(t_hit), _dp(cl)]
+    ms = C.c_double(0.0)
+    if host:
+        check(L.armour_path_audit_host(*args))
+    else:
+        check(L.armour_path_audit(*args, C.byref(ms)))
+    return AuditResult(verdict=verdict, t_hit=t_hit, clearance=cl, ms=ms.value)
+
+
+def audit_items(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, step=0.02):
+    """[P] int64: the sub-intervals (work items) an audit of every piece takes at `step`."""
+    P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)
+    out = np.zeros(P, dtype=np.int64)
+    check(_lib.load().armour_path_audit_items(C.byref(robot), P, _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range), float(duration), _dp(ta), _dp(tb),
+                                              float(step), out.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out

@@ -56,7 +56,7 @@ def boxes_to_obstacles(boxes):
 
 def first_iteration(start, goal, obstacles, lookahead):
     start = np.asarray(start, dtype=np.float64)
-    return dict(q0=start.copy(), qd0=np.zeros(7), qdd0=np.zeros(7), q_des=straight_line_waypoint(start, goal, lookahead),
+    return dict(q0=start.copy(), qd0=np.zeros(7), qdd0=np.zeros(7), q_des=straight_line_waypoint(start, goal, lookahead), lookahead=float(lookahead),
                 obstacles=np.asarray(obstacles, dtype=np.float64), goal=np.asarray(goal, dtype=np.float64))
 
 

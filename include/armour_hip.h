@@ -570,6 +570,53 @@ int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* 
 int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
                         int32_t max_points, double* path, int32_t* points);
 
+/* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
+/* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
+ * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory
+ * (q0[p], qd0[p], qdd0[p], end q0 + k_range .* k[p], `duration`) on the time window [ta[p], tb[p]] within [0, duration], in world
+ * world_of_piece[p] of obstacles [W][O][12], with an optional tube radius e = tube[p] per joint (NULL: zeros) -- how far the executed
+ * joint angles may be from the plan, e.g. the controller's ultimate bound.  Geometry, the node rule and rho_{j,l} are the roadmap's (above).
+ *
+ * Sub-intervals.  The plan's joint j is a degree-5 Bezier curve in s = t / duration with control points P_0..P_5 (P_0 = q0,
+ * P_1 = q0 + a/5, P_2 = q0 + 2a/5 + b/20, P_3 = P_4 = P_5 = q0 + k_range k; a = qd0 duration, b = qdd0 duration^2).  Its derivative is the
+ * degree-4 curve with control points 5 (P_{i+1} - P_i), so by the convex-hull property
+ *   v_j = max_i |5 (P_{i+1,j} - P_{i,j})| / duration  >=  |qd_j(t)|  for every t in [0, duration].
+ * The window is cut into S = max(1, ceil(max_j v_j (tb - ta) / step)) sub-intervals; sub-interval s has the midpoint
+ * t_s = ta + (2s + 1)(tb - ta) / (2S).
+ * Sample test (exact).  The node rule at q(t_s) with the link boxes as they are.  clearance <= 0 there is a PROVED collision of the
+ * nominal path at t_s.
+ * Tube test (conservative).  The node rule at q(t_s) with every half-size of link l enlarged by
+ *   r_l = sum over actuated j <= l of rho_{j,l} (v_j (tb - ta) / (2S) + e_j).
+ * Soundness, as for the edge rule: on sub-interval s the plan's joint j is within v_j (tb - ta)/(2S) of q_j(t_s) (mean value theorem with
+ * the bound v_j), so every configuration within e of the plan there has joint j within v_j (tb - ta)/(2S) + e_j of q_j(t_s); turning the
+ * joints there one at a time moves every point of link l by at most rho_{j,l} times the angle, so link l stays inside the box with
+ * half-sizes h_l + r_l about the midpoint box.  If every enlarged box of every sub-interval is separated from every obstacle, no
+ * configuration within e of the plan collides anywhere on the window.  (Rounding only helps: a plane's numerator is monotone in the
+ * half-sizes in floating point too, so an item whose tube test separates has a separated sample test.)
+ * Verdict per piece:  0 PROVED FREE (every tube test separates);  1 PROVED HIT (some sample test collides; t_hit = the first such t_s);
+ *   2 UNDECIDED (neither).  Verdict 2 is NOT a finding: it says the audit at this `step` could not prove the piece free -- the tube came
+ *   within r_l of an obstacle -- and nothing about a collision.  A smaller step shrinks r_l towards rho e and leaves fewer pieces
+ *   undecided, for proportionally more work items; with e > 0, a piece closer than rho e to an obstacle stays undecided at every step.
+ * Device.  One launch; a work item is one (piece, sub-interval) with its own Bezier evaluation and forward-kinematics pass, pieces are
+ * grouped by world and a block serves one world (obstacles staged in LDS once); fp64 throughout.  A piece's result does not depend on the
+ * other pieces of the call.  Arrays are host pointers: world_of_piece / ta / tb [P], q0 / qd0 / qdd0 / k / tube [P][n], k_range [n],
+ * obstacles [W][O][12] with O <= ARMOUR_ROADMAP_MAX_OBSTACLES.  Outputs: verdict [P]; t_hit [P] (NaN unless verdict 1; may be NULL);
+ * clearance [P] = the minimum sample-test clearance of the piece (may be NULL; when requested no item exits early); ms = device time of
+ * the launch (may be NULL).  ARMOUR_EINVAL on a bad argument (checked before the device is touched), ARMOUR_ECAPACITY when the pieces have
+ * more than 2^31 - 2 sub-intervals in all. */
+int armour_path_audit(const ArmourRobot* robot, int32_t W, int32_t O, const double* obstacles, int32_t P, const int32_t* world_of_piece,
+                      const double* q0, const double* qd0, const double* qdd0, const double* k, const double* k_range, double duration,
+                      const double* ta, const double* tb, const double* tube, double step, int32_t* verdict, double* t_hit, double* clearance,
+                      double* ms);
+/* the same rule by the same functions in a host loop (for tests; runs without a GPU) */
+int armour_path_audit_host(const ArmourRobot* robot, int32_t W, int32_t O, const double* obstacles, int32_t P, const int32_t* world_of_piece,
+                           const double* q0, const double* qd0, const double* qdd0, const double* k, const double* k_range, double duration,
+                           const double* ta, const double* tb, const double* tube, double step, int32_t* verdict, double* t_hit,
+                           double* clearance);
+/* items [P] = S of every piece: the work items an audit at `step` takes (host arithmetic) */
+int armour_path_audit_items(const ArmourRobot* robot, int32_t P, const double* q0, const double* qd0, const double* qdd0, const double* k,
+                            const double* k_range, double duration, const double* ta, const double* tb, double step, int64_t* items);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,134 @@
+"""Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
+and prints ONE JSON line.
+
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats]
+
+* the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
+  executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
+* audit throughput: (piece, sub-interval) items per second of the trial's own executed pieces at W = 1 (world 0's) and W = 107 (all),
+  kernel ms = the median `ms` of armour_path_audit over --reps launches, verdict mode and clearance mode;
+* --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
+  its own: a fresh child process under a time limit that only repeats the W = 107 audit.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def executed_pieces(res):
+    """Every executed piece of a run_trials result as the arrays armour_path_audit takes (world = index into res["worlds"])."""
+    rows = [(w, r["piece"]) for w, wr in enumerate(res["worlds"]) for r in wr["records"]]
+    world = np.array([w for w, _ in rows], dtype=np.int32)
+    cols = [np.stack([p[c] for _, p in rows]) for c in range(4)]
+    return world, cols, np.array([p[4] for _, p in rows]), np.array([p[5] for _, p in rows])
+
+
+def throughput(robot, obs, world, cols, ta, tb, k_range, D, step, reps, clearance):
+    from armour_amd.path_audit import audit, audit_items
+    items = int(audit_items(robot, *cols, k_range, D, ta, tb, step=step).sum())
+    audit(robot, obs, world, *cols, k_range, D, ta, tb, step=step, clearance=clearance)       # warm-up
+    ms = sorted(audit(robot, obs, world, *cols, k_range, D, ta, tb, step=step, clearance=clearance).ms for _ in range(reps))
+    kms = ms[len(ms) // 2]
+    return dict(pieces=int(world.size), items=items, kernel_ms=round(kms, 4), kernel_ms_min=round(ms[0], 4), items_per_s=round(items / (kms * 1e-3)))
+
+
+def child(path, reps):
+    """The profiled run: nothing but the saved W = 107 audit, `reps` times."""
+    from armour_amd.path_audit import audit
+    from armour_amd.planner import kinova_robot
+    d = np.load(path)
+    for _ in range(reps):
+        audit(kinova_robot(), d["obs"], d["world"], d["q0"], d["qd0"], d["qdd0"], d["k"], d["k_range"], float(d["D"]), d["ta"], d["tb"], step=float(d["step"]))
+
+
+def kernel_stats(saved, reps, out_csv):
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tmp, "-o", "trial", "--output-format", "csv", "--",
+               sys.executable, os.path.abspath(__file__), "--child", saved, "--reps", str(reps)]
+        run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        if run.returncode != 0:
+            return dict(error=run.stderr[-400:])
+        files = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
+        if not files:
+            return dict(error="no kernel_stats.csv written")
+        rows = list(csv.reader(open(files[0])))
+        os.makedirs(os.path.dirname(out_csv), exist_ok=True)
+        with open(out_csv, "w", newline="") as f:
+            csv.writer(f).writerows(rows)
+        hit = [dict(zip(rows[0], r)) for r in rows[1:] if "path_audit_kernel" in r[0]]
+        return hit[0] if hit else dict(error="path_audit_kernel not in the trace")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=128)
+    ap.add_argument("--max-iterations", type=int, default=400)
+    ap.add_argument("--steps", type=float, nargs="+", default=[0.01, 0.05])
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--kernel-stats", action="store_true")
+    ap.add_argument("--child")
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.reps)
+    from armour_amd import scenes
+    from armour_amd.path_audit import audit
+    from armour_amd.planner import kinova_robot
+    from armour_amd.tracking import ultimate_bound
+    from armour_amd.trials import run_trials
+    robot = kinova_robot()
+    ws = scenes.reference_worlds()
+    res = run_trials(ws, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
+    s = res["summary"]
+    its = np.array([w["iterations"] for w in res["worlds"]])
+    bt = res["batches"]
+    out = dict(tool="trial_bench", robot="kinova_gen3_no_gripper", T=a.T, worlds=len(ws), max_iterations=a.max_iterations, summary=s,
+               outcomes_saved_scenes={o: sum(1 for w in res["worlds"][:100] if w["outcome"] == o) for o in ("goal", "collision", "stuck", "iteration_limit")},
+               outcomes_hard_scenarios={w["name"]: w["outcome"] for w in res["worlds"][100:]},
+               iterations=dict(mean=float(its.mean()), max=int(its.max()), min=int(its.min())),
+               build_ms_per_batch=dict(mean=float(np.mean([b["build_ms"] for b in bt])), max=float(np.max([b["build_ms"] for b in bt]))),
+               solve_ms_per_batch=dict(mean=float(np.mean([b["solve_ms"] for b in bt])), max=float(np.max([b["solve_ms"] for b in bt]))),
+               audit_ms_per_batch=dict(mean=float(np.mean([b["audit_ms"] for b in bt])), max=float(np.max([b["audit_ms"] for b in bt]))),
+               first_batch=bt[0], min_clearance=float(min(r["clearance"] for w in res["worlds"] for r in w["records"])))
+    k_range, D = res["k_range"], res["duration"]
+    O = max(w["obstacles"].shape[0] for w in res["worlds"])
+    obs = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in res["worlds"]])
+    world, cols, ta, tb = executed_pieces(res)
+    qe = ultimate_bound(robot)[1]
+    out["undecided"] = {}
+    for step in a.steps:
+        for tag, tube in (("no_tube", None), ("ultimate_bound_tube", np.full(robot.num_factors, qe))):
+            v = audit(robot, obs, world, *cols, k_range, D, ta, tb, tube=tube, step=step).verdict
+            out["undecided"]["step_%g/%s" % (step, tag)] = dict(pieces=int(v.size), free=int((v == 0).sum()), hit=int((v == 1).sum()), undecided=int((v == 2).sum()),
+                                                                undecided_share=round(float((v == 2).mean()), 4))
+    out["ultimate_bound_position"] = qe
+    out["throughput"] = {}
+    one = world == 0
+    for step in a.steps:
+        for mode, cl in (("verdict", False), ("clearance", True)):
+            out["throughput"]["step_%g/%s" % (step, mode)] = {
+                "W=107": throughput(robot, obs, world, cols, ta, tb, k_range, D, step, a.reps, cl),
+                "W=1": throughput(robot, obs[:1], world[one], [c[one] for c in cols], ta[one], tb[one], k_range, D, step, a.reps, cl)}
+    if a.kernel_stats:
+        with tempfile.TemporaryDirectory() as tmp:
+            saved = os.path.join(tmp, "pieces.npz")
+            np.savez(saved, obs=obs, world=world, q0=cols[0], qd0=cols[1], qdd0=cols[2], k=cols[3], k_range=k_range, D=D, ta=ta, tb=tb, step=a.steps[0])
+            out["kernel_stats"] = kernel_stats(saved, a.reps, os.path.join(ROOT, "profiles", "trial_kernel_stats.csv"))
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "trial_bench.json"), "w") as f:
+        json.dump(out, f, indent=1, default=float)
+        f.write("\n")
+    print(json.dumps(out, default=float))
+
+
+if __name__ == "__main__":
+    main()
