@@ -84,6 +84,12 @@ class ArmourViolation(C.Structure):
                 ("n_outside_slack", C.c_int32), ("feasible", C.c_int32)]
 
 
+class ArmourSweepRecord(C.Structure):   # armour_sweep: the violation record of one candidate and its cost (40 bytes)
+    _fields_ = [("v", ArmourViolation), ("cost", C.c_double)]
+
+
+SWEEP_MAX_CANDIDATES = 4096   # ARMOUR_SWEEP_MAX_CANDIDATES
+
 OPT_P1_BUILD = 1   # ARMOUR_OPT_P1_BUILD: 0 automatic, 1 per time step, 2 time-vectorised
 OPT_P1_WORK_MEMORY_MB = 2   # ARMOUR_OPT_P1_WORK_MEMORY_MB: cap on the time-vectorised build's work memory, MiB (0: none)
 # the other per-handle options of include/armour_hip.h (launch shapes: bit-identical keys / coefficients / centres for every value)
@@ -142,6 +148,7 @@ EXPORTS = [
     "armour_roadmap_create", "armour_roadmap_destroy", "armour_roadmap_get_sizes", "armour_roadmap_check", "armour_roadmap_plan",
     "armour_track_options_default", "armour_track", "armour_track_auto_steps",
     "armour_path_audit", "armour_path_audit_host", "armour_path_audit_items",
+    "armour_solve_from", "armour_sweep", "armour_sweep_tile",
 ]
 
 _lib = None
@@ -221,6 +228,9 @@ def load():
     L.armour_solve_options_default.argtypes = [C.POINTER(ArmourSolveOptions)]
     L.armour_solve_options_default.restype = None
     L.armour_solve.argtypes = [vp, C.POINTER(ArmourSolveOptions), C.POINTER(ArmourSolveResult)]
+    L.armour_solve_from.argtypes = [vp, C.POINTER(ArmourSolveOptions), dp, C.POINTER(ArmourSolveResult)]
+    L.armour_sweep.argtypes = [vp, C.c_int32, dp, C.c_int32, C.POINTER(ArmourSweepRecord), ip, dp]
+    L.armour_sweep_tile.argtypes = []
     L.armour_debug_qp.argtypes = [C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, ip]
     L.armour_debug_qp_box.argtypes = [C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, ip, ip, dp]
     L.armour_debug_pz_op.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(dp), dp, dp, dp, dp,

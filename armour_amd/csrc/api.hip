@@ -267,6 +267,7 @@ extern "C" void armour_destroy(ArmourPlanner* h) {
     for (void* pin : h->solve_pin) armour_free_pinned(pin);
     dev_free(&h->d_bounds); dev_free(&h->d_viol);
     armour_relevance_free(h);
+    armour_sweep_free(h);
     if (h->d_tr_stage) (void)hipFree(h->d_tr_stage);
     dev_free(&h->solve_dev.ctl); dev_free(&h->solve_dev.blk_word); dev_free(&h->solve_dev.blk_rows); dev_free(&h->solve_dev.qp_rows);
     dev_free(&h->solve_dev.flags);
@@ -519,7 +520,7 @@ int armour_checked_collision_rows(const ArmourPlanner* h) {
 }
 
 // joint i's coefficients of problem b for the plan point (solver_common.h slv::plan_point)
-static void plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]) {
+void armour_plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]) {
     const double D = h->params.duration;
     const bool armtd = h->mode == ARMOUR_MODE_ARMTD;  // CMP/NLPclass.cu:183-243
     c[0] = h->h_q0[ix];
@@ -537,7 +538,7 @@ extern "C" int armour_eval_f(ArmourPlanner* h, const double* k, double* f) {
                 if ((h->robot.continuous[i] != 0) != (pass == 0)) continue;
                 const size_t ix = (size_t)b * n + i;
                 double c[3];
-                plan_coeffs(h, ix, c);
+                armour_plan_coeffs(h, ix, c);
                 const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], h->params.t_plan);
                 const double e = h->robot.continuous[i] ? slv::wrap_to_pi(h->h_qdes[ix] - qp) : (h->h_qdes[ix] - qp);
                 obj += e * e;
@@ -555,7 +556,7 @@ extern "C" int armour_eval_grad_f(ArmourPlanner* h, const double* k, double* gra
         for (int i = 0; i < n; i++) {
             const size_t ix = (size_t)b * n + i;
             double c[3];
-            plan_coeffs(h, ix, c);
+            armour_plan_coeffs(h, ix, c);
             const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], tp);
             const double dk = slv::plan_dk(h->mode, c[2], h->params.k_range[i], tp);
             const double e = h->robot.continuous[i] ? slv::wrap_to_pi(qp - h->h_qdes[ix]) : (qp - h->h_qdes[ix]);

@@ -180,6 +180,7 @@ struct ArmourPlanner {
     bool rel_fresh = false;
     double rel_ms = 0;
     int rel_max_count = 0;
+    unsigned char* d_sweep = nullptr; size_t sweep_cap = 0;   // armour_sweep's device block: candidates | cost coefficients | records | best (sweep.hip)
     SolveDeviceWork solve_dev;
     double* d_bounds = nullptr;      // [2][B][m] g_l, g_u for the solver's device-side scan (uploaded on the first solve of a problem set)
     bool bounds_on_device = false, bounds_on_host = false;
@@ -248,10 +249,14 @@ int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const uns
 // relevance.hip
 int armour_relevance_build(ArmourPlanner* h, bool for_solver);   // (relevance.hip; for_solver: also the lists armour_solve's culled device form walks)
 void armour_relevance_free(ArmourPlanner* h);
+// sweep.hip
+void armour_sweep_free(ArmourPlanner* h);
 int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourViolation* d_out, hipStream_t st);
 int armour_refresh_table_stats(ArmourPlanner* h);
 // collision rows the feasibility re-check looks at (all Q in ARMOUR mode; the first (n-1)*T*O in ARMTD mode, CMP/NLPclass.cu:391-402)
 int armour_checked_collision_rows(const ArmourPlanner* h);
+// joint ix = b * n + i's coefficients c0, c1, c2 of the cost's plan point (solver_common.h slv::plan_point): what armour_eval_f and the sweep's cost read
+void armour_plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]);
 // page-locked scratch slot of the handle with at least `bytes` bytes (registered for the zero-copy eval path); nullptr on failure
 double* armour_handle_pinned(ArmourPlanner* h, int slot, size_t bytes);
 int armour_p2_slice_links_launch(const P2Tables& tb, const double* d_k, double* d_centers, hipStream_t stream);

@@ -3,6 +3,9 @@
 // the same order from 0 (:454-472); planes in ascending order, pos before neg, strict > (RT/CollisionChecking.cu:230-299: the reference's
 // serial winner, which is also what the four-wave merge of collision_block produces) -- so a listed row's g and Jacobian row are the fused
 // evaluation's bit for bit (tests/test_row_relevance.py, tests/test_solve.py).  Plane entries come from the packed copy of the listed rows.
+// sweep.hip (armour_sweep) walks the same rows for a TILE of points: its collision and torque rows repeat the statements of sparse_collision_row<false>
+// and sparse_torque_row below with the point's index added, so that a row's table entries are read once per tile.  The two texts must stay in
+// step -- a change of the order of the sums or of the plane loop here is a change there (tests/test_sweep.py holds them together on the GPU).
 #pragma once
 #include "p2_tiles.h"
 

@@ -106,6 +106,20 @@ __device__ inline void mono_all(const KPow& kp, uint32_t key, double c, int n, d
         }
     }
 }
+// The same product in two steps, for a caller that evaluates ONE monomial key with several coefficients (the three axes of a link monomial) or at
+// several points (sweep.hip: a tile of candidates): mono_factors reads the n table entries of the key once, mono_product multiplies
+// coeff * f_0 * ... * f_{n-1} in factor order -- mono_all<false>'s o[0] bit for bit (absent factors are exact multiplications by 1.0).
+// sweep.hip's rows are built on these two; a change to mono_all's value path belongs here as well (tests/test_sweep.py compares the two on the GPU).
+__device__ inline void mono_factors(const KPow& kp, uint32_t key, int n, double* f) {
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) f[j] = (j < n) ? kp.pw[j][(key >> (2 * j)) & 3u] : 1.0;
+}
+__device__ inline double mono_product(double c, const double* f) {
+    double v = c;
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) v *= f[j];
+    return v;
+}
 // centre of Interval(c - r, c + r) as getCenter computes it (RT/PZsparse.cu:10-12,427-432)
 __device__ inline double interval_center(double c, double r) {
     const double lo = c - r, hi = c + r;

@@ -413,7 +413,7 @@ struct DeviceStage {
     double hard_s = 0;                   // no wait of the kernel outlasts this
 };
 
-static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, const P2Tables& tb, const DevicePlan& p, Clock::time_point t_begin, DeviceStage& s) {
+static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, const double* k_start, const P2Tables& tb, const DevicePlan& p, Clock::time_point t_begin, DeviceStage& s) {
     const int B = h->B, n = h->n, m = h->m;
     const SolvePlan& plan = p.plan;
     int rc;
@@ -443,7 +443,10 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     SolveCtl* hctl = reinterpret_cast<SolveCtl*>(s.hblock);
     memset(s.hres, 0, (size_t)B * sizeof(ArmourSolveResult));
     memset(hctl, 0, (size_t)B * sizeof(SolveCtl));
-    for (int b = 0; b < B; b++) { hctl[b].go = 1; /* phase 0: CMD_EVAL_GJ at x = 0 */ s.hres[b].status = -2; }
+    for (int b = 0; b < B; b++) {   // phase 0: CMD_EVAL_GJ at the start point (zeros, or armour_solve_from's)
+        hctl[b].go = 1; s.hres[b].status = -2;
+        if (k_start) for (int j = 0; j < n; j++) hctl[b].x[j] = k_start[(size_t)b * n + j];
+    }
     memcpy(s.hblock + off_qdes, h->h_qdes.data(), (size_t)B * n * sizeof(double));
     SolveArgs& a = s.a;
     memset(&a, 0, sizeof(a));
@@ -506,14 +509,14 @@ static void report_device_timing(const ArmourPlanner* h, const DevicePlan& p, co
     fprintf(stderr, "\n   all problems: %lld QP steps; longest attempt that ended feasible %lld steps; attempts of more than 60 steps that ended infeasible: %lld\n", steps_all, longest_ok, long_bad);
 }
 
-static int solve_on_device(ArmourPlanner* h, const ArmourSolveOptions& opt, ArmourSolveResult* results, Clock::time_point t_begin, DeviceOutcome* out) {
+static int solve_on_device(ArmourPlanner* h, const ArmourSolveOptions& opt, const double* k_start, ArmourSolveResult* results, Clock::time_point t_begin, DeviceOutcome* out) {
     *out = DeviceOutcome::HandBack;
     const P2Tables tb = armour_make_tables(h);
     DevicePlan p;
     DeviceStage s;
     int rc;
     if ((rc = plan_device_solve(h, tb, p)) != ARMOUR_OK || p.plan.capacity < 1) return rc;
-    if ((rc = stage_device_solve(h, opt, tb, p, t_begin, s)) != ARMOUR_OK) return rc;
+    if ((rc = stage_device_solve(h, opt, k_start, tb, p, t_begin, s)) != ARMOUR_OK) return rc;
     SolveDeviceWork& w = h->solve_dev;
     const int B = h->B, n_launch = p.n_launch;
     const auto t_launch = Clock::now();
@@ -547,7 +550,7 @@ static int solve_on_device(ArmourPlanner* h, const ArmourSolveOptions& opt, Armo
 enum class Scan { Violation = 0, Rows = 1, Verdict = 2 };   // armour_solve_scan_kernel's MODE
 
 struct ProblemState {
-    double x[NV] = {}, f, gradf[NV], viol, mu = 1.0;   // get_starting_point: x = 0
+    double x[NV] = {}, f, gradf[NV], viol, mu = 1.0;   // get_starting_point: x = 0 (armour_solve_from: setup_host_solve overwrites it)
     int iters = 0, evals = 0, status = 0;  // 0 running, 1 converged, 2 max iterations, 3 QP infeasible, 4 line search failed, 5 time limit
     bool done = false;
     bool searching = false;                // in this iteration's line search: step d, length alpha, merit phi0 at x and its slope dphi
@@ -570,7 +573,7 @@ struct HostSolve {
     double t_eval = 0, t_qp = 0;         // ARMOUR_SOLVE_TIMING
 };
 
-static int setup_host_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, HostSolve& s) {
+static int setup_host_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, const double* k_start, HostSolve& s) {
     const int B = h->B, n = h->n, m = h->m;
     int rc;
     s.h = h; s.opt = opt; s.B = B; s.n = n; s.m = m;
@@ -603,6 +606,8 @@ static int setup_host_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, Hos
         }
     s.st.assign(B, ProblemState());
     std::fill(s.hk, s.hk + (size_t)B * n, 0.0);
+    if (k_start)
+        for (int b = 0; b < B; b++) for (int j = 0; j < n; j++) s.hk[(size_t)b * n + j] = s.st[b].x[j] = k_start[(size_t)b * n + j];
     return ARMOUR_OK;
 }
 
@@ -783,11 +788,11 @@ static int finish_host_solve(HostSolve& s, ArmourSolveResult* results, Clock::ti
     return ARMOUR_OK;
 }
 
-// SQP from x = 0: QP steps on host threads, the evaluations (with the scan of what the QPs need) on the device
-static int solve_on_host(ArmourPlanner* h, const ArmourSolveOptions& opt, ArmourSolveResult* results, Clock::time_point t_begin) {
+// SQP from the start point (x = 0 unless the caller gave one): QP steps on host threads, the evaluations (with the scan of what the QPs need) on the device
+static int solve_on_host(ArmourPlanner* h, const ArmourSolveOptions& opt, const double* k_start, ArmourSolveResult* results, Clock::time_point t_begin) {
     HostSolve s;
     int rc;
-    if ((rc = setup_host_solve(h, opt, s)) != ARMOUR_OK) return rc;
+    if ((rc = setup_host_solve(h, opt, k_start, s)) != ARMOUR_OK) return rc;
     const int B = s.B, n = s.n;
     if ((rc = evaluate(s, Scan::Rows)) != ARMOUR_OK) return rc;
     if ((rc = armour_eval_f(h, s.hk, s.f.data())) != ARMOUR_OK) return rc;
@@ -834,9 +839,14 @@ static int solve_on_host(ArmourPlanner* h, const ArmourSolveOptions& opt, Armour
     return finish_host_solve(s, results, t_begin);
 }
 
-extern "C" int armour_solve(ArmourPlanner* h, const ArmourSolveOptions* opt_in, ArmourSolveResult* results) {
+extern "C" int armour_solve(ArmourPlanner* h, const ArmourSolveOptions* opt_in, ArmourSolveResult* results) { return armour_solve_from(h, opt_in, nullptr, results); }
+
+extern "C" int armour_solve_from(ArmourPlanner* h, const ArmourSolveOptions* opt_in, const double* k_start, ArmourSolveResult* results) {
     if (!h || !results) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
     if (!h->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
+    if (k_start)   // the variables' box (and the box the culled form's row lists hold in): checked before the device is touched
+        for (size_t i = 0; i < (size_t)h->B * h->n; i++)
+            if (!(std::fabs(k_start[i]) <= 1.0)) { armour_set_error("armour_solve_from: k_start[%zu] = %g is outside [-1, 1]", i, k_start[i]); return ARMOUR_EINVAL; }
     ArmourSolveOptions opt;
     if (opt_in) opt = *opt_in; else armour_solve_options_default(&opt);
     const auto t_begin = Clock::now();
@@ -849,8 +859,8 @@ extern "C" int armour_solve(ArmourPlanner* h, const ArmourSolveOptions* opt_in, 
     HIPCHK(hipSetDevice(h->device));
     if (want_device) {
         DeviceOutcome out;
-        const int rc = solve_on_device(h, opt, results, t_begin, &out);
+        const int rc = solve_on_device(h, opt, k_start, results, t_begin, &out);
         if (rc != ARMOUR_OK || out == DeviceOutcome::Solved) return rc;
     }
-    return solve_on_host(h, opt, results, t_begin);
+    return solve_on_host(h, opt, k_start, results, t_begin);
 }

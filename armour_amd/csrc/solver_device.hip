@@ -922,11 +922,13 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(WPS, W
     double* jac = a.jac + (size_t)b * m * n;
     if (leader && tid < 3 * NV) L.bz[tid] = tid < 3 * n ? a.tb.bez[(size_t)b * 3 * n + tid] : 0.0;
     if (leader && tid >= 32 && tid < 32 + NV) L.qdes[tid - 32] = tid - 32 < n ? a.q_des[(size_t)b * n + tid - 32] : 0.0;
+    // the start point: what the host put into the control block (armour_solve: zeros, get_starting_point of RT/NLPclass.cu:170-202;
+    // armour_solve_from: the caller's) -- the point phase 0 evaluates
+    if (leader && tid >= 64 && tid < 64 + NV) L.x[tid - 64] = tid - 64 < n ? ld_coh(&c->x[tid - 64]) : 0.0;
     __syncthreads();
     if (leader && tid == 0) {
         L.t_start = wall_clock64();
         for (int j = 0; j < NV; j++) {
-            L.x[j] = 0.0;   // get_starting_point: x = 0 (RT/NLPclass.cu:170-202)
             double Hd = 1e-12;
             if (j < n) {
                 const double dk = plan_dk(a, L.bz, j);

@@ -115,6 +115,83 @@ def _solve_dicts(res, n):
                  iterations=r.iterations, evaluations=r.evaluations, status=r.status, time_ms=r.time_ms) for r in res]
 
 
+# one record of armour_sweep as numpy sees it (ArmourSweepRecord: the ArmourViolation fields, then the cost; 40 bytes)
+SWEEP_DTYPE = np.dtype([("l1_violation", "<f8"), ("worst", "<f8"), ("worst_row", "<i4"), ("n_violated", "<i4"),
+                        ("n_outside_slack", "<i4"), ("feasible", "<i4"), ("cost", "<f8")])
+
+_PRIMES = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53)
+
+
+def _radical_inverse(i, base):
+    """Digits of i in `base`, mirrored at the point: the van der Corput value in [0, 1)."""
+    v, f = 0.0, 1.0 / base
+    while i > 0:
+        v += (i % base) * f
+        i //= base
+        f /= base
+    return v
+
+
+def sweep_candidates(n, S):
+    """The candidate set of a sweep, [S, n] in [-1, 1]^n, deterministic (no RNG): row 0 is the solver's own start, all zeros; row i >= 1 is
+    point i of the Halton sequence in the first n primes mapped to the box (2 h - 1).  A set of S candidates is a prefix of every larger set."""
+    if not 1 <= n <= len(_PRIMES):
+        raise ValueError(f"n = {n}: 1 .. {len(_PRIMES)} trajectory parameters")
+    if S < 1:
+        raise ValueError("S >= 1")
+    k = np.zeros((S, n))
+    for i in range(1, S):
+        for j in range(n):
+            k[i, j] = 2.0 * _radical_inverse(i, _PRIMES[j]) - 1.0
+    return k
+
+
+def best_candidate(feasible, cost):
+    """armour_sweep's selection rule, restated: per problem the index of the smallest cost among the candidates with feasible == 1, the lowest
+    index among equals, -1 if there is none.  feasible, cost: [B, S]."""
+    feasible, cost = np.asarray(feasible), np.asarray(cost, dtype=np.float64)
+    best = np.full(feasible.shape[0], -1, dtype=np.int32)
+    for b in range(feasible.shape[0]):
+        for s in range(feasible.shape[1]):
+            if feasible[b, s] == 1 and (best[b] < 0 or cost[b, s] < cost[b, best[b]]):
+                best[b] = s
+    return best
+
+
+def merge_rescue(first, cand, records, best, refined):
+    """What a planning iteration keeps after a rescue attempt -- a pure function.  first / refined: per-problem result dicts of solve() (refined: the
+    second solve, started at the candidates; may be None); cand [S, n] or [B, S, n]; records [B, S] (SWEEP_DTYPE, or anything indexable the same
+    way); best [B].  Returns (results, rescued) with rescued[b]
+       0  the first solve was feasible: kept untouched;
+       2  it failed, a candidate is safe (best >= 0), and the refined solve is feasible at a cost <= that candidate's: the refined result;
+       1  it failed, a candidate is safe, the refined solve did not qualify: the candidate itself is the plan (k_opt = the candidate, cost = its
+          record's, max_violation = its record's l1, feasible -- the row test that accepts a k_opt accepted it; iterations, evaluations,
+          status and time_ms stay those of the failed first solve: no solver run produced this point);
+      -1  it failed and no candidate is safe: the failure is kept."""
+    cand = np.asarray(cand, dtype=np.float64)
+    out, rescued = [], np.zeros(len(first), dtype=np.int32)
+    for b, r in enumerate(first):
+        if r["feasible"]:
+            out.append(r)
+            continue
+        s = int(best[b])
+        if s < 0:
+            out.append(r)
+            rescued[b] = -1
+            continue
+        rec = records[b][s]
+        c_cost = float(rec["cost"])
+        rf = refined[b] if refined is not None else None
+        if rf is not None and rf["feasible"] and rf["cost"] <= c_cost:
+            out.append(rf)
+            rescued[b] = 2
+            continue
+        kc = cand[b, s] if cand.ndim == 3 else cand[s]
+        out.append(dict(r, k_opt=np.array(kc, dtype=np.float64), cost=c_cost, max_violation=float(rec["l1_violation"]), feasible=True))
+        rescued[b] = 1
+    return out, rescued
+
+
 def batch_partition(B, n_slots):
     """first[d] of armour_batch_*: slot d owns problems [first[d], first[d+1]) (pure host arithmetic in the library)."""
     first = (C.c_int32 * (n_slots + 1))()
@@ -442,13 +519,55 @@ class ArmourNLP:
         """Asynchronous: d_k [B][n] doubles, d_out [B] ArmourViolation records (32 B each), device pointers (ints)."""
         check(self.L.armour_eval_violations_device(self.h, d_k, d_out, stream))
 
-    def solve(self, max_iterations=None, tolerance=None, max_wall_time_s=None, host_qp=False, device_qp=False):
+    def sweep(self, k_cand, per_problem=False):
+        """armour_sweep: S candidates judged per problem in two launches.  k_cand [S, n] shared by all problems, or [B, S, n] with per_problem;
+        every |k| <= 1.  Returns dict(records [B, S] of SWEEP_DTYPE -- the armour_eval_violations record of (problem, candidate) and
+        armour_eval_f's cost --, best [B]: the cheapest feasible candidate or -1, ms: device time)."""
+        k = np.ascontiguousarray(np.asarray(k_cand, dtype=np.float64))
+        want = (self.B, k.shape[-2], self.n) if per_problem else (k.shape[-2], self.n)
+        if k.ndim != len(want) or k.shape != want:
+            raise ValueError(f"k_cand has shape {k.shape}, expected {'[B, S, n]' if per_problem else '[S, n]'}")
+        S = k.shape[-2]
+        rec = np.zeros((self.B, S), dtype=SWEEP_DTYPE)
+        best = np.zeros(self.B, dtype=np.int32)
+        ms = C.c_double()
+        check(self.L.armour_sweep(self.h, S, _dp(k), 1 if per_problem else 0, rec.ctypes.data_as(C.POINTER(_lib.ArmourSweepRecord)),
+                                  best.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ms)))
+        return dict(records=rec, best=best, ms=ms.value)
+
+    def solve_rescued(self, S=128, candidates=None, first=None, **solve_kw):
+        """solve(), and when some problem comes back infeasible one sweep of S shared candidates (sweep_candidates unless given) and one more
+        solve of the batch from start points: a failed problem with a safe candidate starts at that candidate, every other problem at its own
+        first k_opt clipped to the box.  Only failed problems take new results (merge_rescue).  Returns (results, rescued [B])."""
+        if first is None:
+            first = self.solve(**solve_kw)
+        if all(r["feasible"] for r in first):
+            return first, np.zeros(self.B, dtype=np.int32)
+        cand = sweep_candidates(self.n, S) if candidates is None else np.asarray(candidates, dtype=np.float64)
+        sw = self.sweep(cand)
+        start = np.zeros((self.B, self.n))
+        for b, r in enumerate(first):
+            if not r["feasible"] and sw["best"][b] >= 0:
+                start[b] = cand[sw["best"][b]]
+            else:
+                ko = np.asarray(r["k_opt"], dtype=np.float64)
+                start[b] = np.clip(np.where(np.isfinite(ko), ko, 0.0), -1.0, 1.0)
+        # (the second solve only when some FAILED problem has a safe candidate to start at: nothing else could take its result)
+        wanted = any(not r["feasible"] and sw["best"][b] >= 0 for b, r in enumerate(first))
+        refined = self.solve(k_start=start, **solve_kw) if wanted else None
+        return merge_rescue(first, cand, sw["records"], sw["best"], refined)
+
+    def solve(self, max_iterations=None, tolerance=None, max_wall_time_s=None, host_qp=False, device_qp=False, k_start=None):
         """OptimizeTNLP + finalize_solution for all B problems (RT/armour_main.cu:237-304): returns a list of dicts
         (k_opt, cost, feasible, iterations, evaluations, status, time_ms).  host_qp / device_qp hold the solver to one of its two forms
-        (same iterates; automatic: the persistent kernel, for every batch size since round 6)."""
+        (same iterates; automatic: the persistent kernel, for every batch size since round 6).  k_start [B, n] in [-1, 1]: armour_solve_from,
+        the same solver from that point instead of 0."""
         opt = _solve_options(self.L, max_iterations, tolerance, max_wall_time_s, host_qp, device_qp)
         res = (_lib.ArmourSolveResult * self.B)()
-        check(self.L.armour_solve(self.h, C.byref(opt), res))
+        if k_start is None:
+            check(self.L.armour_solve(self.h, C.byref(opt), res))
+        else:
+            check(self.L.armour_solve_from(self.h, C.byref(opt), _dp(self._k(k_start)), res))
         return [dict(k_opt=np.array(r.k_opt[:self.n]), cost=r.cost, max_violation=r.max_violation, feasible=bool(r.feasible),
                      iterations=r.iterations, evaluations=r.evaluations, status=r.status, time_ms=r.time_ms) for r in res]
 

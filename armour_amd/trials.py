@@ -67,7 +67,7 @@ class StraightLineHLP:
 class DevicePlanner:
     """The planning backend of run_trials: one ArmourNLP handle; plan() is armour_set_problems + armour_solve for one batch."""
 
-    def __init__(self, robot=None, T=128, max_batch=128, max_obstacles=16, per_step_build=False, device=0, solve_options=None):
+    def __init__(self, robot=None, T=128, max_batch=128, max_obstacles=16, per_step_build=False, device=0, solve_options=None, rescue_candidates=0):
         self.robot = robot if robot is not None else kinova_robot()
         self.params = default_params(T)
         n = self.robot.num_factors
@@ -78,6 +78,8 @@ class DevicePlanner:
         if per_step_build:
             self.nlp.set_option(_lib.OPT_P1_BUILD, 1)
         self.solve_options = dict(solve_options or {})
+        # > 0: an infeasible solve is followed by a sweep of this many candidates and one more solve from the safe ones (ArmourNLP.solve_rescued)
+        self.rescue_candidates = int(rescue_candidates)
 
     def plan(self, q0, qd0, qdd0, q_des, obstacles):
         """[B, n] x 4 and [B, O, 12] -> (results [B] of dict(k_opt, feasible, iterations, time_ms, ...), build_ms, solve_ms) -- the two times
@@ -85,7 +87,11 @@ class DevicePlanner:
         self.nlp.set_parameters(q0, qd0, qdd0, q_des, obstacles)
         build_ms = self.nlp.build_ms
         t0 = time.perf_counter()
-        res = self.nlp.solve(**self.solve_options)
+        if self.rescue_candidates > 0:
+            res, rescued = self.nlp.solve_rescued(S=self.rescue_candidates, **self.solve_options)
+            res = [dict(r, rescued=int(c)) for r, c in zip(res, rescued)]
+        else:
+            res = self.nlp.solve(**self.solve_options)
         return res, build_ms, (time.perf_counter() - t0) * 1e3
 
     def close(self):
@@ -101,19 +107,22 @@ def _world_record(world):
 
 def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, stop_threshold=4, max_iterations=300, audit_step=0.01, tube=None,
                tracked=False, track_samples=1, track_dt=1e-3, track_seed=0, goal_nodes=10, T=128, per_step_build=False, solve_options=None,
-               backend=None, audit_on_host=False, clearance=True, device=0):
+               backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0):
     """Run every world of `worlds` ([(name, problem)] as scenes.reference_worlds() gives them; a problem holds q0 = the start at rest, goal,
     obstacles [O, 12] and lookahead) to its end.  hlp: "straight" or a factory (world index, world record) -> object with
     get_waypoint(q_cur, lookahead) (e.g. a RoadmapHLP; None = no waypoint: the goal is used).  tube: None or "ultimate_bound" (every joint's
     radius = the controller's ultimate position bound, tracking.ultimate_bound) or an [n] array: the radius the audit takes about each
     executed piece.  tracked: also execute every piece with armour_track on `track_samples` sampled plants per world (slow; opt-in).
-    backend: an object with plan(), robot, k_range, duration, t_plan (default: DevicePlanner).  Returns dict(worlds, summary, ...)."""
+    backend: an object with plan(), robot, k_range, duration, t_plan (default: DevicePlanner).  rescue_candidates > 0 (default 0: today's path):
+    the default backend answers an infeasible solve with a candidate sweep and a second solve from the safe candidates (ArmourNLP.solve_rescued);
+    every record carries `rescued` (0 not needed, 1 a candidate became the plan, 2 the solve from it did, -1 no safe candidate) and the summary
+    counts `rescued_iterations`.  Returns dict(worlds, summary, ...)."""
     ws = [_world_record(w) for w in worlds]
     W = len(ws)
     own_backend = backend is None
     if own_backend:
         backend = DevicePlanner(robot=robot, T=T, max_batch=max(W, 1), max_obstacles=max([w["obstacles"].shape[0] for w in ws] + [1]),
-                                per_step_build=per_step_build, device=device, solve_options=solve_options)
+                                per_step_build=per_step_build, device=device, solve_options=solve_options, rescue_candidates=rescue_candidates)
     robot = backend.robot
     n = robot.num_factors
     k_range, D, t_plan = np.asarray(backend.k_range, dtype=np.float64), float(backend.duration), float(backend.t_plan)
@@ -155,7 +164,8 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
         for b, i in enumerate(live):
             s, r = st[i], res[b]
             rec = dict(iteration=it, q0=q0[b].copy(), qd0=qd0[b].copy(), qdd0=qdd0[b].copy(), q_des=q_des[b].copy(), k_opt=np.array(r["k_opt"], dtype=np.float64),
-                       feasible=bool(r["feasible"]), sqp_iterations=int(r.get("iterations", 0)), build_ms=build_ms, solve_ms=float(r.get("time_ms", solve_ms)))
+                       feasible=bool(r["feasible"]), sqp_iterations=int(r.get("iterations", 0)), build_ms=build_ms, solve_ms=float(r.get("time_ms", solve_ms)),
+                       rescued=int(r.get("rescued", 0)))
             if rec["feasible"]:
                 plan = (q0[b].copy(), qd0[b].copy(), qdd0[b].copy(), rec["k_opt"].copy())
                 piece, kind = plan + (0.0, t_plan), "plan"
@@ -220,6 +230,7 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
     summary = dict(worlds=W, **{o: sum(1 for s in st if s["outcome"] == o) for o in OUTCOMES},
                    iterations=int(sum(b["live"] for b in batches)), batches=len(batches), pieces=pieces_n,
                    undecided_pieces=int(sum(s["undecided"] for s in st)),
+                   rescued_iterations=int(sum(1 for s in st for r in s["records"] if r["rescued"] > 0)),
                    batch_planning_ms_mean=float(plan_ms.mean()) if plan_ms.size else 0.0, batch_planning_ms_max=float(plan_ms.max()) if plan_ms.size else 0.0,
                    planning_ms_per_world_iteration=float(plan_ms.sum() / max(1, sum(b["live"] for b in batches))),
                    audit_ms_total=float(sum(b.get("audit_ms", 0.0) for b in batches)))

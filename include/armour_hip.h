@@ -425,6 +425,44 @@ typedef struct ArmourSolveResult {
 void armour_solve_options_default(ArmourSolveOptions* opt);
 int armour_solve(ArmourPlanner* h, const ArmourSolveOptions* opt, ArmourSolveResult* results /* [B] */);
 int armour_batch_solve(ArmourBatch* bt, const ArmourSolveOptions* opt, ArmourSolveResult* results /* [B] */);
+/* armour_solve from a start point of the caller's: k_start host [B][n], NULL = zeros (armour_solve(h, opt, r) IS armour_solve_from(h, opt, NULL, r)).
+ * The reference starts at 0 and marks that as a weakness (RT/NLPclass.cu:193-198, "try to avoid local minimum"); its MATLAB path starts fmincon at a
+ * random point.  Both forms of the solver take the start: the host-QP form and the persistent kernel, its culled variant included.
+ *   - a component with |k_start| > 1 or a non-finite one: ARMOUR_EINVAL, before any HIP call (the variables' box; the culled form's row lists hold inside it);
+ *   - NULL and an array of +0.0 give armour_solve's results bit for bit, in every field except time_ms;
+ *   - the host form and the device form give bit-equal iterates from any start. */
+int armour_solve_from(ArmourPlanner* h, const ArmourSolveOptions* opt, const double* k_start /* host [B][n]; NULL = zeros */,
+                      ArmourSolveResult* results /* [B] */);
+
+/* ---- candidate sweep: S trial points k of the SAME problems judged in one go (sweep.hip) ---- */
+/* "Is there any safe plan in this reach set?"  The row test of armour_eval_violations and the cost of armour_eval_f for S candidates per problem,
+ * on the relevant rows only (armour_get_row_relevance: the torque rows, the LISTED collision rows, the limit rows), and the best safe candidate
+ * picked on the device.  What a caller does after an infeasible armour_solve: sweep, then armour_solve_from the winner (armour_amd/planner.py
+ * solve_rescued).
+ *   k_cand   host, [S][n] shared by all problems (per_problem = 0) or [B][S][n] (per_problem = 1); every |k| <= 1
+ *   records  [B][S], may be NULL;  best [B], may be NULL;  ms = device time of the sweep's launches, may be NULL.  Synchronous.
+ * CONTRACT
+ *   Violation record.  records[b][s].v is the record armour_eval_violations gives for problem b at that k (ARMOUR_OPT_CULL_ROWS 0 or 1).  worst,
+ *     worst_row, n_violated, n_outside_slack and feasible are EXACT: every row's g is computed with the fused evaluation's arithmetic in its own
+ *     order (the arithmetic of p2_sparse.h's sparse_collision_row / sparse_torque_row and of the limit block, bezier.h / cacc.h).  l1_violation is
+ *     within m * 2^-52 * l1 of that entry's value -- the bound of a sum of m non-negative terms taken in any order; the shipped kernel in fact
+ *     keeps the layout of the row test (thread t of 256 owns the rows r = t mod 256 in ascending order, the same tree combines them), which
+ *     gives the same bits.
+ *   Independence.  A record depends on (problem, k) only: not on S, the candidate's position, the other candidates, B, or per_problem.
+ *   Cost.  records[b][s].cost equals armour_eval_f at that k bit for bit (solver_common.h plan_point / wrap_to_pi, continuous joints first).
+ *   Best candidate.  best[b] = the index of the candidate with the smallest cost among those with v.feasible == 1, the lowest index among equals;
+ *     -1 if none is feasible.  Selected on the device.
+ *   Arguments.  ARMOUR_EINVAL before the first HIP call if S < 1, S > 4096 (ARMOUR_SWEEP_MAX_CANDIDATES), or any |k| > 1 or non-finite k: the
+ *     row lists hold inside the box only.
+ *   Modes.  Every mode ARMOUR_OPT_CULL_ROWS = 1 supports: the Bezier trajectory, ARMTD comparison mode, and input_constraints_off (no torque rows).
+ * Launches: two per call whatever S (the sweep; the selection), after the once-per-problem-set row lists.  A block serves one problem and a tile
+ * of armour_sweep_tile() candidates: it reads each row's table entries once and evaluates them for the whole tile. */
+#define ARMOUR_SWEEP_MAX_CANDIDATES 4096
+typedef struct ArmourSweepRecord { ArmourViolation v; double cost; } ArmourSweepRecord;   /* 40 bytes */
+int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, int32_t per_problem,
+                 ArmourSweepRecord* records, int32_t* best, double* ms);
+/* candidates per block of armour_sweep's kernel (a compile-time tile; tests take their S around it).  No result depends on it. */
+int armour_sweep_tile(void);
 /* test hook for the dense QP: min 1/2 x'diag(Gd)x + g0'x  s.t. lo <= A x <= hi (A row-major [m][n], n <= 7,
  * |bound| >= 1e18 = absent).  Host-only: runs without a GPU. */
 int armour_debug_qp(int32_t n, const double* Gd, const double* g0, int32_t m, const double* A, const double* lo,
