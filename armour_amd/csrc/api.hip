@@ -82,18 +82,6 @@ extern "C" void armour_free_pinned(void* p) {
     (void)hipHostFree(p);
 }
 
-template <class Tp>
-static int dev_alloc(Tp** p, size_t count) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (count == 0) count = 1;
-    HIPCHK(hipMalloc((void**)p, count * sizeof(Tp)));
-    return ARMOUR_OK;
-}
-template <class Tp>
-static void dev_free(Tp** p) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
-
 static int ensure_capacity(ArmourPlanner* h, int B, int O) {
     if (B <= h->allocB && O <= h->allocO) return ARMOUR_OK;
     const int nb = B > h->allocB ? B : h->allocB, no = O > h->allocO ? O : h->allocO;
@@ -101,33 +89,30 @@ static int ensure_capacity(ArmourPlanner* h, int B, int O) {
     // that a hipMalloc failing half-way cannot leave small (or null) buffers behind capacity fields a later call trusts
     h->allocB = 0; h->allocO = 0;
     const size_t nl = (size_t)nb * h->J * h->T, nt = (size_t)nb * h->n * h->T;
-    int rc;
-#define TRY(x) if ((rc = (x)) != ARMOUR_OK) return rc
-    TRY(dev_alloc(&h->d_link_count, nl));
-    TRY(dev_alloc(&h->d_link_center, nl * 3));
-    TRY(dev_alloc(&h->d_link_indep, nl * 3));
-    TRY(dev_alloc(&h->d_link_keys, nl * h->lim.link_monomials));
-    TRY(dev_alloc(&h->d_link_coeff, nl * h->lim.link_monomials * 3));
-    TRY(dev_alloc(&h->d_tq_count, nt));
-    TRY(dev_alloc(&h->d_tq_center, nt));
-    TRY(dev_alloc(&h->d_tq_indep, nt));
-    TRY(dev_alloc(&h->d_tq_keys, nt * h->lim.torque_monomials));
-    TRY(dev_alloc(&h->d_tq_coeff, nt * h->lim.torque_monomials));
-    TRY(dev_alloc(&h->d_planes, (size_t)nb * armour_planes_per_problem(h->J * h->T * no)));
-    TRY(dev_alloc(&h->d_planes_ll, (size_t)nb * armour_planes_ll_per_problem(h->J * h->T)));
-    TRY(dev_alloc(&h->d_obs_center, (size_t)nb * 3 * (no > 0 ? no : 1)));
-    TRY(dev_alloc(&h->d_plane_skip, (size_t)nb));
-    TRY(dev_alloc(&h->d_bez, (size_t)nb * 3 * h->n));
+    ARMOUR_TRY(h->d_link_count.reserve(nl));
+    ARMOUR_TRY(h->d_link_center.reserve(nl * 3));
+    ARMOUR_TRY(h->d_link_indep.reserve(nl * 3));
+    ARMOUR_TRY(h->d_link_keys.reserve(nl * h->lim.link_monomials));
+    ARMOUR_TRY(h->d_link_coeff.reserve(nl * h->lim.link_monomials * 3));
+    ARMOUR_TRY(h->d_tq_count.reserve(nt));
+    ARMOUR_TRY(h->d_tq_center.reserve(nt));
+    ARMOUR_TRY(h->d_tq_indep.reserve(nt));
+    ARMOUR_TRY(h->d_tq_keys.reserve(nt * h->lim.torque_monomials));
+    ARMOUR_TRY(h->d_tq_coeff.reserve(nt * h->lim.torque_monomials));
+    ARMOUR_TRY(h->d_planes.reserve((size_t)nb * armour_planes_per_problem(h->J * h->T * no)));
+    ARMOUR_TRY(h->d_planes_ll.reserve((size_t)nb * armour_planes_ll_per_problem(h->J * h->T)));
+    ARMOUR_TRY(h->d_obs_center.reserve((size_t)nb * 3 * (no > 0 ? no : 1)));
+    ARMOUR_TRY(h->d_plane_skip.reserve((size_t)nb));
+    ARMOUR_TRY(h->d_bez.reserve((size_t)nb * 3 * h->n));
     const size_t mmax = (size_t)h->n * h->T + (size_t)h->J * h->T * no + 4 * h->n;
-    TRY(dev_alloc(&h->d_k, (size_t)nb * h->n));
+    ARMOUR_TRY(h->d_k.reserve((size_t)nb * h->n));
     // g and jac staging: ONE allocation, jac placed directly behind the g of the current problem set (begin_problem_set), so that the
     // synchronous host call can bring both back with a single device-to-host transfer when the caller's buffers are adjacent too.
     // The jac part doubles as the scratch of armour_get_link_centers (B*T*J*3 doubles): m*n >= T*J*3 does not hold for every
     // robot armour_create accepts (n*n < 3J with O = 0), so it is sized for both uses
-    TRY(dev_alloc(&h->d_g, (size_t)nb * mmax + std::max((size_t)nb * mmax * h->n, (size_t)nb * h->T * h->J * 3)));
+    ARMOUR_TRY(h->d_g.reserve((size_t)nb * mmax + std::max((size_t)nb * mmax * h->n, (size_t)nb * h->T * h->J * 3)));
     h->d_jac = h->d_g + (size_t)nb * mmax;
-    TRY(dev_alloc(&h->d_bounds, (size_t)2 * nb * mmax));
-#undef TRY
+    ARMOUR_TRY(h->d_bounds.reserve((size_t)2 * nb * mmax));
     h->allocB = nb;
     h->allocO = no;
     return ARMOUR_OK;
@@ -198,8 +183,7 @@ bool armour_trace_solve() { static const bool on = getenv("ARMOUR_SOLVE_TIMING")
 extern "C" int armour_create(const ArmourRobot* robot, const ArmourParams* params, const ArmourLimits* limits,
                              int32_t device, ArmourPlanner** out) {
     if (!robot || !params || !out) { armour_set_error("armour_create: null argument"); return ARMOUR_EINVAL; }
-    if (robot->num_joints < 1 || robot->num_joints > ARMOUR_MAX_JOINTS || robot->num_factors < 1 ||
-        robot->num_factors > robot->num_joints || robot->num_factors > ARMOUR_MAX_FACTORS) {
+    if (!armour_robot_shape_ok(robot)) {
         armour_set_error("armour_create: unsupported robot (joints=%d, factors=%d; max %d joints, %d factors -- the monomial key "
                          "packs 9 bits per factor into 64, RT/PZsparse.h:8-21)", robot->num_joints, robot->num_factors,
                          ARMOUR_MAX_JOINTS, ARMOUR_MAX_FACTORS);
@@ -265,22 +249,9 @@ extern "C" void armour_destroy(ArmourPlanner* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_step_graphs(h);
     for (void* pin : h->solve_pin) armour_free_pinned(pin);
-    dev_free(&h->d_bounds); dev_free(&h->d_viol);
-    armour_relevance_free(h);
-    armour_sweep_free(h);
-    if (h->d_tr_stage) (void)hipFree(h->d_tr_stage);
-    dev_free(&h->solve_dev.ctl); dev_free(&h->solve_dev.blk_word); dev_free(&h->solve_dev.blk_rows); dev_free(&h->solve_dev.qp_rows);
-    dev_free(&h->solve_dev.flags);
-    dev_free(&h->d_jrs);
     armour_p1_free(h);
-    dev_free(&h->d_link_count); dev_free(&h->d_link_center); dev_free(&h->d_link_indep);
-    dev_free(&h->d_link_keys); dev_free(&h->d_link_coeff);
-    dev_free(&h->d_tq_count); dev_free(&h->d_tq_center); dev_free(&h->d_tq_indep);
-    dev_free(&h->d_tq_keys); dev_free(&h->d_tq_coeff);
-    dev_free(&h->d_planes); dev_free(&h->d_planes_ll); dev_free(&h->d_obs_center); dev_free(&h->d_plane_skip); dev_free(&h->d_bez);
-    dev_free(&h->d_k); dev_free(&h->d_g); h->d_jac = nullptr;   // (d_jac lives inside d_g's allocation)
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // (its DevBuf members free the device buffers)
 }
 
 // mode ARMTD: `qdd0` carries k_range [B][n] (the curve has no initial acceleration) and the third row of d_bez holds it
@@ -292,13 +263,13 @@ static int begin_problem_set(ArmourPlanner* h, int B, int O, const double* q0, c
     // a NaN / inf state would only surface as NaN constraint rows, so it is refused here
     {
         const double* arrs[4] = {q0, qd0, qdd0, q_des};
+        const size_t bn = (size_t)B * h->n;
         for (int a = 0; a < 4; a++)
-            for (size_t i = 0; i < (size_t)B * h->n; i++)
-                if (!std::isfinite(arrs[a][i])) { armour_set_error("non-finite entry in the initial state / goal arrays (array %d, entry %zu)", a, i); return ARMOUR_EINVAL; }
+            if (const size_t i = first_nonfinite(arrs[a], bn); i < bn) { armour_set_error("non-finite entry in the initial state / goal arrays (array %d, entry %zu)", a, i); return ARMOUR_EINVAL; }
     }
     HIPCHK(hipSetDevice(h->device));
     h->ready = false;
-    h->rel_fresh = false; h->rel2_fresh = false;
+    h->rel.fresh = false; h->rel2.fresh = false;
     h->bounds_on_device = false; h->bounds_on_host = false;
     h->tables_from_host = false;
     h->stats_fresh = false;
@@ -349,15 +320,21 @@ int armour_refresh_table_stats(ArmourPlanner* h) {
     return ARMOUR_OK;
 }
 
+// the obstacles of B problems, O each, 12 doubles per obstacle: what both armour_set_problems* forms refuse
+static int check_obstacles(int B, int O, const double* obstacles) {
+    if (O > 0 && !obstacles) { armour_set_error("obstacles is null but O=%d", O); return ARMOUR_EINVAL; }
+    const size_t cnt = (size_t)B * O * 12;
+    if (const size_t i = first_nonfinite(obstacles, cnt); i < cnt) { armour_set_error("non-finite obstacle entry %zu", i); return ARMOUR_EINVAL; }
+    return ARMOUR_OK;
+}
+
 extern "C" int armour_set_problems(ArmourPlanner* h, int32_t B, int32_t O, const double* q0, const double* qd0,
                                    const double* qdd0, const double* q_des, const double* obstacles) {
     armour_build_stamps().n = 0;
     armour_build_stamp("start");
     int rc = begin_problem_set(h, B, O, q0, qd0, qdd0, q_des);
     if (rc != ARMOUR_OK) return rc;
-    if (O > 0 && !obstacles) { armour_set_error("obstacles is null but O=%d", O); return ARMOUR_EINVAL; }
-    for (size_t i = 0; i < (size_t)B * O * 12; i++)
-        if (!std::isfinite(obstacles[i])) { armour_set_error("non-finite obstacle entry %zu", i); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(check_obstacles(B, O, obstacles));
     armour_build_stamp("checks+bezier-upload");
     rc = armour_p1_build(h, obstacles);
     if (rc != ARMOUR_OK) return rc;
@@ -375,16 +352,10 @@ extern "C" int armour_set_problems_armtd(ArmourPlanner* h, int32_t B, int32_t O,
     if (!jrs || !k_range) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
     int rc = begin_problem_set(h, B, O, q0, qd0, k_range, q_des, ARMOUR_MODE_ARMTD);
     if (rc != ARMOUR_OK) return rc;
-    if (O > 0 && !obstacles) { armour_set_error("obstacles is null but O=%d", O); return ARMOUR_EINVAL; }
-    for (size_t i = 0; i < (size_t)B * O * 12; i++)
-        if (!std::isfinite(obstacles[i])) { armour_set_error("non-finite obstacle entry %zu", i); return ARMOUR_EINVAL; }
-    for (size_t i = 0; i < (size_t)B * h->n * 6 * h->T; i++)
-        if (!std::isfinite(jrs[i])) { armour_set_error("non-finite entry %zu in the offline JRS tables", i); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(check_obstacles(B, O, obstacles));
     const size_t cnt = (size_t)B * h->n * 6 * h->T;
-    if (cnt > h->jrs_cap) {
-        if ((rc = dev_alloc(&h->d_jrs, cnt)) != ARMOUR_OK) return rc;
-        h->jrs_cap = cnt;
-    }
+    if (const size_t i = first_nonfinite(jrs, cnt); i < cnt) { armour_set_error("non-finite entry %zu in the offline JRS tables", i); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(h->d_jrs.reserve(cnt));
     HIPCHK(hipMemcpy(h->d_jrs, jrs, cnt * sizeof(double), hipMemcpyHostToDevice));
     rc = armour_p1_build(h, obstacles);
     if (rc != ARMOUR_OK) return rc;
@@ -795,12 +766,7 @@ int armour_upload_bounds(ArmourPlanner* h) {
     const double* d_tr = nullptr;
     if (!h->no_torque()) {
         const size_t ntr = (size_t)h->B * h->n * h->T;
-        if (h->tr_stage_cap < ntr) {
-            if (h->d_tr_stage) (void)hipFree(h->d_tr_stage);
-            h->d_tr_stage = nullptr; h->tr_stage_cap = 0;
-            HIPCHK(hipMalloc((void**)&h->d_tr_stage, ntr * sizeof(double)));
-            h->tr_stage_cap = ntr;
-        }
+        ARMOUR_TRY(h->d_tr_stage.reserve(ntr));
         HIPCHK(hipMemcpyAsync(h->d_tr_stage, h->h_torque_radius.data(), ntr * sizeof(double), hipMemcpyHostToDevice, h->stream));
         d_tr = h->d_tr_stage;
     }
@@ -943,12 +909,7 @@ extern "C" int armour_eval_violations(ArmourPlanner* h, const double* k, ArmourV
     if (!k || !out) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
     HIPCHK(hipSetDevice(h->device));
     const size_t bn = (size_t)h->B * h->n;
-    if ((size_t)h->B > h->viol_cap) {
-        dev_free(&h->d_viol); h->viol_cap = 0;
-        int rc = dev_alloc(&h->d_viol, (size_t)h->B);
-        if (rc != ARMOUR_OK) return rc;
-        h->viol_cap = (size_t)h->B;
-    }
+    ARMOUR_TRY(h->d_viol.reserve((size_t)h->B));
     // page-locked staging on both sides: the two copies are asynchronous and ordered with the launches on the handle's stream
     double* hk = armour_handle_pinned(h, 6, bn * sizeof(double));
     ArmourViolation* hv = reinterpret_cast<ArmourViolation*>(armour_handle_pinned(h, 7, (size_t)h->B * sizeof(ArmourViolation)));
@@ -1045,12 +1006,11 @@ extern "C" int armour_get_hyperplanes(ArmourPlanner* h, double* A, double* d, do
     if (pl.empty()) return ARMOUR_OK;
     if (h->planes_lean) {
         // the resident table holds only what the fused evaluation reads: build the full one, with the same kernel code, into a scratch buffer
-        double* d_full = nullptr;
-        HIPCHK(hipMalloc((void**)&d_full, pl.size() * sizeof(double)));
-        int rc = armour_p1_full_planes(h, d_full);
-        if (rc == ARMOUR_OK && hipMemcpy(pl.data(), d_full, pl.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { armour_set_error("copy of the half-space table failed"); rc = ARMOUR_EDEVICE; }
-        (void)hipFree(d_full);
+        DevBuf<double> d_full;
+        int rc = d_full.reserve(pl.size());
+        if (rc == ARMOUR_OK) rc = armour_p1_full_planes(h, d_full);
         if (rc != ARMOUR_OK) return rc;
+        if (hipMemcpy(pl.data(), d_full, pl.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { armour_set_error("copy of the half-space table failed"); return ARMOUR_EDEVICE; }
     } else
     HIPCHK(hipMemcpy(pl.data(), h->d_planes, pl.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int b = 0; b < B; b++)

@@ -10,11 +10,10 @@
 #include <vector>
 
 #include "../../include/armour_hip.h"
+#include "device_mem.h"
 
 #define ARMOUR_NPLANES 36
 #define ARMOUR_PLANE_COMPONENTS 5  // Ax, Ay, Az, d, delta
-
-void armour_set_error(const char* fmt, ...);
 
 // The half-space table of one problem, layout v2 (round 4).  The row index q = (l*T + t)*O + o is the fastest axis and every array
 // of rows is Qs = armour_row_stride(Q) long -- Q rounded up to 16 doubles, so that each array starts on a 128-B line (with the
@@ -52,27 +51,6 @@ __host__ __device__ inline size_t armour_plane_index(int Q, int q, int p, int c)
 #define ARMOUR_LL_RECORD 48
 __host__ __device__ inline size_t armour_planes_ll_per_problem(int JT) { return (size_t)ARMOUR_LL_RECORD * (size_t)JT; }
 __host__ __device__ inline size_t armour_plane_ll_index(int JT, int lt, int pll, int c) { (void)JT; return (size_t)lt * ARMOUR_LL_RECORD + (size_t)pll * 3 + c; }
-
-#define HIPCHK(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) {                                                                         \
-            armour_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return ARMOUR_EDEVICE;                                                                       \
-        }                                                                                                \
-    } while (0)
-
-// a device buffer of at least `need` elements (`fresh`, if given: set when it was allocated anew)
-template <class Tp>
-inline int grow(Tp** p, size_t* cap, size_t need, bool* fresh = nullptr) {
-    if (need <= *cap && *p) return ARMOUR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    HIPCHK(hipMalloc((void**)p, (need ? need : 1) * sizeof(Tp)));
-    *cap = need;
-    if (fresh) *fresh = true;
-    return ARMOUR_OK;
-}
 
 // spin on hipStreamQuery instead of sleeping in hipStreamSynchronize: the calls that wait are tens of microseconds (api.hip)
 int armour_spin_on_stream(hipStream_t st);
@@ -118,12 +96,26 @@ struct P2Tables {
 
 // device buffers of the device-resident armour_solve (solver_device.hip), grown on demand and kept across solves
 struct SolveDeviceWork {
-    unsigned char* ctl = nullptr; size_t ctl_cap = 0;            // one block: control words | goals | SolveArgs (one copy per solve)
-    unsigned char* blk_word = nullptr; size_t word_cap = 0;
-    int words_clean = 0;                                         // the last launch ended normally: every block has cleared its flag word
-    unsigned char* blk_rows = nullptr; size_t blk_rows_cap = 0;
-    unsigned char* qp_rows = nullptr; size_t qp_rows_cap = 0;
-    unsigned char* flags = nullptr; size_t flags_cap = 0;
+    DevBuf<unsigned char> ctl;        // one block: control words | goals | SolveArgs (one copy per solve)
+    DevBuf<unsigned char> blk_word;
+    int words_clean = 0;              // the last launch ended normally: every block has cleared its flag word
+    DevBuf<unsigned char> blk_rows, qp_rows, flags;
+};
+
+// One set of row lists of the current problem set (relevance.hip): a mask [B][m], the listed collision rows of every problem in ascending
+// order [B][Q], their counts, and the listed rows' plane entries, packed.  The handle holds two: the rows that can be violated at all
+// (armour_get_row_relevance, the culled armour_eval_violations) and the rows that can pass armour_solve's candidate filter for some k.
+struct RelLists {
+    DevBuf<unsigned char> mask;
+    DevBuf<int> rows;
+    DevBuf<int> count;           // relevance: [B] counts | [B][256] per residue class; solver: [B] listed collision rows | [B] listed torque rows
+    DevBuf<double> packed;
+    DevBuf<long long> pack_off;  // [B][2]: offset and row stride of every problem's block, in doubles
+    DevBuf<int> extra;           // relevance: the same rows by (row index mod 256), what the culled row test iterates; solver: the torque rows [B][tq_cap]
+    std::vector<int> h_count, h_tq_count;   // host copies of the counts (h_tq_count: the solver's lists only)
+    int max_count = 0;
+    bool fresh = false;          // built for the current problem set (begin_problem_set clears it)
+    double ms = 0;
 };
 
 struct ArmourPlanner {
@@ -143,8 +135,7 @@ struct ArmourPlanner {
     bool no_torque() const { return mode == ARMOUR_MODE_ARMTD || params.input_constraints_off != 0; }
     int row0 = 0;                   // rows before the collision block (n*T torque rows, or 0 in ARMTD mode)
     std::vector<double> h_krange;   // ARMTD mode: [B][n] acceleration range of each problem's JRS tables
-    double* d_jrs = nullptr;        // ARMTD mode: [B][n][6][T] c/g/r of cos, then of sin (the order of armtd.in)
-    size_t jrs_cap = 0;
+    DevBuf<double> d_jrs;           // ARMTD mode: [B][n][6][T] c/g/r of cos, then of sin (the order of armtd.in)
     // page-locked host scratch of armour_solve (k, g, jac mirrors), grown on demand and kept across solves
     void* solve_pin[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // k, g, jac mirrors; violation sums, row counts, compact rows; [6] k and [7] records of armour_eval_violations; [8] the reach-set build's read-back, [9] its status words
     size_t solve_pin_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -156,68 +147,47 @@ struct ArmourPlanner {
     double tuning[ARMOUR_OPT_LAST_TUNING - ARMOUR_OPT_FIRST_TUNING + 1];
     int tune(int option) const { return (int)tuning[option - ARMOUR_OPT_FIRST_TUNING]; }
     double tune_f(int option) const { return tuning[option - ARMOUR_OPT_FIRST_TUNING]; }
-    ArmourViolation* d_viol = nullptr; size_t viol_cap = 0;   // [B] records of armour_eval_violations
-    // row relevance of the current problem set (relevance.hip): the mask [B][m], the relevant collision rows of every problem in ascending
-    // order [B][Q] and their counts; built on first use (armour_get_row_relevance, the culled armour_eval_violations)
-    unsigned char* d_rel = nullptr; size_t rel_cap = 0;
-    int* d_rel_rows = nullptr; size_t rel_rows_cap = 0;
-    int* d_rel_count = nullptr; size_t rel_count_cap = 0;
-    double* d_rel_packed = nullptr; size_t rel_packed_cap = 0;       // the listed rows' plane entries, packed (relevance.hip)
-    long long* d_rel_pack_off = nullptr; size_t rel_pack_off_cap = 0;   // [B][2]: offset and row stride of every problem's block, in doubles
-    int* d_rel_rows_res = nullptr; size_t rel_rows_res_cap = 0;   // the same rows by (row index mod 256): what the culled row test iterates
-    std::vector<int> h_rel_count;
-    // the solver's mask (rows that can pass armour_solve's candidate filter for some k), its row list, packed entries and torque tile list
-    unsigned char* d_rel2 = nullptr; size_t rel2_cap = 0;
-    int* d_rel2_rows = nullptr; size_t rel2_rows_cap = 0;
-    int* d_rel2_count = nullptr; size_t rel2_count_cap = 0;        // [B] listed collision rows | [B] listed torque tiles
-    double* d_rel2_packed = nullptr; size_t rel2_packed_cap = 0;
-    long long* d_rel2_pack_off = nullptr; size_t rel2_pack_off_cap = 0;
-    int* d_rel2_tq_tiles = nullptr; size_t rel2_tq_tiles_cap = 0;  // [B][rel2_tq_cap]
-    std::vector<int> h_rel2_count, h_rel2_tq_count;
-    bool rel2_fresh = false;
-    double rel2_ms = 0;
-    int rel2_max_count = 0, rel2_tq_cap = 0;
-    bool rel_fresh = false;
-    double rel_ms = 0;
-    int rel_max_count = 0;
-    unsigned char* d_sweep = nullptr; size_t sweep_cap = 0;   // armour_sweep's device block: candidates | cost coefficients | records | best (sweep.hip)
+    DevBuf<ArmourViolation> d_viol;   // [B] records of armour_eval_violations
+    RelLists rel, rel2;      // the relevance lists and the solver's (rel2.mask is filled together with rel.mask)
+    int rel2_tq_cap = 0;
+    DevBuf<unsigned char> d_sweep;   // armour_sweep's device block: candidates | cost coefficients | records | best (sweep.hip)
     SolveDeviceWork solve_dev;
-    double* d_bounds = nullptr;      // [2][B][m] g_l, g_u for the solver's device-side scan (uploaded on the first solve of a problem set)
+    DevBuf<double> d_bounds;         // [2][B][m] g_l, g_u for the solver's device-side scan (uploaded on the first solve of a problem set)
     bool bounds_on_device = false, bounds_on_host = false;
     bool tables_from_host = false;   // armour_debug_load_tables: plane normals are the caller's, not necessarily unit vectors (relevance.hip)
     std::vector<double> h_gl, h_gu;  // host copy of the same bounds (valid while bounds_on_host: the host-driven solver form fills it)
     std::vector<double> h_q0, h_qd0, h_qdd0, h_qdes;  // [B][n]
     std::vector<double> h_torque_radius;              // [B][n][T]
-    double* d_tr_stage = nullptr; size_t tr_stage_cap = 0;   // the same on the device, for the kernel that fills the bounds (armour_upload_bounds)
+    DevBuf<double> d_tr_stage;   // the same on the device, for the kernel that fills the bounds (armour_upload_bounds)
     std::vector<double> h_link_gens;                  // [B][T][J][18]
     std::vector<unsigned long long> h_plane_skip;     // [B] host copy of d_plane_skip
     std::vector<double> h_prune_margin;               // [B] how close the last build's simplify() verdicts came to flipping (armour_get_prune_margin)
     // device tables (sized for allocB x allocO)
     int allocB = 0, allocO = 0;
-    int* d_link_count = nullptr;
-    double* d_link_center = nullptr;
-    double* d_link_indep = nullptr;
-    uint32_t* d_link_keys = nullptr;
-    double* d_link_coeff = nullptr;
-    int* d_tq_count = nullptr;
-    double* d_tq_center = nullptr;
-    double* d_tq_indep = nullptr;
-    uint32_t* d_tq_keys = nullptr;
-    double* d_tq_coeff = nullptr;
-    double* d_planes = nullptr;
-    double* d_obs_center = nullptr;
+    DevBuf<int> d_link_count;
+    DevBuf<double> d_link_center;
+    DevBuf<double> d_link_indep;
+    DevBuf<uint32_t> d_link_keys;
+    DevBuf<double> d_link_coeff;
+    DevBuf<int> d_tq_count;
+    DevBuf<double> d_tq_center;
+    DevBuf<double> d_tq_indep;
+    DevBuf<uint32_t> d_tq_keys;
+    DevBuf<double> d_tq_coeff;
+    DevBuf<double> d_planes;
+    DevBuf<double> d_obs_center;
     int d_from_center = 0;  // the d column of the table is exactly A.c of the stored normals and obs_center (tables built by P1)
     int planes_lean = 0;    // the table holds only what the fused evaluation reads (p1_reach.hip planes_of_group); armour_get_hyperplanes rebuilds the full one
     int planes_have_d = 1;  // its d column is stored (loaded tables, full tables, lean tables of < 8 problems)
     double planes_ms = 0;   // device time of the half-space kernels of the last build
-    double* d_planes_ll = nullptr;
+    DevBuf<double> d_planes_ll;
     int ll_shared = 0;  // the link x link normals of the loaded table are identical over the obstacles (always so for tables built by P1)
-    unsigned long long* d_plane_skip = nullptr;
-    double* d_bez = nullptr;
+    DevBuf<unsigned long long> d_plane_skip;
+    DevBuf<double> d_bez;
     // staging for the host-pointer API
-    double* d_k = nullptr;
-    double* d_g = nullptr;
-    double* d_jac = nullptr;
+    DevBuf<double> d_k;
+    DevBuf<double> d_g;
+    double* d_jac = nullptr;   // inside d_g's allocation, directly behind the g of the current problem set
     double build_ms = 0;
     // where the LAST build's search for a launch shape ended (a sort-buffer overflow sends a build to the next larger shape): the next build of this
     // handle -- the same robot, a similar problem -- starts there instead of repeating the failed launches (8-factor arms on the halved key buffers of
@@ -248,9 +218,6 @@ int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const uns
                      int steps = 1, long long k_stride = 0, long long g_stride = 0, long long j_stride = 0, bool skip_collision_blocks = false);
 // relevance.hip
 int armour_relevance_build(ArmourPlanner* h, bool for_solver);   // (relevance.hip; for_solver: also the lists armour_solve's culled device form walks)
-void armour_relevance_free(ArmourPlanner* h);
-// sweep.hip
-void armour_sweep_free(ArmourPlanner* h);
 int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourViolation* d_out, hipStream_t st);
 int armour_refresh_table_stats(ArmourPlanner* h);
 // collision rows the feasibility re-check looks at (all Q in ARMOUR mode; the first (n-1)*T*O in ARMTD mode, CMP/NLPclass.cu:391-402)

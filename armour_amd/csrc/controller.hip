@@ -153,24 +153,14 @@ struct CtlCache {
     ArmourRobot rb;
     double eps = 0, Kr[ARMOUR_MAX_FACTORS] = {0}, alpha = 0, V_max = 0, r_thr = 0;
     int n = 0, device = -1;
-    CtlArgs* d_args = nullptr;
-    double* d_buf = nullptr; size_t d_cap = 0;   // doubles
+    // (the owners' destructors run at thread or process exit, when the runtime may already be gone: errors are ignored)
+    DevStream stream;
+    DevBuf<CtlArgs> d_args;
+    DevBuf<double> d_buf;
     double* h_pin = nullptr; size_t h_cap = 0;   // doubles
-    hipStream_t stream = nullptr;
-    ~CtlCache() {
-        // (process exit: the runtime may already be gone; errors are ignored)
-        if (d_args) (void)hipFree(d_args);
-        if (d_buf) (void)hipFree(d_buf);
-        if (h_pin) (void)hipHostFree(h_pin);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~CtlCache() { if (h_pin) (void)hipHostFree(h_pin); }
 };
 thread_local CtlCache g_ctl;
-
-bool finite_all(const double* x, size_t count) {
-    for (size_t i = 0; i < count; i++) if (!std::isfinite(x[i])) return false;
-    return true;
-}
 
 constexpr int kSplitMaxStates = kSplitStates * 256;   // up to one four-wave block per CU
 constexpr size_t kStagedDoubles = (size_t)1 << 20;  // calls up to this many input doubles go through the page-locked buffer
@@ -203,14 +193,14 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
     if (c.device != dev) {  // first call of this thread, or the caller switched devices: start over
-        if (c.d_args) { (void)hipFree(c.d_args); c.d_args = nullptr; }
-        if (c.d_buf) { (void)hipFree(c.d_buf); c.d_buf = nullptr; c.d_cap = 0; }
-        if (c.stream) { (void)hipStreamDestroy(c.stream); c.stream = nullptr; }
+        c.d_args.release();
+        c.d_buf.release();
+        c.stream.release();
         c.have_model = false;
         c.device = dev;
     }
-    if (!c.stream) HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    if (!c.d_args) HIPCHK(hipMalloc((void**)&c.d_args, sizeof(CtlArgs)));
+    ARMOUR_TRY(c.stream.create());
+    ARMOUR_TRY(c.d_args.reserve(1));
     bool same = c.have_model && memcmp(&c.rb, robot, sizeof(ArmourRobot)) == 0 && c.eps == model_uncertainty && c.alpha == alpha && c.V_max == V_max &&
                 c.r_thr == r_norm_threshold;
     for (int i = 0; same && i < nf; i++) same = c.Kr[i] == Kr[i];
@@ -227,11 +217,7 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
     }
     const int n = c.n;
     const size_t bn = (size_t)B * n, total = 8 * bn + 1;  // 5 inputs | 3 outputs | status word
-    if (total > c.d_cap) {
-        if (c.d_buf) { (void)hipFree(c.d_buf); c.d_buf = nullptr; c.d_cap = 0; }
-        HIPCHK(hipMalloc((void**)&c.d_buf, total * sizeof(double)));
-        c.d_cap = total;
-    }
+    ARMOUR_TRY(c.d_buf.reserve(total));
     double* d_in = c.d_buf;
     double* d_out = c.d_buf + 5 * bn;
     int* d_status = reinterpret_cast<int*>(c.d_buf + 8 * bn);

@@ -1,0 +1,137 @@
+// Host-side owners of what every entry point holds on the device -- buffers, a stream, a pair of timing events -- and the
+// argument checks the entries share.  Host code only: nothing here is seen by a kernel.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+
+#include "../../include/armour_hip.h"
+
+void armour_set_error(const char* fmt, ...);
+
+#define HIPCHK(expr)                                                                                     \
+    do {                                                                                                 \
+        hipError_t e__ = (expr);                                                                         \
+        if (e__ != hipSuccess) {                                                                         \
+            armour_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return ARMOUR_EDEVICE;                                                                       \
+        }                                                                                                \
+    } while (0)
+
+// for the calls that have reported their error already (reserve, upload, the event pair, ...)
+#define ARMOUR_TRY(expr)                            \
+    do {                                            \
+        const int rc__ = (expr);                    \
+        if (rc__ != ARMOUR_OK) return rc__;         \
+    } while (0)
+
+// An owning device buffer of `cap` elements; converts to its pointer wherever one is expected.  The ONE way to size a device buffer:
+// reserve() keeps the buffer when need <= cap and otherwise frees it and allocates max(need, 1) elements (the contents are lost; a buffer
+// that was never allocated counts as too small for any need, so the pointer is not null after a reserve that succeeded).
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    template <class U> U* as() const { return reinterpret_cast<U*>(p); }   // a block of bytes that holds records
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    // `fresh`, if given: set when the buffer was allocated anew
+    int reserve(size_t need, bool* fresh = nullptr) {
+        if (p && need <= cap) return ARMOUR_OK;
+        release();
+        const size_t count = need ? need : 1;
+        HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
+        cap = count;
+        if (fresh) *fresh = true;
+        return ARMOUR_OK;
+    }
+    int upload(const T* src, size_t count, hipStream_t st) {
+        ARMOUR_TRY(reserve(count));
+        if (count && src) HIPCHK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+        return ARMOUR_OK;
+    }
+};
+
+// a non-blocking stream of the one-shot entries and of the handles that are not planners
+struct DevStream {
+    hipStream_t s = nullptr;
+    DevStream() = default;
+    DevStream(const DevStream&) = delete;
+    DevStream& operator=(const DevStream&) = delete;
+    ~DevStream() { release(); }
+    operator hipStream_t() const { return s; }
+    void release() {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
+    int create() {
+        if (!s) HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return ARMOUR_OK;
+    }
+};
+
+// two events around a piece of a stream's work, created on first use
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    int record_start(hipStream_t st) {
+        if (!e0) HIPCHK(hipEventCreate(&e0));
+        if (!e1) HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, st));
+        return ARMOUR_OK;
+    }
+    int record_stop(hipStream_t st) {
+        HIPCHK(hipEventRecord(e1, st));
+        return ARMOUR_OK;
+    }
+    // (both events must have completed: the caller has synchronised the stream)
+    int elapsed_ms(double* ms) {
+        float f = 0.f;
+        HIPCHK(hipEventElapsedTime(&f, e0, e1));
+        *ms = f;
+        return ARMOUR_OK;
+    }
+};
+
+// ---- argument checks (no device call: they run before an entry touches the device)
+// index of the first entry that is not finite, `count` if there is none
+inline size_t first_nonfinite(const double* x, size_t count) {
+    size_t i = 0;
+    while (i < count && std::isfinite(x[i])) i++;
+    return i;
+}
+inline bool finite_all(const double* x, size_t count) { return first_nonfinite(x, count) == count; }
+
+// joints and factors a robot may have: 1 <= factors <= joints, within the compiled maxima
+inline bool armour_robot_shape_ok(const ArmourRobot* robot) {
+    return robot->num_factors >= 1 && robot->num_factors <= ARMOUR_MAX_FACTORS && robot->num_joints >= robot->num_factors && robot->num_joints <= ARMOUR_MAX_JOINTS;
+}
+inline int armour_check_robot_shape(const char* who, const ArmourRobot* robot) {
+    if (armour_robot_shape_ok(robot)) return ARMOUR_OK;
+    armour_set_error("%s: robot has %d joints, %d factors", who, robot->num_joints, robot->num_factors);
+    return ARMOUR_EINVAL;
+}
+// W worlds of O obstacles each, as the roadmap check and the path audit take them
+inline int armour_check_world_counts(const char* who, int32_t W, int32_t O, const double* obstacles) {
+    if (W >= 0 && W <= 65535 && O >= 0 && O <= ARMOUR_ROADMAP_MAX_OBSTACLES && !(W > 0 && O > 0 && !obstacles)) return ARMOUR_OK;
+    armour_set_error("%s: W = %d (0..65535), O = %d (0..%d)", who, W, O, ARMOUR_ROADMAP_MAX_OBSTACLES);
+    return ARMOUR_EINVAL;
+}

@@ -1792,18 +1792,15 @@ constexpr int kMaxPoolDevices = 64;
 TvArenaPool g_tv_pool[kMaxPoolDevices];
 
 struct P1Work {
-    unsigned char* arena = nullptr;
-    size_t arena_total = 0;
-    unsigned* d_status = nullptr;
-    double* d_link_gens = nullptr; size_t gens_cap = 0;
-    double* d_torque_radius = nullptr; size_t tr_cap = 0;
-    double* d_obstacles = nullptr; size_t obs_cap = 0;
-    int* d_retry = nullptr; size_t retry_cap = 0;  // [1 + B*T]: count, then item indices
-    unsigned long long* d_skip_part = nullptr; size_t skip_part_cap = 0;  // [B][blocks per problem][4 waves]: the planes kernel's masks before the AND
-    unsigned long long* d_margin = nullptr; size_t margin_cap = 0;   // [B]: the prune margin word of every problem (P1Cfg::margin)
-    long long* d_phase = nullptr;   // ARMOUR_P1_TRACE: [1024][8] phase clocks of the last launch's blocks (P1Cfg::phase_log), allocated on first use
-    unsigned char* d_xch = nullptr; size_t xch_cap = 0; int xch_epoch = 0;   // a time step on two CUs: kXchBytes per item, flags tagged with the launch's epoch (cleared when allocated and when the epoch wraps)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // around the reach-set kernel | around the half-space kernels
+    DevBuf<unsigned char> arena;
+    DevBuf<unsigned> d_status;
+    DevBuf<double> d_link_gens, d_torque_radius, d_obstacles;
+    DevBuf<int> d_retry;  // [1 + B*T]: count, then item indices
+    DevBuf<unsigned long long> d_skip_part;  // [B][blocks per problem][4 waves]: the planes kernel's masks before the AND
+    DevBuf<unsigned long long> d_margin;   // [B]: the prune margin word of every problem (P1Cfg::margin)
+    DevBuf<long long> d_phase;   // ARMOUR_P1_TRACE: [1024][8] phase clocks of the last launch's blocks (P1Cfg::phase_log), allocated on first use
+    DevBuf<unsigned char> d_xch; int xch_epoch = 0;   // a time step on two CUs: kXchBytes per item, flags tagged with the launch's epoch (cleared when allocated and when the epoch wraps)
+    EventPair ev_chain, ev_planes;   // around the reach-set kernel | around the half-space kernels
 };
 
 #endif  // P1_TV_VARIANT
@@ -1850,20 +1847,6 @@ void armour_p1_free(ArmourPlanner* h) {
             if (pool.ptr) { (void)hipSetDevice(h->device); (void)hipFree(pool.ptr); pool.ptr = nullptr; pool.bytes = 0; }
         }
     }
-    if (wk->arena) (void)hipFree(wk->arena);
-    if (wk->d_status) (void)hipFree(wk->d_status);
-    if (wk->d_link_gens) (void)hipFree(wk->d_link_gens);
-    if (wk->d_torque_radius) (void)hipFree(wk->d_torque_radius);
-    if (wk->d_margin) (void)hipFree(wk->d_margin);
-    if (wk->d_xch) (void)hipFree(wk->d_xch);
-    if (wk->d_phase) (void)hipFree(wk->d_phase);
-    if (wk->d_obstacles) (void)hipFree(wk->d_obstacles);
-    if (wk->d_skip_part) (void)hipFree(wk->d_skip_part);
-    if (wk->d_retry) (void)hipFree(wk->d_retry);
-    if (wk->ev0) (void)hipEventDestroy(wk->ev0);
-    if (wk->ev1) (void)hipEventDestroy(wk->ev1);
-    if (wk->ev2) (void)hipEventDestroy(wk->ev2);
-    if (wk->ev3) (void)hipEventDestroy(wk->ev3);
     delete wk;
     h->p1 = nullptr;
 }
@@ -2056,8 +2039,7 @@ static int plan_step_launch(const ArmourPlanner* h, int cus, int cap, const int*
 // The launch and the copy of its status words into the page-locked block `st_pin` (a copy into pageable memory would wait by itself), queued and NOT waited for: the caller queues more behind it, waits once and calls finish_step_launch
 static int queue_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, unsigned* st_pin) {
     const Layout L = make_layout(h->J, h->n, h->lim.work_monomials, p.nw);
-    int rc;
-    if ((rc = grow(&wk->arena, &wk->arena_total, (size_t)p.waves * L.total)) != ARMOUR_OK) return rc;
+    ARMOUR_TRY(wk->arena.reserve((size_t)p.waves * L.total));
     P1Cfg cf = p1_cfg_base(h, wk, p.cap);
     cf.arena_bytes = L.total; cf.arena = wk->arena;
     cf.free_running = h->tune(ARMOUR_OPT_P1_STEP_FREE);   // (0 = a barrier per joint)
@@ -2069,9 +2051,9 @@ static int queue_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, un
     cf.queue = cf.queue_order != 0 && p.n_items + p.fk_items > p.waves ? wk->d_status + ST_WORDS + 60 : nullptr;   // (with a block per item there is nothing to draw: B = 1 1.044 against 1.069 ms.  The word: one of the status block that the profile counters of development builds do not reach)
     if (cf.queue) HIPCHK(hipMemsetAsync(cf.queue, 0, sizeof(unsigned), h->stream));
     cf.tail_cross = p.split ? h->tune(ARMOUR_OPT_P1_STEP_TAIL_CROSS) : 0;   // (with its forward kinematics to do the fourth wave has no time to spare)
-    cf.retry_list = p.collect ? wk->d_retry + 1 : nullptr; cf.retry_count = reinterpret_cast<unsigned*>(wk->d_retry);
+    cf.retry_list = p.collect ? wk->d_retry + 1 : nullptr; cf.retry_count = wk->d_retry.as<unsigned>();
     if (p.phase_log) {
-        if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
+        ARMOUR_TRY(wk->d_phase.reserve(1024 * 8));
         HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
         cf.phase_log = wk->d_phase;
     }
@@ -2079,21 +2061,21 @@ static int queue_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, un
     cf.lean_back = h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 1; cf.late_jrs = (h->tune(ARMOUR_OPT_P1_STEP_LEAN_BACK) & 2) == 0;   // (development: + 2 builds every joint before the roles begin)
     if (p.two_cu) {
         bool clear = false;
-        if ((rc = grow(&wk->d_xch, &wk->xch_cap, (size_t)p.n_items * kXchBytes, &clear)) != ARMOUR_OK) return rc;
+        ARMOUR_TRY(wk->d_xch.reserve((size_t)p.n_items * kXchBytes, &clear));
         if (++wk->xch_epoch >= (1 << 23)) { wk->xch_epoch = 1; clear = true; }
-        if (clear) HIPCHK(hipMemsetAsync(wk->d_xch, 0, wk->xch_cap, h->stream));
+        if (clear) HIPCHK(hipMemsetAsync(wk->d_xch, 0, wk->d_xch.cap, h->stream));
         cf.xch = wk->d_xch; cf.xch_epoch = wk->xch_epoch;
     }
     HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
     if (p.collect) HIPCHK(hipMemsetAsync(wk->d_retry, 0, sizeof(int), h->stream));
-    HIPCHK(hipEventRecord(wk->ev0, h->stream));
+    ARMOUR_TRY(wk->ev_chain.record_start(h->stream));
     {
         std::lock_guard<std::mutex> lk(g_p1_launch_mu);
         if (p.nw == 4) HIPCHK(p1_launch(armour_p1_chain_kernel<4>, 4, p.waves, p.smem, h->stream, cf));
         else if (p.nw == kRoles) HIPCHK(p1_launch(armour_p1_chain_kernel<kRoles>, kRoles, p.waves, p.smem, h->stream, cf));
         else HIPCHK(p1_launch(armour_p1_chain_kernel<1>, 1, p.waves, p.smem, h->stream, cf));
     }
-    HIPCHK(hipEventRecord(wk->ev1, h->stream));
+    ARMOUR_TRY(wk->ev_chain.record_stop(h->stream));
     HIPCHK(hipMemcpyAsync(st_pin, wk->d_status, ST_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     armour_build_stamp("launch-queued");
     return ARMOUR_OK;
@@ -2127,9 +2109,9 @@ static int report_step_phases(const P1Work* wk, const StepPlan& p) {
 // After the caller's wait: the launch's status words into `st`, its device time onto *total_ms, build_info, the ARMOUR_P1_TRACE lines
 static int finish_step_launch(ArmourPlanner* h, P1Work* wk, const StepPlan& p, const unsigned* st_pin, unsigned* st, float* total_ms) {
     memcpy(st, st_pin, ST_WORDS * sizeof(unsigned));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
-    *total_ms += ms;
+    double ms = 0;
+    ARMOUR_TRY(wk->ev_chain.elapsed_ms(&ms));
+    *total_ms += (float)ms;
     h->build_info[0] = ARMOUR_P1_KERNEL_PER_STEP; h->build_info[1] = p.nw; h->build_info[2] = p.cap; h->build_info[3]++;
 #ifdef P1_PROFILE
     unsigned long long pr[PR_WORDS];
@@ -2168,11 +2150,11 @@ static int step_pass_verdict(ArmourPlanner* h, unsigned* st, int* cap_raw, bool*
 // ---- the half-space kernels, queued behind the reach sets
 static int queue_planes(ArmourPlanner* h, P1Work* wk) {
     const int B = h->B, T = h->T, J = h->J, O = h->O, Q = J * T * O;
-    HIPCHK(hipEventRecord(wk->ev2, h->stream));
+    ARMOUR_TRY(wk->ev_planes.record_start(h->stream));
     const int nbx = (Q + 63) / 64, nbc = (Q + 255) / 256;
     // [B][nbx][4] per-wave masks of the planes kernel | [B][nbc] per-block masks of the class pre-pass | [B] its result | [B] planes a sampled row needs
     const size_t part_words = (size_t)B * nbx * 4, pre_words = (size_t)B * nbc;
-    if (const int rc = grow(&wk->d_skip_part, &wk->skip_part_cap, part_words + pre_words + 2 * (size_t)B); rc != ARMOUR_OK) return rc;
+    ARMOUR_TRY(wk->d_skip_part.reserve(part_words + pre_words + 2 * (size_t)B));
     unsigned long long* d_pre_part = wk->d_skip_part + part_words;
     unsigned long long* d_pre = d_pre_part + pre_words;
     unsigned long long* d_live = d_pre + B;
@@ -2196,7 +2178,7 @@ static int queue_planes(ArmourPlanner* h, P1Work* wk) {
     h->ll_shared = 1; h->d_from_center = 1;
     h->planes_lean = lean ? 1 : 0; h->planes_have_d = (!lean || store_d) ? 1 : 0;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(wk->ev3, h->stream));
+    ARMOUR_TRY(wk->ev_planes.record_stop(h->stream));
     return ARMOUR_OK;
 }
 
@@ -2296,7 +2278,7 @@ static int build_time_vectorised(ArmourPlanner* h, P1Work* wk, int cus, float* t
             if (max_blocks < 1.0) continue;   // (not even one block of this shape: the next shape, in the end the per-step kernel)
             blocks = (int)std::min((double)blocks, max_blocks);
         }
-        // (not grow(): an arena the device cannot give ends the shape search -- the per-step kernel builds the batch -- instead of the build)
+        // (not a DevBuf: an arena the device cannot give ends the shape search -- the per-step kernel builds the batch -- instead of the build)
         if ((size_t)blocks * TL.total > pool.bytes) {
             if (pool.ptr) (void)hipFree(pool.ptr);
             pool.ptr = nullptr; pool.bytes = 0;
@@ -2312,23 +2294,23 @@ static int build_time_vectorised(ArmourPlanner* h, P1Work* wk, int cus, float* t
         cf.tv_aux_on_fk_wave = h->tune(ARMOUR_OPT_P1_TV_AUX3);
         cf.tail_cross = h->tune(ARMOUR_OPT_P1_TV_TAIL_CROSS);
         if (armour_trace_p1() && blocks <= 1024) {   // when each block's (last) item began and ended: the spread between the groups
-            if (!wk->d_phase) HIPCHK(hipMalloc((void**)&wk->d_phase, 1024 * 8 * sizeof(long long)));
+            ARMOUR_TRY(wk->d_phase.reserve(1024 * 8));
             HIPCHK(hipMemsetAsync(wk->d_phase, 0, 1024 * 8 * sizeof(long long), h->stream));
             cf.phase_log = wk->d_phase;
         }
         unsigned st[ST_WORDS];
         HIPCHK(hipMemsetAsync(wk->d_status, 0, ST_WORDS * sizeof(unsigned), h->stream));
-        HIPCHK(hipEventRecord(wk->ev0, h->stream));
+        ARMOUR_TRY(wk->ev_chain.record_start(h->stream));
         {
             std::lock_guard<std::mutex> lk(g_p1_launch_mu);
             HIPCHK(gr == 64 ? armour_p1_tv_launch_g64(nw_launch, nw, blocks, smem, h->stream, &cf) : armour_p1_tv_launch_g50(nw_launch, nw, blocks, smem, h->stream, &cf));
         }
-        HIPCHK(hipEventRecord(wk->ev1, h->stream));
+        ARMOUR_TRY(wk->ev_chain.record_stop(h->stream));
         HIPCHK(hipMemcpyAsync(st, wk->d_status, sizeof(st), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(p1_wait_stream(h->stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, wk->ev0, wk->ev1));
-        *total_ms += ms;
+        double ms = 0;
+        ARMOUR_TRY(wk->ev_chain.elapsed_ms(&ms));
+        *total_ms += (float)ms;
         h->build_info[0] = ARMOUR_P1_KERNEL_TIME_VECTORISED; h->build_info[1] = nw_launch; h->build_info[2] = cap; h->build_info[3]++;
         if (const int rc = cf.phase_log ? report_tv_phases(cf.phase_log, blocks, G, rnea_items) : ARMOUR_OK; rc != ARMOUR_OK) return rc;
         if (armour_trace_p1()) fprintf(stderr, "[P1 tv] %d groups of <= %d steps%s, sort cap %d: %d blocks of %d wave(s) (%d per CU, %zu B LDS, %d / %d staging rows, %.1f MB arena each, rows of %d), %.2f ms, flags 0x%x, max raw terms %u, max monomials %u\n", groups, LG, fk_items ? " (+ as many forward-kinematics items)" : "", cap, blocks, nw_launch, per_cu, smem, stage_rows, stage_other, TL.total / 1048576.0, gr, ms, st[ST_ERR], st[ST_MAX_RAW], st[ST_MAX_OUT]);
@@ -2343,19 +2325,15 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
         P1Work* nw = new P1Work();
         h->p1 = nw;
         { TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices]; std::lock_guard<std::mutex> lk(pool.mu); pool.users++; }
-        HIPCHK(hipMalloc((void**)&nw->d_status, (ST_WORDS + 64) * sizeof(unsigned)));
-        HIPCHK(hipEventCreate(&nw->ev0));
-        HIPCHK(hipEventCreate(&nw->ev1));
-        HIPCHK(hipEventCreate(&nw->ev2));
-        HIPCHK(hipEventCreate(&nw->ev3));
     }
     P1Work* wk = (P1Work*)h->p1;
     const int B = h->B, T = h->T, J = h->J, n = h->n, O = h->O;
     int rc;
-    if ((rc = grow(&wk->d_link_gens, &wk->gens_cap, (size_t)B * T * J * 18)) != ARMOUR_OK) return rc;
-    if ((rc = grow(&wk->d_torque_radius, &wk->tr_cap, (size_t)B * n * T)) != ARMOUR_OK) return rc;
-    if ((rc = grow(&wk->d_margin, &wk->margin_cap, (size_t)B)) != ARMOUR_OK) return rc;
-    if ((rc = grow(&wk->d_obstacles, &wk->obs_cap, (size_t)B * O * 12)) != ARMOUR_OK) return rc;
+    ARMOUR_TRY(wk->d_status.reserve(ST_WORDS + 64));
+    ARMOUR_TRY(wk->d_link_gens.reserve((size_t)B * T * J * 18));
+    ARMOUR_TRY(wk->d_torque_radius.reserve((size_t)B * n * T));
+    ARMOUR_TRY(wk->d_margin.reserve((size_t)B));
+    ARMOUR_TRY(wk->d_obstacles.reserve((size_t)B * O * 12));
     if (O > 0) HIPCHK(hipMemcpyAsync(wk->d_obstacles, obstacles, (size_t)B * O * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     armour_build_stamp("buffers+obstacles");
 
@@ -2368,7 +2346,7 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     }
     int cap_raw = 64;
     while (cap_raw < h->lim.raw_terms || cap_raw < h->p1_step_cap_hint) cap_raw <<= 1;   // (the hint: what the last build of this handle ended up with)
-    if ((rc = grow(&wk->d_retry, &wk->retry_cap, (size_t)1 + (size_t)B * T)) != ARMOUR_OK) return rc;
+    ARMOUR_TRY(wk->d_retry.reserve((size_t)1 + (size_t)B * T));
     const Layout L4 = make_layout(J, n, h->lim.work_monomials, 4);
     if (L4.idJS + L4.nJS > kMaxSlots) { armour_set_error("slot table too small"); return ARMOUR_EINVAL; }
     float total_ms = 0;
@@ -2434,9 +2412,9 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
         again = false;
         if (chain && ((rc = finish_step_launch(h, wk, plan, st_pin, st, &total_ms)) != ARMOUR_OK || (rc = step_pass_verdict(h, st, &cap_raw, &again)) != ARMOUR_OK)) return rc;
         if (!again && O > 0) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, wk->ev2, wk->ev3));
-            total_ms += ms;
+            double ms = 0;
+            ARMOUR_TRY(wk->ev_planes.elapsed_ms(&ms));
+            total_ms += (float)ms;
             h->planes_ms = ms;
         }
     }

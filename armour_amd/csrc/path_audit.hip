@@ -125,32 +125,6 @@ __global__ __launch_bounds__(PA_BLOCK) void path_audit_kernel(RmRobot rb, PaPiec
     else if (state == 2) undecided[p] = 1;
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t upload(const T* src, size_t count, hipStream_t st) {
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess || !count || !src) return e;
-        return hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st);
-    }
-};
-
-struct DevState {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~DevState() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-bool finite_all(const double* x, size_t count) {
-    for (size_t i = 0; i < count; i++) if (!std::isfinite(x[i])) return false;
-    return true;
-}
-
 // What both entries share: the argument checks and the work list (pieces in world order, their sub-interval offsets).
 struct AuditPlan {
     RmRobot rb;
@@ -167,14 +141,8 @@ int make_plan(const char* who, const ArmourRobot* robot, int32_t W, int32_t O, c
         armour_set_error("%s: null argument", who);
         return ARMOUR_EINVAL;
     }
-    if (robot->num_factors < 1 || robot->num_factors > ARMOUR_MAX_FACTORS || robot->num_joints < robot->num_factors || robot->num_joints > ARMOUR_MAX_JOINTS) {
-        armour_set_error("%s: robot has %d joints, %d factors", who, robot->num_joints, robot->num_factors);
-        return ARMOUR_EINVAL;
-    }
-    if (W < 0 || W > 65535 || O < 0 || O > ARMOUR_ROADMAP_MAX_OBSTACLES || (W > 0 && O > 0 && !obstacles)) {
-        armour_set_error("%s: W = %d (0..65535), O = %d (0..%d)", who, W, O, ARMOUR_ROADMAP_MAX_OBSTACLES);
-        return ARMOUR_EINVAL;
-    }
+    ARMOUR_TRY(armour_check_robot_shape(who, robot));
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
     if (!(step > 0.0) || !std::isfinite(step) || !(duration > 0.0) || !std::isfinite(duration)) {
         armour_set_error("%s: step = %g, duration = %g (both must be positive)", who, step, duration);
         return ARMOUR_EINVAL;
@@ -274,11 +242,8 @@ extern "C" int armour_path_audit_host(const ArmourRobot* robot, int32_t W, int32
     int rc = make_plan("armour_path_audit_host", robot, W, O, obstacles, P, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, verdict, &pl);
     if (rc != ARMOUR_OK) return rc;
     if ((rc = sort_pieces("armour_path_audit_host", &pl, world_of_piece, P, &sd)) != ARMOUR_OK) return rc;
-    std::vector<double> obs((size_t)W * O * RM_OBS_STRIDE, 0.0);   // staged as the kernel stages them
-    for (size_t o = 0; o < (size_t)W * O; o++) {
-        std::memcpy(&obs[o * RM_OBS_STRIDE], obstacles + o * ARMOUR_OBS_DOUBLES, ARMOUR_OBS_DOUBLES * sizeof(double));
-        obstacle_normals(obstacles + o * ARMOUR_OBS_DOUBLES, &obs[o * RM_OBS_STRIDE + 12]);
-    }
+    std::vector<double> obs((size_t)W * O * RM_OBS_STRIDE);   // staged as the kernel stages them
+    stage_obstacles(obstacles, (size_t)W * O, obs.data());
     std::vector<int32_t> first_hit(P, PA_NO_HIT);
     std::vector<uint8_t> undecided(P, 0);
     std::vector<double> item_clear(clearance ? (size_t)pl.items : 0);
@@ -330,51 +295,46 @@ extern "C" int armour_path_audit(const ArmourRobot* robot, int32_t W, int32_t O,
     if (P > 0) {
         // ---- the device
         if (!armour_device_available()) { armour_set_error("armour_path_audit: no HIP device visible (there is no CPU path)"); return ARMOUR_EDEVICE; }
-        DevState d;
-        HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreate(&d.ev0));
-        HIPCHK(hipEventCreate(&d.ev1));
+        DevStream st;
+        EventPair ev;
+        ARMOUR_TRY(st.create());
         DevBuf<double> d_q0, d_qd0, d_qdd0, d_k, d_ta, d_tb, d_tube, d_obs, d_clear;
         DevBuf<int32_t> d_blk_world, d_blk_count, d_item_piece, d_first_hit;
         DevBuf<int64_t> d_blk_item0, d_piece_off;
         DevBuf<uint8_t> d_undecided;
         const size_t pn = (size_t)P * n;
-        HIPCHK(d_q0.upload(pl.pc.q0, pn, d.stream));
-        HIPCHK(d_qd0.upload(pl.pc.qd0, pn, d.stream));
-        HIPCHK(d_qdd0.upload(pl.pc.qdd0, pn, d.stream));
-        HIPCHK(d_k.upload(pl.pc.k, pn, d.stream));
-        HIPCHK(d_ta.upload(pl.pc.ta, P, d.stream));
-        HIPCHK(d_tb.upload(pl.pc.tb, P, d.stream));
-        if (tube) HIPCHK(d_tube.upload(pl.pc.tube, pn, d.stream));
-        HIPCHK(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, d.stream));
-        HIPCHK(d_blk_world.upload(blk_world.data(), blk_world.size(), d.stream));
-        HIPCHK(d_blk_count.upload(blk_count.data(), blk_count.size(), d.stream));
-        HIPCHK(d_blk_item0.upload(blk_item0.data(), blk_item0.size(), d.stream));
-        HIPCHK(d_item_piece.upload(item_piece.data(), item_piece.size(), d.stream));
-        HIPCHK(d_piece_off.upload(pl.piece_off.data(), pl.piece_off.size(), d.stream));
-        HIPCHK(d_first_hit.upload(first_hit.data(), P, d.stream));
-        HIPCHK(d_undecided.upload(undecided.data(), P, d.stream));
-        if (clearance) HIPCHK(d_clear.upload(nullptr, (size_t)items, d.stream));
+        ARMOUR_TRY(d_q0.upload(pl.pc.q0, pn, st));
+        ARMOUR_TRY(d_qd0.upload(pl.pc.qd0, pn, st));
+        ARMOUR_TRY(d_qdd0.upload(pl.pc.qdd0, pn, st));
+        ARMOUR_TRY(d_k.upload(pl.pc.k, pn, st));
+        ARMOUR_TRY(d_ta.upload(pl.pc.ta, P, st));
+        ARMOUR_TRY(d_tb.upload(pl.pc.tb, P, st));
+        if (tube) ARMOUR_TRY(d_tube.upload(pl.pc.tube, pn, st));
+        ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+        ARMOUR_TRY(d_blk_world.upload(blk_world.data(), blk_world.size(), st));
+        ARMOUR_TRY(d_blk_count.upload(blk_count.data(), blk_count.size(), st));
+        ARMOUR_TRY(d_blk_item0.upload(blk_item0.data(), blk_item0.size(), st));
+        ARMOUR_TRY(d_item_piece.upload(item_piece.data(), item_piece.size(), st));
+        ARMOUR_TRY(d_piece_off.upload(pl.piece_off.data(), pl.piece_off.size(), st));
+        ARMOUR_TRY(d_first_hit.upload(first_hit.data(), P, st));
+        ARMOUR_TRY(d_undecided.upload(undecided.data(), P, st));
+        if (clearance) ARMOUR_TRY(d_clear.upload(nullptr, (size_t)items, st));
         PaPieces dpc = pl.pc;
-        dpc.q0 = d_q0.p; dpc.qd0 = d_qd0.p; dpc.qdd0 = d_qdd0.p; dpc.k = d_k.p; dpc.ta = d_ta.p; dpc.tb = d_tb.p;
-        dpc.tube = tube ? d_tube.p : nullptr;
-        HIPCHK(hipEventRecord(d.ev0, d.stream));
+        dpc.q0 = d_q0; dpc.qd0 = d_qd0; dpc.qdd0 = d_qdd0; dpc.k = d_k; dpc.ta = d_ta; dpc.tb = d_tb;
+        dpc.tube = tube ? d_tube : nullptr;
+        ARMOUR_TRY(ev.record_start(st));
         if (!blk_world.empty()) {
             const size_t lds = (size_t)O * RM_OBS_STRIDE * sizeof(double);
-            hipLaunchKernelGGL(path_audit_kernel, dim3((unsigned)blk_world.size()), dim3(PA_BLOCK), lds, d.stream, pl.rb, dpc, d_blk_world.p, d_blk_item0.p,
-                               d_blk_count.p, d_item_piece.p, d_piece_off.p, d_obs.p, O, d_first_hit.p, d_undecided.p, clearance ? d_clear.p : nullptr);
+            hipLaunchKernelGGL(path_audit_kernel, dim3((unsigned)blk_world.size()), dim3(PA_BLOCK), lds, st, pl.rb, dpc, d_blk_world, d_blk_item0,
+                               d_blk_count, d_item_piece, d_piece_off, d_obs, O, d_first_hit, d_undecided, clearance ? d_clear : nullptr);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(d.ev1, d.stream));
-        HIPCHK(hipMemcpyAsync(first_hit.data(), d_first_hit.p, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, d.stream));
-        HIPCHK(hipMemcpyAsync(undecided.data(), d_undecided.p, (size_t)P, hipMemcpyDeviceToHost, d.stream));
-        if (clearance && items) HIPCHK(hipMemcpyAsync(item_clear.data(), d_clear.p, (size_t)items * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCHK(hipStreamSynchronize(d.stream));
-        if (ms) {
-            float f = 0.f;
-            HIPCHK(hipEventElapsedTime(&f, d.ev0, d.ev1));
-            *ms = f;
-        }
+        ARMOUR_TRY(ev.record_stop(st));
+        HIPCHK(hipMemcpyAsync(first_hit.data(), d_first_hit, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(undecided.data(), d_undecided, (size_t)P, hipMemcpyDeviceToHost, st));
+        if (clearance && items) HIPCHK(hipMemcpyAsync(item_clear.data(), d_clear, (size_t)items * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
     }
     finish(pl, P, first_hit.data(), undecided.data(), item_clear.data(), verdict, t_hit, clearance);
     return ARMOUR_OK;
@@ -383,7 +343,7 @@ extern "C" int armour_path_audit(const ArmourRobot* robot, int32_t W, int32_t O,
 extern "C" int armour_path_audit_items(const ArmourRobot* robot, int32_t P, const double* q0, const double* qd0, const double* qdd0, const double* k,
                                        const double* k_range, double duration, const double* ta, const double* tb, double step, int64_t* items) {
     if (!robot || !k_range || !items || P < 0 || (P > 0 && (!q0 || !qd0 || !qdd0 || !k || !ta || !tb)) || !(step > 0.0) || !(duration > 0.0) ||
-        robot->num_factors < 1 || robot->num_factors > ARMOUR_MAX_FACTORS || robot->num_joints < robot->num_factors || robot->num_joints > ARMOUR_MAX_JOINTS) {
+        !armour_robot_shape_ok(robot)) {
         armour_set_error("armour_path_audit_items: bad argument");
         return ARMOUR_EINVAL;
     }

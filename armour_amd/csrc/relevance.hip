@@ -320,39 +320,7 @@ __global__ __launch_bounds__(256) void armour_sparse_violation_kernel(SparseViol
     }
 }
 
-template <class Tp>
-int rel_alloc(Tp** p, size_t* cap, size_t need) {
-    if (*cap >= need) return ARMOUR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIPCHK(hipMalloc((void**)p, need * sizeof(Tp)));
-    *cap = need;
-    return ARMOUR_OK;
-}
-
 }  // namespace
-
-void armour_relevance_free(ArmourPlanner* h) {
-    if (h->d_rel) (void)hipFree(h->d_rel);
-    if (h->d_rel_rows) (void)hipFree(h->d_rel_rows);
-    if (h->d_rel_count) (void)hipFree(h->d_rel_count);
-    if (h->d_rel_rows_res) (void)hipFree(h->d_rel_rows_res);
-    if (h->d_rel_packed) (void)hipFree(h->d_rel_packed);
-    if (h->d_rel_pack_off) (void)hipFree(h->d_rel_pack_off);
-    if (h->d_rel2) (void)hipFree(h->d_rel2);
-    if (h->d_rel2_rows) (void)hipFree(h->d_rel2_rows);
-    if (h->d_rel2_count) (void)hipFree(h->d_rel2_count);
-    if (h->d_rel2_packed) (void)hipFree(h->d_rel2_packed);
-    if (h->d_rel2_pack_off) (void)hipFree(h->d_rel2_pack_off);
-    if (h->d_rel2_tq_tiles) (void)hipFree(h->d_rel2_tq_tiles);
-    h->d_rel2 = nullptr; h->d_rel2_rows = nullptr; h->d_rel2_count = nullptr; h->d_rel2_packed = nullptr; h->d_rel2_pack_off = nullptr; h->d_rel2_tq_tiles = nullptr;
-    h->rel2_cap = h->rel2_rows_cap = h->rel2_count_cap = h->rel2_packed_cap = h->rel2_pack_off_cap = h->rel2_tq_tiles_cap = 0;
-    h->rel2_fresh = false;
-    h->d_rel_packed = nullptr; h->d_rel_pack_off = nullptr; h->rel_packed_cap = h->rel_pack_off_cap = 0;
-    h->d_rel = nullptr; h->d_rel_rows = nullptr; h->d_rel_count = nullptr; h->d_rel_rows_res = nullptr;
-    h->rel_cap = h->rel_rows_cap = h->rel_count_cap = h->rel_rows_res_cap = 0;
-    h->rel_fresh = false;
-}
 
 // offsets of the packed plane entries of B row lists: [2 b] first double of problem b's block, [2 b + 1] its row stride; returns the total
 static long long pack_offsets(const ArmourPlanner* h, const std::vector<int>& count, std::vector<long long>& off) {
@@ -367,93 +335,80 @@ static long long pack_offsets(const ArmourPlanner* h, const std::vector<int>& co
     return total;
 }
 
-// mask + row lists of the current problem set (once per problem set: begin_problem_set clears rel_fresh / rel2_fresh).
+// What both list sets end with, `a` naming the set's mask, rows and counts: the counts (`n_counts` ints, the first B of them the listed
+// collision rows) are read back, then the listed rows' plane entries are packed at the offsets the counts give.  Synchronises the stream
+// once, after the read-back; the pack launch and the copy of the offsets are left queued (`off` must outlive them).
+static int pack_lists(ArmourPlanner* h, RelLists& L, RelTables& a, size_t n_counts, int dfc, std::vector<long long>& off) {
+    const size_t B = (size_t)h->B;
+    L.h_count.resize(n_counts);
+    HIPCHK(hipMemcpyAsync(L.h_count.data(), L.count, n_counts * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    L.h_tq_count.assign(L.h_count.begin() + B, L.h_count.end());
+    L.h_count.resize(B);
+    L.max_count = 0;
+    for (int c : L.h_count) L.max_count = std::max(L.max_count, c);
+    const long long total = pack_offsets(h, L.h_count, off);
+    ARMOUR_TRY(L.packed.reserve((size_t)total));
+    ARMOUR_TRY(L.pack_off.upload(off.data(), 2 * B, h->stream));
+    a.packed = L.packed; a.pack_off = L.pack_off;
+    if (L.max_count > 0) hipLaunchKernelGGL(armour_rel_pack_kernel, dim3((L.max_count + 63) / 64, h->B), dim3(64), 0, h->stream, a, dfc);
+    HIPCHK(hipGetLastError());
+    return ARMOUR_OK;
+}
+
+// mask + row lists of the current problem set (once per problem set: begin_problem_set clears rel.fresh / rel2.fresh).
 // for_solver: also the lists of the solver's mask (rows that can pass armour_solve's candidate filter), their packed plane entries and the
 // torque rows of the mask -- what the culled device form of armour_solve walks (solver_device.hip).
 int armour_relevance_build(ArmourPlanner* h, bool for_solver) {
-    if (h->rel_fresh && (!for_solver || h->rel2_fresh)) return ARMOUR_OK;
-    int rc = armour_upload_bounds(h);
-    if (rc != ARMOUR_OK) return rc;
+    RelLists& R = h->rel;
+    RelLists& S = h->rel2;
+    if (R.fresh && (!for_solver || S.fresh)) return ARMOUR_OK;
+    ARMOUR_TRY(armour_upload_bounds(h));
     const size_t B = (size_t)h->B;
     RelTables a;
     a.tb = armour_make_tables(h);
     a.lo = h->d_bounds; a.hi = h->d_bounds + B * h->m;
     const int dfc = a.tb.obs_center != nullptr && a.tb.ll_shared;
-    struct Events {   // (destroyed on every way out)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
-    hipEvent_t e0 = ev.e0, e1 = ev.e1;
-    if (!h->rel_fresh) {
-        if ((rc = rel_alloc(&h->d_rel, &h->rel_cap, B * h->m)) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel2, &h->rel2_cap, B * h->m)) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel_rows, &h->rel_rows_cap, B * (size_t)std::max(h->Q, 1))) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel_count, &h->rel_count_cap, B * 257)) != ARMOUR_OK) return rc;   // [B] counts | [B][256] per residue class
-        if ((rc = rel_alloc(&h->d_rel_rows_res, &h->rel_rows_res_cap, B * 256 * (size_t)std::max((h->Q + 255) / 256, 1))) != ARMOUR_OK) return rc;
-        a.rel = h->d_rel; a.rel2 = h->d_rel2; a.rows = h->d_rel_rows; a.count = h->d_rel_count; a.rows_res = h->d_rel_rows_res; a.count_res = h->d_rel_count + (size_t)h->B;
+    EventPair ev;
+    std::vector<long long> off;
+    if (!R.fresh) {
+        ARMOUR_TRY(R.mask.reserve(B * h->m));
+        ARMOUR_TRY(S.mask.reserve(B * h->m));
+        ARMOUR_TRY(R.rows.reserve(B * (size_t)std::max(h->Q, 1)));
+        ARMOUR_TRY(R.count.reserve(B * 257));
+        ARMOUR_TRY(R.extra.reserve(B * 256 * (size_t)std::max((h->Q + 255) / 256, 1)));
+        a.rel = R.mask; a.rel2 = S.mask; a.rows = R.rows; a.count = R.count; a.rows_res = R.extra; a.count_res = R.count + B;
         a.tq_tiles = nullptr; a.tq_count = nullptr; a.tq_cap = 0;
         a.packed = nullptr; a.pack_off = nullptr;
-        HIPCHK(hipEventRecord(e0, h->stream));
+        ARMOUR_TRY(ev.record_start(h->stream));
         if (h->Q > 0) hipLaunchKernelGGL(armour_rel_collision_kernel, dim3((h->Q + 63) / 64, h->B), dim3(64), 0, h->stream, a, dfc, h->tables_from_host ? 1 : 0);
         const int other = h->row0 + (h->m - h->row0 - h->Q);
         hipLaunchKernelGGL(armour_rel_other_kernel, dim3((other + 255) / 256, h->B), dim3(256), 0, h->stream, a);
         hipLaunchKernelGGL(armour_rel_list_kernel, dim3(h->B), dim3(256), 0, h->stream, a);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e1, h->stream));
-        h->h_rel_count.resize(B);
-        HIPCHK(hipMemcpyAsync(h->h_rel_count.data(), h->d_rel_count, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        h->rel_ms = ms;
-        h->rel_max_count = 0;
-        for (int c : h->h_rel_count) h->rel_max_count = std::max(h->rel_max_count, c);
-        // the packed plane entries of the listed rows: offsets from the counts just read back
-        std::vector<long long> off;
-        const long long total = pack_offsets(h, h->h_rel_count, off);
-        if ((rc = rel_alloc(&h->d_rel_packed, &h->rel_packed_cap, (size_t)std::max(total, 1ll))) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel_pack_off, &h->rel_pack_off_cap, 2 * B)) != ARMOUR_OK) return rc;
-        HIPCHK(hipMemcpyAsync(h->d_rel_pack_off, off.data(), 2 * B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        a.packed = h->d_rel_packed; a.pack_off = h->d_rel_pack_off;
-        if (h->rel_max_count > 0) hipLaunchKernelGGL(armour_rel_pack_kernel, dim3((h->rel_max_count + 63) / 64, h->B), dim3(64), 0, h->stream, a, dfc);
-        HIPCHK(hipGetLastError());
+        ARMOUR_TRY(ev.record_stop(h->stream));
+        ARMOUR_TRY(pack_lists(h, R, a, B, dfc, off));
         HIPCHK(hipStreamSynchronize(h->stream));   // (`off` is read by the copy)
-        h->rel_fresh = true;
+        ARMOUR_TRY(ev.elapsed_ms(&R.ms));
+        R.fresh = true;
     }
-    if (for_solver && !h->rel2_fresh) {
+    if (for_solver && !S.fresh) {
         const int tq_cap = std::max(1, h->row0);
-        if ((rc = rel_alloc(&h->d_rel2_rows, &h->rel2_rows_cap, B * (size_t)std::max(h->Q, 1))) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel2_count, &h->rel2_count_cap, 2 * B)) != ARMOUR_OK) return rc;   // [B] listed collision rows | [B] listed torque rows
-        if ((rc = rel_alloc(&h->d_rel2_tq_tiles, &h->rel2_tq_tiles_cap, B * (size_t)tq_cap)) != ARMOUR_OK) return rc;
-        a.rel = h->d_rel2; a.rel2 = nullptr; a.rows = h->d_rel2_rows; a.count = h->d_rel2_count; a.rows_res = nullptr; a.count_res = nullptr;
-        a.tq_tiles = h->d_rel2_tq_tiles; a.tq_count = h->d_rel2_count + B; a.tq_cap = tq_cap;
+        ARMOUR_TRY(S.rows.reserve(B * (size_t)std::max(h->Q, 1)));
+        ARMOUR_TRY(S.count.reserve(2 * B));
+        ARMOUR_TRY(S.extra.reserve(B * (size_t)tq_cap));
+        a.rel = S.mask; a.rel2 = nullptr; a.rows = S.rows; a.count = S.count; a.rows_res = nullptr; a.count_res = nullptr;
+        a.tq_tiles = S.extra; a.tq_count = S.count + B; a.tq_cap = tq_cap;
         a.packed = nullptr; a.pack_off = nullptr;
-        HIPCHK(hipEventRecord(e0, h->stream));
+        ARMOUR_TRY(ev.record_start(h->stream));
         hipLaunchKernelGGL(armour_rel_list_kernel, dim3(h->B), dim3(256), 0, h->stream, a);
         HIPCHK(hipGetLastError());
-        std::vector<int> cnt(2 * B);
-        HIPCHK(hipMemcpyAsync(cnt.data(), h->d_rel2_count, 2 * B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->h_rel2_count.assign(cnt.begin(), cnt.begin() + B);
-        h->h_rel2_tq_count.assign(cnt.begin() + B, cnt.end());
+        ARMOUR_TRY(pack_lists(h, S, a, 2 * B, dfc, off));
         h->rel2_tq_cap = tq_cap;
-        h->rel2_max_count = 0;
-        for (int c : h->h_rel2_count) h->rel2_max_count = std::max(h->rel2_max_count, c);
-        std::vector<long long> off;
-        const long long total = pack_offsets(h, h->h_rel2_count, off);
-        if ((rc = rel_alloc(&h->d_rel2_packed, &h->rel2_packed_cap, (size_t)std::max(total, 1ll))) != ARMOUR_OK) return rc;
-        if ((rc = rel_alloc(&h->d_rel2_pack_off, &h->rel2_pack_off_cap, 2 * B)) != ARMOUR_OK) return rc;
-        HIPCHK(hipMemcpyAsync(h->d_rel2_pack_off, off.data(), 2 * B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        a.packed = h->d_rel2_packed; a.pack_off = h->d_rel2_pack_off;
-        if (h->rel2_max_count > 0) hipLaunchKernelGGL(armour_rel_pack_kernel, dim3((h->rel2_max_count + 63) / 64, h->B), dim3(64), 0, h->stream, a, dfc);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e1, h->stream));
+        ARMOUR_TRY(ev.record_stop(h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        h->rel2_ms = ms;
-        h->rel2_fresh = true;
+        ARMOUR_TRY(ev.elapsed_ms(&S.ms));
+        S.fresh = true;
     }
     return ARMOUR_OK;
 }
@@ -462,8 +417,8 @@ int armour_relevance_build(ArmourPlanner* h, bool for_solver) {
 int armour_solver_lists(ArmourPlanner* h, p2::SparseList* sl, const int** tq_tiles, const int** tq_count, int* tq_cap) {
     const int rc = armour_relevance_build(h, true);
     if (rc != ARMOUR_OK) return rc;
-    sl->rows = h->d_rel2_rows; sl->count = h->d_rel2_count; sl->packed = h->d_rel2_packed; sl->pack_off = h->d_rel2_pack_off;
-    *tq_tiles = h->d_rel2_tq_tiles; *tq_count = h->d_rel2_count + (size_t)h->B; *tq_cap = h->rel2_tq_cap;
+    sl->rows = h->rel2.rows; sl->count = h->rel2.count; sl->packed = h->rel2.packed; sl->pack_off = h->rel2.pack_off;
+    *tq_tiles = h->rel2.extra; *tq_count = h->rel2.count + (size_t)h->B; *tq_cap = h->rel2_tq_cap;
     return ARMOUR_OK;
 }
 
@@ -472,9 +427,9 @@ extern "C" int armour_get_row_relevance(ArmourPlanner* h, uint8_t* relevant, int
     HIPCHK(hipSetDevice(h->device));
     const int rc = armour_relevance_build(h, false);
     if (rc != ARMOUR_OK) return rc;
-    if (relevant) HIPCHK(hipMemcpy(relevant, h->d_rel, (size_t)h->B * h->m, hipMemcpyDeviceToHost));
-    if (n_relevant_collision_rows) for (int b = 0; b < h->B; b++) n_relevant_collision_rows[b] = h->h_rel_count[b];
-    if (ms) *ms = h->rel_ms;
+    if (relevant) HIPCHK(hipMemcpy(relevant, h->rel.mask, (size_t)h->B * h->m, hipMemcpyDeviceToHost));
+    if (n_relevant_collision_rows) for (int b = 0; b < h->B; b++) n_relevant_collision_rows[b] = h->rel.h_count[b];
+    if (ms) *ms = h->rel.ms;
     return ARMOUR_OK;
 }
 
@@ -483,12 +438,12 @@ extern "C" int armour_get_solver_rows(ArmourPlanner* h, uint8_t* solver_rows, in
     HIPCHK(hipSetDevice(h->device));
     const int rc = armour_relevance_build(h, true);
     if (rc != ARMOUR_OK) return rc;
-    if (solver_rows) HIPCHK(hipMemcpy(solver_rows, h->d_rel2, (size_t)h->B * h->m, hipMemcpyDeviceToHost));
+    if (solver_rows) HIPCHK(hipMemcpy(solver_rows, h->rel2.mask, (size_t)h->B * h->m, hipMemcpyDeviceToHost));
     for (int b = 0; b < h->B; b++) {
-        if (n_collision_rows) n_collision_rows[b] = h->h_rel2_count[b];
-        if (n_torque_rows) n_torque_rows[b] = h->h_rel2_tq_count[b];
+        if (n_collision_rows) n_collision_rows[b] = h->rel2.h_count[b];
+        if (n_torque_rows) n_torque_rows[b] = h->rel2.h_tq_count[b];
     }
-    if (ms) *ms = h->rel_ms + h->rel2_ms;
+    if (ms) *ms = h->rel.ms + h->rel2.ms;
     return ARMOUR_OK;
 }
 
@@ -503,10 +458,10 @@ int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourVio
     RelTables a;
     a.tb = tb;
     a.lo = h->d_bounds; a.hi = h->d_bounds + (size_t)h->B * h->m;
-    a.rel = h->d_rel; a.rows = h->d_rel_rows; a.count = h->d_rel_count; a.rows_res = h->d_rel_rows_res; a.count_res = h->d_rel_count + (size_t)h->B;
-    a.packed = h->d_rel_packed; a.pack_off = h->d_rel_pack_off;
-    if (h->rel_max_count > 0)
-        hipLaunchKernelGGL(armour_sparse_collision_g_kernel, dim3((h->rel_max_count + 63) / 64, h->B), dim3(64), 0, st, a, d_k, h->d_g);
+    a.rel = h->rel.mask; a.rows = h->rel.rows; a.count = h->rel.count; a.rows_res = h->rel.extra; a.count_res = h->rel.count + (size_t)h->B;
+    a.packed = h->rel.packed; a.pack_off = h->rel.pack_off;
+    if (h->rel.max_count > 0)
+        hipLaunchKernelGGL(armour_sparse_collision_g_kernel, dim3((h->rel.max_count + 63) / 64, h->B), dim3(64), 0, st, a, d_k, h->d_g);
     SparseViolArgs v;
     v.m = h->m; v.row0 = h->row0; v.Q = h->Q; v.n_checked = armour_checked_collision_rows(h);
     v.torque_slack = h->params.torque_violation_threshold; v.collision_slack = h->params.collision_violation_threshold;

@@ -96,20 +96,6 @@ double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
     return std::sqrt(acc);
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t grow(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-};
-
 }  // namespace
 
 struct ArmourRoadmap {
@@ -124,34 +110,25 @@ struct ArmourRoadmap {
     DevBuf<int32_t> d_edges, d_sample_edge;
     DevBuf<int64_t> d_edge_off;
     DevBuf<uint8_t> d_node_free, d_edge_free;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevStream stream;
+    EventPair ev;
     // the last check, on the host
     int32_t W = -1, O = 0;
     std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them
     std::vector<uint8_t> node_free, edge_free;
-    ~ArmourRoadmap() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
                                      const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
     if (!robot || !out || (N > 0 && !nodes) || (E > 0 && !edges)) { armour_set_error("armour_roadmap_create: null argument"); return ARMOUR_EINVAL; }
     *out = nullptr;
-    if (robot->num_factors < 1 || robot->num_factors > ARMOUR_MAX_FACTORS || robot->num_joints < robot->num_factors || robot->num_joints > ARMOUR_MAX_JOINTS) {
-        armour_set_error("armour_roadmap_create: robot has %d joints, %d factors", robot->num_joints, robot->num_factors);
-        return ARMOUR_EINVAL;
-    }
+    ARMOUR_TRY(armour_check_robot_shape("armour_roadmap_create", robot));
     if (N < 0 || E < 0 || !(edge_step > 0.0) || !std::isfinite(edge_step)) {
         armour_set_error("armour_roadmap_create: N = %d, E = %d, edge_step = %g", N, E, edge_step);
         return ARMOUR_EINVAL;
     }
     const int n = robot->num_factors;
-    for (int64_t i = 0; i < (int64_t)N * n; i++)
-        if (!std::isfinite(nodes[i])) { armour_set_error("armour_roadmap_create: node %lld is not finite", (long long)(i / n)); return ARMOUR_EINVAL; }
+    if (const size_t i = first_nonfinite(nodes, (size_t)N * n); i < (size_t)N * n) { armour_set_error("armour_roadmap_create: node %lld is not finite", (long long)(i / n)); return ARMOUR_EINVAL; }
     for (int64_t i = 0; i < 2 * (int64_t)E; i++)
         if (edges[i] < 0 || edges[i] >= N) { armour_set_error("armour_roadmap_create: edge %lld names node %d of %d", (long long)(i / 2), edges[i], N); return ARMOUR_EINVAL; }
     ArmourRoadmap* rm = new (std::nothrow) ArmourRoadmap();
@@ -177,17 +154,12 @@ extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const 
     for (int e = 0; e < E; e++)
         for (int64_t k = off[e]; k < off[e + 1]; k++) sample_edge[(size_t)k] = e;
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&rm->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&rm->ev0));
-    HIPCHK(hipEventCreate(&rm->ev1));
-    HIPCHK(rm->d_nodes.grow(rm->nodes.size()));
-    HIPCHK(rm->d_edges.grow(rm->edges.size()));
-    HIPCHK(rm->d_edge_off.grow(off.size()));
-    HIPCHK(rm->d_sample_edge.grow(sample_edge.size()));
-    if (!rm->nodes.empty()) HIPCHK(hipMemcpy(rm->d_nodes.p, rm->nodes.data(), rm->nodes.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (!rm->edges.empty()) HIPCHK(hipMemcpy(rm->d_edges.p, rm->edges.data(), rm->edges.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(rm->d_edge_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!sample_edge.empty()) HIPCHK(hipMemcpy(rm->d_sample_edge.p, sample_edge.data(), sample_edge.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    ARMOUR_TRY(rm->stream.create());
+    ARMOUR_TRY(rm->d_nodes.upload(rm->nodes.data(), rm->nodes.size(), rm->stream));
+    ARMOUR_TRY(rm->d_edges.upload(rm->edges.data(), rm->edges.size(), rm->stream));
+    ARMOUR_TRY(rm->d_edge_off.upload(off.data(), off.size(), rm->stream));
+    ARMOUR_TRY(rm->d_sample_edge.upload(sample_edge.data(), sample_edge.size(), rm->stream));
+    HIPCHK(hipStreamSynchronize(rm->stream));   // (`off` and `sample_edge` are read by the copies)
     *out = guard.release();
     return ARMOUR_OK;
 }
@@ -209,51 +181,39 @@ extern "C" int armour_roadmap_get_sizes(const ArmourRoadmap* rm, int32_t* N, int
 extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
                                     double* node_clearance, double* ms) {
     if (!rm) { armour_set_error("armour_roadmap_check: null handle"); return ARMOUR_EINVAL; }
-    if (W < 0 || W > 65535 || O < 0 || O > ARMOUR_ROADMAP_MAX_OBSTACLES || (W > 0 && O > 0 && !obstacles)) {
-        armour_set_error("armour_roadmap_check: W = %d (0..65535), O = %d (0..%d)", W, O, ARMOUR_ROADMAP_MAX_OBSTACLES);
-        return ARMOUR_EINVAL;
-    }
+    ARMOUR_TRY(armour_check_world_counts("armour_roadmap_check", W, O, obstacles));
     const size_t nobs = (size_t)W * O * ARMOUR_OBS_DOUBLES;
-    for (size_t i = 0; i < nobs; i++)
-        if (!std::isfinite(obstacles[i])) { armour_set_error("armour_roadmap_check: obstacle %zu is not finite", i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
+    if (const size_t i = first_nonfinite(obstacles, nobs); i < nobs) { armour_set_error("armour_roadmap_check: obstacle %zu is not finite", i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
     HIPCHK(hipSetDevice(rm->device));
     const size_t WN = (size_t)W * rm->N, WE = (size_t)W * rm->E;
-    HIPCHK(rm->d_obs.grow(nobs));
-    HIPCHK(rm->d_node_free.grow(WN));
-    HIPCHK(rm->d_edge_free.grow(WE));
-    if (node_clearance) HIPCHK(rm->d_clear.grow(WN));
-    if (nobs) HIPCHK(hipMemcpyAsync(rm->d_obs.p, obstacles, nobs * sizeof(double), hipMemcpyHostToDevice, rm->stream));
-    if (WE) HIPCHK(hipMemsetAsync(rm->d_edge_free.p, 1, WE, rm->stream));
+    ARMOUR_TRY(rm->d_node_free.reserve(WN));
+    ARMOUR_TRY(rm->d_edge_free.reserve(WE));
+    if (node_clearance) ARMOUR_TRY(rm->d_clear.reserve(WN));
+    ARMOUR_TRY(rm->d_obs.upload(obstacles, nobs, rm->stream));
+    if (WE) HIPCHK(hipMemsetAsync(rm->d_edge_free, 1, WE, rm->stream));
     const int64_t items = (int64_t)rm->N + rm->M;
-    HIPCHK(hipEventRecord(rm->ev0, rm->stream));
+    ARMOUR_TRY(rm->ev.record_start(rm->stream));
     if (W > 0 && items > 0) {
         const dim3 grid((unsigned)((items + RM_BLOCK - 1) / RM_BLOCK), (unsigned)W);
         const size_t lds = (size_t)O * RM_OBS_STRIDE * sizeof(double);
-        hipLaunchKernelGGL(roadmap_check_kernel, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes.p, rm->d_edges.p,
-                           rm->d_edge_off.p, rm->d_sample_edge.p, rm->d_obs.p, O, rm->E, rm->d_node_free.p, rm->d_edge_free.p,
-                           node_clearance ? rm->d_clear.p : nullptr);
+        hipLaunchKernelGGL(roadmap_check_kernel, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes, rm->d_edges,
+                           rm->d_edge_off, rm->d_sample_edge, rm->d_obs, O, rm->E, rm->d_node_free, rm->d_edge_free,
+                           node_clearance ? rm->d_clear : nullptr);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(rm->ev1, rm->stream));
+    ARMOUR_TRY(rm->ev.record_stop(rm->stream));
     rm->node_free.resize(WN);
     rm->edge_free.resize(WE);
-    if (WN) HIPCHK(hipMemcpyAsync(rm->node_free.data(), rm->d_node_free.p, WN, hipMemcpyDeviceToHost, rm->stream));
-    if (WE) HIPCHK(hipMemcpyAsync(rm->edge_free.data(), rm->d_edge_free.p, WE, hipMemcpyDeviceToHost, rm->stream));
-    if (node_clearance && WN) HIPCHK(hipMemcpyAsync(node_clearance, rm->d_clear.p, WN * sizeof(double), hipMemcpyDeviceToHost, rm->stream));
+    if (WN) HIPCHK(hipMemcpyAsync(rm->node_free.data(), rm->d_node_free, WN, hipMemcpyDeviceToHost, rm->stream));
+    if (WE) HIPCHK(hipMemcpyAsync(rm->edge_free.data(), rm->d_edge_free, WE, hipMemcpyDeviceToHost, rm->stream));
+    if (node_clearance && WN) HIPCHK(hipMemcpyAsync(node_clearance, rm->d_clear, WN * sizeof(double), hipMemcpyDeviceToHost, rm->stream));
     HIPCHK(hipStreamSynchronize(rm->stream));
-    if (ms) {
-        float f = 0.f;
-        HIPCHK(hipEventElapsedTime(&f, rm->ev0, rm->ev1));
-        *ms = f;
-    }
+    if (ms) ARMOUR_TRY(rm->ev.elapsed_ms(ms));
     if (node_free && WN) std::memcpy(node_free, rm->node_free.data(), WN);
     if (edge_free && WE) std::memcpy(edge_free, rm->edge_free.data(), WE);
     // the obstacles as the kernel staged them, for the host checks of armour_roadmap_plan
-    rm->obs.assign((size_t)W * O * RM_OBS_STRIDE, 0.0);
-    for (size_t o = 0; o < (size_t)W * O; o++) {
-        std::memcpy(&rm->obs[o * RM_OBS_STRIDE], obstacles + o * ARMOUR_OBS_DOUBLES, ARMOUR_OBS_DOUBLES * sizeof(double));
-        obstacle_normals(obstacles + o * ARMOUR_OBS_DOUBLES, &rm->obs[o * RM_OBS_STRIDE + 12]);
-    }
+    rm->obs.resize((size_t)W * O * RM_OBS_STRIDE);
+    stage_obstacles(obstacles, (size_t)W * O, rm->obs.data());
     rm->W = W;
     rm->O = O;
     return ARMOUR_OK;

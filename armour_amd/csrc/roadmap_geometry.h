@@ -58,6 +58,14 @@ __host__ __device__ inline void obstacle_normals(const double* Z, double* out /*
     }
 }
 
+// `count` obstacles as the kernels stage them in LDS, on the host: staged[o][RM_OBS_STRIDE] = Z[12], then the obstacle's normals
+inline void stage_obstacles(const double* obstacles, size_t count, double* staged) {
+    for (size_t o = 0; o < count; o++) {
+        std::memcpy(staged + o * RM_OBS_STRIDE, obstacles + o * ARMOUR_OBS_DOUBLES, ARMOUR_OBS_DOUBLES * sizeof(double));
+        obstacle_normals(obstacles + o * ARMOUR_OBS_DOUBLES, staged + o * RM_OBS_STRIDE + ARMOUR_OBS_DOUBLES);
+    }
+}
+
 // One link box (centre x, unit axes u[k] = column k of R, half-sizes s) against one staged obstacle.  full = false: true as soon as
 // one plane separates (value > 0; the sign of the numerator is the sign of the value).  full = true: *value = the pair's clearance.
 __host__ __device__ inline bool pair_separated(const double* x, const double (*u)[3], const double* s, const double* ob, bool full,

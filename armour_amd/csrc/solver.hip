@@ -366,7 +366,7 @@ static int plan_device_solve(ArmourPlanner* h, const P2Tables& tb, DevicePlan& p
     p.culled = h->Q > 0 && (cull_opt > 0 || (cull_opt < 0 && (long long)B * h->Q >= kSolveCullMinRows));
     if (p.culled) {
         if ((rc = armour_solver_lists(h, &p.sl, &p.tq_tiles, &p.tq_count, &p.tq_cap)) != ARMOUR_OK) return rc;
-        for (int b = 0; b < B; b++) p.n_tiles_culled = std::max(p.n_tiles_culled, (h->h_rel2_tq_count[b] + P2_BLOCK - 1) / P2_BLOCK + (h->h_rel2_count[b] + P2_BLOCK - 1) / P2_BLOCK + 1);
+        for (int b = 0; b < B; b++) p.n_tiles_culled = std::max(p.n_tiles_culled, (h->rel2.h_tq_count[b] + P2_BLOCK - 1) / P2_BLOCK + (h->rel2.h_count[b] + P2_BLOCK - 1) / P2_BLOCK + 1);
     }
     if ((rc = armour_solve_device_capacity(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->device, B, h->tune(ARMOUR_OPT_SOLVE_WAVES_PER_SIMD), &plan, p.n_tiles_culled)) != ARMOUR_OK) return rc;
     if (plan.capacity < 1) return ARMOUR_OK;
@@ -425,18 +425,18 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     s.off_args = (off_qdes + (size_t)B * n * sizeof(double) + 255) & ~(size_t)255;
     s.args_stride = (sizeof(SolveArgs) + 255) & ~(size_t)255;
     s.block_bytes = s.off_args + (size_t)p.n_launch * s.args_stride;
-    if ((rc = grow(&w.ctl, &w.ctl_cap, s.block_bytes)) != ARMOUR_OK) return rc;
+    ARMOUR_TRY(w.ctl.reserve(s.block_bytes));
     // the blocks' flag words: zero before a launch.  Every block clears its own word when it leaves the kernel, so a fill is only
     // needed when the array is new (or grew)
     // (sized for ONE sub-batch: the launches of a cut batch run one after the other on the stream and index these buffers by
     //  b - b0, so a batch of 1024 problems holds the candidate rows of the <= Bs it solves at a time -- ADVICE round 3)
     bool fresh = false;
-    if ((rc = grow(&w.blk_word, &w.word_cap, (size_t)p.Bs * p.nb * sizeof(BlockWord), &fresh)) != ARMOUR_OK) return rc;
-    if (fresh || !w.words_clean) HIPCHK(hipMemsetAsync(w.blk_word, 0, w.word_cap, h->stream));
+    ARMOUR_TRY(w.blk_word.reserve((size_t)p.Bs * p.nb * sizeof(BlockWord), &fresh));
+    if (fresh || !w.words_clean) HIPCHK(hipMemsetAsync(w.blk_word, 0, w.blk_word.cap, h->stream));
     w.words_clean = 0;   // until this launch has been seen to end
-    if ((rc = grow(&w.blk_rows, &w.blk_rows_cap, (size_t)p.Bs * p.nb * p.cap_blk * sizeof(SolveRow))) != ARMOUR_OK) return rc;
-    if ((rc = grow(&w.qp_rows, &w.qp_rows_cap, (size_t)p.Bs * p.cap_rows * sizeof(SolveRow))) != ARMOUR_OK) return rc;
-    if ((rc = grow(&w.flags, &w.flags_cap, (size_t)p.Bs * 8 * (p.cap_rows + 2 * NV))) != ARMOUR_OK) return rc;   // (active / excluded) x the four QP attempts
+    ARMOUR_TRY(w.blk_rows.reserve((size_t)p.Bs * p.nb * p.cap_blk * sizeof(SolveRow)));
+    ARMOUR_TRY(w.qp_rows.reserve((size_t)p.Bs * p.cap_rows * sizeof(SolveRow)));
+    ARMOUR_TRY(w.flags.reserve((size_t)p.Bs * 8 * (p.cap_rows + 2 * NV)));   // (active / excluded) x the four QP attempts
     s.hres = reinterpret_cast<ArmourSolveResult*>(armour_handle_pinned(h, 1, (size_t)B * sizeof(ArmourSolveResult)));
     s.hblock = reinterpret_cast<unsigned char*>(armour_handle_pinned(h, 2, s.block_bytes));
     if (!s.hres || !s.hblock) return ARMOUR_EDEVICE;
@@ -454,9 +454,9 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     a.lds_rows = (int)(plan.smem / ((NV + 1) * sizeof(double)));
     a.culled = p.culled ? 1 : 0; a.sl = p.sl; a.tq_tiles = p.tq_tiles; a.tq_count = p.tq_count; a.tq_cap = p.tq_cap;
     a.lo = h->d_bounds; a.hi = h->d_bounds + (size_t)B * m; a.g = h->d_g; a.jac = h->d_jac;
-    a.ctl = reinterpret_cast<SolveCtl*>(w.ctl); a.blk_word = reinterpret_cast<BlockWord*>(w.blk_word);
-    a.blk_rows = reinterpret_cast<SolveRow*>(w.blk_rows); a.qp_rows = reinterpret_cast<SolveRow*>(w.qp_rows); a.flags = w.flags;
-    a.q_des = reinterpret_cast<const double*>(reinterpret_cast<unsigned char*>(w.ctl) + off_qdes); a.out = s.hres;   // the kernel writes the results straight into page-locked host memory
+    a.ctl = w.ctl.as<SolveCtl>(); a.blk_word = w.blk_word.as<BlockWord>();
+    a.blk_rows = w.blk_rows.as<SolveRow>(); a.qp_rows = w.qp_rows.as<SolveRow>(); a.flags = w.flags;
+    a.q_des = reinterpret_cast<const double*>(w.ctl + off_qdes); a.out = s.hres;   // the kernel writes the results straight into page-locked host memory
     for (int i = 0; i < n; i++) if (h->robot.continuous[i]) a.continuous_mask |= 1 << i;
     a.max_iter = opt.max_iterations; a.max_ls = opt.max_line_search; a.tol = opt.tolerance;
     a.n_checked_collision = armour_checked_collision_rows(h);
@@ -487,7 +487,7 @@ static void report_device_timing(const ArmourPlanner* h, const DevicePlan& p, co
     const long long* hstamps = s.hstamps;
     const int B = h->B, n_launch = p.n_launch, Bs = p.Bs, nb = p.nb, n_tiles_culled = p.n_tiles_culled;
     if (p.culled) fprintf(stderr, "[armour_solve, device form] culled: at most %d listed tiles per problem (problem 0: %d of %d collision rows, %d of %d torque rows), lists %.3f + %.3f ms\n",
-                          n_tiles_culled, h->h_rel2_count[0], h->Q, h->h_rel2_tq_count[0], h->row0, h->rel_ms, h->rel2_ms);
+                          n_tiles_culled, h->rel2.h_count[0], h->Q, h->rel2.h_tq_count[0], h->row0, h->rel.ms, h->rel2.ms);
     fprintf(stderr, "[armour_solve, device form] B=%d in %d launch(es) of <= %d problems: %d blocks per problem (%d tiles), %.3f ms wall (%.3f ms before the launch), kernel %.3f ms (problem 0); phases of problem 0 in us (barrier passed / leader done):", B, n_launch, Bs, nb, plan.n_tiles, ms,
             std::chrono::duration<double, std::milli>(t_launch - t_begin).count(), hres[0].time_ms / plan.ticks_per_ms);
     int bs = 0;   // the problem whose group left last: what the launch waited for

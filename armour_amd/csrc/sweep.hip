@@ -312,11 +312,6 @@ __global__ __launch_bounds__(256) void armour_sweep_best_kernel(const ArmourSwee
 
 }  // namespace
 
-void armour_sweep_free(ArmourPlanner* h) {
-    if (h->d_sweep) (void)hipFree(h->d_sweep);
-    h->d_sweep = nullptr; h->sweep_cap = 0;
-}
-
 extern "C" int armour_sweep_tile(void) { return kTile; }
 
 extern "C" int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, int32_t per_problem, ArmourSweepRecord* records, int32_t* best, double* ms) {
@@ -340,7 +335,8 @@ extern "C" int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, i
     const size_t off_rec = off_coef + B * 4 * n * sizeof(double);
     const size_t off_best = off_rec + B * (size_t)S * sizeof(ArmourSweepRecord);
     const size_t bytes = off_best + B * sizeof(int);
-    if ((rc = grow(&h->d_sweep, &h->sweep_cap, bytes)) != ARMOUR_OK) return rc;
+    ARMOUR_TRY(h->d_sweep.reserve(bytes));
+    unsigned char* const blk = h->d_sweep;
     std::vector<double> coef(B * 4 * n);
     for (size_t b = 0; b < B; b++)
         for (size_t i = 0; i < n; i++) {
@@ -349,35 +345,30 @@ extern "C" int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, i
             coef[(b * 4 + 0) * n + i] = c[0]; coef[(b * 4 + 1) * n + i] = c[1]; coef[(b * 4 + 2) * n + i] = c[2];
             coef[(b * 4 + 3) * n + i] = h->h_qdes[b * n + i];
         }
-    HIPCHK(hipMemcpyAsync(h->d_sweep, k_cand, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_sweep + off_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(blk, k_cand, nk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(blk + off_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     SweepArgs a;
     a.tb = armour_make_tables(h);
-    a.sl = SparseList{h->d_rel_rows, h->d_rel_count, h->d_rel_packed, h->d_rel_pack_off};
-    a.rows_res = h->d_rel_rows_res; a.count_res = h->d_rel_count + B;
+    a.sl = SparseList{h->rel.rows, h->rel.count, h->rel.packed, h->rel.pack_off};
+    a.rows_res = h->rel.extra; a.count_res = h->rel.count + B;
     a.lo = h->d_bounds; a.hi = h->d_bounds + B * h->m;
-    a.k = reinterpret_cast<const double*>(h->d_sweep); a.k_pstride = per_problem ? (long long)S * (long long)n : 0;
+    a.k = reinterpret_cast<const double*>(blk); a.k_pstride = per_problem ? (long long)S * (long long)n : 0;
     a.S = S; a.strideT = strideT; a.n_checked = armour_checked_collision_rows(h);
     a.torque_slack = h->params.torque_violation_threshold; a.collision_slack = h->params.collision_violation_threshold;
-    a.coef = reinterpret_cast<const double*>(h->d_sweep + off_coef);
+    a.coef = reinterpret_cast<const double*>(blk + off_coef);
     a.continuous_mask = 0;
     for (int i = 0; i < h->n; i++) if (h->robot.continuous[i]) a.continuous_mask |= 1 << i;
     a.t_plan = h->params.t_plan; a.cost_scale = h->params.cost_scale;
-    a.out = reinterpret_cast<ArmourSweepRecord*>(h->d_sweep + off_rec);
-    int* d_best = reinterpret_cast<int*>(h->d_sweep + off_best);
-    struct Events {   // (destroyed on every way out)
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
-    HIPCHK(hipEventRecord(ev.e0, h->stream));
+    a.out = reinterpret_cast<ArmourSweepRecord*>(blk + off_rec);
+    int* d_best = reinterpret_cast<int*>(blk + off_best);
+    EventPair ev;
+    ARMOUR_TRY(ev.record_start(h->stream));
     hipLaunchKernelGGL(armour_sweep_kernel<kTile>, dim3((S + kTile - 1) / kTile, h->B), dim3(256), 0, h->stream, a);
     hipLaunchKernelGGL(armour_sweep_best_kernel, dim3(h->B), dim3(256), 0, h->stream, a.out, S, d_best);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev.e1, h->stream));
-    if (records) HIPCHK(hipMemcpyAsync(records, h->d_sweep + off_rec, B * (size_t)S * sizeof(ArmourSweepRecord), hipMemcpyDeviceToHost, h->stream));
+    ARMOUR_TRY(ev.record_stop(h->stream));
+    if (records) HIPCHK(hipMemcpyAsync(records, blk + off_rec, B * (size_t)S * sizeof(ArmourSweepRecord), hipMemcpyDeviceToHost, h->stream));
     if (best) HIPCHK(hipMemcpyAsync(best, d_best, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (ms) { float t = 0; HIPCHK(hipEventElapsedTime(&t, ev.e0, ev.e1)); *ms = t; }
-    return ARMOUR_OK;
+    return ms ? ev.elapsed_ms(ms) : ARMOUR_OK;
 }

@@ -199,23 +199,6 @@ constexpr double kStepMsRobust = 4.3;
 constexpr double kStepMsPlant = 0.77;
 constexpr double kLaunchTargetMs = 15.0;
 
-struct DevBufs {
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~DevBufs() {
-        for (void* x : p) if (x) (void)hipFree(x);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-bool finite_all(const double* x, size_t count) {
-    for (size_t i = 0; i < count; i++) if (!std::isfinite(x[i])) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" void armour_track_options_default(const ArmourRobot* robot, ArmourTrackOptions* opt) {
@@ -308,38 +291,33 @@ extern "C" int armour_track(const ArmourRobot* robot, const ArmourTrackOptions* 
     const size_t trace_doubles = want_trace ? (size_t)B * ta.n_records * 3 * n : 0;
     // ---- the device
     if (!armour_device_available()) { armour_set_error("armour_track: no HIP device visible (there is no CPU path)"); return ARMOUR_EDEVICE; }
-    DevBufs d;
-    HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&d.ev0));
-    HIPCHK(hipEventCreate(&d.ev1));
-    HIPCHK(hipMalloc(&d.p[0], sizeof(TrackArgs)));
-    HIPCHK(hipMalloc(&d.p[1], sizeof(TrackIn) * B));
-    HIPCHK(hipMalloc(&d.p[2], sizeof(ArmourTrackResult) * B));
-    if (trace_doubles) HIPCHK(hipMalloc(&d.p[3], trace_doubles * sizeof(double)));
-    TrackArgs* d_args = (TrackArgs*)d.p[0];
-    TrackIn* d_in = (TrackIn*)d.p[1];
-    ArmourTrackResult* d_st = (ArmourTrackResult*)d.p[2];
-    double* d_trace = (double*)d.p[3];
-    HIPCHK(hipMemcpyAsync(d_args, &ta, sizeof(TrackArgs), hipMemcpyHostToDevice, d.stream));
-    HIPCHK(hipMemcpyAsync(d_in, ins.data(), sizeof(TrackIn) * B, hipMemcpyHostToDevice, d.stream));
-    HIPCHK(hipMemcpyAsync(d_st, st.data(), sizeof(ArmourTrackResult) * B, hipMemcpyHostToDevice, d.stream));
-    if (trace_doubles) HIPCHK(hipMemsetAsync(d_trace, 0xff, trace_doubles * sizeof(double), d.stream));   // all-ones bytes: NaN for nodes never reached
+    DevStream stream;
+    EventPair ev;
+    DevBuf<TrackArgs> d_args;
+    DevBuf<TrackIn> d_in;
+    DevBuf<ArmourTrackResult> d_st;
+    DevBuf<double> d_trace;
+    ARMOUR_TRY(stream.create());
+    ARMOUR_TRY(d_args.reserve(1));
+    ARMOUR_TRY(d_in.reserve(B));
+    ARMOUR_TRY(d_st.reserve(B));
+    if (trace_doubles) ARMOUR_TRY(d_trace.reserve(trace_doubles));
+    HIPCHK(hipMemcpyAsync(d_args, &ta, sizeof(TrackArgs), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_in, ins.data(), sizeof(TrackIn) * B, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_st, st.data(), sizeof(ArmourTrackResult) * B, hipMemcpyHostToDevice, stream));
+    if (trace_doubles) HIPCHK(hipMemsetAsync(d_trace, 0xff, trace_doubles * sizeof(double), stream));   // all-ones bytes: NaN for nodes never reached
     // every rollout needs N steps and one pass at its last node: ceil((N + 1) / S) launches; rollouts that stop early return at once
     const long long launches = ((long long)N + S) / S;
-    HIPCHK(hipEventRecord(d.ev0, d.stream));
+    ARMOUR_TRY(ev.record_start(stream));
     for (long long l = 0; l < launches; l++) {
-        hipLaunchKernelGGL(armour_track_kernel, dim3((B + 63) / 64), dim3(64), 0, d.stream, d_args, B, d_in, d_st, d_trace, S);
+        hipLaunchKernelGGL(armour_track_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_args, B, d_in, d_st, d_trace, S);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(d.ev1, d.stream));
-    HIPCHK(hipMemcpyAsync(st.data(), d_st, sizeof(ArmourTrackResult) * B, hipMemcpyDeviceToHost, d.stream));
-    if (trace_doubles) HIPCHK(hipMemcpyAsync(trace, d_trace, trace_doubles * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(hipStreamSynchronize(d.stream));
-    if (ms) {
-        float f = 0.f;
-        HIPCHK(hipEventElapsedTime(&f, d.ev0, d.ev1));
-        *ms = f;
-    }
+    ARMOUR_TRY(ev.record_stop(stream));
+    HIPCHK(hipMemcpyAsync(st.data(), d_st, sizeof(ArmourTrackResult) * B, hipMemcpyDeviceToHost, stream));
+    if (trace_doubles) HIPCHK(hipMemcpyAsync(trace, d_trace, trace_doubles * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
     for (int b = 0; b < B; b++) {   // every rollout has passed its last node or stopped: the launches above are enough by construction
         if (!st[b].reserved) { armour_set_error("armour_track: rollout %d did not finish", b); return ARMOUR_ESTATE; }
         st[b].reserved = 0;
