@@ -446,9 +446,8 @@ extern "C" int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, 
     return ARMOUR_OK;
 }
 
-#define NEED_READY(h)                                                                        \
-    if (!(h)) { armour_set_error("null handle"); return ARMOUR_EINVAL; }                     \
-    if (!(h)->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
+// problem b's torque radii [n][T] on the host (nothing to read without torque rows)
+static const double* torque_radius_of(const ArmourPlanner* h, int b) { return h->no_torque() ? nullptr : &h->h_torque_radius[(size_t)b * h->n * h->T]; }
 
 extern "C" int armour_get_sizes(const ArmourPlanner* h, int32_t* B, int32_t* n, int32_t* m) {
     NEED_READY(h);
@@ -460,34 +459,37 @@ extern "C" int armour_get_sizes(const ArmourPlanner* h, int32_t* B, int32_t* n, 
 
 extern "C" int armour_get_bounds(ArmourPlanner* h, double* x_l, double* x_u, double* g_l, double* g_u) {
     NEED_READY(h);
-    const int T = h->T, n = h->n;
+    const int n = h->n;
     if (x_l) for (int i = 0; i < n; i++) x_l[i] = -1.0;
     if (x_u) for (int i = 0; i < n; i++) x_u[i] = 1.0;
     if (!g_l || !g_u) return ARMOUR_OK;
-    for (int b = 0; b < h->B; b++) {
-        double* gl = g_l + (size_t)b * h->m;
-        double* gu = g_u + (size_t)b * h->m;
-        if (!h->no_torque()) {   // RT/NLPclass.cu:117
-            const double* tr = &h->h_torque_radius[(size_t)b * n * T];
-            for (int t = 0; t < T; t++)
-                for (int j = 0; j < n; j++) {
-                    gl[t * n + j] = -h->robot.torque_limits[j] + tr[j * T + t];
-                    gu[t * n + j] = h->robot.torque_limits[j] - tr[j * T + t];
-                }
-        }
-        size_t off = (size_t)h->row0;  // ARMTD mode (CMP/NLPclass.cu:73-140): the same collision and limit bounds, no torque rows
-        for (size_t i = off; i < off + (size_t)h->Q; i++) { gl[i] = -1e19; gu[i] = 0; }
-        off += h->Q;
-        for (int rep = 0; rep < 2; rep++, off += n)
-            for (int i = 0; i < n; i++) { gl[off + i] = h->robot.state_limits_lb[i] + h->ub.qe; gu[off + i] = h->robot.state_limits_ub[i] - h->ub.qe; }
-        for (int rep = 0; rep < 2; rep++, off += n)
-            for (int i = 0; i < n; i++) { gl[off + i] = -h->robot.speed_limits[i] + h->ub.qde; gu[off + i] = h->robot.speed_limits[i] - h->ub.qde; }
+    const slv::RowRule R = armour_row_rule(h);
+    const slv::RowLimits L = armour_row_limits(h);
+    for (int b = 0; b < h->B; b++) {   // RT/NLPclass.cu:87-165; ARMTD mode (CMP/NLPclass.cu:73-140): the same collision and limit bounds, no torque rows
+        const double* tr = torque_radius_of(h, b);
+        for (int r = 0; r < R.m; r++) slv::row_bounds(R, L, r, tr, &g_l[(size_t)b * R.m + r], &g_u[(size_t)b * R.m + r]);
     }
     return ARMOUR_OK;
 }
 
 int armour_checked_collision_rows(const ArmourPlanner* h) {
     return h->mode == ARMOUR_MODE_ARMTD ? (h->n - 1 < h->J ? h->n - 1 : h->J) * h->T * h->O : h->Q;
+}
+
+slv::RowRule armour_row_rule(const ArmourPlanner* h) {
+    slv::RowRule R;
+    R.n = h->n; R.T = h->T; R.m = h->m; R.row0 = h->row0; R.Q = h->Q; R.n_checked = armour_checked_collision_rows(h);
+    R.torque_slack = h->params.torque_violation_threshold; R.collision_slack = h->params.collision_violation_threshold;
+    return R;
+}
+
+slv::RowLimits armour_row_limits(const ArmourPlanner* h) {
+    slv::RowLimits L;
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
+        L.torque_limits[j] = h->robot.torque_limits[j]; L.lb[j] = h->robot.state_limits_lb[j]; L.ub[j] = h->robot.state_limits_ub[j]; L.speed[j] = h->robot.speed_limits[j];
+    }
+    L.qe = h->ub.qe; L.qde = h->ub.qde;
+    return L;
 }
 
 // joint i's coefficients of problem b for the plan point (solver_common.h slv::plan_point)
@@ -503,18 +505,16 @@ extern "C" int armour_eval_f(ArmourPlanner* h, const double* k, double* f) {
     NEED_READY(h);
     const int n = h->n;
     for (int b = 0; b < h->B; b++) {
-        double obj = 0;
-        for (int pass = 0; pass < 2; pass++)  // continuous joints first (solver_common.h)
-            for (int i = 0; i < n; i++) {
-                if ((h->robot.continuous[i] != 0) != (pass == 0)) continue;
-                const size_t ix = (size_t)b * n + i;
-                double c[3];
-                armour_plan_coeffs(h, ix, c);
-                const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], h->params.t_plan);
-                const double e = h->robot.continuous[i] ? slv::wrap_to_pi(h->h_qdes[ix] - qp) : (h->h_qdes[ix] - qp);
-                obj += e * e;
-            }
-        f[b] = obj * h->params.cost_scale;
+        double sq[slv::NV];
+        for (int i = 0; i < n; i++) {
+            const size_t ix = (size_t)b * n + i;
+            double c[3];
+            armour_plan_coeffs(h, ix, c);
+            const double qp = slv::plan_point(h->mode, c[0], c[1], c[2], h->params.k_range[i], k[ix], h->params.t_plan);
+            const double e = h->robot.continuous[i] ? slv::wrap_to_pi(h->h_qdes[ix] - qp) : (h->h_qdes[ix] - qp);
+            sq[i] = e * e;
+        }
+        f[b] = slv::cost_from_sq(n, h->continuous_mask(), sq, h->params.cost_scale);
     }
     return ARMOUR_OK;
 }
@@ -683,62 +683,39 @@ extern "C" int armour_eval_g_jac(ArmourPlanner* h, const double* k, double* g, d
 
 extern "C" int armour_check_feasible(ArmourPlanner* h, const double* g, int32_t* feasible) {
     NEED_READY(h);
-    const int T = h->T, n = h->n;
-    const double tt = h->params.torque_violation_threshold, ct = h->params.collision_violation_threshold;
+    // RT/NLPclass.cu:422-538; CMP/NLPclass.cu:391-402 re-checks the collision rows of links 0 .. NUM_FACTORS-2 only (RT checks every link)
+    const slv::RowRule R = armour_row_rule(h);
+    const slv::RowLimits L = armour_row_limits(h);
     for (int b = 0; b < h->B; b++) {
-        const double* gb = g + (size_t)b * h->m;
+        const double* gb = g + (size_t)b * R.m;
+        const double* tr = torque_radius_of(h, b);
         bool ok = true;
-        if (!h->no_torque()) {   // RT/NLPclass.cu:453
-            const double* tr = &h->h_torque_radius[(size_t)b * n * T];
-            for (int t = 0; t < T && ok; t++)
-                for (int j = 0; j < n; j++) {
-                    const double v = gb[t * n + j];
-                    if (v < -h->robot.torque_limits[j] + tr[j * T + t] - tt || v > h->robot.torque_limits[j] - tr[j * T + t] + tt) { ok = false; break; }
-                }
+        for (int r = 0; r < R.m && ok; r++) {
+            double l, u;
+            slv::row_bounds(R, L, r, tr, &l, &u);
+            ok = !slv::outside_slack(R, r, gb[r], l, u);
         }
-        size_t off = (size_t)h->row0;
-        // CMP/NLPclass.cu:391-402 re-checks the collision rows of links 0 .. NUM_FACTORS-2 only (RT checks every link)
-        const size_t n_checked = (size_t)armour_checked_collision_rows(h);
-        for (size_t i = 0; i < n_checked && ok; i++)
-            if (gb[off + i] > ct) ok = false;
-        off += h->Q;
-        for (int rep = 0; rep < 2 && ok; rep++, off += n)
-            for (int i = 0; i < n; i++)
-                if (gb[off + i] < h->robot.state_limits_lb[i] + h->ub.qe || gb[off + i] > h->robot.state_limits_ub[i] - h->ub.qe) { ok = false; break; }
-        for (int rep = 0; rep < 2 && ok; rep++, off += n)
-            for (int i = 0; i < n; i++)
-                if (gb[off + i] < -h->robot.speed_limits[i] + h->ub.qde || gb[off + i] > h->robot.speed_limits[i] - h->ub.qde) { ok = false; break; }
         feasible[b] = ok ? 1 : 0;
     }
     return ARMOUR_OK;
 }
 
-// g_l / g_u of every problem on the device, the values of armour_get_bounds (RT/NLPclass.cu:87-165) expression for expression, filled by a kernel
-// from the torque radii (B n T doubles to upload instead of 2 B m: 73 MB at B = 128, O = 50 -- 3 ms of the first armour_solve after a build)
+// g_l / g_u of every problem on the device, filled by a kernel from the torque radii (B n T doubles to upload instead of 2 B m: 73 MB at
+// B = 128, O = 50 -- 3 ms of the first armour_solve after a build)
 namespace {
 struct BoundsArgs {
-    int n, T, m, row0, Q, no_torque;
-    double torque_limits[ARMOUR_MAX_FACTORS], lb[ARMOUR_MAX_FACTORS], ub[ARMOUR_MAX_FACTORS], speed[ARMOUR_MAX_FACTORS];
-    double qe, qde;
+    slv::RowRule rule;
+    slv::RowLimits lim;
     const double* tr;   // [B][n][T]
     double* lo; double* hi;   // [B][m]
 };
 __global__ __launch_bounds__(256) void armour_bounds_kernel(BoundsArgs a) {
-    const int b = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.m) return;
+    const int b = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x, m = a.rule.m;
+    if (r >= m) return;
     double l, u;
-    if (r < a.row0) {   // row t * n + j
-        const int t = r / a.n, j = r - t * a.n;
-        const double tr = a.tr[((size_t)b * a.n + j) * a.T + t];
-        l = -a.torque_limits[j] + tr; u = a.torque_limits[j] - tr;
-    } else if (r < a.row0 + a.Q) { l = -1e19; u = 0; }
-    else {
-        const int e = r - a.row0 - a.Q, rep = e / a.n, i = e - rep * a.n;
-        if (rep < 2) { l = a.lb[i] + a.qe; u = a.ub[i] - a.qe; }
-        else { l = -a.speed[i] + a.qde; u = a.speed[i] - a.qde; }
-    }
-    a.lo[(size_t)b * a.m + r] = l;
-    a.hi[(size_t)b * a.m + r] = u;
+    slv::row_bounds(a.rule, a.lim, r, a.tr + (size_t)b * a.rule.n * a.rule.T, &l, &u);
+    a.lo[(size_t)b * m + r] = l;
+    a.hi[(size_t)b * m + r] = u;
 }
 }  // namespace
 
@@ -746,11 +723,7 @@ __global__ __launch_bounds__(256) void armour_bounds_kernel(BoundsArgs a) {
 int armour_bounds_launch(ArmourPlanner* h, const double* d_tr) {
     const size_t bm = (size_t)h->B * h->m;
     BoundsArgs a;
-    a.n = h->n; a.T = h->T; a.m = h->m; a.row0 = h->row0; a.Q = h->Q; a.no_torque = h->no_torque() ? 1 : 0;
-    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
-        a.torque_limits[j] = h->robot.torque_limits[j]; a.lb[j] = h->robot.state_limits_lb[j]; a.ub[j] = h->robot.state_limits_ub[j]; a.speed[j] = h->robot.speed_limits[j];
-    }
-    a.qe = h->ub.qe; a.qde = h->ub.qde;
+    a.rule = armour_row_rule(h); a.lim = armour_row_limits(h);
     a.lo = h->d_bounds; a.hi = h->d_bounds + bm;
     a.tr = d_tr;
     hipLaunchKernelGGL(armour_bounds_kernel, dim3((h->m + 255) / 256, h->B), dim3(256), 0, h->stream, a);
@@ -827,54 +800,21 @@ extern "C" int armour_get_option(ArmourPlanner* h, int32_t option, double* value
 // ---- reduced outputs: the row test of finalize_solution on the device (RT/NLPclass.cu:422-538; CMP/NLPclass.cu:391-402) ----
 namespace {
 struct ViolArgs {
-    int m, row0, Q, n_checked;   // rows per problem; first collision row; collision rows; how many of them the verdict re-checks
-    double torque_slack, collision_slack;
+    slv::RowRule rule;
     const double* g; const double* lo; const double* hi;   // [B][m] each
     ArmourViolation* out;                                   // [B]
 };
-// One 256-thread block per problem.  Thread t takes rows t, t + 256, ... in ascending order and the partial records are
-// combined by a fixed tree, so a record depends on (problem, k) alone.  The outside-the-slack test repeats
-// armour_check_feasible's expressions on the uploaded bounds: (g_l - slack), (g_u + slack) are the host's
-// (-limit + radius) - slack and (limit - radius) + slack.
+// One 256-thread block per problem: the record of row_rules.h over every row, on the uploaded bounds.
 __global__ __launch_bounds__(256) void armour_violation_kernel(ViolArgs a) {
-    __shared__ double s_l1[256], s_w[256];
-    __shared__ int s_row[256], s_nv[256], s_no[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const double* g = a.g + (size_t)b * a.m;
-    const double* lo = a.lo + (size_t)b * a.m;
-    const double* hi = a.hi + (size_t)b * a.m;
-    double l1 = 0.0, worst = 0.0;
-    int wrow = -1, nv = 0, no = 0;
-    for (int r = tid; r < a.m; r += 256) {
-        const double v = g[r], l = lo[r], u = hi[r];
-        const double viol = fmax(0.0, fmax(l - v, v - u));
-        l1 += viol;
-        if (viol > 0.0) nv++;
-        if (viol > worst) { worst = viol; wrow = r; }
-        bool outside;
-        if (r < a.row0) outside = v < l - a.torque_slack || v > u + a.torque_slack;
-        else if (r < a.row0 + a.Q) outside = (r - a.row0) < a.n_checked && v > a.collision_slack;
-        else outside = v < l || v > u;
-        if (outside) no++;
-    }
-    s_l1[tid] = l1; s_w[tid] = worst; s_row[tid] = wrow; s_nv[tid] = nv; s_no[tid] = no;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            s_l1[tid] += s_l1[tid + s]; s_nv[tid] += s_nv[tid + s]; s_no[tid] += s_no[tid + s];
-            const double ow = s_w[tid + s];
-            const int orow = s_row[tid + s];
-            // the larger violation wins; among equals the lower row
-            if (ow > s_w[tid] || (ow == s_w[tid] && orow >= 0 && (s_row[tid] < 0 || orow < s_row[tid]))) { s_w[tid] = ow; s_row[tid] = orow; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        ArmourViolation o;
-        o.l1_violation = s_l1[0]; o.worst = s_w[0]; o.worst_row = s_row[0]; o.n_violated = s_nv[0]; o.n_outside_slack = s_no[0];
-        o.feasible = s_no[0] == 0 ? 1 : 0;
-        a.out[b] = o;
-    }
+    __shared__ slv::ViolShared<1> sh;
+    const int b = blockIdx.x, tid = threadIdx.x, m = a.rule.m;
+    const double* g = a.g + (size_t)b * m;
+    const double* lo = a.lo + (size_t)b * m;
+    const double* hi = a.hi + (size_t)b * m;
+    slv::ViolPartial p[1];
+    for (int r = tid; r < m; r += 256) p[0].take(a.rule, r, g[r], lo[r], hi[r]);
+    slv::ViolPartial::tree_reduce(sh, p, tid);
+    if (tid == 0) a.out[b] = slv::ViolPartial::finish(sh, 0);
 }
 }  // namespace
 
@@ -892,8 +832,7 @@ static int eval_violations_device_impl(ArmourPlanner* h, const double* d_k, Armo
     rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), d_k, h->d_g, nullptr, st);
     if (rc != ARMOUR_OK) return rc;
     ViolArgs a;
-    a.m = h->m; a.row0 = h->row0; a.Q = h->Q; a.n_checked = armour_checked_collision_rows(h);
-    a.torque_slack = h->params.torque_violation_threshold; a.collision_slack = h->params.collision_violation_threshold;
+    a.rule = armour_row_rule(h);
     a.g = h->d_g; a.lo = h->d_bounds; a.hi = h->d_bounds + (size_t)h->B * h->m; a.out = d_out;
     hipLaunchKernelGGL(armour_violation_kernel, dim3(h->B), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());

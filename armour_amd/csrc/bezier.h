@@ -83,6 +83,18 @@ __host__ __device__ inline double qd_extremum_dk(double q0, double a, double b, 
     return dqddk + qdd_des(q0, a, b, k, ts) * dts;
 }
 
+// min / max of a curve over t in [0,1] from its values v1 at t = 0, v2 / v3 at the stationary points e2 / e3 (counted when they lie in [0,1])
+// and v4 at t = 1, and which of the four each is (RT/Trajectory.cu:290-330).  The joint-limit rows of every evaluation select with this rule.
+__host__ __device__ inline void select_extrema(double v1, double v2, double v3, double v4, double e2, double e3, double* mn_out, double* mx_out,
+                                               int* mnId_out, int* mxId_out) {
+    double mn, mx;
+    int mnId, mxId;
+    if (v1 < v4) { mn = v1; mnId = 1; mx = v4; mxId = 4; } else { mn = v4; mnId = 4; mx = v1; mxId = 1; }
+    if (0 <= e2 && e2 <= 1) { if (v2 < mn) { mn = v2; mnId = 2; } if (mx < v2) { mx = v2; mxId = 2; } }
+    if (0 <= e3 && e3 <= 1) { if (v3 < mn) { mn = v3; mnId = 3; } if (mx < v3) { mx = v3; mxId = 3; } }
+    *mn_out = mn; *mx_out = mx; *mnId_out = mnId; *mxId_out = mxId;
+}
+
 // One joint's min / max of position (velocity == false) or velocity (true) over t in [0,1] and their
 // derivative w.r.t. the *normalised* parameter k in [-1,1] (RT/Trajectory.cu:290-397, 433-540).
 // The t = 1 branch returns slope 1.0 for velocity rows as well, as the reference does (:503,:521).
@@ -98,9 +110,7 @@ __host__ __device__ inline void joint_extremum(double q0, double a, double b, do
     const double v4 = velocity ? qd_des(q0, a, b, ka, 1.0) : q_des(q0, a, b, ka, 1.0);
     double mn, mx;
     int mnId, mxId;
-    if (v1 < v4) { mn = v1; mnId = 1; mx = v4; mxId = 4; } else { mn = v4; mnId = 4; mx = v1; mxId = 1; }
-    if (0 <= e2 && e2 <= 1) { if (v2 < mn) { mn = v2; mnId = 2; } if (mx < v2) { mx = v2; mxId = 2; } }
-    if (0 <= e3 && e3 <= 1) { if (v3 < mn) { mn = v3; mnId = 3; } if (mx < v3) { mx = v3; mxId = 3; } }
+    select_extrema(v1, v2, v3, v4, e2, e3, &mn, &mx, &mnId, &mxId);
     *mn_out = velocity ? mn / duration : mn;
     *mx_out = velocity ? mx / duration : mx;
     const double sc = velocity ? k_range / duration : k_range;

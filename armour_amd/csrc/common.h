@@ -11,6 +11,7 @@
 
 #include "../../include/armour_hip.h"
 #include "device_mem.h"
+#include "row_rules.h"
 
 #define ARMOUR_NPLANES 36
 #define ARMOUR_PLANE_COMPONENTS 5  // Ax, Ay, Az, d, delta
@@ -133,6 +134,7 @@ struct ArmourPlanner {
     // no torque rows, forward kinematics only: the comparison planner (CMP/), or the ARMOUR trajectory with TURN_OFF_INPUT_CONSTRAINTS
     // (ArmourParams.input_constraints_off: RT/Parameters.h:46-47, RT/armour_main.cu:115,149-165, RT/NLPclass.cu:46-54)
     bool no_torque() const { return mode == ARMOUR_MODE_ARMTD || params.input_constraints_off != 0; }
+    int continuous_mask() const { int mk = 0; for (int i = 0; i < n; i++) if (robot.continuous[i]) mk |= 1 << i; return mk; }   // bit i: joint i is continuous
     int row0 = 0;                   // rows before the collision block (n*T torque rows, or 0 in ARMTD mode)
     std::vector<double> h_krange;   // ARMTD mode: [B][n] acceleration range of each problem's JRS tables
     DevBuf<double> d_jrs;           // ARMTD mode: [B][n][6][T] c/g/r of cos, then of sin (the order of armtd.in)
@@ -222,6 +224,12 @@ int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourVio
 int armour_refresh_table_stats(ArmourPlanner* h);
 // collision rows the feasibility re-check looks at (all Q in ARMOUR mode; the first (n-1)*T*O in ARMTD mode, CMP/NLPclass.cu:391-402)
 int armour_checked_collision_rows(const ArmourPlanner* h);
+// the current problem set's row rule and what its bounds are made of (row_rules.h): every kernel's arguments and the host's closed forms take these
+slv::RowRule armour_row_rule(const ArmourPlanner* h);
+slv::RowLimits armour_row_limits(const ArmourPlanner* h);
+#define NEED_READY(h)                                                                        \
+    if (!(h)) { armour_set_error("null handle"); return ARMOUR_EINVAL; }                     \
+    if (!(h)->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
 // joint ix = b * n + i's coefficients c0, c1, c2 of the cost's plan point (solver_common.h slv::plan_point): what armour_eval_f and the sweep's cost read
 void armour_plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]);
 // page-locked scratch slot of the handle with at least `bytes` bytes (registered for the zero-copy eval path); nullptr on failure

@@ -608,7 +608,7 @@ __device__ __forceinline__ void limit_block(const P2Tables& tb, const P2Launch& 
     // ------------------------------------------------------------------ joint limit rows
     // RT/Trajectory.cu:256-540.  One thread per (joint, position|velocity, piece): pieces 0-3 evaluate the curve
     // at t = 0, the two stationary points and t = 1, pieces 4-5 the d/dk of the two interior extrema; a second
-    // step per (joint, position|velocity) selects min / max exactly as bez::joint_extremum does.
+    // step per (joint, position|velocity) selects min / max as bez::select_extrema does, written out.
     double* pv = lds;  // [2n][8]
     const int jv = tid >> 3, piece = tid & 7;
     const double* bz = tb.bez + (size_t)b * 3 * n;

@@ -257,64 +257,39 @@ __global__ __launch_bounds__(64) void armour_sparse_collision_g_kernel(RelTables
     sparse_collision_row<false>(tb, sl, b, i, kp, g_all + (size_t)b * tb.m, nullptr);
 }
 
-// ---- armour_violation_kernel (api.hip) over the torque rows, the LISTED collision rows and the limit rows.  Thread t takes the rows r with
-// r mod 256 == t in ascending order, as the full kernel does, and the same tree combines the partial records: an unlisted row would have added
-// exactly 0 to every field, so the record is the full kernel's bit for bit (worst / worst_row: whenever any row is violated).
+// ---- the record of armour_violation_kernel (api.hip) over the torque rows, the LISTED collision rows and the limit rows.  Thread t takes the
+// rows r with r mod 256 == t in ascending order, as the full kernel does: an unlisted row would have added exactly 0 to every field, so the
+// record is the full kernel's bit for bit (worst / worst_row: whenever any row is violated).
 struct SparseViolArgs {
-    int m, row0, Q, n_checked;
-    double torque_slack, collision_slack;
+    slv::RowRule rule;
     const double* g; const double* lo; const double* hi;
     const int* rows_res; const int* count_res;   // (by residue class of the row index: armour_rel_list_kernel)
-    const double* k; int n;                      // the point [B][n]: the lists hold for k inside the box only
+    const double* k;                             // the point [B][n]: the lists hold for k inside the box only
     ArmourViolation* out;
 };
 __global__ __launch_bounds__(256) void armour_sparse_violation_kernel(SparseViolArgs a) {
-    __shared__ double s_l1[256], s_w[256];
-    __shared__ int s_row[256], s_nv[256], s_no[256];
+    __shared__ slv::ViolShared<1> sh;
+    const slv::RowRule& R = a.rule;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const double* g = a.g + (size_t)b * a.m;
-    const double* lo = a.lo + (size_t)b * a.m;
-    const double* hi = a.hi + (size_t)b * a.m;
-    double l1 = 0.0, worst = 0.0;
-    int wrow = -1, nv = 0, no = 0;
-    auto take = [&](int r) {
-        const double v = g[r], l = lo[r], u = hi[r];
-        const double viol = fmax(0.0, fmax(l - v, v - u));
-        l1 += viol;
-        if (viol > 0.0) nv++;
-        if (viol > worst) { worst = viol; wrow = r; }
-        bool outside;
-        if (r < a.row0) outside = v < l - a.torque_slack || v > u + a.torque_slack;
-        else if (r < a.row0 + a.Q) outside = (r - a.row0) < a.n_checked && v > a.collision_slack;
-        else outside = v < l || v > u;
-        if (outside) no++;
-    };
-    for (int r = tid; r < a.row0; r += 256) take(r);
-    const int per = (a.Q + 255) / 256;
+    const double* g = a.g + (size_t)b * R.m;
+    const double* lo = a.lo + (size_t)b * R.m;
+    const double* hi = a.hi + (size_t)b * R.m;
+    slv::ViolPartial p[1];
+    auto take = [&](int r) { p[0].take(R, r, g[r], lo[r], hi[r]); };
+    for (int r = tid; r < R.row0; r += 256) take(r);
+    const int per = (R.Q + 255) / 256;
     const int* mine = a.rows_res + ((size_t)b * 256 + tid) * per;   // the listed rows with (row0 + q) mod 256 == tid, ascending
     const int cnt = a.count_res[(size_t)b * 256 + tid];
-    for (int i = 0; i < cnt; i++) take(a.row0 + mine[i]);
-    for (int r = a.row0 + a.Q + ((tid - (a.row0 + a.Q)) & 255); r < a.m; r += 256) take(r);
-    s_l1[tid] = l1; s_w[tid] = worst; s_row[tid] = wrow; s_nv[tid] = nv; s_no[tid] = no;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            s_l1[tid] += s_l1[tid + s]; s_nv[tid] += s_nv[tid + s]; s_no[tid] += s_no[tid + s];
-            const double ow = s_w[tid + s];
-            const int orow = s_row[tid + s];
-            if (ow > s_w[tid] || (ow == s_w[tid] && orow >= 0 && (s_row[tid] < 0 || orow < s_row[tid]))) { s_w[tid] = ow; s_row[tid] = orow; }
-        }
-        __syncthreads();
-    }
+    for (int i = 0; i < cnt; i++) take(R.row0 + mine[i]);
+    for (int r = R.row0 + R.Q + ((tid - (R.row0 + R.Q)) & 255); r < R.m; r += 256) take(r);
+    slv::ViolPartial::tree_reduce(sh, p, tid);
     if (tid == 0) {
-        ArmourViolation o;
-        o.l1_violation = s_l1[0]; o.worst = s_w[0]; o.worst_row = s_row[0]; o.n_violated = s_nv[0]; o.n_outside_slack = s_no[0];
-        o.feasible = s_no[0] == 0 ? 1 : 0;
+        ArmourViolation o = slv::ViolPartial::finish(sh, 0);
         // The mask says "never violated for a k of [-1, 1]^n".  A point outside the box may violate an unlisted row, so its record cannot claim to be
         // the full evaluation's: it is marked instead (feasible = -1, worst_row = -2; armour_hip.h) -- the host entry never gets here with such a point
         // (it takes every row then), a device caller re-evaluates the problem with ARMOUR_OPT_CULL_ROWS = 0.
         bool in_box = true;
-        for (int j = 0; j < a.n; j++) in_box = in_box && fabs(a.k[(size_t)b * a.n + j]) <= 1.0;
+        for (int j = 0; j < R.n; j++) in_box = in_box && fabs(a.k[(size_t)b * R.n + j]) <= 1.0;
         if (!in_box) { o.feasible = -1; o.worst_row = -2; }
         a.out[b] = o;
     }
@@ -463,9 +438,8 @@ int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourVio
     if (h->rel.max_count > 0)
         hipLaunchKernelGGL(armour_sparse_collision_g_kernel, dim3((h->rel.max_count + 63) / 64, h->B), dim3(64), 0, st, a, d_k, h->d_g);
     SparseViolArgs v;
-    v.m = h->m; v.row0 = h->row0; v.Q = h->Q; v.n_checked = armour_checked_collision_rows(h);
-    v.torque_slack = h->params.torque_violation_threshold; v.collision_slack = h->params.collision_violation_threshold;
-    v.g = h->d_g; v.lo = a.lo; v.hi = a.hi; v.rows_res = a.rows_res; v.count_res = a.count_res; v.k = d_k; v.n = h->n; v.out = d_out;
+    v.rule = armour_row_rule(h);
+    v.g = h->d_g; v.lo = a.lo; v.hi = a.hi; v.rows_res = a.rows_res; v.count_res = a.count_res; v.k = d_k; v.out = d_out;
     hipLaunchKernelGGL(armour_sparse_violation_kernel, dim3(h->B), dim3(256), 0, st, v);
     HIPCHK(hipGetLastError());
     return ARMOUR_OK;

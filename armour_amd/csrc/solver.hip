@@ -213,15 +213,16 @@ QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<Q
 constexpr int kScanRowsPerBlock = 2048;
 
 // MODE 0: violation only (line-search trials); 1: violation + candidate rows (new linearisation); 2: violation + number of
-// rows outside [g_l - slack, g_u + slack] with the slacks of armtd_NLP::finalize_solution (RT/NLPclass.cu:422-538:
-// torque rows 1e-2, collision rows 1e-4, limit rows 0) -- the verdict armour_check_feasible gives on the host.
+// rows outside the slacks of armtd_NLP::finalize_solution (RT/NLPclass.cu:422-538: torque rows 1e-2, collision rows 1e-4,
+// limit rows 0; row_rules.h) -- the verdict armour_check_feasible gives on the host.
 template <int MODE>
-__global__ __launch_bounds__(256) void armour_solve_scan_kernel(int m, int n, int n_torque_rows, int n_collision_rows, int n_unchecked_rows, double torque_slack, double collision_slack, const double* __restrict__ g_all, const double* __restrict__ jac_all,
+__global__ __launch_bounds__(256) void armour_solve_scan_kernel(slv::RowRule rule, const double* __restrict__ g_all, const double* __restrict__ jac_all,
                                                                 const double* __restrict__ lo_all, const double* __restrict__ hi_all, int cap,
                                                                 long long* __restrict__ viol_out, int* __restrict__ count_out, SolveRow* __restrict__ rows_out) {
     // grid (segments, B): a block owns kScanRowsPerBlock consecutive rows and its own slice of the outputs; the host
     // concatenates the slices in segment order
     const int b = blockIdx.y, seg = blockIdx.x, nseg = gridDim.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int m = rule.m, n = rule.n;
     const double* g = g_all + (size_t)b * m;
     constexpr bool ROWS = MODE == 1;
     const double* jac = ROWS ? jac_all + (size_t)b * m * n : nullptr;
@@ -238,12 +239,7 @@ __global__ __launch_bounds__(256) void armour_solve_scan_kernel(int m, int n, in
         const bool in = i < row_end;
         const double gi = in ? g[i] : 0.0, li = in ? lo[i] : -1e300, ui = in ? hi[i] : 1e300;
         vsum += slv::row_violation(gi, li, ui);
-        if (MODE == 2 && in) {
-            // (ARMTD mode: the re-check of CMP/NLPclass.cu:391-402 skips the collision rows of the last links)
-            const int ic = i - n_torque_rows - n_collision_rows;
-            const double slack = i < n_torque_rows ? torque_slack : ic < 0 ? collision_slack : 0.0;
-            if ((ic < 0 || ic >= n_unchecked_rows) && (gi < li - slack || gi > ui + slack)) bad++;
-        }
+        if (MODE == 2 && in && slv::outside_slack(rule, i, gi, li, ui)) bad++;
         if (ROWS) {
             double J[NV], l1 = 0.0;
 #pragma unroll
@@ -457,11 +453,11 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     a.ctl = w.ctl.as<SolveCtl>(); a.blk_word = w.blk_word.as<BlockWord>();
     a.blk_rows = w.blk_rows.as<SolveRow>(); a.qp_rows = w.qp_rows.as<SolveRow>(); a.flags = w.flags;
     a.q_des = reinterpret_cast<const double*>(w.ctl + off_qdes); a.out = s.hres;   // the kernel writes the results straight into page-locked host memory
-    for (int i = 0; i < n; i++) if (h->robot.continuous[i]) a.continuous_mask |= 1 << i;
+    a.continuous_mask = h->continuous_mask();
     a.max_iter = opt.max_iterations; a.max_ls = opt.max_line_search; a.tol = opt.tolerance;
-    a.n_checked_collision = armour_checked_collision_rows(h);
+    const slv::RowRule rule = armour_row_rule(h);
+    a.n_checked_collision = rule.n_checked; a.torque_slack = rule.torque_slack; a.collision_slack = rule.collision_slack;
     a.t_plan = h->params.t_plan; a.cost_scale = h->params.cost_scale;
-    a.torque_slack = h->params.torque_violation_threshold; a.collision_slack = h->params.collision_violation_threshold;
     a.budget_ticks = -1;
     if (opt.max_wall_time_s > 0) {   // (sub-batches run one after the other: each gets an equal share of what is left)
         const double left_ms = (opt.max_wall_time_s - std::chrono::duration<double>(Clock::now() - t_begin).count()) * 1e3 / p.n_launch;
@@ -622,11 +618,9 @@ static int evaluate(HostSolve& s, Scan mode) {
     const bool rows = mode == Scan::Rows;
     int r = armour_eval_g_jac_device(h, s.hk, h->d_g, rows ? h->d_jac : nullptr, h->stream);
     if (r != ARMOUR_OK) return r;
-    const int nCol = armour_checked_collision_rows(h);
     const auto scan = mode == Scan::Violation ? armour_solve_scan_kernel<0> : rows ? armour_solve_scan_kernel<1> : armour_solve_scan_kernel<2>;
-    hipLaunchKernelGGL(scan, dim3(nseg, B), dim3(256), 0, h->stream, m, n, h->row0, nCol, h->Q - nCol, h->params.torque_violation_threshold,
-                       h->params.collision_violation_threshold, h->d_g, rows ? h->d_jac : nullptr, h->d_bounds, h->d_bounds + bm, s.cap_rows, s.hviol_seg,
-                       mode == Scan::Violation ? nullptr : s.hcount, rows ? s.hrows : nullptr);
+    hipLaunchKernelGGL(scan, dim3(nseg, B), dim3(256), 0, h->stream, armour_row_rule(h), h->d_g, rows ? h->d_jac : nullptr,
+                       h->d_bounds, h->d_bounds + bm, s.cap_rows, s.hviol_seg, mode == Scan::Violation ? nullptr : s.hcount, rows ? s.hrows : nullptr);
     HIPCHK(hipGetLastError());
     if ((r = armour_spin_on_stream(h->stream)) != ARMOUR_OK) return r;
     for (int b = 0; b < B; b++) {
@@ -842,8 +836,8 @@ static int solve_on_host(ArmourPlanner* h, const ArmourSolveOptions& opt, const 
 extern "C" int armour_solve(ArmourPlanner* h, const ArmourSolveOptions* opt_in, ArmourSolveResult* results) { return armour_solve_from(h, opt_in, nullptr, results); }
 
 extern "C" int armour_solve_from(ArmourPlanner* h, const ArmourSolveOptions* opt_in, const double* k_start, ArmourSolveResult* results) {
-    if (!h || !results) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
-    if (!h->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
+    if (!results) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
+    NEED_READY(h);
     if (k_start)   // the variables' box (and the box the culled form's row lists hold in): checked before the device is touched
         for (size_t i = 0; i < (size_t)h->B * h->n; i++)
             if (!(std::fabs(k_start[i]) <= 1.0)) { armour_set_error("armour_solve_from: k_start[%zu] = %g is outside [-1, 1]", i, k_start[i]); return ARMOUR_EINVAL; }

@@ -1,6 +1,6 @@
 // Pieces shared by the two forms of armour_solve (solver.hip: QPs on the host; solver_device.hip: the whole SQP iterate
-// in one persistent kernel): the cost's per-joint rule (also api.hip's armour_eval_f / _grad_f), the candidate-row record,
-// the row filter, and the fixed-point violation sum.
+// in one persistent kernel): the cost's per-joint rule and its sum (also api.hip's armour_eval_f / _grad_f and the sweep), the
+// candidate-row record, the row filter, and the fixed-point violation sum.  What a row means is in row_rules.h.
 #pragma once
 #include <cmath>
 
@@ -28,6 +28,14 @@ __host__ __device__ inline double plan_point(int mode, double c0, double c1, dou
 }
 __host__ __device__ inline double plan_dk(int mode, double c2, double k_range_i, double tp) {  // d plan_point / dk
     return mode == ARMOUR_MODE_ARMTD ? cacc::q_plan_dk(c2) : (tp * tp * tp) * (6 * tp * tp - 15 * tp + 10) * k_range_i;
+}
+// f from the joints' squared errors sq[i] = e_i^2: the continuous joints first, then the others (bit i of continuous_mask: joint i is continuous)
+__host__ __device__ inline double cost_from_sq(int n, int continuous_mask, const double* sq, double cost_scale) {
+    double obj = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int i = 0; i < n; i++)
+            if ((((continuous_mask >> i) & 1) != 0) == (pass == 0)) obj += sq[i];
+    return obj * cost_scale;
 }
 __host__ __device__ inline double hess_diag(double cost_scale, double dk) {  // the cost's constant Hessian entry, floored: G stays positive definite
     const double Hd = 2.0 * cost_scale * dk * dk;

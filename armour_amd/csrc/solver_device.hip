@@ -93,7 +93,7 @@ __device__ inline double plan_point(const SolveArgs& a, const double* bz, int i,
     return a.tb.mode == ARMOUR_MODE_ARMTD ? cacc::q_plan(bz[i], bz[n + i], bz[2 * n + i], k)
                                           : bez::q_des(bz[i], bz[n + i], bz[2 * n + i], a.tb.k_range[i] * k, a.t_plan);
 }
-// eval_f from the joints' squared errors, added in the order of solver_common.h (continuous joints first)
+// eval_f from the joints' squared errors: slv::cost_from_sq written out (called instead, it reads n and the mask once: another schedule, as above)
 __device__ inline double cost_sum(const SolveArgs& a, const double* sq) {
     double obj = 0;
     for (int pass = 0; pass < 2; pass++)
@@ -134,8 +134,8 @@ __device__ inline int block_exclusive_scan(int v, int* si4, int& total) {
 
 // ------------------------------------------------------------------------------------------------ per-block scan
 // The block's rows after an evaluation: their L1 violation (fixed point), the candidate rows of the QP compacted in row order
-// into `rows`, and the number of rows outside [g_l - slack, g_u + slack] (finalize_solution).  The row tests are the host
-// form's (solver_common.h; MODE is kept for the two tests' placement only: every phase runs 3 = all of it).
+// into `rows`, and the number of rows outside the slacks: slv::outside_slack (row_rules.h) written out, for the same reason as plan_point
+// above.  The candidate tests are the host form's (solver_common.h; MODE is kept for the two tests' placement only: every phase runs 3).
 struct ScanShared {
     int wave_tot[4];
     long long red[256];

@@ -10,10 +10,10 @@
 // entries ONCE (keys and coefficients of a torque row; link-PZ monomials and packed planes of a listed collision row; the closed form of a
 // limit row) and evaluates them for its C candidates.  The arithmetic is that of p2_sparse.h's sparse_torque_row / sparse_collision_row and of
 // p2_tiles.h's limit_block, statement for statement with the candidate index added, so every g is the fused evaluation's bit for bit.
-// Thread t of the 256 owns the rows r = t (mod 256) in ascending order and the tree of armour_sparse_violation_kernel combines the partial
-// records: l1_violation is that kernel's sum bit for bit as well.  The C partial records of a thread live in registers (every loop over the
-// candidates has a compile-time trip count; nothing is indexed by a run-time candidate number), and no g is ever stored: there is no scratch
-// buffer that grows with S.
+// The record is row_rules.h's, C of them side by side: thread t of the 256 owns the rows r = t (mod 256) in ascending order, so l1_violation
+// is the row test's sum bit for bit as well.  The C partial records of a thread live in registers (every loop over the candidates has a
+// compile-time trip count; nothing is indexed by a run-time candidate number), and no g is ever stored: there is no scratch buffer that
+// grows with S.
 #include <cmath>
 #include <vector>
 
@@ -35,21 +35,21 @@ constexpr int kPlaneBatch = 6;   // planes of a listed row requested together, a
 
 struct SweepArgs {
     P2Tables tb;
+    slv::RowRule rule;
     SparseList sl;                                // the relevance lists: rows [B][Q] ascending, their packed plane entries
     const int* rows_res; const int* count_res;    // the same rows by (row index mod 256): [B][256][ceil(Q / 256)] | [B][256]
     const double* lo; const double* hi;           // bounds [B][m]
     const double* k;                              // candidates [S][n], or [B][S][n] with k_pstride = S * n
     long long k_pstride;
-    int S, strideT, n_checked;
-    double torque_slack, collision_slack;
+    int S, strideT;
     const double* coef;                           // [B][4][n]: the plan point's c0, c1, c2 (armour_plan_coeffs) and q_des
     int continuous_mask;
     double t_plan, cost_scale;
     ArmourSweepRecord* out;                       // [B][S]
 };
 
-// g of the limit row of joint i in block blk (0 .. 3: the n rows of min position, max position, min velocity, max velocity) of problem b at the joint's parameter kj: the
-// selection of p2_tiles.h's limit_block (= bez::joint_extremum) on the same four values; ARMTD mode: cacc::joint_extrema
+// g of the limit row of joint i in block blk (0 .. 3: the n rows of min position, max position, min velocity, max velocity) of problem b at the joint's parameter kj:
+// bez::select_extrema on the four values p2_tiles.h's limit_block takes; ARMTD mode: cacc::joint_extrema
 __device__ inline double limit_row_g(const P2Tables& tb, int b, int i, int blk, double kj) {
     const int n = tb.n;
     const double* bz = tb.bez + (size_t)b * 3 * n;
@@ -66,9 +66,8 @@ __device__ inline double limit_row_g(const P2Tables& tb, int b, int i, int blk, 
     const double v3 = vel ? bez::qd_des(q0, a, bb, ka, e3) : bez::q_des(q0, a, bb, ka, e3);
     const double v4 = vel ? bez::qd_des(q0, a, bb, ka, 1.0) : bez::q_des(q0, a, bb, ka, 1.0);
     double mn, mx;
-    if (v1 < v4) { mn = v1; mx = v4; } else { mn = v4; mx = v1; }
-    if (0 <= e2 && e2 <= 1) { if (v2 < mn) mn = v2; if (mx < v2) mx = v2; }
-    if (0 <= e3 && e3 <= 1) { if (v3 < mn) mn = v3; if (mx < v3) mx = v3; }
+    int mnId, mxId;
+    bez::select_extrema(v1, v2, v3, v4, e2, e3, &mn, &mx, &mnId, &mxId);
     const double v = (blk & 1) ? mx : mn;
     return vel ? v / tb.duration : v;
 }
@@ -76,8 +75,8 @@ __device__ inline double limit_row_g(const P2Tables& tb, int b, int i, int blk, 
 template <int C>
 __global__ __launch_bounds__(256) void armour_sweep_kernel(SweepArgs a) {
     __shared__ KPow kp[C];
-    __shared__ double s_l1[C][256], s_w[C][256];
-    __shared__ int s_row[C][256], s_nv[C][256], s_no[C][256];
+    __shared__ slv::ViolShared<C> sh;
+    __shared__ double s_sq[C][slv::NV];
     const P2Tables& tb = a.tb;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int s0 = blockIdx.x * C;
@@ -92,26 +91,12 @@ __global__ __launch_bounds__(256) void armour_sweep_kernel(SweepArgs a) {
     __syncthreads();
     const double* lo = a.lo + (size_t)b * m;
     const double* hi = a.hi + (size_t)b * m;
-    // the partial records of armour_sparse_violation_kernel, one per candidate
-    double l1[C], worst[C];
-    int wrow[C], nv[C], no[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) { l1[c] = 0.0; worst[c] = 0.0; wrow[c] = -1; nv[c] = 0; no[c] = 0; }
-    // row r with the values v[c] of the C candidates: the row test's `take`
+    slv::ViolPartial p[C];   // one partial record per candidate
+    // row r with the values v[c] of the C candidates
     auto take = [&](int r, const double* v) {
         const double l = lo[r], u = hi[r];
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-            const double viol = fmax(0.0, fmax(l - v[c], v[c] - u));
-            l1[c] += viol;
-            if (viol > 0.0) nv[c]++;
-            if (viol > worst[c]) { worst[c] = viol; wrow[c] = r; }
-            bool outside;
-            if (r < row0) outside = v[c] < l - a.torque_slack || v[c] > u + a.torque_slack;
-            else if (r < row0 + Q) outside = (r - row0) < a.n_checked && v[c] > a.collision_slack;
-            else outside = v[c] < l || v[c] > u;
-            if (outside) no[c]++;
-        }
+        for (int c = 0; c < C; c++) p[c].take(a.rule, r, v[c], l, u);
     };
     // ---- torque rows r = t * n + j: sparse_torque_row's sums (value only), the row's keys and coefficients read once
     for (int r = tid; r < row0; r += 256) {
@@ -248,39 +233,20 @@ __global__ __launch_bounds__(256) void armour_sweep_kernel(SweepArgs a) {
             take(r, v);
         }
     }
-    // ---- the row test's tree, for the C candidates side by side
-#pragma unroll
-    for (int c = 0; c < C; c++) { s_l1[c][tid] = l1[c]; s_w[c][tid] = worst[c]; s_row[c][tid] = wrow[c]; s_nv[c][tid] = nv[c]; s_no[c][tid] = no[c]; }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                s_l1[c][tid] += s_l1[c][tid + s]; s_nv[c][tid] += s_nv[c][tid + s]; s_no[c][tid] += s_no[c][tid + s];
-                const double ow = s_w[c][tid + s];
-                const int orow = s_row[c][tid + s];
-                if (ow > s_w[c][tid] || (ow == s_w[c][tid] && orow >= 0 && (s_row[c][tid] < 0 || orow < s_row[c][tid]))) { s_w[c][tid] = ow; s_row[c][tid] = orow; }
-            }
-        }
-        __syncthreads();
-    }
-    // ---- one thread per candidate: the record and the cost (armour_eval_f's loop: the continuous joints first)
+    slv::ViolPartial::tree_reduce(sh, p, tid);
+    // ---- one thread per candidate: the record and the cost (armour_eval_f's)
     if (tid < C && s0 + tid < a.S) {
         const int c = tid;
         ArmourSweepRecord o;
-        o.v.l1_violation = s_l1[c][0]; o.v.worst = s_w[c][0]; o.v.worst_row = s_row[c][0]; o.v.n_violated = s_nv[c][0]; o.v.n_outside_slack = s_no[c][0];
-        o.v.feasible = s_no[c][0] == 0 ? 1 : 0;
+        o.v = slv::ViolPartial::finish(sh, c);
         const double* cf = a.coef + (size_t)b * 4 * n;
-        double obj = 0;
-        for (int pass = 0; pass < 2; pass++)
-            for (int i = 0; i < n; i++) {
-                const bool cont = (a.continuous_mask >> i) & 1;
-                if (cont != (pass == 0)) continue;
-                const double qp = slv::plan_point(tb.mode, cf[i], cf[n + i], cf[2 * n + i], tb.k_range[i], kp[c].pw[i][1], a.t_plan);
-                const double e = cont ? slv::wrap_to_pi(cf[3 * n + i] - qp) : (cf[3 * n + i] - qp);
-                obj += e * e;
-            }
-        o.cost = obj * a.cost_scale;
+        double* sq = s_sq[c];   // (LDS: indexed by a run-time joint number)
+        for (int i = 0; i < n; i++) {
+            const double qp = slv::plan_point(tb.mode, cf[i], cf[n + i], cf[2 * n + i], tb.k_range[i], kp[c].pw[i][1], a.t_plan);
+            const double e = ((a.continuous_mask >> i) & 1) ? slv::wrap_to_pi(cf[3 * n + i] - qp) : (cf[3 * n + i] - qp);
+            sq[i] = e * e;
+        }
+        o.cost = slv::cost_from_sq(n, a.continuous_mask, sq, a.cost_scale);
         a.out[(size_t)b * a.S + s0 + c] = o;
     }
 }
@@ -315,8 +281,8 @@ __global__ __launch_bounds__(256) void armour_sweep_best_kernel(const ArmourSwee
 extern "C" int armour_sweep_tile(void) { return kTile; }
 
 extern "C" int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, int32_t per_problem, ArmourSweepRecord* records, int32_t* best, double* ms) {
-    if (!h || !k_cand) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
-    if (!h->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
+    if (!k_cand) { armour_set_error("null argument"); return ARMOUR_EINVAL; }
+    NEED_READY(h);
     if (S < 1 || S > ARMOUR_SWEEP_MAX_CANDIDATES) { armour_set_error("armour_sweep: S = %d is outside [1, %d]", S, ARMOUR_SWEEP_MAX_CANDIDATES); return ARMOUR_EINVAL; }
     if (per_problem != 0 && per_problem != 1) { armour_set_error("armour_sweep: per_problem is 0 or 1"); return ARMOUR_EINVAL; }
     const size_t B = (size_t)h->B, n = (size_t)h->n;
@@ -349,15 +315,14 @@ extern "C" int armour_sweep(ArmourPlanner* h, int32_t S, const double* k_cand, i
     HIPCHK(hipMemcpyAsync(blk + off_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     SweepArgs a;
     a.tb = armour_make_tables(h);
+    a.rule = armour_row_rule(h);
     a.sl = SparseList{h->rel.rows, h->rel.count, h->rel.packed, h->rel.pack_off};
     a.rows_res = h->rel.extra; a.count_res = h->rel.count + B;
     a.lo = h->d_bounds; a.hi = h->d_bounds + B * h->m;
     a.k = reinterpret_cast<const double*>(blk); a.k_pstride = per_problem ? (long long)S * (long long)n : 0;
-    a.S = S; a.strideT = strideT; a.n_checked = armour_checked_collision_rows(h);
-    a.torque_slack = h->params.torque_violation_threshold; a.collision_slack = h->params.collision_violation_threshold;
+    a.S = S; a.strideT = strideT;
     a.coef = reinterpret_cast<const double*>(blk + off_coef);
-    a.continuous_mask = 0;
-    for (int i = 0; i < h->n; i++) if (h->robot.continuous[i]) a.continuous_mask |= 1 << i;
+    a.continuous_mask = h->continuous_mask();
     a.t_plan = h->params.t_plan; a.cost_scale = h->params.cost_scale;
     a.out = reinterpret_cast<ArmourSweepRecord*>(blk + off_rec);
     int* d_best = reinterpret_cast<int*>(blk + off_best);
