@@ -149,6 +149,8 @@ EXPORTS = [
     "armour_track_options_default", "armour_track", "armour_track_auto_steps",
     "armour_path_audit", "armour_path_audit_host", "armour_path_audit_items",
     "armour_solve_from", "armour_sweep", "armour_sweep_tile",
+    "armour_self_pairs_default", "armour_self_check", "armour_self_check_host", "armour_self_edges_host", "armour_roadmap_check_self",
+    "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
 ]
 
 _lib = None
@@ -286,6 +288,16 @@ def load():
     L.armour_path_audit.argtypes = audit + [dp]
     L.armour_path_audit_host.argtypes = audit
     L.armour_path_audit_items.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, dp, dp, dp, dp, C.c_double, dp, dp, C.c_double, C.POINTER(C.c_int64)]
+    rp = C.POINTER(ArmourRobot)
+    L.armour_self_pairs_default.argtypes = [rp, u8p]
+    L.armour_self_check.argtypes = [rp, u8p, dp, C.c_int32, dp, u8p, dp, ip, dp]
+    L.armour_self_check_host.argtypes = [rp, u8p, dp, C.c_int32, dp, u8p, dp, ip]
+    L.armour_self_edges_host.argtypes = [rp, u8p, C.c_double, u8p, dp, C.c_int32, dp, dp, u8p]
+    L.armour_roadmap_check_self.argtypes = [vp, u8p, dp, u8p, u8p, dp, dp]
+    L.armour_roadmap_use_self.argtypes = [vp, C.c_int32]
+    audit_self = [rp, u8p, dp, C.c_int32, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp, C.c_double, ip, dp, dp]
+    L.armour_path_audit_self.argtypes = audit_self + [dp]
+    L.armour_path_audit_self_host.argtypes = audit_self
     _lib = L
     return L
 

@@ -11,39 +11,14 @@
 #include <vector>
 
 #include "common.h"
-#include "roadmap_geometry.h"
+#include "roadmap_handle.h"
+#include "self_geometry.h"
 
 using namespace rmgeo;
 
 namespace {
 
 constexpr int RM_BLOCK = 256;                 // four waves; a block serves one world (its obstacles are staged in LDS)
-
-// Sub-segment s of S of the edge a -> b: midpoint configuration and per-link enlargement.
-__host__ __device__ inline void edge_sample(const RmRobot& rb, const double* a, const double* b, int64_t s, int64_t S, double (&q)[ARMOUR_MAX_FACTORS],
-                                            double (&r)[ARMOUR_MAX_JOINTS]) {
-    double D[ARMOUR_MAX_FACTORS];
-    const double t = (double)(2 * s + 1) / (double)(2 * S);
-#pragma unroll
-    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
-        D[j] = j < rb.n ? (rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j]) : 0.0;
-        q[j] = j < rb.n ? a[j] + t * D[j] : 0.0;
-    }
-#pragma unroll
-    for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) {
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < ARMOUR_MAX_FACTORS && j <= l; j++) acc = j < rb.n ? acc + rb.rho[j][l] * fabs(D[j]) : acc;
-        r[l] = acc / (double)(2 * S);
-    }
-}
-
-__host__ __device__ inline int64_t edge_segments(const RmRobot& rb, const double* a, const double* b, double edge_step) {
-    double mx = 0.0;
-    for (int j = 0; j < rb.n; j++) mx = fmax(mx, fabs(rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j]));
-    const double S = ceil(mx / edge_step);
-    return S < 1.0 ? 1 : (int64_t)S;
-}
 
 // One launch: grid (ceil((N + M) / RM_BLOCK), W); item i < N is node i, item N + k is edge sub-segment k (edge sample_edge[k],
 // sub-segment k - edge_off[e]).  edge_free must hold 1 on entry; a colliding sub-segment stores 0 (no atomics: every writer writes 0).
@@ -97,26 +72,6 @@ double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
 }
 
 }  // namespace
-
-struct ArmourRoadmap {
-    int device = 0;
-    RmRobot rb;
-    int32_t N = 0, E = 0;
-    int64_t M = 0;
-    double edge_step = 0.0;
-    std::vector<double> nodes;           // [N][n]
-    std::vector<int32_t> edges;          // [E][2]
-    DevBuf<double> d_nodes, d_obs, d_clear;
-    DevBuf<int32_t> d_edges, d_sample_edge;
-    DevBuf<int64_t> d_edge_off;
-    DevBuf<uint8_t> d_node_free, d_edge_free;
-    DevStream stream;
-    EventPair ev;
-    // the last check, on the host
-    int32_t W = -1, O = 0;
-    std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them
-    std::vector<uint8_t> node_free, edge_free;
-};
 
 extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
                                      const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
@@ -227,7 +182,8 @@ static bool host_edge_free(const ArmourRoadmap* rm, const double* obs, const dou
         edge_sample(rm->rb, a, b, s, S, q, r);
         if (!config_free(rm->rb, q, r, obs, rm->O, false, nullptr)) return false;
     }
-    return true;
+    // with the self masks switched on (armour_roadmap_use_self) the same edge passes the self edge rule as well
+    return !rm->self_on || self_edge_free(rm->rb, rm->self_table, rm->edge_step, a, b);
 }
 
 extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
@@ -238,6 +194,7 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
     }
     *points = 0;
     if (rm->W < 0) { armour_set_error("armour_roadmap_plan: no armour_roadmap_check yet"); return ARMOUR_ESTATE; }
+    if (rm->self_on && !rm->self_checked) { armour_set_error("armour_roadmap_plan: self masks are on and no armour_roadmap_check_self yet"); return ARMOUR_ESTATE; }
     if (w < 0 || w >= rm->W) { armour_set_error("armour_roadmap_plan: world %d of %d", w, rm->W); return ARMOUR_EINVAL; }
     const int n = rm->rb.n, N = rm->N;
     for (int j = 0; j < n; j++)
@@ -245,6 +202,16 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
     const double* obs = rm->obs.data() + (size_t)w * rm->O * RM_OBS_STRIDE;
     const uint8_t* nf = rm->node_free.data() + (size_t)w * N;
     const uint8_t* ef = rm->edge_free.data() + (size_t)w * rm->E;
+    // free in both masks when the self masks are on
+    std::vector<uint8_t> both_n, both_e;
+    if (rm->self_on) {
+        both_n.assign(nf, nf + N);
+        both_e.assign(ef, ef + rm->E);
+        for (int i = 0; i < N; i++) both_n[i] = both_n[i] && rm->self_node_free[i];
+        for (int e = 0; e < rm->E; e++) both_e[e] = both_e[e] && rm->self_edge_free[e];
+        nf = both_n.data();
+        ef = both_e.data();
+    }
     auto node = [&](int i) -> const double* { return i == N ? q_start : i == N + 1 ? q_goal : &rm->nodes[(size_t)i * n]; };
     auto emit = [&](const std::vector<int>& seq) -> int {
         *points = (int32_t)seq.size();

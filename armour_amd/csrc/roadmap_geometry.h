@@ -120,6 +120,34 @@ __host__ __device__ inline bool pair_separated(const double* x, const double (*u
     return best > 0.0;
 }
 
+// One step along the chain: R, p = the frame of link l - 1 on entry, of link l on return; ql = the angle of joint l (read only when it is actuated).
+__host__ __device__ inline void link_frame(const RmRobot& rb, int l, double ql, double* R, double* p) {
+    double t[3], A[9];
+    for (int i = 0; i < 3; i++) t[i] = (R[3 * i] * rb.trans[l][0] + R[3 * i + 1] * rb.trans[l][1]) + R[3 * i + 2] * rb.trans[l][2];
+    for (int i = 0; i < 3; i++) p[i] = p[i] + t[i];
+    matmul3(R, rb.T0[l], A);
+    const int ax = rb.axis[l];
+    if (ax != 0 && l < rb.n) {
+        const double c = cos(ql), sn = ax > 0 ? sin(ql) : -sin(ql);
+        const int e = ax > 0 ? ax : -ax;
+        // Rot about x / y / z: {1,0,0; 0,c,-s; 0,s,c}, {c,0,s; 0,1,0; -s,0,c}, {c,-s,0; s,c,0; 0,0,1}
+        const double Q[9] = {e == 1 ? 1.0 : c,          e == 3 ? -sn : 0.0,       e == 2 ? sn : 0.0,
+                             e == 3 ? sn : 0.0,         e == 2 ? 1.0 : c,         e == 1 ? -sn : 0.0,
+                             e == 2 ? -sn : 0.0,        e == 1 ? sn : 0.0,        e == 3 ? 1.0 : c};
+        matmul3(A, Q, R);
+    } else {
+        for (int i = 0; i < 9; i++) R[i] = A[i];
+    }
+}
+
+// Link l's box in the frame R, p of link l: centre x and unit axes u[k] = column k of R (the half-sizes are the caller's)
+__host__ __device__ inline void link_box(const RmRobot& rb, int l, const double* R, const double* p, double* x, double (*u)[3]) {
+    for (int i = 0; i < 3; i++) x[i] = p[i] + ((R[3 * i] * rb.c[l][0] + R[3 * i + 1] * rb.c[l][1]) + R[3 * i + 2] * rb.c[l][2]);
+    for (int k = 0; k < 3; k++) {
+        u[k][0] = R[k]; u[k][1] = R[3 + k]; u[k][2] = R[6 + k];
+    }
+}
+
 // The rule for one configuration q with per-link enlargement r[l] (all zero for a node) against O staged obstacles (stride
 // RM_OBS_STRIDE); q and r are consumed (shifted).  full = false: returns at the first colliding pair.  full = true: *clearance = min over pairs of the pair clearance.
 __host__ __device__ inline bool config_free(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], const double* obs, int O, bool full,
@@ -128,22 +156,7 @@ __host__ __device__ inline bool config_free(const RmRobot& rb, double (&q)[ARMOU
     double cl = INFINITY;
     bool free_ = true;
     for (int l = 0; l < rb.J; l++) {
-        double t[3], A[9];
-        for (int i = 0; i < 3; i++) t[i] = (R[3 * i] * rb.trans[l][0] + R[3 * i + 1] * rb.trans[l][1]) + R[3 * i + 2] * rb.trans[l][2];
-        for (int i = 0; i < 3; i++) p[i] = p[i] + t[i];
-        matmul3(R, rb.T0[l], A);
-        const int ax = rb.axis[l];
-        if (ax != 0 && l < rb.n) {
-            const double ql = q[0], c = cos(ql), sn = ax > 0 ? sin(ql) : -sin(ql);
-            const int e = ax > 0 ? ax : -ax;
-            // Rot about x / y / z: {1,0,0; 0,c,-s; 0,s,c}, {c,0,s; 0,1,0; -s,0,c}, {c,-s,0; s,c,0; 0,0,1}
-            const double Q[9] = {e == 1 ? 1.0 : c,          e == 3 ? -sn : 0.0,       e == 2 ? sn : 0.0,
-                                 e == 3 ? sn : 0.0,         e == 2 ? 1.0 : c,         e == 1 ? -sn : 0.0,
-                                 e == 2 ? -sn : 0.0,        e == 1 ? sn : 0.0,        e == 3 ? 1.0 : c};
-            matmul3(A, Q, R);
-        } else {
-            for (int i = 0; i < 9; i++) R[i] = A[i];
-        }
+        link_frame(rb, l, q[0], R, p);
         double x[3], u[3][3], s[3];
         const double rl = r[0];
         // shift q and r down one joint: link l always reads entry 0, so neither array is indexed at run time (no scratch memory)
@@ -151,11 +164,8 @@ __host__ __device__ inline bool config_free(const RmRobot& rb, double (&q)[ARMOU
         for (int j = 0; j + 1 < ARMOUR_MAX_FACTORS; j++) q[j] = q[j + 1];
 #pragma unroll
         for (int j = 0; j + 1 < ARMOUR_MAX_JOINTS; j++) r[j] = r[j + 1];
-        for (int i = 0; i < 3; i++) x[i] = p[i] + ((R[3 * i] * rb.c[l][0] + R[3 * i + 1] * rb.c[l][1]) + R[3 * i + 2] * rb.c[l][2]);
-        for (int k = 0; k < 3; k++) {
-            u[k][0] = R[k]; u[k][1] = R[3 + k]; u[k][2] = R[6 + k];
-            s[k] = rb.h[l][k] + rl;
-        }
+        link_box(rb, l, R, p, x, u);
+        for (int k = 0; k < 3; k++) s[k] = rb.h[l][k] + rl;
         for (int o = 0; o < O; o++) {
             double v;
             const bool sep = pair_separated(x, u, s, obs + (size_t)o * RM_OBS_STRIDE, full, &v);

@@ -1,0 +1,57 @@
+// The roadmap handle and the edge rule's sub-segments (include/armour_hip.h, armour_roadmap_*), shared by roadmap.hip (the world check and
+// the search) and self_check.hip (the self-collision masks of the same roadmap).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "common.h"
+#include "roadmap_geometry.h"
+#include "self_geometry.h"
+
+namespace rmgeo {
+
+// Sub-segment s of S of the edge a -> b: midpoint configuration and per-link enlargement.
+__host__ __device__ inline void edge_sample(const RmRobot& rb, const double* a, const double* b, int64_t s, int64_t S, double (&q)[ARMOUR_MAX_FACTORS],
+                                            double (&r)[ARMOUR_MAX_JOINTS]) {
+    double D[ARMOUR_MAX_FACTORS];
+    const double t = (double)(2 * s + 1) / (double)(2 * S);
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
+        D[j] = j < rb.n ? (rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j]) : 0.0;
+        q[j] = j < rb.n ? a[j] + t * D[j] : 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < ARMOUR_MAX_FACTORS && j <= l; j++) acc = j < rb.n ? acc + rb.rho[j][l] * fabs(D[j]) : acc;
+        r[l] = acc / (double)(2 * S);
+    }
+}
+
+}  // namespace rmgeo
+
+struct ArmourRoadmap {
+    int device = 0;
+    rmgeo::RmRobot rb;
+    int32_t N = 0, E = 0;
+    int64_t M = 0;
+    double edge_step = 0.0;
+    std::vector<double> nodes;           // [N][n]
+    std::vector<int32_t> edges;          // [E][2]
+    DevBuf<double> d_nodes, d_obs, d_clear;
+    DevBuf<int32_t> d_edges, d_sample_edge;
+    DevBuf<int64_t> d_edge_off;
+    DevBuf<uint8_t> d_node_free, d_edge_free;
+    DevStream stream;
+    EventPair ev;
+    // the last check, on the host
+    int32_t W = -1, O = 0;
+    std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them
+    std::vector<uint8_t> node_free, edge_free;
+    // the self-collision masks (armour_roadmap_check_self, self_check.hip): world-independent, kept until the next self check
+    bool self_on = false, self_checked = false;
+    rmgeo::SelfTable self_table;
+    std::vector<uint8_t> self_node_free, self_edge_free;   // [N], [E]
+};
+

@@ -68,6 +68,27 @@ def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration,
     return AuditResult(verdict=verdict, t_hit=t_hit, clearance=cl, ms=ms.value)
 
 
+def audit_self(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, pairs=None, shrink=None, clearance=False, host=False):
+    """The same pieces against the arm itself (armour_path_audit_self): verdict 0 proved self-free, 1 proved self-hit (t_hit), 2 undecided.
+    pairs / shrink [J,J] as armour_amd.self_check.check takes them (None: every pair b - a >= 2, no shrink)."""
+    from .self_check import table_args
+    L = _lib.load()
+    P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)
+    tube = None if tube is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tube, dtype=np.float64), (P, n)))
+    pairs, shrink, pp, sp = table_args(robot, pairs, shrink)
+    verdict = np.zeros(P, dtype=np.int32)
+    t_hit = np.zeros(P)
+    cl = np.zeros(P) if clearance else None
+    args = [C.byref(robot), pp, sp, P, _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range), float(duration), _dp(ta), _dp(tb), _dp(tube), float(step),
+            verdict.ctypes.data_as(C.POINTER(C.c_int32)), _dp(t_hit), _dp(cl)]
+    ms = C.c_double(0.0)
+    if host:
+        check(L.armour_path_audit_self_host(*args))
+    else:
+        check(L.armour_path_audit_self(*args, C.byref(ms)))
+    return AuditResult(verdict=verdict, t_hit=t_hit, clearance=cl, ms=ms.value)
+
+
 def audit_items(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, step=0.02):
     """[P] int64: the sub-intervals (work items) an audit of every piece takes at `step`."""
     P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)

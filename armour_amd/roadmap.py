@@ -113,6 +113,28 @@ class Roadmap:
             out["node_clearance"] = cl
         return out
 
+    def check_self(self, pairs=None, shrink=None, clearance=False):
+        """The roadmap's self-collision masks (world-independent; once per roadmap): dict node_free [N] bool, edge_free [E] bool, ms, and
+        node_clearance [N] when `clearance`.  pairs / shrink [J,J] as armour_amd.self_check.check takes them.  The handle keeps the masks."""
+        from .self_check import table_args
+        pairs, shrink, pp, sp = table_args(self.robot, pairs, shrink)
+        nf = np.zeros(self.N, dtype=np.uint8)
+        ef = np.zeros(self.E, dtype=np.uint8)
+        cl = np.zeros(self.N) if clearance else None
+        ms = C.c_double()
+        u8 = C.POINTER(C.c_uint8)
+        check(self.L.armour_roadmap_check_self(self.h, pp, sp, nf.ctypes.data_as(u8), ef.ctypes.data_as(u8), _dp(cl) if clearance else None, C.byref(ms)))
+        out = dict(node_free=nf.astype(bool), edge_free=ef.astype(bool), ms=ms.value)
+        if clearance:
+            out["node_clearance"] = cl
+        return out
+
+    def use_self(self, on=True):
+        """on: plan() takes a node or edge as free only if it is free in the world's mask and the self mask, and checks the edges that join
+        start and goal with the self edge rule too (an error before check_self).  Default off: plan() is unchanged."""
+        check(self.L.armour_roadmap_use_self(self.h, 1 if on else 0))
+        return self
+
     def plan(self, w, start, goal, connect_k=8, max_points=None):
         """Path [P,n] from start to goal through world w's free graph of the last check (start and goal included), None if none."""
         s = np.ascontiguousarray(start, dtype=np.float64).reshape(self.n)

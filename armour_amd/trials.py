@@ -26,10 +26,11 @@ import time
 import numpy as np
 
 from . import _lib, scenes
-from .path_audit import FREE, HIT, UNDECIDED, audit
+from .path_audit import FREE, HIT, UNDECIDED, audit, audit_self
 from .planner import ArmourNLP, default_params, desired_trajectory, kinova_robot
 
 OUTCOMES = ("goal", "collision", "stuck", "iteration_limit")
+SELF_OUTCOME = "self_collision"   # only with run_trials(self_check="stop")
 
 
 def bezier_q(q0, qd0, qdd0, k, k_range, duration, t):
@@ -107,7 +108,7 @@ def _world_record(world):
 
 def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, stop_threshold=4, max_iterations=300, audit_step=0.01, tube=None,
                tracked=False, track_samples=1, track_dt=1e-3, track_seed=0, goal_nodes=10, T=128, per_step_build=False, solve_options=None,
-               backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0):
+               backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0, self_check=None, self_pairs=None, self_shrink=None):
     """Run every world of `worlds` ([(name, problem)] as scenes.reference_worlds() gives them; a problem holds q0 = the start at rest, goal,
     obstacles [O, 12] and lookahead) to its end.  hlp: "straight" or a factory (world index, world record) -> object with
     get_waypoint(q_cur, lookahead) (e.g. a RoadmapHLP; None = no waypoint: the goal is used).  tube: None or "ultimate_bound" (every joint's
@@ -116,7 +117,13 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
     backend: an object with plan(), robot, k_range, duration, t_plan (default: DevicePlanner).  rescue_candidates > 0 (default 0: today's path):
     the default backend answers an infeasible solve with a candidate sweep and a second solve from the safe candidates (ArmourNLP.solve_rescued);
     every record carries `rescued` (0 not needed, 1 a candidate became the plan, 2 the solve from it did, -1 no safe candidate) and the summary
-    counts `rescued_iterations`.  Returns dict(worlds, summary, ...)."""
+    counts `rescued_iterations`.  self_check: None (default: no extra call, records unchanged), "record" (one armour_path_audit_self call per
+    iteration for the executed pieces, with the world audit's tube and step and the table self_pairs / self_shrink; every record carries
+    `self_verdict`, `self_t_hit` and `self_clearance`, the summary counts `self_hit_pieces` and `self_undecided_pieces`) or "stop" (as "record",
+    and verdict 1 ends the world with the outcome `self_collision`, after a world collision and before the goal check).
+    Returns dict(worlds, summary, ...)."""
+    if self_check not in (None, "record", "stop"):
+        raise ValueError(f"unknown self_check {self_check!r}")
     ws = [_world_record(w) for w in worlds]
     W = len(ws)
     own_backend = backend is None
@@ -188,6 +195,10 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
         au = audit(robot, obstacles[live], np.arange(len(live), dtype=np.int32), *cols, k_range, D, ta, tb, tube=tube_e, step=audit_step,
                    clearance=clearance, host=audit_on_host)
         batches[-1]["audit_ms"] = au.ms
+        if self_check is not None:
+            sa = audit_self(robot, *cols, k_range, D, ta, tb, tube=tube_e, step=audit_step, pairs=self_pairs, shrink=self_shrink, clearance=clearance,
+                            host=audit_on_host)
+            batches[-1]["self_audit_ms"] = sa.ms
         if tracked:
             z0 = None if st[live[0]]["z"] is None else np.concatenate([st[i]["z"] for i in live])
             # the windows differ with the kind of piece: one armour_track call per window present
@@ -211,10 +222,14 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
                 s["z"] = tr_rows[b].pop("z")
                 rec["tracking"] = tr_rows[b]
             s["undecided"] += int(au.verdict[b] == UNDECIDED)
+            if self_check is not None:
+                rec.update(self_verdict=int(sa.verdict[b]), self_t_hit=float(sa.t_hit[b]), self_clearance=None if sa.clearance is None else float(sa.clearance[b]))
             nodes = bezier_q(p[0], p[1], p[2], p[3], k_range, D, np.linspace(p[4], p[5], goal_nodes + 1))
             rec["goal_reached"] = goal_reached(nodes, ws[i]["goal"], goal_radius)
             if au.verdict[b] == HIT:
                 s["outcome"] = "collision"
+            elif self_check == "stop" and sa.verdict[b] == HIT:
+                s["outcome"] = SELF_OUTCOME
             elif rec["goal_reached"]:
                 s["outcome"] = "goal"
             elif s["fails"] > stop_threshold:
@@ -234,6 +249,11 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
                    batch_planning_ms_mean=float(plan_ms.mean()) if plan_ms.size else 0.0, batch_planning_ms_max=float(plan_ms.max()) if plan_ms.size else 0.0,
                    planning_ms_per_world_iteration=float(plan_ms.sum() / max(1, sum(b["live"] for b in batches))),
                    audit_ms_total=float(sum(b.get("audit_ms", 0.0) for b in batches)))
+    if self_check is not None:
+        sv = [r["self_verdict"] for s in st for r in s["records"]]
+        summary.update(self_hit_pieces=sum(1 for v in sv if v == HIT), self_undecided_pieces=sum(1 for v in sv if v == UNDECIDED))
+        if self_check == "stop":
+            summary[SELF_OUTCOME] = sum(1 for s in st if s["outcome"] == SELF_OUTCOME)
     if tracked:
         ub, qe, qde = ultimate_bound(robot)
         trk = [r["tracking"] for s in st for r in s["records"]]

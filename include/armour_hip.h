@@ -655,6 +655,74 @@ int armour_path_audit_host(const ArmourRobot* robot, int32_t W, int32_t O, const
 int armour_path_audit_items(const ArmourRobot* robot, int32_t P, const double* q0, const double* qd0, const double* qdd0, const double* k,
                             const double* k_range, double duration, const double* ta, const double* tb, double step, int64_t* items);
 
+/* ---- self-collision checks: the arm's link boxes against each other (self_check.hip) ---- */
+/* The other half of the reference's collision flag (KSI/simulator_armtd.m ORs a self-intersection check into every collision check): is a
+ * configuration, a roadmap edge or an executed plan piece free of collisions of the arm with itself?
+ *
+ * Boxes.  Link l at q is the node rule's box (above): the same frames, c_l and h_l.
+ * Pair table.  pairs [J][J] uint8 (J = num_joints), only a < b is read; NULL is the default, every pair with b - a >= 2 (adjacent links'
+ * bounding boxes always overlap).  A link whose half-sizes are all zero is never tested.  shrink [J][J] doubles, finite and >= 0, only
+ * a < b is read; NULL is zeros.
+ * Pair rule (exact for the boxes it is given).  Pair (a, b) is tested with box a as it is and box b with the half-sizes
+ *   s_b = max(h_b - shrink_ab, 0) + r_ab          (r_ab = 0 for a configuration; the motion bound below otherwise),
+ * d = x_b - x_a the centres' difference, u_ai / u_bk the boxes' unit axes.  The 15 axes m are the 3 axes of a, the 3 of b and the 9 cross
+ * products u_ai x u_bk; a cross product with |m|^2 <= 1e-18 (the axes are unit: the sine of their angle <= 1e-9) is skipped, as in the
+ * node rule.  value(m) = (|m.d| - sum_i s_ai |m.u_ai| - sum_k s_bk |m.u_bk|) / |m|, where a box's own axis contributes its own half-size
+ * alone (its axes are orthonormal) and a cross product's two parents contribute nothing.
+ *   pair clearance = max over the used axes of value;  configuration clearance = min over the listed pairs (+inf with none);
+ *   SELF-FREE iff clearance > 0.  worst_pair = a J + b of the first pair (a, then b ascending) that attains the minimum.
+ * Verdict mode (no clearance asked for) reads only the signs of the numerators, leaves a pair at its first separating axis and the
+ * configuration at its first colliding pair; worst_pair is then that pair, or -1 when the configuration is free.
+ *
+ * Motion bound (relative).  The pose of link b in the frame of link a depends only on joints a+1 .. b: joints <= a move the pair rigidly,
+ * and the test above is invariant under a rigid motion of both boxes.  Where every joint j stays within delta_j of a midpoint value,
+ *   r_ab = sum over actuated j in a+1..b of rho_{j,b} delta_j,       rho_{j,l} the edge rule's (above).
+ * Soundness: the edge rule's argument carried out in frame a.  Hold joints <= a at any value; turn joints a+1..b from their midpoint
+ * values one at a time.  Turning joint j by theta turns every point of link b about an axis through p_j, which moves it by at most
+ * rho_{j,b} theta -- in frame a as in the world, the two differ by a rigid motion.  So, seen from box a, every point of link b stays
+ * within r_ab of its midpoint position, i.e. inside the midpoint box with half-sizes + r_ab, while box a does not move at all.  If the
+ * enlarged box b is separated from box a at the midpoint, the two boxes are separated for every such configuration.  Only box b grows.
+ *   Edge sub-segment s of S (the roadmap's S and midpoint):  delta_j = |D_j| / (2S).
+ *   Audit sub-interval s of S (the path audit's S, midpoint and v_j):  delta_j = v_j (tb - ta) / (2S) + e_j.
+ * A numerator is monotone in the half-sizes in floating point too, so an item whose enlarged test separates has a separated exact test.
+ * Calibration.  sum_k |m.u_k| >= |m| for the axes of a box, so shrinking box b by d raises every axis value by at least d (until a
+ * half-size reaches 0).  A pair that penetrates by p (clearance -p) at a configuration known to be harmless -- the boxes are coarser
+ * than the arm -- is cleared there by shrink_ab = p + margin.
+ *
+ * Device.  One lane per (item, first link a); the lane runs the chain once, keeps box a and tests every listed b as the chain reaches
+ * it.  Verdict bytes start at 1 and a colliding lane stores 0; clearances and worst pairs are merged on the host.  fp64 throughout.
+ * Every entry has a _host twin that runs the same functions in a loop and needs no device. */
+/* pairs [J][J] = the default table (1 where b - a >= 2) */
+int armour_self_pairs_default(const ArmourRobot* robot, uint8_t* pairs);
+/* q [N][n].  Outputs, each may be NULL: free [N] (0/1), clearance [N] (asking for it switches the early exits off), worst_pair [N],
+ * ms = device time of the launch.  ARMOUR_EINVAL on a bad argument, before the device is touched. */
+int armour_self_check(const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, int32_t N, const double* q, uint8_t* free_,
+                      double* clearance, int32_t* worst_pair, double* ms);
+int armour_self_check_host(const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, int32_t N, const double* q, uint8_t* free_,
+                           double* clearance, int32_t* worst_pair);
+/* The self masks of a roadmap, world-independent: one launch over (node | edge sub-segment, first link), once per roadmap.  An edge is
+ * SELF-FREE iff every listed pair's enlarged test separates on every sub-segment, so no configuration on it self-collides and its
+ * endpoints are self-free.  node_free [N], edge_free [E], node_clearance [N], ms: each may be NULL.  The handle keeps the masks and the
+ * table for armour_roadmap_plan. */
+int armour_roadmap_check_self(ArmourRoadmap* rm, const uint8_t* pairs, const double* shrink, uint8_t* node_free, uint8_t* edge_free,
+                              double* node_clearance, double* ms);
+/* on != 0: armour_roadmap_plan takes a node or edge as free only if it is free in the world's mask AND the self mask, and the edges it
+ * checks on the host (direct, start and goal connections) also pass the self edge rule; ARMOUR_ESTATE from the plan before a self check.
+ * Default off: armour_roadmap_plan is unchanged. */
+int armour_roadmap_use_self(ArmourRoadmap* rm, int32_t on);
+/* the self edge rule in a host loop, for edges qa[e] -> qb[e] ([E][n]) that need no roadmap: continuous [n] (NULL: robot->continuous) */
+int armour_self_edges_host(const ArmourRobot* robot, const uint8_t* continuous, double edge_step, const uint8_t* pairs, const double* shrink, int32_t E,
+                           const double* qa, const double* qb, uint8_t* edge_free);
+/* armour_path_audit without a world: pieces, windows, tube, step, sub-intervals and outputs as there.  Verdict per piece: 0 PROVED
+ * SELF-FREE (every enlarged test separates), 1 PROVED SELF-HIT (an exact test at a midpoint collides; t_hit = the first such t_s),
+ * 2 UNDECIDED (neither; not a finding).  clearance [P] = the minimum exact configuration clearance over the midpoints (+inf with no pair). */
+int armour_path_audit_self(const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, int32_t P, const double* q0, const double* qd0,
+                           const double* qdd0, const double* k, const double* k_range, double duration, const double* ta, const double* tb,
+                           const double* tube, double step, int32_t* verdict, double* t_hit, double* clearance, double* ms);
+int armour_path_audit_self_host(const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, int32_t P, const double* q0, const double* qd0,
+                                const double* qdd0, const double* k, const double* k_range, double duration, const double* ta, const double* tb,
+                                const double* tube, double step, int32_t* verdict, double* t_hit, double* clearance);
+
 #ifdef __cplusplus
 }
 #endif
