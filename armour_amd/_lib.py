@@ -308,6 +308,11 @@ class ArmourError(RuntimeError):
         self.code = code
 
 
+def _dp(a):
+    """A float64 array as the double* the C ABI takes (None: a null pointer)."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
 def check(rc):
     if rc < 0:
         raise ArmourError(rc, load().armour_last_error().decode())

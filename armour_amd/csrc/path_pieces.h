@@ -1,6 +1,9 @@
 // The pieces of the path audit (include/armour_hip.h, armour_path_audit*): the plans as the rule reads them, the speed bound, the
-// sub-intervals of a piece and the configuration at a sub-interval's midpoint.  Shared by path_audit.hip and self_check.hip.
+// sub-intervals of a piece, the configuration at a sub-interval's midpoint and what an audit's work item does around its free-test (decode,
+// the three-state decision, the record).  Shared by path_audit.hip and self_check.hip; the host side of an audit is in audit_host.h.
 #pragma once
+#include <cstdint>
+
 #include "bezier.h"
 #include "common.h"
 #include "roadmap_geometry.h"
@@ -13,6 +16,8 @@ struct PaPieces {
     double k_range[ARMOUR_MAX_FACTORS];
     double duration, step;
 };
+
+constexpr int32_t PA_NO_HIT = INT32_MAX;      // first_hit[p] before any sample test collided
 
 // v_j = max_i |5 (P_{i+1,j} - P_{i,j})| / duration over the control points P0 = q0, P1 = q0 + a/5, P2 = q0 + 2a/5 + b/20, P3 = P4 = P5 = q0 + k_range k
 // (a = qd0 duration, b = qdd0 duration^2, as armour_desired_trajectory forms them): a bound of |qd_j| on the whole curve.
@@ -69,6 +74,43 @@ __host__ __device__ inline double piece_sample(const RmRobot& rb, const PaPieces
         r[l] = acc;
     }
     return t;
+}
+
+// Work item `item` of an audit kernel: sub-interval *s of the *S of piece *p = item_piece[item].  False when the item is settled already:
+// in verdict mode (full = false) an item behind a recorded hit of its piece can change neither the minimum nor the verdict.
+__device__ inline bool audit_item(int64_t item, const int32_t* __restrict__ item_piece, const int64_t* __restrict__ piece_off, const int32_t* first_hit,
+                                  bool full, int* p, int64_t* s, int64_t* S) {
+    *p = item_piece[item];
+    *s = item - piece_off[*p];
+    *S = piece_off[*p + 1] - piece_off[*p];
+    return full || !((int64_t)__atomic_load_n(&first_hit[*p], __ATOMIC_RELAXED) < *s);
+}
+
+// The state of an item from its two free-tests: 0 the tube test separates, 1 the sample test collides, 2 neither.  sample_free(full) is the
+// test with the boxes as they are (full: without an early exit, leaving its clearance), tube_free() the test with the enlarged boxes.
+// full: sample first, then tube; otherwise tube first and the sample test only for an item the tube test does not settle.
+template <class Tube, class Sample>
+__host__ __device__ inline int audit_state(bool full, const Tube& tube_free, const Sample& sample_free) {
+    if (full) {
+        if (!sample_free(true)) return 1;
+        return tube_free() ? 0 : 2;
+    }
+    if (tube_free()) return 0;   // enlarged boxes separated: the boxes themselves are
+    return sample_free(false) ? 2 : 1;
+}
+
+// The record of an item's state in its piece's merge words (first_hit holds PA_NO_HIT and undecided 0 before the first item): a colliding
+// item lowers first_hit to its sub-interval (an integer minimum, atomic on the device), an undecided one stores 1 (every writer writes 1).
+__host__ __device__ inline void audit_record(int state, int64_t s, int32_t* first_hit, uint8_t* undecided) {
+    if (state == 1) {
+#ifdef __HIP_DEVICE_COMPILE__
+        atomicMin(first_hit, (int32_t)s);
+#else
+        if ((int32_t)s < *first_hit) *first_hit = (int32_t)s;
+#endif
+    } else if (state == 2) {
+        *undecided = 1;
+    }
 }
 
 }  // namespace rmgeo

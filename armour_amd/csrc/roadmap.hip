@@ -29,11 +29,7 @@ __global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int
                                                                   uint8_t* __restrict__ edge_free, double* __restrict__ clearance) {
     extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
     const int w = blockIdx.y;
-    const double* Zw = obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES;
-    for (int i = threadIdx.x; i < O * ARMOUR_OBS_DOUBLES; i += RM_BLOCK)
-        s_obs[(i / ARMOUR_OBS_DOUBLES) * RM_OBS_STRIDE + i % ARMOUR_OBS_DOUBLES] = Zw[i];
-    for (int o = threadIdx.x; o < O; o += RM_BLOCK) obstacle_normals(Zw + (size_t)o * ARMOUR_OBS_DOUBLES, s_obs + (size_t)o * RM_OBS_STRIDE + 12);
-    __syncthreads();
+    stage_obstacles_lds<RM_BLOCK>(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
     const int64_t item = (int64_t)blockIdx.x * RM_BLOCK + threadIdx.x;
     if (item >= (int64_t)N + M) return;
     double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];

@@ -66,6 +66,15 @@ inline void stage_obstacles(const double* obstacles, size_t count, double* stage
     }
 }
 
+// stage_obstacles on the device: a block of BLOCK lanes stages its world's O obstacles Zw into LDS, s_obs [O][RM_OBS_STRIDE], and meets at the barrier
+template <int BLOCK>
+__device__ inline void stage_obstacles_lds(const double* __restrict__ Zw, int O, double* s_obs) {
+    for (int i = threadIdx.x; i < O * ARMOUR_OBS_DOUBLES; i += BLOCK)
+        s_obs[(i / ARMOUR_OBS_DOUBLES) * RM_OBS_STRIDE + i % ARMOUR_OBS_DOUBLES] = Zw[i];
+    for (int o = threadIdx.x; o < O; o += BLOCK) obstacle_normals(Zw + (size_t)o * ARMOUR_OBS_DOUBLES, s_obs + (size_t)o * RM_OBS_STRIDE + 12);
+    __syncthreads();
+}
+
 // One link box (centre x, unit axes u[k] = column k of R, half-sizes s) against one staged obstacle.  full = false: true as soon as
 // one plane separates (value > 0; the sign of the numerator is the sign of the value).  full = true: *value = the pair's clearance.
 __host__ __device__ inline bool pair_separated(const double* x, const double (*u)[3], const double* s, const double* ob, bool full,

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "audit_host.h"
 #include "common.h"
 #include "path_pieces.h"
 #include "roadmap_handle.h"
@@ -22,7 +23,6 @@ using namespace rmgeo;
 namespace {
 
 constexpr int SC_BLOCK = 256;                 // four waves
-constexpr int32_t SC_NO_HIT = INT32_MAX;      // first_hit[p] before any sample test collided
 
 // grid (ceil((N + M) / SC_BLOCK), rows): item i < N is configuration i, item N + k is edge sub-segment k (edge sample_edge[k], sub-segment
 // k - edge_off[e]), both against the pairs of first link a = blockIdx.y.  node_free / edge_free must hold 1 on entry; a colliding row
@@ -65,8 +65,8 @@ __global__ __launch_bounds__(SC_BLOCK) void self_check_kernel(RmRobot rb, int32_
     }
 }
 
-// One (piece, sub-interval) against the pairs of first link a: 0 the tube test separates, 1 the sample test collides, 2 neither.
-// full: *clearance = the sample test's clearance of the row, computed without an early exit.
+// One (piece, sub-interval) against the pairs of first link a: its audit_state.  full: *clearance = the sample test's clearance of the row,
+// computed without an early exit.
 __host__ __device__ inline int self_item_state(const RmRobot& rb, const PaPieces& pc, int a, int64_t p, int64_t s, int64_t S, const uint8_t* on,
                                                const double* shrink, bool full, double* clearance) {
     double q[ARMOUR_MAX_FACTORS], q1[ARMOUR_MAX_FACTORS], dev[ARMOUR_MAX_FACTORS], still[ARMOUR_MAX_FACTORS];
@@ -76,19 +76,14 @@ __host__ __device__ inline int self_item_state(const RmRobot& rb, const PaPieces
         q1[j] = q[j];
         still[j] = 0.0;
     }
-    double v;
     int b;
-    if (full) {
-        if (!self_row_free(rb, a, q1, still, on, shrink, true, clearance, &b)) return 1;
-        return self_row_free(rb, a, q, dev, on, shrink, false, &v, &b) ? 0 : 2;
-    }
-    if (self_row_free(rb, a, q, dev, on, shrink, false, &v, &b)) return 0;   // box b enlarged and separated: the boxes themselves are
-    return self_row_free(rb, a, q1, still, on, shrink, false, &v, &b) ? 2 : 1;
+    return audit_state(
+        full, [&] { return self_row_free(rb, a, q, dev, on, shrink, false, clearance, &b); },   // box b enlarged
+        [&](bool no_exit) { return self_row_free(rb, a, q1, still, on, shrink, no_exit, clearance, &b); });
 }
 
-// grid (ceil(items / SC_BLOCK), rows): item i is sub-interval i - piece_off[p] of piece p = item_piece[i], against first link a = blockIdx.y.
-// first_hit must hold SC_NO_HIT and undecided 0 on entry: a colliding item lowers first_hit[p] to its sub-interval (an integer minimum), an
-// undecided one stores 1.  Without item_clear an item behind a recorded hit of its piece returns at once.  item_clear [items][rows].
+// grid (ceil(items / SC_BLOCK), rows): item i is sub-interval i - piece_off[p] of piece p = item_piece[i], against first link a = blockIdx.y;
+// first_hit / undecided as audit_record expects them.  With item_clear [items][rows] no item is skipped and every item writes its row's clearance.
 __global__ __launch_bounds__(SC_BLOCK) void self_audit_kernel(RmRobot rb, PaPieces pc, int32_t rows, int64_t items, const int32_t* __restrict__ item_piece,
                                                                const int64_t* __restrict__ piece_off, const uint8_t* __restrict__ on,
                                                                const double* __restrict__ shrink, int32_t* __restrict__ first_hit,
@@ -96,33 +91,17 @@ __global__ __launch_bounds__(SC_BLOCK) void self_audit_kernel(RmRobot rb, PaPiec
     const int a = blockIdx.y;
     const int64_t item = (int64_t)blockIdx.x * SC_BLOCK + threadIdx.x;
     if (item >= items) return;
-    const int p = item_piece[item];
-    const int64_t s = item - piece_off[p], S = piece_off[p + 1] - piece_off[p];
-    if (!item_clear && (int64_t)__atomic_load_n(&first_hit[p], __ATOMIC_RELAXED) < s) return;
-    double cl;
     const bool full = item_clear != nullptr;
+    int p;
+    int64_t s, S;
+    if (!audit_item(item, item_piece, piece_off, first_hit, full, &p, &s, &S)) return;
+    double cl;
     const int state = self_item_state(rb, pc, a, p, s, S, on + a * rb.J, shrink + a * rb.J, full, &cl);
     if (full) item_clear[(size_t)item * rows + a] = cl;
-    if (state == 1) atomicMin(&first_hit[p], (int32_t)s);
-    else if (state == 2) undecided[p] = 1;
+    audit_record(state, s, &first_hit[p], &undecided[p]);
 }
 
 // ---- what the entries share: argument checks and the pair table
-int make_table(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const uint8_t* pairs, const double* shrink, RmRobot* rb, SelfTable* tb) {
-    if (!robot) { armour_set_error("%s: null robot", who); return ARMOUR_EINVAL; }
-    ARMOUR_TRY(armour_check_robot_shape(who, robot));
-    const int J = robot->num_joints;
-    for (int a = 0; shrink && a < J; a++)
-        for (int b = a + 1; b < J; b++)
-            if (!std::isfinite(shrink[a * J + b]) || shrink[a * J + b] < 0.0) {
-                armour_set_error("%s: shrink of pair (%d, %d) is %g (must be finite and >= 0)", who, a, b, shrink[a * J + b]);
-                return ARMOUR_EINVAL;
-            }
-    fill_rm_robot(robot, continuous, rb);
-    fill_self_table(*rb, pairs, shrink, tb);
-    return ARMOUR_OK;
-}
-
 int table_for_handle(const char* who, const RmRobot& rb, const uint8_t* pairs, const double* shrink, SelfTable* tb) {
     for (int a = 0; shrink && a < rb.J; a++)
         for (int b = a + 1; b < rb.J; b++)
@@ -132,6 +111,13 @@ int table_for_handle(const char* who, const RmRobot& rb, const uint8_t* pairs, c
             }
     fill_self_table(rb, pairs, shrink, tb);
     return ARMOUR_OK;
+}
+
+int make_table(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const uint8_t* pairs, const double* shrink, RmRobot* rb, SelfTable* tb) {
+    if (!robot) { armour_set_error("%s: null robot", who); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(armour_check_robot_shape(who, robot));
+    fill_rm_robot(robot, continuous, rb);
+    return table_for_handle(who, *rb, pairs, shrink, tb);
 }
 
 // a configuration's results from its rows' (device order = host order: rows ascending, the first minimum / the first colliding pair wins)
@@ -166,72 +152,13 @@ struct SelfAudit {
     SelfTable tb;
     PaPieces pc;                          // host pointers
     std::vector<int64_t> piece_off;       // [P + 1]
-    int64_t items = 0;
 };
 
-int make_audit(const char* who, const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, int32_t P, const double* q0, const double* qd0,
-               const double* qdd0, const double* k, const double* k_range, double duration, const double* ta, const double* tb, const double* tube, double step,
-               const int32_t* verdict, SelfAudit* au) {
-    if (!robot || !k_range || P < 0 || (P > 0 && (!q0 || !qd0 || !qdd0 || !k || !ta || !tb || !verdict))) {
-        armour_set_error("%s: null argument", who);
-        return ARMOUR_EINVAL;
-    }
+int make_audit(const char* who, const ArmourRobot* robot, const uint8_t* pairs, const double* shrink, const PieceArgs& a, const int32_t* verdict, SelfAudit* au) {
+    if (!robot) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
     ARMOUR_TRY(make_table(who, robot, nullptr, pairs, shrink, &au->rb, &au->tb));
-    if (!(step > 0.0) || !std::isfinite(step) || !(duration > 0.0) || !std::isfinite(duration)) {
-        armour_set_error("%s: step = %g, duration = %g (both must be positive)", who, step, duration);
-        return ARMOUR_EINVAL;
-    }
-    const int n = robot->num_factors;
-    const size_t pn = (size_t)P * n;
-    if (!finite_all(k_range, n) || !finite_all(q0, pn) || !finite_all(qd0, pn) || !finite_all(qdd0, pn) || !finite_all(k, pn) || (tube && !finite_all(tube, pn))) {
-        armour_set_error("%s: non-finite input", who);
-        return ARMOUR_EINVAL;
-    }
-    for (int p = 0; p < P; p++) {
-        if (!(ta[p] >= 0.0) || !(tb[p] >= ta[p]) || !(tb[p] <= duration)) {
-            armour_set_error("%s: piece %d has the window [%g, %g], need 0 <= ta <= tb <= duration = %g", who, p, ta[p], tb[p], duration);
-            return ARMOUR_EINVAL;
-        }
-        for (int j = 0; tube && j < n; j++)
-            if (!(tube[(size_t)p * n + j] >= 0.0)) { armour_set_error("%s: piece %d has a negative tube radius", who, p); return ARMOUR_EINVAL; }
-    }
-    PaPieces& pc = au->pc;
-    std::memset(&pc, 0, sizeof(pc));
-    pc.q0 = q0; pc.qd0 = qd0; pc.qdd0 = qdd0; pc.k = k; pc.ta = ta; pc.tb = tb; pc.tube = tube;
-    for (int j = 0; j < n; j++) pc.k_range[j] = k_range[j];
-    pc.duration = duration;
-    pc.step = step;
-    au->piece_off.assign((size_t)P + 1, 0);
-    for (int p = 0; p < P; p++) {
-        const double S = piece_intervals(au->rb, pc, p);
-        if (!(S + (double)au->piece_off[p] <= (double)(INT32_MAX - 1))) {
-            armour_set_error("%s: more than 2^31 - 2 (piece, sub-interval) items (step %g too small)", who, step);
-            return ARMOUR_ECAPACITY;
-        }
-        au->piece_off[p + 1] = au->piece_off[p] + (int64_t)S;
-    }
-    au->items = au->piece_off[P];
-    return ARMOUR_OK;
-}
-
-// the per-piece results from what the items left
-void finish_audit(const SelfAudit& au, int32_t P, const int32_t* first_hit, const uint8_t* undecided, const double* item_clear, int32_t* verdict, double* t_hit,
-                  double* clearance) {
-    const int rows = au.tb.rows;
-    for (int p = 0; p < P; p++) {
-        const int64_t S = au.piece_off[p + 1] - au.piece_off[p];
-        const bool hit = first_hit[p] != SC_NO_HIT;
-        verdict[p] = hit ? 1 : undecided[p] ? 2 : 0;
-        if (t_hit) {
-            const double ta = au.pc.ta[p], w = au.pc.tb[p] - ta;
-            t_hit[p] = hit ? ta + ((double)(2 * (int64_t)first_hit[p] + 1) * w) / (double)(2 * S) : NAN;
-        }
-        if (clearance) {
-            double cl = INFINITY;
-            for (int64_t x = au.piece_off[p] * rows; x < au.piece_off[p + 1] * rows; x++) cl = fmin(cl, item_clear[x]);
-            clearance[p] = cl;
-        }
-    }
+    ARMOUR_TRY(check_pieces(who, au->rb.n, a, verdict, &au->pc));
+    return piece_offsets(who, au->rb, au->pc, a.P, &au->piece_off);
 }
 
 // the launch of self_check_kernel and the merge of its rows; the buffers are the caller's
@@ -369,23 +296,20 @@ extern "C" int armour_path_audit_self_host(const ArmourRobot* robot, const uint8
                                            const double* qdd0, const double* k, const double* k_range, double duration, const double* ta, const double* tb,
                                            const double* tube, double step, int32_t* verdict, double* t_hit, double* clearance) {
     SelfAudit au;
-    ARMOUR_TRY(make_audit("armour_path_audit_self_host", robot, pairs, shrink, P, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, verdict, &au));
+    ARMOUR_TRY(make_audit("armour_path_audit_self_host", robot, pairs, shrink, {P, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step}, verdict, &au));
     const int rows = au.tb.rows, J = au.tb.J;
-    std::vector<int32_t> first_hit(P, SC_NO_HIT);
-    std::vector<uint8_t> undecided(P, 0);
-    std::vector<double> item_clear(clearance ? (size_t)au.items * rows : 0);
+    AuditMerge mg(P, clearance ? (size_t)au.piece_off[P] * rows : 0);
     for (int p = 0; p < P; p++) {
         const int64_t S = au.piece_off[p + 1] - au.piece_off[p];
-        for (int64_t s = 0; s < S && (clearance || first_hit[p] == SC_NO_HIT); s++)
+        for (int64_t s = 0; s < S && (clearance || mg.first_hit[p] == PA_NO_HIT); s++)
             for (int a = 0; a < rows; a++) {
                 double cl;
                 const int state = self_item_state(au.rb, au.pc, a, p, s, S, au.tb.on + a * J, au.tb.shrink + a * J, clearance != nullptr, &cl);
-                if (clearance) item_clear[(size_t)(au.piece_off[p] + s) * rows + a] = cl;
-                if (state == 1) first_hit[p] = std::min(first_hit[p], (int32_t)s);
-                else if (state == 2) undecided[p] = 1;
+                if (clearance) mg.item_clear[(size_t)(au.piece_off[p] + s) * rows + a] = cl;
+                audit_record(state, s, &mg.first_hit[p], &mg.undecided[p]);
             }
     }
-    finish_audit(au, P, first_hit.data(), undecided.data(), item_clear.data(), verdict, t_hit, clearance);
+    finish_pieces(au.pc, au.piece_off, nullptr, rows, P, mg, verdict, t_hit, clearance);
     return ARMOUR_OK;
 }
 
@@ -394,58 +318,30 @@ extern "C" int armour_path_audit_self(const ArmourRobot* robot, const uint8_t* p
                                       const double* tube, double step, int32_t* verdict, double* t_hit, double* clearance, double* ms) {
     // ---- arguments and the work list, before the device is touched
     SelfAudit au;
-    ARMOUR_TRY(make_audit("armour_path_audit_self", robot, pairs, shrink, P, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, verdict, &au));
+    ARMOUR_TRY(make_audit("armour_path_audit_self", robot, pairs, shrink, {P, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step}, verdict, &au));
     if (ms) *ms = 0.0;
-    const int n = au.rb.n, rows = au.tb.rows;
-    const int64_t items = au.items;
-    std::vector<int32_t> first_hit(P, SC_NO_HIT);
-    std::vector<uint8_t> undecided(P, 0);
-    std::vector<double> item_clear(clearance ? (size_t)items * rows : 0);
+    const int rows = au.tb.rows;
+    const int64_t items = au.piece_off[P];
+    AuditMerge mg(P, clearance ? (size_t)items * rows : 0);
     if (P > 0 && rows > 0) {
-        std::vector<int32_t> item_piece((size_t)items);
-        for (int p = 0; p < P; p++)
-            for (int64_t x = au.piece_off[p]; x < au.piece_off[p + 1]; x++) item_piece[(size_t)x] = p;
         // ---- the device
         if (!armour_device_available()) { armour_set_error("armour_path_audit_self: no HIP device visible (armour_path_audit_self_host runs without one)"); return ARMOUR_EDEVICE; }
-        DevStream st;
-        EventPair ev;
-        ARMOUR_TRY(st.create());
-        DevBuf<double> d_q0, d_qd0, d_qdd0, d_k, d_ta, d_tb, d_tube, d_clear, d_shrink;
-        DevBuf<int32_t> d_item_piece, d_first_hit;
-        DevBuf<int64_t> d_piece_off;
-        DevBuf<uint8_t> d_undecided, d_on;
-        const size_t pn = (size_t)P * n;
-        ARMOUR_TRY(d_q0.upload(q0, pn, st));
-        ARMOUR_TRY(d_qd0.upload(qd0, pn, st));
-        ARMOUR_TRY(d_qdd0.upload(qdd0, pn, st));
-        ARMOUR_TRY(d_k.upload(k, pn, st));
-        ARMOUR_TRY(d_ta.upload(ta, P, st));
-        ARMOUR_TRY(d_tb.upload(tb, P, st));
-        if (tube) ARMOUR_TRY(d_tube.upload(tube, pn, st));
-        ARMOUR_TRY(d_on.upload(au.tb.on, sizeof(au.tb.on), st));
-        ARMOUR_TRY(d_shrink.upload(au.tb.shrink, sizeof(au.tb.shrink) / sizeof(double), st));
-        ARMOUR_TRY(d_item_piece.upload(item_piece.data(), item_piece.size(), st));
-        ARMOUR_TRY(d_piece_off.upload(au.piece_off.data(), au.piece_off.size(), st));
-        ARMOUR_TRY(d_first_hit.upload(first_hit.data(), P, st));
-        ARMOUR_TRY(d_undecided.upload(undecided.data(), P, st));
-        if (clearance) ARMOUR_TRY(d_clear.reserve((size_t)items * rows));
-        PaPieces dpc = au.pc;
-        dpc.q0 = d_q0; dpc.qd0 = d_qd0; dpc.qdd0 = d_qdd0; dpc.k = d_k; dpc.ta = d_ta; dpc.tb = d_tb;
-        dpc.tube = tube ? d_tube : nullptr;
-        ARMOUR_TRY(ev.record_start(st));
+        AuditDevice dev;
+        PaPieces dpc;
+        ARMOUR_TRY(dev.upload(au.pc, P, au.rb.n, au.piece_off, mg, &dpc));
+        DevBuf<double> d_shrink;
+        DevBuf<uint8_t> d_on;
+        ARMOUR_TRY(d_on.upload(au.tb.on, sizeof(au.tb.on), dev.st));
+        ARMOUR_TRY(d_shrink.upload(au.tb.shrink, sizeof(au.tb.shrink) / sizeof(double), dev.st));
+        ARMOUR_TRY(dev.ev.record_start(dev.st));
         if (items > 0) {
             const dim3 grid((unsigned)((items + SC_BLOCK - 1) / SC_BLOCK), (unsigned)rows);
-            hipLaunchKernelGGL(self_audit_kernel, grid, dim3(SC_BLOCK), 0, st, au.rb, dpc, rows, items, d_item_piece, d_piece_off, d_on, d_shrink, d_first_hit,
-                               d_undecided, clearance ? d_clear : nullptr);
+            hipLaunchKernelGGL(self_audit_kernel, grid, dim3(SC_BLOCK), 0, dev.st, au.rb, dpc, rows, items, dev.item_piece, dev.piece_off, d_on, d_shrink,
+                               dev.first_hit, dev.undecided, clearance ? dev.clear.p : nullptr);
             HIPCHK(hipGetLastError());
         }
-        ARMOUR_TRY(ev.record_stop(st));
-        HIPCHK(hipMemcpyAsync(first_hit.data(), d_first_hit, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(undecided.data(), d_undecided, (size_t)P, hipMemcpyDeviceToHost, st));
-        if (clearance && items) HIPCHK(hipMemcpyAsync(item_clear.data(), d_clear, (size_t)items * rows * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
+        ARMOUR_TRY(dev.download(&mg, ms));
     }
-    finish_audit(au, P, first_hit.data(), undecided.data(), item_clear.data(), verdict, t_hit, clearance);
+    finish_pieces(au.pc, au.piece_off, nullptr, rows, P, mg, verdict, t_hit, clearance);
     return ARMOUR_OK;
 }

@@ -14,13 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import _dp, check
 
 FREE, HIT, UNDECIDED = 0, 1, 2
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 @dataclass
@@ -44,49 +40,43 @@ def _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb):
     return P, n, q0, qd0, qdd0, k, k_range, ta, tb
 
 
-def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, clearance=False, host=False):
-    """P pieces in one call.  obstacles [W,O,12] (or [O,12]: W = 1); world_of_piece [P]; q0 / qd0 / qdd0 / k [P,n]; k_range [n]; ta / tb [P] or
-    scalars; tube [P,n], [n] or None (zeros): the per-joint radius about the plan that is audited with it."""
+def _audit(entries, lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, clearance, host):
+    """What audit and audit_self share.  entries: the (device, host) entries' names; lead(P): the arguments between the robot and q0."""
     L = _lib.load()
     P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)
-    obs = np.asarray(obstacles, dtype=np.float64)
-    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-    W, O = obs.shape[0], obs.shape[1]
-    wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
     tube = None if tube is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tube, dtype=np.float64), (P, n)))
     verdict = np.zeros(P, dtype=np.int32)
     t_hit = np.zeros(P)
     cl = np.zeros(P) if clearance else None
-    ip = C.POINTER(C.c_int32)
-    args = [C.byref(robot), W, O, _dp(obs) if obs.size else None, P, wp.ctypes.data_as(ip), _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range),
-            float(duration), _dp(ta), _dp(tb), _dp(tube), float(step), verdict.ctypes.data_as(ip), _dp(t_hit), _dp(cl)]
+    args = [C.byref(robot), *lead(P), _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range), float(duration), _dp(ta), _dp(tb), _dp(tube), float(step),
+            verdict.ctypes.data_as(C.POINTER(C.c_int32)), _dp(t_hit), _dp(cl)]
     ms = C.c_double(0.0)
     if host:
-        check(L.armour_path_audit_host(*args))
+        check(getattr(L, entries[1])(*args))
     else:
-        check(L.armour_path_audit(*args, C.byref(ms)))
+        check(getattr(L, entries[0])(*args, C.byref(ms)))
     return AuditResult(verdict=verdict, t_hit=t_hit, clearance=cl, ms=ms.value)
+
+
+def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, clearance=False, host=False):
+    """P pieces in one call.  obstacles [W,O,12] (or [O,12]: W = 1); world_of_piece [P]; q0 / qd0 / qdd0 / k [P,n]; k_range [n]; ta / tb [P] or
+    scalars; tube [P,n], [n] or None (zeros): the per-joint radius about the plan that is audited with it."""
+    obs = np.asarray(obstacles, dtype=np.float64)
+    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+
+    def lead(P):
+        wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
+        return [obs.shape[0], obs.shape[1], _dp(obs) if obs.size else None, P, wp.ctypes.data_as(C.POINTER(C.c_int32))]
+    return _audit(("armour_path_audit", "armour_path_audit_host"), lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, clearance, host)
 
 
 def audit_self(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, pairs=None, shrink=None, clearance=False, host=False):
     """The same pieces against the arm itself (armour_path_audit_self): verdict 0 proved self-free, 1 proved self-hit (t_hit), 2 undecided.
     pairs / shrink [J,J] as armour_amd.self_check.check takes them (None: every pair b - a >= 2, no shrink)."""
     from .self_check import table_args
-    L = _lib.load()
-    P, n, q0, qd0, qdd0, k, k_range, ta, tb = _pieces(robot, q0, qd0, qdd0, k, k_range, ta, tb)
-    tube = None if tube is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tube, dtype=np.float64), (P, n)))
     pairs, shrink, pp, sp = table_args(robot, pairs, shrink)
-    verdict = np.zeros(P, dtype=np.int32)
-    t_hit = np.zeros(P)
-    cl = np.zeros(P) if clearance else None
-    args = [C.byref(robot), pp, sp, P, _dp(q0), _dp(qd0), _dp(qdd0), _dp(k), _dp(k_range), float(duration), _dp(ta), _dp(tb), _dp(tube), float(step),
-            verdict.ctypes.data_as(C.POINTER(C.c_int32)), _dp(t_hit), _dp(cl)]
-    ms = C.c_double(0.0)
-    if host:
-        check(L.armour_path_audit_self_host(*args))
-    else:
-        check(L.armour_path_audit_self(*args, C.byref(ms)))
-    return AuditResult(verdict=verdict, t_hit=t_hit, clearance=cl, ms=ms.value)
+    return _audit(("armour_path_audit_self", "armour_path_audit_self_host"), lambda P: [pp, sp, P], robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube,
+                  step, clearance, host)
 
 
 def audit_items(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, step=0.02):

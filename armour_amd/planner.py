@@ -18,11 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ArmourLimits, ArmourParams, ArmourRobot, check
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+from ._lib import ArmourLimits, ArmourParams, ArmourRobot, _dp, check
 
 
 def kinova_robot():

@@ -16,12 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import _dp, check
 from .scenes import angdiff, straight_line_waypoint
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def wrapped_diff(a, b, continuous):

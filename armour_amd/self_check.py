@@ -16,13 +16,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import check as _check
+from ._lib import _dp, check as _check
 
 _u8 = C.POINTER(C.c_uint8)
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def table_args(robot, pairs, shrink):

@@ -15,14 +15,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import ArmourTrackOptions, ArmourTrackResult, check
+from ._lib import ArmourTrackOptions, ArmourTrackResult, _dp, check
 from .planner import kinova_robot
 
 CONTROLLERS = {"robust": _lib.TRACK_CTL_ROBUST, "nominal": _lib.TRACK_CTL_NOMINAL, "none": _lib.TRACK_CTL_NONE}
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def ultimate_bound(robot, V_max=None, Kr=None):

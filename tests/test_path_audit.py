@@ -210,6 +210,36 @@ def test_audit_refuses_bad_arguments_before_touching_a_device():
     assert res.verdict[0] == 0 and np.isnan(res.t_hit[0])
 
 
+def test_both_audits_hold_their_pieces_to_the_same_rules():
+    """Every single bad piece argument that both audits check: the same code from audit and audit_self, and the same message after the
+    entry's name (the device entries as well: refused before a device is touched)."""
+    from armour_amd import _lib
+    from armour_amd.path_audit import audit, audit_self
+    robot = _robot("kinova")
+    z = np.zeros((1, 7))
+    one = np.ones((1, 7))
+    nan = np.full((1, 7), np.nan)
+    box = np.array([[5.0, 0, 0, 0.1, 0, 0, 0, 0.1, 0, 0, 0, 0.1]])
+    bad = [(dict(step=0.0), _lib.EINVAL), (dict(duration=0.0), _lib.EINVAL), (dict(ta=0.6, tb=0.5), _lib.EINVAL), (dict(tb=1.5), _lib.EINVAL),
+           (dict(tube=-np.ones(7)), _lib.EINVAL), (dict(q0=nan), _lib.EINVAL), (dict(qd0=nan), _lib.EINVAL), (dict(qdd0=nan), _lib.EINVAL),
+           (dict(k=nan), _lib.EINVAL), (dict(k_range=np.full(7, np.nan)), _lib.EINVAL), (dict(k=one, step=1e-12), _lib.ECAPACITY)]
+    for kw, code in bad:
+        for host in (False, True):
+            pieces = (kw.get("q0", z), kw.get("qd0", z), kw.get("qdd0", z), kw.get("k", z), kw.get("k_range", K_RANGE), kw.get("duration", D),
+                      kw.get("ta", 0.0), kw.get("tb", 0.5))
+            rest = dict(tube=kw.get("tube"), step=kw.get("step", 0.02), host=host)
+            said = []
+            for entry, call in (("armour_path_audit", lambda: audit(robot, box, 0, *pieces, **rest)),
+                                ("armour_path_audit_self", lambda: audit_self(robot, *pieces, **rest))):
+                with pytest.raises(_lib.ArmourError) as ei:
+                    call()
+                assert ei.value.code == code, (kw, host, entry, str(ei.value))
+                head = f"armour error {code}: {entry}{'_host' if host else ''}: "
+                assert str(ei.value).startswith(head), (kw, host, str(ei.value))
+                said.append(str(ei.value)[len(head):])
+            assert said[0] == said[1] and said[0], (kw, host, said)
+
+
 # ----------------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
 @pytest.mark.timeout(1200)
@@ -291,3 +321,54 @@ def test_a_piece_driven_through_a_box_is_a_proved_hit():
     far[0, 2] += 3.0
     res = audit(robot, far, 0, q0, z, z, k, k_range, D, 0.0, D, step=0.01)
     assert res.verdict[0] == 0 and np.isnan(res.t_hit[0])
+
+
+def _round_trip_case():
+    """(robot, worlds, world_of_piece, pieces, k_range, step) of the smallest audit whose bookkeeping can go wrong: five pieces of 1, 255,
+    256, 257 and 1 items in the caller's order [1, 0, 1, 0, 1] of two one-box worlds.  World 0's run (255 + 257 items) crosses a 256-item
+    block boundary and ends on one, world 1's (1 + 256 + 1) crosses one; pieces 1 and 3 drive the forearm through world 0's box; piece 4 is
+    an arm folded onto itself at rest."""
+    from armour_amd.path_audit import audit_items
+    robot = _robot("kinova")
+    g = geometry(robot_dict(robot))
+    q_move = np.array([0.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0])
+    k_move = np.array([1.0, 0, 0, 0, 0, 0, 0])
+    k_range = np.full(7, 0.8)                                    # a long move of the base joint: v_0 = 5 * 0.8 / D = 4
+    c = link_boxes(g, q_des(q_move, 0 * q_move, 0 * q_move, k_range * k_move, 0.5)[None])[2][0, 5]      # the forearm's box centre half way
+    way = np.array([[c[0], c[1], c[2], 0.05, 0, 0, 0, 0.05, 0, 0, 0, 0.05]])
+    far = way.copy()
+    far[0, 2] += 3.0
+    step = 4.0 * D / 256.5                                       # S = ceil(4 w / step): 257 on [0, D], S on a window of (S - 0.5) / 256.5
+    q0 = np.stack([q_move] * 4 + [np.array([0.0, 2.1, 0.0, 2.5, 0.0, 1.0, 0.0])])
+    k = np.stack([k_move] * 4 + [np.zeros(7)])
+    z = np.zeros((5, 7))
+    ta = np.array([0.3, 0.0, 0.002, 0.0, 0.0])
+    tb = ta + np.array([0.0, 254.5 / 256.5, 255.5 / 256.5, 1.0, 0.5]) * D
+    pieces = (q0, z, z, k, ta, tb)
+    assert audit_items(robot, *pieces[:4], k_range, D, ta, tb, step=step).tolist() == [1, 255, 256, 257, 1]
+    return robot, np.stack([way, far]), np.array([1, 0, 1, 0, 1], dtype=np.int32), pieces, k_range, step
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_the_shared_round_trip_keeps_its_books_across_blocks_and_worlds():
+    """audit and audit_self on the device against their host entries: verdicts and t_hit identical, clearances to CL_TOL, in verdict
+    mode and in clearance mode; no piece at all is an empty result and no launch."""
+    from armour_amd.path_audit import audit, audit_self
+    robot, worlds, world, (q0, qd0, qdd0, k, ta, tb), k_range, step = _round_trip_case()
+    seen = set()
+    for tag, run in (("world", lambda **kw: audit(robot, worlds, world, q0, qd0, qdd0, k, k_range, D, ta, tb, step=step, **kw)),
+                     ("self", lambda **kw: audit_self(robot, q0, qd0, qdd0, k, k_range, D, ta, tb, step=step, **kw))):
+        for clearance in (False, True):
+            dev, host = run(clearance=clearance), run(clearance=clearance, host=True)
+            print(tag, clearance, dev.verdict, dev.t_hit, dev.clearance, host.clearance)
+            assert np.array_equal(dev.verdict, host.verdict), (tag, clearance, dev.verdict, host.verdict)
+            assert np.array_equal(dev.t_hit, host.t_hit, equal_nan=True), (tag, clearance, dev.t_hit, host.t_hit)
+            if clearance:
+                assert np.abs(dev.clearance - host.clearance).max() <= CL_TOL, (tag, dev.clearance, host.clearance)
+            seen.add((tag, tuple(host.verdict)))
+    assert ("world", (0, 1, 0, 1, 0)) in seen and any(t == "self" and v[4] == 1 for t, v in seen), seen     # first_hit was exercised in both
+    e = np.zeros((0, 7))
+    for res in (audit(robot, worlds, np.zeros(0, dtype=np.int32), e, e, e, e, k_range, D, np.zeros(0), np.zeros(0), step=step, clearance=True),
+                audit_self(robot, e, e, e, e, k_range, D, np.zeros(0), np.zeros(0), step=step, clearance=True)):
+        assert res.verdict.shape == (0,) and res.t_hit.shape == (0,) and res.clearance.shape == (0,) and res.ms == 0.0
