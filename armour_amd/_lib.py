@@ -151,6 +151,7 @@ EXPORTS = [
     "armour_solve_from", "armour_sweep", "armour_sweep_tile",
     "armour_self_pairs_default", "armour_self_check", "armour_self_check_host", "armour_self_edges_host", "armour_roadmap_check_self",
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
+    "armour_roadmap_field", "armour_roadmap_descend",
 ]
 
 _lib = None
@@ -279,6 +280,8 @@ def load():
     L.armour_roadmap_get_sizes.argtypes = [vp, ip, ip, C.POINTER(C.c_int64)]
     L.armour_roadmap_check.argtypes = [vp, C.c_int32, C.c_int32, dp, u8p, u8p, dp, dp]
     L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
+    L.armour_roadmap_field.argtypes = [vp, dp, C.c_int32, dp, ip, ip, ip, dp]
+    L.armour_roadmap_descend.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, dp, ip, dp]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

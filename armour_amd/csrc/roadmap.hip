@@ -58,6 +58,10 @@ __global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int
     }
 }
 
+}  // namespace
+
+namespace rmhost {
+
 double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
     double acc = 0.0;
     for (int j = 0; j < rb.n; j++) {
@@ -67,7 +71,48 @@ double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
     return std::sqrt(acc);
 }
 
-}  // namespace
+bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b) {
+    const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+    for (int64_t s = 0; s < S; s++) {
+        edge_sample(rm->rb, a, b, s, S, q, r);
+        if (!config_free(rm->rb, q, r, obs, rm->O, false, nullptr)) return false;
+    }
+    // with the self masks switched on (armour_roadmap_use_self) the same edge passes the self edge rule as well
+    return !rm->self_on || self_edge_free(rm->rb, rm->self_table, rm->edge_step, a, b);
+}
+
+void world_view(const ArmourRoadmap* rm, int32_t w, WorldView* v) {
+    const int N = rm->N, E = rm->E;
+    v->obs = rm->obs.data() + (size_t)w * rm->O * RM_OBS_STRIDE;
+    v->nf = rm->node_free.data() + (size_t)w * N;
+    v->ef = rm->edge_free.data() + (size_t)w * E;
+    // free in both masks when the self masks are on
+    if (rm->self_on) {
+        v->both_n.assign(v->nf, v->nf + N);
+        v->both_e.assign(v->ef, v->ef + E);
+        for (int i = 0; i < N; i++) v->both_n[i] = v->both_n[i] && rm->self_node_free[i];
+        for (int e = 0; e < E; e++) v->both_e[e] = v->both_e[e] && rm->self_edge_free[e];
+        v->nf = v->both_n.data();
+        v->ef = v->both_e.data();
+    }
+}
+
+void connect(const ArmourRoadmap* rm, const WorldView& v, const double* q, int32_t connect_k, std::vector<std::pair<double, int>>* out) {
+    const int n = rm->rb.n, N = rm->N;
+    std::vector<std::pair<double, int>> cand;
+    for (int i = 0; i < N; i++)
+        if (v.nf[i]) cand.push_back({wrapped_distance(rm->rb, q, &rm->nodes[(size_t)i * n]), i});
+    const size_t k = std::min<size_t>((size_t)connect_k, cand.size());
+    std::partial_sort(cand.begin(), cand.begin() + k, cand.end());
+    out->clear();
+    for (size_t c = 0; c < k; c++)
+        if (edge_free(rm, v.obs, q, &rm->nodes[(size_t)cand[c].second * n])) out->push_back(cand[c]);
+}
+
+}  // namespace rmhost
+
+using rmhost::wrapped_distance;
 
 extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
                                      const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
@@ -136,6 +181,8 @@ extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, con
     const size_t nobs = (size_t)W * O * ARMOUR_OBS_DOUBLES;
     if (const size_t i = first_nonfinite(obstacles, nobs); i < nobs) { armour_set_error("armour_roadmap_check: obstacle %zu is not finite", i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
     HIPCHK(hipSetDevice(rm->device));
+    rm->field_valid = false;   // the fields of armour_roadmap_field belong to the check they were computed from
+    rm->W = -1;                // from here on d_edge_free is rewritten: a check that fails below leaves no worlds, not the last check's host masks
     const size_t WN = (size_t)W * rm->N, WE = (size_t)W * rm->E;
     ARMOUR_TRY(rm->d_node_free.reserve(WN));
     ARMOUR_TRY(rm->d_edge_free.reserve(WE));
@@ -170,18 +217,6 @@ extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, con
     return ARMOUR_OK;
 }
 
-// the edge rule on the host, for an edge that is not in the roadmap
-static bool host_edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b) {
-    const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
-    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
-    for (int64_t s = 0; s < S; s++) {
-        edge_sample(rm->rb, a, b, s, S, q, r);
-        if (!config_free(rm->rb, q, r, obs, rm->O, false, nullptr)) return false;
-    }
-    // with the self masks switched on (armour_roadmap_use_self) the same edge passes the self edge rule as well
-    return !rm->self_on || self_edge_free(rm->rb, rm->self_table, rm->edge_step, a, b);
-}
-
 extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
                                    int32_t max_points, double* path, int32_t* points) {
     if (!rm || !q_start || !q_goal || !points || max_points < 0 || (max_points > 0 && !path) || connect_k < 0) {
@@ -195,19 +230,9 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
     const int n = rm->rb.n, N = rm->N;
     for (int j = 0; j < n; j++)
         if (!std::isfinite(q_start[j]) || !std::isfinite(q_goal[j])) { armour_set_error("armour_roadmap_plan: start / goal not finite"); return ARMOUR_EINVAL; }
-    const double* obs = rm->obs.data() + (size_t)w * rm->O * RM_OBS_STRIDE;
-    const uint8_t* nf = rm->node_free.data() + (size_t)w * N;
-    const uint8_t* ef = rm->edge_free.data() + (size_t)w * rm->E;
-    // free in both masks when the self masks are on
-    std::vector<uint8_t> both_n, both_e;
-    if (rm->self_on) {
-        both_n.assign(nf, nf + N);
-        both_e.assign(ef, ef + rm->E);
-        for (int i = 0; i < N; i++) both_n[i] = both_n[i] && rm->self_node_free[i];
-        for (int e = 0; e < rm->E; e++) both_e[e] = both_e[e] && rm->self_edge_free[e];
-        nf = both_n.data();
-        ef = both_e.data();
-    }
+    rmhost::WorldView view;
+    rmhost::world_view(rm, w, &view);
+    const uint8_t* ef = view.ef;
     auto node = [&](int i) -> const double* { return i == N ? q_start : i == N + 1 ? q_goal : &rm->nodes[(size_t)i * n]; };
     auto emit = [&](const std::vector<int>& seq) -> int {
         *points = (int32_t)seq.size();
@@ -218,7 +243,7 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
         for (size_t i = 0; i < seq.size(); i++) std::memcpy(path + i * n, node(seq[i]), n * sizeof(double));
         return ARMOUR_OK;
     };
-    if (host_edge_free(rm, obs, q_start, q_goal)) return emit({N, N + 1});
+    if (rmhost::edge_free(rm, view.obs, q_start, q_goal)) return emit({N, N + 1});
     // graph: roadmap nodes 0..N-1, start N, goal N+1
     std::vector<std::vector<std::pair<int, double>>> adj((size_t)N + 2);
     for (int e = 0; e < rm->E; e++) {
@@ -228,18 +253,12 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
         adj[a].push_back({b, len});
         adj[b].push_back({a, len});
     }
+    std::vector<std::pair<double, int>> joined;
     for (int end = N; end <= N + 1; end++) {
-        std::vector<std::pair<double, int>> cand;
-        for (int i = 0; i < N; i++)
-            if (nf[i]) cand.push_back({wrapped_distance(rm->rb, node(end), node(i)), i});
-        const size_t k = std::min<size_t>((size_t)connect_k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + k, cand.end());
-        for (size_t c = 0; c < k; c++) {
-            const int i = cand[c].second;
-            if (host_edge_free(rm, obs, node(end), node(i))) {
-                adj[end].push_back({i, cand[c].first});
-                adj[i].push_back({end, cand[c].first});
-            }
+        rmhost::connect(rm, view, node(end), connect_k, &joined);
+        for (const auto& c : joined) {
+            adj[end].push_back({c.second, c.first});
+            adj[c.second].push_back({end, c.first});
         }
     }
     // A* from start to goal; the heuristic (wrapped distance to the goal) is a metric lower bound of every path's length

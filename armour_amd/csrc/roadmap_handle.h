@@ -1,7 +1,8 @@
 // The roadmap handle and the edge rule's sub-segments (include/armour_hip.h, armour_roadmap_*), shared by roadmap.hip (the world check and
-// the search) and self_check.hip (the self-collision masks of the same roadmap).
+// the search), self_check.hip (the self-collision masks of the same roadmap) and roadmap_field.hip (the cost-to-go fields).
 #pragma once
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -53,5 +54,36 @@ struct ArmourRoadmap {
     bool self_on = false, self_checked = false;
     rmgeo::SelfTable self_table;
     std::vector<uint8_t> self_node_free, self_edge_free;   // [N], [E]
+    // the cost-to-go fields (armour_roadmap_field, roadmap_field.hip).  The edge lengths and the CSR rows (neighbour ascending, then edge id)
+    // depend on the roadmap alone: built and uploaded on first use.
+    bool csr_ready = false;
+    DevBuf<double> d_edge_len, d_seed_val, d_cost;
+    DevBuf<int32_t> d_row_off, d_col, d_eid, d_seed_off, d_seed_node, d_next, d_reached, d_sweeps, d_field_status;
+    DevBuf<uint8_t> d_self_edge_free;
+    // the last field, on the host, for armour_roadmap_descend; a check, a self check or armour_roadmap_use_self ends it
+    bool field_valid = false;
+    std::vector<double> field_goals, field_cost;   // [W][n], [W][N]
+    std::vector<int32_t> field_next;                // [W][N]
 };
+
+// ---- what armour_roadmap_plan (roadmap.hip) and the field entries (roadmap_field.hip) share; defined in roadmap.hip
+namespace rmhost {
+
+double wrapped_distance(const rmgeo::RmRobot& rb, const double* a, const double* b);
+// the edge rule on the host, for an edge that is not in the roadmap (with the self masks on: the self edge rule as well)
+bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b);
+
+// World w of the last check as a search reads it: its staged obstacles and its node / edge masks, ANDed with the self masks when those are on.
+struct WorldView {
+    const double* obs = nullptr;
+    const uint8_t *nf = nullptr, *ef = nullptr;
+    std::vector<uint8_t> both_n, both_e;
+};
+void world_view(const ArmourRoadmap* rm, int32_t w, WorldView* v);
+
+// q's connect_k nearest free nodes by wrapped_distance(q, node) (ties: the smaller index), in that order, those whose connecting edge is free:
+// (distance, node)
+void connect(const ArmourRoadmap* rm, const WorldView& v, const double* q, int32_t connect_k, std::vector<std::pair<double, int>>* out);
+
+}  // namespace rmhost
 

@@ -274,6 +274,7 @@ extern "C" int armour_roadmap_check_self(ArmourRoadmap* rm, const uint8_t* pairs
     SelfTable tb;
     ARMOUR_TRY(table_for_handle("armour_roadmap_check_self", rm->rb, pairs, shrink, &tb));
     HIPCHK(hipSetDevice(rm->device));
+    rm->field_valid = false;   // (armour_roadmap_field: a field belongs to the masks it was computed from)
     std::vector<uint8_t> nf((size_t)rm->N), ef((size_t)rm->E);
     ARMOUR_TRY(run_self_check(rm->rb, tb, rm->N, rm->M, rm->E, rm->d_nodes, rm->d_edges, rm->d_edge_off, rm->d_sample_edge, rm->stream, &rm->ev, nf.data(),
                               ef.data(), node_clearance, nullptr, ms));
@@ -289,6 +290,7 @@ extern "C" int armour_roadmap_check_self(ArmourRoadmap* rm, const uint8_t* pairs
 extern "C" int armour_roadmap_use_self(ArmourRoadmap* rm, int32_t on) {
     if (!rm) { armour_set_error("armour_roadmap_use_self: null handle"); return ARMOUR_EINVAL; }
     rm->self_on = on != 0;
+    rm->field_valid = false;
     return ARMOUR_OK;
 }
 

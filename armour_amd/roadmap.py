@@ -8,6 +8,9 @@ configurations + an adjacency list in, node feasibility / link_c / the collision
     v = rm.check(obstacles)                 # [W,O,12] -> node_free [W,N], edge_free [W,E] (+ node_clearance), one launch
     path = rm.plan(w, q_start, q_goal)      # host A* over world w's free graph, [P,n] (None: no path)
     hlp = RoadmapHLP(rm, goal); q_des = hlp.get_waypoint(q_cur, lookahead)
+    f = rm.field(goals)                     # [W,n] -> every world's cost-to-go cost [W,N] and successors next [W,N], one launch
+    path, length = rm.descend(w, q_start)   # host, no search: nearest nodes + the successor pointers
+    res = run_trials(worlds, hlp=field_hlps(rm, worlds))    # the roadmap as the trials' high-level planner
 
 The node and edge rules (exact node test, conservative edge test with enlarged boxes) are stated in include/armour_hip.h and DESIGN.md.
 """
@@ -17,7 +20,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import _dp, check
-from .scenes import angdiff, straight_line_waypoint
+from .scenes import angdiff, pad_obstacles, straight_line_waypoint
+
+NEXT_GOAL = -2          # ARMOUR_ROADMAP_NEXT_GOAL: the successor of a node that is joined to the goal itself
 
 
 def wrapped_diff(a, b, continuous):
@@ -79,6 +84,7 @@ class Roadmap:
         N, E, M = C.c_int32(), C.c_int32(), C.c_int64()
         check(self.L.armour_roadmap_get_sizes(self.h, C.byref(N), C.byref(E), C.byref(M)))
         self.N, self.E, self.edge_samples = N.value, E.value, M.value
+        self.W = None           # the worlds of the last successful check (None: none yet)
 
     def close(self):
         if getattr(self, "h", None):
@@ -104,6 +110,7 @@ class Roadmap:
         u8 = C.POINTER(C.c_uint8)
         check(self.L.armour_roadmap_check(self.h, W, O, _dp(obs) if obs.size else None, nf.ctypes.data_as(u8), ef.ctypes.data_as(u8),
                                           _dp(cl) if clearance else None, C.byref(ms)))
+        self.W = W              # (a check that fails after its arguments passed leaves the library without worlds: field() is ESTATE)
         out = dict(node_free=nf.astype(bool), edge_free=ef.astype(bool), ms=ms.value)
         if clearance:
             out["node_clearance"] = cl
@@ -141,6 +148,37 @@ class Roadmap:
         check(self.L.armour_roadmap_plan(self.h, int(w), _dp(s), _dp(g), int(connect_k), cap, _dp(path), C.byref(pts)))
         return path[:pts.value].copy() if pts.value else None
 
+    def field(self, goals, connect_k=8):
+        """goals [W,n], one per world of the last check ([n] when that check had one world) -> dict cost [W,N] (shortest free-graph distance
+        to the goal, inf where there is none), next [W,N] (successor node, NEXT_GOAL at a node joined to the goal, -1 unreachable),
+        reached [W], sweeps [W], ms (device time of the launch).  The library takes W from the last check, so any other number of goals is
+        a ValueError here.  The handle keeps the field for descend() until the next check / check_self / use_self."""
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, self.n)
+        W = g.shape[0]
+        if self.W is None:      # no check to take W from: the library says so (ESTATE) before it reads or writes anything
+            check(self.L.armour_roadmap_field(self.h, None, int(connect_k), None, None, None, None, None))
+            raise RuntimeError("armour_roadmap_field accepted a roadmap without a check")
+        if W != self.W:
+            raise ValueError(f"Roadmap.field: {W} goals for the {self.W} worlds of the last check")
+        cost = np.zeros((W, self.N))
+        nxt = np.zeros((W, self.N), dtype=np.int32)
+        reached, sweeps = np.zeros(W, dtype=np.int32), np.zeros(W, dtype=np.int32)
+        ms = C.c_double()
+        i32 = C.POINTER(C.c_int32)
+        check(self.L.armour_roadmap_field(self.h, _dp(g) if g.size else None, int(connect_k), _dp(cost), nxt.ctypes.data_as(i32),
+                                          reached.ctypes.data_as(i32), sweeps.ctypes.data_as(i32), C.byref(ms)))
+        self.field_goals = g.copy()
+        return dict(cost=cost, next=nxt, reached=reached, sweeps=sweeps, ms=ms.value)
+
+    def descend(self, w, start, connect_k=8, max_points=None):
+        """(path [P,n] from start to world w's goal of the last field(), its length) by the field's successors; (None, inf) if none."""
+        s = np.ascontiguousarray(start, dtype=np.float64).reshape(self.n)
+        cap = self.N + 2 if max_points is None else int(max_points)
+        path = np.zeros((cap, self.n))
+        pts, length = C.c_int32(), C.c_double()
+        check(self.L.armour_roadmap_descend(self.h, int(w), _dp(s), int(connect_k), cap, _dp(path), C.byref(pts), C.byref(length)))
+        return (path[:pts.value].copy() if pts.value else None), length.value
+
 
 def waypoint_along(path, q_cur, lookahead, continuous):
     """The point at arc length `lookahead` from q_cur along the polyline q_cur -> path[1] -> ... (segments wrapped on continuous joints),
@@ -176,3 +214,32 @@ class RoadmapHLP:
         if self.path is None:
             return straight_line_waypoint(q_cur, self.goal, lookahead)
         return waypoint_along(self.path, q_cur, lookahead, self.roadmap.continuous.astype(bool))
+
+
+class RoadmapFieldHLP:
+    """RoadmapHLP without the search: get_waypoint(q_cur, lookahead) follows world `world`'s cost-to-go field of the roadmap's last
+    field() (Roadmap.descend) and returns the point `lookahead` along that path; with no path it falls back to
+    scenes.straight_line_waypoint towards the field's goal."""
+
+    def __init__(self, roadmap, world, connect_k=8):
+        self.roadmap, self.world, self.connect_k = roadmap, int(world), int(connect_k)
+        self.goal = np.array(roadmap.field_goals[self.world])
+        self.path = None
+
+    def get_waypoint(self, q_cur, lookahead):
+        self.path, _ = self.roadmap.descend(self.world, q_cur, connect_k=self.connect_k)
+        if self.path is None:
+            return straight_line_waypoint(q_cur, self.goal, lookahead)
+        return waypoint_along(self.path, q_cur, lookahead, self.roadmap.continuous.astype(bool))
+
+
+def field_hlps(roadmap, worlds, connect_k=8):
+    """`worlds` as trials.run_trials takes them ([(name, problem)]): checks the roadmap against all of them in one launch (obstacles padded
+    to one count), computes every world's field towards its goal in one call, and returns the factory (i, world) -> RoadmapFieldHLP that
+    run_trials(hlp=...) accepts.  The roadmap serves these worlds until its next check."""
+    probs = [p for _, p in worlds]
+    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
+    O = max([o.shape[0] for o in obs] + [1])
+    roadmap.check(np.stack([pad_obstacles(o, O) for o in obs]))
+    roadmap.field(np.stack([np.asarray(p["goal"], dtype=np.float64) for p in probs]), connect_k=connect_k)
+    return lambda i, world: RoadmapFieldHLP(roadmap, i, connect_k=connect_k)

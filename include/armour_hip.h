@@ -608,6 +608,42 @@ int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* 
 int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q_start, const double* q_goal, int32_t connect_k,
                         int32_t max_points, double* path, int32_t* points);
 
+/* Cost-to-go fields (roadmap_field.hip): in a trial a world's goal never changes, so the shortest free-graph distance from EVERY node to
+ * the goal, with a successor pointer, is computed once for all W worlds of the last check, in one launch.
+ *
+ * Graph of world w: the roadmap's edges e with edge_free[w][e]; with armour_roadmap_use_self on, also self_edge_free[e] (free in both
+ *   masks, as armour_roadmap_plan).  A free edge has free endpoints, so node masks are not needed.
+ * Edge length: len[e] = wrapped distance of nodes[a] -> nodes[b], a = edges[2e], b = edges[2e + 1] (the square root of the sum over
+ *   joints, in order, of the squared wrapped difference), evaluated once on the host; the device takes no square root.
+ * Seeds: the goal of world w is joined to its connect_k nearest free nodes by host-checked edges, exactly as armour_roadmap_plan joins
+ *   its goal; such a node i starts at seed[i] = wrapped distance of goal -> node i (every other node: seed = +inf).
+ * Field: cost[w][.] is the GREATEST solution of  cost[v] = min(seed[v], min over free edges (u, v) of fl(cost[u] + len[e])),
+ *   +inf where no seed is reachable.  Every sum is one fp64 add, accumulated from the goal outwards.
+ * Successor: next[w][v] = -1 when cost[v] is infinite; ARMOUR_ROADMAP_NEXT_GOAL when seed[v] == cost[v]; otherwise the smallest u over
+ *   the free edges at v with fl(cost[u] + len[e]) == cost[v] and cost[u] < cost[v].  With every length above half an ulp of the costs
+ *   (any roadmap of distinct nodes at a sensible spacing) the second condition follows from the first.  It is there for edges that join
+ *   equal costs -- length 0 (a self loop, duplicate nodes) or a length the sum absorbs -- where each end would name the other: the costs
+ *   fall strictly along next[], so a walk never cycles.  Limitation: a node that reaches its cost ONLY over such an edge has next = -1
+ *   although its cost is finite, and armour_roadmap_descend through it is ARMOUR_ESTATE.
+ * Determinism: x -> fl(x + len) is monotone and never decreases x, so the greatest solution is unique; any relaxation order, in place
+ *   or not, ends at the same doubles, and so does a heap Dijkstra from the seeds.  The device's result is defined bit for bit.
+ * Device: one block per world sweeps its cost row in place until a sweep changes nothing (at most N + 1 sweeps, else ARMOUR_ESTATE);
+ *   W = 1 therefore runs on one compute unit. */
+#define ARMOUR_ROADMAP_NEXT_GOAL (-2)
+/* goals [W][n] for the W worlds of the last armour_roadmap_check.  Outputs, each may be NULL: cost [W][N] (+inf unreachable),
+ * next [W][N], reached [W] (nodes with a finite cost), sweeps [W], ms (device time of the launch).  The handle keeps goals,
+ * cost and next on the host for armour_roadmap_descend.  ARMOUR_ESTATE before a check (or, with self masks on, before a self check). */
+int armour_roadmap_field(ArmourRoadmap* rm, const double* goals, int32_t connect_k, double* cost, int32_t* next,
+                         int32_t* reached, int32_t* sweeps, double* ms);
+/* Host, no search: the direct start -> goal edge if free (as armour_roadmap_plan); else among start's connect_k nearest free nodes
+ * whose connecting edge is free and whose cost is finite, the one with the smallest fl(distance + cost) (first in nearest order on a
+ * tie), then next[] to the goal.  path = start, nodes..., goal; *points = 0: no path; *length = that smallest sum (0-point: +inf;
+ * direct edge: the wrapped distance; may be NULL).  A walk longer than N + 1 steps is ARMOUR_ESTATE.  armour_roadmap_check,
+ * armour_roadmap_check_self and armour_roadmap_use_self each end the field: ARMOUR_ESTATE until the next armour_roadmap_field.
+ * ARMOUR_ECAPACITY (with *points = the length needed) when max_points is too small. */
+int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double* q_start, int32_t connect_k, int32_t max_points,
+                           double* path, int32_t* points, double* length);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

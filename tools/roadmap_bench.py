@@ -1,13 +1,20 @@
 """Throughput of the roadmap check (armour_roadmap_check) and of the host search (armour_roadmap_plan); prints ONE JSON line.
 
-    python tools/roadmap_bench.py [--nodes 20000] [--radius 0.3] [--k-max 16] [--edge-step 0.05] [--reps 10] [--graph-radius 1.5]
+    python tools/roadmap_bench.py [--nodes 20000] [--radius 0.3] [--k-max 16] [--edge-step 0.05] [--reps 10] [--graph-radius 1.5] [--out FILE]
 
 Roadmap: armour_amd.roadmap.uniform_roadmap on the Kinova without gripper.  Worlds: the 107 reference worlds (scenes.reference_worlds,
 O padded with scenes.FAR_BOX), all at once (W = 107) and the first alone (W = 1).  Per row: work items (nodes + edge sub-segments) x W,
 kernel ms (median of `reps` launches, the ms of armour_roadmap_check), checks/s = items x W / kernel time, and the upper bound on
 plane tests per launch (items x W x links x O x 15; the early exit at the first colliding pair does fewer).  With 7 joints a radius of
 0.3 joins almost no pair of 20 000 uniform samples, so a second roadmap with --graph-radius is measured as well; its plan_ms is the
-median host time of armour_roadmap_plan between random free start / goal nodes of world 0."""
+median host time of armour_roadmap_plan between random free start / goal nodes of world 0.
+
+`field` (per roadmap): armour_roadmap_field for all worlds towards their own goals (W = 107) and for the first alone (W = 1) -- kernel ms
+= the median `ms` of `reps` calls after a warm-up, call_ms = the median host time of the same calls (the seed search for W goals, the
+uploads, the launch, the copy of cost and next back, and the wrapper's output arrays), sweeps, the share of nodes reached -- and the host
+median of armour_roadmap_descend over the same 20 start / goal pairs plan_ms is taken on, in the same run (one field per pair's goal, then
+the timed descend).  break_even_queries = field call_ms per world / (plan_ms - descend_ms): the queries per world after which the field has
+paid for itself, by the whole call (null when descend is not faster); break_even_queries_kernel counts the launch alone.  With --out the line is also written to that file (profiles/roadmap_field_bench.json holds a run on the MI355X)."""
 import argparse
 import json
 import os
@@ -20,7 +27,44 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def measure(robot, nodes, edges, cont, obs, edge_step, reps):
+def measure_field(rm, nodes, obs, goals, pairs, plan_ms, reps):
+    """The `field` section: the launch at W = all and W = 1, and descend on the pairs plan() was timed on."""
+    out = {}
+    for W in (obs.shape[0], 1):
+        rm.check(obs[:W])
+        rm.field(goals[:W])                                 # warm-up (the CSR upload, buffers)
+        runs, call = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            runs.append(rm.field(goals[:W]))
+            call.append((time.perf_counter() - t0) * 1e3)
+        ms = sorted(r["ms"] for r in runs)
+        f = runs[-1]
+        out["W=%d" % W] = dict(kernel_ms=round(ms[len(ms) // 2], 4), kernel_ms_min=round(ms[0], 4), call_ms=round(sorted(call)[len(call) // 2], 3),
+                               sweeps_max=int(f["sweeps"].max()),
+                               sweeps_mean=round(float(f["sweeps"].mean()), 2), reached_share=round(float(f["reached"].sum()) / max(1, W * rm.N), 4))
+    rm.check(obs[:1])
+    descend_ms, found, same = [], 0, 0
+    for a, b, planned in pairs:
+        rm.field(nodes[b])
+        t0 = time.perf_counter()
+        p, _ = rm.descend(0, nodes[a], connect_k=8)
+        descend_ms.append((time.perf_counter() - t0) * 1e3)
+        found += p is not None
+        same += (p is not None) == planned
+    if descend_ms:
+        d = float(np.median(descend_ms))
+        gain = plan_ms - d
+        per_world = out["W=%d" % obs.shape[0]]["kernel_ms"] / obs.shape[0]
+        call_per_world = out["W=%d" % obs.shape[0]]["call_ms"] / obs.shape[0]
+        out.update(descend_ms=round(d, 4), descends_found=f"{found}/{len(descend_ms)}", found_as_plan=f"{same}/{len(descend_ms)}",
+                   field_ms_per_world=round(per_world, 4), field_call_ms_per_world=round(call_per_world, 4),
+                   break_even_queries=round(call_per_world / gain, 2) if gain > 0 else None,
+                   break_even_queries_kernel=round(per_world / gain, 2) if gain > 0 else None)
+    return out
+
+
+def measure(robot, nodes, edges, cont, obs, goals, edge_step, reps):
     from armour_amd.roadmap import Roadmap
     rm = Roadmap(robot, nodes, edges, continuous=cont, edge_step=edge_step)
     J, O = robot.num_joints, obs.shape[1]
@@ -35,16 +79,18 @@ def measure(robot, nodes, edges, cont, obs, edge_step, reps):
     v = rm.check(obs)
     free = np.flatnonzero(v["node_free"][0])
     rng = np.random.default_rng(0)
-    plan_ms, found = [], 0
+    plan_ms, found, pairs = [], 0, []
     for _ in range(20 if free.size >= 2 else 0):
         a, b = rng.choice(free, 2, replace=False)
         t0 = time.perf_counter()
         p = rm.plan(0, nodes[a], nodes[b], connect_k=8)
         plan_ms.append((time.perf_counter() - t0) * 1e3)
         found += p is not None
+        pairs.append((a, b, p is not None))
     out = dict(N=rm.N, E=rm.E, edge_samples=rm.edge_samples, O=O, links=J, **rows)
     if plan_ms:
         out.update(plan_ms=round(float(np.median(plan_ms)), 3), plans_found=f"{found}/{len(plan_ms)}")
+    out["field"] = measure_field(rm, nodes, obs, goals, pairs, float(np.median(plan_ms)) if plan_ms else 0.0, reps)
     rm.close()
     return out
 
@@ -57,6 +103,7 @@ def main():
     ap.add_argument("--k-max", type=int, default=16)
     ap.add_argument("--edge-step", type=float, default=0.05)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out")
     a = ap.parse_args()
     from armour_amd.planner import kinova_robot
     from armour_amd.roadmap import uniform_roadmap
@@ -65,11 +112,17 @@ def main():
     n = robot.num_factors
     cont = np.array(robot.continuous[:n]).astype(bool)
     lb, ub = np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n])
-    obs = np.ascontiguousarray(as_batch(reference_worlds())["obstacles"])
+    worlds = reference_worlds()
+    obs = np.ascontiguousarray(as_batch(worlds)["obstacles"])
+    goals = np.stack([np.asarray(p["goal"], dtype=np.float64) for _, p in worlds])
     res = dict(tool="roadmap_bench", robot="kinova_gen3_no_gripper", worlds=obs.shape[0], edge_step=a.edge_step)
     for key, radius in (("radius_%g" % a.radius, a.radius), ("radius_%g" % a.graph_radius, a.graph_radius)):
         nodes, edges = uniform_roadmap(a.nodes, radius, a.k_max, 0, lb, ub, cont)
-        res[key] = measure(robot, nodes, edges, cont.astype(np.uint8), obs, a.edge_step, a.reps)
+        res[key] = measure(robot, nodes, edges, cont.astype(np.uint8), obs, goals, a.edge_step, a.reps)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
     print(json.dumps(res))
 
 

@@ -1,12 +1,15 @@
 """Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
 and prints ONE JSON line.
 
-    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats]
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field]
 
 * the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
   executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
 * audit throughput: (piece, sub-interval) items per second of the trial's own executed pieces at W = 1 (world 0's) and W = 107 (all),
   kernel ms = the median `ms` of armour_path_audit over --reps launches, verdict mode and clearance mode;
+* --hlp roadmap-field: the same worlds once more with the roadmap's cost-to-go fields as the high-level planner (armour_amd.roadmap.field_hlps
+  on uniform_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0)): `hlp_outcomes` holds the outcome counts under both HLPs, the roadmap run's
+  check / field ms and the worlds whose outcome differs.  Everything else in the file is the straight-line run's, as before;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -69,6 +72,26 @@ def kernel_stats(saved, reps, out_csv):
         return hit[0] if hit else dict(error="path_audit_kernel not in the trace")
 
 
+def roadmap_field_trials(robot, ws, straight, a):
+    """The worlds once more under field_hlps; outcome counts under both HLPs and the worlds that end differently."""
+    import time
+    from armour_amd.roadmap import Roadmap, field_hlps, uniform_roadmap
+    from armour_amd.trials import OUTCOMES, run_trials
+    n = robot.num_factors
+    cont = np.array(robot.continuous[:n]).astype(bool)
+    nodes, edges = uniform_roadmap(a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
+    rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
+    t0 = time.perf_counter()
+    make = field_hlps(rm, ws)
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
+    rm.close()
+    count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
+    return dict(roadmap=dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius, check_and_field_wall_ms=setup_ms),
+                straight=count(straight), roadmap_field=count(res), roadmap_field_summary=res["summary"],
+                changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=128)
@@ -76,6 +99,9 @@ def main():
     ap.add_argument("--steps", type=float, nargs="+", default=[0.01, 0.05])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kernel-stats", action="store_true")
+    ap.add_argument("--hlp", choices=["straight", "roadmap-field"], default="straight")
+    ap.add_argument("--roadmap-nodes", type=int, default=20000)
+    ap.add_argument("--roadmap-radius", type=float, default=1.5)
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
@@ -99,6 +125,8 @@ def main():
                solve_ms_per_batch=dict(mean=float(np.mean([b["solve_ms"] for b in bt])), max=float(np.max([b["solve_ms"] for b in bt]))),
                audit_ms_per_batch=dict(mean=float(np.mean([b["audit_ms"] for b in bt])), max=float(np.max([b["audit_ms"] for b in bt]))),
                first_batch=bt[0], min_clearance=float(min(r["clearance"] for w in res["worlds"] for r in w["records"])))
+    if a.hlp == "roadmap-field":
+        out["hlp_outcomes"] = roadmap_field_trials(robot, ws, res, a)
     k_range, D = res["k_range"], res["duration"]
     O = max(w["obstacles"].shape[0] for w in res["worlds"])
     obs = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in res["worlds"]])
