@@ -80,6 +80,9 @@ struct QpResult {
     double max_mult;  // largest multiplier (for the merit penalty)
     int iterations;
     bool feasible;
+    // what the active-set method did on the way (armour_debug_qp_elastic reports them; nothing in the solver reads them): rows dropped from the
+    // active set, those of them that were not its last row (the factor's rows behind them move up), rows excluded, and the active rows at the end
+    int dropped, dropped_mid, excluded, active;
 };
 
 // Goldfarb-Idnani for  min 1/2 x'Gx + g0'x  s.t.  a_i'x >= b_i,  G = diag(Gd) > 0.
@@ -87,6 +90,7 @@ struct QpResult {
 QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<QpRow>& rows, int max_iter = slv::kQpMaxSteps, int box_rows = 0) {
     QpResult res;
     res.iterations = 0; res.feasible = true; res.max_mult = 0;
+    res.dropped = res.dropped_mid = res.excluded = res.active = 0;
     double x[NV], invG[NV];
     for (int j = 0; j < n; j++) { invG[j] = 1.0 / Gd[j]; x[j] = -g0[j] * invG[j]; }
     if (box_rows == 2 * n && (int)rows.size() >= box_rows) {   // the box-clipped minimiser first (solver_common.h)
@@ -142,7 +146,7 @@ QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<Q
                     for (int j = 0; j < n; j++) s += rows[A[i]].a[j] * np[j] * invG[j];
                     rhs[i] = s;
                 }
-                if (!spd_solve(M, q, rhs, r)) { excluded[p] = 1; break; }  // dependent active set: skip this row
+                if (!spd_solve(M, q, rhs, r)) { excluded[p] = 1; res.excluded++; break; }  // dependent active set: skip this row
             }
             double zz = 0, znp = 0;
             for (int j = 0; j < n; j++) {
@@ -168,6 +172,7 @@ QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<Q
                 for (int i = 0; i < q; i++) u[i] -= t * r[i];
                 up += t;
                 is_active[A[l]] = 0;
+                res.dropped++; if (l < q - 1) res.dropped_mid++;
                 for (int i = l; i < q - 1; i++) { A[i] = A[i + 1]; u[i] = u[i + 1]; }
                 q--;
                 continue;
@@ -182,13 +187,15 @@ QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<Q
                 added = true;
             } else {        // partial step: drop the blocking row and try again
                 is_active[A[l]] = 0;
+                res.dropped++; if (l < q - 1) res.dropped_mid++;
                 for (int i = l; i < q - 1; i++) { A[i] = A[i + 1]; u[i] = u[i + 1]; }
                 q--;
             }
         }
         if (!res.feasible) break;
-        if (!added && !excluded[p]) { excluded[p] = 1; }  // could not make progress on this row
+        if (!added && !excluded[p]) { excluded[p] = 1; res.excluded++; }  // could not make progress on this row
     }
+    res.active = q;
     for (int j = 0; j < n; j++) res.x[j] = x[j];
     for (int i = 0; i < q; i++) if (u[i] > res.max_mult) res.max_mult = u[i];
     // The result is VERIFIED against every row, active ones included.  Excluded rows that remain violated mean the linearisation is inconsistent;
@@ -203,6 +210,36 @@ QpResult solve_qp(int n, const double* Gd, const double* g0, const std::vector<Q
         if (s < -1e-7) res.feasible = false;
     }
     return res;
+}
+
+// ---- the elastic attempts of one QP ----
+// sigma = the fraction of its violation a violated row may keep: 0, 0.5, 0.9, 0.99 one after the other, the first feasible attempt wins.
+// `rows_at(sigma)` fills `rows` for an attempt (the candidate rows with their elastic right-hand sides, then the variables' box as 2 n trailing
+// rows).  Returns the attempt taken -- the last one, infeasible, when none was feasible -- with its number and sigma; `tried`, if given,
+// receives every attempt run ([0, *attempt]).  One copy for qp_step and for the test hook armour_debug_qp_elastic.
+constexpr int kElasticAttempts = 4;
+inline double elastic_sigma(int attempt) { return attempt == 0 ? 0.0 : attempt == 1 ? 0.5 : attempt == 2 ? 0.9 : 0.99; }
+inline double elastic_rhs(double v, double sigma) { return v - (v > 0 ? sigma * v : 0.0); }
+template <class RowsAt>
+QpResult solve_qp_elastic(int n, const double* Hd, const double* gradf, std::vector<QpRow>& rows, RowsAt&& rows_at, double* sigma_out, int* attempt_out, QpResult* tried = nullptr) {
+    QpResult qp;
+    int attempt = 0;
+    for (;; attempt++) {
+        rows_at(elastic_sigma(attempt));
+        qp = solve_qp(n, Hd, gradf, rows, slv::kQpMaxSteps, 2 * n);
+        if (tried) tried[attempt] = qp;
+        if (qp.feasible || attempt == kElasticAttempts - 1) break;
+    }
+    *sigma_out = elastic_sigma(attempt);
+    *attempt_out = attempt;
+    return qp;
+}
+// the variables' box x_l <= x + d <= x_u as 2 n rows on the step d: lower then upper bound of variable 0, 1, ...
+inline void append_box_rows(int n, const double* xl, const double* xu, const double* x, std::vector<QpRow>& rows) {
+    for (int j = 0; j < n; j++) {
+        QpRow r; memset(&r, 0, sizeof(r)); r.a[j] = 1.0; r.b = xl[j] - x[j]; rows.push_back(r);
+        QpRow r2; memset(&r2, 0, sizeof(r2)); r2.a[j] = -1.0; r2.b = -(xu[j] - x[j]); rows.push_back(r2);
+    }
 }
 
 // ---- device-side scan of one evaluation: what the host QP needs instead of the whole g / jac ----
@@ -332,6 +369,82 @@ extern "C" int armour_debug_qp_box(int32_t n, const double* Gd, const double* g0
     *feasible = q.feasible ? 1 : 0;
     if (steps) *steps = q.iterations;
     if (max_mult) *max_mult = q.max_mult;
+    return ARMOUR_OK;
+}
+
+// the arguments the two hooks below share: the QP as armour_solve poses it at the iterate x
+static int check_posed_qp(const char* who, int32_t n, const double* Hd, const double* gradf, const double* x, int32_t ncand, const double* a, const double* v) {
+    if (n < 1 || n > NV || ncand < 0 || ncand > 16384 || !Hd || !gradf || !x || (ncand > 0 && (!a || !v))) { armour_set_error("%s: bad argument (n = %d, ncand = %d)", who, n, ncand); return ARMOUR_EINVAL; }
+    bool ok = finite_all(Hd, n) && finite_all(gradf, n) && finite_all(x, n) && finite_all(a, (size_t)ncand * n) && finite_all(v, ncand);
+    for (int j = 0; j < n && ok; j++) ok = Hd[j] > 0;
+    if (!ok) { armour_set_error("%s: non-finite input or Hd <= 0", who); return ARMOUR_EINVAL; }
+    return ARMOUR_OK;
+}
+
+// test hook: the QP of one SQP step with its elastic attempts, the host form's code (solve_qp_elastic, solve_qp).  The QP as armour_solve poses it:
+// n variables, the cost's diagonal Hd and gradient gradf, the iterate x (the box rows -1 - x <= d <= 1 - x are appended as the solver appends them)
+// and ncand candidate rows  a_i'd >= v_i - sigma max(v_i, 0)  (a: [ncand][n] row-major).  Host-only.
+extern "C" int armour_debug_qp_elastic(int32_t n, const double* Hd, const double* gradf, const double* x, int32_t ncand, const double* a, const double* v,
+                                       double* d, int32_t* feasible, int32_t* attempt, double* max_mult, int32_t* steps, int32_t* dropped,
+                                       int32_t* dropped_mid, int32_t* excluded, int32_t* active) {
+    ARMOUR_TRY(check_posed_qp("armour_debug_qp_elastic", n, Hd, gradf, x, ncand, a, v));
+    if (!d || !feasible || !attempt) { armour_set_error("armour_debug_qp_elastic: null output"); return ARMOUR_EINVAL; }
+    double xl[NV], xu[NV];
+    for (int j = 0; j < NV; j++) { xl[j] = -1.0; xu[j] = 1.0; }
+    std::vector<QpRow> rows;
+    const auto rows_at = [&](double sigma) {
+        rows.clear();
+        for (int i = 0; i < ncand; i++) {
+            QpRow r; for (int j = 0; j < n; j++) r.a[j] = a[(size_t)i * n + j];
+            r.b = elastic_rhs(v[i], sigma); rows.push_back(r);
+        }
+        append_box_rows(n, xl, xu, x, rows);
+    };
+    QpResult tried[kElasticAttempts];
+    double sigma = 0.0;
+    int k = 0;
+    const QpResult qp = solve_qp_elastic(n, Hd, gradf, rows, rows_at, &sigma, &k, tried);
+    for (int j = 0; j < n; j++) d[j] = qp.x[j];
+    *feasible = qp.feasible ? 1 : 0;
+    *attempt = k;
+    if (max_mult) *max_mult = qp.max_mult;
+    for (int e = 0; e < kElasticAttempts; e++) {
+        const bool ran = e <= k;
+        if (steps) steps[e] = ran ? tried[e].iterations : -1;
+        if (dropped) dropped[e] = ran ? tried[e].dropped : -1;
+        if (dropped_mid) dropped_mid[e] = ran ? tried[e].dropped_mid : -1;
+        if (excluded) excluded[e] = ran ? tried[e].excluded : -1;
+        if (active) active[e] = ran ? tried[e].active : -1;
+    }
+    return ARMOUR_OK;
+}
+
+// test hook: the same QP through the device form's solve_qp_wave (solver_device.hip: armour_qp_probe_kernel, one plain launch of one block).  wps: the
+// build (1 or 2 waves per SIMD); lds_rows: candidate rows the LDS staging holds (0: what armour_solve gives that build; less: the tests' small regimes).
+extern "C" int armour_debug_qp_device(int32_t n, const double* Hd, const double* gradf, const double* x, int32_t ncand, const double* a, const double* v,
+                                      int32_t wps, int32_t lds_rows, double* d, int32_t* feasible, int32_t* attempt, double* max_mult, int32_t* qp_iter) {
+    ARMOUR_TRY(check_posed_qp("armour_debug_qp_device", n, Hd, gradf, x, ncand, a, v));
+    if (!d || !feasible || !attempt || (wps != 1 && wps != 2) || lds_rows < 0 || lds_rows > armour_qp_probe_lds_rows(wps)) {
+        armour_set_error("armour_debug_qp_device: wps = %d (1, 2), lds_rows = %d (0..%d), or a null output", wps, lds_rows, armour_qp_probe_lds_rows(wps == 2 ? 2 : 1));
+        return ARMOUR_EINVAL;
+    }
+    if (!armour_device_available()) { armour_set_error("armour_debug_qp_device: no HIP device visible (armour_debug_qp_elastic runs without one)"); return ARMOUR_EDEVICE; }
+    QpProbe io;
+    memset(&io, 0, sizeof(io));
+    for (int j = 0; j < NV; j++) { io.x[j] = j < n ? x[j] : 0.0; io.gradf[j] = j < n ? gradf[j] : 0.0; io.Hd[j] = j < n ? Hd[j] : 1e-12; }   // (past n: what the solve kernel puts there)
+    io.ncand = ncand;
+    std::vector<SolveRow> rows((size_t)ncand);
+    for (int i = 0; i < ncand; i++) {
+        SolveRow& r = rows[i];
+        r.idx = i; r.side = 0; r.v = v[i];
+        for (int j = 0; j < NV; j++) r.a[j] = j < n ? a[(size_t)i * n + j] : 0.0;
+    }
+    ARMOUR_TRY(armour_qp_probe(n, rows.data(), wps, lds_rows, &io));
+    for (int j = 0; j < n; j++) d[j] = io.d[j];
+    *feasible = io.feasible;
+    *attempt = io.attempt;
+    if (max_mult) *max_mult = io.max_mult;
+    if (qp_iter) for (int e = 0; e < 4; e++) qp_iter[e] = e <= io.attempt ? io.qp_iter[e] : -1;   // (attempts above the one taken may have been cut short: not reported)
     return ARMOUR_OK;
 }
 
@@ -648,7 +761,7 @@ static int evaluate(HostSolve& s, Scan mode) {
 // order -- or, after an overflow, the same filter over the whole linearisation -- then the variables' box as 2 n trailing rows.
 static void gather_rows(const HostSolve& s, int b, double sigma, std::vector<QpRow>& rows) {
     const int n = s.n, m = s.m, nseg = s.nseg;
-    const auto elastic = [sigma](double v) { return v - (v > 0 ? sigma * v : 0.0); };
+    const auto elastic = [sigma](double v) { return elastic_rhs(v, sigma); };
     rows.clear();
     if (!s.full_on_host) {
         for (int sg = 0; sg < nseg; sg++) {
@@ -671,11 +784,7 @@ static void gather_rows(const HostSolve& s, int b, double sigma, std::vector<QpR
             if (slv::row_lower_candidate(g[i], lo[i], l1)) { QpRow r; for (int j = 0; j < n; j++) r.a[j] = Ji[j]; r.b = elastic(lo[i] - g[i]); rows.push_back(r); }
         }
     }
-    const double* x = s.st[b].x;
-    for (int j = 0; j < n; j++) {
-        QpRow r; memset(&r, 0, sizeof(r)); r.a[j] = 1.0; r.b = s.xl[j] - x[j]; rows.push_back(r);
-        QpRow r2; memset(&r2, 0, sizeof(r2)); r2.a[j] = -1.0; r2.b = -(s.xu[j] - x[j]); rows.push_back(r2);
-    }
+    append_box_rows(n, s.xl.data(), s.xu.data(), s.st[b].x, rows);
 }
 
 // The QP step of SQP iteration `it` for problems [b0, b1) (one host thread's share): up to four elastic attempts, the convergence test, and
@@ -687,14 +796,9 @@ static void qp_step(HostSolve& s, int it, int b0, int b1) {
     for (int b = b0; b < b1; b++) {
         ProblemState& p = s.st[b];
         if (p.done) continue;
-        QpResult qp;
         double sigma = 0.0;
-        for (int attempt = 0; attempt < 4; attempt++) {
-            gather_rows(s, b, sigma, rows);
-            qp = solve_qp(n, &s.Hd[(size_t)b * NV], p.gradf, rows, slv::kQpMaxSteps, 2 * n);
-            if (qp.feasible) break;
-            sigma = attempt == 0 ? 0.5 : attempt == 1 ? 0.9 : 0.99;
-        }
+        int attempt = 0;
+        const QpResult qp = solve_qp_elastic(n, &s.Hd[(size_t)b * NV], p.gradf, rows, [&](double sg) { gather_rows(s, b, sg, rows); }, &sigma, &attempt);
         if (armour_trace_solve() && s.B == 1) {
             fprintf(stderr, "[armour_solve, host form] iteration %d: QP %s at sigma %.2f after %d steps, %zu rows; x =", it, qp.feasible ? "feasible" : "INFEASIBLE", sigma, qp.iterations, rows.size());
             for (int j = 0; j < n; j++) fprintf(stderr, " %.6g", p.x[j]);

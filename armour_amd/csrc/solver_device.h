@@ -73,3 +73,15 @@ int armour_solve_device_capacity(const P2Tables& tb, int max_link, int max_torqu
 int armour_solver_lists(ArmourPlanner* h, p2::SparseList* sl, const int** tq_tiles, const int** tq_count, int* tq_cap);   // relevance.hip
 // d_args: the SolveArgs in device memory (the kernel reads them through the pointer)
 int armour_solve_device_launch(const SolveArgs* d_args, int nb, const SolvePlan& plan, int B, hipStream_t stream);
+
+// ---- test hook armour_debug_qp_device: one QP through solve_qp_wave, outside a solve (solver_device.hip armour_qp_probe_kernel) ----
+struct QpProbe {
+    double x[slv::NV], gradf[slv::NV], Hd[slv::NV];   // in: the iterate, the cost's gradient and diagonal Hessian (entries past n: 0, 0, 1e-12)
+    int ncand, pad0;                                  // in: candidate rows
+    double d[slv::NV], max_mult;                      // out: the step and the largest multiplier of the attempt taken
+    int feasible, attempt, qp_iter[4];                // out: that attempt's verdict and number; steps of every attempt (valid up to the one taken)
+};
+// candidate rows the LDS staging of the `wps` build holds in a solve (SolveArgs::lds_rows as stage_device_solve sets it)
+int armour_qp_probe_lds_rows(int wps);
+// rows: io->ncand host rows.  lds_rows: 0 = armour_qp_probe_lds_rows(wps), or fewer.
+int armour_qp_probe(int n, const slv::SolveRow* rows, int wps, int lds_rows, QpProbe* io);

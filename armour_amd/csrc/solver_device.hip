@@ -370,7 +370,7 @@ __device__ inline int wave_argmin_first(double best, int bi) {
 }
 
 template <int WPS>
-__device__ inline void solve_qp_wave(const SolveArgs& a, const Leader& L, QpShared& S, const SolveRow* cand, const double* lds_rows, unsigned char* flags_g, int max_iter = kQpMaxSteps) {
+__device__ __forceinline__ void solve_qp_wave(const SolveArgs& a, const Leader& L, QpShared& S, const SolveRow* cand, const double* lds_rows, unsigned char* flags_g, int max_iter = kQpMaxSteps) {
     constexpr int kRegRows = WPS == 1 ? 4 : 2;   // rows a lane keeps in registers (the two-waves-per-SIMD build has 256 registers for everything)
     const int n = a.tb.n, lane = threadIdx.x & 63, attempt = threadIdx.x >> 6;
     QpWave& W = S.w[attempt];
@@ -505,6 +505,10 @@ __device__ inline void solve_qp_wave(const SolveArgs& a, const Leader& L, QpShar
             for (int i = 0; i < NV; i++) rr[i] = 0.0;
             WAVE_LDS_SYNC();
             if (q > 0) {
+                // M: an entry per lane; rhs: the NV lanes behind them where the wave has that many (NV = 7: 56 lanes), a second pass on lanes < NV
+                // where it has not (NV = 8: M takes all 64)
+                constexpr bool kRhsOwnLanes = NV * NV + NV <= 64;
+                static_assert(NV * NV <= 64, "solve_qp_wave: one lane per entry of M");
                 if (lane < NV * NV) {
                     const int i = lane / NV, k = lane - i * NV;
                     if (i < q && k <= i) {
@@ -513,9 +517,18 @@ __device__ inline void solve_qp_wave(const SolveArgs& a, const Leader& L, QpShar
                         for (int j = 0; j < NV; j++) if (j < n) s += W.An[i][j] * W.An[k][j] * ih[j];
                         W.M[i * NV + k] = s; W.M[k * NV + i] = s;
                     }
-                } else if (lane < NV * NV + NV) {
+                } else if (kRhsOwnLanes && lane < NV * NV + NV) {
                     const int i = lane - NV * NV;
                     if (i < q) {
+                        double s = 0;
+#pragma unroll
+                        for (int j = 0; j < NV; j++) if (j < n) s += W.An[i][j] * npr[j] * ih[j];
+                        W.rhs[i] = s;
+                    }
+                }
+                if constexpr (!kRhsOwnLanes) {
+                    if (lane < NV && lane < q) {
+                        const int i = lane;
                         double s = 0;
 #pragma unroll
                         for (int j = 0; j < NV; j++) if (j < n) s += W.An[i][j] * npr[j] * ih[j];
@@ -796,6 +809,7 @@ __device__ __forceinline__ int leader_step(const SolveArgs& a, Leader& L, QpShar
             }
             // the candidates' normals and values once more in LDS (the tiles' scratch, idle during the leader's step), component-major: what the
             // four attempts' searches read at every step -- from global memory a step of a 2 000-row QP waited ten load latencies
+            // (armour_qp_probe_kernel below repeats the staging and the choice of the attempt: change them together)
             const double* staged = nullptr;
             if (L.ncand > 64 * (WPS == 1 ? 4 : 2) - 2 * n && L.ncand <= a.lds_rows) {
                 for (int i = tid; i < L.ncand; i += 256) {
@@ -1055,9 +1069,89 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(WPS, W
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the QP alone (test hook)
+// armour_debug_qp_device: ONE QP through solve_qp_wave as a solve would run it -- the same function, the same LDS types, the same register budget
+// (WPS) -- without a world, a reach set or a group of blocks: a plain launch of one block, no wait on anybody.  The rows' staging and the choice
+// of the attempt REPEAT leader_step's lines (that kernel's schedule is too sensitive to share code with a probe): change them together.
+template <int WPS>
+__global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void armour_qp_probe_kernel(const SolveArgs* __restrict__ args, const SolveRow* __restrict__ cand,
+                                                                                                                  QpProbe* __restrict__ io) {
+    const SolveArgs& a = *args;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    __shared__ Leader L;
+    __shared__ QpShared QS;
+    const int tid = threadIdx.x, n = a.tb.n;
+    double* lds_stage = reinterpret_cast<double*>(smem_raw);
+    if (tid < NV) { L.x[tid] = io->x[tid]; L.gradf[tid] = io->gradf[tid]; L.Hd[tid] = io->Hd[tid]; }
+    if (tid == 0) L.ncand = io->ncand;
+    __syncthreads();
+    if (tid == 0) {
+        QS.first_ok = 4;
+        for (int j = 0; j < NV; j++) L.invHd[j] = 1.0 / L.Hd[j];
+    }
+    const double* staged = nullptr;
+    if (L.ncand > 64 * (WPS == 1 ? 4 : 2) - 2 * n && L.ncand <= a.lds_rows) {
+        for (int i = tid; i < L.ncand; i += 256) {
+            const SolveRow& r = cand[i];
+#pragma unroll
+            for (int j = 0; j < NV; j++) lds_stage[(size_t)j * a.lds_rows + i] = r.a[j];
+            lds_stage[(size_t)NV * a.lds_rows + i] = r.v;
+        }
+        staged = lds_stage;
+    }
+    __syncthreads();
+    solve_qp_wave<WPS>(a, L, QS, cand, staged, a.flags);
+    __syncthreads();
+    if (tid == 0) {
+        int k = 0;
+        while (k < 3 && !QS.w[k].feasible) k++;
+        const QpWave& W = QS.w[k];
+        for (int j = 0; j < NV; j++) io->d[j] = W.qx[j];
+        io->max_mult = W.max_mult; io->feasible = W.feasible; io->attempt = k;
+        for (int e = 0; e < 4; e++) io->qp_iter[e] = QS.w[e].qp_iter;
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host side
+// dynamic LDS of the solve kernel: the tiles' scratch, and during the leader's step the staged candidate rows of the QP -- as much as the occupancy
+// leaves (one block per CU / two; the kernel holds 29 KB of its own)
+constexpr size_t kSolveLdsOnePerCu = (size_t)96 * 1024, kSolveLdsTwoPerCu = (size_t)40 * 1024;
+
+int armour_qp_probe_lds_rows(int wps) { return (int)((wps == 1 ? kSolveLdsOnePerCu : kSolveLdsTwoPerCu) / ((NV + 1) * sizeof(double))); }
+
+int armour_qp_probe(int n, const SolveRow* rows, int wps, int lds_rows, QpProbe* io) {
+    static_assert(P2_BLOCK == 256, "solve_qp_wave: four waves, one per elastic attempt");
+    const int ncand = io->ncand;
+    if (lds_rows <= 0) lds_rows = armour_qp_probe_lds_rows(wps);
+    DevStream st;
+    ARMOUR_TRY(st.create());
+    DevBuf<SolveRow> d_rows;
+    DevBuf<unsigned char> d_flags;
+    DevBuf<SolveArgs> d_args;
+    DevBuf<QpProbe> d_io;
+    SolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tb.n = n; a.nb = 1; a.b0 = 0;
+    a.cap_rows = std::max(ncand, 1);   // (solve_qp_wave's global flags: eight arrays of cap_rows + 2 NV bytes, indexed below ncand + 2 n)
+    a.lds_rows = lds_rows;
+    ARMOUR_TRY(d_rows.upload(rows, (size_t)ncand, st));
+    ARMOUR_TRY(d_flags.reserve((size_t)8 * (a.cap_rows + 2 * NV)));
+    a.qp_rows = d_rows; a.flags = d_flags; a.stamps = nullptr;
+    ARMOUR_TRY(d_args.upload(&a, 1, st));
+    ARMOUR_TRY(d_io.upload(io, 1, st));
+    const void* fn = wps == 1 ? (const void*)armour_qp_probe_kernel<1> : (const void*)armour_qp_probe_kernel<2>;
+    const size_t smem = (size_t)lds_rows * (NV + 1) * sizeof(double);   // (<= the solve kernel's of the same build: armour_debug_qp_device checks)
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    if (wps == 1) hipLaunchKernelGGL(armour_qp_probe_kernel<1>, dim3(1), dim3(P2_BLOCK), smem, st, d_args.p, d_rows.p, d_io.p);
+    else hipLaunchKernelGGL(armour_qp_probe_kernel<2>, dim3(1), dim3(P2_BLOCK), smem, st, d_args.p, d_rows.p, d_io.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(io, d_io, sizeof(QpProbe), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return ARMOUR_OK;
+}
+
 int armour_solve_device_capacity(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, int device, int b_launch, int waves_per_simd, SolvePlan* plan,
                                  int n_tiles_override) {
     P2Launch lp;
@@ -1077,15 +1171,15 @@ int armour_solve_device_capacity(const P2Tables& tb, int max_link, int max_torqu
     const void* fn2 = !tb.ll_shared ? (const void*)armour_solve_kernel<false, 9, 2> : six ? (const void*)armour_solve_kernel<true, 6, 2> : (const void*)armour_solve_kernel<true, 9, 2>;
     const int wps_env = waves_per_simd;   // ARMOUR_OPT_SOLVE_WAVES_PER_SIMD (0: automatic)
     // dynamic LDS: the tiles' scratch, and during the leader's step the staged candidate rows of the QP (8 (NV + 1) bytes a row): as much as the
-    // occupancy leaves -- one block per CU: 96 KB (1 365 rows), two: 40 KB (568 rows); the kernel holds 29 KB of its own
-    const size_t smem1 = std::max(smem, (size_t)96 * 1024), smem2 = std::max(smem, (size_t)40 * 1024);
+    // occupancy leaves -- one block per CU: 96 KB (NV = 7: 1 536 rows, NV = 8: 1 365), two: 40 KB (640 / 568 rows); the kernel holds 29 KB of its own
+    const size_t smem1 = std::max(smem, kSolveLdsOnePerCu), smem2 = std::max(smem, kSolveLdsTwoPerCu);
     int per_cu = 0;
     {   // (per kernel function and device, once: the attribute call is a driver round trip and a lone solve is 0.14 ms)
         static std::atomic<unsigned long long> set1[3], set2[3];
         const int which = !tb.ll_shared ? 0 : six ? 1 : 2;
         const unsigned long long bit = 1ull << (device & 63);
-        if (smem1 > 96 * 1024 || !(set1[which].load() & bit)) { HIPCHK(hipFuncSetAttribute(fn1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1)); set1[which].fetch_or(bit); }
-        if (smem2 > 40 * 1024 || !(set2[which].load() & bit)) { HIPCHK(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2)); set2[which].fetch_or(bit); }
+        if (smem1 > kSolveLdsOnePerCu || !(set1[which].load() & bit)) { HIPCHK(hipFuncSetAttribute(fn1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1)); set1[which].fetch_or(bit); }
+        if (smem2 > kSolveLdsTwoPerCu || !(set2[which].load() & bit)) { HIPCHK(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2)); set2[which].fetch_or(bit); }
     }
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn1, P2_BLOCK, smem1));
     const int cap1 = per_cu * prop.multiProcessorCount;

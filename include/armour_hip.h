@@ -475,6 +475,24 @@ int armour_debug_qp(int32_t n, const double* Gd, const double* g0, int32_t m, co
 int armour_debug_qp_box(int32_t n, const double* Gd, const double* g0, int32_t m, const double* A, const double* lo, const double* hi,
                         const double* x_lo, const double* x_hi, int32_t first_try, double* x, int32_t* feasible, int32_t* steps, double* max_mult);
 
+/* test hooks for the QP of one SQP step with its ELASTIC ATTEMPTS (sigma = 0, 0.5, 0.9, 0.99: a violated row may keep that fraction of its violation;
+ * the first feasible attempt wins), posed as armour_solve poses it: n variables, the cost's diagonal Hd[n] > 0 and gradient gradf[n], the iterate x[n]
+ * -- the box rows -1 - x <= d <= 1 - x are appended as the solver appends them -- and ncand <= 16384 candidate rows  a_i'd >= v_i - sigma max(v_i, 0)
+ * (a: [ncand][n] row-major).  Both return the step d[n], feasible, the attempt taken (0..3; 3 with feasible = 0: none was feasible) and its largest
+ * multiplier (max_mult may be NULL), and per attempt arrays of 4 ints (NULL: not wanted; -1: not reported).
+ *
+ * armour_debug_qp_elastic: the host form's code.  Host-only.  Per attempt tried: active-set steps, rows dropped from the active set, those of
+ *   them that were not its last row, rows excluded, active rows at the end.
+ * armour_debug_qp_device: the device form's QP (the persistent kernel's wave-level code, one attempt per wave) in a launch of its own: one block, no
+ *   problem set.  wps: 1 | 2, the kernel build (waves per SIMD: ARMOUR_OPT_SOLVE_WAVES_PER_SIMD); lds_rows: candidate rows the LDS staging holds, 0 =
+ *   what a solve of that build has (96 KB or 40 KB over 8 (ARMOUR_MAX_FACTORS + 1) bytes a row), or fewer (more: ARMOUR_EINVAL).  qp_iter: the steps
+ *   of every attempt up to the one taken (the attempts above it may have been stopped early).  The two forms agree bit for bit. */
+int armour_debug_qp_elastic(int32_t n, const double* Hd, const double* gradf, const double* x, int32_t ncand, const double* a, const double* v,
+                            double* d, int32_t* feasible, int32_t* attempt, double* max_mult, int32_t* steps, int32_t* dropped,
+                            int32_t* dropped_mid, int32_t* excluded, int32_t* active);
+int armour_debug_qp_device(int32_t n, const double* Hd, const double* gradf, const double* x, int32_t ncand, const double* a, const double* v,
+                           int32_t wps, int32_t lds_rows, double* d, int32_t* feasible, int32_t* attempt, double* max_mult, int32_t* qp_iter);
+
 /* ---- diagnostics the reference writes to its 4 extra files (RT/armour_main.cu:329-372) ---- */
 /* torque_radius [B][n][T]   (armour_control_input_radius.out holds its transpose) */
 int armour_get_torque_radius(ArmourPlanner* h, double* torque_radius);

@@ -49,6 +49,70 @@ def make_eight_factor_arm(robot):
     return robot
 
 
+def eight_factor_world(seed, O):
+    """a random state, goal and O boxes for the eight-factor arm (the recipe of _body below, any seed)"""
+    n = 8
+    rng = np.random.default_rng(seed)
+    lb = np.array([-np.pi, -2.41, -np.pi, -2.66, -np.pi, -2.23, -np.pi, -2.2]) + 0.3
+    q0 = rng.uniform(lb, -lb)
+    speed = np.array([1.3963, 1.3963, 1.3963, 1.3963, 1.2218, 1.2218, 1.2218, 1.2218])
+    qd0, qdd0 = rng.uniform(-0.5, 0.5, n) * speed, rng.uniform(-1.0, 1.0, n)
+    q_des = q0 + rng.uniform(-np.pi / 8, np.pi / 8, n)
+    obs = np.zeros((O, 12))
+    obs[:, 0:3] = rng.uniform([-0.8, -0.8, 0.05], [0.8, 0.8, 1.2], (O, 3))
+    s = rng.uniform(0.01, 0.5, (O, 3))
+    obs[:, 3], obs[:, 7], obs[:, 11] = s[:, 0] / 2, s[:, 1] / 2, s[:, 2] / 2
+    return q0, qd0, qdd0, q_des, obs
+
+
+def first_qp_cut_rows(nlp, b=0):
+    """Rows of the FIRST QP of problem b's solve (the linearisation at the start point k = 0) that the box-clipped minimiser of the cost violates by
+    more than the solver's 1e-7: more than zero means that QP cannot end at its box-clipped first try -- it takes active-set steps.  The cost is
+    exactly quadratic with a diagonal Hessian, so the minimiser over the box is the unconstrained one clipped variable by variable."""
+    n = nlp.n
+    zero = np.zeros((nlp.B, n))
+    g, jac = nlp.eval_g_jac(zero)
+    _, _, gl, gu = nlp.get_bounds_info()
+    g0 = nlp.eval_grad_f(zero)[b]
+    Hd = np.array([(nlp.eval_grad_f(np.tile(np.eye(n)[j], (nlp.B, 1)))[b] - g0)[j] for j in range(n)])
+    d_box = np.clip(-g0 / Hd, -1.0, 1.0)
+    lin = g[b] + jac[b] @ d_box
+    return int(np.sum((lin > gu[b] + 1e-7) | (lin < gl[b] - 1e-7)))
+
+
+# Worlds of the eight-factor arm whose solves iterate.  The synthetic arm's torque rows are violated whatever k is (every world above ends with
+# "QP infeasible" before the first step, k_opt = 0), so these are posed without them (input_constraints_off); in the first, 61 collision rows cut
+# the first QP's box-clipped point off: the device form's QP takes active-set steps with 8 variables, and the iterates depend on them.
+ACTIVE_SET_WORLDS = dict(T=40, O=6, seeds=(4, 3, 6))
+
+
+def _solve_comparison_on_worlds_that_iterate():
+    """(runs with ARMOUR_KEY128=1)  host-driven against device-resident solve, both kernel builds, on ACTIVE_SET_WORLDS"""
+    from armour_amd import _lib
+    from armour_amd.planner import ArmourNLP, default_params, kinova_robot
+    cfg = ACTIVE_SET_WORLDS
+    params = default_params(cfg["T"])
+    params.k_range[7] = params.k_range[6]
+    params.input_constraints_off = 1
+    nlp = ArmourNLP(robot=make_eight_factor_arm(kinova_robot()), params=params)
+    worlds = [eight_factor_world(seed, cfg["O"]) for seed in cfg["seeds"]]
+    nlp.set_parameters(*[np.stack([w[i] for w in worlds]) for i in range(5)])
+    cut = first_qp_cut_rows(nlp, 0)
+    assert cut > 0, "the first world's first QP ends at the box-clipped point: no active-set step is tested"
+    host = nlp.solve(host_qp=True)
+    assert host[0]["iterations"] >= 2 and all(h["iterations"] >= 1 for h in host), host
+    for wps in (0, 1, 2):
+        nlp.set_option(_lib.OPT_SOLVE_WAVES_PER_SIMD, wps)
+        for a, c in zip(host, nlp.solve(device_qp=True)):
+            assert (np.array_equal(a["k_opt"], c["k_opt"]) and a["feasible"] == c["feasible"] and a["iterations"] == c["iterations"]
+                    and a["evaluations"] == c["evaluations"] and a["status"] == c["status"] and a["cost"] == c["cost"]
+                    and a["max_violation"] == c["max_violation"]), (wps, a, c)
+    nlp.set_option(_lib.OPT_SOLVE_WAVES_PER_SIMD, 0)
+    print(f"solve (8 variables, {cut} rows cut the first QP's box-clipped point off): feasible {host[0]['feasible']}, status {host[0]['status']}, "
+          f"{host[0]['iterations']} iterations, k_opt {np.round(host[0]['k_opt'], 4)}", flush=True)
+    nlp.close()
+
+
 def _body():
     """(runs with ARMOUR_KEY128=1)"""
     sys.path.insert(0, ROOT)
@@ -106,6 +170,7 @@ def _body():
             for a, c in zip(host, dev):
                 assert np.array_equal(a["k_opt"], c["k_opt"]) and a["feasible"] == c["feasible"] and a["iterations"] == c["iterations"] and len(a["k_opt"]) == 8
             print(f"solve (8 variables): feasible {host[0]['feasible']}, {host[0]['iterations']} iterations, k_opt {np.round(host[0]['k_opt'], 4)}", flush=True)
+            _solve_comparison_on_worlds_that_iterate()
         built[name] = tabs
         nlp.close()
     for (c1, r1, k1, co1), (c2, r2, k2, co2) in zip(built["per_step"], built["time_vectorised"]):

@@ -88,6 +88,15 @@ def test_device_resident_solve_equals_the_host_driven_one(seed, O, T, B, monkeyp
         for a, c in zip(host, nlp.solve(device_qp=True)):
             assert _same_solution(a, c), (blocks, a, c)
     nlp.set_option(_lib.OPT_SOLVE_BLOCKS, 0)
+    # both builds of the kernel (ARMOUR_OPT_SOLVE_WAVES_PER_SIMD: 1 = one block per CU, 2 = two, which is otherwise chosen for large batches only):
+    # fewer rows in registers, less LDS for the staged rows, the same iterates
+    try:
+        for wps in (1, 2):
+            nlp.set_option(_lib.OPT_SOLVE_WAVES_PER_SIMD, wps)
+            for a, c in zip(host, nlp.solve(device_qp=True)):
+                assert _same_solution(a, c), ("waves per SIMD", wps, a, c)
+    finally:
+        nlp.set_option(_lib.OPT_SOLVE_WAVES_PER_SIMD, 0)
     # a batch cut into sub-batches launched back to back (round 3: what large batches with many obstacles do by themselves)
     if B > 1:
         for sub in (1, 2):
