@@ -15,6 +15,8 @@ MAXJ = 9                    # ARMOUR_MAX_JOINTS
 MAXF = 8 if KEY128 else 7   # ARMOUR_MAX_FACTORS (checked against armour_abi_max_factors() of the library that was loaded)
 
 OK, EINVAL, EDEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4
+ROADMAP_KNN_MAX = 64         # ARMOUR_ROADMAP_KNN_MAX
+ROADMAP_KNN_MANY = 2048      # ARMOUR_ROADMAP_KNN_MANY: from this many queries on the search takes a lane per query
 
 
 class ArmourRobot(C.Structure):
@@ -152,6 +154,7 @@ EXPORTS = [
     "armour_self_pairs_default", "armour_self_check", "armour_self_check_host", "armour_self_edges_host", "armour_roadmap_check_self",
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
     "armour_roadmap_field", "armour_roadmap_descend",
+    "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
 ]
 
 _lib = None
@@ -284,6 +287,12 @@ def load():
     L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
     L.armour_roadmap_field.argtypes = [vp, dp, C.c_int32, dp, ip, ip, ip, dp]
     L.armour_roadmap_descend.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, dp, ip, dp]
+    L.armour_roadmap_create_host.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, C.c_int32, ip, u8p, C.c_double, C.POINTER(vp)]
+    knn = [vp, C.c_int32, dp, ip, ip, C.c_int32, C.c_double, ip, dp, ip, dp]
+    L.armour_roadmap_knn.argtypes = knn
+    L.armour_roadmap_knn_host.argtypes = knn
+    L.armour_roadmap_connect_batch.argtypes = [vp, C.c_int32, ip, dp, dp, C.c_int32, ip, dp, u8p, ip, u8p, dp]
+    L.armour_roadmap_descend_batch.argtypes = [vp, C.c_int32, ip, dp, C.c_int32, C.c_int32, ip, ip, u8p, dp]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

@@ -62,14 +62,7 @@ __global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int
 
 namespace rmhost {
 
-double wrapped_distance(const RmRobot& rb, const double* a, const double* b) {
-    double acc = 0.0;
-    for (int j = 0; j < rb.n; j++) {
-        const double d = rb.cont[j] ? wrap_diff(a[j], b[j]) : b[j] - a[j];
-        acc += d * d;
-    }
-    return std::sqrt(acc);
-}
+double wrapped_distance(const RmRobot& rb, const double* a, const double* b) { return wrapped_norm(rb, a, b); }
 
 bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b) {
     const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
@@ -114,8 +107,9 @@ void connect(const ArmourRoadmap* rm, const WorldView& v, const double* q, int32
 
 using rmhost::wrapped_distance;
 
-extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
-                                     const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
+// armour_roadmap_create and armour_roadmap_create_host (on_device = false: the host half alone, device -1)
+static int create_roadmap(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges, const uint8_t* continuous, double edge_step,
+                          bool on_device, int32_t device, ArmourRoadmap** out) {
     if (!robot || !out || (N > 0 && !nodes) || (E > 0 && !edges)) { armour_set_error("armour_roadmap_create: null argument"); return ARMOUR_EINVAL; }
     *out = nullptr;
     ARMOUR_TRY(armour_check_robot_shape("armour_roadmap_create", robot));
@@ -149,6 +143,10 @@ extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const 
     std::vector<int32_t> sample_edge((size_t)rm->M);
     for (int e = 0; e < E; e++)
         for (int64_t k = off[e]; k < off[e + 1]; k++) sample_edge[(size_t)k] = e;
+    if (!on_device) {
+        *out = guard.release();
+        return ARMOUR_OK;
+    }
     HIPCHK(hipSetDevice(device));
     ARMOUR_TRY(rm->stream.create());
     ARMOUR_TRY(rm->d_nodes.upload(rm->nodes.data(), rm->nodes.size(), rm->stream));
@@ -160,9 +158,19 @@ extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const 
     return ARMOUR_OK;
 }
 
+extern "C" int armour_roadmap_create(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
+                                     const uint8_t* continuous, double edge_step, int32_t device, ArmourRoadmap** out) {
+    return create_roadmap(robot, N, nodes, E, edges, continuous, edge_step, true, device, out);
+}
+
+extern "C" int armour_roadmap_create_host(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
+                                          const uint8_t* continuous, double edge_step, ArmourRoadmap** out) {
+    return create_roadmap(robot, N, nodes, E, edges, continuous, edge_step, false, -1, out);
+}
+
 extern "C" void armour_roadmap_destroy(ArmourRoadmap* rm) {
     if (!rm) return;
-    (void)hipSetDevice(rm->device);
+    if (rm->device >= 0) (void)hipSetDevice(rm->device);
     delete rm;
 }
 

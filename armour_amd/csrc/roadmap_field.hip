@@ -198,6 +198,25 @@ extern "C" int armour_roadmap_field(ArmourRoadmap* rm, const double* goals, int3
     return ARMOUR_OK;
 }
 
+int rmhost::descend_walk(const char* who, int32_t N, int32_t w, const double* cost, const int32_t* next, const std::vector<std::pair<double, int>>& joined,
+                         std::vector<int>* seq, double* total) {
+    seq->clear();
+    *total = INFINITY;
+    int first = -1;
+    for (const auto& c : joined) {
+        const double sum = c.first + cost[c.second];
+        if (sum < *total) { *total = sum; first = c.second; }
+    }
+    if (first < 0) return ARMOUR_OK;
+    seq->push_back(first);
+    for (int v = first; next[v] != ARMOUR_ROADMAP_NEXT_GOAL;) {
+        v = next[v];
+        if (v < 0 || v >= N || (int64_t)seq->size() > (int64_t)N + 1) { armour_set_error("%s: the successors of world %d do not lead to the goal", who, w); return ARMOUR_ESTATE; }
+        seq->push_back(v);
+    }
+    return ARMOUR_OK;
+}
+
 extern "C" int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double* q_start, int32_t connect_k, int32_t max_points, double* path,
                                       int32_t* points, double* length) {
     if (!rm || !q_start || !points || max_points < 0 || (max_points > 0 && !path) || connect_k < 0) {
@@ -222,19 +241,8 @@ extern "C" int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double
     } else {
         std::vector<std::pair<double, int>> joined;
         rmhost::connect(rm, view, q_start, connect_k, &joined);
-        total = INFINITY;
-        int first = -1;
-        for (const auto& c : joined) {
-            const double sum = c.first + cost[c.second];
-            if (sum < total) { total = sum; first = c.second; }
-        }
-        if (first < 0) return ARMOUR_OK;   // *points = 0: no path
-        seq.push_back(first);
-        for (int v = first; next[v] != ARMOUR_ROADMAP_NEXT_GOAL;) {
-            v = next[v];
-            if (v < 0 || v >= N || (int64_t)seq.size() > (int64_t)N + 1) { armour_set_error("armour_roadmap_descend: the successors of world %d do not lead to the goal", w); return ARMOUR_ESTATE; }
-            seq.push_back(v);
-        }
+        ARMOUR_TRY(rmhost::descend_walk("armour_roadmap_descend", N, w, cost, next, joined, &seq, &total));
+        if (seq.empty()) return ARMOUR_OK;   // *points = 0: no path
     }
     *points = (int32_t)seq.size() + 2;
     if (length) *length = total;

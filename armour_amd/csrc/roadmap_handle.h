@@ -30,10 +30,25 @@ __host__ __device__ inline void edge_sample(const RmRobot& rb, const double* a, 
     }
 }
 
+// The roadmap's wrapped distance a -> b, its one copy: D_j joint by joint in index order (wrapped on continuous joints), acc += D_j * D_j
+// from 0 (wrapped_sq), then one square root.  Written over all ARMOUR_MAX_FACTORS joints with a select so that a lane whose a is an array
+// of its own keeps it in registers; the operations and their order are those of the loop over rb.n joints.
+__host__ __device__ inline double wrapped_sq(const RmRobot& rb, const double* a, const double* b) {
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) {
+        const double aj = j < rb.n ? a[j] : 0.0, bj = j < rb.n ? b[j] : 0.0;
+        const double d = rb.cont[j] ? wrap_diff(aj, bj) : bj - aj;
+        acc = j < rb.n ? acc + d * d : acc;
+    }
+    return acc;
+}
+__host__ __device__ inline double wrapped_norm(const RmRobot& rb, const double* a, const double* b) { return sqrt(wrapped_sq(rb, a, b)); }
+
 }  // namespace rmgeo
 
 struct ArmourRoadmap {
-    int device = 0;
+    int device = 0;                      // < 0: a handle of armour_roadmap_create_host (no stream, no device buffers)
     rmgeo::RmRobot rb;
     int32_t N = 0, E = 0;
     int64_t M = 0;
@@ -64,6 +79,10 @@ struct ArmourRoadmap {
     bool field_valid = false;
     std::vector<double> field_goals, field_cost;   // [W][n], [W][N]
     std::vector<int32_t> field_next;                // [W][N]
+    // the nearest-neighbour search and the batched joins (roadmap_knn.hip): queries in, partial lists, results out
+    DevBuf<double> d_kq, d_kdist, d_pdist, d_ktarget, d_self_shrink;
+    DevBuf<int32_t> d_kmask, d_kexcl, d_kidx, d_kcount, d_pidx, d_pcount;
+    DevBuf<uint8_t> d_self_node_free, d_self_on, d_kok;
 };
 
 // ---- what armour_roadmap_plan (roadmap.hip) and the field entries (roadmap_field.hip) share; defined in roadmap.hip
@@ -84,6 +103,13 @@ void world_view(const ArmourRoadmap* rm, int32_t w, WorldView* v);
 // q's connect_k nearest free nodes by wrapped_distance(q, node) (ties: the smaller index), in that order, those whose connecting edge is free:
 // (distance, node)
 void connect(const ArmourRoadmap* rm, const WorldView& v, const double* q, int32_t connect_k, std::vector<std::pair<double, int>>* out);
+
+// armour_roadmap_descend's choice and walk (roadmap_field.hip), shared with armour_roadmap_descend_batch: among `joined` ((distance, node) in
+// nearest order, edges free) the node of the smallest fl(distance + cost), first on a tie, then next[] to the goal.  cost / next: world w's
+// rows of the field.  seq is cleared and filled with the nodes (empty: no path, *total = +inf).  ARMOUR_ESTATE when the successors do not
+// lead to the goal within N + 1 steps.
+int descend_walk(const char* who, int32_t N, int32_t w, const double* cost, const int32_t* next, const std::vector<std::pair<double, int>>& joined,
+                 std::vector<int>* seq, double* total);
 
 }  // namespace rmhost
 

@@ -11,6 +11,9 @@ configurations + an adjacency list in, node feasibility / link_c / the collision
     f = rm.field(goals)                     # [W,n] -> every world's cost-to-go cost [W,N] and successors next [W,N], one launch
     path, length = rm.descend(w, q_start)   # host, no search: nearest nodes + the successor pointers
     res = run_trials(worlds, hlp=field_hlps(rm, worlds))    # the roadmap as the trials' high-level planner
+    index, dist, count = rm.knn(queries, k=8)               # [Q,n] -> each query's k nearest nodes in the order (distance, index), one call
+    rm = Roadmap(robot, *device_roadmap(robot, 200000, 0.3, 16, 0, lb, ub, cont), continuous=cont)    # the edges by that search
+    paths = rm.descend_many(worlds, starts)                 # descend() for Q queries with one device call
 
 The node and edge rules (exact node test, conservative edge test with enlarged boxes) are stated in include/armour_hip.h and DESIGN.md.
 """
@@ -67,7 +70,8 @@ def uniform_roadmap(N, radius, k_max, seed, lb, ub, continuous):
 class Roadmap:
     """A roadmap on one device: nodes [N,n], edges [E,2], the edge rule's step (radians per sub-segment)."""
 
-    def __init__(self, robot, nodes, edges, continuous=None, edge_step=0.05, device=0):
+    def __init__(self, robot, nodes, edges, continuous=None, edge_step=0.05, device=0, host=False):
+        """host=True: a handle that holds nothing on a device (armour_roadmap_create_host); it serves knn(host=True) and nothing else."""
         self.L = _lib.load()
         self.robot = robot
         self.n = robot.num_factors
@@ -77,9 +81,9 @@ class Roadmap:
             else np.ascontiguousarray(continuous, dtype=np.uint8).reshape(self.n)
         self.edge_step = float(edge_step)
         h = C.c_void_p()
-        check(self.L.armour_roadmap_create(C.byref(robot), self.nodes.shape[0], _dp(self.nodes), self.edges.shape[0],
-                                           self.edges.ctypes.data_as(C.POINTER(C.c_int32)),
-                                           self.continuous.ctypes.data_as(C.POINTER(C.c_uint8)), self.edge_step, device, C.byref(h)))
+        args = (C.byref(robot), self.nodes.shape[0], _dp(self.nodes), self.edges.shape[0], self.edges.ctypes.data_as(C.POINTER(C.c_int32)),
+                self.continuous.ctypes.data_as(C.POINTER(C.c_uint8)), self.edge_step)
+        check(self.L.armour_roadmap_create_host(*args, C.byref(h)) if host else self.L.armour_roadmap_create(*args, device, C.byref(h)))
         self.h = h
         N, E, M = C.c_int32(), C.c_int32(), C.c_int64()
         check(self.L.armour_roadmap_get_sizes(self.h, C.byref(N), C.byref(E), C.byref(M)))
@@ -180,6 +184,101 @@ class Roadmap:
         return (path[:pts.value].copy() if pts.value else None), length.value
 
 
+    def knn(self, queries, k, radius=np.inf, worlds=None, exclude=None, host=False):
+        """queries [Q,n] -> (index [Q,k] int32, dist [Q,k], count [Q]): each query's first k candidates in the order (wrapped distance, node
+        index); the slots past count[i] hold -1 / inf.  Candidates: nodes within `radius`, other than node exclude[i] (exclude [Q], -1: none),
+        and free in world worlds[i] of the last check ([Q]; -1 or worlds=None: every node; with use_self on, free in the self mask too).
+        host=True: the same rule in the library's host loop.  The rule is stated in include/armour_hip.h."""
+        q = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, self.n)
+        Q, k = q.shape[0], int(k)
+        i32 = C.POINTER(C.c_int32)
+        opt = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32), (Q,)))
+        w, ex = opt(worlds), opt(exclude)
+        slots = max(k, 0)
+        index, dist, count = np.full((Q, slots), -1, dtype=np.int32), np.full((Q, slots), np.inf), np.zeros(Q, dtype=np.int32)
+        ms = C.c_double()
+        fn = self.L.armour_roadmap_knn_host if host else self.L.armour_roadmap_knn
+        check(fn(self.h, Q, _dp(q), None if w is None else w.ctypes.data_as(i32), None if ex is None else ex.ctypes.data_as(i32), k, float(radius),
+                 index.ctypes.data_as(i32), _dp(dist), count.ctypes.data_as(i32), C.byref(ms)))
+        self.knn_ms = ms.value
+        return index, dist, count
+
+    def connect_many(self, worlds, starts, targets=None, connect_k=8):
+        """starts [Q,n] in the worlds `worlds` [Q] of the last check -> dict node [Q,connect_k] (each start's nearest free nodes, -1 padded),
+        dist [Q,connect_k], edge_ok [Q,connect_k] bool (the edge start -> node is free by the edge rule), count [Q], ms, and with targets
+        [Q,n] direct [Q] bool (the edge start -> target is free): what plan / field / descend compute to join a point, for Q points in one
+        device call."""
+        q = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, self.n)
+        Q, k = q.shape[0], int(connect_k)
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(worlds, dtype=np.int32), (Q,)))
+        tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.float64).reshape(Q, self.n)
+        slots = max(k, 0)
+        node, dist = np.full((Q, slots), -1, dtype=np.int32), np.full((Q, slots), np.inf)
+        ok, count, direct = np.zeros((Q, slots), dtype=np.uint8), np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.uint8)
+        ms = C.c_double()
+        i32, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        check(self.L.armour_roadmap_connect_batch(self.h, Q, w.ctypes.data_as(i32), _dp(q), _dp(tg), k, node.ctypes.data_as(i32), _dp(dist), ok.ctypes.data_as(u8),
+                                                  count.ctypes.data_as(i32), direct.ctypes.data_as(u8), C.byref(ms)))
+        out = dict(node=node, dist=dist, edge_ok=ok.astype(bool), count=count, ms=ms.value)
+        if tg is not None:
+            out["direct"] = direct.astype(bool)
+        return out
+
+    def descend_many(self, worlds, starts, connect_k=8, seq_capacity=None):
+        """descend() for Q queries with one device call: worlds [Q], starts [Q,n] -> [(path [P,n] | None, length)] as descend returns them."""
+        q = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, self.n)
+        Q = q.shape[0]
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(worlds, dtype=np.int32), (Q,)))
+        cap = Q * 64 if seq_capacity is None else int(seq_capacity)
+        i32 = C.POINTER(C.c_int32)
+        while True:
+            off, seq = np.zeros(Q + 1, dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)
+            status, length = np.zeros(Q, dtype=np.uint8), np.full(Q, np.inf)
+            rc = self.L.armour_roadmap_descend_batch(self.h, Q, w.ctypes.data_as(i32), _dp(q), int(connect_k), cap, off.ctypes.data_as(i32), seq.ctypes.data_as(i32),
+                                                     status.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(length))
+            if rc == _lib.ECAPACITY and seq_capacity is None and off[Q] > cap:
+                cap = int(off[Q])          # seq_off is complete on ECAPACITY: once more with the room it names
+                continue
+            check(rc)
+            break
+        out = []
+        for i in range(Q):
+            if status[i] == 0:
+                out.append((None, float(length[i])))
+            else:
+                goal = self.field_goals[w[i]]
+                out.append((np.vstack([q[i], self.nodes[seq[off[i]:off[i + 1]]], goal]), float(length[i])))
+        return out
+
+
+def device_roadmap(robot, N, radius, k_max, seed, lb, ub, continuous, device=0):
+    """uniform_roadmap with the neighbour search on the device: the same seeded nodes, and the edges from ONE self-query of an edge-less
+    handle (every node's k_max nearest other nodes within `radius`), their union sorted and deduplicated with i < j.  Returns (nodes, edges)
+    as uniform_roadmap does, so Roadmap(robot, *device_roadmap(...)) reads like today's call."""
+    cont = np.asarray(continuous, dtype=bool)
+    lo = np.where(cont, -np.pi, np.asarray(lb, dtype=np.float64))
+    hi = np.where(cont, np.pi, np.asarray(ub, dtype=np.float64))
+    nodes = lo + (hi - lo) * np.random.default_rng(seed).random((int(N), cont.size))
+    k = min(int(k_max), _lib.ROADMAP_KNN_MAX)
+    if k < int(k_max) and int(N) - 1 > k:
+        raise ValueError(f"device_roadmap: k_max = {k_max} above the search's {_lib.ROADMAP_KNN_MAX}")
+    if int(N) < 2 or k <= 0:
+        return nodes, np.zeros((0, 2), dtype=np.int32)
+    bare = Roadmap(robot, nodes, np.zeros((0, 2), dtype=np.int32), continuous=cont.astype(np.uint8), device=device)
+    try:
+        index, _, _ = bare.knn(nodes, k, radius=radius, exclude=np.arange(int(N), dtype=np.int32))
+    finally:
+        bare.close()
+    rows = np.repeat(np.arange(int(N), dtype=np.int32), k)
+    cols = index.ravel()
+    keep = cols >= 0
+    e = np.sort(np.stack([rows[keep], cols[keep]], axis=1), axis=1)
+    if not e.shape[0]:
+        return nodes, np.zeros((0, 2), dtype=np.int32)
+    e = np.unique(e, axis=0)
+    return nodes, np.ascontiguousarray(e, dtype=np.int32)
+
+
 def waypoint_along(path, q_cur, lookahead, continuous):
     """The point at arc length `lookahead` from q_cur along the polyline q_cur -> path[1] -> ... (segments wrapped on continuous joints),
     continued along the last segment past the goal (no clipping, as robot_arm_straight_line_HLP.get_waypoint)."""
@@ -233,13 +332,27 @@ class RoadmapFieldHLP:
         return waypoint_along(self.path, q_cur, lookahead, self.roadmap.continuous.astype(bool))
 
 
-def field_hlps(roadmap, worlds, connect_k=8):
+def field_hlps(roadmap, worlds, connect_k=8, batched=False):
     """`worlds` as trials.run_trials takes them ([(name, problem)]): checks the roadmap against all of them in one launch (obstacles padded
     to one count), computes every world's field towards its goal in one call, and returns the factory (i, world) -> RoadmapFieldHLP that
-    run_trials(hlp=...) accepts.  The roadmap serves these worlds until its next check."""
+    run_trials(hlp=...) accepts.  The roadmap serves these worlds until its next check.  batched=True: the factory also carries
+    get_waypoints(indices, qs, lookaheads) -> the waypoints of those worlds from ONE descend_many, which run_trials calls once per iteration
+    in place of a get_waypoint per world (the same waypoints)."""
     probs = [p for _, p in worlds]
     obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
     O = max([o.shape[0] for o in obs] + [1])
     roadmap.check(np.stack([pad_obstacles(o, O) for o in obs]))
     roadmap.field(np.stack([np.asarray(p["goal"], dtype=np.float64) for p in probs]), connect_k=connect_k)
-    return lambda i, world: RoadmapFieldHLP(roadmap, i, connect_k=connect_k)
+
+    def make(i, world):
+        return RoadmapFieldHLP(roadmap, i, connect_k=connect_k)
+
+    def get_waypoints(indices, qs, lookaheads):
+        cont = roadmap.continuous.astype(bool)
+        paths = roadmap.descend_many(indices, qs, connect_k=connect_k)
+        return [straight_line_waypoint(q, roadmap.field_goals[i], la) if path is None else waypoint_along(path, q, la, cont)
+                for i, q, la, (path, _) in zip(indices, qs, lookaheads, paths)]
+
+    if batched:
+        make.get_waypoints = get_waypoints
+    return make

@@ -111,7 +111,9 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
                backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0, self_check=None, self_pairs=None, self_shrink=None):
     """Run every world of `worlds` ([(name, problem)] as scenes.reference_worlds() gives them; a problem holds q0 = the start at rest, goal,
     obstacles [O, 12] and lookahead) to its end.  hlp: "straight" or a factory (world index, world record) -> object with
-    get_waypoint(q_cur, lookahead) (e.g. a RoadmapHLP; None = no waypoint: the goal is used).  tube: None or "ultimate_bound" (every joint's
+    get_waypoint(q_cur, lookahead) (e.g. a RoadmapHLP; None = no waypoint: the goal is used); a factory that also has
+    get_waypoints(indices, qs, lookaheads) -> list is asked once per iteration for all live worlds instead.  batches[] records hlp_ms, the
+    wall time of an iteration's waypoint queries.  tube: None or "ultimate_bound" (every joint's
     radius = the controller's ultimate position bound, tracking.ultimate_bound) or an [n] array: the radius the audit takes about each
     executed piece.  tracked: also execute every piece with armour_track on `track_samples` sampled plants per world (slow; opt-in).
     backend: an object with plan(), robot, k_range, duration, t_plan (default: DevicePlanner).  rescue_candidates > 0 (default 0: today's path):
@@ -143,6 +145,7 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
     else:
         tube_e = None if tube is None else np.broadcast_to(np.asarray(tube, dtype=np.float64), (n,)).copy()
     hlps = [StraightLineHLP(w["goal"]) if hlp == "straight" else hlp(i, w) for i, w in enumerate(ws)]
+    batch_hlp = getattr(hlp, "get_waypoints", None)      # a factory that answers all live worlds in one call (roadmap.field_hlps(batched=True))
     z = np.zeros(n)
     st = [dict(q=w["start"].copy(), qd=z.copy(), qdd=z.copy(), plan=None, at_rest=True, fails=0, outcome=None, records=[], undecided=0) for w in ws]
     if tracked:
@@ -158,14 +161,17 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
         if not live:
             break
         # 1. waypoints
-        q_des = []
-        for i in live:
-            wp = hlps[i].get_waypoint(st[i]["q"].copy(), ws[i]["lookahead"])
-            q_des.append(ws[i]["goal"].copy() if wp is None else np.asarray(wp, dtype=np.float64))
+        t_hlp = time.perf_counter()
+        if batch_hlp is not None:      # one call for all live worlds
+            wps = batch_hlp(list(live), [st[i]["q"].copy() for i in live], [ws[i]["lookahead"] for i in live])
+        else:
+            wps = [hlps[i].get_waypoint(st[i]["q"].copy(), ws[i]["lookahead"]) for i in live]
+        q_des = [ws[i]["goal"].copy() if wp is None else np.asarray(wp, dtype=np.float64) for i, wp in zip(live, wps)]
+        hlp_ms = (time.perf_counter() - t_hlp) * 1e3
         q0, qd0, qdd0, q_des = (np.stack(a) for a in ([st[i]["q"] for i in live], [st[i]["qd"] for i in live], [st[i]["qdd"] for i in live], q_des))
         # 2. one batch
         res, build_ms, solve_ms = backend.plan(q0, qd0, qdd0, q_des, obstacles[live])
-        batches.append(dict(iteration=it, live=len(live), build_ms=build_ms, solve_ms=solve_ms))
+        batches.append(dict(iteration=it, live=len(live), hlp_ms=hlp_ms, build_ms=build_ms, solve_ms=solve_ms))
         # 3 / 4. what every world executes: (plan q0, qd0, qdd0, k, ta, tb) and its next state
         pieces = []
         for b, i in enumerate(live):

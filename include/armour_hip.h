@@ -662,6 +662,52 @@ int armour_roadmap_field(ArmourRoadmap* rm, const double* goals, int32_t connect
 int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double* q_start, int32_t connect_k, int32_t max_points,
                            double* path, int32_t* points, double* length);
 
+/* Nearest-neighbour search over the handle's nodes (roadmap_knn.hip): Q queries in one call, brute force on the device.
+ *
+ * Distance of a query q and a node x: the roadmap's wrapped distance.  Joint by joint in index order, D_j = the wrapped difference of
+ *   the edge rule on continuous joints and x_j - q_j otherwise; acc += D_j * D_j from 0; d = sqrt(acc).  fp64, no fused multiply-add.
+ * Candidates of query i: the nodes v with
+ *   mask_row[i] < 0 (or mask_row == NULL), or v free in world mask_row[i] of the last armour_roadmap_check -- node_free[w][v], ANDed
+ *     with the self mask self_node_free[v] when armour_roadmap_use_self is on (what the search entries take as free);
+ *   v != exclude[i] (exclude may be NULL; an entry that names no node, e.g. -1, excludes nothing);
+ *   d <= radius (radius = +inf: no limit).
+ * Result of query i: the first min(k, #candidates) candidates in the TOTAL order (d, v) ascending -- distance first, then the smaller
+ *   index: index[i][0..count[i]), dist[i][..], the rest of the k slots padded with -1 / +inf.  A total order makes the result unique,
+ *   so it does not depend on how the nodes are dealt to lanes, waves and blocks or on the order partial lists are merged in: the device
+ *   and the host entry return the same bits.  It is the order armour_roadmap_plan / _field / _descend join a start or goal by
+ *   (std::partial_sort of (distance, index) over the free nodes).
+ * Arguments: 1 <= k <= ARMOUR_ROADMAP_KNN_MAX, else ARMOUR_EINVAL; Q < 0, a non-finite query, a negative or NaN radius: ARMOUR_EINVAL.
+ *   Q = 0 or N = 0: ARMOUR_OK, nothing written.  A mask_row entry >= 0 before a check (or, with the self masks on, before a self
+ *   check) is ARMOUR_ESTATE, one >= W ARMOUR_EINVAL.  *ms (may be NULL): device time of the launches.
+ * Device: Q >= ARMOUR_ROADMAP_KNN_MANY queries take one lane per query (the nodes cut into up to 16 slices when the queries alone do
+ *   not fill the device); fewer take one block per (query, 256 nodes).  Every shape writes sorted partial lists and a second launch
+ *   merges them by rank.  DESIGN.md 4.12b.
+ * armour_roadmap_knn_host is the same rule in a host loop and touches no device; a handle of armour_roadmap_create_host serves it
+ * (and nothing that needs the device: those entries return ARMOUR_EDEVICE on it). */
+#define ARMOUR_ROADMAP_KNN_MAX 64
+#define ARMOUR_ROADMAP_KNN_MANY 2048
+int armour_roadmap_create_host(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,
+                               const uint8_t* continuous, double edge_step, ArmourRoadmap** out);
+int armour_roadmap_knn(ArmourRoadmap* rm, int32_t Q, const double* queries, const int32_t* mask_row, const int32_t* exclude,
+                       int32_t k, double radius, int32_t* index, double* dist, int32_t* count, double* ms);
+int armour_roadmap_knn_host(ArmourRoadmap* rm, int32_t Q, const double* queries, const int32_t* mask_row, const int32_t* exclude,
+                            int32_t k, double radius, int32_t* index, double* dist, int32_t* count, double* ms);
+/* Q queries joined to the graph in one call: for query i the connect_k (0..ARMOUR_ROADMAP_KNN_MAX) nearest free nodes of world
+ * world[i] by the search above (node / dist [Q][connect_k], -1 / +inf padded, count [Q]) and, on the device in the same call, the edge
+ * rule q[i] -> node for each (edge_ok [Q][connect_k], 0 in the padding) and, with target ([Q][n], may be NULL), q[i] -> target[i]
+ * (direct [Q]).  With the self masks on an edge must pass the self edge rule too, as everywhere.  This is what the search entries
+ * compute when they join a start or a goal, before they drop the nodes whose edge is not free.  State rules: armour_roadmap_plan's. */
+int armour_roadmap_connect_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* world, const double* q, const double* target,
+                                 int32_t connect_k, int32_t* node, double* dist, uint8_t* edge_ok, int32_t* count, uint8_t* direct,
+                                 double* ms);
+/* armour_roadmap_descend for Q queries (world[i], q_start[i]) with ONE armour_roadmap_connect_batch call (target = each world's field
+ * goal); the choice among the joined nodes and the walk along next[] are armour_roadmap_descend's own code.  status[i]: 0 no path,
+ * 1 the direct edge, 2 through the nodes seq[seq_off[i] .. seq_off[i + 1]) (node indices; the path is start, those nodes, the goal);
+ * length[i] as armour_roadmap_descend (may be NULL).  seq_off [Q + 1] is always complete: ARMOUR_ECAPACITY when seq_off[Q] exceeds
+ * seq_capacity (then seq is not written).  State and argument rules: armour_roadmap_descend's, connect_k <= ARMOUR_ROADMAP_KNN_MAX. */
+int armour_roadmap_descend_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* world, const double* q_start, int32_t connect_k,
+                                 int32_t seq_capacity, int32_t* seq_off, int32_t* seq, uint8_t* status, double* length);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

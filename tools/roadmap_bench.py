@@ -14,7 +14,15 @@ median host time of armour_roadmap_plan between random free start / goal nodes o
 uploads, the launch, the copy of cost and next back, and the wrapper's output arrays), sweeps, the share of nodes reached -- and the host
 median of armour_roadmap_descend over the same 20 start / goal pairs plan_ms is taken on, in the same run (one field per pair's goal, then
 the timed descend).  break_even_queries = field call_ms per world / (plan_ms - descend_ms): the queries per world after which the field has
-paid for itself, by the whole call (null when descend is not faster); break_even_queries_kernel counts the launch alone.  With --out the line is also written to that file (profiles/roadmap_field_bench.json holds a run on the MI355X)."""
+paid for itself, by the whole call (null when descend is not faster); break_even_queries_kernel counts the launch alone.  With --out the line is also written to that file (profiles/roadmap_field_bench.json holds a run on the MI355X).
+
+--knn measures the nearest-neighbour search instead (armour_roadmap_knn and what is built on it) and writes profiles/roadmap_knn_bench.json
+(or --out): `build` -- roadmap.device_roadmap against roadmap.uniform_roadmap at --nodes (radius --graph-radius, --k-max), wall ms of
+each, the search's device ms, and whether the edges are equal; `build_large` -- device_roadmap alone at --large-nodes; `descend` --
+Roadmap.descend_many for the reference worlds (one start per world, --reps calls after a warm-up, median wall ms) against the loop of
+Roadmap.descend over the same starts, and the search alone at that shape (Roadmap.knn, device ms); `trial` -- trials.run_trials on the
+reference worlds for --trial-iterations iterations under field_hlps with and without batched: hlp / build / solve / audit ms per batch
+iteration (mean) and the first iteration's (all worlds live)."""
 import argparse
 import json
 import os
@@ -95,6 +103,64 @@ def measure(robot, nodes, edges, cont, obs, goals, edge_step, reps):
     return out
 
 
+def measure_knn(robot, cont, lb, ub, worlds, obs, goals, a):
+    from armour_amd.roadmap import Roadmap, device_roadmap, field_hlps, uniform_roadmap
+    from armour_amd.trials import run_trials
+    res = {}
+    wall = lambda f: (lambda t0, r: (r, (time.perf_counter() - t0) * 1e3))(time.perf_counter(), f())
+    # the build: device against host at --nodes, device alone at --large-nodes
+    device_roadmap(robot, 2048, a.graph_radius, a.k_max, 1, lb, ub, cont)                      # warm-up (module load)
+    (n1, e1), dev_ms = wall(lambda: device_roadmap(robot, a.nodes, a.graph_radius, a.k_max, 0, lb, ub, cont))
+    (n0, e0), host_ms = wall(lambda: uniform_roadmap(a.nodes, a.graph_radius, a.k_max, 0, lb, ub, cont))
+    bare = Roadmap(robot, n1, np.zeros((0, 2), dtype=np.int32), continuous=cont.astype(np.uint8))
+    ex = np.arange(a.nodes, dtype=np.int32)
+    search = []
+    for _ in range(a.reps):
+        bare.knn(n1, a.k_max, radius=a.graph_radius, exclude=ex)
+        search.append(bare.knn_ms)
+    bare.close()
+    res["build"] = dict(N=a.nodes, radius=a.graph_radius, k_max=a.k_max, E=int(e1.shape[0]), device_wall_ms=round(dev_ms, 2), host_wall_ms=round(host_ms, 2),
+                        search_device_ms=round(float(np.median(search)), 3), same_edges=bool(np.array_equal(e0, e1) and np.array_equal(n0, n1)))
+    (n2, e2), large_ms = wall(lambda: device_roadmap(robot, a.large_nodes, a.radius, a.k_max, 0, lb, ub, cont))
+    bare = Roadmap(robot, n2, np.zeros((0, 2), dtype=np.int32), continuous=cont.astype(np.uint8))
+    bare.knn(n2, a.k_max, radius=a.radius, exclude=np.arange(a.large_nodes, dtype=np.int32))
+    res["build_large"] = dict(N=a.large_nodes, radius=a.radius, k_max=a.k_max, E=int(e2.shape[0]), device_wall_ms=round(large_ms, 2), search_device_ms=round(bare.knn_ms, 3))
+    bare.close()
+    # descend: one start per world, batched against the loop
+    rm = Roadmap(robot, n1, e1, continuous=cont.astype(np.uint8), edge_step=a.edge_step)
+    W = obs.shape[0]
+    rm.check(obs)
+    rm.field(goals)
+    starts = np.stack([np.asarray(p["q0"], dtype=np.float64) for _, p in worlds])
+    idx = np.arange(W, dtype=np.int32)
+    rm.descend_many(idx, starts)
+    many, loop, knn_ms, join_ms = [], [], [], []
+    for _ in range(a.reps):
+        got, ms = wall(lambda: rm.descend_many(idx, starts))
+        many.append(ms)
+        ref, ms = wall(lambda: [rm.descend(int(w), starts[w]) for w in idx])
+        loop.append(ms)
+        rm.knn(starts, 8, worlds=idx)
+        knn_ms.append(rm.knn_ms)
+        join_ms.append(rm.connect_many(idx, starts, targets=goals)["ms"])
+    same = all((p is None and r is None) or (p is not None and r is not None and np.array_equal(p, r)) for (p, _), (r, _) in zip(got, ref))
+    res["descend"] = dict(Q=W, N=rm.N, E=rm.E, descend_many_wall_ms=round(float(np.median(many)), 3), descend_loop_wall_ms=round(float(np.median(loop)), 3),
+                          knn_device_ms=round(float(np.median(knn_ms)), 4), connect_batch_device_ms=round(float(np.median(join_ms)), 4),
+                          paths=sum(1 for p, _ in got if p is not None), same_paths=bool(same))
+    # a trial's iterations under both factories
+    res["trial"] = {}
+    for batched in (False, True):
+        make = field_hlps(rm, worlds, batched=batched)
+        out = run_trials(worlds, hlp=make, T=a.T, max_iterations=a.trial_iterations)
+        bt = out["batches"]
+        res["trial"]["batched" if batched else "loop"] = dict(
+            batches=len(bt), first_batch={k: round(float(v), 3) for k, v in bt[0].items()},
+            **{key + "_mean": round(float(np.mean([b[key] for b in bt])), 3) for key in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")},
+            hlp_ms_per_live_world=round(float(sum(b["hlp_ms"] for b in bt) / sum(b["live"] for b in bt)), 4))
+    rm.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=20000)
@@ -104,6 +170,10 @@ def main():
     ap.add_argument("--edge-step", type=float, default=0.05)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out")
+    ap.add_argument("--knn", action="store_true")
+    ap.add_argument("--large-nodes", type=int, default=200000)
+    ap.add_argument("--trial-iterations", type=int, default=20)
+    ap.add_argument("--T", type=int, default=128)
     a = ap.parse_args()
     from armour_amd.planner import kinova_robot
     from armour_amd.roadmap import uniform_roadmap
@@ -116,7 +186,10 @@ def main():
     obs = np.ascontiguousarray(as_batch(worlds)["obstacles"])
     goals = np.stack([np.asarray(p["goal"], dtype=np.float64) for _, p in worlds])
     res = dict(tool="roadmap_bench", robot="kinova_gen3_no_gripper", worlds=obs.shape[0], edge_step=a.edge_step)
-    for key, radius in (("radius_%g" % a.radius, a.radius), ("radius_%g" % a.graph_radius, a.graph_radius)):
+    if a.knn:
+        res.update(mode="knn", **measure_knn(robot, cont, lb, ub, worlds, obs, goals, a))
+        a.out = a.out or os.path.join(ROOT, "profiles", "roadmap_knn_bench.json")
+    for key, radius in [] if a.knn else (("radius_%g" % a.radius, a.radius), ("radius_%g" % a.graph_radius, a.graph_radius)):
         nodes, edges = uniform_roadmap(a.nodes, radius, a.k_max, 0, lb, ub, cont)
         res[key] = measure(robot, nodes, edges, cont.astype(np.uint8), obs, goals, a.edge_step, a.reps)
     if a.out:

@@ -1,7 +1,7 @@
 """Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
 and prints ONE JSON line.
 
-    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field]
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]]
 
 * the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
   executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
@@ -9,7 +9,9 @@ and prints ONE JSON line.
   kernel ms = the median `ms` of armour_path_audit over --reps launches, verdict mode and clearance mode;
 * --hlp roadmap-field: the same worlds once more with the roadmap's cost-to-go fields as the high-level planner (armour_amd.roadmap.field_hlps
   on uniform_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0)): `hlp_outcomes` holds the outcome counts under both HLPs, the roadmap run's
-  check / field ms and the worlds whose outcome differs.  Everything else in the file is the straight-line run's, as before;
+  check / field ms, the worlds whose outcome differs and `ms_per_batch` (the waypoint queries' hlp_ms next to build, solve and audit ms);
+  with --batched the waypoints of an iteration come from one Roadmap.descend_many call.  Everything else in the file is the straight-line
+  run's, as before;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -82,13 +84,15 @@ def roadmap_field_trials(robot, ws, straight, a):
     nodes, edges = uniform_roadmap(a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
     rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
     t0 = time.perf_counter()
-    make = field_hlps(rm, ws)
+    make = field_hlps(rm, ws, batched=a.batched)
     setup_ms = (time.perf_counter() - t0) * 1e3
     res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
     rm.close()
+    per_batch = lambda key: dict(mean=float(np.mean([b[key] for b in res["batches"]])), max=float(np.max([b[key] for b in res["batches"]])))
     count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
     return dict(roadmap=dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius, check_and_field_wall_ms=setup_ms),
-                straight=count(straight), roadmap_field=count(res), roadmap_field_summary=res["summary"],
+                straight=count(straight), roadmap_field=count(res), roadmap_field_summary=res["summary"], batched=bool(a.batched),
+                ms_per_batch={key: per_batch(key) for key in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0],
                 changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
 
 
@@ -102,6 +106,7 @@ def main():
     ap.add_argument("--hlp", choices=["straight", "roadmap-field"], default="straight")
     ap.add_argument("--roadmap-nodes", type=int, default=20000)
     ap.add_argument("--roadmap-radius", type=float, default=1.5)
+    ap.add_argument("--batched", action="store_true")
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
