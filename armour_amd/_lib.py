@@ -17,6 +17,8 @@ MAXF = 8 if KEY128 else 7   # ARMOUR_MAX_FACTORS (checked against armour_abi_max
 OK, EINVAL, EDEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4
 ROADMAP_KNN_MAX = 64         # ARMOUR_ROADMAP_KNN_MAX
 ROADMAP_KNN_MANY = 2048      # ARMOUR_ROADMAP_KNN_MANY: from this many queries on the search takes a lane per query
+TREE_NOT_FOUND, TREE_FOUND, TREE_START_BLOCKED, TREE_GOAL_BLOCKED, TREE_FULL = 0, 1, 2, 3, 4   # ARMOUR_TREE_*
+TREE_MAX_NODES, TREE_MAX_ITERATIONS = 8192, 100000   # ARMOUR_TREE_MAX_NODES, ARMOUR_TREE_MAX_ITERATIONS
 
 
 class ArmourRobot(C.Structure):
@@ -155,6 +157,7 @@ EXPORTS = [
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
     "armour_roadmap_field", "armour_roadmap_descend",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
+    "armour_tree_plan", "armour_tree_plan_host",
 ]
 
 _lib = None
@@ -293,6 +296,10 @@ def load():
     L.armour_roadmap_knn_host.argtypes = knn
     L.armour_roadmap_connect_batch.argtypes = [vp, C.c_int32, ip, dp, dp, C.c_int32, ip, dp, u8p, ip, u8p, dp]
     L.armour_roadmap_descend_batch.argtypes = [vp, C.c_int32, ip, dp, C.c_int32, C.c_int32, ip, ip, u8p, dp]
+    tree = [C.POINTER(ArmourRobot), u8p, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, C.POINTER(C.c_uint64), C.c_double, C.c_double, C.c_int32, C.c_int32,
+            C.c_int32, ip, ip, ip, dp, ip, dp, ip, dp]
+    L.armour_tree_plan.argtypes = tree            # (the last pointer: ms)
+    L.armour_tree_plan_host.argtypes = tree       # (the last pointer: margin [W])
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

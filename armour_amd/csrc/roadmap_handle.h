@@ -44,6 +44,8 @@ __host__ __device__ inline double wrapped_sq(const RmRobot& rb, const double* a,
     return acc;
 }
 __host__ __device__ inline double wrapped_norm(const RmRobot& rb, const double* a, const double* b) { return sqrt(wrapped_sq(rb, a, b)); }
+// the total order (distance, index) of the nearest-neighbour search and of the tree planner's nearest node: the smaller index on a tie
+__host__ __device__ inline bool key_less(double da, int va, double db, int vb) { return da < db || (da == db && va < vb); }
 
 }  // namespace rmgeo
 

@@ -35,8 +35,6 @@ constexpr int KT_BLOCK = 256;                 // tile and merge: four waves
 constexpr int CE_BLOCK = 256;                 // connect edges: four waves, a block per query
 constexpr int KNN_NONE = INT_MAX;             // the index of "no candidate": (inf, KNN_NONE) follows every key of a node
 
-__host__ __device__ inline bool key_less(double da, int va, double db, int vb) { return da < db || (da == db && va < vb); }
-
 // acc <= sq_bound(x) whenever sqrt(acc) <= x in fp64: sqrt is correctly rounded, so sqrt(acc) <= x gives acc <= x^2 (1 + 2^-53)^2, and
 // fl(x * x) >= x^2 (1 - 2^-53); 1e-15 is nine times 2^-53.  Below 1e-290 (x * x may have lost bits or underflowed: x < 1e-145) the bound
 // is held at 1e-290, above every such x^2.  It only spares square roots: what passes is decided by the distance itself.

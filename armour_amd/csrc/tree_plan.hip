@@ -1,0 +1,530 @@
+// Batched tree planner (include/armour_hip.h, armour_tree_plan): bidirectional RRT-Connect for W worlds in ONE launch, a block per world,
+// the whole loop inside the block.  The rule is the roadmap's, reused as it stands: the node rule (config_free), the edge rule's sub-segments
+// (edge_segments / edge_sample) and the wrapped distance (wrapped_sq); what is new here -- the counter hash, the steer and cut steps and the
+// order (distance, index) -- is written once below as __host__ __device__ code, run by the kernel's lanes and by armour_tree_plan_host's loop.
+//
+// Nothing but __syncthreads() orders the block: a tree's nodes live in global memory, written and read by this block alone; every decision
+// that steers the loop is taken from values all lanes hold alike, so the barriers are reached by all of them.  The loop is bounded by
+// max_iterations, a prefix by ARMOUR_TREE_MAX_SEGMENTS, a nearest scan and a path walk by the tree's count.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "roadmap_handle.h"
+
+using namespace rmgeo;
+
+namespace {
+
+constexpr int TP_BLOCK = 256;                 // four waves; a block is one world (its obstacles are staged in LDS)
+constexpr int TP_WAVES = TP_BLOCK / 64;
+constexpr int TP_NONE = INT_MAX;              // "no sub-segment collides" / the index of "no node"
+
+// What a world's run reads besides the robot: by value in the kernel's arguments (pointers: the device's; the host twin passes its own)
+struct TreeArgs {
+    double lb[ARMOUR_MAX_FACTORS], ub[ARMOUR_MAX_FACTORS];
+    double step, edge_step;
+    int32_t O, max_iterations, max_nodes, max_points;
+    const double *obstacles, *starts, *goals;
+    const uint64_t* seeds;
+    int32_t *status, *iterations, *points, *count, *parent;
+    double *path, *nodes;
+};
+
+// u(seed, i, j) of the header: a splitmix64 finaliser of the counter, 53 bits -> [0, 1)
+__host__ __device__ inline double tree_u(uint64_t seed, uint64_t i, uint64_t j) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (((i << 8) | j) + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1p-53;
+}
+__host__ __device__ inline double tree_sample(const TreeArgs& a, uint64_t seed, int i, int j) { return a.lb[j] + tree_u(seed, (uint64_t)i, (uint64_t)j) * (a.ub[j] - a.lb[j]); }
+
+__host__ __device__ inline double joint_diff(const RmRobot& rb, int j, double a, double b) { return rb.cont[j] ? wrap_diff(a, b) : b - a; }
+// joint j of the steer step: from the nearest node a towards the sample qr, the whole way when dist = sqrt(acc) <= step
+__host__ __device__ inline double steer_joint(const RmRobot& rb, int j, double a, double qr, double dist, double step) {
+    const double D = joint_diff(rb, j, a, qr);
+    return dist <= step ? a + D : a + (step / dist) * D;
+}
+// joint j of the point that ends the free prefix of m of S sub-segments of the edge a -> b
+__host__ __device__ inline double cut_joint(const RmRobot& rb, int j, double a, double b, int m, int S) { return a + ((double)m / (double)S) * joint_diff(rb, j, a, b); }
+
+// S of the edge a -> b as a prefix walks it (the argument checks keep every edge of a run below the cap; the clamp bounds the loop regardless)
+__host__ __device__ inline int prefix_segments(const RmRobot& rb, const double* a, const double* b, double edge_step) {
+    const int64_t S = edge_segments(rb, a, b, edge_step);
+    return S > ARMOUR_TREE_MAX_SEGMENTS ? ARMOUR_TREE_MAX_SEGMENTS : (int)S;
+}
+// sub-segment s of S of the edge a -> b against the staged obstacles: the edge rule's enlarged test, verdict mode
+__host__ __device__ inline bool segment_free(const RmRobot& rb, const double* a, const double* b, int s, int S, const double* obs, int O) {
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+    edge_sample(rb, a, b, s, S, q, r);
+    return config_free(rb, q, r, obs, O, false, nullptr);
+}
+__host__ __device__ inline bool node_free(const RmRobot& rb, const double* x, const double* obs, int O) {
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
+#pragma unroll
+    for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
+    return config_free(rb, q, r, obs, O, false, nullptr);
+}
+
+// ---- the block's cooperative steps.  Every result is the same in all lanes.
+struct TreeShared {
+    double a[ARMOUR_MAX_FACTORS], b[ARMOUR_MAX_FACTORS];   // the edge a prefix walks; b doubles as the query of a nearest scan
+    double red_d[TP_WAVES];
+    int red_v[TP_WAVES];
+    int first[TP_WAVES];
+    int flag[2];
+};
+
+// argmin over nodes[0 .. cnt) of (wrapped_sq(node, sh.b), index); the caller has put a barrier after the last write of sh.b and of the nodes
+__device__ inline void block_nearest(const RmRobot& rb, TreeShared& sh, const double* nodes, int cnt, double* acc, int* index) {
+    const int n = rb.n, t = threadIdx.x;
+    double q[ARMOUR_MAX_FACTORS];
+#pragma unroll
+    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = sh.b[j];
+    double bd = INFINITY;
+    int bv = TP_NONE;
+    for (int v = t; v < cnt; v += TP_BLOCK) {
+        const double d = wrapped_sq(rb, nodes + (size_t)v * n, q);
+        if (key_less(d, v, bd, bv)) { bd = d; bv = v; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(bd, o);
+        const int ov = __shfl_xor(bv, o);
+        if (key_less(od, ov, bd, bv)) { bd = od; bv = ov; }
+    }
+    if ((t & 63) == 0) { sh.red_d[t >> 6] = bd; sh.red_v[t >> 6] = bv; }
+    __syncthreads();
+    bd = sh.red_d[0]; bv = sh.red_v[0];
+#pragma unroll
+    for (int w = 1; w < TP_WAVES; w++)
+        if (key_less(sh.red_d[w], sh.red_v[w], bd, bv)) { bd = sh.red_d[w]; bv = sh.red_v[w]; }
+    *acc = bd;
+    *index = bv;
+}
+
+// prefix(sh.a, sh.b): *S sub-segments, returns m.  Sub-segments are taken in ascending chunks, up to the first chunk with a hit.  An edge of
+// at most TP_BLOCK / 2 sub-segments (every extend step; most joins) gives each sub-segment G = min(O, TP_BLOCK / S) lanes, lane g of them
+// testing the obstacles [g O / G, (g + 1) O / G) -- a sub-segment is free iff it is free of every obstacle, so the verdict is the same and
+// the lanes that would idle shorten the longest lane's work from O obstacles to O / G.  Lanes are in ascending order of sub-segment, so the
+// first colliding lane names the first colliding sub-segment.  The caller has put a barrier after the last write of sh.a / sh.b; on return
+// every lane is past the last read of them.
+__device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edge_step, const double* s_obs, int O, int* S_out) {
+    const int t = threadIdx.x;
+    const int S = prefix_segments(rb, sh.a, sh.b, edge_step);
+    *S_out = S;
+    int G = 1;
+    if (2 * S <= TP_BLOCK && O > 1) G = TP_BLOCK / S < O ? TP_BLOCK / S : O;
+    const int per = TP_BLOCK / G;                           // sub-segments per chunk
+    const int g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
+    int m = S;
+    for (int base = 0; base < S; base += per) {
+        const int s = base + t / G;
+        const bool hit = t < per * G && s < S && !segment_free(rb, sh.a, sh.b, s, S, s_obs + (size_t)o0 * RM_OBS_STRIDE, o1 - o0);
+        const unsigned long long mask = __ballot(hit);
+        if ((t & 63) == 0) sh.first[t >> 6] = mask ? base + ((t & ~63) + __ffsll((long long)mask) - 1) / G : TP_NONE;
+        __syncthreads();
+        int f = sh.first[0];
+#pragma unroll
+        for (int w = 1; w < TP_WAVES; w++) f = sh.first[w] < f ? sh.first[w] : f;
+        __syncthreads();                                    // sh.first has been read: the next chunk, or the next prefix, may write it
+        if (f != TP_NONE) { m = f; break; }
+    }
+    return m;
+}
+
+// grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The trees of world w: nodes [w][2][max_nodes][n], parent [w][2][max_nodes], count [w][2].
+__global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArgs ar) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+    __shared__ TreeShared sh;
+    const int w = blockIdx.x, t = threadIdx.x, n = rb.n, O = ar.O, cap = ar.max_nodes;
+    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    const double* start = ar.starts + (size_t)w * n;
+    const double* goal = ar.goals + (size_t)w * n;
+    const uint64_t seed = ar.seeds[w];
+    double* nodes[2] = {ar.nodes + ((size_t)w * 2) * cap * n, ar.nodes + ((size_t)w * 2 + 1) * cap * n};
+    int32_t* parent[2] = {ar.parent + ((size_t)w * 2) * cap, ar.parent + ((size_t)w * 2 + 1) * cap};
+    int cnt[2] = {0, 0};
+    int status = ARMOUR_TREE_NOT_FOUND, iterations = 0, points = 0;
+
+    // the node rule at start and goal (lanes 0 and 1), and the direct edge
+    if (t < 2) sh.flag[t] = node_free(rb, t == 0 ? start : goal, s_obs, O) ? 1 : 0;
+    if (t < ARMOUR_MAX_FACTORS) {
+        sh.a[t] = t < n ? start[t] : 0.0;
+        sh.b[t] = t < n ? goal[t] : 0.0;
+    }
+    __syncthreads();
+    bool run = false;
+    if (!sh.flag[0]) {
+        status = ARMOUR_TREE_START_BLOCKED;
+    } else if (!sh.flag[1]) {
+        status = ARMOUR_TREE_GOAL_BLOCKED;
+    } else {
+        int S;
+        const int m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+        if (m == S) {
+            status = ARMOUR_TREE_FOUND;
+            points = 2;
+            if (ar.path && points <= ar.max_points && t < n) {
+                ar.path[((size_t)w * ar.max_points) * n + t] = start[t];
+                ar.path[((size_t)w * ar.max_points + 1) * n + t] = goal[t];
+            }
+        } else {
+            run = true;
+        }
+    }
+    if (run) {
+        if (t < n) {
+            nodes[0][t] = start[t];
+            nodes[1][t] = goal[t];
+        }
+        if (t == 0) parent[0][0] = parent[1][0] = -1;
+        cnt[0] = cnt[1] = 1;
+        iterations = ar.max_iterations;
+        for (int i = 0; i < ar.max_iterations; i++) {
+            const int a = i & 1, b = 1 - a;
+            if (cnt[a] >= cap || cnt[b] >= cap) { status = ARMOUR_TREE_FULL; iterations = i; break; }
+            // ---- sample (into sh.b, the query of the scan)
+            if (t < ARMOUR_MAX_FACTORS) sh.b[t] = t < n ? tree_sample(ar, seed, i, t) : 0.0;
+            __syncthreads();                                // also: the nodes appended in iteration i - 1 are written
+            // ---- nearest in tree a, steer
+            double acc;
+            int v;
+            block_nearest(rb, sh, nodes[a], cnt[a], &acc, &v);
+            if (acc == 0.0) continue;
+            const double dist = sqrt(acc);
+            if (t < ARMOUR_MAX_FACTORS) {                   // lane t alone reads and writes joint t of sh.a / sh.b
+                const double x = t < n ? nodes[a][(size_t)v * n + t] : 0.0;
+                sh.a[t] = x;
+                sh.b[t] = t < n ? steer_joint(rb, t, x, sh.b[t], dist, ar.step) : 0.0;
+            }
+            __syncthreads();
+            // ---- extend: the free prefix of nearest -> qn
+            int S;
+            int m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+            if (m == 0) continue;
+            if (t < n) {
+                if (m < S) sh.b[t] = cut_joint(rb, t, sh.a[t], sh.b[t], m, S);
+                nodes[a][(size_t)cnt[a] * n + t] = sh.b[t];
+            }
+            if (t == 0) parent[a][cnt[a]] = v;
+            const int joined_a = cnt[a];
+            cnt[a]++;
+            __syncthreads();                                // qn is in sh.b and in tree a
+            // ---- connect: the other tree's nearest node towards qn
+            int vb;
+            block_nearest(rb, sh, nodes[b], cnt[b], &acc, &vb);
+            if (t < ARMOUR_MAX_FACTORS) sh.a[t] = t < n ? nodes[b][(size_t)vb * n + t] : 0.0;
+            __syncthreads();
+            m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+            if (m == S) {
+                // joined: the start tree's chain root -> ..., then the goal tree's chain ... -> root.  The walks are bounded by the counts.
+                const int join[2] = {a == 0 ? joined_a : vb, a == 0 ? vb : joined_a};
+                int len[2];
+                for (int k = 0; k < 2; k++) {
+                    int d = 0;
+                    for (int x = join[k]; x >= 0 && x < cnt[k] && d < cnt[k]; x = parent[k][x]) d++;
+                    len[k] = d;
+                }
+                status = ARMOUR_TREE_FOUND;
+                iterations = i + 1;
+                points = len[0] + len[1];
+                if (ar.path && points <= ar.max_points && t < n) {
+                    double* out = ar.path + ((size_t)w * ar.max_points) * n;
+                    int pos = len[0] - 1, d = 0;
+                    for (int x = join[0]; d < len[0]; x = parent[0][x], d++, pos--) out[(size_t)pos * n + t] = nodes[0][(size_t)x * n + t];
+                    pos = len[0]; d = 0;
+                    for (int x = join[1]; d < len[1]; x = parent[1][x], d++, pos++) out[(size_t)pos * n + t] = nodes[1][(size_t)x * n + t];
+                }
+                break;
+            }
+            if (m >= 1) {
+                if (t < n) nodes[b][(size_t)cnt[b] * n + t] = cut_joint(rb, t, sh.a[t], sh.b[t], m, S);
+                if (t == 0) parent[b][cnt[b]] = vb;
+                cnt[b]++;
+            }
+        }
+    }
+    if (t == 0) {
+        ar.status[w] = status;
+        ar.iterations[w] = iterations;
+        ar.points[w] = points;
+        ar.count[2 * w] = cnt[0];
+        ar.count[2 * w + 1] = cnt[1];
+    }
+}
+
+// ---- the host twin's steps: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
+struct HostWorld {
+    const RmRobot& rb;
+    const double* obs;
+    int O;
+    double edge_step;
+    double* margin;
+
+    void note(double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS]) const {
+        double cl;
+        config_free(rb, q, r, obs, O, true, &cl);
+        *margin = std::fmin(*margin, std::fabs(cl));
+    }
+    bool node(const double* x) const {
+        if (margin) {
+            double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS] = {};
+            for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
+            note(q, r);
+        }
+        return node_free(rb, x, obs, O);
+    }
+    int prefix(const double* a, const double* b, int* S_out) const {
+        const int S = prefix_segments(rb, a, b, edge_step);
+        *S_out = S;
+        for (int s = 0; s < S; s++) {
+            if (margin) {
+                double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+                edge_sample(rb, a, b, s, S, q, r);
+                note(q, r);
+            }
+            if (!segment_free(rb, a, b, s, S, obs, O)) return s;
+        }
+        return S;
+    }
+};
+
+int nearest_host(const RmRobot& rb, const double* nodes, int cnt, const double* q, double* acc) {
+    double bd = INFINITY;
+    int bv = TP_NONE;
+    for (int v = 0; v < cnt; v++) {
+        const double d = wrapped_sq(rb, nodes + (size_t)v * rb.n, q);
+        if (key_less(d, v, bd, bv)) { bd = d; bv = v; }
+    }
+    *acc = bd;
+    return bv;
+}
+
+// world w of the host twin; the trees go to nodes [2][max_nodes][n] / parent [2][max_nodes] (the caller's rows or scratch)
+void plan_world_host(const RmRobot& rb, const TreeArgs& ar, int w, const double* obs, double* nodes0, int32_t* parent0, double* margin) {
+    const int n = rb.n, cap = ar.max_nodes;
+    const double* start = ar.starts + (size_t)w * n;
+    const double* goal = ar.goals + (size_t)w * n;
+    const uint64_t seed = ar.seeds[w];
+    if (margin) *margin = INFINITY;
+    const HostWorld hw{rb, obs, ar.O, ar.edge_step, margin};
+    double* nodes[2] = {nodes0, nodes0 + (size_t)cap * n};
+    int32_t* parent[2] = {parent0, parent0 + cap};
+    int cnt[2] = {0, 0};
+    int32_t& status = ar.status[w];
+    int32_t& iterations = ar.iterations[w];
+    int32_t& points = ar.points[w];
+    status = ARMOUR_TREE_NOT_FOUND; iterations = 0; points = 0;
+    auto done = [&] { if (ar.count) { ar.count[2 * w] = cnt[0]; ar.count[2 * w + 1] = cnt[1]; } };
+    if (!hw.node(start)) { status = ARMOUR_TREE_START_BLOCKED; return done(); }
+    if (!hw.node(goal)) { status = ARMOUR_TREE_GOAL_BLOCKED; return done(); }
+    int S;
+    int m = hw.prefix(start, goal, &S);
+    double* out = ar.path ? ar.path + ((size_t)w * ar.max_points) * n : nullptr;
+    if (m == S) {
+        status = ARMOUR_TREE_FOUND;
+        points = 2;
+        if (out && points <= ar.max_points) {
+            std::memcpy(out, start, n * sizeof(double));
+            std::memcpy(out + n, goal, n * sizeof(double));
+        }
+        return done();
+    }
+    std::memcpy(nodes[0], start, n * sizeof(double));
+    std::memcpy(nodes[1], goal, n * sizeof(double));
+    parent[0][0] = parent[1][0] = -1;
+    cnt[0] = cnt[1] = 1;
+    iterations = ar.max_iterations;
+    double qr[ARMOUR_MAX_FACTORS] = {}, qn[ARMOUR_MAX_FACTORS] = {};
+    for (int i = 0; i < ar.max_iterations; i++) {
+        const int a = i & 1, b = 1 - a;
+        if (cnt[a] >= cap || cnt[b] >= cap) { status = ARMOUR_TREE_FULL; iterations = i; break; }
+        for (int j = 0; j < n; j++) qr[j] = tree_sample(ar, seed, i, j);
+        double acc;
+        const int v = nearest_host(rb, nodes[a], cnt[a], qr, &acc);
+        if (acc == 0.0) continue;
+        const double dist = sqrt(acc);
+        const double* near = nodes[a] + (size_t)v * n;
+        for (int j = 0; j < n; j++) qn[j] = steer_joint(rb, j, near[j], qr[j], dist, ar.step);
+        m = hw.prefix(near, qn, &S);
+        if (m == 0) continue;
+        if (m < S)
+            for (int j = 0; j < n; j++) qn[j] = cut_joint(rb, j, near[j], qn[j], m, S);
+        std::memcpy(nodes[a] + (size_t)cnt[a] * n, qn, n * sizeof(double));
+        parent[a][cnt[a]] = v;
+        const int joined_a = cnt[a]++;
+        const int vb = nearest_host(rb, nodes[b], cnt[b], qn, &acc);
+        const double* other = nodes[b] + (size_t)vb * n;
+        m = hw.prefix(other, qn, &S);
+        if (m == S) {
+            const int join[2] = {a == 0 ? joined_a : vb, a == 0 ? vb : joined_a};
+            int len[2];
+            for (int k = 0; k < 2; k++) {
+                int d = 0;
+                for (int x = join[k]; x >= 0 && x < cnt[k] && d < cnt[k]; x = parent[k][x]) d++;
+                len[k] = d;
+            }
+            status = ARMOUR_TREE_FOUND;
+            iterations = i + 1;
+            points = len[0] + len[1];
+            if (out && points <= ar.max_points) {
+                int pos = len[0] - 1, d = 0;
+                for (int x = join[0]; d < len[0]; x = parent[0][x], d++, pos--) std::memcpy(out + (size_t)pos * n, nodes[0] + (size_t)x * n, n * sizeof(double));
+                pos = len[0]; d = 0;
+                for (int x = join[1]; d < len[1]; x = parent[1][x], d++, pos++) std::memcpy(out + (size_t)pos * n, nodes[1] + (size_t)x * n, n * sizeof(double));
+            }
+            break;
+        }
+        if (m >= 1) {
+            double* x = nodes[b] + (size_t)cnt[b] * n;
+            for (int j = 0; j < n; j++) x[j] = cut_joint(rb, j, other[j], qn[j], m, S);
+            parent[b][cnt[b]++] = vb;
+        }
+    }
+    done();
+}
+
+// the argument rules of both entries, before a device is touched; fills rb and ar (the caller's pointers)
+int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+               const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations,
+               int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path, int32_t* count, double* nodes,
+               int32_t* parent, RmRobot* rb, TreeArgs* ar) {
+    if (!robot || !lb || !ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(armour_check_robot_shape(who, robot));
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
+    const int n = robot->num_factors;
+    if (W > 0 && (!starts || !goals || !seeds || !status || !iterations || !points)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    if (max_nodes < 2 || max_nodes > ARMOUR_TREE_MAX_NODES || max_iterations < 0 || max_iterations > ARMOUR_TREE_MAX_ITERATIONS || max_points < 0) {
+        armour_set_error("%s: max_nodes = %d (2..%d), max_iterations = %d (0..%d), max_points = %d", who, max_nodes, ARMOUR_TREE_MAX_NODES, max_iterations,
+                         ARMOUR_TREE_MAX_ITERATIONS, max_points);
+        return ARMOUR_EINVAL;
+    }
+    if (!(step > 0.0) || !(edge_step > 0.0) || !std::isfinite(step) || !std::isfinite(edge_step)) {
+        armour_set_error("%s: step = %g, edge_step = %g", who, step, edge_step);
+        return ARMOUR_EINVAL;
+    }
+    for (int j = 0; j < n; j++)
+        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: sampling box [%g, %g] of joint %d", who, lb[j], ub[j], j); return ARMOUR_EINVAL; }
+    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(starts, (size_t)W * n) || !finite_all(goals, (size_t)W * n)) {
+        armour_set_error("%s: a start, a goal or an obstacle is not finite", who);
+        return ARMOUR_EINVAL;
+    }
+    fill_rm_robot(robot, continuous, rb);
+    // No edge of a run is longer, joint by joint, than pi (a wrapped joint) or the span of the box, the start and the goal (any other: a new
+    // node lies between an old one and a sample): that many sub-segments must fit the cap.
+    for (int j = 0; j < n; j++) {
+        double lo = lb[j], hi = ub[j];
+        for (int32_t w = 0; w < W && !rb->cont[j]; w++) {
+            lo = std::fmin(lo, std::fmin(starts[(size_t)w * n + j], goals[(size_t)w * n + j]));
+            hi = std::fmax(hi, std::fmax(starts[(size_t)w * n + j], goals[(size_t)w * n + j]));
+        }
+        const double span = rb->cont[j] ? RM_PI : hi - lo;
+        if (!(std::ceil(span / edge_step) <= (double)ARMOUR_TREE_MAX_SEGMENTS)) {
+            armour_set_error("%s: joint %d spans %g, more than %d sub-segments of edge_step %g", who, j, span, ARMOUR_TREE_MAX_SEGMENTS, edge_step);
+            return ARMOUR_ECAPACITY;
+        }
+    }
+    std::memset(ar, 0, sizeof(*ar));
+    for (int j = 0; j < n; j++) { ar->lb[j] = lb[j]; ar->ub[j] = ub[j]; }
+    ar->step = step; ar->edge_step = edge_step;
+    ar->O = O; ar->max_iterations = max_iterations; ar->max_nodes = max_nodes; ar->max_points = max_points;
+    ar->obstacles = obstacles; ar->starts = starts; ar->goals = goals; ar->seeds = seeds;
+    ar->status = status; ar->iterations = iterations; ar->points = points; ar->count = count; ar->parent = parent;
+    ar->path = path; ar->nodes = nodes;
+    return ARMOUR_OK;
+}
+
+// the roadmap entries' capacity rule: points [W] is complete; a found path longer than max_points was not written
+int check_capacity(const char* who, int32_t W, const int32_t* points, const double* path, int32_t max_points) {
+    for (int32_t w = 0; path && w < W; w++)
+        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
+    return ARMOUR_OK;
+}
+
+}  // namespace
+
+extern "C" int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                     const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                                     int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                                     double* path, int32_t* count, double* nodes, int32_t* parent, double* margin) {
+    const char* who = "armour_tree_plan_host";
+    RmRobot rb;
+    TreeArgs ar;
+    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status,
+                          iterations, points, path, count, nodes, parent, &rb, &ar));
+    const int n = rb.n;
+    std::vector<double> obs((size_t)O * RM_OBS_STRIDE), own_nodes(nodes ? 0 : (size_t)2 * max_nodes * n);   // staged as the kernel stages them
+    std::vector<int32_t> own_parent(parent ? 0 : (size_t)2 * max_nodes);
+    for (int32_t w = 0; w < W; w++) {
+        stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
+        plan_world_host(rb, ar, w, obs.data(), nodes ? nodes + (size_t)w * 2 * max_nodes * n : own_nodes.data(),
+                        parent ? parent + (size_t)w * 2 * max_nodes : own_parent.data(), margin ? margin + w : nullptr);
+    }
+    return check_capacity(who, W, points, path, max_points);
+}
+
+extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                                int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path,
+                                int32_t* count, double* nodes, int32_t* parent, double* ms) {
+    const char* who = "armour_tree_plan";
+    RmRobot rb;
+    TreeArgs ar;
+    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status,
+                          iterations, points, path, count, nodes, parent, &rb, &ar));
+    if (ms) *ms = 0.0;
+    if (W == 0) return ARMOUR_OK;
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
+    const int n = rb.n;
+    const size_t Wn = (size_t)W * n, trees = (size_t)W * 2 * max_nodes, path_len = path ? (size_t)W * max_points * n : 0;
+    DevStream st;
+    EventPair ev;
+    DevBuf<double> d_obs, d_starts, d_goals, d_nodes, d_path;
+    DevBuf<uint64_t> d_seeds;
+    DevBuf<int32_t> d_out, d_parent;                      // d_out: status | iterations | points [W] each, then count [W][2]
+    ARMOUR_TRY(st.create());
+    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_starts.upload(starts, Wn, st));
+    ARMOUR_TRY(d_goals.upload(goals, Wn, st));
+    ARMOUR_TRY(d_seeds.upload(seeds, (size_t)W, st));
+    ARMOUR_TRY(d_nodes.reserve(trees * n));
+    ARMOUR_TRY(d_parent.reserve(trees));
+    ARMOUR_TRY(d_out.reserve((size_t)5 * W));
+    if (path) ARMOUR_TRY(d_path.reserve(path_len));
+    TreeArgs dev = ar;
+    dev.obstacles = d_obs; dev.starts = d_starts; dev.goals = d_goals; dev.seeds = d_seeds;
+    dev.status = d_out; dev.iterations = d_out + W; dev.points = d_out + 2 * (size_t)W; dev.count = d_out + 3 * (size_t)W;
+    dev.parent = d_parent; dev.nodes = d_nodes; dev.path = path ? d_path.p : nullptr;
+    ARMOUR_TRY(ev.record_start(st));
+    hipLaunchKernelGGL(tree_plan_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, rb, dev);
+    HIPCHK(hipGetLastError());
+    ARMOUR_TRY(ev.record_stop(st));
+    std::vector<int32_t> out((size_t)5 * W);
+    HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
+    std::memcpy(status, out.data(), (size_t)W * sizeof(int32_t));
+    std::memcpy(iterations, out.data() + W, (size_t)W * sizeof(int32_t));
+    std::memcpy(points, out.data() + 2 * (size_t)W, (size_t)W * sizeof(int32_t));
+    const int32_t* h_count = out.data() + 3 * (size_t)W;
+    if (count) std::memcpy(count, h_count, (size_t)2 * W * sizeof(int32_t));
+    // the trees and the paths: only the rows that were written come back (the rest of the caller's arrays is left as it was)
+    for (int32_t w = 0; w < W; w++) {
+        for (int k = 0; k < 2; k++) {
+            const size_t row = (size_t)w * 2 + k, c = (size_t)h_count[2 * w + k];
+            if (nodes && c) HIPCHK(hipMemcpyAsync(nodes + row * max_nodes * n, d_nodes + row * max_nodes * n, c * n * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (parent && c) HIPCHK(hipMemcpyAsync(parent + row * max_nodes, d_parent + row * max_nodes, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        }
+        if (path && points[w] > 0 && points[w] <= max_points)
+            HIPCHK(hipMemcpyAsync(path + (size_t)w * max_points * n, d_path + (size_t)w * max_points * n, (size_t)points[w] * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return check_capacity(who, W, points, path, max_points);
+}

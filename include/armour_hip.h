@@ -708,6 +708,77 @@ int armour_roadmap_connect_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* wo
 int armour_roadmap_descend_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* world, const double* q_start, int32_t connect_k,
                                  int32_t seq_capacity, int32_t* seq_off, int32_t* seq, uint8_t* status, double* length);
 
+/* ---- batched tree planner: bidirectional RRT-Connect for W worlds in one launch (tree_plan.hip) ---- */
+/* The reference's single-query high-level planners (RRT_HLP, RRT_connect_HLP, robot_arm_RRT_HLP with HLP_grow_tree_mode = 'new'): a fresh
+ * pair of trees per query, grown where the query is, with no graph built beforehand.  Everything geometric is the roadmap's, reused as it
+ * stands: the node rule, the edge rule's sub-segments (S, midpoints, enlargements) and the wrapped distance.  Deterministic: a world's
+ * result depends on its own inputs and seed alone, and the device and the host entry run the same functions.
+ *
+ * Trees.  Tree 0 is rooted at start, tree 1 at goal.  Nodes are kept UNWRAPPED: a continuous joint may leave [-pi, pi]; every difference
+ *   of two configurations is the edge rule's D (wrapped on continuous joints), so that is harmless.
+ * Random numbers.  Counter-based, arithmetic mod 2^64:
+ *     u(seed, i, j):  z = seed + 0x9E3779B97F4A7C15 * (((i << 8) | j) + 1)
+ *                     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+ *                     u = (z >> 11) * 2^-53
+ *   The sample of iteration i is qr_j = lb_j + u(seed, i, j) (ub_j - lb_j).
+ * prefix(a, b) -> (m, S).  The edge rule's S sub-segments of the edge a -> b; m = the index of the first sub-segment whose enlarged test
+ *   does not separate, m = S when all do.  Sub-segments 0 .. m - 1 cover q(t), t in [0, m / S], each by its own test, so the edge rule's
+ *   soundness argument holds for that prefix unchanged: no configuration on a -> a + (m / S) D collides.
+ * nearest(tree, q).  The node with the smallest (acc, index), acc = the squared wrapped distance node -> q (the sum of the nearest-
+ *   neighbour search, without its square root): a total order, the smaller index on a tie.
+ * The run of one world (cap = max_nodes):
+ *     node rule at start, then at goal: not free -> START_BLOCKED / GOAL_BLOCKED, 0 iterations, no trees (count 0, 0)
+ *     (m, S) = prefix(start, goal);  m == S -> FOUND, the path [start, goal], 0 iterations, no trees (as armour_roadmap_plan's direct edge)
+ *     trees = {start}, {goal}
+ *     for i = 0 .. max_iterations - 1:     a = i & 1 (the tree that extends), b = 1 - a
+ *         either tree holds cap nodes -> TREE_FULL, iterations = i
+ *         qr = the sample of i;  v = nearest(tree a, qr);  acc == 0 -> next i
+ *         dist = sqrt(acc);  D = node v -> qr;  qn = node v + D when dist <= step, else node v + (step / dist) D
+ *         (m, S) = prefix(node v, qn);  m == 0 -> next i;  m < S -> qn = node v + (m / S) D(node v -> qn)      (extend keeps the free prefix)
+ *         append qn to tree a with parent v
+ *         vb = nearest(tree b, qn);  (m, S) = prefix(node vb, qn)
+ *         m == S -> FOUND, iterations = i + 1 (qn is NOT added to tree b);  m >= 1 -> append node vb + (m / S) D(node vb -> qn), parent vb
+ *     NOT_FOUND, iterations = max_iterations
+ *   m / S is fl(m) / fl(S) in fp64; fp64 throughout, no fused multiply-add.
+ * Path.  start = tree 0's root, ..., the joining edge, ..., tree 1's root = goal, whichever tree extended last; consecutive equal points
+ *   are possible.  Soundness: every segment of a returned path is a union of sub-segments whose enlarged tests separated (a tree edge is
+ *   a free prefix, the joining edge a whole free edge), so no configuration on the path collides.
+ * Limits (ARMOUR_EINVAL before a device is touched): W and O as armour_roadmap_check; 2 <= max_nodes <= ARMOUR_TREE_MAX_NODES;
+ *   0 <= max_iterations <= ARMOUR_TREE_MAX_ITERATIONS; step, edge_step > 0 and finite; lb <= ub, finite; finite starts, goals and
+ *   obstacles; max_points >= 0.  W = 0 is a success that does nothing.  ARMOUR_ECAPACITY when an edge of a run could have more than
+ *   ARMOUR_TREE_MAX_SEGMENTS sub-segments: ceil(span_j / edge_step) with span_j = pi on a continuous joint and otherwise the extent of
+ *   [lb_j, ub_j] and every start and goal (a new node lies between an old one and a sample).
+ * Arrays are host pointers.  continuous [n] (NULL: robot->continuous); lb / ub [n] the sampling box; obstacles [W][O][12]; starts / goals
+ *   [W][n]; seeds [W].  Outputs: status / iterations / points [W]; optional (NULL: not returned) path [W][max_points][n], count [W][2],
+ *   nodes [W][2][max_nodes][n], parent [W][2][max_nodes] (-1 at a root), ms (device time of the launch).  Only the first count rows of a
+ *   tree and the first points rows of a path are written.  When a found path has more than max_points points the call returns
+ *   ARMOUR_ECAPACITY with points [W] complete and that world's path unwritten (the roadmap entries' rule; without path nothing is refused).
+ * Device: one launch, grid W, a 256-lane block per world with the world's obstacles staged in LDS; the loop above runs inside the block,
+ *   ordered by __syncthreads() alone -- no atomics, no flags, no block waits on another -- and is bounded by max_iterations.  The nearest
+ *   scan deals the nodes to lanes and reduces (acc, index) by shuffles and LDS; a prefix takes its sub-segments in ascending chunks and
+ *   stops at the first chunk with a hit; a short edge gives each sub-segment several lanes, each with a slice of the obstacles (the
+ *   verdict of a sub-segment is the AND over obstacles, so nothing changes but the time).  W = 1 runs on one compute unit, and a launch
+ *   lasts as long as its slowest world.  DESIGN.md 4.12c.
+ * armour_tree_plan_host is the same functions in a loop and touches no device.  margin [W] (may be NULL): the smallest |clearance| over
+ *   the checks that decided the world's run -- the two node checks and sub-segments 0 .. min(m, S - 1) of every prefix -- i.e. how far
+ *   the run was from a verdict that rounding in sin / cos could flip (+inf when nothing was checked). */
+#define ARMOUR_TREE_NOT_FOUND 0
+#define ARMOUR_TREE_FOUND 1
+#define ARMOUR_TREE_START_BLOCKED 2
+#define ARMOUR_TREE_GOAL_BLOCKED 3
+#define ARMOUR_TREE_FULL 4
+#define ARMOUR_TREE_MAX_NODES 8192
+#define ARMOUR_TREE_MAX_ITERATIONS 100000
+#define ARMOUR_TREE_MAX_SEGMENTS 1048576
+int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                     const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                     int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                     double* path, int32_t* count, double* nodes, int32_t* parent, double* ms);
+int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                          const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                          int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                          double* path, int32_t* count, double* nodes, int32_t* parent, double* margin);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

@@ -1,7 +1,7 @@
 """Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
 and prints ONE JSON line.
 
-    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]]
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]|tree]
 
 * the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
   executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
@@ -12,6 +12,11 @@ and prints ONE JSON line.
   check / field ms, the worlds whose outcome differs and `ms_per_batch` (the waypoint queries' hlp_ms next to build, solve and audit ms);
   with --batched the waypoints of an iteration come from one Roadmap.descend_many call.  Everything else in the file is the straight-line
   run's, as before;
+* --hlp tree: the same worlds once more with the batched tree planner as the high-level planner (armour_amd.tree_planner.tree_hlps: a fresh
+  RRT-Connect per world and iteration, all live worlds in one armour_tree_plan call; --tree-seed, --tree-iterations, --tree-nodes):
+  `hlp_outcomes_tree` holds the outcome counts beside the straight-line run's, the worlds whose outcome differs and `ms_per_batch` (hlp_ms next
+  to build, solve and audit ms).  One run, one seed.  A `hlp_outcomes` section that profiles/trial_bench.json already holds (a roadmap-field
+  run) is kept, so that the three planners' rows stand side by side;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -96,6 +101,19 @@ def roadmap_field_trials(robot, ws, straight, a):
                 changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
 
 
+def tree_trials(robot, ws, straight, a):
+    """The worlds once more under tree_hlps; outcome counts under both HLPs and the worlds that end differently."""
+    from armour_amd.tree_planner import tree_hlps
+    from armour_amd.trials import OUTCOMES, run_trials
+    options = dict(step=0.5, edge_step=0.05, max_iterations=a.tree_iterations, max_nodes=a.tree_nodes)
+    res = run_trials(ws, hlp=tree_hlps(ws, robot, seed=a.tree_seed, **options), T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
+    per_batch = lambda key: dict(mean=float(np.mean([b[key] for b in res["batches"]])), max=float(np.max([b[key] for b in res["batches"]])))
+    count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
+    return dict(tree=dict(options, seed=a.tree_seed), straight=count(straight), tree_outcomes=count(res), tree_summary=res["summary"],
+                ms_per_batch={key: per_batch(key) for key in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0],
+                changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=128)
@@ -103,7 +121,10 @@ def main():
     ap.add_argument("--steps", type=float, nargs="+", default=[0.01, 0.05])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kernel-stats", action="store_true")
-    ap.add_argument("--hlp", choices=["straight", "roadmap-field"], default="straight")
+    ap.add_argument("--hlp", choices=["straight", "roadmap-field", "tree"], default="straight")
+    ap.add_argument("--tree-seed", type=int, default=0)
+    ap.add_argument("--tree-iterations", type=int, default=2000)
+    ap.add_argument("--tree-nodes", type=int, default=2048)
     ap.add_argument("--roadmap-nodes", type=int, default=20000)
     ap.add_argument("--roadmap-radius", type=float, default=1.5)
     ap.add_argument("--batched", action="store_true")
@@ -132,6 +153,13 @@ def main():
                first_batch=bt[0], min_clearance=float(min(r["clearance"] for w in res["worlds"] for r in w["records"])))
     if a.hlp == "roadmap-field":
         out["hlp_outcomes"] = roadmap_field_trials(robot, ws, res, a)
+    saved_json = os.path.join(ROOT, "profiles", "trial_bench.json")
+    if a.hlp == "tree":
+        out["hlp_outcomes_tree"] = tree_trials(robot, ws, res, a)
+        if os.path.exists(saved_json):
+            kept = json.load(open(saved_json)).get("hlp_outcomes")
+            if kept is not None:
+                out["hlp_outcomes"] = kept
     k_range, D = res["k_range"], res["duration"]
     O = max(w["obstacles"].shape[0] for w in res["worlds"])
     obs = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in res["worlds"]])
@@ -157,7 +185,7 @@ def main():
             np.savez(saved, obs=obs, world=world, q0=cols[0], qd0=cols[1], qdd0=cols[2], k=cols[3], k_range=k_range, D=D, ta=ta, tb=tb, step=a.steps[0])
             out["kernel_stats"] = kernel_stats(saved, a.reps, os.path.join(ROOT, "profiles", "trial_kernel_stats.csv"))
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "trial_bench.json"), "w") as f:
+    with open(saved_json, "w") as f:
         json.dump(out, f, indent=1, default=float)
         f.write("\n")
     print(json.dumps(out, default=float))
