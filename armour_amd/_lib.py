@@ -19,6 +19,8 @@ ROADMAP_KNN_MAX = 64         # ARMOUR_ROADMAP_KNN_MAX
 ROADMAP_KNN_MANY = 2048      # ARMOUR_ROADMAP_KNN_MANY: from this many queries on the search takes a lane per query
 TREE_NOT_FOUND, TREE_FOUND, TREE_START_BLOCKED, TREE_GOAL_BLOCKED, TREE_FULL = 0, 1, 2, 3, 4   # ARMOUR_TREE_*
 TREE_MAX_NODES, TREE_MAX_ITERATIONS = 8192, 100000   # ARMOUR_TREE_MAX_NODES, ARMOUR_TREE_MAX_ITERATIONS
+SHORTCUT_OK, SHORTCUT_INVALID = 0, 1                 # ARMOUR_SHORTCUT_*
+SHORTCUT_MAX_POINTS, SHORTCUT_MAX_PASSES = 1024, 8   # ARMOUR_SHORTCUT_MAX_POINTS, ARMOUR_SHORTCUT_MAX_PASSES
 
 
 class ArmourRobot(C.Structure):
@@ -157,7 +159,7 @@ EXPORTS = [
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
     "armour_roadmap_field", "armour_roadmap_descend",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
-    "armour_tree_plan", "armour_tree_plan_host",
+    "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
 ]
 
 _lib = None
@@ -300,6 +302,9 @@ def load():
             C.c_int32, ip, ip, ip, dp, ip, dp, ip, dp]
     L.armour_tree_plan.argtypes = tree            # (the last pointer: ms)
     L.armour_tree_plan_host.argtypes = tree       # (the last pointer: margin [W])
+    short = [C.POINTER(ArmourRobot), u8p, C.c_int32, C.c_int32, dp, C.c_int32, dp, ip, C.c_double, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp, dp, dp]
+    L.armour_path_shortcut.argtypes = short       # (the last pointer: ms)
+    L.armour_path_shortcut_host.argtypes = short  # (the last pointer: margin [W])
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

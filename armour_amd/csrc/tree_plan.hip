@@ -14,14 +14,11 @@
 
 #include "common.h"
 #include "roadmap_handle.h"
+#include "tree_block.h"
 
-using namespace rmgeo;
+using namespace treeblk;   // the steps shared with path_shortcut.hip (and, through it, rmgeo)
 
 namespace {
-
-constexpr int TP_BLOCK = 256;                 // four waves; a block is one world (its obstacles are staged in LDS)
-constexpr int TP_WAVES = TP_BLOCK / 64;
-constexpr int TP_NONE = INT_MAX;              // "no sub-segment collides" / the index of "no node"
 
 // What a world's run reads besides the robot: by value in the kernel's arguments (pointers: the device's; the host twin passes its own)
 struct TreeArgs {
@@ -44,35 +41,11 @@ __host__ __device__ inline double tree_u(uint64_t seed, uint64_t i, uint64_t j) 
 }
 __host__ __device__ inline double tree_sample(const TreeArgs& a, uint64_t seed, int i, int j) { return a.lb[j] + tree_u(seed, (uint64_t)i, (uint64_t)j) * (a.ub[j] - a.lb[j]); }
 
-__host__ __device__ inline double joint_diff(const RmRobot& rb, int j, double a, double b) { return rb.cont[j] ? wrap_diff(a, b) : b - a; }
 // joint j of the steer step: from the nearest node a towards the sample qr, the whole way when dist = sqrt(acc) <= step
 __host__ __device__ inline double steer_joint(const RmRobot& rb, int j, double a, double qr, double dist, double step) {
     const double D = joint_diff(rb, j, a, qr);
     return dist <= step ? a + D : a + (step / dist) * D;
 }
-// joint j of the point that ends the free prefix of m of S sub-segments of the edge a -> b
-__host__ __device__ inline double cut_joint(const RmRobot& rb, int j, double a, double b, int m, int S) { return a + ((double)m / (double)S) * joint_diff(rb, j, a, b); }
-
-// S of the edge a -> b as a prefix walks it (the argument checks keep every edge of a run below the cap; the clamp bounds the loop regardless)
-__host__ __device__ inline int prefix_segments(const RmRobot& rb, const double* a, const double* b, double edge_step) {
-    const int64_t S = edge_segments(rb, a, b, edge_step);
-    return S > ARMOUR_TREE_MAX_SEGMENTS ? ARMOUR_TREE_MAX_SEGMENTS : (int)S;
-}
-// sub-segment s of S of the edge a -> b against the staged obstacles: the edge rule's enlarged test, verdict mode
-__host__ __device__ inline bool segment_free(const RmRobot& rb, const double* a, const double* b, int s, int S, const double* obs, int O) {
-    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
-    edge_sample(rb, a, b, s, S, q, r);
-    return config_free(rb, q, r, obs, O, false, nullptr);
-}
-__host__ __device__ inline bool node_free(const RmRobot& rb, const double* x, const double* obs, int O) {
-    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
-#pragma unroll
-    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
-#pragma unroll
-    for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
-    return config_free(rb, q, r, obs, O, false, nullptr);
-}
-
 // ---- the block's cooperative steps.  Every result is the same in all lanes.
 struct TreeShared {
     double a[ARMOUR_MAX_FACTORS], b[ARMOUR_MAX_FACTORS];   // the edge a prefix walks; b doubles as the query of a nearest scan
@@ -259,42 +232,6 @@ __global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArg
         ar.count[2 * w + 1] = cnt[1];
     }
 }
-
-// ---- the host twin's steps: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
-struct HostWorld {
-    const RmRobot& rb;
-    const double* obs;
-    int O;
-    double edge_step;
-    double* margin;
-
-    void note(double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS]) const {
-        double cl;
-        config_free(rb, q, r, obs, O, true, &cl);
-        *margin = std::fmin(*margin, std::fabs(cl));
-    }
-    bool node(const double* x) const {
-        if (margin) {
-            double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS] = {};
-            for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
-            note(q, r);
-        }
-        return node_free(rb, x, obs, O);
-    }
-    int prefix(const double* a, const double* b, int* S_out) const {
-        const int S = prefix_segments(rb, a, b, edge_step);
-        *S_out = S;
-        for (int s = 0; s < S; s++) {
-            if (margin) {
-                double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
-                edge_sample(rb, a, b, s, S, q, r);
-                note(q, r);
-            }
-            if (!segment_free(rb, a, b, s, S, obs, O)) return s;
-        }
-        return S;
-    }
-};
 
 int nearest_host(const RmRobot& rb, const double* nodes, int cnt, const double* q, double* acc) {
     double bd = INFINITY;

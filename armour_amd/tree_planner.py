@@ -9,7 +9,12 @@ planned by one call:
     hlp = TreeHLP(robot, world_obstacles, goal, seed); q_des = hlp.get_waypoint(q_cur, lookahead)
     out = run_trials(worlds, hlp=tree_hlps(worlds, robot))       # the trees as the trials' high-level planner, one call per iteration
 
-The rule (hash, steer, free prefix, join), its soundness claim and the limits are stated in include/armour_hip.h; DESIGN.md 4.12c.
+Raw tree paths follow every kink of a random tree.  shortcut_paths (armour_path_shortcut) proves W polylines free and returns shorter ones made
+of free segments, in one launch; TreeHLP / tree_hlps use it with shortcut=p (every found path is shortened with p passes) and mode='seed'
+(the reference's HLP_grow_tree_mode = 'seed': the last path, from where the arm is now, is offered first and a tree grows only when it fails).
+
+The rules (hash, steer, free prefix, join; validate, prune, refine), their soundness claims and the limits are stated in
+include/armour_hip.h; DESIGN.md 4.12c, 4.12d.
 """
 import ctypes as C
 
@@ -20,6 +25,7 @@ from ._lib import _dp, check
 from .roadmap import waypoint_along
 from .scenes import pad_obstacles, straight_line_waypoint
 
+SHORTCUT_OK, SHORTCUT_INVALID = _lib.SHORTCUT_OK, _lib.SHORTCUT_INVALID
 NOT_FOUND, FOUND, START_BLOCKED, GOAL_BLOCKED, TREE_FULL = (_lib.TREE_NOT_FOUND, _lib.TREE_FOUND, _lib.TREE_START_BLOCKED, _lib.TREE_GOAL_BLOCKED,
                                                             _lib.TREE_FULL)
 
@@ -79,44 +85,136 @@ def plan_trees(robot, obstacles, starts, goals, seeds, lb=None, ub=None, continu
     return out
 
 
+class ShortPaths:
+    """What shortcut_paths returns: status [W] (SHORTCUT_OK / SHORTCUT_INVALID), paths (a list; [P,n] where OK, else None), first_bad [W]
+    (the first edge that is not free; -1 where OK), passes_done [W], length_in / length_out [W], ms (device time of the launch; 0 on the
+    host) and margin [W] (host only, else None: the smallest |clearance| over the checks made)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def shortcut_paths(robot, obstacles, paths, edge_step=0.05, passes=2, continuous=None, host=False):
+    """obstacles [W,O,12] (or [O,12]: W = 1), paths: W arrays [P_w,n] (P_w >= 2; the lengths may differ, they are padded) -> ShortPaths.
+    Every edge of a path is proved free (else INVALID), then the path is pruned, and refined and pruned again passes - 1 times.
+    host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
+    L = _lib.load()
+    n = robot.num_factors
+    obs = np.asarray(obstacles, dtype=np.float64)
+    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+    W, O = obs.shape[0], obs.shape[1]
+    ps = [np.asarray(p, dtype=np.float64).reshape(-1, n) for p in paths]
+    if len(ps) != W:
+        raise ValueError(f"{len(ps)} paths for {W} worlds")
+    counts = np.array([p.shape[0] for p in ps], dtype=np.int32)
+    max_in = max(int(counts.max()) if W else 2, 2)
+    max_points = min(max(2 * max_in - 1, 2), _lib.SHORTCUT_MAX_POINTS)     # room for one refine of a path that prune could not shorten
+    padded = np.zeros((W, max_in, n))
+    for w, p in enumerate(ps):
+        padded[w, :p.shape[0]] = p
+    cont = None if continuous is None else np.ascontiguousarray(continuous, dtype=np.uint8).reshape(n)
+    i32, u8 = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    status, points, first_bad, passes_done = (np.zeros(W, dtype=np.int32) for _ in range(4))
+    out = np.zeros((W, max_points, n))
+    length_in, length_out = np.zeros(W), np.zeros(W)
+    margin = np.zeros(W) if host else None
+    ms = C.c_double()
+    fn = L.armour_path_shortcut_host if host else L.armour_path_shortcut
+    check(fn(C.byref(robot), None if cont is None else cont.ctypes.data_as(u8), W, O, _dp(obs) if obs.size else None, max_in, _dp(padded),
+             counts.ctypes.data_as(i32), float(edge_step), int(passes), max_points, status.ctypes.data_as(i32), points.ctypes.data_as(i32),
+             first_bad.ctypes.data_as(i32), passes_done.ctypes.data_as(i32), _dp(out), _dp(length_in), _dp(length_out), _dp(margin) if host else C.byref(ms)))
+    short = [out[w, :points[w]].copy() if status[w] == SHORTCUT_OK else None for w in range(W)]
+    return ShortPaths(status=status, paths=short, first_bad=first_bad, passes_done=passes_done, length_in=length_in, length_out=length_out, margin=margin,
+                      ms=0.0 if host else ms.value)
+
+
 def call_seed(seed, world, call):
     """The seed of world `world`'s call number `call` (from 0) in a trial: (seed + (world << 32) + call) mod 2^64."""
     return (int(seed) + (int(world) << 32) + int(call)) % (1 << 64)
 
 
 class TreeHLP:
-    """High-level planner that grows a fresh pair of trees from q_cur at every call (the reference's HLP_grow_tree_mode = 'new'):
-    get_waypoint(q_cur, lookahead) is one one-world plan_trees call, then the point `lookahead` along the path (roadmap.waypoint_along);
-    with no path it falls back to scenes.straight_line_waypoint.  The c-th call uses the seed call_seed(seed, world, c)."""
+    """High-level planner over the batched trees: get_waypoint(q_cur, lookahead) is the point `lookahead` along this call's path
+    (roadmap.waypoint_along); with no path it falls back to scenes.straight_line_waypoint.  The c-th call uses the seed
+    call_seed(seed, world, c) when it grows trees.
+      mode='new' (the default; the reference's HLP_grow_tree_mode = 'new'): a fresh pair of trees from q_cur at every call, one one-world
+        plan_trees call.
+      mode='seed': the path of the last call is kept, and the next call first offers [q_cur] + path[1:] to shortcut_paths with
+        max(shortcut, 1) passes; when that is OK it is the path and no tree is grown (`reused` counts these), otherwise -- or with no
+        last path -- trees grow as in 'new'.
+      shortcut=p > 0: every path the trees find goes through shortcut_paths(passes=p) before the waypoint is taken."""
 
-    def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, **plan_options):
+    def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, shortcut=0, mode="new", **plan_options):
+        if mode not in ("new", "seed") or int(shortcut) < 0:
+            raise ValueError(f"mode = {mode!r} ('new' or 'seed'), shortcut = {shortcut} (>= 0)")
         self.robot, self.goal, self.seed, self.world, self.host = robot, np.asarray(goal, dtype=np.float64), int(seed), int(world), bool(host)
+        self.shortcut, self.mode = int(shortcut), mode
         self.obstacles = np.asarray(world_obstacles, dtype=np.float64).reshape(-1, 12)
         self.options = plan_options
         n = robot.num_factors
         cont = plan_options.get("continuous")
         self.continuous = np.array([robot.continuous[j] for j in range(n)], dtype=bool) if cont is None else np.asarray(cont, dtype=bool)
         self.calls, self.path, self.status, self.margin_min = 0, None, None, np.inf      # margin_min: over the calls so far (host only)
+        self.reused = 0
 
-    def _took(self, res, k):
-        self.calls += 1
-        self.path, self.status = res.paths[k], int(res.status[k])
+    def _noted(self, res, k):
         if res.margin is not None:
             self.margin_min = min(self.margin_min, float(res.margin[k]))
 
     def get_waypoint(self, q_cur, lookahead):
-        res = plan_trees(self.robot, self.obstacles, [q_cur], [self.goal], [call_seed(self.seed, self.world, self.calls)], host=self.host, **self.options)
-        self._took(res, 0)
-        if self.path is None:
-            return straight_line_waypoint(q_cur, self.goal, lookahead)
-        return waypoint_along(self.path, q_cur, lookahead, self.continuous)
+        return _waypoints([self], [q_cur], [lookahead])[0][0]
 
 
-def tree_hlps(worlds, robot, seed=0, host=False, batched=True, **plan_options):
+def _waypoints(hl, qs, lookaheads):
+    """One call of each of the HLPs `hl` (one robot, one obstacle count, the same options) from qs, in at most three launches: the
+    shortening of the kept paths ('seed'), the trees for the rest, the shortening of the new paths -> (waypoints, the launches' ms)."""
+    h0 = hl[0]
+    robot, host, opts = h0.robot, h0.host, h0.options
+    short = dict(edge_step=opts.get("edge_step", 0.05), continuous=opts.get("continuous"), host=host)
+    qs = [np.asarray(q, dtype=np.float64) for q in qs]
+    paths, ms = [None] * len(hl), 0.0
+    kept = [k for k, h in enumerate(hl) if h.mode == "seed" and h.path is not None]
+    if kept:
+        res = shortcut_paths(robot, np.stack([hl[k].obstacles for k in kept]), [np.vstack([qs[k][None], hl[k].path[1:]]) for k in kept],
+                             passes=max(h0.shortcut, 1), **short)
+        ms += res.ms
+        for i, k in enumerate(kept):
+            hl[k]._noted(res, i)
+            if res.status[i] == SHORTCUT_OK:
+                paths[k], hl[k].status = res.paths[i], FOUND
+                hl[k].reused += 1
+    grow = [k for k in range(len(hl)) if paths[k] is None]
+    if grow:
+        res = plan_trees(robot, np.stack([hl[k].obstacles for k in grow]), np.stack([qs[k] for k in grow]), np.stack([hl[k].goal for k in grow]),
+                         [call_seed(hl[k].seed, hl[k].world, hl[k].calls) for k in grow], host=host, **opts)
+        ms += res.ms
+        for i, k in enumerate(grow):
+            hl[k]._noted(res, i)
+            paths[k], hl[k].status = res.paths[i], int(res.status[i])
+        found = [k for k in grow if paths[k] is not None]
+        if h0.shortcut > 0 and found:
+            res = shortcut_paths(robot, np.stack([hl[k].obstacles for k in found]), [paths[k] for k in found], passes=h0.shortcut, **short)
+            ms += res.ms
+            for i, k in enumerate(found):
+                hl[k]._noted(res, i)
+                if res.status[i] != SHORTCUT_OK:
+                    raise RuntimeError(f"world {hl[k].world}: edge {int(res.first_bad[i])} of a path the tree planner just proved is not free")
+                paths[k] = res.paths[i]
+    out = []
+    for h, q, la, path in zip(hl, qs, lookaheads, paths):
+        h.calls += 1
+        h.path = path
+        out.append(straight_line_waypoint(q, h.goal, la) if path is None else waypoint_along(path, q, la, h.continuous))
+    return out, ms
+
+
+def tree_hlps(worlds, robot, seed=0, host=False, batched=True, shortcut=0, mode="new", **plan_options):
     """`worlds` as trials.run_trials takes them ([(name, problem)]) -> the factory (i, world) -> TreeHLP that run_trials(hlp=...) accepts
     (world i's obstacles padded to the worlds' largest count, its goal, the trial's seed).  With batched (the default) the factory also
-    carries get_waypoints(indices, qs, lookaheads), which plans ALL live worlds of an iteration with ONE armour_tree_plan call; the seeds are
-    the per-world objects' (call_seed), so the waypoints are the same either way.  plan_options go to plan_trees (step, edge_step,
+    carries get_waypoints(indices, qs, lookaheads), which serves ALL live worlds of an iteration with at most three launches -- one
+    armour_path_shortcut call for the worlds that hold a path (mode='seed'), ONE armour_tree_plan call for the rest, one
+    armour_path_shortcut call for the new paths (shortcut > 0) -- make.last_ms is their sum; the seeds are the per-world objects'
+    (call_seed), so the waypoints are the same either way.  shortcut / mode: TreeHLP's.  plan_options go to plan_trees (step, edge_step,
     max_iterations, max_nodes, lb, ub, continuous)."""
     probs = [p for _, p in worlds]
     obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
@@ -126,19 +224,12 @@ def tree_hlps(worlds, robot, seed=0, host=False, batched=True, **plan_options):
     made = {}
 
     def make(i, world):
-        made[i] = TreeHLP(robot, obstacles[i], goals[i], seed=seed, world=i, host=host, **plan_options)
+        made[i] = TreeHLP(robot, obstacles[i], goals[i], seed=seed, world=i, host=host, shortcut=shortcut, mode=mode, **plan_options)
         return made[i]
 
     def get_waypoints(indices, qs, lookaheads):
-        idx = [int(i) for i in indices]
-        hl = [made[i] if i in made else make(i, None) for i in idx]
-        res = plan_trees(robot, obstacles[idx], np.stack(qs), np.stack([goals[i] for i in idx]), [call_seed(seed, i, h.calls) for i, h in zip(idx, hl)],
-                         host=host, **plan_options)
-        make.last_ms = res.ms
-        out = []
-        for k, (h, q, la) in enumerate(zip(hl, qs, lookaheads)):
-            h._took(res, k)
-            out.append(straight_line_waypoint(q, h.goal, la) if h.path is None else waypoint_along(h.path, q, la, h.continuous))
+        hl = [made[int(i)] if int(i) in made else make(int(i), None) for i in indices]
+        out, make.last_ms = _waypoints(hl, qs, lookaheads)
         return out
 
     make.hlps = made

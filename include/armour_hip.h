@@ -779,6 +779,58 @@ int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, c
                           int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
                           double* path, int32_t* count, double* nodes, int32_t* parent, double* margin);
 
+/* ---- path shortening: W polylines in W worlds validated, pruned and refined in one launch (path_shortcut.hip) ---- */
+/* What a user of a sampling planner expects back, and what the reference's HLPs need to reuse their last path (HLP_grow_tree_mode =
+ * 'seed'): given a polyline per world, prove that every segment is still free and return a shorter polyline made of free segments.  It
+ * applies to any path: the tree planner's, the roadmap's, a caller's own.  The tree planner's definitions are reused as they stand:
+ * prefix(a, b) -> (m, S), the wrapped difference D(a -> b) and the wrapped distance.  An edge a -> b is FREE when m == S.  Points are kept
+ * unwrapped and are never recomputed, except for inserted midpoints.  Deterministic; the device and the host entry run the same functions.
+ *
+ * One world, its path p_0 .. p_{P-1} (P >= 2), edge_step, passes >= 1:
+ *   validate.  For s = 0 .. P - 2 in order the edge p_s -> p_{s+1} must be free.  The first s that is not gives status
+ *     ARMOUR_SHORTCUT_INVALID, first_bad = s, points = 0, passes_done = 0, length_out = 0; the world's output rows are not written.
+ *   prune(list).  i = 0, out = [p_0]; while i < last: j = the largest index > i whose edge p_i -> p_j is free, append p_j, i = j.
+ *     j = i + 1 always qualifies and is taken untested: every edge of the list is known free when prune runs.  The verdict of a candidate
+ *     is a pure function of its two end points, so the order of evaluation is the implementation's choice and does not show in the result.
+ *   refine(list).  For every consecutive pair (a, b) whose points differ bitwise: mid_j = a_j + 0.5 D_j(a -> b) (fp64, no fused multiply-
+ *     add), inserted only when a -> mid and mid -> b are both free by their own tests -- a whole edge's freedom is not inherited by its
+ *     halves, each half has its own S and its own enlargements.  If 2 count - 1 > max_points, this refine and every later pass are skipped.
+ *   the run.  validate; prune; then for each further pass: refine, prune.  Status ARMOUR_SHORTCUT_OK, first_bad = -1, passes_done = the
+ *     number of prunes that ran.
+ *   Soundness.  Every segment of an output path is an edge whose every sub-segment's enlarged test separated -- an input edge, a candidate
+ *     that prune accepted or a half that refine accepted -- so no configuration on the output collides (the tree planner's argument).
+ *   Length.  length_in / length_out = the sum of the wrapped distances of consecutive points, in index order, of the input and of the
+ *     output.  Prune replaces a chain by the wrapped-shortest edge and refine splits an edge in two: length_out <= length_in up to rounding.
+ * Limits (ARMOUR_EINVAL before a device is touched): W and O as armour_roadmap_check; 2 <= counts[w] <= max_in <=
+ *   ARMOUR_SHORTCUT_MAX_POINTS; 2 <= max_points <= ARMOUR_SHORTCUT_MAX_POINTS; 1 <= passes <= ARMOUR_SHORTCUT_MAX_PASSES; edge_step > 0
+ *   and finite; finite obstacles and points (the first counts[w] of a path; the padding is not read).  W = 0 is a success that does nothing.
+ *   ARMOUR_ECAPACITY when an edge between any two points could have more than ARMOUR_TREE_MAX_SEGMENTS sub-segments: ceil(span_j /
+ *   edge_step) with span_j = pi on a continuous joint and otherwise the extent of all the paths' points (a midpoint lies between two
+ *   points); and when a world's pruned path has more than max_points points -- points [W] is then complete and that world's rows are
+ *   unwritten (the roadmap entries' rule).
+ * Arrays are host pointers.  paths [W][max_in][n], counts [W]; outputs status / points / first_bad / passes_done [W], length_in /
+ *   length_out [W], out [W][max_points][n] (may be NULL; only the first points rows of a world are written), ms (may be NULL: device time
+ *   of the launch).
+ * Device: one launch, grid W, a 256-lane block per world, the world's obstacles and its path in LDS, ordered by __syncthreads() alone.
+ *   validate, an anchor's prune candidates (j = last, last - 1, ...) and refine's halves are each a flat work list of (candidate,
+ *   sub-segment) items laid across the lanes, several candidates to a chunk; prune stops at the first chunk after which some candidate is
+ *   fully tested and free and every candidate above it has a hit.  DESIGN.md 4.12d.
+ * armour_path_shortcut_host is the same functions in a loop and touches no device: validate in order, prune's candidates in descending j
+ *   down to i + 2, refine's a -> mid and then (only when that is free) mid -> b, each with prefix.  margin [W] (may be NULL): the smallest
+ *   |clearance| over the checks that evaluation made -- sub-segments 0 .. min(m, S - 1) of every prefix; +inf when nothing was checked. */
+#define ARMOUR_SHORTCUT_OK 0
+#define ARMOUR_SHORTCUT_INVALID 1
+#define ARMOUR_SHORTCUT_MAX_POINTS 1024
+#define ARMOUR_SHORTCUT_MAX_PASSES 8
+int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
+                         const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
+                         int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out,
+                         double* ms);
+int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles,
+                              int32_t max_in, const double* paths, const int32_t* counts, double edge_step, int32_t passes,
+                              int32_t max_points, int32_t* status, int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out,
+                              double* length_in, double* length_out, double* margin);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

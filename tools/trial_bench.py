@@ -1,7 +1,7 @@
 """Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
 and prints ONE JSON line.
 
-    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]|tree]
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]|tree [--tree-shortcut P] [--tree-mode seed]]
 
 * the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
   executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
@@ -16,7 +16,10 @@ and prints ONE JSON line.
   RRT-Connect per world and iteration, all live worlds in one armour_tree_plan call; --tree-seed, --tree-iterations, --tree-nodes):
   `hlp_outcomes_tree` holds the outcome counts beside the straight-line run's, the worlds whose outcome differs and `ms_per_batch` (hlp_ms next
   to build, solve and audit ms).  One run, one seed.  A `hlp_outcomes` section that profiles/trial_bench.json already holds (a roadmap-field
-  run) is kept, so that the three planners' rows stand side by side;
+  run) is kept, so that the three planners' rows stand side by side.  With --tree-shortcut P (every found path shortened with P passes of
+  armour_path_shortcut) and / or --tree-mode seed (the last path is offered first; a tree grows only when it fails) the run goes under
+  `hlp_outcomes_tree_seed` instead, with the number of reused paths and hard_2_wall's outcome by name, and the `hlp_outcomes_tree` row that
+  the file already holds is kept for comparison;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -106,10 +109,16 @@ def tree_trials(robot, ws, straight, a):
     from armour_amd.tree_planner import tree_hlps
     from armour_amd.trials import OUTCOMES, run_trials
     options = dict(step=0.5, edge_step=0.05, max_iterations=a.tree_iterations, max_nodes=a.tree_nodes)
-    res = run_trials(ws, hlp=tree_hlps(ws, robot, seed=a.tree_seed, **options), T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
+    make = tree_hlps(ws, robot, seed=a.tree_seed, shortcut=a.tree_shortcut, mode=a.tree_mode, **options)
+    res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
     per_batch = lambda key: dict(mean=float(np.mean([b[key] for b in res["batches"]])), max=float(np.max([b[key] for b in res["batches"]])))
     count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
-    return dict(tree=dict(options, seed=a.tree_seed), straight=count(straight), tree_outcomes=count(res), tree_summary=res["summary"],
+    extra = {}
+    if a.tree_shortcut or a.tree_mode != "new":
+        extra = dict(shortcut=a.tree_shortcut, mode=a.tree_mode, hlp_calls=int(sum(h.calls for h in make.hlps.values())),
+                     paths_reused=int(sum(h.reused for h in make.hlps.values())),
+                     hard_scenarios={w["name"]: w["outcome"] for w in res["worlds"][100:]})
+    return dict(tree=dict(options, seed=a.tree_seed, **extra), straight=count(straight), tree_outcomes=count(res), tree_summary=res["summary"],
                 ms_per_batch={key: per_batch(key) for key in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0],
                 changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
 
@@ -125,6 +134,8 @@ def main():
     ap.add_argument("--tree-seed", type=int, default=0)
     ap.add_argument("--tree-iterations", type=int, default=2000)
     ap.add_argument("--tree-nodes", type=int, default=2048)
+    ap.add_argument("--tree-shortcut", type=int, default=0)
+    ap.add_argument("--tree-mode", choices=["new", "seed"], default="new")
     ap.add_argument("--roadmap-nodes", type=int, default=20000)
     ap.add_argument("--roadmap-radius", type=float, default=1.5)
     ap.add_argument("--batched", action="store_true")
@@ -155,11 +166,13 @@ def main():
         out["hlp_outcomes"] = roadmap_field_trials(robot, ws, res, a)
     saved_json = os.path.join(ROOT, "profiles", "trial_bench.json")
     if a.hlp == "tree":
-        out["hlp_outcomes_tree"] = tree_trials(robot, ws, res, a)
+        variant = a.tree_shortcut or a.tree_mode != "new"
+        out["hlp_outcomes_tree_seed" if variant else "hlp_outcomes_tree"] = tree_trials(robot, ws, res, a)
         if os.path.exists(saved_json):
-            kept = json.load(open(saved_json)).get("hlp_outcomes")
-            if kept is not None:
-                out["hlp_outcomes"] = kept
+            saved = json.load(open(saved_json))
+            for key in ("hlp_outcomes", "hlp_outcomes_tree", "hlp_outcomes_tree_seed"):
+                if key not in out and saved.get(key) is not None:
+                    out[key] = saved[key]
     k_range, D = res["k_range"], res["duration"]
     O = max(w["obstacles"].shape[0] for w in res["worlds"])
     obs = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in res["worlds"]])
