@@ -21,6 +21,8 @@ TREE_NOT_FOUND, TREE_FOUND, TREE_START_BLOCKED, TREE_GOAL_BLOCKED, TREE_FULL = 0
 TREE_MAX_NODES, TREE_MAX_ITERATIONS = 8192, 100000   # ARMOUR_TREE_MAX_NODES, ARMOUR_TREE_MAX_ITERATIONS
 SHORTCUT_OK, SHORTCUT_INVALID = 0, 1                 # ARMOUR_SHORTCUT_*
 SHORTCUT_MAX_POINTS, SHORTCUT_MAX_PASSES = 1024, 8   # ARMOUR_SHORTCUT_MAX_POINTS, ARMOUR_SHORTCUT_MAX_PASSES
+IK_NONE_CONVERGED, IK_FOUND, IK_ALL_BLOCKED = 0, 1, 2   # ARMOUR_IK_*
+IK_MAX_SEEDS, IK_MAX_ITERATIONS, IK_MAX_TARGETS = 256, 1000, 1048576   # ARMOUR_IK_MAX_SEEDS, ARMOUR_IK_MAX_ITERATIONS, ARMOUR_IK_MAX_TARGETS
 
 
 class ArmourRobot(C.Structure):
@@ -160,6 +162,7 @@ EXPORTS = [
     "armour_roadmap_field", "armour_roadmap_descend",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
+    "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
 ]
 
 _lib = None
@@ -305,6 +308,11 @@ def load():
     short = [C.POINTER(ArmourRobot), u8p, C.c_int32, C.c_int32, dp, C.c_int32, dp, ip, C.c_double, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp, dp, dp]
     L.armour_path_shortcut.argtypes = short       # (the last pointer: ms)
     L.armour_path_shortcut_host.argtypes = short  # (the last pointer: margin [W])
+    ik = [C.POINTER(ArmourRobot), u8p, dp, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, ip, dp, dp, C.POINTER(C.c_uint64), C.c_double, C.c_double,
+          C.c_double, C.c_int32, ip, ip, dp, dp, dp, ip, ip, dp]
+    L.armour_ik.argtypes = ik                     # (the last pointer: ms)
+    L.armour_ik_host.argtypes = ik                # (the last pointer: margin [N])
+    L.armour_ik_end_effector_host.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, dp, dp, dp]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

@@ -2,6 +2,7 @@
 // tree planner's rule that both apply to an edge a -> b (the wrapped joint difference, S of a prefix, one sub-segment's verdict, the node rule,
 // the cut point), and the host twins' prefix with its margin.  include/armour_hip.h states the rule; everything here is the roadmap's
 // geometry (roadmap_handle.h) called the same way by a kernel's lanes and by a host loop.
+// The block shape and the counter hash u(seed, i, j) are also what the inverse kinematics (ik.hip) takes from here.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -17,6 +18,14 @@ constexpr int TP_BLOCK = 256;                 // four waves; a block is one worl
 constexpr int TP_WAVES = TP_BLOCK / 64;
 constexpr int TP_NONE = INT_MAX;              // "no sub-segment collides" / the index of "no node"
 
+// u(seed, i, j) of the header (the tree planner's samples, the inverse kinematics' start points): a splitmix64 finaliser of the counter, 53 bits -> [0, 1)
+__host__ __device__ inline double tree_u(uint64_t seed, uint64_t i, uint64_t j) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (((i << 8) | j) + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1p-53;
+}
 __host__ __device__ inline double joint_diff(const RmRobot& rb, int j, double a, double b) { return rb.cont[j] ? wrap_diff(a, b) : b - a; }
 // joint j of the point that ends the free prefix of m of S sub-segments of the edge a -> b
 __host__ __device__ inline double cut_joint(const RmRobot& rb, int j, double a, double b, int m, int S) { return a + ((double)m / (double)S) * joint_diff(rb, j, a, b); }

@@ -31,14 +31,6 @@ struct TreeArgs {
     double *path, *nodes;
 };
 
-// u(seed, i, j) of the header: a splitmix64 finaliser of the counter, 53 bits -> [0, 1)
-__host__ __device__ inline double tree_u(uint64_t seed, uint64_t i, uint64_t j) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (((i << 8) | j) + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (double)(z >> 11) * 0x1p-53;
-}
 __host__ __device__ inline double tree_sample(const TreeArgs& a, uint64_t seed, int i, int j) { return a.lb[j] + tree_u(seed, (uint64_t)i, (uint64_t)j) * (a.ub[j] - a.lb[j]); }
 
 // joint j of the steer step: from the nearest node a towards the sample qr, the whole way when dist = sqrt(acc) <= step

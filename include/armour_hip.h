@@ -831,6 +831,72 @@ int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t* continuou
                               int32_t max_points, int32_t* status, int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out,
                               double* length_in, double* length_out, double* margin);
 
+/* ---- batched collision-aware inverse kinematics for workspace goals (ik.hip) ---- */
+/* The reference's end-effector planner (arm_end_effector_RRT_star_HLP) takes its goal and waypoints as points of the workspace and turns
+ * each into a configuration with agent_info.inverse_kinematics(z, q_0): position only, inside the joint limits, started from a guess.  The
+ * arm is redundant (3 equations, up to ARMOUR_MAX_FACTORS joints), so which solution is useful depends on the world (it must be free) and
+ * on where the arm is (it should be near): N targets are solved from S start points each, every converged solution is judged by the node
+ * rule against its target's world, and one is picked per target.  Frames, the node rule and the wrapped distance are the roadmap's, the
+ * counter hash u(seed, i, j) is the tree planner's.  Deterministic; the device and the host entry run the same functions.
+ *
+ * One ITEM is (target t, seed s), s = 0 .. S - 1.  fp64 throughout, no fused multiply-add; dot(a, b) = (a0 b0 + a1 b1) + a2 b2.
+ * End-effector point p(q).  R = I, p = 0; for l = 0 .. J - 1 the roadmap's step along the chain (link l's translation, rpy, joint
+ *   rotation) gives the frame R_l, o_l of link l.  p(q) = o_{J-1} + R_{J-1} tool, row i: o_i + ((R_i0 tool_0 + R_i1 tool_1) + R_i2 tool_2).
+ *   tool = 0 is the last frame's origin (the reference's J(:, end)).
+ * Position Jacobian.  Column j of an actuated joint (j < n, axis_j != 0) is c_j = a_j x (p(q) - o_j), a_j = sign(axis_j) times the column
+ *   |axis_j| - 1 of R_j (the joint's world axis), the difference taken component by component and the cross product as the node rule
+ *   writes it (m0 = a1 d2 - a2 d1, ...).  A joint that is not actuated has no column (c_j = 0).
+ * Start point.  s = 0: q_j = q_ref[t][j].  s >= 1: q_j = lb_j + u(seeds[t], s, j) (ub_j - lb_j).  Then every non-continuous joint is
+ *   clipped, q_j = min(max(q_j, lb_j), ub_j); continuous joints are kept unwrapped, as tree nodes are.
+ * Iteration, k = 0, 1, ...:
+ *     e = target - p(q);  err = sqrt(dot(e, e))
+ *     err <= tol            -> CONVERGED, iterations = k
+ *     k == max_iterations   -> not converged, iterations = k
+ *     err > e_max           -> sc = e_max / err;  e_i = e_i sc
+ *     A = J J^T + lambda^2 I (3 x 3): A_ik = 0, then + c_j[i] c_j[k] for j = 0 .. n - 1 in order, then A_ii + lambda lambda
+ *     Cholesky A = L L^T:  L00 = sqrt(A00); L10 = A10 / L00; L20 = A20 / L00; L11 = sqrt(A11 - L10 L10); L21 = (A21 - L20 L10) / L11;
+ *                          L22 = sqrt((A22 - L20 L20) - L21 L21)
+ *     L z = e:    z0 = e0 / L00; z1 = (e1 - L10 z0) / L11; z2 = ((e2 - L20 z0) - L21 z1) / L22
+ *     L^T y = z:  y2 = z2 / L22; y1 = (z1 - L21 y2) / L11; y0 = ((z0 - L10 y1) - L20 y2) / L00
+ *     q_j = q_j + dot(c_j, y), then the clip of the start point
+ *   This is the damped least-squares step with a clamped error and a fixed lambda; no step is rejected.  The item's outputs are q, err and
+ *   iterations as the iteration left them.
+ * Free test.  A converged item is FREE when the node rule at q (no enlargement) separates every link box from every obstacle of world
+ *   world[t]; world[t] = -1 means no obstacles.  flags: bit 0 converged, bit 1 free (0 when not converged).
+ * Pick.  Among the items of target t with both bits, the one with the smallest (acc, s), acc = the squared wrapped distance q_ref[t] -> q
+ *   (the tree planner's order: a total order).  best[t] = that s and q_best[t] = its q; best[t] = -1 and the row unwritten with none.
+ *   status[t]: ARMOUR_IK_FOUND; ARMOUR_IK_ALL_BLOCKED (some item converged, none is free); ARMOUR_IK_NONE_CONVERGED.
+ * Limits (ARMOUR_EINVAL before a device is touched): 0 <= N <= ARMOUR_IK_MAX_TARGETS; 1 <= S <= ARMOUR_IK_MAX_SEEDS;
+ *   0 <= max_iterations <= ARMOUR_IK_MAX_ITERATIONS; lambda, e_max, tol > 0 and finite; lb <= ub, finite; finite targets, q_ref, tool and
+ *   obstacles; W and O as armour_roadmap_check; -1 <= world[t] < W.  N = 0 is a success that does nothing.
+ * Arrays are host pointers.  continuous [n] (NULL: robot->continuous); lb / ub [n]; tool [3]; obstacles [W][O][12]; world [N]; targets
+ *   [N][3]; q_ref [N][n]; seeds [N].  Outputs: status / best [N], q_best [N][n]; optional (NULL: not returned) q [N][S][n], err [N][S],
+ *   iterations [N][S], flags [N][S], ms (device time of the launch).
+ * Device: one launch, grid N, a 256-lane block per target with the world's obstacles staged in LDS, ordered by __syncthreads() alone --
+ *   no atomics, no block waits on another.  Lane s solves item s; up to 128 seeds the free test of an item is shared by G = min(O, 256 / S)
+ *   lanes, lane g with the obstacles [g O / G, (g + 1) O / G) (the verdict is the AND over obstacles, so nothing changes but the time);
+ *   the pick is a reduction of (acc, s) by shuffles and LDS.  N = 1 runs on one compute unit, and a launch lasts as long as its slowest
+ *   item.  DESIGN.md 4.12e.
+ * armour_ik_host is the same functions in a loop and touches no device.  margin [N] (may be NULL): the smallest |clearance| of the node
+ *   rule over the target's converged items -- how far the free verdicts were from one that rounding in sin / cos could flip (+inf when no
+ *   item converged or the world has no obstacles).
+ * armour_ik_end_effector_host: p [N][3] = p(q[i]) and, unless NULL, jac [N][3][n] (row r, column j = c_j[r]) for q [N][n]; host only. */
+#define ARMOUR_IK_NONE_CONVERGED 0
+#define ARMOUR_IK_FOUND 1
+#define ARMOUR_IK_ALL_BLOCKED 2
+#define ARMOUR_IK_MAX_SEEDS 256
+#define ARMOUR_IK_MAX_ITERATIONS 1000
+#define ARMOUR_IK_MAX_TARGETS 1048576
+int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
+              int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref,
+              const uint64_t* seeds, double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best,
+              double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags, double* ms);
+int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N,
+                   int32_t S, int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref,
+                   const uint64_t* seeds, double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best,
+                   double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags, double* margin);
+int armour_ik_end_effector_host(const ArmourRobot* robot, int32_t N, const double* q, const double* tool, double* p, double* jac);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory
