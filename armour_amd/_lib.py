@@ -6,6 +6,8 @@ There is no CPU path: if the shared library is missing or fails to load this mod
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ARMOUR_KEY128=1 selects the second ABI of include/armour_types.h for the whole process: libarmour_hip_k128.so (128-bit monomial keys, 8 factors)
 KEY128 = os.environ.get("ARMOUR_KEY128", "0") not in ("", "0")
@@ -13,6 +15,33 @@ LIB_PATH = os.environ.get("ARMOUR_HIP_LIB") or os.path.join(_HERE, "lib", "libar
 
 MAXJ = 9                    # ARMOUR_MAX_JOINTS
 MAXF = 8 if KEY128 else 7   # ARMOUR_MAX_FACTORS (checked against armour_abi_max_factors() of the library that was loaded)
+KEY_WORDS = 2 if KEY128 else 1   # u64 words of a monomial key as the one-operator hook passes it, low word first (sizeof(pzkey_t) / 8)
+
+
+def keys_to_words(keys):
+    """Monomial keys -> contiguous [n, KEY_WORDS] u64 array.  keys: Python integers (a list, or an array of them), a u64 array, or [n, KEY_WORDS] already."""
+    a = np.asarray(keys)
+    if a.ndim == 2:
+        assert a.shape[1] == KEY_WORDS, (a.shape, KEY_WORDS)
+        return np.ascontiguousarray(a, dtype=np.uint64)
+    out = np.zeros((len(a), KEY_WORDS), np.uint64)
+    for i, k in enumerate(a.tolist()):
+        k = int(k)
+        assert 0 <= k < 1 << (64 * KEY_WORDS), "key does not fit the library's key width"
+        for w in range(KEY_WORDS):
+            out[i, w] = (k >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def words_to_keys(words):
+    """[n, KEY_WORDS] u64 -> keys: a u64 array with one word per key (as ever), an object array of Python integers with two."""
+    if KEY_WORDS == 1:
+        return np.ascontiguousarray(words[:, 0])
+    out = np.empty(len(words), dtype=object)
+    for i in range(len(words)):
+        out[i] = sum(int(words[i, w]) << (64 * w) for w in range(KEY_WORDS))
+    return out
+
 
 OK, EINVAL, EDEVICE, ECAPACITY, ESTATE = 0, -1, -2, -3, -4
 ROADMAP_KNN_MAX = 64         # ARMOUR_ROADMAP_KNN_MAX
@@ -250,7 +279,7 @@ def load():
     L.armour_debug_qp_elastic.argtypes = [C.c_int32, dp, dp, dp, C.c_int32, dp, dp, dp, ip, ip, dp, ip, ip, ip, ip, ip]
     L.armour_debug_qp_device.argtypes = [C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip, ip, dp, ip]
     L.armour_debug_pz_op.argtypes = [vp, C.c_int32, C.c_int32, ip, ip, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(dp), dp, dp, dp, dp,
-                                     C.c_int32, C.c_int32, C.POINTER(C.c_uint64), dp, dp]
+                                     C.c_int32, C.c_int32, C.POINTER(C.c_uint64), dp, dp, C.c_int32, C.c_int32]
     L.armour_get_torque_radius.argtypes = [vp, dp]
     L.armour_get_link_generators.argtypes = [vp, dp]
     L.armour_get_link_centers.argtypes = [vp, dp, dp]

@@ -967,15 +967,38 @@ extern "C" int armour_get_hyperplanes(ArmourPlanner* h, double* A, double* d, do
     return ARMOUR_OK;
 }
 
+// The operand shapes of the one-operator hook's op codes (include/armour_hip.h): entries per coefficient of each operand, 0 behind the last one.
+// Code 12 takes its third operand as 3x1 (r < 0) or as 1x1 embedded into entry r.
+static const int kPzOpShapes[18][4] = {
+    {9, 3, 0, 0}, {9, 9, 0, 0}, {1, 1, 0, 0}, {1, 3, 0, 0}, {3, 3, 0, 0}, {3, 3, 0, 0}, {3, 1, 0, 0}, {1, 1, 1, 0}, {3, 0, 0, 0}, {3, 0, 0, 0}, {3, 3, 0, 0}, {1, 1, 0, 0},
+    {3, 3, 3, 0}, {3, 3, 3, 3}, {1, 1, 1, 0}, {1, 0, 0, 0}, {3, 3, 3, 0}, {9, 0, 0, 0}};
+// what the hook requires of an op code's operands; nullptr, or what is wrong
+static const char* pz_op_operands_wrong(const ArmourPlanner* h, int op, int nops, const int32_t* sz, const int32_t* cnt, int r) {
+    if (op < 0 || op > 17) return "unknown op code";
+    if (!sz || !cnt) return "null argument";
+    for (int o = 0; o < 4; o++) {
+        const int want = (op == 12 && o == 2 && r >= 0) ? 1 : kPzOpShapes[op][o];
+        if (want == 0) { if (nops != o) return "wrong number of operands for this op code"; break; }
+        if (o >= nops) return "wrong number of operands for this op code";
+        if (sz[o] != want) return "an operand's shape is not the op code's";
+        if (cnt[o] < 0 || cnt[o] > h->lim.work_monomials || (sz[o] == 9 && o == 1 && cnt[o] > 8)) return "an operand has more monomials than its slot holds";
+    }
+    if ((op == 6 || op == 15) && (r < 0 || r > 2)) return "r is not an entry of a 3-vector";
+    if (op == 12 && (r < -1 || r > 2)) return "r is neither -1 nor an entry of a 3-vector";
+    return nullptr;
+}
+// sort-buffer entries as the caller may choose them: powers of two, at least a wave's worth, 16-bit term indices
+static bool pz_op_cap_ok(int cap) { return cap >= 64 && cap <= 8192 && (cap & (cap - 1)) == 0; }
+
 extern "C" int armour_debug_pz_op(ArmourPlanner* h, int32_t op, int32_t nops, const int32_t* sz, const int32_t* cnt, const uint64_t* const* keys,
                                   const double* const* coef, const double* cen, const double* ind, const double* ind2, const double* consts,
-                                  int32_t r, int32_t out_cap, uint64_t* out_keys, double* out_coef, double* out_misc) {
-    if (!h || nops < 1 || nops > 3 || op < 0 || op > 11) { armour_set_error("armour_debug_pz_op: bad argument"); return ARMOUR_EINVAL; }
-    for (int o = 0; o < nops; o++)
-        if ((sz[o] != 1 && sz[o] != 3 && sz[o] != 9) || cnt[o] < 0 || cnt[o] > h->lim.work_monomials || (sz[o] == 9 && o == 1 && cnt[o] > 8)) {
-            armour_set_error("armour_debug_pz_op: bad operand"); return ARMOUR_EINVAL;
-        }
-    return armour_p1_debug_pz_op(h, op, nops, sz, cnt, keys, coef, cen, ind, ind2, consts, r, out_cap, out_keys, out_coef, out_misc);
+                                  int32_t r, int32_t out_cap, uint64_t* out_keys, double* out_coef, double* out_misc, int32_t cap_key, int32_t cap_raw) {
+    if (!h || out_cap < 0 || !keys || !coef || !cen || !ind || !ind2 || !out_keys || !out_coef || !out_misc) { armour_set_error("armour_debug_pz_op: bad argument"); return ARMOUR_EINVAL; }
+    if (const char* why = pz_op_operands_wrong(h, op, nops, sz, cnt, r)) { armour_set_error("armour_debug_pz_op: op %d: %s", op, why); return ARMOUR_EINVAL; }
+    if ((cap_key != 0 || cap_raw != 0) && !(pz_op_cap_ok(cap_key) && pz_op_cap_ok(cap_raw))) {
+        armour_set_error("armour_debug_pz_op: cap_key / cap_raw are 0, 0 or powers of two in [64, 8192]"); return ARMOUR_EINVAL;
+    }
+    return armour_p1_debug_pz_op(h, op, nops, sz, cnt, keys, coef, cen, ind, ind2, consts, r, out_cap, out_keys, out_coef, out_misc, cap_key, cap_raw);
 }
 
 extern "C" int armour_get_plane_skip(ArmourPlanner* h, uint64_t* plane_skip) {

@@ -259,4 +259,4 @@ inline int armour_p1_auto_kernel(int B, int T, int min_groups, bool fk_only) {
 
 int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, const int* cnt, const uint64_t* const* keys,
                           const double* const* coef, const double* cen, const double* ind, const double* ind2, const double* consts,
-                          int r, int out_cap, uint64_t* out_keys, double* out_coef, double* out_misc);
+                          int r, int out_cap, uint64_t* out_keys, double* out_coef, double* out_misc, int cap_key, int cap_raw);

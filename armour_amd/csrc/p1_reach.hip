@@ -1678,12 +1678,15 @@ __global__ __launch_bounds__(256) void armour_p1_skip_reduce_kernel(const unsign
 // Operand block layout (doubles / u64 in two flat buffers): see armour_debug_pz_op in api.  ops:
 //   0 mul 3x3*3x1   1 mul 3x3*3x3   2 mul 1x1*1x1   3 mul 1x1*3x1   4 a+b (3x1)   5 a-b (3x1)   6 addOneDimPZ(a 3x1, b 1x1, r)
 //   7 stack(a,b,c 1x1)   8 cross(a 3x1, const)   9 cross(const, a 3x1)   10 cross(a 3x1, b 3x1)   11 sa*a + sb*b (1x1)
+//   12 sum3(a, b, c; c 1x1 into entry r when r >= 0)   13 sum4(a, b, c, d)   14 comb3 (1x1, scales in consts)   15 embedOneDim(a 1x1, r)
+//   16 sum3(a, crossPzMat(w, consts), c)   17 transpose33
+// Keys: kPzKeyWords u64 words each, low word first (pz_key.h).
 struct PzOpArgs {
     int op, nops, r;
-    int sz[3], cnt[3];
-    const uint64_t* keys[3];
-    const double* coef[3];
-    double cen[3][9], ind[3][9], ind2[3][9];
+    int sz[4], cnt[4];
+    const uint64_t* keys[4];
+    const double* coef[4];
+    double cen[4][9], ind[4][9], ind2[4][9];
     double consts[4];
     uint64_t* out_keys; double* out_coef; double* out_misc;  // misc: cnt, cen[9], ind[9], ind2[9]
     int out_cap;
@@ -1718,12 +1721,12 @@ __global__ __launch_bounds__(64) P1_OCC void armour_p1_pzop_kernel(P1Cfg cf, con
     c.freeV = (1ull << c.L.nV) - 1ull; c.freeS = (1u << kNS) - 1u;
     for (int i = threadIdx.x; i < kMaxSlots; i += WAVE) c.w.cnt[i] = 0;
     __syncthreads();
-    PZ in[3];
+    PZ in[4];
     for (int o = 0; o < a.nops; o++) {
         // 3x3 operands: the first in a work slot, the second in a small (<= 8 monomials) slot like a joint rotation
         in[o] = a.sz[o] == 9 ? (o == 0 ? c.M(0) : c.JM(0)) : a.sz[o] == 3 ? c.allocV() : c.allocS();
         const int n = a.cnt[o], sz = a.sz[o];
-        for (int m = threadIdx.x; m < n; m += WAVE) in[o].keys[m] = (pzkey_t)a.keys[o][m];
+        for (int m = threadIdx.x; m < n; m += WAVE) in[o].keys[m] = pzkey_from_words(a.keys[o] + (size_t)m * kPzKeyWords);
         for (int m = threadIdx.x; m < n * sz; m += WAVE) in[o].coef[m] = a.coef[o][m];
         if (threadIdx.x < sz) { in[o].cen[threadIdx.x] = a.cen[o][threadIdx.x]; in[o].ind[threadIdx.x] = a.ind[o][threadIdx.x]; in[o].ind2[threadIdx.x] = a.ind2[o][threadIdx.x]; }
         if (threadIdx.x == 0) c.w.cnt[in[o].id] = n;
@@ -1747,6 +1750,12 @@ __global__ __launch_bounds__(64) P1_OCC void armour_p1_pzop_kernel(P1Cfg cf, con
         case 8: out = c.crossPzMat(in[0], a.consts); break;
         case 9: out = c.crossMatPz(a.consts, in[0]); break;
         case 10: out = c.crossPzPz(in[0], in[1]); break;
+        case 12: out = c.sum3(in[0], in[1], in[2], a.r); break;
+        case 13: out = c.sum4(in[0], in[1], in[2], in[3]); break;
+        case 14: out = c.comb3(view(w, in[0]), a.consts[0], view(w, in[1]), a.consts[1], view(w, in[2]), a.consts[2]); break;
+        case 15: out = c.embedOneDim(in[0], a.r); break;
+        case 16: { const PZ x = c.crossPzMat(in[1], a.consts); out = c.sum3(in[0], x, in[2]); } break;
+        case 17: out = c.M(1); transpose33(w, out, in[0]); break;
         default: out = c.comb2(view(w, in[0]), a.consts[0], view(w, in[1]), a.consts[1]); break;
     }
     const long long cyc1 = clock64();
@@ -1757,7 +1766,7 @@ __global__ __launch_bounds__(64) P1_OCC void armour_p1_pzop_kernel(P1Cfg cf, con
         for (int i = 0; i < PR_WORDS && 32 + i < 64; i++) a.out_misc[32 + i] = (double)w.prof[i];
 #endif
     }
-    for (int m = threadIdx.x; m < n && m < a.out_cap; m += WAVE) a.out_keys[m] = (uint64_t)out.keys[m];   // (a 128-bit key build hands back the low word: the operator tests run on the 64-bit build)
+    for (int m = threadIdx.x; m < n && m < a.out_cap; m += WAVE) pzkey_to_words(out.keys[m], a.out_keys + (size_t)m * kPzKeyWords);
     for (int m = threadIdx.x; m < n * sz && m < a.out_cap * sz; m += WAVE) a.out_coef[m] = out.coef[m];
     {   // the operator's prune margin (pz_wave.h Wave::mg): the smallest |squared norm - thr_sq| over the lanes -> out_misc[60]; thr_sq -> [61]
         double m = w.mg[threadIdx.x];
@@ -1857,13 +1866,17 @@ static size_t ci_doubles(const Layout& L) { return (size_t)L.nV * 9 + kNS * 3 + 
 // test hook (include/armour_hip.h: armour_debug_pz_op)
 int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, const int* cnt, const uint64_t* const* keys,
                           const double* const* coef, const double* cen, const double* ind, const double* ind2, const double* consts,
-                          int r, int out_cap, uint64_t* out_keys, double* out_coef, double* out_misc) {
+                          int r, int out_cap, uint64_t* out_keys, double* out_coef, double* out_misc, int cap_key, int cap_raw) {
     HIPCHK(hipSetDevice(h->device));
     const int J = h->J, n = h->n;
-    int cap_raw = 64;
-    while (cap_raw < h->lim.raw_terms) cap_raw <<= 1;
+    if (cap_raw == 0) {   // (0, 0: full-width key buffers of the handle's raw-term limit; otherwise the shape a build's wave has, e.g. kFkCapKey / kFkCapRaw)
+        cap_raw = 64;
+        while (cap_raw < h->lim.raw_terms) cap_raw <<= 1;
+        cap_key = cap_raw;
+    }
     const Layout L = make_layout(J, n, h->lim.work_monomials, 1);
-    const size_t smem = p1_wave_lds(cap_raw, cap_raw) + p1_shared_lds(ci_doubles(L));
+    const size_t smem = p1_wave_lds(cap_key, cap_raw) + p1_shared_lds(ci_doubles(L));
+    if (smem > (size_t)160 * 1024) { armour_set_error("armour_debug_pz_op: sort buffers of %d keys / %d raw terms do not fit the LDS", cap_key, cap_raw); return ARMOUR_EINVAL; }
     HIPCHK(hipFuncSetAttribute((const void*)armour_p1_pzop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     unsigned char* arena = nullptr;
     HIPCHK(hipMalloc((void**)&arena, L.total));
@@ -1880,19 +1893,19 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
     };
     for (int o = 0; o < nops; o++) {
         a.sz[o] = sz[o]; a.cnt[o] = cnt[o];
-        a.keys[o] = (const uint64_t*)up(keys[o], (size_t)cnt[o] * 8);
+        a.keys[o] = (const uint64_t*)up(keys[o], (size_t)cnt[o] * sizeof(pzkey_t));
         a.coef[o] = (const double*)up(coef[o], (size_t)cnt[o] * sz[o] * 8);
         for (int e = 0; e < sz[o]; e++) { a.cen[o][e] = cen[o * 9 + e]; a.ind[o][e] = ind[o * 9 + e]; a.ind2[o][e] = ind2[o * 9 + e]; }
     }
     for (int i = 0; i < 4; i++) a.consts[i] = consts ? consts[i] : 0.0;
-    a.out_keys = (uint64_t*)up(nullptr, (size_t)out_cap * 8);
+    a.out_keys = (uint64_t*)up(nullptr, (size_t)out_cap * sizeof(pzkey_t));
     a.out_coef = (double*)up(nullptr, (size_t)out_cap * 9 * 8);
     a.out_misc = (double*)up(nullptr, 64 * 8);
     if (a.out_misc) (void)hipMemset(a.out_misc, 0, 64 * 8);
     P1Cfg cf;
     memset(&cf, 0, sizeof(cf));
     cf.B = 1; cf.T = h->T; cf.J = J; cf.n = n;
-    cf.capW = h->lim.work_monomials; cf.capRaw = cap_raw; cf.capKey = cap_raw; /* (the one-operator test hook: full-width key buffers) */ cf.capL = h->lim.link_monomials; cf.capT = h->lim.torque_monomials;
+    cf.capW = h->lim.work_monomials; cf.capRaw = cap_raw; cf.capKey = cap_key; cf.capL = h->lim.link_monomials; cf.capT = h->lim.torque_monomials;
     cf.arena_bytes = L.total; cf.arena = arena;
     cf.rb = h->robot; cf.pr = h->params; cf.ub = h->ub;
     const PzOpArgs* d_args = (const PzOpArgs*)up(&a, sizeof(a));
@@ -1900,7 +1913,7 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) {
-        (void)hipMemcpy(out_keys, a.out_keys, (size_t)out_cap * 8, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(out_keys, a.out_keys, (size_t)out_cap * sizeof(pzkey_t), hipMemcpyDeviceToHost);
         (void)hipMemcpy(out_coef, a.out_coef, (size_t)out_cap * 9 * 8, hipMemcpyDeviceToHost);
         (void)hipMemcpy(out_misc, a.out_misc, 64 * 8, hipMemcpyDeviceToHost);
     }

@@ -20,6 +20,22 @@ typedef uint64_t pzkey_t;
 #define PZKEY_MAX (~(pzkey_t)0)
 __host__ __device__ inline pzkey_t pzkey_bit(int s) { return (pzkey_t)1 << s; }
 
+// A key as the one-operator test hook passes it (include/armour_hip.h: armour_debug_pz_op): kPzKeyWords u64 words, low word first
+constexpr int kPzKeyWords = (int)(sizeof(pzkey_t) / sizeof(uint64_t));
+__host__ __device__ inline pzkey_t pzkey_from_words(const uint64_t* w) {
+    pzkey_t k = (pzkey_t)w[0];
+#if defined(ARMOUR_KEY128)
+    k |= (pzkey_t)w[1] << 64;
+#endif
+    return k;
+}
+__host__ __device__ inline void pzkey_to_words(pzkey_t k, uint64_t* w) {
+    w[0] = (uint64_t)k;
+#if defined(ARMOUR_KEY128)
+    w[1] = (uint64_t)(k >> 64);
+#endif
+}
+
 // lane l's key, in every lane (l wave-uniform)
 __device__ inline pzkey_t pzkey_readlane(pzkey_t v, int l) {
     const uint64_t lo = (uint64_t)v;

@@ -547,15 +547,25 @@ const char* armour_p2_kernel_name(void);
 /* Runs the device implementation of one operator of RT/PZsparse.cu (the same functions the reach-set kernel uses):
  *   op 0 mul 3x3*3x1, 1 mul 3x3*3x3, 2 mul 1x1*1x1, 3 mul 1x1*3x1 (:864-994); 4 a+b, 5 a-b on 3x1 (:743-834);
  *   6 addOneDimPZ(a 3x1, b 1x1, r) (:1068-1085); 7 stack(a,b,c) (:1087-1116); 8 cross(a, const), 9 cross(const, a),
- *   10 cross(a, b) (:1118-1167); 11 consts[0]*a + consts[1]*b on 1x1 (:996-1030 + :743-764).
- * Operand o: sz[o] in {1,3,9} entries per coefficient (row-major), cnt[o] monomials with keys[o][cnt] sorted unique and
- * coef[o][cnt][sz]; cen / ind / ind2 are [nops][9].  Result: out_keys[<=out_cap], out_coef[<=out_cap][sz],
+ *   10 cross(a, b) (:1118-1167); 11 consts[0]*a + consts[1]*b on 1x1 (:996-1030 + :743-764);
+ * and the compound operators of the reach-set chain, each the composition named with simplify() after every step:
+ *   12 sum3 = (a + b) + c on 3x1, with r >= 0: c is 1x1 and goes into entry r (addOneDimPZ), r = -1: c is 3x1;  13 sum4 = ((a + b) + c) + d on 3x1;
+ *   14 comb3 = (consts[0]*a + consts[1]*b) + consts[2]*c on 1x1;  15 embedOneDim = addOneDimPZ(PZsparse(0,0,0), a 1x1, r);
+ *   16 (a + cross(w, consts)) + c on 3x1, operands a, w, c;  17 transpose of a 3x3 (:1050-1066, no simplify).
+ * Operand o: sz[o] entries per coefficient (row-major) -- 1, 3 or 9 as the op code's operator takes them, anything else is ARMOUR_EINVAL --,
+ * cnt[o] monomials with keys[o][cnt] sorted unique and coef[o][cnt][sz]; cen / ind / ind2 are [nops][9]; nops <= 4.  A key is passed in the
+ * library's own width: sizeof(pzkey_t) / 8 u64 words, low word first -- one word in the 7-factor ABI, two in the 8-factor (128-bit key) ABI of
+ * include/armour_types.h --, in keys[o] and in out_keys alike.
+ * cap_key, cap_raw: the entries of the wave's two sort buffers (keys | term indices): 0, 0 = both as wide as the handle's raw-term limit; otherwise
+ * powers of two in [64, 8192] -- the builds give the fourth wave of a four-wave block 1024 / 2048 and every wave of the 128-bit ABI cap / 2 keys,
+ * and the sorter an operator takes depends on the two separately.
+ * Result: out_keys[<=out_cap], out_coef[<=out_cap][sz],
  * out_misc[64] = {count, sz, error flags, cen[9], ind[9], ind2[9], [30] the operator's shader-clock cycles, [31] raw terms,
  * [32..] phase counters in -DP1_PROFILE builds, [60] the smallest |s - [61]| over the SQUARED norms s of the operator's simplify() verdicts,
  * [61] the squared threshold they were compared with (+inf in [60]: no verdict; armour_get_prune_margin)}. */
 int armour_debug_pz_op(ArmourPlanner* h, int32_t op, int32_t nops, const int32_t* sz, const int32_t* cnt, const uint64_t* const* keys,
                        const double* const* coef, const double* cen, const double* ind, const double* ind2, const double* consts,
-                       int32_t r, int32_t out_cap, uint64_t* out_keys, double* out_coef, double* out_misc);
+                       int32_t r, int32_t out_cap, uint64_t* out_keys, double* out_coef, double* out_misc, int32_t cap_key, int32_t cap_raw);
 
 /* ---- test hook: load externally built reach-set tables instead of running P1 ---- */
 /* Used only by tests to isolate P2 (tables built by the CPU oracle); never called by the product path.

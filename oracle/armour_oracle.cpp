@@ -859,7 +859,8 @@ void oracle_slice_links(void* h, const double* k, double* center /*[T][J][3]*/) 
     Ctx cx; cx.kl.n = P.n;
     for (int t = 0; t < P.T; t++) for (int l = 0; l < P.J; l++) slice_value(cx, P.links[l * P.T + t], k, &center[(t * P.J + l) * 3], nullptr);
 }
-/* one operator of pz.hpp on caller-supplied operands (mirror of armour_debug_pz_op, same op codes and layout) */
+/* one operator of pz.hpp on caller-supplied operands (mirror of armour_debug_pz_op, same op codes 0-11 and layout; a key is sizeof(okey_t) / 8
+ * u64 words, low word first: one word here, two in the -DARMOUR_KEY128 build) */
 int oracle_pz_op(int op, int nops, const int* sz, const int* cnt, const uint64_t* const* keys, const double* const* coef,
                  const double* cen, const double* ind, const double* consts, int r, double threshold, int out_cap,
                  uint64_t* out_keys, double* out_coef, double* out_misc) {
@@ -870,7 +871,9 @@ int oracle_pz_op(int op, int nops, const int* sz, const int* cnt, const uint64_t
         for (int e = 0; e < sz[o]; e++) { in[o].center[e] = cen[o * 9 + e]; in[o].indep[e] = ind[o * 9 + e]; }
         for (int m = 0; m < cnt[o]; m++) {
             Mono mo{};
-            mo.key = keys[o][m];
+            const int kw = (int)(sizeof(okey_t) / sizeof(uint64_t));
+            mo.key = 0;
+            for (int w = kw - 1; w >= 0; w--) mo.key = (okey_t)(mo.key << (kw > 1 ? 64 : 0)) | keys[o][(size_t)m * kw + w];
             for (int e = 0; e < sz[o]; e++) mo.c[e] = coef[o][(size_t)m * sz[o] + e];
             in[o].poly.push_back(mo);
         }
@@ -890,7 +893,8 @@ int oracle_pz_op(int op, int nops, const int* sz, const int* cnt, const uint64_t
     const int n = (int)out.poly.size(), osz = out.sz();
     if (n > out_cap) return -1;
     for (int m = 0; m < n; m++) {
-        out_keys[m] = (uint64_t)out.poly[m].key;
+        const int kw = (int)(sizeof(okey_t) / sizeof(uint64_t));
+        for (int w = 0; w < kw; w++) out_keys[(size_t)m * kw + w] = (uint64_t)(out.poly[m].key >> (kw > 1 ? 64 * w : 0));
         for (int e = 0; e < osz; e++) out_coef[(size_t)m * osz + e] = out.poly[m].c[e];
     }
     out_misc[0] = n; out_misc[1] = osz; out_misc[2] = cx.st.min_margin;

@@ -275,13 +275,42 @@ def max_threads():
     return lib().oracle_max_threads()
 
 
+KEY_WORDS = 2 if KEY128 else 1   # u64 words of a monomial key, low word first (sizeof(okey_t) / 8)
+
+
+def keys_to_words(keys):
+    """Monomial keys -> contiguous [n, KEY_WORDS] u64 array.  keys: Python integers (a list, or an array of them), a u64 array, or [n, KEY_WORDS] already."""
+    a = np.asarray(keys)
+    if a.ndim == 2:
+        assert a.shape[1] == KEY_WORDS, (a.shape, KEY_WORDS)
+        return np.ascontiguousarray(a, dtype=np.uint64)
+    out = np.zeros((len(a), KEY_WORDS), np.uint64)
+    for i, k in enumerate(a.tolist()):
+        k = int(k)
+        assert 0 <= k < 1 << (64 * KEY_WORDS), "key does not fit the library's key width"
+        for w in range(KEY_WORDS):
+            out[i, w] = (k >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def words_to_keys(words):
+    """[n, KEY_WORDS] u64 -> keys: a u64 array with one word per key, an object array of Python integers with two."""
+    if KEY_WORDS == 1:
+        return np.ascontiguousarray(words[:, 0])
+    out = np.empty(len(words), dtype=object)
+    for i in range(len(words)):
+        out[i] = sum(int(words[i, w]) << (64 * w) for w in range(KEY_WORDS))
+    return out
+
+
 def pz_op(op, operands, consts=None, r=0, threshold=5e-4, out_cap=1 << 16):
-    """One PZ operator of the restatement (op codes of armour_debug_pz_op).  operands: list of dicts
-    {sz, keys[cnt] u64, coef[cnt, sz], cen[sz], ind[sz]}.  Returns dict(keys, coef, cen, ind, min_margin)."""
+    """One PZ operator of the restatement (op codes 0-11 of armour_debug_pz_op).  operands: list of dicts
+    {sz, keys[cnt], coef[cnt, sz], cen[sz], ind[sz]}; keys as keys_to_words takes them, returned as words_to_keys gives them.
+    Returns dict(keys, coef, cen, ind, min_margin)."""
     n = len(operands)
     sz = (C.c_int * n)(*[o["sz"] for o in operands])
     cnt = (C.c_int * n)(*[len(o["keys"]) for o in operands])
-    ks = [np.ascontiguousarray(o["keys"], dtype=np.uint64) if len(o["keys"]) else np.zeros(1, np.uint64) for o in operands]
+    ks = [keys_to_words(o["keys"]) if len(o["keys"]) else np.zeros((1, KEY_WORDS), np.uint64) for o in operands]
     cs = [np.ascontiguousarray(o["coef"], dtype=np.float64).reshape(-1) if len(o["keys"]) else np.zeros(1) for o in operands]
     kp = (C.POINTER(C.c_uint64) * n)(*[k.ctypes.data_as(C.POINTER(C.c_uint64)) for k in ks])
     cp = (C.POINTER(C.c_double) * n)(*[_dp(c) for c in cs])
@@ -289,13 +318,13 @@ def pz_op(op, operands, consts=None, r=0, threshold=5e-4, out_cap=1 << 16):
     for i, o in enumerate(operands):
         cen[i, :o["sz"]] = o["cen"]; ind[i, :o["sz"]] = o["ind"]
     cst = np.zeros(4) if consts is None else np.ascontiguousarray(np.concatenate([np.asarray(consts, dtype=np.float64), np.zeros(4)])[:4])
-    ok, oc, misc = np.zeros(out_cap, np.uint64), np.zeros(out_cap * 9), np.zeros(32)
+    ok, oc, misc = np.zeros((out_cap, KEY_WORDS), np.uint64), np.zeros(out_cap * 9), np.zeros(32)
     rc = lib().oracle_pz_op(op, n, sz, cnt, kp, cp, _dp(cen), _dp(ind), _dp(cst), r, threshold, out_cap,
                             ok.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(oc), _dp(misc))
     if rc != 0:
         raise RuntimeError("oracle_pz_op overflow")
     m, osz = int(misc[0]), int(misc[1])
-    return dict(keys=ok[:m].copy(), coef=oc[:m * osz].reshape(m, osz).copy(), cen=misc[3:3 + osz].copy(), ind=misc[12:12 + osz].copy(), min_margin=misc[2])
+    return dict(keys=words_to_keys(ok[:m]), coef=oc[:m * osz].reshape(m, osz).copy(), cen=misc[3:3 + osz].copy(), ind=misc[12:12 + osz].copy(), min_margin=misc[2])
 
 
 def robust_controller(Kr, alpha, V_max, r_thr, q, qd, q_des, qd_des, qdd_des, eps=0.03, robot=None):
