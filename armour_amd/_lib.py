@@ -178,7 +178,7 @@ EXPORTS = [
     "armour_get_link_generators", "armour_get_link_centers", "armour_get_pz", "armour_get_table_sizes",
     "armour_solve_options_default", "armour_solve", "armour_debug_qp", "armour_debug_qp_box", "armour_debug_qp_elastic", "armour_debug_qp_device", "armour_debug_pz_op",
     "armour_get_hyperplanes", "armour_get_build_ms", "armour_get_build_info", "armour_p2_kernel_name", "armour_debug_load_tables",
-    "armour_get_plane_skip", "armour_get_prune_margin", "armour_batch_get_prune_margin", "armour_set_option", "armour_get_option", "armour_controller_set_kernel", "armour_device_memory", "armour_abi_max_factors", "armour_eval_violations_device", "armour_eval_violations", "armour_get_row_relevance", "armour_get_solver_rows",
+    "armour_get_plane_skip", "armour_get_prune_margin", "armour_batch_get_prune_margin", "armour_set_option", "armour_get_option", "armour_controller_set_kernel", "armour_device_memory", "armour_abi_max_factors", "armour_eval_violations_device", "armour_eval_violations", "armour_get_row_relevance", "armour_get_solver_rows", "armour_debug_get_row_lists",
     "armour_batch_partition", "armour_batch_create", "armour_batch_destroy", "armour_batch_set_option", "armour_batch_set_problems",
     "armour_batch_get_sizes", "armour_batch_get_bounds", "armour_batch_eval_g_jac", "armour_batch_eval_violations", "armour_batch_solve",
     "armour_batch_get_build_ms", "armour_batch_get_build_info",
@@ -302,6 +302,7 @@ def load():
     L.armour_eval_violations.argtypes = [vp, dp, C.POINTER(ArmourViolation)]
     L.armour_get_row_relevance.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.armour_get_solver_rows.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    L.armour_debug_get_row_lists.argtypes = [vp, C.c_int32, ip, ip, ip, ip, C.POINTER(C.c_int64), dp, C.c_int64, C.POINTER(C.c_int64)]
     L.armour_batch_partition.argtypes = [C.c_int32, C.c_int32, ip]
     L.armour_batch_create.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourParams), C.POINTER(ArmourLimits), ip, C.c_int32, C.POINTER(vp)]
     L.armour_batch_destroy.argtypes = [vp]

@@ -422,6 +422,39 @@ extern "C" int armour_get_solver_rows(ArmourPlanner* h, uint8_t* solver_rows, in
     return ARMOUR_OK;
 }
 
+// test hook: the lists as they stand on the device (copies only; armour_hip.h)
+extern "C" int armour_debug_get_row_lists(ArmourPlanner* h, int32_t which, int32_t* rows, int32_t* count, int32_t* aux, int32_t* aux_count,
+                                          int64_t* pack_off, double* packed, int64_t packed_capacity, int64_t* packed_total) {
+    if (!h || !h->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
+    if (which != 0 && which != 1) { armour_set_error("armour_debug_get_row_lists: which = %d (0 relevance, 1 solver)", which); return ARMOUR_EINVAL; }
+    const RelLists& L = which == 0 ? h->rel : h->rel2;
+    if (!L.fresh) { armour_set_error("the row lists of this problem set are not built: call armour_get_%s first", which == 0 ? "row_relevance" : "solver_rows"); return ARMOUR_ESTATE; }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t B = (size_t)h->B, Q = (size_t)h->Q;
+    std::vector<long long> off;
+    const long long total = pack_offsets(h, L.h_count, off);
+    if (packed_total) *packed_total = total;
+    if (packed && packed_capacity < total) { armour_set_error("armour_debug_get_row_lists: packed_capacity %lld < %lld", (long long)packed_capacity, total); return ARMOUR_EINVAL; }
+    if (rows && Q > 0) HIPCHK(hipMemcpy(rows, L.rows, B * Q * sizeof(int), hipMemcpyDeviceToHost));
+    if (count) HIPCHK(hipMemcpy(count, L.count, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (which == 0) {
+        const size_t per = (Q + 255) / 256;
+        if (aux && per > 0) HIPCHK(hipMemcpy(aux, L.extra, B * 256 * per * sizeof(int), hipMemcpyDeviceToHost));
+        if (aux_count) HIPCHK(hipMemcpy(aux_count, L.count + B, B * 256 * sizeof(int), hipMemcpyDeviceToHost));
+    } else {
+        if (aux && h->row0 > 0) HIPCHK(hipMemcpy2D(aux, (size_t)h->row0 * sizeof(int), L.extra, (size_t)h->rel2_tq_cap * sizeof(int), (size_t)h->row0 * sizeof(int), B, hipMemcpyDeviceToHost));
+        if (aux_count) HIPCHK(hipMemcpy(aux_count, L.count + B, B * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (pack_off) {
+        std::vector<long long> d_off(2 * B);
+        HIPCHK(hipMemcpy(d_off.data(), L.pack_off, 2 * B * sizeof(long long), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < 2 * B; i++) pack_off[i] = d_off[i];
+    }
+    if (packed && total > 0) HIPCHK(hipMemcpy(packed, L.packed, (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    return ARMOUR_OK;
+}
+
 // the culled form of armour_eval_violations_device (api.hip): torque + limit blocks of the fused evaluation, the listed collision rows, the
 // row test over the same rows
 int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourViolation* d_out, hipStream_t st) {

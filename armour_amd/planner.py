@@ -511,6 +511,24 @@ class ArmourNLP:
         check(self.L.armour_get_solver_rows(self.h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), cnt.ctypes.data_as(i32), tq.ctypes.data_as(i32), C.byref(ms)))
         return mask.astype(bool), cnt, tq, ms.value
 
+    def debug_row_lists(self, which):
+        """Test hook (armour_debug_get_row_lists): the row lists behind row_relevance() (which = 0) or solver_rows() (which = 1), which must have
+        been called for this problem set.  dict(rows [B, Q], count [B], aux, aux_count, pack_off [B, 2], packed): aux = the rows by residue class
+        [B, 256, ceil(Q / 256)] with aux_count [B, 256] (which = 0), or the mask's torque rows [B, row0] with aux_count [B] (which = 1)."""
+        B, Q, row0 = self.B, self.J * self.T * self.O, self.m - self.J * self.T * self.O - 4 * self.n
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        rows, count = np.full((B, Q), -1, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        if which == 0:
+            aux, aux_count = np.full((B, 256, (Q + 255) // 256), -1, dtype=np.int32), np.zeros((B, 256), dtype=np.int32)
+        else:
+            aux, aux_count = np.full((B, row0), -1, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        pack_off, total = np.zeros((B, 2), dtype=np.int64), C.c_int64()
+        check(self.L.armour_debug_get_row_lists(self.h, which, None, None, None, None, None, None, 0, C.byref(total)))
+        packed = np.zeros(max(total.value, 1))
+        check(self.L.armour_debug_get_row_lists(self.h, which, rows.ctypes.data_as(i32), count.ctypes.data_as(i32), aux.ctypes.data_as(i32),
+                                                aux_count.ctypes.data_as(i32), pack_off.ctypes.data_as(i64), _dp(packed), total.value, None))
+        return dict(rows=rows, count=count, aux=aux, aux_count=aux_count, pack_off=pack_off, packed=packed[:total.value])
+
     def eval_violations_device(self, d_k, d_out, stream=0):
         """Asynchronous: d_k [B][n] doubles, d_out [B] ArmourViolation records (32 B each), device pointers (ints)."""
         check(self.L.armour_eval_violations_device(self.h, d_k, d_out, stream))

@@ -268,12 +268,28 @@ int armour_eval_violations(ArmourPlanner* h, const double* k, ArmourViolation* o
  * separates the whole family of sliced link centres (collision rows), the sliced torque's interval stays inside the bounds (torque rows) --
  * 1 otherwise; the 4n joint-limit rows are always 1.  Sound (a 0 is never violated: 1e-9 margin on the test), not tight.  On random worlds
  * about 2 % of the collision rows are 1.  n_relevant_collision_rows [B] and ms (device time of the test) may be NULL; so may `relevant`.
- * Computed once per problem set, on the device (relevance.hip).  ARMOUR_OPT_CULL_ROWS = 1 makes armour_eval_violations* use it. */
+ * Computed once per problem set, on the device (relevance.hip).  ARMOUR_OPT_CULL_ROWS = 1 makes armour_eval_violations* use it.
+ * THE RULE (normative; tests/relevance_rule.py restates it, tests/test_row_masks.py holds the kernels to it row by row).  c and coef_i: centre
+ * and monomial coefficients of the row's link PZ; (A_p, d_p, delta_p): plane p of the row; sums in fp64.
+ *   collision row:  L_p = |A_p . c - d_p| - (1 + 1e-12) sum_i |A_p . coef_i| - delta_p  over the LIVE planes p (armour_get_plane_skip) with a
+ *                   non-zero normal; relevant = 0  iff  max_p L_p >= 1e-9.  (A zero-normal plane never separates, whatever its d and delta.)
+ *   torque row:     cen and rad = sum_i |coef_i| of the row's torque PZ, bounds l, u:  relevant = 1  iff  cen + rad >= u - 1e-9  or
+ *                   cen - rad <= l + 1e-9.
+ *   limit rows:     always 1. */
 int armour_get_row_relevance(ArmourPlanner* h, uint8_t* relevant, int32_t* n_relevant_collision_rows, double* ms);
 /* The SOLVER's rows of the current problem set: solver_rows[B][m], 1 = the row can pass armour_solve's candidate filter for some k in [-1,1]^n
  * (g_i + 2 |J_i|_1 > u_i or g_i - 2 |J_i|_1 < l_i: solver_common.h; the filter leaves out rows that cannot become active within the variables'
  * box, and this mask the rows it leaves out at EVERY k) -- a superset of armour_get_row_relevance's mask; what the culled device form of armour_solve
- * walks (ARMOUR_OPT_SOLVE_CULL).  n_collision_rows [B] and n_torque_rows [B] may be NULL; so may `solver_rows`. */
+ * walks (ARMOUR_OPT_SOLVE_CULL).  n_collision_rows [B] and n_torque_rows [B] may be NULL; so may `solver_rows`.
+ * THE RULE (normative, in the terms of armour_get_row_relevance's).  deg_i = total degree of monomial i (the sum of its key's 2-bit fields).
+ *   collision row:  solver_rows = 0  iff  relevant = 0  and some live plane p with a non-zero normal has
+ *                       L_p - 3e-5 sum_i |A_p . coef_i|  >=  1e-9 + 2 |rd|_2 amax (1 + 3e-5) - u,
+ *                   rd[e] = sum_i deg_i |coef_i[e]|;  amax = 1 for tables the library built (unit normals) and
+ *                   max(1, max over the live planes p of |A_p|_2 (1 + 1e-12)) for tables loaded by armour_debug_load_tables.
+ *   torque row:     solver_rows = 1  iff  relevant = 1  or the relevance test holds with (rad + 2 radd) (1 + 3e-5) in place of rad,
+ *                   radd = sum_i deg_i |coef_i|.
+ *   limit rows:     always 1.
+ * (3e-5 > (1 + 1e-6)^21 - 1: the solver evaluates its lists at points up to 1e-6 outside the box, monomials have total degree <= 21.) */
 int armour_get_solver_rows(ArmourPlanner* h, uint8_t* solver_rows, int32_t* n_collision_rows, int32_t* n_torque_rows, double* ms);
 
 /* ---- in-process multi-device batch ---- */
@@ -578,6 +594,21 @@ int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, const doubl
                              int32_t cap_l, const int32_t* torque_count, const double* torque_center,
                              const uint64_t* torque_keys, const double* torque_coeffs, int32_t cap_t,
                              const double* A, const double* d, const double* delta, const double* torque_radius);
+
+/* ---- test hook: the row LISTS behind armour_get_row_relevance (which = 0) / armour_get_solver_rows (which = 1) ---- */
+/* Read only: copies out what relevance.hip built for the current problem set and launches nothing.  ARMOUR_ESTATE without a problem set, and
+ * when the set's lists have not been built yet (call armour_get_row_relevance / armour_get_solver_rows first).  Every pointer may be NULL.
+ *   rows       [B][Q]   problem b's listed collision rows q, ascending, in rows[b][0 .. count[b])  (entries behind the count are not defined)
+ *   count      [B]
+ *   aux, aux_count      which = 0: the same rows by residue class of the row index, aux [B][256][ceil(Q / 256)]: class c holds the listed q
+ *                       with (row0 + q) mod 256 == c, ascending, aux_count [B][256] of them;
+ *                       which = 1: the torque rows of the solver's mask, aux [B][row0] ascending, aux_count [B]
+ *   pack_off   [2 B]    [2 b] the first double of problem b's block of packed plane entries, [2 b + 1] its row stride = count[b] rounded up to 16
+ *   packed              the packed block: entry [(j * 5 + c) * stride + i] of problem b's block = component c of {Ax, Ay, Az, d, delta} of the
+ *                       j-th live plane (ascending; armour_get_plane_skip) of listed row i.  packed_total (may be NULL) receives its length in
+ *                       doubles; with `packed` given, packed_capacity < that length is ARMOUR_EINVAL. */
+int armour_debug_get_row_lists(ArmourPlanner* h, int32_t which, int32_t* rows, int32_t* count, int32_t* aux, int32_t* aux_count,
+                               int64_t* pack_off, double* packed, int64_t packed_capacity, int64_t* packed_total);
 
 /* ---- roadmap high-level planner: a joint-space roadmap checked against worlds' obstacles on the device ---- */
 /* What the reference's sample-based HLP does with its prebuilt collision_checker (kinova_samplebased_HLP_realtime): node feasibility,
