@@ -391,6 +391,12 @@ typedef struct ArmourTrackOptions {
     double dt, t0, t1, duration;                                /* 0 <= t0 < t1 <= duration; dt > 0 */
     double reserved[4];
 } ArmourTrackOptions;
+/* What a result holds at the edges:
+ *   - a torque limit <= 0 contributes no ratio to max_torque_ratio (nothing is divided by it) and still flags: ARMOUR_TRACK_LIMIT_TORQUE is
+ *     set at the first node where that joint's u is not zero;
+ *   - the maxima ignore NaN (fmax): a NaN candidate leaves a maximum as it was, an infinite one makes it infinite;
+ *   - a status-2 rollout keeps the last finite state: q, qd and t_end are those of the node the failed step started from, `steps` is
+ *     unchanged by it, that node's monitors (maxima, flags, first_violation_t) and its trace record are in, later trace records are NaN. */
 typedef struct ArmourTrackResult {
     int32_t status;            /* 0 reached t1, 1 nominal torque outside the interval torque, 2 non-finite state */
     int32_t steps;             /* steps taken */

@@ -3,7 +3,10 @@ tracking controller -- uarmtd_agent.dynamics + integrator with the LLC in the ri
 
 The device is checked against a host restatement written here: the same RK4 and node rule, the controller of the CPU oracle
 (oracle.cpu_oracle.robust_controller), the plant's M columns and bias from oracle.cpu_oracle.pass_rnea_scaled.  The restatement is
-itself held by two invariants (exact tracking under the nominal controller, fourth-order energy convergence of the passive plant)."""
+itself held by two invariants (exact tracking under the nominal controller, fourth-order energy convergence of the passive plant).
+The limit monitors are a function of the nodes alone (limit_monitors; with_limits monitors a finished run again under other limits) and
+report how far every node stayed from every limit; _compare holds the device to the restatement, flags and times exactly.  The verdict
+paths -- limits, stops, ragged grids, block edges, the 8-factor ABI -- are in test_tracking_edges.py."""
 import ctypes as C
 import math
 
@@ -46,9 +49,50 @@ def _reference(q0, qd0, qdd0, k, k_range, D, t):
     return q, qd, qdd
 
 
+def _limits(rb, n):
+    return (np.array(rb.state_limits_lb[:n]), np.array(rb.state_limits_ub[:n]), np.array(rb.speed_limits[:n]), np.array(rb.torque_limits[:n]))
+
+
+def limit_monitors(nodes, lb, ub, speed, torque):
+    """The kernel's limit monitors over a rollout's nodes [(t, q, qd, u), ...], joint by joint as tracking.hip has them: the torque ratio only
+    for joints whose limit is above 0 (a limit <= 0 contributes no ratio and still flags), each flag from two one-sided comparisons (a NaN
+    crosses nothing), maxima by fmax (a NaN candidate is ignored), first_violation_t the first flagged node's t.  The monitors read the
+    state and change none of it, so the same nodes can be monitored again under other limits (with_limits).
+    margins: per quantity the smallest distance, over nodes and joints, between the monitored value and a limit -- a flag asserted on the
+    device is only as sure as this distance is large against the parity tolerance."""
+    out = dict(limit_flags=0, first_violation_t=np.nan, max_torque_ratio=0.0)
+    margins = dict(torque=np.inf, position=np.inf, speed=np.inf)
+    for t, q, qd, u in nodes:
+        flags = 0
+        for i in range(len(q)):
+            if torque[i] > 0:
+                out["max_torque_ratio"] = float(np.fmax(out["max_torque_ratio"], abs(u[i]) / torque[i]))
+            if u[i] > torque[i] or u[i] < -torque[i]:
+                flags |= _lib.TRACK_LIMIT_TORQUE
+            if q[i] < lb[i] or q[i] > ub[i]:
+                flags |= _lib.TRACK_LIMIT_POSITION
+            if qd[i] > speed[i] or qd[i] < -speed[i]:
+                flags |= _lib.TRACK_LIMIT_SPEED
+        with np.errstate(invalid="ignore"):
+            margins["torque"] = float(np.fmin(margins["torque"], np.fmin.reduce(np.abs(np.abs(u) - torque))))
+            margins["position"] = float(np.fmin(margins["position"], np.fmin.reduce(np.fmin(np.abs(q - lb), np.abs(q - ub)))))
+            margins["speed"] = float(np.fmin(margins["speed"], np.fmin.reduce(np.abs(np.abs(qd) - speed))))
+        if flags and out["limit_flags"] == 0:
+            out["first_violation_t"] = t
+        out["limit_flags"] |= flags
+    out["margins"] = margins
+    return out
+
+
+def with_limits(run, rb):
+    """A host_track result monitored again under the limits of `rb` (every other field is the run's own)."""
+    return {**run, **limit_monitors(run["nodes"], *_limits(rb, len(run["q"])))}
+
+
 def host_track(rb, q0, qd0, qdd0, k, k_range, D, t0=0.0, t1=None, dt=1e-3, controller="robust", z0=None, sm=None, sI=None, Kr=None, alpha=None,
                V_max=None, r_thr=0.0, eps=None, record_every=0):
-    """One rollout of armour_track restated on the host (numpy + the CPU oracle)."""
+    """One rollout of armour_track restated on the host (numpy + the CPU oracle).  Besides the fields of ArmourTrackResult: trace, nodes
+    (t, q, qd, u of every node reached), N, h and margins (limit_monitors)."""
     from oracle.cpu_oracle import pass_rnea_scaled, robust_controller
     n = rb.num_factors
     t1 = D if t1 is None else t1
@@ -60,8 +104,6 @@ def host_track(rb, q0, qd0, qdd0, k, k_range, D, t0=0.0, t1=None, dt=1e-3, contr
     sI = np.zeros(n) if sI is None else np.asarray(sI, dtype=np.float64)
     N = int(np.ceil((t1 - t0) / dt - 1e-9))
     h = (t1 - t0) / N
-    lb, ub = np.array(rb.state_limits_lb[:n]), np.array(rb.state_limits_ub[:n])
-    speed, torque = np.array(rb.speed_limits[:n]), np.array(rb.torque_limits[:n])
     zeros = np.zeros(n)
 
     def rhs(t, q, qd):
@@ -83,52 +125,48 @@ def host_track(rb, q0, qd0, qdd0, k, k_range, D, t0=0.0, t1=None, dt=1e-3, contr
     q, qd = _reference(q0, qd0, qdd0, k, k_range, D, t0)[:2]
     if z0 is not None:
         q, qd = np.array(z0[:n], dtype=np.float64), np.array(z0[n:], dtype=np.float64)
-    res = dict(status=0, steps=0, limit_flags=0, first_violation_t=np.nan, max_pos_error=0.0, max_vel_error=0.0, max_V=0.0, max_robust_input=0.0,
-               max_torque_ratio=0.0)
+    res = dict(status=0, steps=0, max_pos_error=0.0, max_vel_error=0.0, max_V=0.0, max_robust_input=0.0, t_end=t0, N=N, h=h)
     trace = np.full((N // record_every + 1, 3, n), np.nan) if record_every else None
-    for s in range(N + 1):
-        t = t1 if s == N else t0 + s * h
-        kqd, u, v, qr, qdr, V, ok = rhs(t, q, qd)
-        flags = 0
-        flags |= 1 if np.any(np.abs(u) > torque) else 0
-        flags |= 2 if np.any((q < lb) | (q > ub)) else 0
-        flags |= 4 if np.any(np.abs(qd) > speed) else 0
-        res["max_pos_error"] = max(res["max_pos_error"], np.abs(_wrap(qr - q)).max())
-        res["max_vel_error"] = max(res["max_vel_error"], np.abs(qdr - qd).max())
-        res["max_robust_input"] = max(res["max_robust_input"], np.abs(v).max())
-        res["max_torque_ratio"] = max(res["max_torque_ratio"], (np.abs(u) / torque).max())
-        res["max_V"] = max(res["max_V"], V)
-        if flags and res["limit_flags"] == 0:
-            res["first_violation_t"] = t
-        res["limit_flags"] |= flags
-        res["t_end"] = t
-        if record_every and s % record_every == 0:
-            trace[s // record_every] = (q, qd, u)
-        if not ok:
-            res["status"] = 1
-            break
-        if s == N:
-            break
-        kq, acc_q, acc_qd = qd.copy(), qd.copy(), kqd.copy()
-        for stg in (1, 2, 3):
-            ch = h if stg == 3 else 0.5 * h
-            zq, zqd = q + ch * kq, qd + ch * kqd
-            kqd, _, _, _, _, _, ok = rhs(t + ch, zq, zqd)
+    nodes = []
+    fmax = lambda name, cand: float(np.fmax(res[name], np.fmax.reduce(np.atleast_1d(cand))))   # fmax: a NaN candidate is ignored
+    with np.errstate(all="ignore"):   # (a non-finite state is ordinary arithmetic here, as on the device)
+        for s in range(N + 1):
+            t = t1 if s == N else t0 + s * h
+            kqd, u, v, qr, qdr, V, ok = rhs(t, q, qd)
+            res["max_pos_error"] = fmax("max_pos_error", np.abs(_wrap(qr - q)))
+            res["max_vel_error"] = fmax("max_vel_error", np.abs(qdr - qd))
+            res["max_robust_input"] = fmax("max_robust_input", np.abs(v))
+            res["max_V"] = fmax("max_V", V)
+            nodes.append((t, q.copy(), qd.copy(), u.copy()))
+            res["t_end"] = t
+            if record_every and s % record_every == 0:
+                trace[s // record_every] = (q, qd, u)
             if not ok:
+                res["status"] = 1
                 break
-            w = 1.0 if stg == 3 else 2.0
-            kq = zqd
-            acc_q, acc_qd = acc_q + w * kq, acc_qd + w * kqd
-        if not ok:
-            res["status"] = 1
-            break
-        nq, nqd = q + (h / 6) * acc_q, qd + (h / 6) * acc_qd
-        if not (np.all(np.isfinite(nq)) and np.all(np.isfinite(nqd))):
-            res["status"] = 2
-            break
-        q, qd = nq, nqd
-        res["steps"] = s + 1
-    res["q"], res["qd"], res["trace"] = q, qd, trace
+            if s == N:
+                break
+            kq, acc_q, acc_qd = qd.copy(), qd.copy(), kqd.copy()
+            for stg in (1, 2, 3):
+                ch = h if stg == 3 else 0.5 * h
+                zq, zqd = q + ch * kq, qd + ch * kqd
+                kqd, _, _, _, _, _, ok = rhs(t + ch, zq, zqd)
+                if not ok:
+                    break
+                w = 1.0 if stg == 3 else 2.0
+                kq = zqd
+                acc_q, acc_qd = acc_q + w * kq, acc_qd + w * kqd
+            if not ok:
+                res["status"] = 1
+                break
+            nq, nqd = q + (h / 6) * acc_q, qd + (h / 6) * acc_qd
+            if not (np.all(np.isfinite(nq)) and np.all(np.isfinite(nqd))):
+                res["status"] = 2   # the state stays at the last finite node, steps unchanged
+                break
+            q, qd = nq, nqd
+            res["steps"] = s + 1
+    res["q"], res["qd"], res["trace"], res["nodes"] = q, qd, trace, nodes
+    res.update(limit_monitors(nodes, *_limits(rb, n)))
     return res
 
 
@@ -235,16 +273,41 @@ def test_restatement_is_fourth_order_on_the_passive_plant():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _compare(dev, host_runs, tol=1e-9):
-    for b, h in enumerate(host_runs):
-        assert dev.status[b] == h["status"] and dev.steps[b] == h["steps"] and dev.limit_flags[b] == h["limit_flags"], b
+def _same_bits(a, b):
+    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
+
+
+def _compare(dev, host_runs, tol=1e-9, lanes=None):
+    """Device lane lanes[i] (default i) against host_runs[i]; returns the largest |device - restatement| over states, maxima and trace."""
+    worst = 0.0
+    for i, h in enumerate(host_runs):
+        b = i if lanes is None else lanes[i]
+        assert dev.status[b] == h["status"] and dev.steps[b] == h["steps"] and dev.limit_flags[b] == h["limit_flags"], \
+            (b, dev.status[b], h["status"], dev.steps[b], h["steps"], dev.limit_flags[b], h["limit_flags"])
+        assert _same_bits(dev.t_end[b], h["t_end"]), (b, dev.t_end[b], h["t_end"])
+        assert _same_bits(dev.first_violation_t[b], h["first_violation_t"]) or (np.isnan(dev.first_violation_t[b]) and np.isnan(h["first_violation_t"])), \
+            (b, dev.first_violation_t[b], h["first_violation_t"])
         assert np.abs(dev.q[b] - h["q"]).max() <= tol and np.abs(dev.qd[b] - h["qd"]).max() <= tol, b
+        worst = max(worst, np.abs(dev.q[b] - h["q"]).max(), np.abs(dev.qd[b] - h["qd"]).max())
         for name in ("max_pos_error", "max_vel_error", "max_V", "max_robust_input", "max_torque_ratio"):
             d, r = getattr(dev, name)[b], h[name]
-            assert abs(d - r) <= tol * max(abs(r), 1e-300) or abs(d - r) <= 1e-15, (b, name, d, r)
+            assert np.isnan(d) == np.isnan(r), (b, name, d, r)
+            if np.isinf(r) or np.isinf(d):   # equal infinities are equal
+                assert d == r, (b, name, d, r)
+            elif not np.isnan(r):
+                assert abs(d - r) <= tol * max(abs(r), 1e-300) or abs(d - r) <= 1e-15, (b, name, d, r)
+                worst = max(worst, abs(d - r))
         if h["trace"] is not None:
-            assert np.nanmax(np.abs(dev.trace[b] - h["trace"])) <= tol * max(1.0, np.nanmax(np.abs(h["trace"]))), b
-            assert np.array_equal(np.isnan(dev.trace[b]), np.isnan(h["trace"])), b
+            dt_, ht = dev.trace[b], h["trace"]
+            assert np.array_equal(np.isnan(dt_), np.isnan(ht)), b
+            inf = np.isinf(ht) | np.isinf(dt_)
+            assert np.array_equal(dt_[inf], ht[inf]), b
+            fin = np.isfinite(ht)
+            if fin.any():
+                diff = np.abs(dt_[fin] - ht[fin]).max()
+                assert diff <= tol * max(1.0, np.abs(ht[fin]).max()), (b, diff)
+                worst = max(worst, diff)
+    return float(worst)
 
 
 @pytest.mark.gpu
