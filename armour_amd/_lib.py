@@ -52,6 +52,8 @@ SHORTCUT_OK, SHORTCUT_INVALID = 0, 1                 # ARMOUR_SHORTCUT_*
 SHORTCUT_MAX_POINTS, SHORTCUT_MAX_PASSES = 1024, 8   # ARMOUR_SHORTCUT_MAX_POINTS, ARMOUR_SHORTCUT_MAX_PASSES
 IK_NONE_CONVERGED, IK_FOUND, IK_ALL_BLOCKED = 0, 1, 2   # ARMOUR_IK_*
 IK_MAX_SEEDS, IK_MAX_ITERATIONS, IK_MAX_TARGETS = 256, 1000, 1048576   # ARMOUR_IK_MAX_SEEDS, ARMOUR_IK_MAX_ITERATIONS, ARMOUR_IK_MAX_TARGETS
+WS_PARTIAL, WS_REACHED, WS_START_BLOCKED = 0, 1, 2      # ARMOUR_WS_*
+WS_MAX_NODES, WS_MAX_SEGMENTS = 4096, 1024              # ARMOUR_WS_MAX_NODES, ARMOUR_WS_MAX_SEGMENTS
 
 
 class ArmourRobot(C.Structure):
@@ -192,6 +194,7 @@ EXPORTS = [
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
+    "armour_ws_tree_plan", "armour_ws_tree_plan_host",
 ]
 
 _lib = None
@@ -343,6 +346,10 @@ def load():
     L.armour_ik.argtypes = ik                     # (the last pointer: ms)
     L.armour_ik_host.argtypes = ik                # (the last pointer: margin [N])
     L.armour_ik_end_effector_host.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, dp, dp, dp]
+    ws = [dp, dp, C.c_int32, C.c_int32, dp, dp, dp, C.POINTER(C.c_uint64), C.c_int32, dp, ip] + [C.c_double] * 6 + [C.c_int32] * 3 + [ip] * 5 + [
+        dp, dp, dp, ip, dp, ip, dp, dp]
+    L.armour_ws_tree_plan.argtypes = ws           # (the last pointer: ms)
+    L.armour_ws_tree_plan_host.argtypes = ws      # (the last pointer: margin [W])
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

@@ -1,0 +1,680 @@
+// Batched workspace RRT* (include/armour_hip.h, armour_ws_tree_plan): the tree of the reference's end-effector planner
+// (arm_end_effector_RRT_star_HLP over RRT_star_HLP / RRT_HLP) for W worlds in ONE launch, a block per world, the whole loop inside the block.
+// A node is a point of the workspace and a test is an axis-aligned box against an obstacle: rmgeo::pair_separated as it stands, with the
+// axes e_0, e_1, e_2.  What is new -- the difference and its squared length, S of an edge, one sub-segment's box, the steer step, the sample
+// and the cost of a node -- is written once below as __host__ __device__ code, run by the kernel's lanes and by armour_ws_tree_plan_host's loop.
+//
+// Nothing but __syncthreads() orders the block: a tree's nodes live in global memory, written and read by this block alone (keeping them
+// in LDS was measured and is a few per cent faster only where it fits, up to ~1700 nodes: DESIGN.md 4.12f); every decision
+// that steers a loop is taken from values all lanes hold alike, so the barriers are reached by all of them.  The loop is bounded by
+// max_iterations, a work list by count * ARMOUR_WS_MAX_SEGMENTS items, a scan and a path walk by the tree's count, the cost re-derivation
+// by count passes.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "roadmap_handle.h"
+#include "tree_block.h"
+
+using namespace treeblk;   // the block shape, u(seed, i, j), key_less and, through it, rmgeo
+
+namespace {
+
+constexpr int WS_CAP = ARMOUR_WS_MAX_NODES;
+constexpr int WS_PER_LANE = WS_CAP / TP_BLOCK;           // nodes per lane when the whole tree is dealt to the lanes: node t + k TP_BLOCK is lane t's k-th
+static_assert(WS_PER_LANE * TP_BLOCK == WS_CAP && WS_PER_LANE <= 32, "a lane keeps one bit per node of its own");
+
+// What a world's run reads: by value in the kernel's arguments (pointers: the device's; the host twin passes its own)
+struct WsArgs {
+    double lb[3], ub[3];
+    double step, edge_step, rewire_radius, goal_rate, buffer, goal_tol;
+    int32_t O, max_iterations, max_nodes, max_points, max_init;
+    const double *obstacles, *starts, *goals, *init;
+    const int32_t* init_count;
+    const uint64_t* seeds;
+    int32_t *status, *iterations, *points, *rewires, *chain_kept, *count, *parent;
+    double *path_cost, *goal_dist, *path, *nodes, *node_cost, *node_len;
+};
+
+// ---- the scalar steps of the rule, one copy
+// D = b - a component by component; returns acc = dot(D, D)
+__host__ __device__ inline double ws_diff(const double* a, const double* b, double (&D)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) D[i] = b[i] - a[i];
+    return dot3(D, D);
+}
+// S of an edge of length len
+__host__ __device__ inline int ws_segments(double len, double edge_step) {
+    const double S = ceil(len / edge_step);
+    return S < 1.0 ? 1 : S > (double)ARMOUR_WS_MAX_SEGMENTS ? ARMOUR_WS_MAX_SEGMENTS : (int)S;
+}
+// the box of sub-segment s of S of the edge a -> a + D with buffer buf: centre x, half-sizes h
+__host__ __device__ inline void ws_sub_box(const double* a, const double (&D)[3], int s, int S, double buf, double (&x)[3], double (&h)[3]) {
+    const double ts = (double)(2 * s + 1) / (double)(2 * S), two_S = (double)(2 * S);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        x[i] = a[i] + ts * D[i];
+        h[i] = buf + fabs(D[i]) / two_S;
+    }
+}
+// the box (x, e_0 e_1 e_2, h) against the staged obstacles [o0, o1): true when every one separates (verdict mode)
+__host__ __device__ inline bool ws_box_free(const double (&x)[3], const double (&h)[3], const double* obs, int o0, int o1) {
+    const double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int o = o0; o < o1; o++)
+        if (!pair_separated(x, E, h, obs + (size_t)o * RM_OBS_STRIDE, false, nullptr)) return false;
+    return true;
+}
+// min over the obstacles of the pair clearance of that box (+inf without obstacles): what the host twin's margin is made of
+inline double ws_box_clearance(const double (&x)[3], const double (&h)[3], const double* obs, int O) {
+    const double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double cl = INFINITY;
+    for (int o = 0; o < O; o++) {
+        double v;
+        pair_separated(x, E, h, obs + (size_t)o * RM_OBS_STRIDE, true, &v);
+        cl = std::fmin(cl, v);
+    }
+    return cl;
+}
+__host__ __device__ inline bool ws_sub_free(const double* a, const double (&D)[3], int s, int S, double buf, const double* obs, int o0, int o1) {
+    double x[3], h[3];
+    ws_sub_box(a, D, s, S, buf, x, h);
+    return ws_box_free(x, h, obs, o0, o1);
+}
+// the sample of iteration i
+__host__ __device__ inline void ws_sample(const WsArgs& a, uint64_t seed, int i, const double* goal, double (&qr)[3]) {
+    const bool to_goal = tree_u(seed, (uint64_t)i, 3) < a.goal_rate;
+#pragma unroll
+    for (int j = 0; j < 3; j++) qr[j] = to_goal ? goal[j] : a.lb[j] + tree_u(seed, (uint64_t)i, (uint64_t)j) * (a.ub[j] - a.lb[j]);
+}
+// the steer step from the nearest node xv towards qr (D = qr - xv, dist = sqrt(dot(D, D)))
+__host__ __device__ inline void ws_steer(const double* xv, const double (&qr)[3], const double (&D)[3], double dist, double step, double (&qn)[3]) {
+    const double f = step / dist;
+#pragma unroll
+    for (int j = 0; j < 3; j++) qn[j] = dist <= step ? qr[j] : xv[j] + f * D[j];
+}
+
+// component t of a point that every lane holds, by selects: no array of a lane's own is indexed at run time (no scratch memory)
+__device__ inline double pick3(const double (&a)[3], int t) { return t == 0 ? a[0] : t == 1 ? a[1] : a[2]; }
+
+// ---- the block's cooperative steps.  Every result is the same in all lanes.
+struct WsShared {
+    double red_d[TP_WAVES];
+    int red_v[TP_WAVES], wsum[TP_WAVES], any[TP_WAVES];
+    int cand[TP_BLOCK];              // a round's candidates (node indices)
+    int end[TP_BLOCK];               // one past the last work item of round candidate k
+    unsigned char hit[TP_BLOCK];     // 1: some sub-segment of round candidate k did not separate
+    unsigned char free_[WS_CAP];     // per node: 1 = a candidate of this iteration whose edge to qn is free
+};
+
+__device__ inline bool block_any(WsShared& sh, bool flag) {
+    const int t = threadIdx.x;
+    const unsigned long long mask = __ballot(flag);
+    if ((t & 63) == 0) sh.any[t >> 6] = mask != 0ull;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < TP_WAVES; w++) r |= sh.any[w];
+    __syncthreads();                                        // sh.any has been read: the next call may write it
+    return r != 0;
+}
+// inclusive sum of v over lanes 0 .. t; *total = the block's sum
+__device__ inline int block_scan(WsShared& sh, int v, int* total) {
+    const int t = threadIdx.x;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if ((t & 63) >= o) x += y;
+    }
+    if ((t & 63) == 63) sh.wsum[t >> 6] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < TP_WAVES; w++) {
+        base += w < (t >> 6) ? sh.wsum[w] : 0;
+        tot += sh.wsum[w];
+    }
+    __syncthreads();                                        // sh.wsum has been read
+    *total = tot;
+    return base + x;
+}
+// the smallest (d, v) of the lanes' keys in the order key_less; a lane without a key passes (INFINITY, TP_NONE)
+__device__ inline void block_argmin(WsShared& sh, double* d, int* v) {
+    const int t = threadIdx.x;
+    double bd = *d;
+    int bv = *v;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(bd, o);
+        const int ov = __shfl_xor(bv, o);
+        if (key_less(od, ov, bd, bv)) { bd = od; bv = ov; }
+    }
+    if ((t & 63) == 0) { sh.red_d[t >> 6] = bd; sh.red_v[t >> 6] = bv; }
+    __syncthreads();
+    bd = sh.red_d[0]; bv = sh.red_v[0];
+#pragma unroll
+    for (int w = 1; w < TP_WAVES; w++)
+        if (key_less(sh.red_d[w], sh.red_v[w], bd, bv)) { bd = sh.red_d[w]; bv = sh.red_v[w]; }
+    __syncthreads();                                        // sh.red_* have been read
+    *d = bd;
+    *v = bv;
+}
+// the edge a -> a + D of S sub-segments, dealt to the lanes in chunks of TP_BLOCK: free when every sub-segment separates
+__device__ inline bool block_edge_free(WsShared& sh, const double* a, const double (&D)[3], int S, double buf, const double* s_obs, int O) {
+    bool hit = false;
+    for (int s = threadIdx.x; s < S; s += TP_BLOCK) hit = hit || !ws_sub_free(a, D, s, S, buf, s_obs, 0, O);
+    return !block_any(sh, hit);
+}
+
+// grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The tree of world w: nodes [w][max_nodes][3], parent / node_cost / node_len [w][max_nodes].
+__global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+    __shared__ WsShared sh;
+    const int w = blockIdx.x, t = threadIdx.x, O = ar.O, cap = ar.max_nodes;
+    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    for (int c = t; c < cap; c += TP_BLOCK) sh.free_[c] = 0;
+    const uint64_t seed = ar.seeds[w];
+    const double buf = ar.buffer, rr2 = ar.rewire_radius * ar.rewire_radius;
+    double start[3], goal[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        start[j] = ar.starts[(size_t)w * 3 + j];
+        goal[j] = ar.goals[(size_t)w * 3 + j];
+    }
+    double* nx = ar.nodes + (size_t)w * cap * 3;
+    double* ncost = ar.node_cost + (size_t)w * cap;
+    double* nlen = ar.node_len + (size_t)w * cap;
+    int32_t* par = ar.parent + (size_t)w * cap;
+    int cnt = 0, status = ARMOUR_WS_START_BLOCKED, iterations = 0, points = 0, rewires = 0, kept = 0;
+    double path_cost = 0.0, goal_dist;
+    {
+        double D[3];
+        goal_dist = sqrt(ws_diff(start, goal, D));
+    }
+
+    // ---- the point rule at start: the obstacles dealt to the lanes
+    bool hit = false;
+    {
+        const double h[3] = {buf, buf, buf};
+        for (int o = t; o < O; o += TP_BLOCK) hit = hit || !ws_box_free(start, h, s_obs, o, o + 1);
+    }
+    if (!block_any(sh, hit)) {
+        if (t < 3) nx[t] = pick3(start, t);
+        if (t == 0) { par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0; }
+        cnt = 1;
+        // ---- the initial chain: edge by edge from the last kept node, up to the first edge that is not free
+        const int chain = ar.init ? ar.init_count[w] : 0;
+        double prev[3] = {start[0], start[1], start[2]}, prev_cost = 0.0;
+        for (int c = 0; c < chain && cnt < cap; c++) {
+            double x[3], D[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) x[j] = ar.init[((size_t)w * ar.max_init + c) * 3 + j];
+            const double d = sqrt(ws_diff(prev, x, D));
+            if (!block_edge_free(sh, prev, D, ws_segments(d, ar.edge_step), buf, s_obs, O)) break;
+            prev_cost = prev_cost + d;
+            if (t < 3) nx[(size_t)cnt * 3 + t] = pick3(x, t);
+            if (t == 0) { par[cnt] = cnt - 1; nlen[cnt] = d; ncost[cnt] = prev_cost; }
+#pragma unroll
+            for (int j = 0; j < 3; j++) prev[j] = x[j];
+            cnt++;
+            kept++;
+        }
+        iterations = ar.max_iterations;
+        for (int i = 0; i < ar.max_iterations; i++) {
+            if (cnt >= cap) { iterations = i; break; }
+            __syncthreads();                                // the nodes, parents and costs of iteration i - 1 are written
+            // ---- sample (every lane: the same arithmetic on the same values), nearest, steer
+            double qr[3], qn[3], D[3];
+            ws_sample(ar, seed, i, goal, qr);
+            double acc = INFINITY;
+            int v = TP_NONE;
+            for (int c = t; c < cnt; c += TP_BLOCK) {
+                const double d2 = ws_diff(nx + (size_t)c * 3, qr, D);
+                if (key_less(d2, c, acc, v)) { acc = d2; v = c; }
+            }
+            block_argmin(sh, &acc, &v);
+            if (acc == 0.0) continue;
+            {
+                const double xv[3] = {nx[(size_t)v * 3], nx[(size_t)v * 3 + 1], nx[(size_t)v * 3 + 2]};
+                ws_diff(xv, qr, D);
+                ws_steer(xv, qr, D, sqrt(acc), ar.step, qn);
+            }
+            // ---- near set: bit k of `mine` = node t + k TP_BLOCK is a candidate; ranks in lane-major order
+            unsigned mine = 0;
+#pragma unroll
+            for (int k = 0; k < WS_PER_LANE; k++) {
+                const int c = t + k * TP_BLOCK;
+                if (c < cnt && (c == v || ws_diff(nx + (size_t)c * 3, qn, D) <= rr2)) mine |= 1u << k;
+            }
+            int C;
+            const int rank0 = block_scan(sh, __popc(mine), &C) - __popc(mine);
+            // ---- edge tests, TP_BLOCK candidates to a round: a flat list of (candidate, sub-segment) items across the lanes
+            for (int r0 = 0; r0 < C; r0 += TP_BLOCK) {
+                const int Cr = C - r0 < TP_BLOCK ? C - r0 : TP_BLOCK;
+                int rank = rank0;
+                for (unsigned m = mine; m; m &= m - 1, rank++)
+                    if (rank >= r0 && rank < r0 + TP_BLOCK) sh.cand[rank - r0] = t + (__ffs((int)m) - 1) * TP_BLOCK;
+                sh.hit[t] = 0;
+                __syncthreads();
+                const int c = t < Cr ? sh.cand[t] : 0;
+                int S = 0;
+                if (t < Cr) S = ws_segments(sqrt(ws_diff(nx + (size_t)c * 3, qn, D)), ar.edge_step);
+                int T;
+                sh.end[t] = block_scan(sh, S, &T);
+                __syncthreads();
+                // a short list gives each item G = min(O, TP_BLOCK / T) lanes, lane g of them with the obstacles [g O / G, (g + 1) O / G): a sub-segment
+                // is free iff it is free of every obstacle, so the verdict is the same and the longest lane's work shrinks from O obstacles to O / G
+                int G = 1;
+                if (2 * T <= TP_BLOCK && O > 1) G = TP_BLOCK / T < O ? TP_BLOCK / T : O;
+                const int per = TP_BLOCK / G, g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
+                for (int base = 0; base < T; base += per) {
+                    const int it = base + t / G;
+                    if (t < per * G && it < T) {
+                        int lo = 0, hi = Cr - 1;            // the candidate of item `it`: the first k with end[k] > it
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (sh.end[mid] > it) hi = mid; else lo = mid + 1;
+                        }
+                        const int first = lo ? sh.end[lo - 1] : 0;
+                        const double* xc = nx + (size_t)sh.cand[lo] * 3;
+                        ws_diff(xc, qn, D);
+                        if (!ws_sub_free(xc, D, it - first, sh.end[lo] - first, buf, s_obs, o0, o1)) sh.hit[lo] = 1;   // every lane that stores, stores this 1
+                    }
+                }
+                __syncthreads();
+                if (t < Cr) sh.free_[c] = sh.hit[t] ? 0 : 1;
+                __syncthreads();                            // sh.cand / sh.end / sh.hit have been read: the next round may write them
+            }
+            // ---- parent: the free candidate with the smallest (cost_c + d_c, c)
+            double pk = INFINITY;
+            int p = TP_NONE;
+            for (unsigned m = mine; m; m &= m - 1) {
+                const int c = t + (__ffs((int)m) - 1) * TP_BLOCK;
+                if (!sh.free_[c]) continue;
+                const double key = ncost[c] + sqrt(ws_diff(nx + (size_t)c * 3, qn, D));
+                if (key_less(key, c, pk, p)) { pk = key; p = c; }
+            }
+            block_argmin(sh, &pk, &p);
+            if (p == TP_NONE) continue;                     // (no candidate is free: no flag is set)
+            const double d_p = sqrt(ws_diff(nx + (size_t)p * 3, qn, D)), cost_qn = ncost[p] + d_p;
+            // ---- rewire: each free candidate decides for itself, on the costs as they stand; the flags are cleared for the next iteration
+            int mine_rewired = 0;
+            for (unsigned m = mine; m; m &= m - 1) {
+                const int c = t + (__ffs((int)m) - 1) * TP_BLOCK;
+                if (!sh.free_[c]) continue;
+                sh.free_[c] = 0;
+                if (c == p) continue;
+                const double d_c = sqrt(ws_diff(nx + (size_t)c * 3, qn, D));
+                if (cost_qn + d_c < ncost[c]) { par[c] = cnt; nlen[c] = d_c; mine_rewired++; }
+            }
+            if (t < 3) nx[(size_t)cnt * 3 + t] = pick3(qn, t);
+            if (t == 0) { par[cnt] = p; nlen[cnt] = d_p; ncost[cnt] = cost_qn; }
+            cnt++;
+            int rewired;
+            block_scan(sh, mine_rewired, &rewired);         // (its barriers: the new node, the parents and the lengths are written)
+            rewires += rewired;
+            // ---- cost re-derivation: cost_k = cost_parent(k) + len_k in passes, each reading the pass before, until a pass changes nothing
+            for (int pass = 0; rewired > 0 && pass < cnt; pass++) {
+                double nv[WS_PER_LANE];
+                bool changed = false;
+#pragma unroll
+                for (int k = 0; k < WS_PER_LANE; k++) {
+                    const int c = t + k * TP_BLOCK;
+                    nv[k] = 0.0;
+                    if (c < cnt && par[c] >= 0) {
+                        nv[k] = ncost[par[c]] + nlen[c];
+                        changed = changed || nv[k] != ncost[c];
+                    }
+                }
+                __syncthreads();                            // every lane has read the costs of the pass before
+#pragma unroll
+                for (int k = 0; k < WS_PER_LANE; k++) {
+                    const int c = t + k * TP_BLOCK;
+                    if (c < cnt && par[c] >= 0) ncost[c] = nv[k];
+                }
+                if (!block_any(sh, changed)) break;         // (its barriers: the costs of this pass are written)
+            }
+        }
+        __syncthreads();
+        // ---- best node: within goal_tol the smallest (cost + distance, index), else the smallest (squared distance, index)
+        double bk = INFINITY, ba = INFINITY;
+        int bi = TP_NONE, ai = TP_NONE;
+        for (int c = t; c < cnt; c += TP_BLOCK) {
+            double D[3];
+            const double g2 = ws_diff(nx + (size_t)c * 3, goal, D), g = sqrt(g2);
+            if (key_less(g2, c, ba, ai)) { ba = g2; ai = c; }
+            if (g <= ar.goal_tol) {
+                const double key = ncost[c] + g;
+                if (key_less(key, c, bk, bi)) { bk = key; bi = c; }
+            }
+        }
+        block_argmin(sh, &bk, &bi);
+        block_argmin(sh, &ba, &ai);
+        status = bi != TP_NONE ? ARMOUR_WS_REACHED : ARMOUR_WS_PARTIAL;
+        const int best = bi != TP_NONE ? bi : ai;
+        {
+            double D[3];
+            goal_dist = sqrt(ws_diff(nx + (size_t)best * 3, goal, D));
+        }
+        path_cost = ncost[best];
+        // the path root -> best: two walks, bounded by the count
+        int len = 0;
+        for (int x = best; x >= 0 && x < cnt && len < cnt; x = par[x]) len++;
+        points = len;
+        if (ar.path && points <= ar.max_points && t < 3) {
+            double* out = ar.path + ((size_t)w * ar.max_points) * 3;
+            int pos = len - 1, d = 0;
+            for (int x = best; d < len; x = par[x], d++, pos--) out[(size_t)pos * 3 + t] = nx[(size_t)x * 3 + t];
+        }
+    }
+    if (t == 0) {
+        ar.status[w] = status;
+        ar.iterations[w] = iterations;
+        ar.points[w] = points;
+        ar.rewires[w] = rewires;
+        ar.chain_kept[w] = kept;
+        ar.count[w] = cnt;
+        ar.path_cost[w] = path_cost;
+        ar.goal_dist[w] = goal_dist;
+    }
+}
+
+// ---- the host twin: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
+struct WsHost {
+    const double* obs;
+    int O;
+    double buf, edge_step;
+    double* margin;
+
+    void note(const double (&x)[3], const double (&h)[3]) const {
+        if (margin) *margin = std::fmin(*margin, std::fabs(ws_box_clearance(x, h, obs, O)));
+    }
+    bool point(const double* p) const {
+        const double x[3] = {p[0], p[1], p[2]}, h[3] = {buf, buf, buf};
+        note(x, h);
+        return ws_box_free(x, h, obs, 0, O);
+    }
+    // prefix(a, b): sub-segments in ascending order up to the first that does not separate; free when m == S
+    bool edge(const double* a, const double* b) const {
+        double D[3];
+        const int S = ws_segments(sqrt(ws_diff(a, b, D)), edge_step);
+        for (int s = 0; s < S; s++) {
+            double x[3], h[3];
+            ws_sub_box(a, D, s, S, buf, x, h);
+            note(x, h);
+            if (!ws_box_free(x, h, obs, 0, O)) return false;
+        }
+        return true;
+    }
+};
+
+// world w of the host twin; the tree goes to nx [max_nodes][3] / par / ncost / nlen [max_nodes] (the caller's rows or scratch)
+void plan_world_host(const WsArgs& ar, int w, const double* obs, double* nx, int32_t* par, double* ncost, double* nlen, double* margin) {
+    const int cap = ar.max_nodes;
+    const double* start = ar.starts + (size_t)w * 3;
+    const double* goal = ar.goals + (size_t)w * 3;
+    const uint64_t seed = ar.seeds[w];
+    const double rr2 = ar.rewire_radius * ar.rewire_radius;
+    if (margin) *margin = INFINITY;
+    const WsHost hw{obs, ar.O, ar.buffer, ar.edge_step, margin};
+    double D[3];
+    int cnt = 0, rewires = 0, kept = 0;
+    ar.status[w] = ARMOUR_WS_START_BLOCKED;
+    ar.iterations[w] = ar.points[w] = ar.rewires[w] = ar.chain_kept[w] = 0;
+    if (ar.count) ar.count[w] = 0;
+    ar.path_cost[w] = 0.0;
+    ar.goal_dist[w] = sqrt(ws_diff(start, goal, D));
+    if (!hw.point(start)) return;
+    std::memcpy(nx, start, 3 * sizeof(double));
+    par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0;
+    cnt = 1;
+    const int chain = ar.init ? ar.init_count[w] : 0;
+    for (int c = 0; c < chain && cnt < cap; c++) {
+        const double* x = ar.init + ((size_t)w * ar.max_init + c) * 3;
+        const double* prev = nx + (size_t)(cnt - 1) * 3;
+        if (!hw.edge(prev, x)) break;
+        const double d = sqrt(ws_diff(prev, x, D));
+        std::memcpy(nx + (size_t)cnt * 3, x, 3 * sizeof(double));
+        par[cnt] = cnt - 1; nlen[cnt] = d; ncost[cnt] = ncost[cnt - 1] + d;
+        cnt++;
+        kept++;
+    }
+    int iterations = ar.max_iterations;
+    std::vector<int> free_c;
+    std::vector<double> free_d;
+    for (int i = 0; i < ar.max_iterations; i++) {
+        if (cnt >= cap) { iterations = i; break; }
+        double qr[3], qn[3];
+        ws_sample(ar, seed, i, goal, qr);
+        double acc = INFINITY;
+        int v = TP_NONE;
+        for (int c = 0; c < cnt; c++) {
+            const double d2 = ws_diff(nx + (size_t)c * 3, qr, D);
+            if (key_less(d2, c, acc, v)) { acc = d2; v = c; }
+        }
+        if (acc == 0.0) continue;
+        ws_diff(nx + (size_t)v * 3, qr, D);
+        ws_steer(nx + (size_t)v * 3, qr, D, sqrt(acc), ar.step, qn);
+        free_c.clear(); free_d.clear();
+        double pk = INFINITY;
+        int p = TP_NONE;
+        for (int c = 0; c < cnt; c++) {
+            const double d2 = ws_diff(nx + (size_t)c * 3, qn, D);
+            if (!(c == v || d2 <= rr2) || !hw.edge(nx + (size_t)c * 3, qn)) continue;
+            const double d_c = sqrt(d2), key = ncost[c] + d_c;
+            free_c.push_back(c); free_d.push_back(d_c);
+            if (key_less(key, c, pk, p)) { pk = key; p = c; }
+        }
+        if (p == TP_NONE) continue;
+        const double d_p = sqrt(ws_diff(nx + (size_t)p * 3, qn, D)), cost_qn = ncost[p] + d_p;
+        int rewired = 0;
+        for (size_t k = 0; k < free_c.size(); k++) {
+            const int c = free_c[k];
+            if (c != p && cost_qn + free_d[k] < ncost[c]) { par[c] = cnt; nlen[c] = free_d[k]; rewired++; }
+        }
+        std::memcpy(nx + (size_t)cnt * 3, qn, 3 * sizeof(double));
+        par[cnt] = p; nlen[cnt] = d_p; ncost[cnt] = cost_qn;
+        cnt++;
+        rewires += rewired;
+        // the costs, re-derived in place: the same fixed point as the kernel's passes (the definition is recursive from the root)
+        for (int pass = 0; rewired > 0 && pass < cnt; pass++) {
+            bool changed = false;
+            for (int c = 1; c < cnt; c++) {
+                const double nv = ncost[par[c]] + nlen[c];
+                if (nv != ncost[c]) { ncost[c] = nv; changed = true; }
+            }
+            if (!changed) break;
+        }
+    }
+    double bk = INFINITY, ba = INFINITY;
+    int bi = TP_NONE, ai = TP_NONE;
+    for (int c = 0; c < cnt; c++) {
+        const double g2 = ws_diff(nx + (size_t)c * 3, goal, D), g = sqrt(g2);
+        if (key_less(g2, c, ba, ai)) { ba = g2; ai = c; }
+        if (g <= ar.goal_tol) {
+            const double key = ncost[c] + g;
+            if (key_less(key, c, bk, bi)) { bk = key; bi = c; }
+        }
+    }
+    const int best = bi != TP_NONE ? bi : ai;
+    int len = 0;
+    for (int x = best; x >= 0 && x < cnt && len < cnt; x = par[x]) len++;
+    ar.status[w] = bi != TP_NONE ? ARMOUR_WS_REACHED : ARMOUR_WS_PARTIAL;
+    ar.iterations[w] = iterations;
+    ar.points[w] = len;
+    ar.rewires[w] = rewires;
+    ar.chain_kept[w] = kept;
+    if (ar.count) ar.count[w] = cnt;
+    ar.path_cost[w] = ncost[best];
+    ar.goal_dist[w] = sqrt(ws_diff(nx + (size_t)best * 3, goal, D));
+    if (ar.path && len <= ar.max_points) {
+        double* out = ar.path + ((size_t)w * ar.max_points) * 3;
+        int pos = len - 1, d = 0;
+        for (int x = best; d < len; x = par[x], d++, pos--) std::memcpy(out + (size_t)pos * 3, nx + (size_t)x * 3, 3 * sizeof(double));
+    }
+}
+
+// the argument rules of both entries, before a device is touched; fills ar (the caller's pointers)
+int check_args(const char* who, const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
+               const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step, double rewire_radius,
+               double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status,
+               int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path, int32_t* count,
+               double* nodes, int32_t* parent, double* node_cost, WsArgs* ar) {
+    if (!lb || !ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
+    if (W > 0 && (!starts || !goals || !seeds || !status || !iterations || !points || !rewires || !chain_kept || !path_cost || !goal_dist)) {
+        armour_set_error("%s: null argument", who);
+        return ARMOUR_EINVAL;
+    }
+    if (max_nodes < 1 || max_nodes > ARMOUR_WS_MAX_NODES || max_iterations < 0 || max_iterations > ARMOUR_TREE_MAX_ITERATIONS || max_points < 0) {
+        armour_set_error("%s: max_nodes = %d (1..%d), max_iterations = %d (0..%d), max_points = %d", who, max_nodes, ARMOUR_WS_MAX_NODES, max_iterations,
+                         ARMOUR_TREE_MAX_ITERATIONS, max_points);
+        return ARMOUR_EINVAL;
+    }
+    const double reals[6] = {step, edge_step, rewire_radius, goal_rate, buffer, goal_tol};
+    if (!finite_all(reals, 6) || !(step > 0.0) || !(edge_step > 0.0) || rewire_radius < 0.0 || buffer < 0.0 || goal_tol < 0.0 || goal_rate < 0.0 || goal_rate > 1.0) {
+        armour_set_error("%s: step = %g, edge_step = %g (> 0), rewire_radius = %g, buffer = %g, goal_tol = %g (>= 0), goal_rate = %g (0..1)", who, step, edge_step,
+                         rewire_radius, buffer, goal_tol, goal_rate);
+        return ARMOUR_EINVAL;
+    }
+    for (int j = 0; j < 3; j++)
+        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: sampling box [%g, %g] of axis %d", who, lb[j], ub[j], j); return ARMOUR_EINVAL; }
+    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(starts, (size_t)W * 3) || !finite_all(goals, (size_t)W * 3)) {
+        armour_set_error("%s: a start, a goal or an obstacle is not finite", who);
+        return ARMOUR_EINVAL;
+    }
+    if (!(std::ceil(std::fmax(step, rewire_radius) / edge_step) <= (double)ARMOUR_WS_MAX_SEGMENTS)) {
+        armour_set_error("%s: step = %g, rewire_radius = %g: more than %d sub-segments of edge_step %g", who, step, rewire_radius, ARMOUR_WS_MAX_SEGMENTS, edge_step);
+        return ARMOUR_EINVAL;
+    }
+    if (init) {
+        if (max_init < 1 || (W > 0 && !init_count)) { armour_set_error("%s: max_init = %d (>= 1 with init), init_count", who, max_init); return ARMOUR_EINVAL; }
+        for (int32_t w = 0; w < W; w++) {
+            const int32_t c = init_count[w];
+            if (c < 0 || c > max_init) { armour_set_error("%s: init_count[%d] = %d (0..%d)", who, w, c, max_init); return ARMOUR_EINVAL; }
+            const double* x = init + (size_t)w * max_init * 3;
+            if (!finite_all(x, (size_t)c * 3)) { armour_set_error("%s: world %d's chain is not finite", who, w); return ARMOUR_EINVAL; }
+            const double* prev = starts + (size_t)w * 3;
+            for (int32_t k = 0; k < c; prev = x + (size_t)k * 3, k++) {
+                double D[3];
+                const double len = std::sqrt(ws_diff(prev, x + (size_t)k * 3, D));
+                if (!(std::ceil(len / edge_step) <= (double)ARMOUR_WS_MAX_SEGMENTS)) {
+                    armour_set_error("%s: world %d's chain edge %d of length %g: more than %d sub-segments of edge_step %g", who, w, k, len, ARMOUR_WS_MAX_SEGMENTS, edge_step);
+                    return ARMOUR_EINVAL;
+                }
+            }
+        }
+    }
+    std::memset(ar, 0, sizeof(*ar));
+    for (int j = 0; j < 3; j++) { ar->lb[j] = lb[j]; ar->ub[j] = ub[j]; }
+    ar->step = step; ar->edge_step = edge_step; ar->rewire_radius = rewire_radius; ar->goal_rate = goal_rate; ar->buffer = buffer; ar->goal_tol = goal_tol;
+    ar->O = O; ar->max_iterations = max_iterations; ar->max_nodes = max_nodes; ar->max_points = max_points; ar->max_init = init ? max_init : 0;
+    ar->obstacles = obstacles; ar->starts = starts; ar->goals = goals; ar->init = init; ar->init_count = init ? init_count : nullptr; ar->seeds = seeds;
+    ar->status = status; ar->iterations = iterations; ar->points = points; ar->rewires = rewires; ar->chain_kept = chain_kept; ar->count = count;
+    ar->parent = parent; ar->path_cost = path_cost; ar->goal_dist = goal_dist; ar->path = path; ar->nodes = nodes; ar->node_cost = node_cost;
+    return ARMOUR_OK;
+}
+
+// the roadmap entries' capacity rule: points [W] is complete; a path longer than max_points was not written
+int check_capacity(const char* who, int32_t W, const int32_t* points, const double* path, int32_t max_points) {
+    for (int32_t w = 0; path && w < W; w++)
+        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
+    return ARMOUR_OK;
+}
+
+}  // namespace
+
+extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
+                                        const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                                        double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
+                                        int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
+                                        double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost,
+                                        double* margin) {
+    const char* who = "armour_ws_tree_plan_host";
+    WsArgs ar;
+    ARMOUR_TRY(check_args(who, lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                          max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent,
+                          node_cost, &ar));
+    const size_t cap = (size_t)max_nodes;
+    std::vector<double> obs((size_t)O * RM_OBS_STRIDE), own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);   // staged as the kernel stages them
+    std::vector<int32_t> own_parent(parent ? 0 : cap);
+    for (int32_t w = 0; w < W; w++) {
+        stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
+        plan_world_host(ar, w, obs.data(), nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
+                        node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr);
+    }
+    return check_capacity(who, W, points, path, max_points);
+}
+
+extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
+                                   const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                                   double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
+                                   int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
+                                   double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* ms) {
+    const char* who = "armour_ws_tree_plan";
+    WsArgs ar;
+    ARMOUR_TRY(check_args(who, lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                          max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent,
+                          node_cost, &ar));
+    if (ms) *ms = 0.0;
+    if (W == 0) return ARMOUR_OK;
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ws_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
+    const size_t cap = (size_t)max_nodes, rows = (size_t)W * cap, path_len = path ? (size_t)W * max_points * 3 : 0;
+    DevStream st;
+    EventPair ev;
+    DevBuf<double> d_obs, d_starts, d_goals, d_init, d_nodes, d_cost, d_len, d_path, d_real;   // d_real: path_cost | goal_dist [W] each
+    DevBuf<uint64_t> d_seeds;
+    DevBuf<int32_t> d_init_count, d_out, d_parent;          // d_out: status | iterations | points | rewires | chain_kept | count [W] each
+    ARMOUR_TRY(st.create());
+    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_starts.upload(starts, (size_t)W * 3, st));
+    ARMOUR_TRY(d_goals.upload(goals, (size_t)W * 3, st));
+    ARMOUR_TRY(d_seeds.upload(seeds, (size_t)W, st));
+    if (init) {
+        ARMOUR_TRY(d_init.upload(init, (size_t)W * max_init * 3, st));
+        ARMOUR_TRY(d_init_count.upload(init_count, (size_t)W, st));
+    }
+    ARMOUR_TRY(d_nodes.reserve(rows * 3));
+    ARMOUR_TRY(d_cost.reserve(rows));
+    ARMOUR_TRY(d_len.reserve(rows));
+    ARMOUR_TRY(d_parent.reserve(rows));
+    ARMOUR_TRY(d_out.reserve((size_t)6 * W));
+    ARMOUR_TRY(d_real.reserve((size_t)2 * W));
+    if (path) ARMOUR_TRY(d_path.reserve(path_len));
+    WsArgs dev = ar;
+    dev.obstacles = d_obs; dev.starts = d_starts; dev.goals = d_goals; dev.seeds = d_seeds;
+    dev.init = init ? d_init.p : nullptr; dev.init_count = init ? d_init_count.p : nullptr;
+    dev.status = d_out; dev.iterations = d_out + W; dev.points = d_out + 2 * (size_t)W; dev.rewires = d_out + 3 * (size_t)W;
+    dev.chain_kept = d_out + 4 * (size_t)W; dev.count = d_out + 5 * (size_t)W;
+    dev.path_cost = d_real; dev.goal_dist = d_real + W;
+    dev.parent = d_parent; dev.nodes = d_nodes; dev.node_cost = d_cost; dev.node_len = d_len; dev.path = path ? d_path.p : nullptr;
+    ARMOUR_TRY(ev.record_start(st));
+    hipLaunchKernelGGL(ws_tree_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, dev);
+    HIPCHK(hipGetLastError());
+    ARMOUR_TRY(ev.record_stop(st));
+    std::vector<int32_t> out((size_t)6 * W);
+    std::vector<double> real((size_t)2 * W);
+    HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(real.data(), d_real, real.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
+    int32_t* const ints[5] = {status, iterations, points, rewires, chain_kept};
+    for (int k = 0; k < 5; k++) std::memcpy(ints[k], out.data() + k * (size_t)W, (size_t)W * sizeof(int32_t));
+    const int32_t* h_count = out.data() + 5 * (size_t)W;
+    if (count) std::memcpy(count, h_count, (size_t)W * sizeof(int32_t));
+    std::memcpy(path_cost, real.data(), (size_t)W * sizeof(double));
+    std::memcpy(goal_dist, real.data() + W, (size_t)W * sizeof(double));
+    // the trees and the paths: only the rows that were written come back (the rest of the caller's arrays is left as it was)
+    for (int32_t w = 0; w < W; w++) {
+        const size_t c = (size_t)h_count[w], row = (size_t)w * cap;
+        if (nodes && c) HIPCHK(hipMemcpyAsync(nodes + row * 3, d_nodes + row * 3, c * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (parent && c) HIPCHK(hipMemcpyAsync(parent + row, d_parent + row, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (node_cost && c) HIPCHK(hipMemcpyAsync(node_cost + row, d_cost + row, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (path && points[w] > 0 && points[w] <= max_points)
+            HIPCHK(hipMemcpyAsync(path + (size_t)w * max_points * 3, d_path + (size_t)w * max_points * 3, (size_t)points[w] * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return check_capacity(who, W, points, path, max_points);
+}

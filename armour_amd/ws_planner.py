@@ -1,0 +1,237 @@
+"""Batched workspace RRT* and the end-effector high-level planner on the MI355X (include/armour_hip.h, armour_ws_tree_plan).
+
+The reference's experiment scripts plan their waypoints with arm_end_effector_RRT_star_HLP: an RRT* for the end-effector POINT in the 3-D
+workspace, the point `lookahead_distance` along its best path, and inverse kinematics from 0.5 (q_cur + goal) to turn that point into a
+configuration (the goal configuration when that fails).  Here the trees of all live worlds of a trial grow in one launch and their waypoints
+are solved by one armour_ik call:
+
+    res = plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub)    # [W,O,12], [W,3], [W,3], [W] -> status [W], paths [W], path_cost [W]
+    res.paths[w]                                                           # [P,3] from start to the best node (None when the start is blocked)
+    z_des = waypoint_along_points(res.paths[w], z, 0.1)                    # the point 0.1 m past z's projection on the path
+    hlp = WorkspaceTreeHLP(robot, world_obstacles, goal); q_des = hlp.get_waypoint(q_cur, 0.1)
+    out = run_trials(worlds, hlp=workspace_hlps(worlds, robot))            # the end-effector planner as the trials' high-level planner
+
+The rule (point and edge tests, samples, parent choice, rewiring, cost re-derivation, best node), its two deliberate departures from the
+reference, the soundness arguments and the limits are stated in include/armour_hip.h; DESIGN.md 4.12f.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import _dp, check
+from . import ik
+from .scenes import pad_obstacles
+from .tree_planner import call_seed
+
+PARTIAL, REACHED, START_BLOCKED = _lib.WS_PARTIAL, _lib.WS_REACHED, _lib.WS_START_BLOCKED
+
+# Arm-sized defaults.  The reference's step 0.5 m and rewire distance 1 m are sized for ground vehicles in rooms of tens of metres; an arm's
+# workspace is a ball of about 1 m.  The same proportions to the workspace -- a step of a tenth of the reach, a rewire radius of twice the
+# step, as 1 m is twice 0.5 m -- give 0.1 m and 0.2 m; goal_tol is one edge_step.  DESIGN.md 4.12f.
+STEP, EDGE_STEP, REWIRE_RADIUS, GOAL_RATE, GOAL_TOL = 0.1, 0.01, 0.2, 0.1, 0.01
+MAX_ITERATIONS, MAX_NODES = 1000, 1024
+
+
+class WorkspacePlans:
+    """What plan_workspace_trees returns: status [W] (PARTIAL / REACHED / START_BLOCKED), iterations / rewires / chain_kept / count [W],
+    path_cost / goal_dist [W], paths (a list; [P,3] from the start to the best node, None where the start is blocked), ms (device time of
+    the launch; 0 on the host), margin [W] (host only, else None: the smallest |clearance| that decided the run), and with trees=True nodes
+    [W,max_nodes,3], parent [W,max_nodes], node_cost [W,max_nodes] (rows past count are zero)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def workspace_box(robot, tool=None):
+    """A default sampling box from the chain's reach: the cube about the base whose half-side is the sum of the links' translation lengths
+    (plus |tool|), i.e. a box no end-effector point can leave -> (lb [3], ub [3])."""
+    J = robot.num_joints
+    trans = np.array(robot.trans[:3 * J], dtype=np.float64).reshape(J, 3)
+    reach = float(np.sqrt((trans * trans).sum(1)).sum()) + (0.0 if tool is None else float(np.linalg.norm(np.asarray(tool, dtype=np.float64))))
+    return np.full(3, -reach), np.full(3, reach)
+
+
+def plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, step=STEP, edge_step=EDGE_STEP, rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE, buffer=0.0,
+                         goal_tol=GOAL_TOL, max_iterations=MAX_ITERATIONS, max_nodes=MAX_NODES, init=None, host=False, trees=False, max_points=None):
+    """obstacles [W,O,12] (or [O,12]: W = 1), starts / goals [W,3] (points of the workspace), seeds [W] (uint64), lb / ub [3] (the sampling box)
+    -> WorkspacePlans.  edge_step and goal_rate default to the reference's (arm_end_effector_RRT_star_HLP.m:5, RRT_star_HLP.m:24); step,
+    rewire_radius and goal_tol are arm-sized (see STEP above).  rewire_radius = 0 is plain RRT.  init: None, or W entries, each None or a
+    chain [C,3] offered before the loop (the reference's 'seed' mode).  max_points: the path rows to reserve (default: max_nodes, which a
+    path cannot exceed).  host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
+    L = _lib.load()
+    obs = np.asarray(obstacles, dtype=np.float64)
+    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+    W, O = obs.shape[0], obs.shape[1]
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(W, 3))
+    g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(W, 3))
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (W,)))
+    lb = np.ascontiguousarray(lb, dtype=np.float64).reshape(3)
+    ub = np.ascontiguousarray(ub, dtype=np.float64).reshape(3)
+    cap = int(max_nodes)
+    max_points = max(cap, 0) if max_points is None else int(max_points)
+    i32 = C.POINTER(C.c_int32)
+    chain, chain_count, max_init = None, None, 0
+    if init is not None:
+        chains = [np.zeros((0, 3)) if c is None else np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in init]
+        if len(chains) != W:
+            raise ValueError(f"{len(chains)} chains for {W} worlds")
+        chain_count = np.array([c.shape[0] for c in chains], dtype=np.int32)
+        max_init = max(int(chain_count.max()) if W else 1, 1)
+        chain = np.zeros((W, max_init, 3))
+        for w, c in enumerate(chains):
+            chain[w, :c.shape[0]] = c
+    status, iterations, points, rewires, chain_kept, count = (np.zeros(W, dtype=np.int32) for _ in range(6))
+    path_cost, goal_dist = np.zeros(W), np.zeros(W)
+    path = np.zeros((W, max(max_points, 0), 3))
+    rows = max(cap, 0) if trees else 0
+    nodes, parent, node_cost = np.zeros((W, rows, 3)), np.zeros((W, rows), dtype=np.int32), np.zeros((W, rows))
+    margin = np.zeros(W) if host else None
+    ms = C.c_double()
+    fn = L.armour_ws_tree_plan_host if host else L.armour_ws_tree_plan
+    check(fn(_dp(lb), _dp(ub), W, O, _dp(obs) if obs.size else None, _dp(s), _dp(g), sd.ctypes.data_as(C.POINTER(C.c_uint64)), max_init, _dp(chain),
+             None if chain_count is None else chain_count.ctypes.data_as(i32), float(step), float(edge_step), float(rewire_radius), float(goal_rate), float(buffer),
+             float(goal_tol), int(max_iterations), cap, max_points, status.ctypes.data_as(i32), iterations.ctypes.data_as(i32), points.ctypes.data_as(i32),
+             rewires.ctypes.data_as(i32), chain_kept.ctypes.data_as(i32), _dp(path_cost), _dp(goal_dist), _dp(path), count.ctypes.data_as(i32),
+             _dp(nodes) if trees else None, parent.ctypes.data_as(i32) if trees else None, _dp(node_cost) if trees else None,
+             _dp(margin) if host else C.byref(ms)))
+    paths = [path[w, :points[w]].copy() if status[w] != START_BLOCKED else None for w in range(W)]
+    out = WorkspacePlans(status=status, iterations=iterations, rewires=rewires, chain_kept=chain_kept, count=count, path_cost=path_cost, goal_dist=goal_dist,
+                         paths=paths, nodes=None, parent=None, node_cost=None, margin=margin, ms=0.0 if host else ms.value)
+    if trees:
+        out.nodes, out.parent, out.node_cost = nodes, parent, node_cost
+    return out
+
+
+def _project(path, z):
+    """(segment, t, distance along the path) of the point of the polyline nearest to z; the first segment on a tie."""
+    best, along = None, 0.0
+    for k in range(len(path) - 1):
+        a, d = path[k], path[k + 1] - path[k]
+        dd = float(d @ d)
+        t = 0.0 if dd == 0.0 else min(max(float((z - a) @ d) / dd, 0.0), 1.0)
+        e = z - (a + t * d)
+        dist2, seg = float(e @ e), float(np.sqrt(dd))
+        if best is None or dist2 < best[0]:
+            best = (dist2, k, t, along + t * seg)
+        along += seg
+    return best[1:]
+
+
+def waypoint_along_points(path, z, lookahead):
+    """The point `lookahead` metres past the projection of z on the polyline path [P,3] (RRT_HLP.m:341-359: the agent's distance along the
+    best path, plus the lookahead, clipped to the path's length, interpolated on the path); the last point when the path ends sooner.
+    Host only."""
+    path = np.asarray(path, dtype=np.float64).reshape(-1, 3)
+    z = np.asarray(z, dtype=np.float64).reshape(3)
+    if path.shape[0] == 1:
+        return path[0].copy()
+    _, _, d = _project(path, z)
+    target, along = d + float(lookahead), 0.0
+    for k in range(path.shape[0] - 1):
+        seg = float(np.linalg.norm(path[k + 1] - path[k]))
+        if seg > 0.0 and target <= along + seg:
+            return path[k] + ((target - along) / seg) * (path[k + 1] - path[k])
+        along += seg
+    return path[-1].copy()
+
+
+class WorkspaceTreeHLP:
+    """The reference's arm_end_effector_RRT_star_HLP for one world: get_waypoint(q_cur, lookahead) grows a workspace tree from the end
+    effector of q_cur towards the end effector of the goal configuration, takes the point `lookahead` METRES along its path and returns
+    the configuration that inverse kinematics finds for it (q_ref = 0.5 (q_cur + goal) with ik_reference='mid', q_cur with 'current'),
+    judged free in this world; the goal configuration when no free solution is found (the reference's fall-back) or the start is blocked.
+    The c-th call uses the seed call_seed(seed, world, c) for the tree and for the inverse kinematics.
+      mode='new' (the default; the reference's grow_tree_mode = 'new'): a fresh tree at every call.
+      mode='seed': [the current point] + the rest of the last path, from the vertex after the one nearest to the current point, is offered
+        as the initial chain.
+    plan_options go to plan_workspace_trees (step, edge_step, rewire_radius, goal_rate, buffer, goal_tol, max_iterations, max_nodes; lb /
+    ub default to workspace_box); ik_options go to ik.solve_ik (S, lam, e_max, tol, max_iterations, tool)."""
+
+    def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, mode="new", ik_reference="mid", ik_options=None, **plan_options):
+        if mode not in ("new", "seed") or ik_reference not in ("mid", "current"):
+            raise ValueError(f"mode = {mode!r} ('new' or 'seed'), ik_reference = {ik_reference!r} ('mid' or 'current')")
+        self.robot, self.goal, self.seed, self.world, self.host = robot, np.asarray(goal, dtype=np.float64), int(seed), int(world), bool(host)
+        self.mode, self.ik_reference = mode, ik_reference
+        self.obstacles = np.asarray(world_obstacles, dtype=np.float64).reshape(-1, 12)
+        self.ik_options = dict(ik_options or {})
+        self.options = dict(plan_options)
+        lb, ub = workspace_box(robot, self.ik_options.get("tool"))
+        self.options.setdefault("lb", lb)
+        self.options.setdefault("ub", ub)
+        self.goal_point = ik.end_effector(robot, self.goal, self.ik_options.get("tool"))
+        self.calls, self.path, self.status, self.ik_status, self.waypoint, self.margin_min = 0, None, None, None, None, np.inf
+        self.fallbacks = 0                 # calls that returned the goal configuration
+
+    def get_waypoint(self, q_cur, lookahead):
+        return _waypoints([self], [q_cur], [lookahead])[0][0]
+
+
+def _chain(h, z):
+    if h.mode != "seed" or h.path is None:
+        return None
+    k = int(np.argmin(((h.path - z) ** 2).sum(1)))
+    return np.vstack([z[None], h.path[k + 1:]])
+
+
+def _waypoints(hl, qs, lookaheads):
+    """One call of each of the HLPs `hl` (one robot, one obstacle count, the same options) from qs: ONE armour_ws_tree_plan call and ONE
+    armour_ik call -> (waypoint configurations, the launches' ms)."""
+    h0 = hl[0]
+    robot, host = h0.robot, h0.host
+    qs = np.stack([np.asarray(q, dtype=np.float64) for q in qs])
+    obstacles = np.stack([h.obstacles for h in hl])
+    z = ik.end_effector(robot, qs, h0.ik_options.get("tool")).reshape(-1, 3)
+    seeds = np.array([call_seed(h.seed, h.world, h.calls) for h in hl], dtype=np.uint64)
+    chains = [_chain(h, z[k]) for k, h in enumerate(hl)]
+    res = plan_workspace_trees(obstacles, z, np.stack([h.goal_point for h in hl]), seeds, init=chains if any(c is not None for c in chains) else None,
+                               host=host, **h0.options)
+    points = np.stack([z[k] if p is None else waypoint_along_points(p, z[k], la) for k, (p, la) in enumerate(zip(res.paths, lookaheads))])
+    goals = np.stack([h.goal for h in hl])
+    sol = ik.solve_ik(robot, points, 0.5 * (qs + goals) if h0.ik_reference == "mid" else qs, obstacles, np.arange(len(hl)), seeds, host=host, **h0.ik_options)
+    out = []
+    for k, h in enumerate(hl):
+        found = res.paths[k] is not None and sol.status[k] == ik.FOUND
+        h.calls += 1
+        h.path, h.status, h.ik_status, h.waypoint = res.paths[k], int(res.status[k]), int(sol.status[k]), points[k]
+        h.fallbacks += 0 if found else 1
+        if res.margin is not None:
+            h.margin_min = min(h.margin_min, float(res.margin[k]))
+        out.append(sol.q[k].copy() if found else h.goal.copy())
+    return out, res.ms + sol.ms
+
+
+def workspace_hlps(worlds, robot, seed=0, lookahead=0.1, mode="new", ik_reference="mid", host=False, batched=True, ik_options=None, **options):
+    """`worlds` as trials.run_trials takes them ([(name, problem)]) -> the factory (i, world) -> WorkspaceTreeHLP that run_trials(hlp=...)
+    accepts (world i's obstacles padded to the worlds' largest count, its goal configuration, the trial's seed).  With batched (the default)
+    the factory carries get_waypoints(indices, qs, lookaheads), which serves ALL live worlds of an iteration with ONE armour_ws_tree_plan call and ONE armour_ik
+    call (make.last_ms is their device time): the end-effector points of qs (ik.end_effector), the trees, the workspace waypoints, then
+    solve_ik(targets = the waypoints, q_ref = 0.5 (q_cur + goal) | q_cur, world = the target's world); a target that is not IK_FOUND yields
+    the goal configuration.  The seeds are the per-world objects' (tree_planner.call_seed), so the waypoints are the same either way.
+    lookahead is in METRES of end-effector travel (default: the reference scripts' 0.1): the trials' own `lookahead` values are distances in
+    joint space and are ignored, per world and batched alike.  mode / ik_reference / ik_options / options: WorkspaceTreeHLP's."""
+    probs = [p for _, p in worlds]
+    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
+    O = max([o.shape[0] for o in obs] + [1])
+    obstacles = np.stack([pad_obstacles(o, O) for o in obs]) if obs else np.zeros((0, O, 12))
+    goals = [np.asarray(p["goal"], dtype=np.float64) for p in probs]
+    made = {}
+    lookahead = float(lookahead)
+
+    class _Metres(WorkspaceTreeHLP):
+        def get_waypoint(self, q_cur, _joint_space_lookahead):
+            return _waypoints([self], [q_cur], [lookahead])[0][0]
+
+    def make(i, world):
+        made[i] = _Metres(robot, obstacles[i], goals[i], seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference, ik_options=ik_options, **options)
+        return made[i]
+
+    def get_waypoints(indices, qs, lookaheads):
+        hl = [made[int(i)] if int(i) in made else make(int(i), None) for i in indices]
+        out, make.last_ms = _waypoints(hl, qs, [lookahead] * len(hl))
+        return out
+
+    make.hlps = made
+    if batched:
+        make.get_waypoints = get_waypoints
+    return make

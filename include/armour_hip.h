@@ -944,6 +944,98 @@ int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuous, const do
                    double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags, double* margin);
 int armour_ik_end_effector_host(const ArmourRobot* robot, int32_t N, const double* q, const double* tool, double* p, double* jac);
 
+/* ---- batched workspace RRT*: the end-effector planner's tree for W worlds in one launch (ws_tree.hip) ---- */
+/* The reference's experiments plan their waypoints with arm_end_effector_RRT_star_HLP: an RRT* grown in the 3-D workspace for the
+ * end-effector POINT (RRT_HLP.m, RRT_star_HLP.m), whose best path is followed for a lookahead distance and turned into a configuration by
+ * inverse kinematics (armour_ik).  This entry grows that tree, W worlds at a time.  Deterministic: a world's result depends on its own
+ * inputs and seed alone, and the device and the host entry run the same functions.  fp64 throughout, no fused multiply-add;
+ * dot(a, b) = (a0 b0 + a1 b1) + a2 b2 as the inverse kinematics writes it.
+ *
+ * Point rule.  A point x with buffer b >= 0 is the box with centre x, axes e_0, e_1, e_2 and half-sizes (b, b, b); it is tested against an
+ *   obstacle by the roadmap's pair test as it stands (verdict mode), and x is FREE when every obstacle of the world separates.  The
+ *   reference inflates its axis-aligned boxes by 2 b per side (arm_end_effector_RRT_star_HLP.m:117): the same set for those boxes, and
+ *   this form is defined for the general obstacle [c g1 g2 g3] as well.  Nothing geometric is restated.
+ * Edge rule (conservative, sound).  The edge a -> b:  D = b - a component by component, len = sqrt(dot(D, D)),
+ *   S = min(ARMOUR_WS_MAX_SEGMENTS, max(1, ceil(len / edge_step))).  Sub-segment s = 0 .. S - 1 is tested as the box with centre a + t_s D,
+ *   t_s = fl(2 s + 1) / fl(2 S), and half-sizes b + |D_i| / fl(2 S): the exact bounding box of the sub-segment, grown by the buffer, so a
+ *   sub-segment whose test separates touches no buffered obstacle -- for any S >= 1, which is why the cap on S costs resolution and not
+ *   soundness.  prefix(a, b) -> (m, S) as in the tree planner (m = the first sub-segment that does not separate, S when all do); the edge
+ *   is FREE when m == S.  An edge is always tested in the direction existing node -> new point: one test serves the parent choice and
+ *   the rewire.
+ * Samples.  u(seed, i, j) is the tree planner's.  In iteration i: u(seed, i, 3) < goal_rate -> the sample is the goal; otherwise
+ *   qr_j = lb_j + u(seed, i, j) (ub_j - lb_j), j = 0 .. 2.
+ * The run of one world (cap = max_nodes; a node holds x, parent, len = the length of its parent edge, and cost):
+ *     point rule at start: not free -> START_BLOCKED, 0 iterations, count 0, no path (path_cost 0, goal_dist = |goal - start|)
+ *     tree = {start}: cost 0, len 0, parent -1
+ *     initial chain (init, init_count[w] >= 1; the reference's 'seed' mode, RRT_HLP.m:104-107): chain point c = 0, 1, ... is appended with
+ *       parent = the node appended before it (the root for c = 0), len = d, cost = cost_parent + d, d = the edge's len, while that edge is
+ *       free and the tree is not full; the first edge that is not free ends the chain.  chain_kept = how many were appended.
+ *     for i = 0 .. max_iterations - 1:
+ *         the tree holds cap nodes -> stop, iterations = i
+ *         qr = the sample of i;  v = the node with the smallest (acc, index), acc = dot(D, D), D = qr - x_v;  acc == 0 -> next i
+ *         dist = sqrt(acc);  qn = qr when dist <= step, else qn_j = x_v_j + (step / dist) D_j
+ *         candidates = every node c with acc_c <= rewire_radius rewire_radius (acc_c: from x_c to qn), and v.  rewire_radius = 0: plain RRT.
+ *         for each candidate c:  d_c = sqrt(acc_c);  c is free when the edge x_c -> qn is FREE
+ *         no candidate is free -> next i
+ *         parent p = the free candidate with the smallest (cost_c + d_c, c);  append qn with len = d_p, cost = cost_p + d_p
+ *         rewire: every other free candidate c with cost_qn + d_c < cost_c (the costs as they were before any rewire of this iteration)
+ *           gets parent = qn, len = d_c;  rewires counts them
+ *         after any rewire the costs are re-derived so that cost_k = fl(cost_parent(k) + len_k) holds for every node, bit for bit: a
+ *           recursive definition from the root, independent of the schedule that reaches it
+ *     iterations = max_iterations when the loop ends by itself
+ *   Best node.  g_k = sqrt(acc), acc from x_k to goal.  Among the nodes with g_k <= goal_tol the smallest (cost_k + g_k, k): status REACHED.
+ *     With none, the smallest (acc, k): status PARTIAL, the reference's "path to the node closest to the goal" (RRT_HLP.m:267-299).
+ *     The path runs root -> best node (points of them); path_cost = the best node's cost, goal_dist = its g.
+ * Two deliberate departures from RRT_star_HLP.m:
+ *   Parent choice.  The reference picks the candidate parent by min(cost) alone (:110); here it is cost + distance, RRT* as published.
+ *   Stale costs.  After a rewire the reference never updates the rewired node's cost nor its descendants' (:147-153), which is how its
+ *     tree can come to hold a loop ("The RRT has a loop in it by accident!", RRT_HLP.m:308).  With re-derived costs no cycle can form:
+ *     costs are monotone along a branch, because fl(a + d) >= a for d >= 0; so an ancestor c of qn has cost_c <= cost_qn and cannot pass
+ *     the strict test cost_qn + d_c < cost_c; so every rewired node gets a parent (qn, a new leaf) that is not its descendant, and qn's
+ *     own chain to the root holds no rewired node.  The structure stays a tree rooted at start.
+ *   Soundness of the path: every tree edge -- a chain edge, a parent edge, a rewired edge -- is an edge whose every sub-segment's test
+ *     separated, so no point of a returned path, grown by the buffer, touches an obstacle.
+ * Limits (ARMOUR_EINVAL before a device is touched): W and O as armour_roadmap_check; 1 <= max_nodes <= ARMOUR_WS_MAX_NODES;
+ *   0 <= max_iterations <= ARMOUR_TREE_MAX_ITERATIONS; step, edge_step > 0; rewire_radius, buffer, goal_tol >= 0; 0 <= goal_rate <= 1; all
+ *   finite; lb <= ub, finite; finite starts, goals, chains and obstacles; 0 <= init_count[w] <= max_init (>= 1) when init is given;
+ *   ceil(max(step, rewire_radius) / edge_step) and ceil(len / edge_step) of every chain edge at most ARMOUR_WS_MAX_SEGMENTS (1024: a
+ *   1 m edge at 1 mm), so that no bound of a work list depends on what the run does; max_points >= 0.  When a path has more than max_points
+ *   points the call returns ARMOUR_ECAPACITY with points [W] complete and that world's rows unwritten (the roadmap entries' rule; without
+ *   path nothing is refused).  W = 0 is a success that does nothing.
+ * Arrays are host pointers.  lb / ub [3] the sampling box; obstacles [W][O][12]; starts / goals [W][3]; seeds [W]; optional init
+ *   [W][max_init][3] with init_count [W] (init NULL: no chains).  Outputs: status / iterations / points / rewires / chain_kept [W],
+ *   path_cost / goal_dist [W]; optional (NULL: not returned) path [W][max_points][3], count [W], nodes [W][max_nodes][3], parent
+ *   [W][max_nodes] (-1 at the root), node_cost [W][max_nodes], ms (device time of the launch).  Only the first count rows of a tree and
+ *   the first points rows of a path are written.
+ * Device: one launch, grid W, a 256-lane block per world with the world's obstacles staged in LDS; the loop above runs inside the block,
+ *   ordered by __syncthreads() alone -- no atomics, no flags, no block waits on another.  The tree lives in global memory, written and
+ *   read by its block alone.  The nearest scan and the near set deal the nodes to lanes; the candidates' sub-segments are one flat work
+ *   list across the lanes, 256 candidates to a round, and a short list gives each item several lanes, each with a slice of the obstacles
+ *   (the verdict of a sub-segment is the AND over obstacles, so nothing changes but the time); the parent is a reduction, every free
+ *   candidate decides its own rewire, and the costs are re-derived in passes that read the pass before until one changes nothing.
+ *   RRT* runs a fixed number of iterations, so the blocks of a launch do comparable work; W = 1 runs on one compute unit.
+ *   DESIGN.md 4.12f.
+ * armour_ws_tree_plan_host is the same functions in a loop and touches no device.  margin [W] (may be NULL): the smallest |clearance|
+ *   (per box: the minimum over the world's obstacles of the pair clearance) over the checks that decided -- the start point and
+ *   sub-segments 0 .. min(m, S - 1) of every prefix; +inf when nothing was checked or the world has no obstacles. */
+#define ARMOUR_WS_PARTIAL 0
+#define ARMOUR_WS_REACHED 1
+#define ARMOUR_WS_START_BLOCKED 2
+#define ARMOUR_WS_MAX_NODES 4096
+#define ARMOUR_WS_MAX_SEGMENTS 1024
+int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts,
+                        const double* goals, const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count,
+                        double step, double edge_step, double rewire_radius, double goal_rate, double buffer, double goal_tol,
+                        int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                        int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path, int32_t* count,
+                        double* nodes, int32_t* parent, double* node_cost, double* ms);
+int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts,
+                             const double* goals, const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count,
+                             double step, double edge_step, double rewire_radius, double goal_rate, double buffer, double goal_tol,
+                             int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations,
+                             int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path,
+                             int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* margin);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

@@ -1,7 +1,7 @@
 """Whole planning trials (armour_amd.trials.run_trials) and the path audit (armour_path_audit) measured; writes profiles/trial_bench.json
 and prints ONE JSON line.
 
-    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]|tree [--tree-shortcut P] [--tree-mode seed]]
+    python tools/trial_bench.py [--T 128] [--max-iterations 400] [--steps 0.01 0.05] [--reps 10] [--kernel-stats] [--hlp straight|roadmap-field [--batched]|tree [--tree-shortcut P] [--tree-mode seed]|workspace]
 
 * the 107 reference worlds end to end: outcomes, iterations, build / solve ms per batch iteration, audit ms, and -- re-auditing every
   executed piece -- the undecided pieces at each of --steps (with and without the controller's ultimate bound as tube);
@@ -20,6 +20,11 @@ and prints ONE JSON line.
   armour_path_shortcut) and / or --tree-mode seed (the last path is offered first; a tree grows only when it fails) the run goes under
   `hlp_outcomes_tree_seed` instead, with the number of reused paths and hard_2_wall's outcome by name, and the `hlp_outcomes_tree` row that
   the file already holds is kept for comparison;
+* --hlp workspace: the same worlds once more with the reference's own high-level planner, the end-effector RRT* (armour_amd.ws_planner.
+  workspace_hlps: a fresh workspace tree per world and iteration, all live worlds in one armour_ws_tree_plan call and one armour_ik call;
+  --tree-seed, --ws-iterations, --ws-nodes, --ws-lookahead in metres, --ws-buffer): `hlp_outcomes_workspace` holds the outcome counts beside
+  the straight-line run's, the worlds whose outcome differs, how many waypoints fell back to the goal configuration and `ms_per_batch`.  The
+  sections of the other planners that profiles/trial_bench.json already holds are kept;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -123,6 +128,24 @@ def tree_trials(robot, ws, straight, a):
                 changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
 
 
+def workspace_trials(robot, ws, straight, a):
+    """The worlds once more under workspace_hlps; outcome counts under both HLPs and the worlds that end differently."""
+    from armour_amd.trials import OUTCOMES, run_trials
+    from armour_amd.ws_planner import EDGE_STEP, GOAL_RATE, GOAL_TOL, REWIRE_RADIUS, STEP, workspace_hlps
+    options = dict(max_iterations=a.ws_iterations, max_nodes=a.ws_nodes, buffer=a.ws_buffer)
+    make = workspace_hlps(ws, robot, seed=a.tree_seed, lookahead=a.ws_lookahead, **options)
+    res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
+    per_batch = lambda key: dict(mean=float(np.mean([b[key] for b in res["batches"]])), max=float(np.max([b[key] for b in res["batches"]])))
+    count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
+    calls, fallbacks = int(sum(h.calls for h in make.hlps.values())), int(sum(h.fallbacks for h in make.hlps.values()))
+    return dict(workspace=dict(options, seed=a.tree_seed, lookahead_m=a.ws_lookahead, step=STEP, edge_step=EDGE_STEP, rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE,
+                               goal_tol=GOAL_TOL, hlp_calls=calls, goal_configuration_fallbacks=fallbacks),
+                straight=count(straight), workspace_outcomes=count(res), workspace_summary=res["summary"],
+                hard_scenarios={w["name"]: w["outcome"] for w in res["worlds"][100:]},
+                ms_per_batch={key: per_batch(key) for key in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0],
+                changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=128)
@@ -130,7 +153,11 @@ def main():
     ap.add_argument("--steps", type=float, nargs="+", default=[0.01, 0.05])
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kernel-stats", action="store_true")
-    ap.add_argument("--hlp", choices=["straight", "roadmap-field", "tree"], default="straight")
+    ap.add_argument("--hlp", choices=["straight", "roadmap-field", "tree", "workspace"], default="straight")
+    ap.add_argument("--ws-iterations", type=int, default=1000)
+    ap.add_argument("--ws-nodes", type=int, default=1024)
+    ap.add_argument("--ws-lookahead", type=float, default=0.1)
+    ap.add_argument("--ws-buffer", type=float, default=0.0)
     ap.add_argument("--tree-seed", type=int, default=0)
     ap.add_argument("--tree-iterations", type=int, default=2000)
     ap.add_argument("--tree-nodes", type=int, default=2048)
@@ -168,11 +195,13 @@ def main():
     if a.hlp == "tree":
         variant = a.tree_shortcut or a.tree_mode != "new"
         out["hlp_outcomes_tree_seed" if variant else "hlp_outcomes_tree"] = tree_trials(robot, ws, res, a)
-        if os.path.exists(saved_json):
-            saved = json.load(open(saved_json))
-            for key in ("hlp_outcomes", "hlp_outcomes_tree", "hlp_outcomes_tree_seed"):
-                if key not in out and saved.get(key) is not None:
-                    out[key] = saved[key]
+    if a.hlp == "workspace":
+        out["hlp_outcomes_workspace"] = workspace_trials(robot, ws, res, a)
+    if a.hlp in ("tree", "workspace") and os.path.exists(saved_json):
+        saved = json.load(open(saved_json))
+        for key in ("hlp_outcomes", "hlp_outcomes_tree", "hlp_outcomes_tree_seed", "hlp_outcomes_workspace"):
+            if key not in out and saved.get(key) is not None:
+                out[key] = saved[key]
     k_range, D = res["k_range"], res["duration"]
     O = max(w["obstacles"].shape[0] for w in res["worlds"])
     obs = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in res["worlds"]])

@@ -1,0 +1,130 @@
+// Build check of the workspace tree's host twin (armour_amd/csrc/ws_tree.hip) under the host sanitizers: a program of its own that calls
+// armour_ws_tree_plan_host on a wall with a window (the straight segment collides, so the tree has to go through the window or around), with
+// and without an initial chain, at the node cap and with every optional output absent, checks what every run must satisfy -- every parent
+// chain reaches the root within count steps, cost_k = cost_parent + |x_k - x_parent| bit for bit, the path runs from the start to a node
+// whose distance to the goal is goal_dist, the same seed gives the same bytes -- and the refusals, and prints what it found.
+//   make -C armour_amd/csrc wshost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
+// It supplies the symbols ws_tree.hip takes from api.hip, so that nothing else of the library is linked.
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../include/armour_hip.h"
+
+static char g_error[512];
+void armour_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+extern "C" int armour_device_available(void) { return 0; }
+
+static void box(std::vector<double>* out, double cx, double cy, double cz, double hx, double hy, double hz) {
+    const double Z[12] = {cx, cy, cz, hx, 0, 0, 0, hy, 0, 0, 0, hz};
+    out->insert(out->end(), Z, Z + 12);
+}
+
+struct Out {
+    std::vector<int32_t> status, iterations, points, rewires, kept, count, parent;
+    std::vector<double> path_cost, goal_dist, path, nodes, cost, margin;
+};
+
+int main() {
+    const int W = 3, O = 4, cap = 512, iters = 300, max_init = 4;
+    const double lb[3] = {-0.1, -0.7, -0.1}, ub[3] = {1.1, 0.7, 1.1}, start[3] = {0.1, -0.3, 0.2}, goal[3] = {0.9, 0.3, 0.8};
+    std::vector<double> obstacles, starts, goals;
+    for (int w = 0; w < W; w++) {
+        box(&obstacles, 0.5, -0.35, 0.5, 0.02, 0.25, 0.5);
+        box(&obstacles, 0.5, 0.35, 0.5, 0.02, 0.25, 0.5);
+        box(&obstacles, 0.5, 0.0, 0.2, 0.02, 0.1, 0.2);
+        box(&obstacles, 0.5, 0.0, 0.8, 0.02, 0.1, 0.2);
+        starts.insert(starts.end(), start, start + 3);
+        goals.insert(goals.end(), goal, goal + 3);
+    }
+    // world 1's chain: its third edge crosses the wall beside the window; world 2's goes through the window to the goal
+    const double chains[W][max_init][3] = {{}, {{0.2, -0.2, 0.3}, {0.4, 0.0, 0.5}, {0.6, 0.3, 0.5}, {0.8, 0.3, 0.7}}, {{0.4, 0.0, 0.5}, {0.6, 0.0, 0.5}, {0.9, 0.3, 0.8}}};
+    const int32_t chain_count[W] = {0, 4, 3};
+    const uint64_t seeds[W] = {1, 2, 3};
+    auto run = [&](Out* o, int32_t nodes_cap, int32_t room, bool with_chain, double radius) {
+        o->status.assign(W, -1); o->iterations.assign(W, -1); o->points.assign(W, -1); o->rewires.assign(W, -1); o->kept.assign(W, -1); o->count.assign(W, -1);
+        o->parent.assign((size_t)W * nodes_cap, -7); o->path_cost.assign(W, -1.0); o->goal_dist.assign(W, -1.0); o->path.assign((size_t)W * (room ? room : 1) * 3, 0.0);
+        o->nodes.assign((size_t)W * nodes_cap * 3, 0.0); o->cost.assign((size_t)W * nodes_cap, 0.0); o->margin.assign(W, 0.0);
+        return armour_ws_tree_plan_host(lb, ub, W, O, obstacles.data(), starts.data(), goals.data(), seeds, max_init, with_chain ? &chains[0][0][0] : nullptr,
+                                        with_chain ? chain_count : nullptr, 0.1, 0.01, radius, 0.1, 0.01, 0.01, iters, nodes_cap, room, o->status.data(),
+                                        o->iterations.data(), o->points.data(), o->rewires.data(), o->kept.data(), o->path_cost.data(), o->goal_dist.data(),
+                                        o->path.data(), o->count.data(), o->nodes.data(), o->parent.data(), o->cost.data(), o->margin.data());
+    };
+    auto check_trees = [&](const Out& a, int32_t nodes_cap, int32_t room) {
+        for (int w = 0; w < W; w++) {
+            const int c = a.count[w], P = a.points[w];
+            const double* x = &a.nodes[(size_t)w * nodes_cap * 3];
+            const int32_t* par = &a.parent[(size_t)w * nodes_cap];
+            const double* cost = &a.cost[(size_t)w * nodes_cap];
+            if (c < 1 || c > nodes_cap || par[0] != -1 || cost[0] != 0.0 || std::memcmp(x, start, sizeof(start))) { printf("FAILED: world %d: the root\n", w); return false; }
+            for (int k = 1; k < c; k++) {
+                int steps = 0;
+                for (int v = k; v != 0; v = par[v])
+                    if (par[v] < 0 || par[v] >= c || ++steps >= c) { printf("FAILED: world %d: node %d does not reach the root\n", w, k); return false; }
+                const double* p = x + (size_t)par[k] * 3;
+                const double D[3] = {x[3 * k] - p[0], x[3 * k + 1] - p[1], x[3 * k + 2] - p[2]};
+                if (cost[k] != cost[par[k]] + std::sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2])) { printf("FAILED: world %d: the cost of node %d\n", w, k); return false; }
+            }
+            const double* path = &a.path[(size_t)w * room * 3];
+            if (P < 1 || P > c || std::memcmp(path, start, sizeof(start))) { printf("FAILED: world %d: a path of %d points\n", w, P); return false; }
+            const double* e = path + (size_t)(P - 1) * 3;
+            const double D[3] = {goal[0] - e[0], goal[1] - e[1], goal[2] - e[2]};
+            if (a.goal_dist[w] != std::sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]) || (a.status[w] == ARMOUR_WS_REACHED) != (a.goal_dist[w] <= 0.01)) {
+                printf("FAILED: world %d: status %d, goal_dist %g\n", w, a.status[w], a.goal_dist[w]);
+                return false;
+            }
+            if (!(a.margin[w] > 0.0)) { printf("FAILED: world %d: margin %g\n", w, a.margin[w]); return false; }
+        }
+        return true;
+    };
+    Out a, b, c;
+    if (run(&a, cap, cap, true, 0.2) != ARMOUR_OK || run(&b, cap, cap, true, 0.2) != ARMOUR_OK) { printf("FAILED: %s\n", g_error); return 1; }
+    if (a.status != b.status || a.iterations != b.iterations || a.points != b.points || a.rewires != b.rewires || a.count != b.count || a.parent != b.parent ||
+        std::memcmp(a.path.data(), b.path.data(), a.path.size() * sizeof(double)) || std::memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(double)) ||
+        std::memcmp(a.cost.data(), b.cost.data(), a.cost.size() * sizeof(double))) {
+        printf("FAILED: the same call twice gave different results\n");
+        return 1;
+    }
+    if (!check_trees(a, cap, cap)) return 1;
+    if (a.kept[0] != 0 || a.kept[1] != 2 || a.kept[2] != 3 || a.status[2] != ARMOUR_WS_REACHED || a.rewires[0] <= 0) {
+        printf("FAILED: chains kept %d %d %d, status %d, rewires %d\n", a.kept[0], a.kept[1], a.kept[2], a.status[2], a.rewires[0]);
+        return 1;
+    }
+    // plain RRT, no chain; a tree at its cap of 8 nodes (the chain of world 1 stops there or before)
+    if (run(&c, cap, cap, false, 0.0) != ARMOUR_OK || !check_trees(c, cap, cap) || c.rewires[0] || c.rewires[1] || c.rewires[2]) { printf("FAILED: plain RRT: %s\n", g_error); return 1; }
+    if (run(&c, 8, 8, true, 0.2) != ARMOUR_OK || !check_trees(c, 8, 8) || c.count[0] != 8 || c.iterations[0] >= iters) { printf("FAILED: the full tree: %s\n", g_error); return 1; }
+    // too little room for a path: ECAPACITY with the points complete; the optional outputs may all be absent
+    if (run(&b, cap, 2, true, 0.2) != ARMOUR_ECAPACITY || b.points != a.points) { printf("FAILED: a path longer than max_points was not refused\n"); return 1; }
+    std::vector<int32_t> st(W), it(W), pt(W), rw(W), kp(W);
+    std::vector<double> pc(W), gd(W);
+    auto bare = [&](double step, double edge_step, double radius, double rate, double buffer, int32_t n_iter, int32_t nodes_cap) {
+        return armour_ws_tree_plan_host(lb, ub, W, O, obstacles.data(), starts.data(), goals.data(), seeds, max_init, &chains[0][0][0], chain_count, step, edge_step, radius,
+                                        rate, buffer, 0.01, n_iter, nodes_cap, 0, st.data(), it.data(), pt.data(), rw.data(), kp.data(), pc.data(), gd.data(), nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr);
+    };
+    if (bare(0.1, 0.01, 0.2, 0.1, 0.01, iters, cap) != ARMOUR_OK || st != a.status || it != a.iterations || pt != a.points || rw != a.rewires ||
+        std::memcmp(pc.data(), a.path_cost.data(), W * sizeof(double))) {
+        printf("FAILED: the call without optional outputs: %s\n", g_error);
+        return 1;
+    }
+    if (bare(0.0, 0.01, 0.2, 0.1, 0.0, iters, cap) != ARMOUR_EINVAL || bare(0.1, -1.0, 0.2, 0.1, 0.0, iters, cap) != ARMOUR_EINVAL ||
+        bare(0.1, 0.01, -0.2, 0.1, 0.0, iters, cap) != ARMOUR_EINVAL || bare(0.1, 0.01, 0.2, 1.5, 0.0, iters, cap) != ARMOUR_EINVAL ||
+        bare(0.1, 0.01, 0.2, 0.1, -0.1, iters, cap) != ARMOUR_EINVAL || bare(0.1, 0.01, 0.2, 0.1, 0.0, -1, cap) != ARMOUR_EINVAL ||
+        bare(0.1, 0.01, 0.2, 0.1, 0.0, iters, 0) != ARMOUR_EINVAL || bare(0.1, 0.01, 0.2, 0.1, 0.0, iters, ARMOUR_WS_MAX_NODES + 1) != ARMOUR_EINVAL ||
+        bare(0.1, 0.00001, 0.2, 0.1, 0.0, iters, cap) != ARMOUR_EINVAL) {
+        printf("FAILED: a bad argument passed\n");
+        return 1;
+    }
+    printf("ws tree host check ok: %d / %d / %d nodes, %d / %d / %d rewires, path costs %.4f %.4f %.4f, chains kept %d %d %d, margins %.3g %.3g %.3g\n", a.count[0],
+           a.count[1], a.count[2], a.rewires[0], a.rewires[1], a.rewires[2], a.path_cost[0], a.path_cost[1], a.path_cost[2], a.kept[0], a.kept[1], a.kept[2], a.margin[0],
+           a.margin[1], a.margin[2]);
+    return 0;
+}
