@@ -296,6 +296,7 @@ static int begin_problem_set(ArmourPlanner* h, int B, int O, const double* q0, c
             bz[((size_t)b * 3 + 2) * h->n + i] = qdd0[b * h->n + i] * D * D;
         }
     HIPCHK(hipMemcpy(h->d_bez, bz.data(), bz.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->h_bez = std::move(bz);
     return ARMOUR_OK;
 }
 
@@ -553,14 +554,14 @@ extern "C" int armour_eval_g_jac_device(ArmourPlanner* h, const double* d_k, dou
     NEED_READY(h);
     if (!d_k) { armour_set_error("d_k is null"); return ARMOUR_EINVAL; }
     const P2Tables tb = armour_make_tables(h);
-    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream);
+    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream);
 }
 
 static int enqueue_steps(ArmourPlanner* h, const double* d_k, int steps, double* d_g, double* d_jac, hipStream_t st) {
     const P2Tables tb = armour_make_tables(h);
     const size_t stride = (size_t)h->B * h->n;
     for (int s = 0; s < steps; s++) {
-        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), d_k + (size_t)s * stride, d_g, d_jac, st);
+        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k + (size_t)s * stride, d_g, d_jac, st);
         if (rc != ARMOUR_OK) return rc;
     }
     return ARMOUR_OK;
@@ -636,7 +637,7 @@ extern "C" int armour_eval_g_jac_device_multi(ArmourPlanner* h, const double* d_
     if (points == 0) return ARMOUR_OK;
     const P2Tables tb = armour_make_tables(h);
     const long long bn = (long long)h->B * h->n, bm = (long long)h->B * h->m;
-    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream,
+    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream,
                             points, bn, bm, bm * h->n);
 }
 
@@ -663,14 +664,14 @@ extern "C" int armour_eval_g_jac(ArmourPlanner* h, const double* k, double* g, d
     const int pinned_mode = h->tune(ARMOUR_OPT_PINNED_MODE);
     const bool all_pinned = in_pinned(k, bn * sizeof(double)) && in_pinned(g, bm * sizeof(double)) && in_pinned(jac, bm * h->n * sizeof(double));
     if (all_pinned && pinned_mode == 1) {
-        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), k, g, jac, h->stream);
+        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), k, g, jac, h->stream);
         if (rc != ARMOUR_OK) return rc;
         return armour_spin_on_stream(h->stream);
     }
     const double* k_dev = h->d_k;
     if (all_pinned && pinned_mode == 2) k_dev = k;
     else HIPCHK(hipMemcpyAsync(h->d_k, k, bn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), k_dev, g ? h->d_g : nullptr, jac ? h->d_jac : nullptr, h->stream);
+    int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), k_dev, g ? h->d_g : nullptr, jac ? h->d_jac : nullptr, h->stream);
     if (rc != ARMOUR_OK) return rc;
     if (g && jac && jac == g + bm) {   // the caller's g and jac are one block (as the device copies are): one transfer instead of two
         HIPCHK(hipMemcpyAsync(g, h->d_g, bm * (1 + (size_t)h->n) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -829,7 +830,7 @@ static int eval_violations_device_impl(ArmourPlanner* h, const double* d_k, Armo
     if (allow_cull && h->tune(ARMOUR_OPT_CULL_ROWS)) return armour_eval_violations_culled(h, d_k, d_out, st);   // the relevant rows only: relevance.hip
     const P2Tables tb = armour_make_tables(h);
     // g only (the Jacobian tile, 7/8 of the output bytes, is neither computed nor written), into the handle's own g buffer
-    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), d_k, h->d_g, nullptr, st);
+    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, h->d_g, nullptr, st);
     if (rc != ARMOUR_OK) return rc;
     ViolArgs a;
     a.rule = armour_row_rule(h);

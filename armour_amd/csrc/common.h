@@ -163,6 +163,7 @@ struct ArmourPlanner {
     DevBuf<double> d_tr_stage;   // the same on the device, for the kernel that fills the bounds (armour_upload_bounds)
     std::vector<double> h_link_gens;                  // [B][T][J][18]
     std::vector<unsigned long long> h_plane_skip;     // [B] host copy of d_plane_skip
+    std::vector<double> h_bez;                        // [B][3][n] host copy of d_bez (one-problem launches pass it in the kernel arguments)
     std::vector<double> h_prune_margin;               // [B] how close the last build's simplify() verdicts came to flipping (armour_get_prune_margin)
     // device tables (sized for allocB x allocO)
     int allocB = 0, allocO = 0;
@@ -216,7 +217,7 @@ bool armour_trace_p1();      // ARMOUR_P1_TRACE
 bool armour_trace_solve();   // ARMOUR_SOLVE_TIMING
 
 // p2_eval.hip
-int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* d_k, double* d_g, double* d_jac, hipStream_t stream,
+int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, const double* d_k, double* d_g, double* d_jac, hipStream_t stream,
                      int steps = 1, long long k_stride = 0, long long g_stride = 0, long long j_stride = 0, bool skip_collision_blocks = false);
 // relevance.hip
 int armour_relevance_build(ArmourPlanner* h, bool for_solver);   // (relevance.hip; for_solver: also the lists armour_solve's culled device form walks)

@@ -98,7 +98,7 @@ bool armour_p2_ex_layout_ok(unsigned long long skip) {
     return true;
 }
 
-int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, int steps, long long k_stride,
+int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, int steps, long long k_stride,
                    long long g_stride, long long j_stride, P2Launch* lp_out, size_t* smem_out, bool* dfc_out, bool* six_out, bool* exact_out) {
     P2Launch lp;
     lp.role0 = 0;
@@ -109,6 +109,10 @@ int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsig
     lp.strideT = max_torque > 0 ? max_torque : 1;
     lp.skip_by_value = (tb.B == 1 && h_skip) ? 1 : 0;
     lp.skip0 = lp.skip_by_value ? h_skip[0] : 0ull;
+    // h_bez: the host's copy of tb.bez ([B][3][n]), or null: the limit block then reads tb.bez
+    lp.bez_by_value = (tb.B == 1 && h_bez) ? 1 : 0;
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < ARMOUR_MAX_FACTORS; i++) lp.bez0[c * ARMOUR_MAX_FACTORS + i] = (lp.bez_by_value && i < tb.n) ? h_bez[c * tb.n + i] : 0.0;
     lp.steps = steps; lp.k_stride = k_stride; lp.g_stride = g_stride; lp.j_stride = j_stride;
     lp.magic_O = div_magic(tb.O > 0 ? tb.O : 1); lp.magic_pp3 = div_magic(3 * lp.strideL);
     if (tb.Q >= (1 << 20)) { armour_set_error("more than 2^20 collision rows per problem"); return ARMOUR_ECAPACITY; }
@@ -117,7 +121,7 @@ int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsig
     if (lp.strideT > 32 * P2_TQ_ROUNDS) { armour_set_error("torque PZ with %d monomials exceeds the P2 kernel's %d", lp.strideT, 32 * P2_TQ_ROUNDS); return ARMOUR_ECAPACITY; }
     const size_t col = ((size_t)lp.max_pairs * P2_SL + (size_t)lp.pair_chunk * lp.strideL * P2_SL + 4 * 64 * 4 + 64 * ARMOUR_MAX_FACTORS) * sizeof(double) + 4 * 64 * sizeof(int);
     const size_t tq = (size_t)P2_TQ_ROWS * lp.strideT * P2_TQW * sizeof(double);
-    const size_t lim = (size_t)2 * ARMOUR_MAX_FACTORS * 8 * sizeof(double);
+    const size_t lim = (size_t)(2 * ARMOUR_MAX_FACTORS * 8 + 2 * ARMOUR_MAX_FACTORS + 3 * 4 * ARMOUR_MAX_FACTORS) * sizeof(double);  // limit_block: pv, kb, sg, sd, cs
     const size_t smem = 2 * sizeof(KPow) + std::max(std::max(col, tq), lim);
     if (smem > 64 * 1024) { armour_set_error("P2 kernel needs %zu B of LDS (link/torque monomial counts too large)", smem); return ARMOUR_ECAPACITY; }
     const bool dfc = tb.obs_center != nullptr && tb.ll_shared;
@@ -131,13 +135,13 @@ int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsig
     return ARMOUR_OK;
 }
 
-int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* d_k, double* d_g, double* d_jac,
+int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, const double* d_k, double* d_g, double* d_jac,
                      hipStream_t stream, int steps, long long k_stride, long long g_stride, long long j_stride, bool skip_collision_blocks) {
     if (!d_g && !d_jac) return ARMOUR_OK;
     P2Launch lp;
     size_t smem = 0;
     bool dfc, six, exact;
-    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, steps, k_stride, g_stride, j_stride, &lp, &smem, &dfc, &six, &exact);
+    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, steps, k_stride, g_stride, j_stride, &lp, &smem, &dfc, &six, &exact);
     if (rc != ARMOUR_OK) return rc;
     if (skip_collision_blocks) lp.role0 = lp.nbc;   // the torque blocks and the limit block only
     dim3 grid(lp.nbc + lp.nbt + 1 - lp.role0, tb.B), block(P2_BLOCK);

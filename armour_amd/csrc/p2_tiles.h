@@ -149,6 +149,10 @@ struct P2Launch {
     int steps;
     long long k_stride, g_stride, j_stride;
     unsigned long long magic_O, magic_pp3;  // div_magic(O), div_magic(3 * strideL)
+    // 1: the Bezier scalars of the (single) problem are in `bez0`, entry c of joint i at [c * ARMOUR_MAX_FACTORS + i] (saves the limit block a
+    // dependent load at B = 1, as skip0 does the collision blocks)
+    int bez_by_value;
+    double bez0[3 * ARMOUR_MAX_FACTORS];
 };
 
 // registers of one slicing pass: the (monomial, axis) tasks of this thread and, for threads < pairs*24, the inputs of
@@ -276,14 +280,18 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     const int q_lt = fast_div(q, lp.magic_O), q_o = q - q_lt * O;  // q = (l*T + t)*O + o
     // compact link x link normals: one 384-B record per (link, time step), entry 3*(p - 21) + c
     const double* pll = tb.planes_ll + (size_t)b * armour_planes_ll_per_problem(JT) + (size_t)q_lt * ARMOUR_LL_RECORD;
-    unsigned long long live = ~(lp.skip_by_value ? lp.skip0 : tb.plane_skip[b]) & ((1ull << ARMOUR_NPLANES) - 1ull);
+    // (the by-value mask is pinned to scalar registers: left alone, the compiler merges the two sources of the mask into ONE vector load from a
+    //  selected address -- the argument block's or the table's -- a memory round trip at B = 1 whose wait also covers k_first)
+    unsigned long long skip0 = lp.skip0;
+    asm volatile("" : "+s"(skip0));
+    unsigned long long live = ~(lp.skip_by_value ? skip0 : tb.plane_skip[b]) & ((1ull << ARMOUR_NPLANES) - 1ull);
     const bool plane0_live = (live & 1ull) != 0;
     const int na = __popcll(live), base = na >> 2, rem = na & 3;
     const int my_cnt = base + (wv < rem ? 1 : 0), my_start = wv * base + min(wv, rem);
     for (int s = 0; s < my_start; s++) live &= live - 1ull;
     double a0[PPW], a1[PPW], a2[PPW], dd[PPW], dl[PPW];
-    const int lt_first = q_begin / O;
-    const int npairs = (q_end - 1) / O - lt_first + 1;
+    const int lt_first = fast_div(q_begin, lp.magic_O);   // (Q < 2^20: armour_p2_plan)
+    const int npairs = fast_div(q_end - 1, lp.magic_O) - lt_first + 1;
     const bool single_pass = npairs <= lp.pair_chunk;
     PassRegs pr;
     if (EX) load_pass_uncond(tb, lp, b, lt_first, npairs, pr);
@@ -609,76 +617,119 @@ __device__ __forceinline__ void limit_block(const P2Tables& tb, const P2Launch& 
     // RT/Trajectory.cu:256-540.  One thread per (joint, position|velocity, piece): pieces 0-3 evaluate the curve
     // at t = 0, the two stationary points and t = 1, pieces 4-5 the d/dk of the two interior extrema; a second
     // step per (joint, position|velocity) selects min / max as bez::select_extrema does, written out.
-    double* pv = lds;  // [2n][8]
-    const int jv = tid >> 3, piece = tid & 7;
+    // Each of the four path families -- position / velocity values, position / velocity d/dk -- has a wave of its own (wave = 2 * is_dk +
+    // is_velocity: a wave runs ONE family's square roots and divisions, not all four one after the other); value waves hold
+    // lane = joint * 4 + piece, d/dk waves lane = joint * 2 + (sign < 0).  The point's k comes from the register the caller loaded
+    // (k_first; later points one point ahead, as the other tiles fetch them); k_range and, where the launch has one problem, the Bezier
+    // scalars come out of the kernel arguments with scalar loads -- the first lane of each wave spreads one array through LDS, since
+    // indexing an argument array by lane makes the compiler fetch it with a vector load from the argument block's address, one more
+    // memory round trip (and it turns a select chain over the entries back into that load).  The 4n rows are contiguous in g and in jac: their values and the one
+    // non-zero entry of each Jacobian row are staged in LDS and written in one pass, one thread per double.
+    static_assert(P2_BLOCK >= 4 * ARMOUR_MAX_FACTORS * 8 && ARMOUR_MAX_FACTORS <= 8, "the store pass holds one (row, column) per thread: 4n rows x 8 columns");
+    double* pv = lds;                                // [2n][8]
+    double* kb = pv + 2 * ARMOUR_MAX_FACTORS * 8;    // [2][ARMOUR_MAX_FACTORS] the point's k, double-buffered over the points
+    double* sg = kb + 2 * ARMOUR_MAX_FACTORS;        // [4n] the rows' values: min, max of the position, min, max of the velocity (n each)
+    double* sd = sg + 4 * ARMOUR_MAX_FACTORS;        // [4n] the rows' Jacobian entry in their own joint's column (every other entry is 0)
+    double* cs = sd + 4 * ARMOUR_MAX_FACTORS;        // [4][ARMOUR_MAX_FACTORS] k_range | the problem's Bezier scalars (lp.bez0 or tb.bez)
     const double* bz = tb.bez + (size_t)b * 3 * n;
-    if (tb.mode == ARMOUR_MODE_ARMTD) {
-        // ARMTD comparison mode: constant-acceleration curve, CMP/Trajectory.cu:83-383 (cacc.h); bez = q0, qd0, k_range.
-        // One thread per joint; rows q_min, q_max, qd_min, qd_max (n each), Jacobian diagonal = d/d(k_range*k) as the
-        // reference stores it, every other entry of the rows 0.
-        for (int s = 0; s < nsteps; s++) {
-            const double* k = k0 + (size_t)s * lp.k_stride;
-            double* g = WANT_G ? g0 + (size_t)s * lp.g_stride : nullptr;
-            double* jac = WANT_J ? jac0 + (size_t)s * lp.j_stride : nullptr;
-            if (tid < n) {
-                const cacc::Extrema e = cacc::joint_extrema(bz[tid], bz[n + tid], bz[2 * n + tid] * k[tid]);
-                const cacc::Cand c4[4] = {e.q_min, e.q_max, e.qd_min, e.qd_max};
-                const size_t off = (size_t)tb.row0 + Q;
-                for (int r = 0; r < 4; r++) {
-                    const size_t row = off + (size_t)r * n + tid;
-                    if (WANT_G) g[row] = c4[r].v;
-                    if (WANT_J) for (int c = 0; c < n; c++) jac[row * n + c] = (c == tid) ? c4[r].d : 0.0;
+    const bool armtd = tb.mode == ARMOUR_MODE_ARMTD;
+    const size_t off = (size_t)tb.row0 + Q;
+    const bool by_value = lp.bez_by_value != 0;
+    // (before k_first is touched: the argument loads below then run while the fresh k, an HBM miss, is in flight; one wave per array, so that
+    //  each wave waits for one group of scalar loads and the four groups are in flight together)
+    if (lane == 0) {
+        if (wv == 0) {
+#pragma unroll
+            for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) cs[j] = tb.k_range[j];
+        } else if (by_value) {
+#pragma unroll
+            for (int c = 1; c < 4; c++) {
+                if (wv == c) {
+#pragma unroll
+                    for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) cs[c * ARMOUR_MAX_FACTORS + j] = lp.bez0[(c - 1) * ARMOUR_MAX_FACTORS + j];
                 }
             }
         }
-        return;
     }
+    if (!by_value && tid < 3 * n) {   // several problems: this problem's scalars from tb.bez, once for all points
+        const int c = tid >= 2 * n ? 2 : tid >= n ? 1 : 0;
+        cs[(1 + c) * ARMOUR_MAX_FACTORS + tid - c * n] = bz[tid];
+    }
+    if (tid < n) kb[tid] = k_first;
+    __syncthreads();
     for (int s = 0; s < nsteps; s++) {
-        const double* k = k0 + (size_t)s * lp.k_stride;
+        const double k_cur = k_next;
+        if (tid < n && s + 1 < nsteps) k_next = k0[(size_t)(s + 1) * lp.k_stride + tid];
         double* g = WANT_G ? g0 + (size_t)s * lp.g_stride : nullptr;
         double* jac = WANT_J ? jac0 + (size_t)s * lp.j_stride : nullptr;
-        if (jv < 2 * n && piece < 6) {
-            const int i = jv % n;
-            const bool vel = jv >= n;
-            const double q0 = bz[i], a = bz[n + i], bb = bz[2 * n + i], ka = tb.k_range[i] * k[i];
-            double e2, e3, v;
-            if (!vel) bez::q_stationary(a, bb, ka, &e2, &e3); else bez::qd_stationary(a, bb, ka, &e2, &e3);
-            if (piece < 4) {
-                const double tt = piece == 0 ? 0.0 : piece == 1 ? e2 : piece == 2 ? e3 : 1.0;
-                v = vel ? bez::qd_des(q0, a, bb, ka, tt) : bez::q_des(q0, a, bb, ka, tt);
-            } else {
-                const int sg = piece == 4 ? +1 : -1;
-                v = vel ? bez::qd_extremum_dk(q0, a, bb, ka, sg) : bez::q_extremum_dk(q0, a, bb, ka, sg);
+        if (armtd) {
+            // ARMTD comparison mode: constant-acceleration curve, CMP/Trajectory.cu:83-383 (cacc.h); bez = q0, qd0, k_range.
+            // One thread per joint; rows q_min, q_max, qd_min, qd_max (n each), Jacobian diagonal = d/d(k_range*k) as the
+            // reference stores it, every other entry of the rows 0.
+            if (tid < n) {
+                const double c0 = cs[ARMOUR_MAX_FACTORS + tid], c1 = cs[2 * ARMOUR_MAX_FACTORS + tid], c2 = cs[3 * ARMOUR_MAX_FACTORS + tid];
+                const cacc::Extrema e = cacc::joint_extrema(c0, c1, c2 * k_cur);
+                const cacc::Cand c4[4] = {e.q_min, e.q_max, e.qd_min, e.qd_max};
+#pragma unroll
+                for (int r = 0; r < 4; r++) { sg[r * n + tid] = c4[r].v; sd[r * n + tid] = c4[r].d; }
             }
-            pv[jv * 8 + piece] = v;
-            if (piece == 1) pv[jv * 8 + 6] = e2;
-            if (piece == 2) pv[jv * 8 + 7] = e3;
-        }
-        __syncthreads();
-        if (tid < 2 * n) {
-            const int i = tid % n;
-            const bool vel = tid >= n;
-            const double* v = pv + tid * 8;
-            const double v1 = v[0], v2 = v[1], v3 = v[2], v4 = v[3], e2 = v[6], e3 = v[7];
-            double mn, mx;
-            int mnId, mxId;
-            if (v1 < v4) { mn = v1; mnId = 1; mx = v4; mxId = 4; } else { mn = v4; mnId = 4; mx = v1; mxId = 1; }
-            if (0 <= e2 && e2 <= 1) { if (v2 < mn) { mn = v2; mnId = 2; } if (mx < v2) { mx = v2; mxId = 2; } }
-            if (0 <= e3 && e3 <= 1) { if (v3 < mn) { mn = v3; mnId = 3; } if (mx < v3) { mx = v3; mxId = 3; } }
-            const double sc = vel ? tb.k_range[i] / tb.duration : tb.k_range[i];
-            const double dmn = (mnId == 1 ? 0.0 : mnId == 2 ? v[4] : mnId == 3 ? v[5] : 1.0) * sc;
-            const double dmx = (mxId == 1 ? 0.0 : mxId == 2 ? v[4] : mxId == 3 ? v[5] : 1.0) * sc;
-            const size_t off = (size_t)tb.row0 + Q;
-            const size_t r_mn = off + (vel ? 2 * n : 0) + i, r_mx = r_mn + n;
-            if (WANT_G) { g[r_mn] = vel ? mn / tb.duration : mn; g[r_mx] = vel ? mx / tb.duration : mx; }
-            if (WANT_J) {
-                for (int c = 0; c < n; c++) {
-                    jac[r_mn * n + c] = (c == i) ? dmn : 0.0;
-                    jac[r_mx * n + c] = (c == i) ? dmx : 0.0;
+        } else {
+            const bool is_dk = wv >= 2, vel = (wv & 1) != 0;   // (uniform: the branches below are the scalar unit's)
+            const int i = is_dk ? lane >> 1 : lane >> 2;
+            if (i < n) {
+                const int jv = vel ? n + i : i;
+                const double q0 = cs[ARMOUR_MAX_FACTORS + i], a = cs[2 * ARMOUR_MAX_FACTORS + i], bb = cs[3 * ARMOUR_MAX_FACTORS + i];
+                const double ka = cs[i] * kb[(s & 1) * ARMOUR_MAX_FACTORS + i];
+                double v;
+                if (!is_dk) {
+                    const int piece = lane & 3;
+                    double e2, e3;
+                    if (!vel) bez::q_stationary(a, bb, ka, &e2, &e3); else bez::qd_stationary(a, bb, ka, &e2, &e3);
+                    const double tt = piece == 0 ? 0.0 : piece == 1 ? e2 : piece == 2 ? e3 : 1.0;
+                    if (!vel) v = bez::q_des(q0, a, bb, ka, tt); else v = bez::qd_des(q0, a, bb, ka, tt);
+                    pv[jv * 8 + piece] = v;
+                    if (piece == 1) pv[jv * 8 + 6] = e2;
+                    if (piece == 2) pv[jv * 8 + 7] = e3;
+                } else {
+                    const int sgn = (lane & 1) ? -1 : +1;
+                    if (!vel) v = bez::q_extremum_dk(q0, a, bb, ka, sgn); else v = bez::qd_extremum_dk(q0, a, bb, ka, sgn);
+                    pv[jv * 8 + 4 + (lane & 1)] = v;
                 }
             }
+            __syncthreads();
+            if (tid < n && s + 1 < nsteps) kb[((s + 1) & 1) * ARMOUR_MAX_FACTORS + tid] = k_next;   // (read after the next barrier; its last readers are behind the one above)
+            if (tid < 2 * n) {
+                const bool velr = tid >= n;
+                const int ir = velr ? tid - n : tid;
+                const double* v = pv + tid * 8;
+                const double v1 = v[0], v2 = v[1], v3 = v[2], v4 = v[3], e2 = v[6], e3 = v[7];
+                double mn, mx;
+                int mnId, mxId;
+                if (v1 < v4) { mn = v1; mnId = 1; mx = v4; mxId = 4; } else { mn = v4; mnId = 4; mx = v1; mxId = 1; }
+                if (0 <= e2 && e2 <= 1) { if (v2 < mn) { mn = v2; mnId = 2; } if (mx < v2) { mx = v2; mxId = 2; } }
+                if (0 <= e3 && e3 <= 1) { if (v3 < mn) { mn = v3; mnId = 3; } if (mx < v3) { mx = v3; mxId = 3; } }
+                const double kr = cs[ir];
+                const double sc = velr ? kr / tb.duration : kr;
+                const double dmn = (mnId == 1 ? 0.0 : mnId == 2 ? v[4] : mnId == 3 ? v[5] : 1.0) * sc;
+                const double dmx = (mxId == 1 ? 0.0 : mxId == 2 ? v[4] : mxId == 3 ? v[5] : 1.0) * sc;
+                const int r_mn = (velr ? 2 * n : 0) + ir, r_mx = r_mn + n;
+                sg[r_mn] = velr ? mn / tb.duration : mn; sg[r_mx] = velr ? mx / tb.duration : mx;
+                sd[r_mn] = dmn; sd[r_mx] = dmx;
+            }
         }
-        __syncthreads();  // `pv` is rewritten by the next point
+        __syncthreads();
+        // the 4n rows in one pass: thread (r, c) = (tid / 8, tid % 8) writes entry c of Jacobian row r -- consecutive live threads, consecutive doubles
+        if (WANT_G && tid < 4 * n) g[off + tid] = sg[tid];
+        if (WANT_J) {
+            const int r = tid >> 3, c = tid & 7;
+            if (r < 4 * n && c < n) {
+                int ir = r;
+                if (ir >= 2 * n) ir -= 2 * n;
+                if (ir >= n) ir -= n;
+                jac[(off + r) * n + c] = (c == ir) ? sd[r] : 0.0;
+            }
+        }
+        if (MULTI && armtd) __syncthreads();  // `sg` / `sd` are rewritten by the next point (the ARMOUR branch has a barrier of its own in between)
     }
 }
 

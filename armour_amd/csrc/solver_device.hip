@@ -1157,7 +1157,7 @@ int armour_solve_device_capacity(const P2Tables& tb, int max_link, int max_torqu
     P2Launch lp;
     size_t smem = 0;
     bool dfc, six, exact;
-    int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact);
+    int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, /*h_bez=*/nullptr, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact);
     if (rc != ARMOUR_OK) return rc;
     plan->lp = lp; plan->smem = smem; plan->six = six;
     plan->n_tiles = n_tiles_override > 0 ? n_tiles_override : lp.nbt + lp.nbc + 1;

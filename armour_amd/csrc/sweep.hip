@@ -49,7 +49,8 @@ struct SweepArgs {
 };
 
 // g of the limit row of joint i in block blk (0 .. 3: the n rows of min position, max position, min velocity, max velocity) of problem b at the joint's parameter kj:
-// bez::select_extrema on the four values p2_tiles.h's limit_block takes; ARMTD mode: cacc::joint_extrema
+// bez::select_extrema on the four values p2_tiles.h's limit_block takes (there one lane per value and one wave per path family, here one
+// thread for all four: the same bezier.h calls on the same arguments); ARMTD mode: cacc::joint_extrema
 __device__ inline double limit_row_g(const P2Tables& tb, int b, int i, int blk, double kj) {
     const int n = tb.n;
     const double* bz = tb.bez + (size_t)b * 3 * n;
