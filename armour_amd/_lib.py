@@ -195,6 +195,7 @@ EXPORTS = [
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
     "armour_ws_tree_plan", "armour_ws_tree_plan_host",
+    "armour_debug_block_steps", "armour_debug_block_split", "armour_debug_block_owner",
 ]
 
 _lib = None
@@ -350,6 +351,9 @@ def load():
         dp, dp, dp, ip, dp, ip, dp, dp]
     L.armour_ws_tree_plan.argtypes = ws           # (the last pointer: ms)
     L.armour_ws_tree_plan_host.argtypes = ws      # (the last pointer: margin [W])
+    L.armour_debug_block_steps.argtypes = [dp, ip, ip, ip, dp, ip, ip, ip, ip, ip]
+    L.armour_debug_block_split.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip]
+    L.armour_debug_block_owner.argtypes = [ip, C.c_int32, C.c_int32, ip, ip]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,
@@ -388,3 +392,17 @@ def check(rc):
     if rc < 0:
         raise ArmourError(rc, load().armour_last_error().decode())
     return rc
+
+
+def as_worlds(obstacles):
+    """obstacles [W,O,12] (or [O,12]: W = 1) -> (the contiguous float64 array [W,O,12], W, O), as every entry with worlds takes them."""
+    obs = np.asarray(obstacles, dtype=np.float64)
+    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+    return obs, obs.shape[0], obs.shape[1]
+
+
+class Result:
+    """What a wrapper returns: its keyword arguments as attributes (the wrappers' result classes say which)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)

@@ -6,6 +6,8 @@
 
 #include <cmath>
 #include <cstddef>
+#include <cstring>
+#include <vector>
 
 #include "../../include/armour_hip.h"
 
@@ -135,3 +137,35 @@ inline int armour_check_world_counts(const char* who, int32_t W, int32_t O, cons
     armour_set_error("%s: W = %d (0..65535), O = %d (0..%d)", who, W, O, ARMOUR_ROADMAP_MAX_OBSTACLES);
     return ARMOUR_EINVAL;
 }
+// the roadmap entries' capacity rule: points [W] is complete; a path longer than max_points was not written.  `wanted`: the rule applies
+// (the tree planners': the caller gave a path array; the shortener's: always)
+inline int armour_check_path_capacity(const char* who, int32_t W, const int32_t* points, int32_t max_points, bool wanted) {
+    for (int32_t w = 0; wanted && w < W; w++)
+        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
+    return ARMOUR_OK;
+}
+// a box [lb, ub] of n components: finite and ordered.  `what`: how the message names it ("sampling box", "box"); `noun`: a component ("joint", "axis")
+inline int armour_check_box(const char* who, const char* what, const char* noun, int n, const double* lb, const double* ub) {
+    for (int j = 0; j < n; j++)
+        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: %s [%g, %g] of %s %d", who, what, lb[j], ub[j], noun, j); return ARMOUR_EINVAL; }
+    return ARMOUR_OK;
+}
+
+// k result columns of W elements each, packed in one device buffer so that one copy brings all of them back: reserve, hand column i to the
+// kernel, fetch (the caller synchronises the stream), copy column i -- or `span` columns from i, for a result of [W][span] -- to the caller's array
+template <class T>
+struct DevColumns {
+    DevBuf<T> dev;
+    std::vector<T> host;
+    size_t W = 0;
+    int reserve(int k, size_t W_) { W = W_; host.resize((size_t)k * W); return dev.reserve(host.size()); }
+    T* column(int i) const { return dev.p + (size_t)i * W; }
+    int fetch(hipStream_t st) {
+        HIPCHK(hipMemcpyAsync(host.data(), dev, host.size() * sizeof(T), hipMemcpyDeviceToHost, st));
+        return ARMOUR_OK;
+    }
+    const T* fetched(int i) const { return host.data() + (size_t)i * W; }
+    void copy_out(int i, T* to, int span = 1) const {
+        if (to) std::memcpy(to, fetched(i), (size_t)span * W * sizeof(T));
+    }
+};

@@ -36,6 +36,11 @@ struct IkArgs {
     int32_t *status, *best, *iterations, *flags;
     double *q_best, *q, *err;
 };
+// an entry's arguments as it was given them: the kernel's, and what only check_args reads (it copies the box to lb / ub and the tool point)
+struct IkCall : IkArgs {
+    const double *box_lb, *box_ub, *tool_in;
+    int32_t N, W;
+};
 
 // The chain at q: pe = the end-effector point; o[j] / a[j] = the origin of frame j and the signed world axis of joint j (zero for a joint
 // that is not actuated).  Unrolled over the compiled maximum, so q, o and a are indexed by constants.
@@ -139,9 +144,8 @@ __host__ __device__ inline bool ik_free(const RmRobot& rb, const double (&q)[ARM
 
 struct IkShared {
     double q[ARMOUR_MAX_FACTORS][IK_SPLIT_SEEDS];   // joint j of item s, for the lanes that share the item's free test
-    double red_d[TP_WAVES];
-    int red_v[TP_WAVES];
-    int red_c[TP_WAVES];
+    BlockKeys keys;
+    BlockWords some;                                // per wave: some lane's item converged
     uint8_t conv[TP_BLOCK], hit[TP_BLOCK];
 };
 
@@ -182,12 +186,10 @@ __global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar) {
     sh.hit[t] = 0;
     __syncthreads();
 
-    // ---- free test of the converged items.  Up to TP_BLOCK / 2 seeds an item has G = min(O, TP_BLOCK / S) lanes, lane g of them with the
-    // obstacles [g O / G, (g + 1) O / G): the verdict is the AND over obstacles, so the split changes nothing but the time.
-    int G = 1;
-    if (S <= IK_SPLIT_SEEDS && O > 1) G = TP_BLOCK / S < O ? TP_BLOCK / S : O;
+    // ---- free test of the converged items.  Up to TP_BLOCK / 2 seeds an item's obstacles are split over several lanes (obstacle_split).
     {
-        const int it = t / G, g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
+        const ObstacleSplit sp = obstacle_split(S, O, true, t);
+        const int it = t / sp.G, o0 = sp.o0, o1 = sp.o1;
         if (it < S && sh.conv[it] && o1 > o0) {
             double x[ARMOUR_MAX_FACTORS];
 #pragma unroll
@@ -199,25 +201,18 @@ __global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar) {
     const bool free_ = conv && !sh.hit[t];
     if (t < S && ar.flags) ar.flags[item] = (conv ? 1 : 0) | (free_ ? 2 : 0);
 
-    // ---- pick: the smallest (acc, s) over the items that are converged and free; the order is total
+    // ---- pick: the smallest (acc, s) over the items that are converged and free; the order is total.  The convergence ballot rides on the
+    // argmin's barrier: each wave's word is written before it and folded after it.  Neither sh.keys nor sh.some is written again (the
+    // kernel ends), so the argmin is not released.
     double bd = INFINITY;
     int bv = TP_NONE;
     if (free_) { bd = wrapped_sq(rb, q_ref, q); bv = t; }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_xor(bd, off);
-        const int ov = __shfl_xor(bv, off);
-        if (key_less(od, ov, bd, bv)) { bd = od; bv = ov; }
-    }
     const unsigned long long any = __ballot(conv);
-    if ((t & 63) == 0) { sh.red_d[t >> 6] = bd; sh.red_v[t >> 6] = bv; sh.red_c[t >> 6] = any ? 1 : 0; }
-    __syncthreads();
-    bd = sh.red_d[0]; bv = sh.red_v[0];
-    int some = sh.red_c[0];
+    if ((t & 63) == 0) sh.some.w[t >> 6] = any ? 1 : 0;
+    block_argmin<false>(sh.keys, &bd, &bv);
+    int some = 0;
 #pragma unroll
-    for (int k = 1; k < TP_WAVES; k++) {
-        if (key_less(sh.red_d[k], sh.red_v[k], bd, bv)) { bd = sh.red_d[k]; bv = sh.red_v[k]; }
-        some |= sh.red_c[k];
-    }
+    for (int k = 0; k < TP_WAVES; k++) some |= sh.some.w[k];
     if (t == bv) {                                          // the picked item's own lane holds its q
 #pragma unroll
         for (int j = 0; j < ARMOUR_MAX_FACTORS; j++)
@@ -270,42 +265,33 @@ void ik_target_host(const RmRobot& rb, const IkArgs& ar, int tg, const double* o
     if (margin) *margin = m;
 }
 
-// the argument rules of both entries, before a device is touched; fills rb and ar (the caller's pointers)
-int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
-               int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds, double lambda,
-               double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err, int32_t* iterations,
-               int32_t* flags, RmRobot* rb, IkArgs* ar) {
-    if (!robot || !lb || !ub || !tool) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+// the argument rules of both entries, before a device is touched, on ar as the entry filled it; fills rb and ar.lb / ar.ub / ar.tool
+int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, RmRobot* rb, IkCall* ar) {
+    const int32_t N = ar->N, S = ar->S, W = ar->W, O = ar->O;
+    if (!robot || !ar->box_lb || !ar->box_ub || !ar->tool_in) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
     ARMOUR_TRY(armour_check_robot_shape(who, robot));
-    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, ar->obstacles));
     const int n = robot->num_factors;
-    if (N < 0 || N > ARMOUR_IK_MAX_TARGETS || S < 1 || S > ARMOUR_IK_MAX_SEEDS || max_iterations < 0 || max_iterations > ARMOUR_IK_MAX_ITERATIONS) {
-        armour_set_error("%s: N = %d (0..%d), S = %d (1..%d), max_iterations = %d (0..%d)", who, N, ARMOUR_IK_MAX_TARGETS, S, ARMOUR_IK_MAX_SEEDS, max_iterations,
+    if (N < 0 || N > ARMOUR_IK_MAX_TARGETS || S < 1 || S > ARMOUR_IK_MAX_SEEDS || ar->max_iterations < 0 || ar->max_iterations > ARMOUR_IK_MAX_ITERATIONS) {
+        armour_set_error("%s: N = %d (0..%d), S = %d (1..%d), max_iterations = %d (0..%d)", who, N, ARMOUR_IK_MAX_TARGETS, S, ARMOUR_IK_MAX_SEEDS, ar->max_iterations,
                          ARMOUR_IK_MAX_ITERATIONS);
         return ARMOUR_EINVAL;
     }
-    if (N > 0 && (!world || !targets || !q_ref || !seeds || !status || !best || !q_best)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
-    if (!(lambda > 0.0) || !(e_max > 0.0) || !(tol > 0.0) || !std::isfinite(lambda) || !std::isfinite(e_max) || !std::isfinite(tol)) {
-        armour_set_error("%s: lambda = %g, e_max = %g, tol = %g (all must be positive and finite)", who, lambda, e_max, tol);
+    if (N > 0 && (!ar->world || !ar->targets || !ar->q_ref || !ar->seeds || !ar->status || !ar->best || !ar->q_best)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    if (!(ar->lambda > 0.0) || !(ar->e_max > 0.0) || !(ar->tol > 0.0) || !std::isfinite(ar->lambda) || !std::isfinite(ar->e_max) || !std::isfinite(ar->tol)) {
+        armour_set_error("%s: lambda = %g, e_max = %g, tol = %g (all must be positive and finite)", who, ar->lambda, ar->e_max, ar->tol);
         return ARMOUR_EINVAL;
     }
-    for (int j = 0; j < n; j++)
-        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: box [%g, %g] of joint %d", who, lb[j], ub[j], j); return ARMOUR_EINVAL; }
-    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(targets, (size_t)N * 3) || !finite_all(q_ref, (size_t)N * n) || !finite_all(tool, 3)) {
+    ARMOUR_TRY(armour_check_box(who, "box", "joint", n, ar->box_lb, ar->box_ub));
+    if (!finite_all(ar->obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(ar->targets, (size_t)N * 3) || !finite_all(ar->q_ref, (size_t)N * n) || !finite_all(ar->tool_in, 3)) {
         armour_set_error("%s: a target, a reference configuration, the tool point or an obstacle is not finite", who);
         return ARMOUR_EINVAL;
     }
     for (int32_t t = 0; t < N; t++)
-        if (world[t] < -1 || world[t] >= W) { armour_set_error("%s: target %d is in world %d (-1..%d)", who, t, world[t], W - 1); return ARMOUR_EINVAL; }
+        if (ar->world[t] < -1 || ar->world[t] >= W) { armour_set_error("%s: target %d is in world %d (-1..%d)", who, t, ar->world[t], W - 1); return ARMOUR_EINVAL; }
     fill_rm_robot(robot, continuous, rb);
-    std::memset(ar, 0, sizeof(*ar));
-    for (int j = 0; j < n; j++) { ar->lb[j] = lb[j]; ar->ub[j] = ub[j]; }
-    for (int i = 0; i < 3; i++) ar->tool[i] = tool[i];
-    ar->lambda = lambda; ar->e_max = e_max; ar->tol = tol;
-    ar->S = S; ar->O = O; ar->max_iterations = max_iterations;
-    ar->obstacles = obstacles; ar->targets = targets; ar->q_ref = q_ref; ar->world = world; ar->seeds = seeds;
-    ar->status = status; ar->best = best; ar->iterations = iterations; ar->flags = flags;
-    ar->q_best = q_best; ar->q = q; ar->err = err;
+    for (int j = 0; j < n; j++) { ar->lb[j] = ar->box_lb[j]; ar->ub[j] = ar->box_ub[j]; }
+    for (int i = 0; i < 3; i++) ar->tool[i] = ar->tool_in[i];
     return ARMOUR_OK;
 }
 
@@ -317,15 +303,12 @@ extern "C" int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuou
                               int32_t* iterations, int32_t* flags, double* margin) {
     const char* who = "armour_ik_host";
     RmRobot rb;
-    IkArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best,
-                          q_best, q, err, iterations, flags, &rb, &ar));
-    std::vector<double> obs((size_t)O * RM_OBS_STRIDE);     // staged as the kernel stages them
-    for (int32_t t = 0; t < N; t++) {
-        const int32_t w = world[t];
-        if (w >= 0) stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
-        ik_target_host(rb, ar, t, obs.data(), w < 0 ? 0 : O, margin ? margin + t : nullptr);
-    }
+    IkCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.tool_in = tool; ar.N = N; ar.S = S; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.world = world; ar.targets = targets;
+    ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
+    ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
+    for_each_staged(N, O, obstacles, world, [&](int32_t t, const double* obs, int count) { ik_target_host(rb, ar, t, obs, count, margin ? margin + t : nullptr); });
     return ARMOUR_OK;
 }
 
@@ -335,9 +318,11 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
                          int32_t* iterations, int32_t* flags, double* ms) {
     const char* who = "armour_ik";
     RmRobot rb;
-    IkArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best,
-                          q_best, q, err, iterations, flags, &rb, &ar));
+    IkCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.tool_in = tool; ar.N = N; ar.S = S; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.world = world; ar.targets = targets;
+    ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
+    ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
     if (ms) *ms = 0.0;
     if (N == 0) return ARMOUR_OK;
     if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ik_host is the host form)", who); return ARMOUR_EDEVICE; }
@@ -347,7 +332,8 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
     EventPair ev;
     DevBuf<double> d_obs, d_targets, d_ref, d_qbest, d_q, d_err;
     DevBuf<uint64_t> d_seeds;
-    DevBuf<int32_t> d_world, d_out, d_items;               // d_out: status | best [N] each; d_items: iterations | flags [N][S] each
+    DevBuf<int32_t> d_world, d_items;                      // d_items: iterations | flags [N][S] each, either may be absent
+    DevColumns<int32_t> out;                               // status | best [N] each
     ARMOUR_TRY(st.create());
     ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
     ARMOUR_TRY(d_targets.upload(targets, (size_t)N * 3, st));
@@ -355,13 +341,13 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
     ARMOUR_TRY(d_seeds.upload(seeds, (size_t)N, st));
     ARMOUR_TRY(d_world.upload(world, (size_t)N, st));
     ARMOUR_TRY(d_qbest.reserve((size_t)N * n));
-    ARMOUR_TRY(d_out.reserve((size_t)2 * N));
+    ARMOUR_TRY(out.reserve(2, (size_t)N));
     if (q) ARMOUR_TRY(d_q.reserve(items * n));
     if (err) ARMOUR_TRY(d_err.reserve(items));
     if (iterations || flags) ARMOUR_TRY(d_items.reserve(2 * items));
-    IkArgs dev = ar;
+    IkArgs dev = ar;                                       // (the kernel's part)
     dev.obstacles = d_obs; dev.targets = d_targets; dev.q_ref = d_ref; dev.seeds = d_seeds; dev.world = d_world;
-    dev.status = d_out; dev.best = d_out + N; dev.q_best = d_qbest;
+    dev.status = out.column(0); dev.best = out.column(1); dev.q_best = d_qbest;
     dev.q = q ? d_q.p : nullptr;
     dev.err = err ? d_err.p : nullptr;
     dev.iterations = iterations ? d_items.p : nullptr;
@@ -370,16 +356,15 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
     hipLaunchKernelGGL(ik_kernel, dim3((unsigned)N), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, rb, dev);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
-    std::vector<int32_t> out((size_t)2 * N);
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ARMOUR_TRY(out.fetch(st));
     if (q) HIPCHK(hipMemcpyAsync(q, d_q, items * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (err) HIPCHK(hipMemcpyAsync(err, d_err, items * sizeof(double), hipMemcpyDeviceToHost, st));
     if (iterations) HIPCHK(hipMemcpyAsync(iterations, d_items, items * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (flags) HIPCHK(hipMemcpyAsync(flags, d_items + items, items * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    std::memcpy(status, out.data(), (size_t)N * sizeof(int32_t));
-    std::memcpy(best, out.data() + N, (size_t)N * sizeof(int32_t));
+    out.copy_out(0, status);
+    out.copy_out(1, best);
     // only the rows that were written come back (a target without a pick leaves the caller's row as it was)
     for (int32_t t = 0; t < N; t++)
         if (best[t] >= 0) HIPCHK(hipMemcpyAsync(q_best + (size_t)t * n, d_qbest + (size_t)t * n, n * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -39,6 +39,10 @@ struct ShortcutArgs {
     int32_t *status, *points, *first_bad, *passes_done;
     double *out, *length_in, *length_out;
 };
+// an entry's arguments as it was given them: the kernel's, and what only check_args reads
+struct ShortcutCall : ShortcutArgs {
+    int32_t W;
+};
 
 __host__ __device__ inline bool same_bits(double x, double y) {
     uint64_t a, b;
@@ -59,49 +63,14 @@ __device__ inline int lane_segments(const RmRobot& rb, const double (&a)[ARMOUR_
     return S < 1.0 ? 1 : S > (double)ARMOUR_TREE_MAX_SEGMENTS ? ARMOUR_TREE_MAX_SEGMENTS : (int)S;
 }
 
-// ---- the block's cooperative steps.  Every result is the same in all lanes.
+// ---- the block's cooperative steps (on tree_block.h's).  Every result is the same in all lanes.
 struct ShortShared {
     int hit[2 * SC_MAX];       // per candidate of the current work list: 1 = some sub-segment's enlarged test did not separate
     int pos[SC_MAX];           // refine: the index of point k in the refined list
     double norm[SC_MAX];       // the wrapped length of segment k, for the sums in index order
     int end[TP_BLOCK];         // a chunk's window: one past the last work item of window candidate t
-    int wsum[TP_WAVES], first[TP_WAVES];
+    BlockWords words;
 };
-
-// the smallest lane with `flag`, TP_NONE when there is none (block_prefix's ballot and LDS words)
-__device__ inline int block_first(ShortShared& sh, bool flag) {
-    const int t = threadIdx.x;
-    const unsigned long long mask = __ballot(flag);
-    if ((t & 63) == 0) sh.first[t >> 6] = mask ? (t & ~63) + __ffsll((long long)mask) - 1 : TP_NONE;
-    __syncthreads();
-    int f = sh.first[0];
-#pragma unroll
-    for (int w = 1; w < TP_WAVES; w++) f = sh.first[w] < f ? sh.first[w] : f;
-    __syncthreads();                                        // sh.first has been read: the next call may write it
-    return f;
-}
-
-// inclusive sum of v over lanes 0 .. t; *total = the block's sum
-__device__ inline int block_scan(ShortShared& sh, int v, int* total) {
-    const int t = threadIdx.x;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if ((t & 63) >= o) x += y;
-    }
-    if ((t & 63) == 63) sh.wsum[t >> 6] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < TP_WAVES; w++) {
-        base += w < (t >> 6) ? sh.wsum[w] : 0;
-        tot += sh.wsum[w];
-    }
-    __syncthreads();                                        // sh.wsum has been read
-    *total = tot;
-    return base + x;
-}
 
 // The work list's candidate k as an edge a -> b, from the list pts [count][n] in LDS.  validate: p_k -> p_{k+1}; prune: p_anchor -> p_{last-k};
 // refine: half k & 1 of the pair (p_{k>>1}, p_{(k>>1)+1}) about its midpoint -- false when the pair's points are equal bit for bit (no midpoint
@@ -129,9 +98,8 @@ __device__ __forceinline__ bool load_edge(const RmRobot& rb, const EdgeSet& es, 
 
 // One work list of C candidates (C <= 2 SC_MAX).  A chunk looks at a window of up to TP_BLOCK candidates from its cursor (cbase, and sbase
 // sub-segments of candidate cbase already tested), numbers their remaining sub-segments as work items in candidate order and tests the first
-// TP_BLOCK of them, a lane each.  When the whole rest of the list is at most TP_BLOCK / 2 items, each item gets G = min(O, TP_BLOCK / items)
-// lanes, lane g of them testing the obstacles [g O / G, (g + 1) O / G): the tree planner's obstacle split (a sub-segment is free iff it is
-// free of every obstacle).  A lane whose test does not separate stores 1 to its candidate's word sh.hit -- several lanes may store to one
+// TP_BLOCK of them, a lane each.  When the whole rest of the list is at most TP_BLOCK / 2 items, each item's obstacles are split over
+// several lanes (obstacle_split).  A lane whose test does not separate stores 1 to its candidate's word sh.hit -- several lanes may store to one
 // word, all of them the same 1.  After the chunk's barrier:
 //   validate  returns the first candidate with a hit (candidates are in ascending order, so it is the first edge that is not free);
 //   prune     returns the first candidate that is fully tested without a hit -- every candidate above it has a hit;
@@ -154,32 +122,21 @@ __device__ inline int run_edges(const RmRobot& rb, ShortShared& sh, const EdgeSe
             if (t == 0) Sk -= sbase;
         }
         int T;
-        sh.end[t] = block_scan(sh, Sk, &T);
+        sh.end[t] = block_scan(sh.words, Sk, &T);
         __syncthreads();
-        int G = 1;
-        if (nw == C - cbase && 2 * T <= TP_BLOCK && O > 1) G = TP_BLOCK / T < O ? TP_BLOCK / T : O;
-        const int per = TP_BLOCK / G;                       // work items per chunk
-        const int item = t / G, g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
-        if (t < per * G && item < T) {
-            int lo = 0, hi = nw;                            // the item's candidate: the number of ends <= item
-            for (int it = 0; it < 9 && lo < hi; it++) {
-                const int mid = (lo + hi) >> 1;
-                if (sh.end[mid] <= item) lo = mid + 1; else hi = mid;
-            }
-            const int k = lo, start = k ? sh.end[k - 1] : 0, done = k ? 0 : sbase;
+        const ObstacleSplit sp = obstacle_split(T, O, nw == C - cbase, t);
+        const int per = sp.per, item = t / sp.G;            // per work items to a chunk
+        if (t < per * sp.G && item < T) {
+            const int k = item_owner(sh.end, nw, item), start = k ? sh.end[k - 1] : 0, done = k ? 0 : sbase;
             load_edge(rb, es, pts, cbase + k, a, b);
-            if (!segment_free(rb, a, b, item - start + done, sh.end[k] - start + done, s_obs + (size_t)o0 * RM_OBS_STRIDE, o1 - o0)) sh.hit[cbase + k] = 1;
+            if (!segment_free(rb, a, b, item - start + done, sh.end[k] - start + done, s_obs + (size_t)sp.o0 * RM_OBS_STRIDE, sp.o1 - sp.o0)) sh.hit[cbase + k] = 1;
         }
         __syncthreads();
-        int lo = 0, hi = nw;                                // the candidates with an item in this chunk: 1 + the number of ends < per
-        for (int it = 0; it < 9 && lo < hi; it++) {
-            const int mid = (lo + hi) >> 1;
-            if (sh.end[mid] < per) lo = mid + 1; else hi = mid;
-        }
-        const int kn = lo + 1 < nw ? lo + 1 : nw;
+        const int in_chunk = item_owner(sh.end, nw, per - 1) + 1;   // the candidates with an item in this chunk: 1 + the number of ends < per
+        const int kn = in_chunk < nw ? in_chunk : nw;
         const bool full = t < kn && sh.end[t] <= per, h = t < kn && sh.hit[cbase + t] != 0;
         if (es.kind != SC_REFINE) {
-            const int stop = block_first(sh, es.kind == SC_PRUNE ? (full && !h) : h);
+            const int stop = block_first(sh.words, es.kind == SC_PRUNE ? (full && !h) : h);
             if (stop != TP_NONE) return cbase + stop;
         }
         const int last = kn - 1;
@@ -227,7 +184,7 @@ __device__ inline int block_refine(const RmRobot& rb, ShortShared& sh, double* p
         mine += k < count - 1 && !sh.hit[2 * k] && !sh.hit[2 * k + 1] ? 1 : 0;
     }
     int inserted;
-    const int upto = block_scan(sh, mine, &inserted) - mine;
+    const int upto = block_scan(sh.words, mine, &inserted) - mine;
 #pragma unroll
     for (int u = 0; u < SC_PER_LANE; u++) {
         const int k = SC_PER_LANE * t + u;
@@ -393,61 +350,43 @@ void shortcut_world_host(const RmRobot& rb, const ShortcutArgs& ar, int w, const
     if (ar.out && count <= ar.max_points) std::memcpy(ar.out + (size_t)w * ar.max_points * n, pts.data(), (size_t)count * n * sizeof(double));
 }
 
-// the argument rules of both entries, before a device is touched; fills rb and ar (the caller's pointers)
-int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
-               const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status, int32_t* points,
-               int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, RmRobot* rb, ShortcutArgs* ar) {
+// the argument rules of both entries, before a device is touched, on ar as the entry filled it; fills rb
+int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, RmRobot* rb, const ShortcutCall& ar) {
+    const int32_t W = ar.W, O = ar.O, max_in = ar.max_in;
     if (!robot) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
     ARMOUR_TRY(armour_check_robot_shape(who, robot));
-    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, ar.obstacles));
     const int n = robot->num_factors;
-    if (W > 0 && (!paths || !counts || !status || !points || !first_bad || !passes_done || !length_in || !length_out)) {
+    if (W > 0 && (!ar.paths || !ar.counts || !ar.status || !ar.points || !ar.first_bad || !ar.passes_done || !ar.length_in || !ar.length_out)) {
         armour_set_error("%s: null argument", who);
         return ARMOUR_EINVAL;
     }
-    if (max_in < 2 || max_in > ARMOUR_SHORTCUT_MAX_POINTS || max_points < 2 || max_points > ARMOUR_SHORTCUT_MAX_POINTS || passes < 1 ||
-        passes > ARMOUR_SHORTCUT_MAX_PASSES) {
-        armour_set_error("%s: max_in = %d, max_points = %d (2..%d), passes = %d (1..%d)", who, max_in, max_points, ARMOUR_SHORTCUT_MAX_POINTS, passes,
+    if (max_in < 2 || max_in > ARMOUR_SHORTCUT_MAX_POINTS || ar.max_points < 2 || ar.max_points > ARMOUR_SHORTCUT_MAX_POINTS || ar.passes < 1 ||
+        ar.passes > ARMOUR_SHORTCUT_MAX_PASSES) {
+        armour_set_error("%s: max_in = %d, max_points = %d (2..%d), passes = %d (1..%d)", who, max_in, ar.max_points, ARMOUR_SHORTCUT_MAX_POINTS, ar.passes,
                          ARMOUR_SHORTCUT_MAX_PASSES);
         return ARMOUR_EINVAL;
     }
-    if (!(edge_step > 0.0) || !std::isfinite(edge_step)) { armour_set_error("%s: edge_step = %g", who, edge_step); return ARMOUR_EINVAL; }
+    if (!(ar.edge_step > 0.0) || !std::isfinite(ar.edge_step)) { armour_set_error("%s: edge_step = %g", who, ar.edge_step); return ARMOUR_EINVAL; }
     for (int32_t w = 0; w < W; w++) {
-        if (counts[w] < 2 || counts[w] > max_in) { armour_set_error("%s: world %d's path has %d points (2..max_in = %d)", who, w, counts[w], max_in); return ARMOUR_EINVAL; }
-        if (!finite_all(paths + (size_t)w * max_in * n, (size_t)counts[w] * n)) { armour_set_error("%s: a point of world %d's path is not finite", who, w); return ARMOUR_EINVAL; }
+        if (ar.counts[w] < 2 || ar.counts[w] > max_in) { armour_set_error("%s: world %d's path has %d points (2..max_in = %d)", who, w, ar.counts[w], max_in); return ARMOUR_EINVAL; }
+        if (!finite_all(ar.paths + (size_t)w * max_in * n, (size_t)ar.counts[w] * n)) { armour_set_error("%s: a point of world %d's path is not finite", who, w); return ARMOUR_EINVAL; }
     }
-    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES)) { armour_set_error("%s: an obstacle is not finite", who); return ARMOUR_EINVAL; }
+    if (!finite_all(ar.obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES)) { armour_set_error("%s: an obstacle is not finite", who); return ARMOUR_EINVAL; }
     fill_rm_robot(robot, continuous, rb);
-    // No edge of a run is longer, joint by joint, than pi (a wrapped joint) or the extent of the paths' points (any other: a midpoint lies
-    // between two points): that many sub-segments must fit the cap.
+    // the extent of a joint: that of the paths' points (any other point: a midpoint lies between two points)
+    double extent[ARMOUR_MAX_FACTORS];
     for (int j = 0; j < n; j++) {
         double lo = INFINITY, hi = -INFINITY;
         for (int32_t w = 0; w < W && !rb->cont[j]; w++)
-            for (int32_t k = 0; k < counts[w]; k++) {
-                const double x = paths[((size_t)w * max_in + k) * n + j];
+            for (int32_t k = 0; k < ar.counts[w]; k++) {
+                const double x = ar.paths[((size_t)w * max_in + k) * n + j];
                 lo = std::fmin(lo, x);
                 hi = std::fmax(hi, x);
             }
-        const double span = rb->cont[j] ? RM_PI : (W > 0 ? hi - lo : 0.0);
-        if (!(std::ceil(span / edge_step) <= (double)ARMOUR_TREE_MAX_SEGMENTS)) {
-            armour_set_error("%s: joint %d spans %g, more than %d sub-segments of edge_step %g", who, j, span, ARMOUR_TREE_MAX_SEGMENTS, edge_step);
-            return ARMOUR_ECAPACITY;
-        }
+        extent[j] = W > 0 ? hi - lo : 0.0;
     }
-    std::memset(ar, 0, sizeof(*ar));
-    ar->edge_step = edge_step;
-    ar->O = O; ar->max_in = max_in; ar->max_points = max_points; ar->passes = passes;
-    ar->obstacles = obstacles; ar->paths = paths; ar->counts = counts;
-    ar->status = status; ar->points = points; ar->first_bad = first_bad; ar->passes_done = passes_done;
-    ar->out = out; ar->length_in = length_in; ar->length_out = length_out;
-    return ARMOUR_OK;
-}
-
-// the roadmap entries' capacity rule: points [W] is complete; a path longer than max_points was not written
-int check_capacity(const char* who, int32_t W, const int32_t* points, int32_t max_points) {
-    for (int32_t w = 0; w < W; w++)
-        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
-    return ARMOUR_OK;
+    return check_joint_spans(who, *rb, extent, ar.edge_step);
 }
 
 }  // namespace
@@ -458,15 +397,13 @@ extern "C" int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t
                                          double* margin) {
     const char* who = "armour_path_shortcut_host";
     RmRobot rb;
-    ShortcutArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out,
-                          length_in, length_out, &rb, &ar));
-    std::vector<double> obs((size_t)O * RM_OBS_STRIDE);                          // staged as the kernel stages them
-    for (int32_t w = 0; w < W; w++) {
-        stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
-        shortcut_world_host(rb, ar, w, obs.data(), margin ? margin + w : nullptr);
-    }
-    return check_capacity(who, W, points, max_points);
+    ShortcutCall ar{};
+    ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.max_in = max_in; ar.paths = paths; ar.counts = counts; ar.edge_step = edge_step; ar.passes = passes;
+    ar.max_points = max_points; ar.status = status; ar.points = points; ar.first_bad = first_bad; ar.passes_done = passes_done; ar.out = out;
+    ar.length_in = length_in; ar.length_out = length_out;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, ar));
+    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) { shortcut_world_host(rb, ar, w, obs, margin ? margin + w : nullptr); });
+    return armour_check_path_capacity(who, W, points, max_points, true);
 }
 
 extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
@@ -474,9 +411,11 @@ extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* con
                                     int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, double* ms) {
     const char* who = "armour_path_shortcut";
     RmRobot rb;
-    ShortcutArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out,
-                          length_in, length_out, &rb, &ar));
+    ShortcutCall ar{};
+    ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.max_in = max_in; ar.paths = paths; ar.counts = counts; ar.edge_step = edge_step; ar.passes = passes;
+    ar.max_points = max_points; ar.status = status; ar.points = points; ar.first_bad = first_bad; ar.passes_done = passes_done; ar.out = out;
+    ar.length_in = length_in; ar.length_out = length_out;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, ar));
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
     if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_path_shortcut_host is the host form)", who); return ARMOUR_EDEVICE; }
@@ -485,19 +424,21 @@ extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* con
     const size_t lds = ((size_t)O * RM_OBS_STRIDE + rows * n) * sizeof(double);
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_paths, d_path_out, d_len;     // d_len: length_in | length_out [W] each
-    DevBuf<int32_t> d_counts, d_out;                      // d_out: status | points | first_bad | passes_done [W] each
+    DevBuf<double> d_obs, d_paths, d_path_out;
+    DevBuf<int32_t> d_counts;
+    DevColumns<double> len;                               // length_in | length_out [W] each
+    DevColumns<int32_t> res;                              // status | points | first_bad | passes_done [W] each
     ARMOUR_TRY(st.create());
     ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
     ARMOUR_TRY(d_paths.upload(paths, (size_t)W * max_in * n, st));
     ARMOUR_TRY(d_counts.upload(counts, (size_t)W, st));
-    ARMOUR_TRY(d_out.reserve((size_t)4 * W));
-    ARMOUR_TRY(d_len.reserve((size_t)2 * W));
+    ARMOUR_TRY(res.reserve(4, (size_t)W));
+    ARMOUR_TRY(len.reserve(2, (size_t)W));
     if (out) ARMOUR_TRY(d_path_out.reserve(out_len));
-    ShortcutArgs dev = ar;
+    ShortcutArgs dev = ar;                                // (the kernel's part)
     dev.obstacles = d_obs; dev.paths = d_paths; dev.counts = d_counts;
-    dev.status = d_out; dev.points = d_out + W; dev.first_bad = d_out + 2 * (size_t)W; dev.passes_done = d_out + 3 * (size_t)W;
-    dev.length_in = d_len; dev.length_out = d_len + W;
+    dev.status = res.column(0); dev.points = res.column(1); dev.first_bad = res.column(2); dev.passes_done = res.column(3);
+    dev.length_in = len.column(0); dev.length_out = len.column(1);
     dev.out = out ? d_path_out.p : nullptr;
     // beside the kernel's static 21.6 KB: at the caps 55 KB of obstacles and 56 KB of path, which a block may have once it asks
     if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(path_shortcut_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -505,22 +446,18 @@ extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* con
     hipLaunchKernelGGL(path_shortcut_kernel, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
-    std::vector<int32_t> h_out((size_t)4 * W);
-    std::vector<double> h_len((size_t)2 * W);
-    HIPCHK(hipMemcpyAsync(h_out.data(), d_out, h_out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h_len.data(), d_len, h_len.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    ARMOUR_TRY(res.fetch(st));
+    ARMOUR_TRY(len.fetch(st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    std::memcpy(status, h_out.data(), (size_t)W * sizeof(int32_t));
-    std::memcpy(points, h_out.data() + W, (size_t)W * sizeof(int32_t));
-    std::memcpy(first_bad, h_out.data() + 2 * (size_t)W, (size_t)W * sizeof(int32_t));
-    std::memcpy(passes_done, h_out.data() + 3 * (size_t)W, (size_t)W * sizeof(int32_t));
-    std::memcpy(length_in, h_len.data(), (size_t)W * sizeof(double));
-    std::memcpy(length_out, h_len.data() + W, (size_t)W * sizeof(double));
+    int32_t* const ints[4] = {status, points, first_bad, passes_done};
+    for (int k = 0; k < 4; k++) res.copy_out(k, ints[k]);
+    len.copy_out(0, length_in);
+    len.copy_out(1, length_out);
     // only the rows that were written come back (the rest of the caller's array is left as it was)
     for (int32_t w = 0; out && w < W; w++)
         if (points[w] > 0 && points[w] <= max_points)
             HIPCHK(hipMemcpyAsync(out + (size_t)w * max_points * n, d_path_out + (size_t)w * max_points * n, (size_t)points[w] * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    return check_capacity(who, W, points, max_points);
+    return armour_check_path_capacity(who, W, points, max_points, true);
 }

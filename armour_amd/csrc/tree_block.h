@@ -3,9 +3,14 @@
 // the cut point), and the host twins' prefix with its margin.  include/armour_hip.h states the rule; everything here is the roadmap's
 // geometry (roadmap_handle.h) called the same way by a kernel's lanes and by a host loop.
 // The block shape and the counter hash u(seed, i, j) are also what the inverse kinematics (ik.hip) takes from here.
+// The block-cooperative steps of the per-world kernels are here too (below): first / any lane with a flag, inclusive scan, argmin in the
+// order key_less, the obstacle split and the owner of a work item.  path_shortcut.hip and ik.hip take all they need from here; tree_plan.hip
+// takes block_first and ws_tree.hip block_any / block_scan / block_argmin, and each of the two keeps the rest inline, where the shared form
+// measured slower.  The argument rules and the staging loop of all four kernels' host entries are here as well.
 #pragma once
 #include <climits>
 #include <cmath>
+#include <vector>
 
 #include "common.h"
 #include "roadmap_handle.h"
@@ -50,6 +55,106 @@ __host__ __device__ inline bool node_free(const RmRobot& rb, const double* x, co
     return config_free(rb, q, r, obs, O, false, nullptr);
 }
 
+// ---- the block's cooperative steps: TP_BLOCK lanes, ordered by __syncthreads() alone.  Every result is the same in all lanes.
+// The per-wave words a step goes through.  Every step is: each wave's lane writes its word, BARRIER, every lane folds the TP_WAVES words,
+// and a second barrier after the fold releases the words, so that the next step of any kind may write them at once.  block_argmin alone
+// has a form without the second barrier (RELEASE = false), for a caller that names the barrier every lane reaches before the keys are
+// written again.
+struct BlockWords { int w[TP_WAVES]; };                          // first, any, scan
+struct BlockKeys { double d[TP_WAVES]; int v[TP_WAVES]; };      // argmin (a kernel without an argmin has no such words)
+
+// the smallest lane with `flag`, TP_NONE when there is none
+__device__ inline int block_first(BlockWords& bw, bool flag) {
+    const int t = threadIdx.x;
+    const unsigned long long mask = __ballot(flag);
+    if ((t & 63) == 0) bw.w[t >> 6] = mask ? (t & ~63) + __ffsll((long long)mask) - 1 : TP_NONE;
+    __syncthreads();
+    int f = bw.w[0];
+#pragma unroll
+    for (int w = 1; w < TP_WAVES; w++) f = bw.w[w] < f ? bw.w[w] : f;
+    __syncthreads();
+    return f;
+}
+// whether any lane has `flag`: the first step with less output (an OR of the waves' words)
+__device__ inline bool block_any(BlockWords& bw, bool flag) {
+    const int t = threadIdx.x;
+    const unsigned long long mask = __ballot(flag);
+    if ((t & 63) == 0) bw.w[t >> 6] = mask != 0ull;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < TP_WAVES; w++) r |= bw.w[w];
+    __syncthreads();
+    return r != 0;
+}
+// inclusive sum of v over lanes 0 .. t; *total = the block's sum
+__device__ inline int block_scan(BlockWords& bw, int v, int* total) {
+    const int t = threadIdx.x;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if ((t & 63) >= o) x += y;
+    }
+    if ((t & 63) == 63) bw.w[t >> 6] = x;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < TP_WAVES; w++) {
+        base += w < (t >> 6) ? bw.w[w] : 0;
+        tot += bw.w[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + x;
+}
+// the smallest (d, v) of the lanes' keys in the order key_less; a lane without a key passes (INFINITY, TP_NONE)
+template <bool RELEASE = true>
+__device__ inline void block_argmin(BlockKeys& bk, double* d, int* v) {
+    const int t = threadIdx.x;
+    double bd = *d;
+    int bv = *v;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(bd, o);
+        const int ov = __shfl_xor(bv, o);
+        if (key_less(od, ov, bd, bv)) { bd = od; bv = ov; }
+    }
+    if ((t & 63) == 0) { bk.d[t >> 6] = bd; bk.v[t >> 6] = bv; }
+    __syncthreads();
+    bd = bk.d[0]; bv = bk.v[0];
+#pragma unroll
+    for (int w = 1; w < TP_WAVES; w++)
+        if (key_less(bk.d[w], bk.v[w], bd, bv)) { bd = bk.d[w]; bv = bk.v[w]; }
+    if (RELEASE) __syncthreads();
+    *d = bd;
+    *v = bv;
+}
+
+// The obstacle split.  `items` >= 1 work items (sub-segments, seeds) are to be tested against O staged obstacles by TP_BLOCK lanes.  When the
+// caller allows it and the items fill at most half the block, each item gets G = min(O, TP_BLOCK / items) lanes instead of one, lane t being
+// lane g = t % G of item t / G and testing the obstacles [o0, o1) = [g O / G, (g + 1) O / G).  Sound because an item is free iff it is free
+// of every obstacle: the intervals of an item's G lanes partition [0, O), so the OR of their hits is the item's verdict, and the longest
+// lane's work shrinks from O obstacles to ceil(O / G).  Lanes stay in ascending order of item, so the first lane with a hit names the first
+// item with one.  per = TP_BLOCK / G items are taken at a time, by the lanes t < per * G.
+struct ObstacleSplit { int G, per, o0, o1; };
+__host__ __device__ inline ObstacleSplit obstacle_split(int items, int O, bool allowed, int t) {
+    int G = 1;
+    if (allowed && 2 * items <= TP_BLOCK && O > 1) G = TP_BLOCK / items < O ? TP_BLOCK / items : O;
+    const int per = TP_BLOCK / G, g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
+    return ObstacleSplit{G, per, o0, o1};
+}
+// The owner of work item `item` among n <= TP_BLOCK candidates whose items are numbered in candidate order, end[k] = one past the last item
+// of candidate k (ascending; equal neighbours = a candidate without items): the number of ends <= item, which is the first k with
+// end[k] > item, and n when there is none.  Nine rounds halve [0, 256] to nothing; the count bounds the loop regardless of end[].
+__host__ __device__ inline int item_owner(const int* end, int n, int item) {
+    int lo = 0, hi = n;
+    for (int it = 0; it < 9 && lo < hi; it++) {
+        const int mid = (lo + hi) >> 1;
+        if (end[mid] <= item) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // ---- the host twins' steps: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
 struct HostWorld {
     const RmRobot& rb;
@@ -85,5 +190,30 @@ struct HostWorld {
         return S;
     }
 };
+
+// ---- the host entries' shared argument rules and staging loop
+// No edge of a run is longer, joint by joint, than pi (a wrapped joint) or extent[j], the caller's bound on the spread of joint j over every
+// point a run can hold: that many sub-segments must fit the cap.
+inline int check_joint_spans(const char* who, const RmRobot& rb, const double* extent, double edge_step) {
+    for (int j = 0; j < rb.n; j++) {
+        const double span = rb.cont[j] ? RM_PI : extent[j];
+        if (!(std::ceil(span / edge_step) <= (double)ARMOUR_TREE_MAX_SEGMENTS)) {
+            armour_set_error("%s: joint %d spans %g, more than %d sub-segments of edge_step %g", who, j, span, ARMOUR_TREE_MAX_SEGMENTS, edge_step);
+            return ARMOUR_ECAPACITY;
+        }
+    }
+    return ARMOUR_OK;
+}
+// Item i of `count` (a world, or a target in world world[i]; -1: no obstacles) with its world's obstacles staged as the kernels stage them:
+// run(i, staged obstacles, their number)
+template <class F>
+inline void for_each_staged(int32_t count, int32_t O, const double* obstacles, const int32_t* world, F&& run) {
+    std::vector<double> obs((size_t)O * RM_OBS_STRIDE);
+    for (int32_t i = 0; i < count; i++) {
+        const int32_t w = world ? world[i] : i;
+        if (w >= 0) stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
+        run(i, obs.data(), w < 0 ? 0 : O);
+    }
+}
 
 }  // namespace treeblk

@@ -30,6 +30,11 @@ struct TreeArgs {
     int32_t *status, *iterations, *points, *count, *parent;
     double *path, *nodes;
 };
+// an entry's arguments as it was given them: the kernel's, and what only check_args reads (it copies the box to lb / ub)
+struct TreeCall : TreeArgs {
+    const double *box_lb, *box_ub;
+    int32_t W;
+};
 
 __host__ __device__ inline double tree_sample(const TreeArgs& a, uint64_t seed, int i, int j) { return a.lb[j] + tree_u(seed, (uint64_t)i, (uint64_t)j) * (a.ub[j] - a.lb[j]); }
 
@@ -38,16 +43,19 @@ __host__ __device__ inline double steer_joint(const RmRobot& rb, int j, double a
     const double D = joint_diff(rb, j, a, qr);
     return dist <= step ? a + D : a + (step / dist) * D;
 }
-// ---- the block's cooperative steps.  Every result is the same in all lanes.
+// ---- the block's cooperative steps.  Every result is the same in all lanes.  The first colliding lane is tree_block.h's block_first; the
+// argmin's fold and the obstacle split stay inline: through block_argmin / obstacle_split the kernel measured 0.4 to 0.7 % slower
+// (DESIGN.md 4.12d).
 struct TreeShared {
     double a[ARMOUR_MAX_FACTORS], b[ARMOUR_MAX_FACTORS];   // the edge a prefix walks; b doubles as the query of a nearest scan
     double red_d[TP_WAVES];
     int red_v[TP_WAVES];
-    int first[TP_WAVES];
+    BlockWords words;
     int flag[2];
 };
 
-// argmin over nodes[0 .. cnt) of (wrapped_sq(node, sh.b), index); the caller has put a barrier after the last write of sh.b and of the nodes
+// argmin over nodes[0 .. cnt) of (wrapped_sq(node, sh.b), index); the caller has put a barrier after the last write of sh.b and of the nodes,
+// and reaches one before the next call writes sh.red_*: the barrier that publishes sh.a / sh.b for the prefix, or the one after the sample
 __device__ inline void block_nearest(const RmRobot& rb, TreeShared& sh, const double* nodes, int cnt, double* acc, int* index) {
     const int n = rb.n, t = threadIdx.x;
     double q[ARMOUR_MAX_FACTORS];
@@ -76,10 +84,9 @@ __device__ inline void block_nearest(const RmRobot& rb, TreeShared& sh, const do
 
 // prefix(sh.a, sh.b): *S sub-segments, returns m.  Sub-segments are taken in ascending chunks, up to the first chunk with a hit.  An edge of
 // at most TP_BLOCK / 2 sub-segments (every extend step; most joins) gives each sub-segment G = min(O, TP_BLOCK / S) lanes, lane g of them
-// testing the obstacles [g O / G, (g + 1) O / G) -- a sub-segment is free iff it is free of every obstacle, so the verdict is the same and
-// the lanes that would idle shorten the longest lane's work from O obstacles to O / G.  Lanes are in ascending order of sub-segment, so the
-// first colliding lane names the first colliding sub-segment.  The caller has put a barrier after the last write of sh.a / sh.b; on return
-// every lane is past the last read of them.
+// testing the obstacles [g O / G, (g + 1) O / G): tree_block.h's obstacle_split, which says why it is sound.  Lanes are in ascending order
+// of sub-segment, so the first colliding lane names the first colliding sub-segment.  The caller has put a barrier after the last write of
+// sh.a / sh.b; on return every lane is past the last read of them, and sh.words is released.
 __device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edge_step, const double* s_obs, int O, int* S_out) {
     const int t = threadIdx.x;
     const int S = prefix_segments(rb, sh.a, sh.b, edge_step);
@@ -92,14 +99,8 @@ __device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edg
     for (int base = 0; base < S; base += per) {
         const int s = base + t / G;
         const bool hit = t < per * G && s < S && !segment_free(rb, sh.a, sh.b, s, S, s_obs + (size_t)o0 * RM_OBS_STRIDE, o1 - o0);
-        const unsigned long long mask = __ballot(hit);
-        if ((t & 63) == 0) sh.first[t >> 6] = mask ? base + ((t & ~63) + __ffsll((long long)mask) - 1) / G : TP_NONE;
-        __syncthreads();
-        int f = sh.first[0];
-#pragma unroll
-        for (int w = 1; w < TP_WAVES; w++) f = sh.first[w] < f ? sh.first[w] : f;
-        __syncthreads();                                    // sh.first has been read: the next chunk, or the next prefix, may write it
-        if (f != TP_NONE) { m = f; break; }
+        const int f = block_first(sh.words, hit);           // (released: the next chunk, or the next prefix, may write the words)
+        if (f != TP_NONE) { m = base + f / G; break; }
     }
     return m;
 }
@@ -320,60 +321,41 @@ void plan_world_host(const RmRobot& rb, const TreeArgs& ar, int w, const double*
     done();
 }
 
-// the argument rules of both entries, before a device is touched; fills rb and ar (the caller's pointers)
-int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
-               const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations,
-               int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path, int32_t* count, double* nodes,
-               int32_t* parent, RmRobot* rb, TreeArgs* ar) {
-    if (!robot || !lb || !ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+// the argument rules of both entries, before a device is touched, on ar as the entry filled it; fills rb and ar.lb / ar.ub
+int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continuous, RmRobot* rb, TreeCall* ar) {
+    const int32_t W = ar->W, O = ar->O;
+    if (!robot || !ar->box_lb || !ar->box_ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
     ARMOUR_TRY(armour_check_robot_shape(who, robot));
-    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, ar->obstacles));
     const int n = robot->num_factors;
-    if (W > 0 && (!starts || !goals || !seeds || !status || !iterations || !points)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
-    if (max_nodes < 2 || max_nodes > ARMOUR_TREE_MAX_NODES || max_iterations < 0 || max_iterations > ARMOUR_TREE_MAX_ITERATIONS || max_points < 0) {
-        armour_set_error("%s: max_nodes = %d (2..%d), max_iterations = %d (0..%d), max_points = %d", who, max_nodes, ARMOUR_TREE_MAX_NODES, max_iterations,
-                         ARMOUR_TREE_MAX_ITERATIONS, max_points);
+    if (W > 0 && (!ar->starts || !ar->goals || !ar->seeds || !ar->status || !ar->iterations || !ar->points)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    if (ar->max_nodes < 2 || ar->max_nodes > ARMOUR_TREE_MAX_NODES || ar->max_iterations < 0 || ar->max_iterations > ARMOUR_TREE_MAX_ITERATIONS || ar->max_points < 0) {
+        armour_set_error("%s: max_nodes = %d (2..%d), max_iterations = %d (0..%d), max_points = %d", who, ar->max_nodes, ARMOUR_TREE_MAX_NODES, ar->max_iterations,
+                         ARMOUR_TREE_MAX_ITERATIONS, ar->max_points);
         return ARMOUR_EINVAL;
     }
-    if (!(step > 0.0) || !(edge_step > 0.0) || !std::isfinite(step) || !std::isfinite(edge_step)) {
-        armour_set_error("%s: step = %g, edge_step = %g", who, step, edge_step);
+    if (!(ar->step > 0.0) || !(ar->edge_step > 0.0) || !std::isfinite(ar->step) || !std::isfinite(ar->edge_step)) {
+        armour_set_error("%s: step = %g, edge_step = %g", who, ar->step, ar->edge_step);
         return ARMOUR_EINVAL;
     }
-    for (int j = 0; j < n; j++)
-        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: sampling box [%g, %g] of joint %d", who, lb[j], ub[j], j); return ARMOUR_EINVAL; }
-    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(starts, (size_t)W * n) || !finite_all(goals, (size_t)W * n)) {
+    ARMOUR_TRY(armour_check_box(who, "sampling box", "joint", n, ar->box_lb, ar->box_ub));
+    if (!finite_all(ar->obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(ar->starts, (size_t)W * n) || !finite_all(ar->goals, (size_t)W * n)) {
         armour_set_error("%s: a start, a goal or an obstacle is not finite", who);
         return ARMOUR_EINVAL;
     }
     fill_rm_robot(robot, continuous, rb);
-    // No edge of a run is longer, joint by joint, than pi (a wrapped joint) or the span of the box, the start and the goal (any other: a new
-    // node lies between an old one and a sample): that many sub-segments must fit the cap.
+    // the extent of a joint: the span of the box, the starts and the goals (any other point: a new node lies between an old one and a sample)
+    double extent[ARMOUR_MAX_FACTORS];
     for (int j = 0; j < n; j++) {
-        double lo = lb[j], hi = ub[j];
+        double lo = ar->box_lb[j], hi = ar->box_ub[j];
         for (int32_t w = 0; w < W && !rb->cont[j]; w++) {
-            lo = std::fmin(lo, std::fmin(starts[(size_t)w * n + j], goals[(size_t)w * n + j]));
-            hi = std::fmax(hi, std::fmax(starts[(size_t)w * n + j], goals[(size_t)w * n + j]));
+            lo = std::fmin(lo, std::fmin(ar->starts[(size_t)w * n + j], ar->goals[(size_t)w * n + j]));
+            hi = std::fmax(hi, std::fmax(ar->starts[(size_t)w * n + j], ar->goals[(size_t)w * n + j]));
         }
-        const double span = rb->cont[j] ? RM_PI : hi - lo;
-        if (!(std::ceil(span / edge_step) <= (double)ARMOUR_TREE_MAX_SEGMENTS)) {
-            armour_set_error("%s: joint %d spans %g, more than %d sub-segments of edge_step %g", who, j, span, ARMOUR_TREE_MAX_SEGMENTS, edge_step);
-            return ARMOUR_ECAPACITY;
-        }
+        extent[j] = hi - lo;
     }
-    std::memset(ar, 0, sizeof(*ar));
-    for (int j = 0; j < n; j++) { ar->lb[j] = lb[j]; ar->ub[j] = ub[j]; }
-    ar->step = step; ar->edge_step = edge_step;
-    ar->O = O; ar->max_iterations = max_iterations; ar->max_nodes = max_nodes; ar->max_points = max_points;
-    ar->obstacles = obstacles; ar->starts = starts; ar->goals = goals; ar->seeds = seeds;
-    ar->status = status; ar->iterations = iterations; ar->points = points; ar->count = count; ar->parent = parent;
-    ar->path = path; ar->nodes = nodes;
-    return ARMOUR_OK;
-}
-
-// the roadmap entries' capacity rule: points [W] is complete; a found path longer than max_points was not written
-int check_capacity(const char* who, int32_t W, const int32_t* points, const double* path, int32_t max_points) {
-    for (int32_t w = 0; path && w < W; w++)
-        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
+    ARMOUR_TRY(check_joint_spans(who, *rb, extent, ar->edge_step));
+    for (int j = 0; j < n; j++) { ar->lb[j] = ar->box_lb[j]; ar->ub[j] = ar->box_ub[j]; }
     return ARMOUR_OK;
 }
 
@@ -385,18 +367,19 @@ extern "C" int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* co
                                      double* path, int32_t* count, double* nodes, int32_t* parent, double* margin) {
     const char* who = "armour_tree_plan_host";
     RmRobot rb;
-    TreeArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status,
-                          iterations, points, path, count, nodes, parent, &rb, &ar));
+    TreeCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds;
+    ar.step = step; ar.edge_step = edge_step; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points;
+    ar.status = status; ar.iterations = iterations; ar.points = points; ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
     const int n = rb.n;
-    std::vector<double> obs((size_t)O * RM_OBS_STRIDE), own_nodes(nodes ? 0 : (size_t)2 * max_nodes * n);   // staged as the kernel stages them
+    std::vector<double> own_nodes(nodes ? 0 : (size_t)2 * max_nodes * n);
     std::vector<int32_t> own_parent(parent ? 0 : (size_t)2 * max_nodes);
-    for (int32_t w = 0; w < W; w++) {
-        stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
-        plan_world_host(rb, ar, w, obs.data(), nodes ? nodes + (size_t)w * 2 * max_nodes * n : own_nodes.data(),
-                        parent ? parent + (size_t)w * 2 * max_nodes : own_parent.data(), margin ? margin + w : nullptr);
-    }
-    return check_capacity(who, W, points, path, max_points);
+    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) {
+        plan_world_host(rb, ar, w, obs, nodes ? nodes + (size_t)w * 2 * max_nodes * n : own_nodes.data(), parent ? parent + (size_t)w * 2 * max_nodes : own_parent.data(),
+                        margin ? margin + w : nullptr);
+    });
+    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
 }
 
 extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
@@ -405,9 +388,11 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
                                 int32_t* count, double* nodes, int32_t* parent, double* ms) {
     const char* who = "armour_tree_plan";
     RmRobot rb;
-    TreeArgs ar;
-    ARMOUR_TRY(check_args(who, robot, continuous, lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status,
-                          iterations, points, path, count, nodes, parent, &rb, &ar));
+    TreeCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds;
+    ar.step = step; ar.edge_step = edge_step; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points;
+    ar.status = status; ar.iterations = iterations; ar.points = points; ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent;
+    ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
     if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
@@ -417,7 +402,8 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
     EventPair ev;
     DevBuf<double> d_obs, d_starts, d_goals, d_nodes, d_path;
     DevBuf<uint64_t> d_seeds;
-    DevBuf<int32_t> d_out, d_parent;                      // d_out: status | iterations | points [W] each, then count [W][2]
+    DevBuf<int32_t> d_parent;
+    DevColumns<int32_t> out;                              // status | iterations | points [W] each, then count [W][2]
     ARMOUR_TRY(st.create());
     ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
     ARMOUR_TRY(d_starts.upload(starts, Wn, st));
@@ -425,25 +411,24 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
     ARMOUR_TRY(d_seeds.upload(seeds, (size_t)W, st));
     ARMOUR_TRY(d_nodes.reserve(trees * n));
     ARMOUR_TRY(d_parent.reserve(trees));
-    ARMOUR_TRY(d_out.reserve((size_t)5 * W));
+    ARMOUR_TRY(out.reserve(5, (size_t)W));
     if (path) ARMOUR_TRY(d_path.reserve(path_len));
-    TreeArgs dev = ar;
+    TreeArgs dev = ar;                                    // (the kernel's part)
     dev.obstacles = d_obs; dev.starts = d_starts; dev.goals = d_goals; dev.seeds = d_seeds;
-    dev.status = d_out; dev.iterations = d_out + W; dev.points = d_out + 2 * (size_t)W; dev.count = d_out + 3 * (size_t)W;
+    dev.status = out.column(0); dev.iterations = out.column(1); dev.points = out.column(2); dev.count = out.column(3);
     dev.parent = d_parent; dev.nodes = d_nodes; dev.path = path ? d_path.p : nullptr;
     ARMOUR_TRY(ev.record_start(st));
     hipLaunchKernelGGL(tree_plan_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, rb, dev);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
-    std::vector<int32_t> out((size_t)5 * W);
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ARMOUR_TRY(out.fetch(st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    std::memcpy(status, out.data(), (size_t)W * sizeof(int32_t));
-    std::memcpy(iterations, out.data() + W, (size_t)W * sizeof(int32_t));
-    std::memcpy(points, out.data() + 2 * (size_t)W, (size_t)W * sizeof(int32_t));
-    const int32_t* h_count = out.data() + 3 * (size_t)W;
-    if (count) std::memcpy(count, h_count, (size_t)2 * W * sizeof(int32_t));
+    out.copy_out(0, status);
+    out.copy_out(1, iterations);
+    out.copy_out(2, points);
+    out.copy_out(3, count, 2);
+    const int32_t* h_count = out.fetched(3);
     // the trees and the paths: only the rows that were written come back (the rest of the caller's arrays is left as it was)
     for (int32_t w = 0; w < W; w++) {
         for (int k = 0; k < 2; k++) {
@@ -455,5 +440,5 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
             HIPCHK(hipMemcpyAsync(path + (size_t)w * max_points * n, d_path + (size_t)w * max_points * n, (size_t)points[w] * n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
-    return check_capacity(who, W, points, path, max_points);
+    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
 }

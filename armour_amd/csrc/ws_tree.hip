@@ -38,6 +38,11 @@ struct WsArgs {
     int32_t *status, *iterations, *points, *rewires, *chain_kept, *count, *parent;
     double *path_cost, *goal_dist, *path, *nodes, *node_cost, *node_len;
 };
+// an entry's arguments as it was given them: the kernel's, and what only check_args reads (it copies the box to lb / ub)
+struct WsCall : WsArgs {
+    const double *box_lb, *box_ub;
+    int32_t W;
+};
 
 // ---- the scalar steps of the rule, one copy
 // D = b - a component by component; returns acc = dot(D, D)
@@ -99,73 +104,23 @@ __host__ __device__ inline void ws_steer(const double* xv, const double (&qr)[3]
 // component t of a point that every lane holds, by selects: no array of a lane's own is indexed at run time (no scratch memory)
 __device__ inline double pick3(const double (&a)[3], int t) { return t == 0 ? a[0] : t == 1 ? a[1] : a[2]; }
 
-// ---- the block's cooperative steps.  Every result is the same in all lanes.
+// ---- the block's cooperative steps: tree_block.h's block_any / block_scan / block_argmin, every call released by the step's own trailing
+// barrier.  The obstacle split and the owner search of a round stay inline below: through obstacle_split / item_owner the kernel measured
+// 1.7 % slower.
 struct WsShared {
-    double red_d[TP_WAVES];
-    int red_v[TP_WAVES], wsum[TP_WAVES], any[TP_WAVES];
+    BlockKeys keys;
+    BlockWords sums, any;            // the scan's and the any step's words
     int cand[TP_BLOCK];              // a round's candidates (node indices)
     int end[TP_BLOCK];               // one past the last work item of round candidate k
     unsigned char hit[TP_BLOCK];     // 1: some sub-segment of round candidate k did not separate
     unsigned char free_[WS_CAP];     // per node: 1 = a candidate of this iteration whose edge to qn is free
 };
 
-__device__ inline bool block_any(WsShared& sh, bool flag) {
-    const int t = threadIdx.x;
-    const unsigned long long mask = __ballot(flag);
-    if ((t & 63) == 0) sh.any[t >> 6] = mask != 0ull;
-    __syncthreads();
-    int r = 0;
-#pragma unroll
-    for (int w = 0; w < TP_WAVES; w++) r |= sh.any[w];
-    __syncthreads();                                        // sh.any has been read: the next call may write it
-    return r != 0;
-}
-// inclusive sum of v over lanes 0 .. t; *total = the block's sum
-__device__ inline int block_scan(WsShared& sh, int v, int* total) {
-    const int t = threadIdx.x;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if ((t & 63) >= o) x += y;
-    }
-    if ((t & 63) == 63) sh.wsum[t >> 6] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < TP_WAVES; w++) {
-        base += w < (t >> 6) ? sh.wsum[w] : 0;
-        tot += sh.wsum[w];
-    }
-    __syncthreads();                                        // sh.wsum has been read
-    *total = tot;
-    return base + x;
-}
-// the smallest (d, v) of the lanes' keys in the order key_less; a lane without a key passes (INFINITY, TP_NONE)
-__device__ inline void block_argmin(WsShared& sh, double* d, int* v) {
-    const int t = threadIdx.x;
-    double bd = *d;
-    int bv = *v;
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o);
-        const int ov = __shfl_xor(bv, o);
-        if (key_less(od, ov, bd, bv)) { bd = od; bv = ov; }
-    }
-    if ((t & 63) == 0) { sh.red_d[t >> 6] = bd; sh.red_v[t >> 6] = bv; }
-    __syncthreads();
-    bd = sh.red_d[0]; bv = sh.red_v[0];
-#pragma unroll
-    for (int w = 1; w < TP_WAVES; w++)
-        if (key_less(sh.red_d[w], sh.red_v[w], bd, bv)) { bd = sh.red_d[w]; bv = sh.red_v[w]; }
-    __syncthreads();                                        // sh.red_* have been read
-    *d = bd;
-    *v = bv;
-}
 // the edge a -> a + D of S sub-segments, dealt to the lanes in chunks of TP_BLOCK: free when every sub-segment separates
 __device__ inline bool block_edge_free(WsShared& sh, const double* a, const double (&D)[3], int S, double buf, const double* s_obs, int O) {
     bool hit = false;
     for (int s = threadIdx.x; s < S; s += TP_BLOCK) hit = hit || !ws_sub_free(a, D, s, S, buf, s_obs, 0, O);
-    return !block_any(sh, hit);
+    return !block_any(sh.any, hit);
 }
 
 // grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The tree of world w: nodes [w][max_nodes][3], parent / node_cost / node_len [w][max_nodes].
@@ -200,7 +155,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
         const double h[3] = {buf, buf, buf};
         for (int o = t; o < O; o += TP_BLOCK) hit = hit || !ws_box_free(start, h, s_obs, o, o + 1);
     }
-    if (!block_any(sh, hit)) {
+    if (!block_any(sh.any, hit)) {
         if (t < 3) nx[t] = pick3(start, t);
         if (t == 0) { par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0; }
         cnt = 1;
@@ -234,7 +189,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                 const double d2 = ws_diff(nx + (size_t)c * 3, qr, D);
                 if (key_less(d2, c, acc, v)) { acc = d2; v = c; }
             }
-            block_argmin(sh, &acc, &v);
+            block_argmin(sh.keys, &acc, &v);
             if (acc == 0.0) continue;
             {
                 const double xv[3] = {nx[(size_t)v * 3], nx[(size_t)v * 3 + 1], nx[(size_t)v * 3 + 2]};
@@ -249,7 +204,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                 if (c < cnt && (c == v || ws_diff(nx + (size_t)c * 3, qn, D) <= rr2)) mine |= 1u << k;
             }
             int C;
-            const int rank0 = block_scan(sh, __popc(mine), &C) - __popc(mine);
+            const int rank0 = block_scan(sh.sums, __popc(mine), &C) - __popc(mine);
             // ---- edge tests, TP_BLOCK candidates to a round: a flat list of (candidate, sub-segment) items across the lanes
             for (int r0 = 0; r0 < C; r0 += TP_BLOCK) {
                 const int Cr = C - r0 < TP_BLOCK ? C - r0 : TP_BLOCK;
@@ -262,10 +217,10 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                 int S = 0;
                 if (t < Cr) S = ws_segments(sqrt(ws_diff(nx + (size_t)c * 3, qn, D)), ar.edge_step);
                 int T;
-                sh.end[t] = block_scan(sh, S, &T);
+                sh.end[t] = block_scan(sh.sums, S, &T);
                 __syncthreads();
-                // a short list gives each item G = min(O, TP_BLOCK / T) lanes, lane g of them with the obstacles [g O / G, (g + 1) O / G): a sub-segment
-                // is free iff it is free of every obstacle, so the verdict is the same and the longest lane's work shrinks from O obstacles to O / G
+                // a short list gives each item G = min(O, TP_BLOCK / T) lanes, lane g of them with the obstacles [g O / G, (g + 1) O / G):
+                // tree_block.h's obstacle_split, which says why it is sound, inline
                 int G = 1;
                 if (2 * T <= TP_BLOCK && O > 1) G = TP_BLOCK / T < O ? TP_BLOCK / T : O;
                 const int per = TP_BLOCK / G, g = t % G, o0 = (g * O) / G, o1 = ((g + 1) * O) / G;
@@ -296,7 +251,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                 const double key = ncost[c] + sqrt(ws_diff(nx + (size_t)c * 3, qn, D));
                 if (key_less(key, c, pk, p)) { pk = key; p = c; }
             }
-            block_argmin(sh, &pk, &p);
+            block_argmin(sh.keys, &pk, &p);
             if (p == TP_NONE) continue;                     // (no candidate is free: no flag is set)
             const double d_p = sqrt(ws_diff(nx + (size_t)p * 3, qn, D)), cost_qn = ncost[p] + d_p;
             // ---- rewire: each free candidate decides for itself, on the costs as they stand; the flags are cleared for the next iteration
@@ -313,7 +268,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
             if (t == 0) { par[cnt] = p; nlen[cnt] = d_p; ncost[cnt] = cost_qn; }
             cnt++;
             int rewired;
-            block_scan(sh, mine_rewired, &rewired);         // (its barriers: the new node, the parents and the lengths are written)
+            block_scan(sh.sums, mine_rewired, &rewired);         // (its barriers: the new node, the parents and the lengths are written)
             rewires += rewired;
             // ---- cost re-derivation: cost_k = cost_parent(k) + len_k in passes, each reading the pass before, until a pass changes nothing
             for (int pass = 0; rewired > 0 && pass < cnt; pass++) {
@@ -334,7 +289,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                     const int c = t + k * TP_BLOCK;
                     if (c < cnt && par[c] >= 0) ncost[c] = nv[k];
                 }
-                if (!block_any(sh, changed)) break;         // (its barriers: the costs of this pass are written)
+                if (!block_any(sh.any, changed)) break;         // (its barriers: the costs of this pass are written)
             }
         }
         __syncthreads();
@@ -350,8 +305,8 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                 if (key_less(key, c, bk, bi)) { bk = key; bi = c; }
             }
         }
-        block_argmin(sh, &bk, &bi);
-        block_argmin(sh, &ba, &ai);
+        block_argmin(sh.keys, &bk, &bi);
+        block_argmin(sh.keys, &ba, &ai);
         status = bi != TP_NONE ? ARMOUR_WS_REACHED : ARMOUR_WS_PARTIAL;
         const int best = bi != TP_NONE ? bi : ai;
         {
@@ -516,32 +471,30 @@ void plan_world_host(const WsArgs& ar, int w, const double* obs, double* nx, int
     }
 }
 
-// the argument rules of both entries, before a device is touched; fills ar (the caller's pointers)
-int check_args(const char* who, const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
-               const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step, double rewire_radius,
-               double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status,
-               int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path, int32_t* count,
-               double* nodes, int32_t* parent, double* node_cost, WsArgs* ar) {
-    if (!lb || !ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
-    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
-    if (W > 0 && (!starts || !goals || !seeds || !status || !iterations || !points || !rewires || !chain_kept || !path_cost || !goal_dist)) {
+// the argument rules of both entries, before a device is touched, on ar as the entry filled it; fills ar.lb / ar.ub and drops a chain's
+// length and counts when there is no chain
+int check_args(const char* who, WsCall* ar) {
+    const int32_t W = ar->W, O = ar->O, max_init = ar->max_init;
+    const double step = ar->step, edge_step = ar->edge_step, rewire_radius = ar->rewire_radius;
+    if (!ar->box_lb || !ar->box_ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, ar->obstacles));
+    if (W > 0 && (!ar->starts || !ar->goals || !ar->seeds || !ar->status || !ar->iterations || !ar->points || !ar->rewires || !ar->chain_kept || !ar->path_cost || !ar->goal_dist)) {
         armour_set_error("%s: null argument", who);
         return ARMOUR_EINVAL;
     }
-    if (max_nodes < 1 || max_nodes > ARMOUR_WS_MAX_NODES || max_iterations < 0 || max_iterations > ARMOUR_TREE_MAX_ITERATIONS || max_points < 0) {
-        armour_set_error("%s: max_nodes = %d (1..%d), max_iterations = %d (0..%d), max_points = %d", who, max_nodes, ARMOUR_WS_MAX_NODES, max_iterations,
-                         ARMOUR_TREE_MAX_ITERATIONS, max_points);
+    if (ar->max_nodes < 1 || ar->max_nodes > ARMOUR_WS_MAX_NODES || ar->max_iterations < 0 || ar->max_iterations > ARMOUR_TREE_MAX_ITERATIONS || ar->max_points < 0) {
+        armour_set_error("%s: max_nodes = %d (1..%d), max_iterations = %d (0..%d), max_points = %d", who, ar->max_nodes, ARMOUR_WS_MAX_NODES, ar->max_iterations,
+                         ARMOUR_TREE_MAX_ITERATIONS, ar->max_points);
         return ARMOUR_EINVAL;
     }
-    const double reals[6] = {step, edge_step, rewire_radius, goal_rate, buffer, goal_tol};
-    if (!finite_all(reals, 6) || !(step > 0.0) || !(edge_step > 0.0) || rewire_radius < 0.0 || buffer < 0.0 || goal_tol < 0.0 || goal_rate < 0.0 || goal_rate > 1.0) {
+    const double reals[6] = {step, edge_step, rewire_radius, ar->goal_rate, ar->buffer, ar->goal_tol};
+    if (!finite_all(reals, 6) || !(step > 0.0) || !(edge_step > 0.0) || rewire_radius < 0.0 || ar->buffer < 0.0 || ar->goal_tol < 0.0 || ar->goal_rate < 0.0 || ar->goal_rate > 1.0) {
         armour_set_error("%s: step = %g, edge_step = %g (> 0), rewire_radius = %g, buffer = %g, goal_tol = %g (>= 0), goal_rate = %g (0..1)", who, step, edge_step,
-                         rewire_radius, buffer, goal_tol, goal_rate);
+                         rewire_radius, ar->buffer, ar->goal_tol, ar->goal_rate);
         return ARMOUR_EINVAL;
     }
-    for (int j = 0; j < 3; j++)
-        if (!std::isfinite(lb[j]) || !std::isfinite(ub[j]) || !(lb[j] <= ub[j])) { armour_set_error("%s: sampling box [%g, %g] of axis %d", who, lb[j], ub[j], j); return ARMOUR_EINVAL; }
-    if (!finite_all(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(starts, (size_t)W * 3) || !finite_all(goals, (size_t)W * 3)) {
+    ARMOUR_TRY(armour_check_box(who, "sampling box", "axis", 3, ar->box_lb, ar->box_ub));
+    if (!finite_all(ar->obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(ar->starts, (size_t)W * 3) || !finite_all(ar->goals, (size_t)W * 3)) {
         armour_set_error("%s: a start, a goal or an obstacle is not finite", who);
         return ARMOUR_EINVAL;
     }
@@ -549,14 +502,14 @@ int check_args(const char* who, const double* lb, const double* ub, int32_t W, i
         armour_set_error("%s: step = %g, rewire_radius = %g: more than %d sub-segments of edge_step %g", who, step, rewire_radius, ARMOUR_WS_MAX_SEGMENTS, edge_step);
         return ARMOUR_EINVAL;
     }
-    if (init) {
-        if (max_init < 1 || (W > 0 && !init_count)) { armour_set_error("%s: max_init = %d (>= 1 with init), init_count", who, max_init); return ARMOUR_EINVAL; }
+    if (ar->init) {
+        if (max_init < 1 || (W > 0 && !ar->init_count)) { armour_set_error("%s: max_init = %d (>= 1 with init), init_count", who, max_init); return ARMOUR_EINVAL; }
         for (int32_t w = 0; w < W; w++) {
-            const int32_t c = init_count[w];
+            const int32_t c = ar->init_count[w];
             if (c < 0 || c > max_init) { armour_set_error("%s: init_count[%d] = %d (0..%d)", who, w, c, max_init); return ARMOUR_EINVAL; }
-            const double* x = init + (size_t)w * max_init * 3;
+            const double* x = ar->init + (size_t)w * max_init * 3;
             if (!finite_all(x, (size_t)c * 3)) { armour_set_error("%s: world %d's chain is not finite", who, w); return ARMOUR_EINVAL; }
-            const double* prev = starts + (size_t)w * 3;
+            const double* prev = ar->starts + (size_t)w * 3;
             for (int32_t k = 0; k < c; prev = x + (size_t)k * 3, k++) {
                 double D[3];
                 const double len = std::sqrt(ws_diff(prev, x + (size_t)k * 3, D));
@@ -566,21 +519,11 @@ int check_args(const char* who, const double* lb, const double* ub, int32_t W, i
                 }
             }
         }
+    } else {
+        ar->max_init = 0;
+        ar->init_count = nullptr;
     }
-    std::memset(ar, 0, sizeof(*ar));
-    for (int j = 0; j < 3; j++) { ar->lb[j] = lb[j]; ar->ub[j] = ub[j]; }
-    ar->step = step; ar->edge_step = edge_step; ar->rewire_radius = rewire_radius; ar->goal_rate = goal_rate; ar->buffer = buffer; ar->goal_tol = goal_tol;
-    ar->O = O; ar->max_iterations = max_iterations; ar->max_nodes = max_nodes; ar->max_points = max_points; ar->max_init = init ? max_init : 0;
-    ar->obstacles = obstacles; ar->starts = starts; ar->goals = goals; ar->init = init; ar->init_count = init ? init_count : nullptr; ar->seeds = seeds;
-    ar->status = status; ar->iterations = iterations; ar->points = points; ar->rewires = rewires; ar->chain_kept = chain_kept; ar->count = count;
-    ar->parent = parent; ar->path_cost = path_cost; ar->goal_dist = goal_dist; ar->path = path; ar->nodes = nodes; ar->node_cost = node_cost;
-    return ARMOUR_OK;
-}
-
-// the roadmap entries' capacity rule: points [W] is complete; a path longer than max_points was not written
-int check_capacity(const char* who, int32_t W, const int32_t* points, const double* path, int32_t max_points) {
-    for (int32_t w = 0; path && w < W; w++)
-        if (points[w] > max_points) { armour_set_error("%s: world %d's path of %d points, room for %d", who, w, points[w], max_points); return ARMOUR_ECAPACITY; }
+    for (int j = 0; j < 3; j++) { ar->lb[j] = ar->box_lb[j]; ar->ub[j] = ar->box_ub[j]; }
     return ARMOUR_OK;
 }
 
@@ -593,19 +536,21 @@ extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int3
                                         double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost,
                                         double* margin) {
     const char* who = "armour_ws_tree_plan_host";
-    WsArgs ar;
-    ARMOUR_TRY(check_args(who, lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
-                          max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent,
-                          node_cost, &ar));
+    WsCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds; ar.max_init = max_init;
+    ar.init = init; ar.init_count = init_count; ar.step = step; ar.edge_step = edge_step; ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate;
+    ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points; ar.status = status;
+    ar.iterations = iterations; ar.points = points; ar.rewires = rewires; ar.chain_kept = chain_kept; ar.path_cost = path_cost; ar.goal_dist = goal_dist;
+    ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent; ar.node_cost = node_cost;
+    ARMOUR_TRY(check_args(who, &ar));
     const size_t cap = (size_t)max_nodes;
-    std::vector<double> obs((size_t)O * RM_OBS_STRIDE), own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);   // staged as the kernel stages them
+    std::vector<double> own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);
     std::vector<int32_t> own_parent(parent ? 0 : cap);
-    for (int32_t w = 0; w < W; w++) {
-        stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
-        plan_world_host(ar, w, obs.data(), nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
+    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) {
+        plan_world_host(ar, w, obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
                         node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr);
-    }
-    return check_capacity(who, W, points, path, max_points);
+    });
+    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
 }
 
 extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
@@ -614,19 +559,24 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
                                    int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
                                    double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* ms) {
     const char* who = "armour_ws_tree_plan";
-    WsArgs ar;
-    ARMOUR_TRY(check_args(who, lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
-                          max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent,
-                          node_cost, &ar));
+    WsCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds; ar.max_init = max_init;
+    ar.init = init; ar.init_count = init_count; ar.step = step; ar.edge_step = edge_step; ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate;
+    ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points; ar.status = status;
+    ar.iterations = iterations; ar.points = points; ar.rewires = rewires; ar.chain_kept = chain_kept; ar.path_cost = path_cost; ar.goal_dist = goal_dist;
+    ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent; ar.node_cost = node_cost;
+    ARMOUR_TRY(check_args(who, &ar));
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
     if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ws_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
     const size_t cap = (size_t)max_nodes, rows = (size_t)W * cap, path_len = path ? (size_t)W * max_points * 3 : 0;
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_starts, d_goals, d_init, d_nodes, d_cost, d_len, d_path, d_real;   // d_real: path_cost | goal_dist [W] each
+    DevBuf<double> d_obs, d_starts, d_goals, d_init, d_nodes, d_cost, d_len, d_path;
     DevBuf<uint64_t> d_seeds;
-    DevBuf<int32_t> d_init_count, d_out, d_parent;          // d_out: status | iterations | points | rewires | chain_kept | count [W] each
+    DevBuf<int32_t> d_init_count, d_parent;
+    DevColumns<int32_t> out;                                // status | iterations | points | rewires | chain_kept | count [W] each
+    DevColumns<double> real;                                // path_cost | goal_dist [W] each
     ARMOUR_TRY(st.create());
     ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
     ARMOUR_TRY(d_starts.upload(starts, (size_t)W * 3, st));
@@ -640,32 +590,29 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
     ARMOUR_TRY(d_cost.reserve(rows));
     ARMOUR_TRY(d_len.reserve(rows));
     ARMOUR_TRY(d_parent.reserve(rows));
-    ARMOUR_TRY(d_out.reserve((size_t)6 * W));
-    ARMOUR_TRY(d_real.reserve((size_t)2 * W));
+    ARMOUR_TRY(out.reserve(6, (size_t)W));
+    ARMOUR_TRY(real.reserve(2, (size_t)W));
     if (path) ARMOUR_TRY(d_path.reserve(path_len));
-    WsArgs dev = ar;
+    WsArgs dev = ar;                                        // (the kernel's part)
     dev.obstacles = d_obs; dev.starts = d_starts; dev.goals = d_goals; dev.seeds = d_seeds;
     dev.init = init ? d_init.p : nullptr; dev.init_count = init ? d_init_count.p : nullptr;
-    dev.status = d_out; dev.iterations = d_out + W; dev.points = d_out + 2 * (size_t)W; dev.rewires = d_out + 3 * (size_t)W;
-    dev.chain_kept = d_out + 4 * (size_t)W; dev.count = d_out + 5 * (size_t)W;
-    dev.path_cost = d_real; dev.goal_dist = d_real + W;
+    dev.status = out.column(0); dev.iterations = out.column(1); dev.points = out.column(2); dev.rewires = out.column(3);
+    dev.chain_kept = out.column(4); dev.count = out.column(5);
+    dev.path_cost = real.column(0); dev.goal_dist = real.column(1);
     dev.parent = d_parent; dev.nodes = d_nodes; dev.node_cost = d_cost; dev.node_len = d_len; dev.path = path ? d_path.p : nullptr;
     ARMOUR_TRY(ev.record_start(st));
     hipLaunchKernelGGL(ws_tree_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, dev);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
-    std::vector<int32_t> out((size_t)6 * W);
-    std::vector<double> real((size_t)2 * W);
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(real.data(), d_real, real.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    ARMOUR_TRY(out.fetch(st));
+    ARMOUR_TRY(real.fetch(st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    int32_t* const ints[5] = {status, iterations, points, rewires, chain_kept};
-    for (int k = 0; k < 5; k++) std::memcpy(ints[k], out.data() + k * (size_t)W, (size_t)W * sizeof(int32_t));
-    const int32_t* h_count = out.data() + 5 * (size_t)W;
-    if (count) std::memcpy(count, h_count, (size_t)W * sizeof(int32_t));
-    std::memcpy(path_cost, real.data(), (size_t)W * sizeof(double));
-    std::memcpy(goal_dist, real.data() + W, (size_t)W * sizeof(double));
+    int32_t* const ints[6] = {status, iterations, points, rewires, chain_kept, count};
+    for (int k = 0; k < 6; k++) out.copy_out(k, ints[k]);
+    const int32_t* h_count = out.fetched(5);
+    real.copy_out(0, path_cost);
+    real.copy_out(1, goal_dist);
     // the trees and the paths: only the rows that were written come back (the rest of the caller's arrays is left as it was)
     for (int32_t w = 0; w < W; w++) {
         const size_t c = (size_t)h_count[w], row = (size_t)w * cap;
@@ -676,5 +623,5 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
             HIPCHK(hipMemcpyAsync(path + (size_t)w * max_points * 3, d_path + (size_t)w * max_points * 3, (size_t)points[w] * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
-    return check_capacity(who, W, points, path, max_points);
+    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
 }

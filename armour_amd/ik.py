@@ -26,14 +26,11 @@ NONE_CONVERGED, FOUND, ALL_BLOCKED = _lib.IK_NONE_CONVERGED, _lib.IK_FOUND, _lib
 CONVERGED_BIT, FREE_BIT = 1, 2
 
 
-class IKSolutions:
+class IKSolutions(_lib.Result):
     """What solve_ik returns: status [N] (NONE_CONVERGED / FOUND / ALL_BLOCKED), best [N] (the picked seed, -1 without one), q [N,n] (the
     picked configuration; NaN rows where status != FOUND), ms (device time of the launch; 0 on the host), margin [N] (host only, else None:
     the smallest |clearance| over the target's converged items), and with details=True the per-item arrays q_all [N,S,n], err [N,S],
     iterations [N,S], flags [N,S] (bit 0 converged, bit 1 free)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def _tool(tool):
@@ -68,12 +65,7 @@ def solve_ik(robot, targets, q_ref, obstacles=None, world=None, seeds=0, S=32, t
     tg = np.ascontiguousarray(np.asarray(targets, dtype=np.float64).reshape(-1, 3))
     N = tg.shape[0]
     ref = np.ascontiguousarray(np.broadcast_to(np.asarray(q_ref, dtype=np.float64), (N, n)))
-    if obstacles is None:
-        obs = np.zeros((0, 0, 12))
-    else:
-        obs = np.asarray(obstacles, dtype=np.float64)
-        obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-    W, O = obs.shape[0], obs.shape[1]
+    obs, W, O = _lib.as_worlds(np.zeros((0, 0, 12)) if obstacles is None else obstacles)
     if world is None:
         world = np.full(N, -1) if W == 0 else (np.arange(N) if W == N else np.zeros(N))
     wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, dtype=np.int32), (N,)))

@@ -61,12 +61,11 @@ def _audit(entries, lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tu
 def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, clearance=False, host=False):
     """P pieces in one call.  obstacles [W,O,12] (or [O,12]: W = 1); world_of_piece [P]; q0 / qd0 / qdd0 / k [P,n]; k_range [n]; ta / tb [P] or
     scalars; tube [P,n], [n] or None (zeros): the per-joint radius about the plan that is audited with it."""
-    obs = np.asarray(obstacles, dtype=np.float64)
-    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
+    obs, W, O = _lib.as_worlds(obstacles)
 
     def lead(P):
         wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
-        return [obs.shape[0], obs.shape[1], _dp(obs) if obs.size else None, P, wp.ctypes.data_as(C.POINTER(C.c_int32))]
+        return [W, O, _dp(obs) if obs.size else None, P, wp.ctypes.data_as(C.POINTER(C.c_int32))]
     return _audit(("armour_path_audit", "armour_path_audit_host"), lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, clearance, host)
 
 

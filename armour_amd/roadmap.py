@@ -104,9 +104,7 @@ class Roadmap:
     def check(self, obstacles, clearance=False):
         """obstacles [W,O,12] (or [O,12]: W = 1) -> dict node_free [W,N] bool, edge_free [W,E] bool, ms (device time of the launch),
         and node_clearance [W,N] when `clearance`."""
-        obs = np.asarray(obstacles, dtype=np.float64)
-        obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-        W, O = obs.shape[0], obs.shape[1]
+        obs, W, O = _lib.as_worlds(obstacles)
         nf = np.zeros((W, self.N), dtype=np.uint8)
         ef = np.zeros((W, self.E), dtype=np.uint8)
         cl = np.zeros((W, self.N)) if clearance else None

@@ -30,13 +30,10 @@ NOT_FOUND, FOUND, START_BLOCKED, GOAL_BLOCKED, TREE_FULL = (_lib.TREE_NOT_FOUND,
                                                             _lib.TREE_FULL)
 
 
-class TreePlans:
+class TreePlans(_lib.Result):
     """What plan_trees returns: status / iterations [W], paths (a list; [P,n] where status == FOUND, else None), ms (device time of the
     launch; 0 on the host), margin [W] (host only, else None: the smallest |clearance| that decided the run), and with trees=True count
     [W,2], nodes [W,2,max_nodes,n], parent [W,2,max_nodes] (rows past count are zero)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def sampling_box(robot, continuous=None):
@@ -54,9 +51,7 @@ def plan_trees(robot, obstacles, starts, goals, seeds, lb=None, ub=None, continu
     sampling_box).  host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
     L = _lib.load()
     n = robot.num_factors
-    obs = np.asarray(obstacles, dtype=np.float64)
-    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-    W, O = obs.shape[0], obs.shape[1]
+    obs, W, O = _lib.as_worlds(obstacles)
     s = np.ascontiguousarray(starts, dtype=np.float64).reshape(W, n)
     g = np.ascontiguousarray(goals, dtype=np.float64).reshape(W, n)
     sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (W,)))
@@ -85,13 +80,10 @@ def plan_trees(robot, obstacles, starts, goals, seeds, lb=None, ub=None, continu
     return out
 
 
-class ShortPaths:
+class ShortPaths(_lib.Result):
     """What shortcut_paths returns: status [W] (SHORTCUT_OK / SHORTCUT_INVALID), paths (a list; [P,n] where OK, else None), first_bad [W]
     (the first edge that is not free; -1 where OK), passes_done [W], length_in / length_out [W], ms (device time of the launch; 0 on the
     host) and margin [W] (host only, else None: the smallest |clearance| over the checks made)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def shortcut_paths(robot, obstacles, paths, edge_step=0.05, passes=2, continuous=None, host=False):
@@ -100,9 +92,7 @@ def shortcut_paths(robot, obstacles, paths, edge_step=0.05, passes=2, continuous
     host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
     L = _lib.load()
     n = robot.num_factors
-    obs = np.asarray(obstacles, dtype=np.float64)
-    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-    W, O = obs.shape[0], obs.shape[1]
+    obs, W, O = _lib.as_worlds(obstacles)
     ps = [np.asarray(p, dtype=np.float64).reshape(-1, n) for p in paths]
     if len(ps) != W:
         raise ValueError(f"{len(ps)} paths for {W} worlds")
@@ -208,14 +198,10 @@ def _waypoints(hl, qs, lookaheads):
     return out, ms
 
 
-def tree_hlps(worlds, robot, seed=0, host=False, batched=True, shortcut=0, mode="new", **plan_options):
-    """`worlds` as trials.run_trials takes them ([(name, problem)]) -> the factory (i, world) -> TreeHLP that run_trials(hlp=...) accepts
-    (world i's obstacles padded to the worlds' largest count, its goal, the trial's seed).  With batched (the default) the factory also
-    carries get_waypoints(indices, qs, lookaheads), which serves ALL live worlds of an iteration with at most three launches -- one
-    armour_path_shortcut call for the worlds that hold a path (mode='seed'), ONE armour_tree_plan call for the rest, one
-    armour_path_shortcut call for the new paths (shortcut > 0) -- make.last_ms is their sum; the seeds are the per-world objects'
-    (call_seed), so the waypoints are the same either way.  shortcut / mode: TreeHLP's.  plan_options go to plan_trees (step, edge_step,
-    max_iterations, max_nodes, lb, ub, continuous)."""
+def hlp_factory(worlds, build, waypoints, batched):
+    """What tree_hlps and ws_planner.workspace_hlps return: the factory make(i, world) -> build(i, world i's obstacles padded to the worlds'
+    largest count, its goal), with make.hlps (the objects made so far) and, when batched, make.get_waypoints(indices, qs, lookaheads) =
+    waypoints(the objects of `indices`, made on demand, qs, lookaheads)[0]; make.last_ms is that call's second result."""
     probs = [p for _, p in worlds]
     obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
     O = max([o.shape[0] for o in obs] + [1])
@@ -224,15 +210,27 @@ def tree_hlps(worlds, robot, seed=0, host=False, batched=True, shortcut=0, mode=
     made = {}
 
     def make(i, world):
-        made[i] = TreeHLP(robot, obstacles[i], goals[i], seed=seed, world=i, host=host, shortcut=shortcut, mode=mode, **plan_options)
+        made[i] = build(i, obstacles[i], goals[i])
         return made[i]
 
     def get_waypoints(indices, qs, lookaheads):
         hl = [made[int(i)] if int(i) in made else make(int(i), None) for i in indices]
-        out, make.last_ms = _waypoints(hl, qs, lookaheads)
+        out, make.last_ms = waypoints(hl, qs, lookaheads)
         return out
 
     make.hlps = made
     if batched:
         make.get_waypoints = get_waypoints
     return make
+
+
+def tree_hlps(worlds, robot, seed=0, host=False, batched=True, shortcut=0, mode="new", **plan_options):
+    """`worlds` as trials.run_trials takes them ([(name, problem)]) -> the factory (i, world) -> TreeHLP that run_trials(hlp=...) accepts
+    (world i's obstacles padded to the worlds' largest count, its goal, the trial's seed).  With batched (the default) the factory also
+    carries get_waypoints(indices, qs, lookaheads), which serves ALL live worlds of an iteration with at most three launches -- one
+    armour_path_shortcut call for the worlds that hold a path (mode='seed'), ONE armour_tree_plan call for the rest, one
+    armour_path_shortcut call for the new paths (shortcut > 0) -- make.last_ms is their sum; the seeds are the per-world objects'
+    (call_seed), so the waypoints are the same either way.  shortcut / mode: TreeHLP's.  plan_options go to plan_trees (step, edge_step,
+    max_iterations, max_nodes, lb, ub, continuous)."""
+    return hlp_factory(worlds, lambda i, obstacles, goal: TreeHLP(robot, obstacles, goal, seed=seed, world=i, host=host, shortcut=shortcut, mode=mode, **plan_options),
+                       _waypoints, batched)

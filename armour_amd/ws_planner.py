@@ -21,8 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import _dp, check
 from . import ik
-from .scenes import pad_obstacles
-from .tree_planner import call_seed
+from .tree_planner import call_seed, hlp_factory
 
 PARTIAL, REACHED, START_BLOCKED = _lib.WS_PARTIAL, _lib.WS_REACHED, _lib.WS_START_BLOCKED
 
@@ -33,14 +32,11 @@ STEP, EDGE_STEP, REWIRE_RADIUS, GOAL_RATE, GOAL_TOL = 0.1, 0.01, 0.2, 0.1, 0.01
 MAX_ITERATIONS, MAX_NODES = 1000, 1024
 
 
-class WorkspacePlans:
+class WorkspacePlans(_lib.Result):
     """What plan_workspace_trees returns: status [W] (PARTIAL / REACHED / START_BLOCKED), iterations / rewires / chain_kept / count [W],
     path_cost / goal_dist [W], paths (a list; [P,3] from the start to the best node, None where the start is blocked), ms (device time of
     the launch; 0 on the host), margin [W] (host only, else None: the smallest |clearance| that decided the run), and with trees=True nodes
     [W,max_nodes,3], parent [W,max_nodes], node_cost [W,max_nodes] (rows past count are zero)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def workspace_box(robot, tool=None):
@@ -60,9 +56,7 @@ def plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, step=STEP, edg
     chain [C,3] offered before the loop (the reference's 'seed' mode).  max_points: the path rows to reserve (default: max_nodes, which a
     path cannot exceed).  host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
     L = _lib.load()
-    obs = np.asarray(obstacles, dtype=np.float64)
-    obs = np.ascontiguousarray(obs.reshape((1,) + obs.shape) if obs.ndim == 2 else obs)
-    W, O = obs.shape[0], obs.shape[1]
+    obs, W, O = _lib.as_worlds(obstacles)
     s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(W, 3))
     g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(W, 3))
     sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (W,)))
@@ -210,28 +204,12 @@ def workspace_hlps(worlds, robot, seed=0, lookahead=0.1, mode="new", ik_referenc
     the goal configuration.  The seeds are the per-world objects' (tree_planner.call_seed), so the waypoints are the same either way.
     lookahead is in METRES of end-effector travel (default: the reference scripts' 0.1): the trials' own `lookahead` values are distances in
     joint space and are ignored, per world and batched alike.  mode / ik_reference / ik_options / options: WorkspaceTreeHLP's."""
-    probs = [p for _, p in worlds]
-    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
-    O = max([o.shape[0] for o in obs] + [1])
-    obstacles = np.stack([pad_obstacles(o, O) for o in obs]) if obs else np.zeros((0, O, 12))
-    goals = [np.asarray(p["goal"], dtype=np.float64) for p in probs]
-    made = {}
     lookahead = float(lookahead)
 
     class _Metres(WorkspaceTreeHLP):
         def get_waypoint(self, q_cur, _joint_space_lookahead):
             return _waypoints([self], [q_cur], [lookahead])[0][0]
 
-    def make(i, world):
-        made[i] = _Metres(robot, obstacles[i], goals[i], seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference, ik_options=ik_options, **options)
-        return made[i]
-
-    def get_waypoints(indices, qs, lookaheads):
-        hl = [made[int(i)] if int(i) in made else make(int(i), None) for i in indices]
-        out, make.last_ms = _waypoints(hl, qs, [lookahead] * len(hl))
-        return out
-
-    make.hlps = made
-    if batched:
-        make.get_waypoints = get_waypoints
-    return make
+    return hlp_factory(worlds, lambda i, obstacles, goal: _Metres(robot, obstacles, goal, seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference,
+                                                                  ik_options=ik_options, **options),
+                       lambda hl, qs, _joint_space_lookaheads: _waypoints(hl, qs, [lookahead] * len(hl)), batched)

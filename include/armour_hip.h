@@ -616,6 +616,23 @@ int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, const doubl
 int armour_debug_get_row_lists(ArmourPlanner* h, int32_t which, int32_t* rows, int32_t* count, int32_t* aux, int32_t* aux_count,
                                int64_t* pack_off, double* packed, int64_t packed_capacity, int64_t* packed_total);
 
+/* ---- test hooks: the block steps under the per-world planner kernels (armour_tree_plan, armour_path_shortcut, armour_ik, armour_ws_tree_plan) ---- */
+/* armour_debug_block_steps: ONE block of 256 lanes runs each cooperative step once on the caller's per-lane values (all [256]) and touches no
+ * planner state.  Lane t holds the key (d[t], v[t]) -- a lane without a key passes (+inf, INT32_MAX) --, the flag flag[t] != 0 and the term n[t].
+ *   min_d, min_v  the smallest key in the order "d, then v"
+ *   first         the smallest lane with its flag set, INT32_MAX when there is none;   any   1 when some lane has it set, else 0
+ *   sums [256]    sums[t] = n[0] + ... + n[t];   total = sums[255]
+ * ARMOUR_EINVAL on a null pointer, ARMOUR_EDEVICE without a device.
+ * armour_debug_block_split (host only): how `items` >= 1 work items share the 256 lanes when each is tested against O obstacles:
+ * split [256][4] = {G, per, o0, o1} of lane t -- G = min(O, 256 / items) lanes to an item when allowed != 0, 2 items <= 256 and O > 1, else 1;
+ * per = 256 / G items at a time; lane t is lane g = t mod G of item t / G and takes the obstacles [o0, o1) = [g O / G, (g + 1) O / G).
+ * armour_debug_block_owner (host only): end [n] ascending, n <= 256, end[k] = one past the last work item of candidate k;
+ * owner[i] = the number of ends <= item[i] = the first candidate whose end exceeds item[i], n when there is none. */
+int armour_debug_block_steps(const double* d, const int32_t* v, const int32_t* flag, const int32_t* n, double* min_d, int32_t* min_v, int32_t* first,
+                             int32_t* any, int32_t* sums, int32_t* total);
+int armour_debug_block_split(int32_t items, int32_t O, int32_t allowed, int32_t* split);
+int armour_debug_block_owner(const int32_t* end, int32_t n, int32_t count, const int32_t* item, int32_t* owner);
+
 /* ---- roadmap high-level planner: a joint-space roadmap checked against worlds' obstacles on the device ---- */
 /* What the reference's sample-based HLP does with its prebuilt collision_checker (kinova_samplebased_HLP_realtime): node feasibility,
  * node clearance and the collision-free subset of a roadmap's edges, per world; then a search of the free graph for waypoints.
