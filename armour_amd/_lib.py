@@ -104,7 +104,7 @@ class ArmourTrackOptions(C.Structure):
     _fields_ = [("controller", C.c_int32), ("record_every", C.c_int32), ("steps_per_launch", C.c_int32), ("reserved0", C.c_int32),
                 ("Kr", C.c_double * MAXF), ("alpha", C.c_double), ("V_max", C.c_double), ("r_norm_threshold", C.c_double),
                 ("model_uncertainty", C.c_double), ("dt", C.c_double), ("t0", C.c_double), ("t1", C.c_double), ("duration", C.c_double),
-                ("reserved", C.c_double * 4)]
+                ("althoff_Kp", C.c_double * 2), ("reserved", C.c_double * 2)]
 
 
 class ArmourTrackResult(C.Structure):
@@ -114,7 +114,7 @@ class ArmourTrackResult(C.Structure):
                 ("max_torque_ratio", C.c_double), ("first_violation_t", C.c_double)]
 
 
-TRACK_CTL_ROBUST, TRACK_CTL_NOMINAL, TRACK_CTL_NONE = 0, 1, 2   # ARMOUR_TRACK_CTL_*
+TRACK_CTL_ROBUST, TRACK_CTL_NOMINAL, TRACK_CTL_NONE, TRACK_CTL_ALTHOFF = 0, 1, 2, 4   # ARMOUR_TRACK_CTL_* (3 is unassigned)
 TRACK_LIMIT_TORQUE, TRACK_LIMIT_POSITION, TRACK_LIMIT_SPEED = 1, 2, 4   # ARMOUR_TRACK_LIMIT_*
 
 
@@ -176,7 +176,7 @@ EXPORTS = [
     "armour_robot_kinova_gen3_no_gripper", "armour_robot_kinova_gen3_gripper", "armour_robot_fetch", "armour_robot_fetch8", "armour_params_default", "armour_create", "armour_destroy",
     "armour_last_error", "armour_device_available", "armour_alloc_pinned", "armour_free_pinned", "armour_set_problems", "armour_set_problems_armtd", "armour_get_sizes",
     "armour_get_bounds", "armour_eval_f", "armour_eval_grad_f", "armour_eval_g_jac",
-    "armour_eval_g_jac_device", "armour_eval_g_jac_device_steps", "armour_prepare_steps", "armour_eval_g_jac_device_multi", "armour_desired_trajectory", "armour_robust_controller", "armour_check_feasible", "armour_get_torque_radius",
+    "armour_eval_g_jac_device", "armour_eval_g_jac_device_steps", "armour_prepare_steps", "armour_eval_g_jac_device_multi", "armour_desired_trajectory", "armour_robust_controller", "armour_althoff_controller", "armour_check_feasible", "armour_get_torque_radius",
     "armour_get_link_generators", "armour_get_link_centers", "armour_get_pz", "armour_get_table_sizes",
     "armour_solve_options_default", "armour_solve", "armour_debug_qp", "armour_debug_qp_box", "armour_debug_qp_elastic", "armour_debug_qp_device", "armour_debug_pz_op",
     "armour_get_hyperplanes", "armour_get_build_ms", "armour_get_build_info", "armour_p2_kernel_name", "armour_debug_load_tables",
@@ -271,6 +271,7 @@ def load():
     L.armour_eval_g_jac_device_multi.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     L.armour_desired_trajectory.argtypes = [C.c_int32, dp, dp, dp, dp, C.c_double, dp, C.c_double, dp, dp, dp]
     L.armour_robust_controller.argtypes = [C.POINTER(ArmourRobot), C.c_double, dp, C.c_double, C.c_double, C.c_double, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp]
+    L.armour_althoff_controller.argtypes = [C.POINTER(ArmourRobot), C.c_double, dp, dp, dp, dp, C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp]
     L.armour_check_feasible.argtypes = [vp, dp, ip]
     L.armour_solve_options_default.argtypes = [C.POINTER(ArmourSolveOptions)]
     L.armour_solve_options_default.restype = None

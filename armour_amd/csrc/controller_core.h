@@ -5,7 +5,8 @@
 //   rnea.cpp:6-96 / :98-185              passRNEA / passRNEA_Int
 //   robot_models.cpp:124-160, :176-255   conversion of the model file to CoM frames; the interval model (mass and
 //                                        inertia widened by +-eps, everything else a point interval)
-//   robust_controller.cpp:63-168         RobustController::update, ARMOUR method
+//   robust_controller.cpp:63-168         RobustController::update, ARMOUR method (robust_update)
+//   robust_controller.cpp:63-128         the same update, ALTHOFF method (althoff_update, at the end of this file)
 // The reference writes every class twice (double and Boost interval); here the scalar type is a template parameter
 // and both instantiations follow the same operation order (sums of products accumulate k = 0, 1, 2 as Eigen's
 // fixed-size products do).  Intervals round outward by one ulp per operation (the value nextafter gives), as the reach-set code does.
@@ -255,19 +256,27 @@ CTL_HD CTL_FLATTEN double robust_prepare(int n, const double* Kr, const double* 
     for (int i = 0; i < n; i++) r_norm += r[i] * r[i];
     return sqrt(r_norm);
 }
-// combine: the robust input from the nominal torque, the interval torque and (when |r| is above the threshold) the interval M r (:88-166).
-// Returns false if the nominal torque leaves the interval torque (the reference throws).  u = tau = u_nominal - v.
-CTL_HD CTL_FLATTEN bool robust_combine(int n, double alpha, double V_max, double r_norm_threshold, const double* r, double r_norm, const double* u_nominal,
-                           const Itv* u_int, const Itv* Mr, double* u, double* v_out) {
+// The interval check and the model-error bound both robust inputs start from (:94-108): phi_i = u_int_i - u_nominal_i, bound_i =
+// max(|phi_i.lo|, |phi_i.hi|); *bound_sq = sum of bound_i^2 in joint order.  Returns false if a nominal torque leaves its interval.
+CTL_HD CTL_FLATTEN bool torque_bound_sq(int n, const double* u_nominal, const Itv* u_int, double* bound_sq) {
     bool ok = true;
-    double bound_sq = 0.0;
+    double sq = 0.0;
     for (int i = 0; i < n; i++) {
         if (u_nominal[i] > u_int[i].hi || u_nominal[i] < u_int[i].lo) ok = false;
         const Itv phi = u_int[i] - Itv{u_nominal[i], u_nominal[i]};
         const double bnd = fmax(fabs(phi.lo), fabs(phi.hi));
-        bound_sq += bnd * bnd;
-        v_out[i] = 0.0;
+        sq += bnd * bnd;
     }
+    *bound_sq = sq;
+    return ok;
+}
+// combine: the robust input from the nominal torque, the interval torque and (when |r| is above the threshold) the interval M r (:88-166).
+// Returns false if the nominal torque leaves the interval torque (the reference throws).  u = tau = u_nominal - v.
+CTL_HD CTL_FLATTEN bool robust_combine(int n, double alpha, double V_max, double r_norm_threshold, const double* r, double r_norm, const double* u_nominal,
+                           const Itv* u_int, const Itv* Mr, double* u, double* v_out) {
+    double bound_sq;
+    const bool ok = torque_bound_sq(n, u_nominal, u_int, &bound_sq);
+    for (int i = 0; i < n; i++) v_out[i] = 0.0;
     if (r_norm > r_norm_threshold) {
         Itv V{0.0, 0.0};
         for (int i = 0; i < n; i++) V = V + (0.5 * r[i]) * Mr[i];
@@ -292,6 +301,35 @@ CTL_HD CTL_FLATTEN bool robust_update(const Model<double>& md, const Model<Itv>&
     rnea_dynamics(imd, k, q_d, qa_d, qa_dd, false, true, u_int);
     if (r_norm > r_norm_threshold) rnea_dynamics(imd, k, zero, zero, r, false, false, Mr);
     return robust_combine(n, alpha, V_max, r_norm_threshold, r, r_norm, u_nominal, u_int, Mr, u, v_out);
+}
+
+// RobustController::update, ALTHOFF method (robust_controller.cpp:63-128; Giusti and Althoff's robust input, the second controller of
+// kinova_src/scripts/kinova_compare_robust_controller.m): robust_prepare, the nominal pass, ONE interval kinematics and dynamics pass (no
+// interval M r), the interval check and the bound of torque_bound_sq, then :123-127
+//   phi_t = Kp[0] + Ki[0] e_acc,  kappa_t = Kp[1] + Ki[1] e_acc,  v = -(kappa_t |bound|_2 + phi_t) r,  u = u_nominal - v.
+// No threshold on |r| and no division by it: r = 0 gives v = 0 exactly (u = u_nominal to the bit).  e_acc is the accumulated state error
+// update() receives as eAcc.  As the reference's MEX runs it (kinova_controller_ALTHOFF.cpp:55, :78) e_acc is always 0: a fresh
+// RobustController per call (ssErrorAccum = 0) and update()'s default deltaT = 0, so ssErrorAccum never moves whatever maxError is,
+// and phi_t = Kp[0], kappa_t = Kp[1].  Returns false if a nominal torque leaves its interval (the reference throws).
+CTL_HD CTL_FLATTEN bool althoff_update(const Model<double>& md, const Model<Itv>& imd, const double* Kr, const double* Kp, const double* Ki, double e_acc,
+                           const double* q, const double* q_d, const double* qd, const double* qd_d, const double* qd_dd, double* u, double* u_nominal,
+                           double* v_out) {
+    const int n = md.n;
+    double qa_d[ARMOUR_MAX_FACTORS], qa_dd[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_FACTORS];
+    (void)robust_prepare(n, Kr, q, q_d, qd, qd_d, qd_dd, qa_d, qa_dd, r);
+    pass_rnea<double>(md, q, q_d, qa_d, qa_dd, false, true, u_nominal);
+    Itv u_int[ARMOUR_MAX_FACTORS];
+    pass_rnea<Itv>(imd, q, q_d, qa_d, qa_dd, false, true, u_int);
+    double bound_sq;
+    const bool ok = torque_bound_sq(n, u_nominal, u_int, &bound_sq);
+    const double phi_t = Kp[0] + Ki[0] * e_acc;
+    const double kappa_t = Kp[1] + Ki[1] * e_acc;
+    const double gain = -(kappa_t * sqrt(bound_sq) + phi_t);
+    for (int i = 0; i < n; i++) {
+        v_out[i] = gain * r[i];
+        u[i] = u_nominal[i] - v_out[i];
+    }
+    return ok;
 }
 
 }  // namespace ctl

@@ -348,6 +348,22 @@ int armour_robust_controller(const ArmourRobot* robot, double model_uncertainty,
  * either way, tests/test_controller.py): -1 (default) the four-wave latency kernel up to 4096 states and one lane per state
  * beyond, 0 always one lane per state, 1 always the latency kernel. */
 int armour_controller_set_kernel(int32_t which);
+/* kinova_controller_ALTHOFF(Kr, Kp, Ki, maxError, q, qd, q_des, qd_des, qdd_des[, eps]) ->  [u, tau, v]
+ * (kinova_robust_controllers_mex/kinova_controller_ALTHOFF.cpp:19-90; RobustController::update, ALTHOFF method,
+ * robust_controller.cpp:63-128 -- the robust input of Giusti and Althoff, the controller kinova_compare_robust_controller.m runs beside
+ * ARMOUR's) for B states at once: tau and the interval torque as in armour_robust_controller (the same nominal and interval passes,
+ * without the interval M r pass), bound_i = max |interval torque_i - tau_i|, then
+ *   phi_t = Kp[0] + Ki[0] e_acc[b],  kappa_t = Kp[1] + Ki[1] e_acc[b],  v = -(kappa_t |bound|_2 + phi_t) r,  u = tau - v
+ * with r = (qd_des - qd) + Kr .* wrap(q_des - q).  No threshold on |r| and no division by it: r = 0 gives v = 0 and u = tau exactly.
+ * e_acc [B] is the accumulated state error update() receives (NULL: zeros).  As the reference's MEX runs it e_acc is always 0 -- a fresh
+ * controller per call and deltaT = 0, so ssErrorAccum never moves and maxError has no effect -- which is why maxError is no argument here.
+ * One device lane per state, one kernel (no latency form: the study calls this with tens of thousands of states).  Pointers and shapes as
+ * armour_robust_controller.  ARMOUR_EINVAL, before the device is touched, for a null argument (e_acc excepted), B < 1, a non-finite
+ * entry of q .. qdd_des, Kr, Kp, Ki or e_acc, and a model_uncertainty that is negative or non-finite; ARMOUR_ESTATE if a nominal torque
+ * leaves its interval; ARMOUR_EDEVICE without a device. */
+int armour_althoff_controller(const ArmourRobot* robot, double model_uncertainty, const double* Kr, const double Kp[2], const double Ki[2],
+                              const double* e_acc /* [B] or NULL = zeros */, int32_t B, const double* q, const double* qd, const double* q_des,
+                              const double* qd_des, const double* qdd_des, double* u, double* tau, double* v);
 
 /* ---- closed-loop tracking: the plan executed by an uncertain arm under the controller (tracking.hip) ---- */
 /* uarmtd_agent.dynamics + uarmtd_agent.integrator with its low-level controller in the right-hand side (KSI/uarmtd_agent.m:280-293,
@@ -357,7 +373,10 @@ int armour_controller_set_kernel(int32_t which);
  *                step, so a rollout's bits depend on nothing but its own inputs); node k is at t0 + k h, node N at t1.
  *   Controller   ARMOUR_TRACK_CTL_ROBUST: RobustController::update, ARMOUR method, with opt->Kr .. model_uncertainty -- the arithmetic of
  *                armour_robust_controller;  _NOMINAL: u = the nominal passivity RNEA torque, v = 0 (KSI/uarmtd_nominal_passivity_LLC.m);
- *                _NONE: u = 0, the passive plant.
+ *                _NONE: u = 0, the passive plant;  _ALTHOFF: RobustController::update, ALTHOFF method, with opt->Kr, model_uncertainty
+ *                and Kp = opt->althoff_Kp -- the arithmetic of armour_althoff_controller with e_acc = 0 at every stage, as in the
+ *                reference's runs; |v| goes into max_robust_input and status 1 means what it means under _ROBUST.  A non-finite
+ *                althoff_Kp is ARMOUR_EINVAL under _ALTHOFF and ignored otherwise.
  *   Plant        qdd = M_true(q)^-1 (u - h_true(q, qd)), the controller's own nominal model (CoM frames) with link i's mass scaled by
  *                (1 + mass_scale[b][i]) and its CoM-frame inertia by (1 + inertia_scale[b][i]); M_true carries the armature on its diagonal
  *                (the reference's transmision_inertia), h_true = passivity RNEA (q, qd, qd, 0) with gravity.  Unlike uarmtd_agent, h_true
@@ -378,6 +397,9 @@ int armour_controller_set_kernel(int32_t which);
 #define ARMOUR_TRACK_CTL_ROBUST 0
 #define ARMOUR_TRACK_CTL_NOMINAL 1
 #define ARMOUR_TRACK_CTL_NONE 2
+/* (3 is unassigned and refused: callers and tests have relied on armour_track answering controller = 3 with ARMOUR_EINVAL since the entry
+ * exists, so a new mode does not take the number) */
+#define ARMOUR_TRACK_CTL_ALTHOFF 4
 #define ARMOUR_TRACK_LIMIT_TORQUE 1
 #define ARMOUR_TRACK_LIMIT_POSITION 2
 #define ARMOUR_TRACK_LIMIT_SPEED 4
@@ -389,7 +411,8 @@ typedef struct ArmourTrackOptions {
     double Kr[ARMOUR_MAX_FACTORS];
     double alpha, V_max, r_norm_threshold, model_uncertainty;   /* as armour_robust_controller */
     double dt, t0, t1, duration;                                /* 0 <= t0 < t1 <= duration; dt > 0 */
-    double reserved[4];
+    double althoff_Kp[2];      /* _ALTHOFF: (phi, kappa) of v = -(kappa |bound| + phi) r; the first two of four doubles that were reserved */
+    double reserved[2];
 } ArmourTrackOptions;
 /* What a result holds at the edges:
  *   - a torque limit <= 0 contributes no ratio to max_torque_ratio (nothing is divided by it) and still flags: ARMOUR_TRACK_LIMIT_TORQUE is
@@ -407,7 +430,7 @@ typedef struct ArmourTrackResult {
     double first_violation_t;  /* the first node with a limit crossing; NaN: none */
 } ArmourTrackResult;
 /* Kr = robot->K on every joint, alpha = robot->alpha, V_max = robot->V_m, r_norm_threshold = 0, model_uncertainty = robot->mass_uncertainty
- * (KSI/uarmtd_robust_CBF_LLC.m:6-9 as the planner's robot constants set them), controller ROBUST, dt = 1e-3, t0 = 0, t1 = duration = 1,
+ * (KSI/uarmtd_robust_CBF_LLC.m:6-9 as the planner's robot constants set them), althoff_Kp = {28.1037, 28.1037} (:11), controller ROBUST, dt = 1e-3, t0 = 0, t1 = duration = 1,
  * no trace, automatic steps per launch. */
 void armour_track_options_default(const ArmourRobot* robot, ArmourTrackOptions* opt);
 int armour_track(const ArmourRobot* robot, const ArmourTrackOptions* opt, int32_t B, const double* q0, const double* qd0, const double* qdd0,

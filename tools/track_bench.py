@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """armour_track on the MI355X: device ms per call and rollout-steps/s for whole rollouts of the reference's controller study
 (T = 2.5 s, dt = 1e-3, robust controller, Kinova, true plants 1.01 x nominal) at B = 1, 16, 128, 700 (the reference study's 7 x 100)
-and 4096; the per-step cost behind armour_track's automatic steps per launch (tracking.hip kStepMs*); writes profiles/track_bench.json.
+and 4096; the per-step cost of the robust, the passive and the Althoff mode behind armour_track's automatic steps per launch (tracking.hip
+kStepMs*); writes profiles/track_bench.json.
 
     python tools/track_bench.py [--out profiles/track_bench.json] [--batches 1,16,128,700,4096] [--T 2.5]
     python tools/track_bench.py --tau-study      # host restatement only (no GPU): maxima at dt = 1e-3 against dt = 5e-4
@@ -47,8 +48,8 @@ def bench(args):
     rb = kinova_robot()
     n = rb.num_factors
     out = dict(what="armour_track, Kinova, robust controller, T = %g s, dt = 1e-3, true plant 1.01 x nominal; device ms = events around the launches" % args.T,
-               per_step_ms={c: per_step(rb, c) for c in ("robust", "none")},
-               auto_steps_per_launch={c: L.armour_track_auto_steps(v) for c, v in (("robust", 0), ("nominal", 1), ("none", 2))}, rows=[])
+               per_step_ms={c: per_step(rb, c) for c in ("robust", "none", "althoff")},
+               auto_steps_per_launch={c: L.armour_track_auto_steps(v) for c, v in (("robust", 0), ("nominal", 1), ("none", 2), ("althoff", 4))}, rows=[])
     print(json.dumps({k: v for k, v in out.items() if k != "rows"}), flush=True)
     for B in [int(x) for x in args.batches.split(",")]:
         rng = np.random.default_rng(B)
