@@ -196,6 +196,7 @@ EXPORTS = [
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
     "armour_ws_tree_plan", "armour_ws_tree_plan_host",
     "armour_debug_block_steps", "armour_debug_block_split", "armour_debug_block_owner",
+    "armour_debug_p2_plan", "armour_debug_p2_plan_shape",
 ]
 
 _lib = None
@@ -355,6 +356,9 @@ def load():
     L.armour_debug_block_steps.argtypes = [dp, ip, ip, ip, dp, ip, ip, ip, ip, ip]
     L.armour_debug_block_split.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip]
     L.armour_debug_block_owner.argtypes = [ip, C.c_int32, C.c_int32, ip, ip]
+    if hasattr(L, "armour_debug_p2_plan"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        L.armour_debug_p2_plan.argtypes = [vp, ip, C.POINTER(C.c_uint32)]
+        L.armour_debug_p2_plan_shape.argtypes = [C.c_int32] * 8 + [C.POINTER(C.c_uint64), ip, C.POINTER(C.c_uint32)]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

@@ -37,6 +37,10 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE
                                                                   double* __restrict__ g_all, double* __restrict__ jac_all,
                                                                   P2Launch lp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+#ifdef P2_TIMELINE  // development only: the kernel's first instruction, before any wait for the argument loads (P2_STAMP(0)'s wait covers this read too)
+    unsigned long long t_entry;
+    asm volatile("s_memrealtime %0" : "=s"(t_entry) :: "memory");
+#endif
     // (Round 4, measured and dropped: an XCD-aware mapping -- linear workgroup l runs on XCD l % 8; give each XCD a CONTIGUOUS range of the
     //  (problem, row block) pairs so that neighbouring blocks, which share their (link, time step) records, share an L2 -- configs[2]
     //  539 us against 500: what a block streams is 30 KB of its own rows and 3 KB of shared records, and eight XCDs that each walk one
@@ -51,6 +55,10 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE
     if ((P2_ABLATE & 1) && role < lp.nbc) return;
     if ((P2_ABLATE & 2) && role >= lp.nbc && role < lp.nbc + lp.nbt) return;
     if ((P2_ABLATE & 4) && role >= lp.nbc + lp.nbt) return;
+#endif
+#ifdef P2_TIMELINE
+    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw, t_entry);
+    else
 #endif
     if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
     else if (role < lp.nbc + lp.nbt) torque_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
@@ -131,6 +139,42 @@ int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsig
     // ... exactly 24 (6 per wave) and the blocks slice in one pass: the EX kernels (ARMOUR_OPT_P2_EX = 0 turns them off)
     bool exact = six && tb.ex_allowed && lp.max_pairs <= lp.pair_chunk;
     for (int b = 0; exact && b < tb.B; b++) exact = armour_p2_ex_layout_ok(h_skip[b]);
+    // The EX kernels add 32-bit byte offsets to a 64-bit base per problem: every table they index must be shorter than 2^32 B per problem
+    // (Q < 2^20 bounds the plane table at 1.6 GB; the link-PZ coefficients are the one that can pass it).  Launches that are not take the
+    // kernels above, whose addresses are 64-bit.
+    const unsigned long long Qs = (unsigned long long)armour_row_stride(tb.Q), JT = (unsigned long long)tb.J * (unsigned long long)tb.T;
+    const unsigned long long planes_bytes = armour_planes_per_problem(tb.Q) * sizeof(double), ll_bytes = armour_planes_ll_per_problem((int)JT) * sizeof(double);
+    const unsigned long long pz_bytes = JT * (unsigned long long)std::max(tb.capL, 1) * 3ull * sizeof(double);
+    const unsigned long long out_bytes = (unsigned long long)std::max(tb.m, 0) * (unsigned long long)std::max(tb.n, 1) * sizeof(double);
+    if (std::max(std::max(planes_bytes, ll_bytes), std::max(pz_bytes, out_bytes)) >= (1ull << 32)) exact = false;
+    lp.ex_plane_bytes = 0; lp.ex_cd = 0; lp.ex_dll = 0; lp.ex_d = 0; lp.ex_planes_bytes = 0; lp.ex_ll_bytes = 0; lp.ex_shared = 0;
+    lp.ex_cnt_bytes = 0; lp.ex_key_bytes = 0; lp.ex_co_bytes = 0; lp.ex_cen_bytes = 0;
+    for (int w = 0; w < 2; w++) {
+        lp.ex_ll0[w] = 0;
+        for (int i = 0; i < 6; i++) lp.ex_ob[w][i] = 0;
+    }
+    if (exact) {
+        lp.ex_plane_bytes = (unsigned int)(Qs * 2 * sizeof(double));
+        lp.ex_cd = (unsigned int)(armour_planes_cd_offset(tb.Q) * sizeof(double));
+        lp.ex_dll = (unsigned int)(armour_planes_dll_offset(tb.Q) * sizeof(double));
+        lp.ex_d = (unsigned int)(armour_planes_d_offset(tb.Q) * sizeof(double));
+        lp.ex_planes_bytes = (unsigned int)planes_bytes; lp.ex_ll_bytes = (unsigned int)ll_bytes;
+        lp.ex_cnt_bytes = (unsigned int)(JT * sizeof(int)); lp.ex_key_bytes = (unsigned int)(JT * (unsigned long long)tb.capL * sizeof(uint32_t));
+        lp.ex_co_bytes = (unsigned int)pz_bytes; lp.ex_cen_bytes = (unsigned int)(JT * 3ull * sizeof(double));
+        bool shared = true;
+        for (int b = 1; shared && b < tb.B; b++) shared = h_skip[b] == h_skip[0];
+        if (shared) {
+            // the dealing of collision_block: the 24 live planes in ascending order, six to a wave
+            unsigned long long live = ~h_skip[0] & ((1ull << ARMOUR_NPLANES) - 1ull);
+            int pl[24];
+            for (int i = 0; i < 24; i++) { pl[i] = __builtin_ctzll(live); live &= live - 1ull; }
+            for (int w = 0; w < 2; w++) {
+                for (int i = 0; i < 6; i++) lp.ex_ob[w][i] = (unsigned int)pl[6 * w + i] * lp.ex_plane_bytes;
+                lp.ex_ll0[w] = (unsigned int)(pl[12 + 6 * w] - ARMOUR_FIRST_LL_PLANE);
+            }
+            lp.ex_shared = 1; lp.skip_by_value = 1; lp.skip0 = h_skip[0];
+        }
+    }
     *lp_out = lp; *smem_out = smem; *dfc_out = dfc; *six_out = six; *exact_out = exact;
     return ARMOUR_OK;
 }
@@ -166,6 +210,46 @@ int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const uns
 #undef P2_LAUNCH_M
     HIPCHK(hipGetLastError());
     return ARMOUR_OK;
+}
+
+// armour_p2_plan's verdict and the addressing members it fills, for the tests (include/armour_hip.h)
+static int p2_plan_report(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, int32_t* verdict, uint32_t* fields) {
+    if (!verdict || !fields) { armour_set_error("armour_debug_p2_plan: null output"); return ARMOUR_EINVAL; }
+    P2Launch lp;
+    size_t smem = 0;
+    bool dfc, six, exact;
+    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact);
+    if (rc != ARMOUR_OK) return rc;
+    const size_t at_lp = (sizeof(P2Tables) + 3 * sizeof(void*) + alignof(P2Launch) - 1) / alignof(P2Launch) * alignof(P2Launch);   // (tb, k, g, jac, lp)
+    verdict[0] = dfc; verdict[1] = six; verdict[2] = exact; verdict[3] = (int32_t)(at_lp + sizeof(P2Launch)); verdict[4] = lp.ex_shared; verdict[5] = lp.skip_by_value;
+    const uint32_t f[6] = {lp.ex_plane_bytes, lp.ex_cd, lp.ex_dll, lp.ex_d, lp.ex_planes_bytes, lp.ex_ll_bytes};
+    for (int i = 0; i < 6; i++) fields[i] = f[i];
+    for (int w = 0; w < 2; w++) {
+        for (int i = 0; i < 6; i++) fields[6 + 6 * w + i] = lp.ex_ob[w][i];
+        fields[18 + w] = lp.ex_ll0[w];
+    }
+    return ARMOUR_OK;
+}
+
+extern "C" int armour_debug_p2_plan(ArmourPlanner* h, int32_t* verdict, uint32_t* fields) {
+    NEED_READY(h);
+    return p2_plan_report(armour_make_tables(h), h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), verdict, fields);
+}
+
+extern "C" int armour_debug_p2_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,
+                                          const uint64_t* skip, int32_t* verdict, uint32_t* fields) {
+    if (B < 1 || T < 1 || J < 1 || n < 1 || n > ARMOUR_MAX_FACTORS || O < 1 || capL < 1 || max_link < 1 || !skip || (long long)J * T * O >= (1ll << 31)) {
+        armour_set_error("armour_debug_p2_plan_shape: bad shape or null masks");
+        return ARMOUR_EINVAL;
+    }
+    static const double none = 0.0;   // (the plan only asks whether the obstacle centres exist)
+    std::vector<unsigned long long> h_skip(skip, skip + B);
+    P2Tables tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.B = B; tb.T = T; tb.J = J; tb.n = n; tb.O = O; tb.Q = J * T * O; tb.row0 = n * T; tb.m = tb.row0 + tb.Q + 4 * n;
+    tb.capL = capL; tb.capT = 1; tb.ll_shared = 1; tb.ex_allowed = 1; tb.mode = ARMOUR_MODE_ARMOUR;
+    tb.obs_center = recompute_d ? &none : nullptr;
+    return p2_plan_report(tb, max_link, 1, h_skip.data(), nullptr, verdict, fields);
 }
 
 int armour_p2_slice_links_launch(const P2Tables& tb, const double* d_k, double* d_centers, hipStream_t stream) {

@@ -134,6 +134,21 @@ __device__ inline int fast_div(int x, unsigned long long m) { return (int)(((uns
 // 16-B table entries as a NATIVE vector: a load of HIP's double2 (a struct) is split into two 8-B loads by the optimiser before the
 // two plane-loading paths of the EX kernels are merged, and the backend cannot pair them again afterwards (seen in the ISA)
 typedef double v2d __attribute__((ext_vector_type(2)));
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+
+// The EX kernels' addressing: a 64-bit base per problem, wave-uniform (b * per-problem size + pointer, on the scalar unit), plus an UNSIGNED
+// 32-bit byte offset per lane -- armour_p2_plan proves that no per-problem table they index reaches 2^32 B.  In this form a load is
+// `global_load v, v_off, s[base]` and the offset arithmetic is one 32-bit multiply-add, where (size_t) element indices cost a 64-bit
+// multiply and a 64-bit shift-add per load and lane.
+template <typename V>
+__device__ __forceinline__ V ld32(const char* base, uint32_t byte_off) { return *reinterpret_cast<const V*>(base + byte_off); }
+__device__ __forceinline__ void st32(char* base, uint32_t byte_off, double v) { *reinterpret_cast<double*>(base + byte_off) = v; }
+// The plane table through a buffer resource (raw, no stride): address = base + lane offset + a wave-uniform offset in a scalar register, so
+// the plane and section a wave reads cost no instruction per load.  Built from wave-uniform values only.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const char* base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, (int)bytes, 0x00020000);
+}
 
 struct P2Launch {
     int nbc, nbt;       // collision / torque block counts
@@ -153,6 +168,19 @@ struct P2Launch {
     // dependent load at B = 1, as skip0 does the collision blocks)
     int bez_by_value;
     double bez0[3 * ARMOUR_MAX_FACTORS];
+    // EX launches: the problem-level part of the plane table's addressing (common.h armour_plane_index), which is the same in every launch
+    // between two problem sets, as plain scalars: the collision block reads them with the kernel arguments instead of deriving them per block
+    // with 64-bit multiply chains and a walk over the live-plane mask.  All in BYTES from the start of one problem's table; armour_p2_plan
+    // proves that every per-problem table an EX launch reads is shorter than 2^32 B (it takes the 64-bit kernels otherwise), so a lane
+    // adds 32-bit offsets to a scalar 64-bit base.
+    unsigned int ex_plane_bytes;             // one plane of a paired section: 16 * armour_row_stride(Q) (a plane of D: half of it)
+    unsigned int ex_cd, ex_dll, ex_d;        // sections CD, DLL and D
+    unsigned int ex_planes_bytes, ex_ll_bytes;   // one problem's plane table / link x link records
+    unsigned int ex_cnt_bytes, ex_key_bytes, ex_co_bytes, ex_cen_bytes;   // one problem's link_count, link_keys, link_coeff, link_center (= link_indep)
+    // 1: every problem of the launch has the live-plane mask of problem 0 (always at B = 1; then skip_by_value = 1, skip0 = that mask)
+    int ex_shared;
+    unsigned int ex_ob[2][6];                // waves 0 and 1: p * ex_plane_bytes of the wave's six planes
+    unsigned int ex_ll0[2];                  // waves 2 and 3: p - ARMOUR_FIRST_LL_PLANE of the wave's first plane
 };
 
 // registers of one slicing pass: the (monomial, axis) tasks of this thread and, for threads < pairs*24, the inputs of
@@ -206,27 +234,33 @@ __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, 
     const int tid = threadIdx.x;
     const int per_pair = lp.strideL * P2_SL, per_pair3 = lp.strideL * 3;
     const int ntask = pc * per_pair3;
-    const size_t idx0 = (size_t)b * tb.J * tb.T + lt_first;
+    // (ld32: the problem's tables as scalar bases, a lane's entry as 32-bit bytes; JT * capL * 24 B < 2^32 by armour_p2_plan)
+    const uint32_t capL = (uint32_t)tb.capL;
+    const char* cnt_b = reinterpret_cast<const char*>(tb.link_count) + (size_t)(uint32_t)b * lp.ex_cnt_bytes;
+    const char* key_b = reinterpret_cast<const char*>(tb.link_keys) + (size_t)(uint32_t)b * lp.ex_key_bytes;
+    const char* co_b = reinterpret_cast<const char*>(tb.link_coeff) + (size_t)(uint32_t)b * lp.ex_co_bytes;
+    const char* cen_b = reinterpret_cast<const char*>(tb.link_center) + (size_t)(uint32_t)b * lp.ex_cen_bytes;
+    const char* ind_b = reinterpret_cast<const char*>(tb.link_indep) + (size_t)(uint32_t)b * lp.ex_cen_bytes;
 #pragma unroll
     for (int r = 0; r < P2_TASK_ROUNDS; r++) {
         const int task = tid + r * P2_BLOCK;
         const bool valid = task < ntask;
         const int tk = valid ? task : 0;
         const int pi = fast_div(tk, lp.magic_pp3), rem = tk - pi * per_pair3, mo = rem / 3, e = rem - mo * 3;
-        const size_t idx = idx0 + pi;
-        const int moc = min(mo, tb.capL - 1);
-        const int cnt = tb.link_count[idx];
-        pr.tkey[r] = tb.link_keys[idx * tb.capL + moc];
-        pr.tco[r] = tb.link_coeff[(idx * tb.capL + moc) * 3 + e];
+        const uint32_t idx = (uint32_t)(lt_first + pi);
+        const uint32_t ent = idx * capL + (uint32_t)min(mo, tb.capL - 1);
+        const int cnt = ld32<int>(cnt_b, idx * 4u);
+        pr.tkey[r] = ld32<uint32_t>(key_b, ent * 4u);
+        pr.tco[r] = ld32<double>(co_b, (ent * 3u + (uint32_t)e) * 8u);
         pr.tcnt[r] = cnt - (valid ? mo : (1 << 20));  // > 0: live monomial (cnt <= capL, so a clamped mo is never live)
         pr.tdst[r] = pi * per_pair + mo * P2_SL + e;
     }
     const int tc = tid < pc * P2_SL ? tid : 0;
     const int pi = tc / P2_SL, c = tc - pi * P2_SL, e = c % 3;
-    const size_t idx = idx0 + pi;
-    pr.rc_cnt = min(tb.link_count[idx], lp.strideL);  // used by threads < pc*P2_SL only
-    pr.rc_cen = tb.link_center[idx * 3 + e];            // used for the value column (c < 3) only
-    pr.rc_ind = tb.link_indep[idx * 3 + e];
+    const uint32_t idx = (uint32_t)(lt_first + pi);
+    pr.rc_cnt = min(ld32<int>(cnt_b, idx * 4u), lp.strideL);  // used by threads < pc*P2_SL only
+    pr.rc_cen = ld32<double>(cen_b, (idx * 3u + (uint32_t)e) * 8u);            // used for the value column (c < 3) only
+    pr.rc_ind = ld32<double>(ind_b, (idx * 3u + (uint32_t)e) * 8u);
 }
 
 // EX: every wave holds exactly PPW live planes and the block slices in one pass: the PZ-table loads are issued first and
@@ -234,7 +268,11 @@ __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, 
 // the planes are still in flight; the barriers before the scan wait for LDS traffic only.
 template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX>
 __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Launch& lp, const int b, const int role, const double* __restrict__ k0,
-                                   const double k_first, double* __restrict__ g0_in, double* __restrict__ jac0_in, unsigned char* smem_raw) {
+                                   const double k_first, double* __restrict__ g0_in, double* __restrict__ jac0_in, unsigned char* smem_raw
+#ifdef P2_TIMELINE
+                                   , unsigned long long t_entry = 0   // the kernel's entry stamp (p2_eval.hip)
+#endif
+                                   ) {
     KPow* kp2 = reinterpret_cast<KPow*>(smem_raw);  // double-buffered over the points
     double* lds = reinterpret_cast<double*>(smem_raw + 2 * sizeof(KPow));
     const int n = tb.n, T = tb.T, O = tb.O, Q = tb.Q, m = tb.m;
@@ -274,7 +312,6 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     const double* pl0 = tb.planes + (size_t)b * armour_planes_per_problem(Q);
     const v2d* plAB = reinterpret_cast<const v2d*>(pl0) + q;
     const v2d* plCD = reinterpret_cast<const v2d*>(pl0 + armour_planes_cd_offset(Q)) + q;
-    const v2d* plLL = reinterpret_cast<const v2d*>(pl0 + armour_planes_dll_offset(Q)) + q;
     const double* plD = pl0 + armour_planes_d_offset(Q) + q;
     const int JT = tb.J * T;
     const int q_lt = fast_div(q, lp.magic_O), q_o = q - q_lt * O;  // q = (l*T + t)*O + o
@@ -285,7 +322,7 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     unsigned long long skip0 = lp.skip0;
     asm volatile("" : "+s"(skip0));
     unsigned long long live = ~(lp.skip_by_value ? skip0 : tb.plane_skip[b]) & ((1ull << ARMOUR_NPLANES) - 1ull);
-    const bool plane0_live = (live & 1ull) != 0;
+    bool plane0_live = (live & 1ull) != 0;
     const int na = __popcll(live), base = na >> 2, rem = na & 3;
     const int my_cnt = base + (wv < rem ? 1 : 0), my_start = wv * base + min(wv, rem);
     for (int s = 0; s < my_start; s++) live &= live - 1ull;
@@ -304,30 +341,50 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     bool ll_wave = false;
     if (EX) {
         static_assert(!EX || PPW == 6, "the EX kernels hold six planes per wave");
+        // Addresses: a buffer resource over the problem's table + this lane's row (q * 16 B, q * 8 B in section D, q_lt * 384 B into the
+        // records) + a wave-uniform byte offset in a scalar register that names the section and the plane.  The scalar offsets come from
+        // the launch plan (P2Launch ex_*: nothing here depends on k or on the launch) by scalar selects on the wave number; launches
+        // whose problems have different masks walk this problem's mask for the plane numbers instead.
         ll_wave = wv >= 2;
-        const v2d* ra[12];
-        const double* da[6];
+        const uint32_t pb = lp.ex_plane_bytes, pbd = pb >> 1;
+        uint32_t po[6] = {0, 0, 0, 0, 0, 0}, pll0 = 0;   // obstacle waves: p * pb of the six planes; link x link waves: p - 21 of the first
+        if (__builtin_expect(lp.ex_shared != 0, 1)) {
+            plane0_live = (lp.skip0 & 1ull) == 0;
+            if (ll_wave) pll0 = wv == 2 ? lp.ex_ll0[0] : lp.ex_ll0[1];
+            else {
+#pragma unroll
+                for (int i = 0; i < 6; i++) po[i] = wv == 0 ? lp.ex_ob[0][i] : lp.ex_ob[1][i];
+            }
+        } else {   // problems with different masks: the dealing of the other kernels, six planes to a wave in ascending order
+            unsigned long long mine = ~tb.plane_skip[b] & ((1ull << ARMOUR_NPLANES) - 1ull);
+            plane0_live = (mine & 1ull) != 0;
+            for (int s = 0; s < 6 * wv; s++) mine &= mine - 1ull;
+            pll0 = (uint32_t)(__builtin_ctzll(mine) - ARMOUR_FIRST_LL_PLANE);   // (used by the link x link waves only)
+#pragma unroll
+            for (int i = 0; i < 6; i++) { po[i] = (uint32_t)__builtin_ctzll(mine) * pb; mine &= mine - 1ull; }
+        }
+        uint32_t so[12], sd[6];
         if (ll_wave) {
-            const int pll0 = __builtin_ctzll(live) - ARMOUR_FIRST_LL_PLANE;
-            const v2d* nrm = reinterpret_cast<const v2d*>(pll + (size_t)pll0 * 3);
+            const uint32_t s0 = pll0 * (3u * (uint32_t)sizeof(double)), s1 = lp.ex_dll + (pll0 >> 1) * pb, s2 = lp.ex_d + (ARMOUR_FIRST_LL_PLANE + pll0) * pbd;
 #pragma unroll
-            for (int j = 0; j < 9; j++) ra[j] = nrm + j;
+            for (int j = 0; j < 9; j++) so[j] = s0 + 16u * j;
 #pragma unroll
-            for (int j = 0; j < 3; j++) ra[9 + j] = plLL + (size_t)((pll0 >> 1) + j) * Qs;
+            for (int j = 0; j < 3; j++) so[9 + j] = s1 + (uint32_t)j * pb;
 #pragma unroll
-            for (int i = 0; i < 6; i++) da[i] = plD + (size_t)(ARMOUR_FIRST_LL_PLANE + pll0 + i) * Qs;
+            for (int i = 0; i < 6; i++) sd[i] = s2 + (uint32_t)i * pbd;
         } else {
 #pragma unroll
-            for (int i = 0; i < 6; i++) {
-                const size_t o = (size_t)__builtin_ctzll(live) * Qs;
-                live &= live - 1ull;
-                ra[2 * i] = plAB + o; ra[2 * i + 1] = plCD + o; da[i] = plD + o;
-            }
+            for (int i = 0; i < 6; i++) { so[2 * i] = po[i]; so[2 * i + 1] = lp.ex_cd + po[i]; sd[i] = lp.ex_d + (po[i] >> 1); }
         }
+        const char* plb = reinterpret_cast<const char*>(tb.planes) + (size_t)(uint32_t)b * lp.ex_planes_bytes;
+        const char* llb = reinterpret_cast<const char*>(tb.planes_ll) + (size_t)(uint32_t)b * lp.ex_ll_bytes;
+        const __amdgpu_buffer_rsrc_t rs_pl = table_rsrc(plb, lp.ex_planes_bytes);
+        const __amdgpu_buffer_rsrc_t rs_a = table_rsrc(ll_wave ? llb : plb, ll_wave ? lp.ex_ll_bytes : lp.ex_planes_bytes);
+        const uint32_t vq = (uint32_t)q * 16u, va = ll_wave ? (uint32_t)q_lt * (uint32_t)(ARMOUR_LL_RECORD * sizeof(double)) : vq;
 #pragma unroll
-        for (int j = 0; j < 12; j++) raw[j] = *ra[j];
+        for (int j = 0; j < 12; j++) raw[j] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(j < 9 ? rs_a : rs_pl, j < 9 ? va : vq, (int)so[j], 0));
 #pragma unroll
-        for (int i = 0; i < 6; i++) { dd[i] = 0.0; if (!DFC) dd[i] = *da[i]; }
+        for (int i = 0; i < 6; i++) { dd[i] = 0.0; if (!DFC) dd[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs_pl, (uint32_t)q * 8u, (int)sd[i], 0)); }
     } else {
 #pragma unroll
     for (int i = 0; i < PPW; i++) {
@@ -359,8 +416,13 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     // expression of armour_p1_planes_kernel, instead of read -- 8 B less per plane and row
     double oc0 = 0.0, oc1 = 0.0, oc2 = 0.0;
     if (DFC) {
-        const double* oc = tb.obs_center + (size_t)b * 3 * O + q_o;
-        oc0 = oc[0]; oc1 = oc[O]; oc2 = oc[2 * (size_t)O];
+        if (EX) {
+            const char* ocb = reinterpret_cast<const char*>(tb.obs_center + (size_t)(uint32_t)b * (uint32_t)(3 * O));
+            oc0 = ld32<double>(ocb, (uint32_t)q_o * 8u); oc1 = ld32<double>(ocb, (uint32_t)(q_o + O) * 8u); oc2 = ld32<double>(ocb, (uint32_t)(q_o + 2 * O) * 8u);
+        } else {
+            const double* oc = tb.obs_center + (size_t)b * 3 * O + q_o;
+            oc0 = oc[0]; oc1 = oc[O]; oc2 = oc[2 * (size_t)O];
+        }
     }
     P2_STAMP(1);
     // 2. per point: slice the (l,t) link PZs this block's rows touch (one thread per (pair, monomial, axis)), then
@@ -478,7 +540,10 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
 #if defined(P2_ABLATE) && (P2_ABLATE & 32)
             if (WANT_G && wv == 0 && m_elt == 12345.678) g[(size_t)tb.row0 + q_begin + lane] = -m_elt;
 #else
-            if (WANT_G && wv == 0 && q_begin + lane < q_end) g[(size_t)tb.row0 + q_begin + lane] = -m_elt;
+            if (WANT_G && wv == 0 && q_begin + lane < q_end) {
+                if (EX) st32(reinterpret_cast<char*>(g), (uint32_t)(tb.row0 + q_begin + lane) * 8u, -m_elt);   // (m * n * 8 B < 2^32: armour_p2_plan)
+                else g[(size_t)tb.row0 + q_begin + lane] = -m_elt;
+            }
 #endif
             if (WANT_J) {
 #pragma unroll
@@ -499,7 +564,13 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
 #if defined(P2_ABLATE) && (P2_ABLATE & 32)
             for (int i = tid; i < total; i += P2_BLOCK) if (stage[i] == 12345.678) jrow[i] = stage[i];
 #else
-            for (int i = tid; i < total; i += P2_BLOCK) jrow[i] = stage[i];
+            if (EX) {
+                char* jb = reinterpret_cast<char*>(jac);
+                const uint32_t j0 = (uint32_t)(tb.row0 + q_begin) * (uint32_t)n;
+                for (int i = tid; i < total; i += P2_BLOCK) st32(jb, (j0 + (uint32_t)i) * 8u, stage[i]);
+            } else {
+                for (int i = tid; i < total; i += P2_BLOCK) jrow[i] = stage[i];
+            }
 #endif
         }
     }
@@ -508,7 +579,8 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     stamp[7] = __builtin_amdgcn_s_memtime() - cyc0;
     if (tid == 0 && (role == 0 || role == lp.nbc / 2 || role == lp.nbc - 1)) {
         const int slot = role == 0 ? 0 : role == lp.nbc - 1 ? 2 : 1;
-        for (int i2 = 0; i2 < 8; i2++) g0_in[(size_t)tb.row0 + Q + slot * 8 + i2] = (double)(stamp[i2] & 0xffffffffffffull);
+        for (int i2 = 0; i2 < 8; i2++) g0_in[(size_t)tb.row0 + Q + slot * 9 + i2] = (double)(stamp[i2] & 0xffffffffffffull);
+        g0_in[(size_t)tb.row0 + Q + slot * 9 + 8] = (double)(t_entry & 0xffffffffffffull);   // (27 of the 4n = 28 limit rows)
     }
 #endif
 }

@@ -639,6 +639,21 @@ int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, const doubl
 int armour_debug_get_row_lists(ArmourPlanner* h, int32_t which, int32_t* rows, int32_t* count, int32_t* aux, int32_t* aux_count,
                                int64_t* pack_off, double* packed, int64_t packed_capacity, int64_t* packed_total);
 
+/* ---- test hooks: which fused-evaluation kernel a one-point launch takes, and the plane-table addressing its launch plan carries ---- */
+/* armour_debug_p2_plan: the plan of a one-point armour_eval_g_jac_device launch of the handle's current problem set.
+ *   verdict [6]   {d recomputed from the obstacle centres, at most 24 live planes per problem (6-slot kernels), the exact-layout (EX) kernel,
+ *                  bytes of kernel arguments, every problem shares problem 0's live-plane mask, the mask travels by value}
+ *   fields [20]   what an EX launch reads instead of deriving it per block, all 0 when it is not one; in bytes from the start of one problem's
+ *                 plane table: {one plane of a paired section, section CD, section DLL, section D, the whole table, the link x link records},
+ *                 then, when the mask is shared, p * (bytes of a plane) of the six planes of wave 0 and of wave 1, and p - 21 of the first
+ *                 link x link plane of wave 2 and of wave 3 (0 otherwise: the kernel walks the mask).
+ * armour_debug_p2_plan_shape (host only, no handle, no device): the same for tables of B problems with T steps, J links, n factors, O obstacles,
+ * capL stored and max_link live monomials per link PZ and the live-plane masks skip [B] (bit p set: plane p is skipped); recompute_d != 0:
+ * tables without the d column.  A shape whose per-problem tables reach 2^32 bytes is no EX launch (verdict[2] = 0). */
+int armour_debug_p2_plan(ArmourPlanner* h, int32_t* verdict, uint32_t* fields);
+int armour_debug_p2_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,
+                               const uint64_t* skip, int32_t* verdict, uint32_t* fields);
+
 /* ---- test hooks: the block steps under the per-world planner kernels (armour_tree_plan, armour_path_shortcut, armour_ik, armour_ws_tree_plan) ---- */
 /* armour_debug_block_steps: ONE block of 256 lanes runs each cooperative step once on the caller's per-lane values (all [256]) and touches no
  * planner state.  Lane t holds the key (d[t], v[t]) -- a lane without a key passes (+inf, INT32_MAX) --, the flag flag[t] != 0 and the term n[t].

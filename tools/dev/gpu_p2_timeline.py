@@ -18,12 +18,14 @@ for rep in range(2):
     st.synchronize()
 gfull = dg.cpu().numpy()
 g = gfull[:, 7 * T + 7 * T * O:]
-raw = g[:, :24].reshape(K, 3, 8)
+raw = g[:, :27].reshape(K, 3, 9)   # per stamped block: stamps 0..6, shader cycles, the kernel's entry stamp
 stamps = raw[:, :, :7]
+entry = raw[:, :, 8]
 print('shader cycles per block / (end-start) ns -> GHz:', np.median(raw[8:, :, 7] / ((raw[8:, :, 6] - raw[8:, :, 0]) * 10.0), axis=0))
 names = ["start", "planes issued", "k+tables+barrier", "mono+barrier", "reduce+barrier", "scan+barrier", "end"]
 base = stamps[:, :, 0].min(axis=1)            # earliest of the three blocks, per launch
 rel = (stamps - base[:, None, None]) * 10.0   # ns
+print("kernel entry -> start stamp (the argument round trip and the role dispatch), median ns per block:", np.median((stamps[8:, :, 0] - entry[8:]) * 10.0, axis=0))
 print("median ns since the earliest block start, per block (first / middle / last collision block):")
 for i, nme in enumerate(names):
     print(f"  {nme:18s}", np.median(rel[8:, :, i], axis=0))
@@ -31,7 +33,7 @@ prev_end = stamps[:-1, :, 6].max(axis=1)
 print("gap from previous launch's last end stamp to this launch's first start: median ns", np.median((base[1:] - prev_end)[8:]) * 10.0)
 print("launch-to-launch (start to start) median ns", np.median(np.diff(base)[8:]) * 10.0)
 
-sl = gfull[:, :24].reshape(K, 3, 8)[:, :, :7]
+sl = gfull[:, :27].reshape(K, 3, 9)[:, :, :7]
 if sl[8:].any():
     rel2 = (sl - base[:, None, None]) * 10.0
     print("slicing-wave view (split kernel):")

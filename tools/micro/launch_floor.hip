@@ -5,7 +5,10 @@
 #include <cstdlib>
 #include <chrono>
 
-struct Big { double a[48]; };  // 384 B of kernarg, about what the P2 kernel takes
+#ifndef LF_DOUBLES   // -DLF_DOUBLES=78: 632 B, the one-point P2 kernel's arguments since the launch plan carries the plane-table addressing
+#define LF_DOUBLES 48
+#endif
+struct Big { double a[LF_DOUBLES]; };  // 384 B of kernarg by default (the mode names below say 392 B: + the output pointer)
 
 __global__ void k_small(double* out) { if (out && threadIdx.x == 999999) out[0] = 1.0; }
 __global__ void k_big(Big b, double* out) { if (out && threadIdx.x == 999999) out[0] = b.a[5]; }
@@ -57,7 +60,7 @@ int main() {
                 hipStreamSynchronize(s);
                 float gms; hipEventElapsedTime(&gms, e0, e1);
                 hipGraphExecDestroy(exec); hipGraphDestroy(graph);
-                printf("mode %d (%s) block %3d grid %4d: %.2f us/launch (host enqueue %.2f us), in a graph %.2f us/node\n", mode, mode == 0 ? "8 B kernarg" : mode == 1 ? "392 B kernarg" : mode == 2 ? "392 B + load/store" : "392 B + load/store + 40 KB LDS", blk, g, ms * 1e3 / reps, host_us, gms * 1e3 / 2000);
+                printf("[%d B struct] mode %d (%s) block %3d grid %4d: %.2f us/launch (host enqueue %.2f us), in a graph %.2f us/node\n", (int)sizeof(Big), mode, mode == 0 ? "8 B kernarg" : mode == 1 ? "392 B kernarg" : mode == 2 ? "392 B + load/store" : "392 B + load/store + 40 KB LDS", blk, g, ms * 1e3 / reps, host_us, gms * 1e3 / 2000);
             }
     return 0;
 }
