@@ -195,6 +195,8 @@ EXPORTS = [
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
     "armour_ws_tree_plan", "armour_ws_tree_plan_host",
+    "armour_ws_trees_create", "armour_ws_trees_create_host", "armour_ws_trees_destroy", "armour_ws_trees_grow", "armour_ws_trees_read",
+    "armour_debug_ws_trees_set_iterations",
     "armour_debug_block_steps", "armour_debug_block_split", "armour_debug_block_owner",
     "armour_debug_p2_plan", "armour_debug_p2_plan_shape",
 ]
@@ -353,6 +355,15 @@ def load():
         dp, dp, dp, ip, dp, ip, dp, dp]
     L.armour_ws_tree_plan.argtypes = ws           # (the last pointer: ms)
     L.armour_ws_tree_plan_host.argtypes = ws      # (the last pointer: margin [W])
+    if hasattr(L, "armour_ws_trees_create"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        trees = [dp, dp, C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_uint64)] + [C.c_double] * 6 + [C.c_int32, C.POINTER(vp)]
+        L.armour_ws_trees_create.argtypes = trees
+        L.armour_ws_trees_create_host.argtypes = trees
+        L.armour_ws_trees_destroy.argtypes = [vp]
+        L.armour_ws_trees_destroy.restype = None
+        L.armour_ws_trees_grow.argtypes = [vp, C.c_int32, ip, dp, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp, dp, ip, dp, dp]
+        L.armour_ws_trees_read.argtypes = [vp, C.c_int32, ip, dp, ip, dp, ip]
+        L.armour_debug_ws_trees_set_iterations.argtypes = [vp, C.c_int32, C.c_int32]
     L.armour_debug_block_steps.argtypes = [dp, ip, ip, ip, dp, ip, ip, ip, ip, ip]
     L.armour_debug_block_split.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip]
     L.armour_debug_block_owner.argtypes = [ip, C.c_int32, C.c_int32, ip, ip]

@@ -3,6 +3,8 @@
 // A node is a point of the workspace and a test is an axis-aligned box against an obstacle: rmgeo::pair_separated as it stands, with the
 // axes e_0, e_1, e_2.  What is new -- the difference and its squared length, S of an edge, one sub-segment's box, the steer step, the sample
 // and the cost of a node -- is written once below as __host__ __device__ code, run by the kernel's lanes and by armour_ws_tree_plan_host's loop.
+// The resident trees (armour_ws_trees_*, at the end of this file) are the same run resumed: the kernel's RESUMED form and the host loop with a
+// world's state go on from the tree, the iteration index and the rewire count that a handle keeps between calls.
 //
 // Nothing but __syncthreads() orders the block: a tree's nodes live in global memory, written and read by this block alone (keeping them
 // in LDS was measured and is a few per cent faster only where it fits, up to ~1700 nodes: DESIGN.md 4.12f); every decision
@@ -24,6 +26,7 @@ using namespace treeblk;   // the block shape, u(seed, i, j), key_less and, thro
 namespace {
 
 constexpr int WS_CAP = ARMOUR_WS_MAX_NODES;
+constexpr int WS_STATE = 4;                              // words of a resident tree's state: count, iterations done, rewires, (spare)
 constexpr int WS_PER_LANE = WS_CAP / TP_BLOCK;           // nodes per lane when the whole tree is dealt to the lanes: node t + k TP_BLOCK is lane t's k-th
 static_assert(WS_PER_LANE * TP_BLOCK == WS_CAP && WS_PER_LANE <= 32, "a lane keeps one bit per node of its own");
 
@@ -37,11 +40,16 @@ struct WsArgs {
     const uint64_t* seeds;
     int32_t *status, *iterations, *points, *rewires, *chain_kept, *count, *parent;
     double *path_cost, *goal_dist, *path, *nodes, *node_cost, *node_len;
+    // the resumed form alone (armour_ws_trees_grow): block / slot l serves world worlds[l]; state [W][WS_STATE] = a world's count, iterations
+    // done and rewires between calls
+    const int32_t* worlds;
+    int32_t* state;
 };
 // an entry's arguments as it was given them: the kernel's, and what only check_args reads (it copies the box to lb / ub)
 struct WsCall : WsArgs {
     const double *box_lb, *box_ub;
     int32_t W;
+    bool resident;   // armour_ws_trees_create: no starts and no outputs yet
 };
 
 // ---- the scalar steps of the rule, one copy
@@ -124,25 +132,37 @@ __device__ inline bool block_edge_free(WsShared& sh, const double* a, const doub
 }
 
 // grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The tree of world w: nodes [w][max_nodes][3], parent / node_cost / node_len [w][max_nodes].
+// RESUMED (armour_ws_trees_grow; grid L): slot l = blockIdx.x serves world w = worlds[l] -- the start and every output are slot l's, the
+// obstacles, the goal, the seed and the tree world w's -- and the tree goes on from state[w]: a planted tree (count > 0) skips the start test,
+// iteration i of this launch is iteration base + i of the world, and the state is written back at the end.  Not resumed, l = w, base = 0 and
+// every `RESUMED` below is a constant: the plan kernel is the code it was.
+template <bool RESUMED>
 __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
     extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
     __shared__ WsShared sh;
-    const int w = blockIdx.x, t = threadIdx.x, O = ar.O, cap = ar.max_nodes;
+    const int l = blockIdx.x, w = RESUMED ? ar.worlds[l] : l, t = threadIdx.x, O = ar.O, cap = ar.max_nodes;
     stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
     for (int c = t; c < cap; c += TP_BLOCK) sh.free_[c] = 0;
     const uint64_t seed = ar.seeds[w];
     const double buf = ar.buffer, rr2 = ar.rewire_radius * ar.rewire_radius;
+    int cnt = 0, base = 0, rewires = 0;
+    if (RESUMED) {
+        cnt = ar.state[(size_t)w * WS_STATE];
+        base = ar.state[(size_t)w * WS_STATE + 1];
+        rewires = ar.state[(size_t)w * WS_STATE + 2];
+    }
+    const bool planted = RESUMED && cnt > 0;                // (the same in every lane) the start is not read
     double start[3], goal[3];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        start[j] = ar.starts[(size_t)w * 3 + j];
+        start[j] = planted ? 0.0 : ar.starts[(size_t)l * 3 + j];
         goal[j] = ar.goals[(size_t)w * 3 + j];
     }
     double* nx = ar.nodes + (size_t)w * cap * 3;
     double* ncost = ar.node_cost + (size_t)w * cap;
     double* nlen = ar.node_len + (size_t)w * cap;
     int32_t* par = ar.parent + (size_t)w * cap;
-    int cnt = 0, status = ARMOUR_WS_START_BLOCKED, iterations = 0, points = 0, rewires = 0, kept = 0;
+    int status = ARMOUR_WS_START_BLOCKED, iterations = 0, points = 0, kept = 0;
     double path_cost = 0.0, goal_dist;
     {
         double D[3];
@@ -151,16 +171,18 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
 
     // ---- the point rule at start: the obstacles dealt to the lanes
     bool hit = false;
-    {
+    if (!planted) {
         const double h[3] = {buf, buf, buf};
         for (int o = t; o < O; o += TP_BLOCK) hit = hit || !ws_box_free(start, h, s_obs, o, o + 1);
     }
-    if (!block_any(sh.any, hit)) {
-        if (t < 3) nx[t] = pick3(start, t);
-        if (t == 0) { par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0; }
-        cnt = 1;
+    if (planted || !block_any(sh.any, hit)) {
+        if (!planted) {
+            if (t < 3) nx[t] = pick3(start, t);
+            if (t == 0) { par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0; }
+            cnt = 1;
+        }
         // ---- the initial chain: edge by edge from the last kept node, up to the first edge that is not free
-        const int chain = ar.init ? ar.init_count[w] : 0;
+        const int chain = !RESUMED && ar.init ? ar.init_count[w] : 0;
         double prev[3] = {start[0], start[1], start[2]}, prev_cost = 0.0;
         for (int c = 0; c < chain && cnt < cap; c++) {
             double x[3], D[3];
@@ -176,13 +198,13 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
             cnt++;
             kept++;
         }
-        iterations = ar.max_iterations;
+        iterations = base + ar.max_iterations;
         for (int i = 0; i < ar.max_iterations; i++) {
-            if (cnt >= cap) { iterations = i; break; }
-            __syncthreads();                                // the nodes, parents and costs of iteration i - 1 are written
+            if (cnt >= cap) { iterations = base + i; break; }
+            __syncthreads();                                // the nodes, parents and costs of iteration i - 1 (or of the launch before) are written
             // ---- sample (every lane: the same arithmetic on the same values), nearest, steer
             double qr[3], qn[3], D[3];
-            ws_sample(ar, seed, i, goal, qr);
+            ws_sample(ar, seed, base + i, goal, qr);
             double acc = INFINITY;
             int v = TP_NONE;
             for (int c = t; c < cnt; c += TP_BLOCK) {
@@ -319,20 +341,25 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
         for (int x = best; x >= 0 && x < cnt && len < cnt; x = par[x]) len++;
         points = len;
         if (ar.path && points <= ar.max_points && t < 3) {
-            double* out = ar.path + ((size_t)w * ar.max_points) * 3;
+            double* out = ar.path + ((size_t)l * ar.max_points) * 3;
             int pos = len - 1, d = 0;
             for (int x = best; d < len; x = par[x], d++, pos--) out[(size_t)pos * 3 + t] = nx[(size_t)x * 3 + t];
         }
     }
     if (t == 0) {
-        ar.status[w] = status;
-        ar.iterations[w] = iterations;
-        ar.points[w] = points;
-        ar.rewires[w] = rewires;
-        ar.chain_kept[w] = kept;
-        ar.count[w] = cnt;
-        ar.path_cost[w] = path_cost;
-        ar.goal_dist[w] = goal_dist;
+        ar.status[l] = status;
+        ar.iterations[l] = iterations;
+        ar.points[l] = points;
+        ar.rewires[l] = rewires;
+        ar.chain_kept[l] = kept;
+        ar.count[l] = cnt;
+        ar.path_cost[l] = path_cost;
+        ar.goal_dist[l] = goal_dist;
+        if (RESUMED) {                                      // (a blocked start leaves count 0, 0 iterations, 0 rewires)
+            ar.state[(size_t)w * WS_STATE] = cnt;
+            ar.state[(size_t)w * WS_STATE + 1] = iterations;
+            ar.state[(size_t)w * WS_STATE + 2] = rewires;
+        }
     }
 }
 
@@ -365,27 +392,32 @@ struct WsHost {
     }
 };
 
-// world w of the host twin; the tree goes to nx [max_nodes][3] / par / ncost / nlen [max_nodes] (the caller's rows or scratch)
-void plan_world_host(const WsArgs& ar, int w, const double* obs, double* nx, int32_t* par, double* ncost, double* nlen, double* margin) {
+// slot l = world w of the host twin (the plan entry: l = w); the tree goes to nx [max_nodes][3] / par / ncost / nlen [max_nodes] (the caller's
+// rows or scratch).  state (null: the plan entry): world w's WS_STATE words of a handle -- the run resumes the tree they describe, as the
+// kernel's resumed form does, and writes them back.
+void plan_world_host(const WsArgs& ar, int l, int w, const double* obs, double* nx, int32_t* par, double* ncost, double* nlen, double* margin, int32_t* state) {
     const int cap = ar.max_nodes;
-    const double* start = ar.starts + (size_t)w * 3;
     const double* goal = ar.goals + (size_t)w * 3;
     const uint64_t seed = ar.seeds[w];
     const double rr2 = ar.rewire_radius * ar.rewire_radius;
     if (margin) *margin = INFINITY;
     const WsHost hw{obs, ar.O, ar.buffer, ar.edge_step, margin};
     double D[3];
-    int cnt = 0, rewires = 0, kept = 0;
-    ar.status[w] = ARMOUR_WS_START_BLOCKED;
-    ar.iterations[w] = ar.points[w] = ar.rewires[w] = ar.chain_kept[w] = 0;
-    if (ar.count) ar.count[w] = 0;
-    ar.path_cost[w] = 0.0;
-    ar.goal_dist[w] = sqrt(ws_diff(start, goal, D));
-    if (!hw.point(start)) return;
-    std::memcpy(nx, start, 3 * sizeof(double));
-    par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0;
-    cnt = 1;
-    const int chain = ar.init ? ar.init_count[w] : 0;
+    int cnt = state ? state[0] : 0, rewires = state ? state[2] : 0, kept = 0;
+    const int base = state ? state[1] : 0;
+    if (cnt == 0) {
+        const double* start = ar.starts + (size_t)l * 3;
+        ar.status[l] = ARMOUR_WS_START_BLOCKED;
+        ar.iterations[l] = ar.points[l] = ar.rewires[l] = ar.chain_kept[l] = 0;
+        if (ar.count) ar.count[l] = 0;
+        ar.path_cost[l] = 0.0;
+        ar.goal_dist[l] = sqrt(ws_diff(start, goal, D));
+        if (!hw.point(start)) return;
+        std::memcpy(nx, start, 3 * sizeof(double));
+        par[0] = -1; ncost[0] = 0.0; nlen[0] = 0.0;
+        cnt = 1;
+    }
+    const int chain = !state && ar.init ? ar.init_count[w] : 0;
     for (int c = 0; c < chain && cnt < cap; c++) {
         const double* x = ar.init + ((size_t)w * ar.max_init + c) * 3;
         const double* prev = nx + (size_t)(cnt - 1) * 3;
@@ -396,13 +428,13 @@ void plan_world_host(const WsArgs& ar, int w, const double* obs, double* nx, int
         cnt++;
         kept++;
     }
-    int iterations = ar.max_iterations;
+    int iterations = base + ar.max_iterations;
     std::vector<int> free_c;
     std::vector<double> free_d;
     for (int i = 0; i < ar.max_iterations; i++) {
-        if (cnt >= cap) { iterations = i; break; }
+        if (cnt >= cap) { iterations = base + i; break; }
         double qr[3], qn[3];
-        ws_sample(ar, seed, i, goal, qr);
+        ws_sample(ar, seed, base + i, goal, qr);
         double acc = INFINITY;
         int v = TP_NONE;
         for (int c = 0; c < cnt; c++) {
@@ -456,29 +488,31 @@ void plan_world_host(const WsArgs& ar, int w, const double* obs, double* nx, int
     const int best = bi != TP_NONE ? bi : ai;
     int len = 0;
     for (int x = best; x >= 0 && x < cnt && len < cnt; x = par[x]) len++;
-    ar.status[w] = bi != TP_NONE ? ARMOUR_WS_REACHED : ARMOUR_WS_PARTIAL;
-    ar.iterations[w] = iterations;
-    ar.points[w] = len;
-    ar.rewires[w] = rewires;
-    ar.chain_kept[w] = kept;
-    if (ar.count) ar.count[w] = cnt;
-    ar.path_cost[w] = ncost[best];
-    ar.goal_dist[w] = sqrt(ws_diff(nx + (size_t)best * 3, goal, D));
+    ar.status[l] = bi != TP_NONE ? ARMOUR_WS_REACHED : ARMOUR_WS_PARTIAL;
+    ar.iterations[l] = iterations;
+    ar.points[l] = len;
+    ar.rewires[l] = rewires;
+    ar.chain_kept[l] = kept;
+    if (ar.count) ar.count[l] = cnt;
+    ar.path_cost[l] = ncost[best];
+    ar.goal_dist[l] = sqrt(ws_diff(nx + (size_t)best * 3, goal, D));
+    if (state) { state[0] = cnt; state[1] = iterations; state[2] = rewires; }
     if (ar.path && len <= ar.max_points) {
-        double* out = ar.path + ((size_t)w * ar.max_points) * 3;
+        double* out = ar.path + ((size_t)l * ar.max_points) * 3;
         int pos = len - 1, d = 0;
         for (int x = best; d < len; x = par[x], d++, pos--) std::memcpy(out + (size_t)pos * 3, nx + (size_t)x * 3, 3 * sizeof(double));
     }
 }
 
-// the argument rules of both entries, before a device is touched, on ar as the entry filled it; fills ar.lb / ar.ub and drops a chain's
-// length and counts when there is no chain
+// the argument rules of the plan entries and of armour_ws_trees_create (`resident`: everything but the starts and the outputs, which come with
+// a grow), before a device is touched, on ar as the entry filled it; fills ar.lb / ar.ub and drops a chain's length and counts when there is
+// no chain
 int check_args(const char* who, WsCall* ar) {
     const int32_t W = ar->W, O = ar->O, max_init = ar->max_init;
     const double step = ar->step, edge_step = ar->edge_step, rewire_radius = ar->rewire_radius;
     if (!ar->box_lb || !ar->box_ub) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
     ARMOUR_TRY(armour_check_world_counts(who, W, O, ar->obstacles));
-    if (W > 0 && (!ar->starts || !ar->goals || !ar->seeds || !ar->status || !ar->iterations || !ar->points || !ar->rewires || !ar->chain_kept || !ar->path_cost || !ar->goal_dist)) {
+    if (W > 0 && (!ar->goals || !ar->seeds || (!ar->resident && (!ar->starts || !ar->status || !ar->iterations || !ar->points || !ar->rewires || !ar->chain_kept || !ar->path_cost || !ar->goal_dist)))) {
         armour_set_error("%s: null argument", who);
         return ARMOUR_EINVAL;
     }
@@ -494,7 +528,7 @@ int check_args(const char* who, WsCall* ar) {
         return ARMOUR_EINVAL;
     }
     ARMOUR_TRY(armour_check_box(who, "sampling box", "axis", 3, ar->box_lb, ar->box_ub));
-    if (!finite_all(ar->obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || !finite_all(ar->starts, (size_t)W * 3) || !finite_all(ar->goals, (size_t)W * 3)) {
+    if (!finite_all(ar->obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES) || (!ar->resident && !finite_all(ar->starts, (size_t)W * 3)) || !finite_all(ar->goals, (size_t)W * 3)) {
         armour_set_error("%s: a start, a goal or an obstacle is not finite", who);
         return ARMOUR_EINVAL;
     }
@@ -547,8 +581,8 @@ extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int3
     std::vector<double> own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);
     std::vector<int32_t> own_parent(parent ? 0 : cap);
     for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) {
-        plan_world_host(ar, w, obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
-                        node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr);
+        plan_world_host(ar, w, w, obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
+                        node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr, nullptr);
     });
     return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
 }
@@ -601,7 +635,7 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
     dev.path_cost = real.column(0); dev.goal_dist = real.column(1);
     dev.parent = d_parent; dev.nodes = d_nodes; dev.node_cost = d_cost; dev.node_len = d_len; dev.path = path ? d_path.p : nullptr;
     ARMOUR_TRY(ev.record_start(st));
-    hipLaunchKernelGGL(ws_tree_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, dev);
+    hipLaunchKernelGGL(ws_tree_kernel<false>, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, dev);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
     ARMOUR_TRY(out.fetch(st));
@@ -624,4 +658,216 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
     }
     HIPCHK(hipStreamSynchronize(st));
     return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
+}
+
+// ---- resident trees (include/armour_hip.h, armour_ws_trees_*): the trees of W worlds kept between calls and grown in instalments by the
+// kernel's resumed form (the host handle: by plan_world_host with the world's state)
+struct ArmourWsTrees {
+    int device = 0;                      // < 0: a handle of armour_ws_trees_create_host (no stream, no device buffers)
+    int32_t W = 0;
+    WsArgs args{};                       // the fixed parameters (box, steps, O, max_nodes); every pointer is set per call
+    std::vector<double> obstacles, goals;        // [W][O][12], [W][3]
+    std::vector<uint64_t> seeds;                 // [W]
+    std::vector<int32_t> state;                  // [W][WS_STATE]: the host handle's state; a device handle's copy of what its kernel wrote back
+    // the host handle's trees
+    std::vector<double> nodes, node_cost, node_len;
+    std::vector<int32_t> parent;
+    // the device handle's: uploaded and reserved by the first grow that launches (create touches no device)
+    bool on_device = false;
+    DevStream stream;
+    EventPair ev;
+    DevBuf<double> d_obs, d_goals, d_nodes, d_cost, d_len, d_starts, d_path;
+    DevBuf<uint64_t> d_seeds;
+    DevBuf<int32_t> d_parent, d_state, d_worlds;
+    DevColumns<int32_t> out;             // status | iterations | points | rewires | chain_kept | count [L] each
+    DevColumns<double> real;             // path_cost | goal_dist [L] each
+};
+
+namespace {
+
+int trees_create(const char* who, bool host, const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* goals, const uint64_t* seeds,
+                 double step, double edge_step, double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_nodes, ArmourWsTrees** out) {
+    if (!out) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    *out = nullptr;
+    WsCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.goals = goals; ar.seeds = seeds; ar.step = step; ar.edge_step = edge_step;
+    ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate; ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_nodes = max_nodes; ar.resident = true;
+    ARMOUR_TRY(check_args(who, &ar));
+    ArmourWsTrees* h = new ArmourWsTrees;
+    h->device = host ? -1 : 0;
+    h->W = W;
+    h->args = ar;                                           // (the kernel's part)
+    h->args.obstacles = h->args.goals = nullptr;
+    h->args.seeds = nullptr;
+    if (W > 0 && O > 0) h->obstacles.assign(obstacles, obstacles + (size_t)W * O * ARMOUR_OBS_DOUBLES);
+    if (W > 0) {
+        h->goals.assign(goals, goals + (size_t)W * 3);
+        h->seeds.assign(seeds, seeds + (size_t)W);
+    }
+    h->state.assign((size_t)W * WS_STATE, 0);
+    if (host) {
+        const size_t rows = (size_t)W * max_nodes;
+        h->nodes.assign(rows * 3, 0.0);
+        h->node_cost.assign(rows, 0.0);
+        h->node_len.assign(rows, 0.0);
+        h->parent.assign(rows, 0);
+    }
+    *out = h;
+    return ARMOUR_OK;
+}
+
+// the index list of a grow or a read: every entry in [0, W); `seen` (grow): no world twice, because two blocks would write one tree
+int check_worlds(const char* who, const ArmourWsTrees* h, int32_t L, const int32_t* worlds, std::vector<uint8_t>* seen) {
+    if (!h || L < 0 || (L > 0 && !worlds)) { armour_set_error("%s: null argument or L = %d", who, L); return ARMOUR_EINVAL; }
+    if (seen) seen->assign((size_t)h->W, 0);
+    for (int32_t l = 0; l < L; l++) {
+        const int32_t w = worlds[l];
+        if (w < 0 || w >= h->W) { armour_set_error("%s: worlds[%d] = %d (0..%d)", who, l, w, h->W - 1); return ARMOUR_EINVAL; }
+        if (seen && (*seen)[w]) { armour_set_error("%s: world %d is listed twice", who, w); return ARMOUR_EINVAL; }
+        if (seen) (*seen)[w] = 1;
+    }
+    return ARMOUR_OK;
+}
+
+// the device handle's fixed inputs and tree storage, once
+int trees_to_device(ArmourWsTrees* h) {
+    if (h->on_device) return ARMOUR_OK;
+    const size_t rows = (size_t)h->W * h->args.max_nodes;
+    ARMOUR_TRY(h->stream.create());
+    ARMOUR_TRY(h->d_obs.upload(h->obstacles.data(), h->obstacles.size(), h->stream));
+    ARMOUR_TRY(h->d_goals.upload(h->goals.data(), h->goals.size(), h->stream));
+    ARMOUR_TRY(h->d_seeds.upload(h->seeds.data(), h->seeds.size(), h->stream));
+    ARMOUR_TRY(h->d_state.upload(h->state.data(), h->state.size(), h->stream));
+    ARMOUR_TRY(h->d_nodes.reserve(rows * 3));
+    ARMOUR_TRY(h->d_cost.reserve(rows));
+    ARMOUR_TRY(h->d_len.reserve(rows));
+    ARMOUR_TRY(h->d_parent.reserve(rows));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->on_device = true;
+    return ARMOUR_OK;
+}
+
+}  // namespace
+
+extern "C" int armour_ws_trees_create(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* goals, const uint64_t* seeds,
+                                      double step, double edge_step, double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_nodes,
+                                      ArmourWsTrees** out) {
+    return trees_create("armour_ws_trees_create", false, lb, ub, W, O, obstacles, goals, seeds, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol, max_nodes, out);
+}
+
+extern "C" int armour_ws_trees_create_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* goals, const uint64_t* seeds,
+                                           double step, double edge_step, double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_nodes,
+                                           ArmourWsTrees** out) {
+    return trees_create("armour_ws_trees_create_host", true, lb, ub, W, O, obstacles, goals, seeds, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol, max_nodes, out);
+}
+
+extern "C" void armour_ws_trees_destroy(ArmourWsTrees* trees) { delete trees; }
+
+// test hook: what world `world` counts as its iterations done, so that the INT32_MAX rule of a grow can be reached without 2^31 iterations
+extern "C" int armour_debug_ws_trees_set_iterations(ArmourWsTrees* h, int32_t world, int32_t done) {
+    const char* who = "armour_debug_ws_trees_set_iterations";
+    if (!h || world < 0 || world >= h->W || done < 0) { armour_set_error("%s: world = %d, done = %d", who, world, done); return ARMOUR_EINVAL; }
+    if (h->on_device) { armour_set_error("%s: the handle's state is on the device", who); return ARMOUR_ESTATE; }
+    h->state[(size_t)world * WS_STATE + 1] = done;
+    return ARMOUR_OK;
+}
+
+extern "C" int armour_ws_trees_grow(ArmourWsTrees* h, int32_t L, const int32_t* worlds, const double* starts, int32_t iterations, int32_t max_points, int32_t* status,
+                                    int32_t* iterations_done, int32_t* points, int32_t* rewires, double* path_cost, double* goal_dist, double* path, int32_t* count,
+                                    double* ms, double* margin) {
+    const char* who = "armour_ws_trees_grow";
+    std::vector<uint8_t> seen;
+    ARMOUR_TRY(check_worlds(who, h, L, worlds, &seen));
+    if (iterations < 0 || iterations > ARMOUR_TREE_MAX_ITERATIONS || max_points < 0) {
+        armour_set_error("%s: iterations = %d (0..%d), max_points = %d", who, iterations, ARMOUR_TREE_MAX_ITERATIONS, max_points);
+        return ARMOUR_EINVAL;
+    }
+    if (L > 0 && (!status || !iterations_done || !points || !rewires || !path_cost || !goal_dist)) { armour_set_error("%s: null argument", who); return ARMOUR_EINVAL; }
+    if (margin && h->device >= 0) { armour_set_error("%s: margin is the host handle's (armour_ws_trees_create_host)", who); return ARMOUR_EINVAL; }
+    for (int32_t l = 0; l < L; l++) {
+        const int32_t* st = &h->state[(size_t)worlds[l] * WS_STATE];
+        if (st[1] > INT32_MAX - iterations) { armour_set_error("%s: world %d has run %d iterations: %d more pass INT32_MAX", who, worlds[l], st[1], iterations); return ARMOUR_EINVAL; }
+        if (st[0] == 0 && (!starts || !finite_all(starts + (size_t)l * 3, 3))) { armour_set_error("%s: world %d's tree is empty and starts[%d] is not finite", who, worlds[l], l); return ARMOUR_EINVAL; }
+    }
+    if (ms) *ms = 0.0;
+    if (L == 0) return ARMOUR_OK;
+    const int32_t O = h->args.O;
+    const size_t cap = (size_t)h->args.max_nodes;
+    WsArgs ar = h->args;
+    ar.max_iterations = iterations; ar.max_points = max_points;
+    if (h->device < 0) {
+        std::vector<int32_t> kept((size_t)L);
+        ar.starts = starts; ar.goals = h->goals.data(); ar.seeds = h->seeds.data();
+        ar.status = status; ar.iterations = iterations_done; ar.points = points; ar.rewires = rewires; ar.chain_kept = kept.data(); ar.count = count;
+        ar.path_cost = path_cost; ar.goal_dist = goal_dist; ar.path = path;
+        for_each_staged(L, O, h->obstacles.data(), worlds, [&](int32_t l, const double* obs, int) {
+            const size_t row = (size_t)worlds[l] * cap;
+            plan_world_host(ar, l, worlds[l], obs, &h->nodes[row * 3], &h->parent[row], &h->node_cost[row], &h->node_len[row], margin ? margin + l : nullptr,
+                            &h->state[(size_t)worlds[l] * WS_STATE]);
+        });
+        return armour_check_path_capacity(who, L, points, max_points, path != nullptr);
+    }
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ws_trees_create_host makes the host form)", who); return ARMOUR_EDEVICE; }
+    ARMOUR_TRY(trees_to_device(h));
+    hipStream_t st = h->stream;
+    const size_t path_len = path ? (size_t)L * max_points * 3 : 0;
+    ARMOUR_TRY(h->d_worlds.upload(worlds, (size_t)L, st));
+    ARMOUR_TRY(h->d_starts.upload(starts, (size_t)L * 3, st));       // (starts may be null when every listed tree is planted: reserved, never read)
+    ARMOUR_TRY(h->out.reserve(6, (size_t)L));
+    ARMOUR_TRY(h->real.reserve(2, (size_t)L));
+    if (path) ARMOUR_TRY(h->d_path.reserve(path_len));
+    ar.obstacles = h->d_obs; ar.starts = h->d_starts; ar.goals = h->d_goals; ar.seeds = h->d_seeds; ar.worlds = h->d_worlds; ar.state = h->d_state;
+    ar.status = h->out.column(0); ar.iterations = h->out.column(1); ar.points = h->out.column(2); ar.rewires = h->out.column(3);
+    ar.chain_kept = h->out.column(4); ar.count = h->out.column(5);
+    ar.path_cost = h->real.column(0); ar.goal_dist = h->real.column(1);
+    ar.parent = h->d_parent; ar.nodes = h->d_nodes; ar.node_cost = h->d_cost; ar.node_len = h->d_len; ar.path = path ? h->d_path.p : nullptr;
+    ARMOUR_TRY(h->ev.record_start(st));
+    hipLaunchKernelGGL(ws_tree_kernel<true>, dim3((unsigned)L), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, ar);
+    HIPCHK(hipGetLastError());
+    ARMOUR_TRY(h->ev.record_stop(st));
+    ARMOUR_TRY(h->out.fetch(st));
+    ARMOUR_TRY(h->real.fetch(st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ms) ARMOUR_TRY(h->ev.elapsed_ms(ms));
+    int32_t* const ints[6] = {status, iterations_done, points, rewires, nullptr, count};
+    for (int k = 0; k < 6; k++) h->out.copy_out(k, ints[k]);
+    h->real.copy_out(0, path_cost);
+    h->real.copy_out(1, goal_dist);
+    const int32_t* h_count = h->out.fetched(5);
+    bool any_path = false;
+    for (int32_t l = 0; l < L; l++) {
+        int32_t* s = &h->state[(size_t)worlds[l] * WS_STATE];
+        s[0] = h_count[l]; s[1] = iterations_done[l]; s[2] = rewires[l];
+        if (path && points[l] > 0 && points[l] <= max_points) {
+            HIPCHK(hipMemcpyAsync(path + (size_t)l * max_points * 3, h->d_path + (size_t)l * max_points * 3, (size_t)points[l] * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            any_path = true;
+        }
+    }
+    if (any_path) HIPCHK(hipStreamSynchronize(st));
+    return armour_check_path_capacity(who, L, points, max_points, path != nullptr);
+}
+
+extern "C" int armour_ws_trees_read(ArmourWsTrees* h, int32_t L, const int32_t* worlds, double* nodes, int32_t* parent, double* node_cost, int32_t* count) {
+    const char* who = "armour_ws_trees_read";
+    ARMOUR_TRY(check_worlds(who, h, L, worlds, nullptr));
+    const size_t cap = (size_t)h->args.max_nodes;
+    bool copied = false;
+    for (int32_t l = 0; l < L; l++) {
+        const size_t c = (size_t)h->state[(size_t)worlds[l] * WS_STATE], src = (size_t)worlds[l] * cap, dst = (size_t)l * cap;
+        if (count) count[l] = (int32_t)c;
+        if (!c) continue;
+        if (h->device < 0) {
+            if (nodes) std::memcpy(nodes + dst * 3, &h->nodes[src * 3], c * 3 * sizeof(double));
+            if (parent) std::memcpy(parent + dst, &h->parent[src], c * sizeof(int32_t));
+            if (node_cost) std::memcpy(node_cost + dst, &h->node_cost[src], c * sizeof(double));
+            continue;
+        }
+        hipStream_t st = h->stream;                         // (count > 0: a grow has launched, so the trees are on the device)
+        if (nodes) HIPCHK(hipMemcpyAsync(nodes + dst * 3, h->d_nodes + src * 3, c * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (parent) HIPCHK(hipMemcpyAsync(parent + dst, h->d_parent + src, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (node_cost) HIPCHK(hipMemcpyAsync(node_cost + dst, h->d_cost + src, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        copied = true;
+    }
+    if (copied) HIPCHK(hipStreamSynchronize(h->stream));
+    return ARMOUR_OK;
 }

@@ -10,9 +10,12 @@ are solved by one armour_ik call:
     z_des = waypoint_along_points(res.paths[w], z, 0.1)                    # the point 0.1 m past z's projection on the path
     hlp = WorkspaceTreeHLP(robot, world_obstacles, goal); q_des = hlp.get_waypoint(q_cur, 0.1)
     out = run_trials(worlds, hlp=workspace_hlps(worlds, robot))            # the end-effector planner as the trials' high-level planner
+    trees = WorkspaceTrees(obstacles, goals, seeds, lb, ub)                # resident trees: the reference's grow_tree_mode = 'keep'
+    res = trees.grow(worlds, starts, 100)                                  # 100 more iterations for the listed worlds -> WorkspacePlans
+    out = run_trials(worlds, hlp=workspace_hlps(worlds, robot, mode='keep', max_iterations=100, max_nodes=4096))
 
 The rule (point and edge tests, samples, parent choice, rewiring, cost re-derivation, best node), its two deliberate departures from the
-reference, the soundness arguments and the limits are stated in include/armour_hip.h; DESIGN.md 4.12f.
+reference, the soundness arguments and the limits are stated in include/armour_hip.h; DESIGN.md 4.12f, and 4.12g for the resident trees.
 """
 import ctypes as C
 
@@ -21,6 +24,7 @@ import numpy as np
 from . import _lib
 from ._lib import _dp, check
 from . import ik
+from .scenes import pad_obstacles
 from .tree_planner import call_seed, hlp_factory
 
 PARTIAL, REACHED, START_BLOCKED = _lib.WS_PARTIAL, _lib.WS_REACHED, _lib.WS_START_BLOCKED
@@ -97,6 +101,78 @@ def plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, step=STEP, edg
     return out
 
 
+class WorkspaceTrees:
+    """Resident workspace trees (include/armour_hip.h, armour_ws_trees_*): the trees of W worlds with fixed obstacles [W,O,12], goals [W,3],
+    seeds [W] and parameters, kept between calls and grown in instalments -- the reference's grow_tree_mode = 'keep'.  After grows of
+    n_1, ..., n_k iterations a world's tree, its cumulative iterations / rewires and the last grow's status and path are bit for bit those
+    of plan_workspace_trees from the point that planted it with max_iterations = sum n.  host=True: the library's host loop (no device).
+      grow(worlds, starts, iterations, margin=False) -> WorkspacePlans, one entry per listed world, in that order
+      read(worlds) -> Result(nodes [L,max_nodes,3], parent [L,max_nodes], node_cost [L,max_nodes], count [L]) (rows past count are zero)
+      close() frees the handle (also on garbage collection)."""
+    handles_created = 0                   # over the process: a batched 'keep' planner makes ONE for all its worlds
+
+    def __init__(self, obstacles, goals, seeds, lb, ub, step=STEP, edge_step=EDGE_STEP, rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE, buffer=0.0,
+                 goal_tol=GOAL_TOL, max_nodes=MAX_NODES, host=False):
+        self._h = None
+        L = _lib.load()
+        obs, W, O = _lib.as_worlds(obstacles)
+        g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(W, 3))
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (W,)))
+        lb = np.ascontiguousarray(lb, dtype=np.float64).reshape(3)
+        ub = np.ascontiguousarray(ub, dtype=np.float64).reshape(3)
+        self.W, self.O, self.max_nodes, self.host = W, O, int(max_nodes), bool(host)
+        h = C.c_void_p()
+        fn = L.armour_ws_trees_create_host if host else L.armour_ws_trees_create
+        check(fn(_dp(lb), _dp(ub), W, O, _dp(obs) if obs.size else None, _dp(g), sd.ctypes.data_as(C.POINTER(C.c_uint64)), float(step), float(edge_step),
+                 float(rewire_radius), float(goal_rate), float(buffer), float(goal_tol), self.max_nodes, C.byref(h)))
+        self._h = h
+        WorkspaceTrees.handles_created += 1
+
+    def _worlds(self, worlds):
+        return np.ascontiguousarray(np.asarray(worlds, dtype=np.int32).reshape(-1))
+
+    def grow(self, worlds, starts, iterations, margin=False, max_points=None):
+        """worlds [L] (indices, none twice), starts [L,3] (read only for the worlds whose tree is empty; None when none is), `iterations`
+        more iterations for each -> WorkspacePlans (iterations / rewires cumulative; chain_kept zeros; margin [L] of THIS call when asked
+        for, host handles only)."""
+        wl = self._worlds(worlds)
+        n = len(wl)
+        s = None if starts is None else np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(n, 3))
+        max_points = self.max_nodes if max_points is None else int(max_points)
+        i32 = C.POINTER(C.c_int32)
+        status, iterations_done, points, rewires, count = (np.zeros(n, dtype=np.int32) for _ in range(5))
+        path_cost, goal_dist = np.zeros(n), np.zeros(n)
+        path = np.zeros((n, max(max_points, 0), 3))
+        mg = np.zeros(n) if margin else None
+        ms = C.c_double()
+        check(_lib.load().armour_ws_trees_grow(self._h, n, wl.ctypes.data_as(i32), _dp(s), int(iterations), max_points, status.ctypes.data_as(i32),
+                                              iterations_done.ctypes.data_as(i32), points.ctypes.data_as(i32), rewires.ctypes.data_as(i32), _dp(path_cost),
+                                              _dp(goal_dist), _dp(path), count.ctypes.data_as(i32), C.byref(ms), _dp(mg)))
+        paths = [path[k, :points[k]].copy() if status[k] != START_BLOCKED else None for k in range(n)]
+        return WorkspacePlans(status=status, iterations=iterations_done, rewires=rewires, chain_kept=np.zeros(n, dtype=np.int32), count=count, path_cost=path_cost,
+                              goal_dist=goal_dist, paths=paths, nodes=None, parent=None, node_cost=None, margin=mg, ms=ms.value)
+
+    def read(self, worlds):
+        wl = self._worlds(worlds)
+        n = len(wl)
+        i32 = C.POINTER(C.c_int32)
+        nodes, parent, node_cost = np.zeros((n, self.max_nodes, 3)), np.zeros((n, self.max_nodes), dtype=np.int32), np.zeros((n, self.max_nodes))
+        count = np.zeros(n, dtype=np.int32)
+        check(_lib.load().armour_ws_trees_read(self._h, n, wl.ctypes.data_as(i32), _dp(nodes), parent.ctypes.data_as(i32), _dp(node_cost), count.ctypes.data_as(i32)))
+        return _lib.Result(nodes=nodes, parent=parent, node_cost=node_cost, count=count)
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().armour_ws_trees_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _project(path, z):
     """(segment, t, distance along the path) of the point of the polyline nearest to z; the first segment on a tie."""
     best, along = None, 0.0
@@ -139,12 +215,23 @@ class WorkspaceTreeHLP:
       mode='new' (the default; the reference's grow_tree_mode = 'new'): a fresh tree at every call.
       mode='seed': [the current point] + the rest of the last path, from the vertex after the one nearest to the current point, is offered
         as the initial chain.
+      mode='keep' (the reference's grow_tree_mode = 'keep', the mode of its hard scenarios): the tree planted at the first call stays in a
+        WorkspaceTrees handle and every call grows it by max_iterations more iterations (the tree's seed is call_seed(seed, world, 0), fixed;
+        max_nodes bounds the tree over ALL calls); the waypoint is taken on the tree's current best path from the projection of the current
+        point, as ever.  A call whose start is blocked while the tree is empty falls back to the goal and the next call plants from the
+        new point.  The object does not own its tree: `trees` is the WorkspaceTrees that holds it (or a callable that returns it, called
+        at the first waypoint) and `slot` this world's index there -- made from this world's padded obstacles, goal POINT and
+        call_seed(seed, world, 0), as workspace_hlps does for all its worlds at once; whoever made the handle closes it.  mode='keep'
+        without `trees` is a ValueError.
     plan_options go to plan_workspace_trees (step, edge_step, rewire_radius, goal_rate, buffer, goal_tol, max_iterations, max_nodes; lb /
     ub default to workspace_box); ik_options go to ik.solve_ik (S, lam, e_max, tol, max_iterations, tool)."""
 
-    def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, mode="new", ik_reference="mid", ik_options=None, **plan_options):
-        if mode not in ("new", "seed") or ik_reference not in ("mid", "current"):
-            raise ValueError(f"mode = {mode!r} ('new' or 'seed'), ik_reference = {ik_reference!r} ('mid' or 'current')")
+    def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, mode="new", ik_reference="mid", ik_options=None, trees=None, slot=0,
+                 **plan_options):
+        if mode not in ("new", "seed", "keep") or ik_reference not in ("mid", "current"):
+            raise ValueError(f"mode = {mode!r} ('new', 'seed' or 'keep'), ik_reference = {ik_reference!r} ('mid' or 'current')")
+        if (mode == "keep") != (trees is not None):
+            raise ValueError("mode = 'keep' takes the WorkspaceTrees that holds this world's tree (trees=, slot=), and no other mode does")
         self.robot, self.goal, self.seed, self.world, self.host = robot, np.asarray(goal, dtype=np.float64), int(seed), int(world), bool(host)
         self.mode, self.ik_reference = mode, ik_reference
         self.obstacles = np.asarray(world_obstacles, dtype=np.float64).reshape(-1, 12)
@@ -156,9 +243,43 @@ class WorkspaceTreeHLP:
         self.goal_point = ik.end_effector(robot, self.goal, self.ik_options.get("tool"))
         self.calls, self.path, self.status, self.ik_status, self.waypoint, self.margin_min = 0, None, None, None, None, np.inf
         self.fallbacks = 0                 # calls that returned the goal configuration
+        self.trees, self.slot, self.count = trees, int(slot), 0      # 'keep': the handle (a callable: made at the first call), this world's index in it, the tree's nodes
+
+    def _handle(self):
+        """'keep': the handle that holds this world's tree"""
+        if callable(self.trees):
+            self.trees = self.trees()
+        return self.trees
 
     def get_waypoint(self, q_cur, lookahead):
         return _waypoints([self], [q_cur], [lookahead])[0][0]
+
+
+def keep_trees(obstacles, goal_points, seeds, host, options):
+    """The WorkspaceTrees of a 'keep' planner from its plan options (max_iterations is a grow's, not the handle's)"""
+    o = {k: v for k, v in options.items() if k != "max_iterations"}
+    return WorkspaceTrees(obstacles, np.stack(goal_points), np.array(seeds, dtype=np.uint64), host=host, **o)
+
+
+def _grow_kept(hl, z):
+    """One instalment for each of the 'keep' HLPs `hl` from the points z: ONE armour_ws_trees_grow call per handle (the batched factory's
+    worlds share one) -> a WorkspacePlans in hl's order"""
+    iterations = hl[0].options.get("max_iterations", MAX_ITERATIONS)
+    groups = {}
+    for k, h in enumerate(hl):
+        groups.setdefault(id(h._handle()), []).append(k)
+    parts, ms = {}, 0.0
+    for ks in groups.values():
+        trees = hl[ks[0]].trees
+        res = trees.grow([hl[k].slot for k in ks], z[ks], iterations, margin=trees.host)
+        ms += res.ms
+        for j, k in enumerate(ks):
+            parts[k] = (res, j)
+            hl[k].count = int(res.count[j])
+    pick = lambda name: np.array([getattr(parts[k][0], name)[parts[k][1]] for k in range(len(hl))])
+    return WorkspacePlans(status=pick("status"), iterations=pick("iterations"), rewires=pick("rewires"), chain_kept=pick("chain_kept"), count=pick("count"),
+                          path_cost=pick("path_cost"), goal_dist=pick("goal_dist"), paths=[parts[k][0].paths[parts[k][1]] for k in range(len(hl))], nodes=None,
+                          parent=None, node_cost=None, margin=pick("margin") if hl[0].host else None, ms=ms)
 
 
 def _chain(h, z):
@@ -169,17 +290,20 @@ def _chain(h, z):
 
 
 def _waypoints(hl, qs, lookaheads):
-    """One call of each of the HLPs `hl` (one robot, one obstacle count, the same options) from qs: ONE armour_ws_tree_plan call and ONE
-    armour_ik call -> (waypoint configurations, the launches' ms)."""
+    """One call of each of the HLPs `hl` (one robot, one obstacle count, the same options) from qs: ONE armour_ws_tree_plan call (mode 'keep': one
+    armour_ws_trees_grow call on the shared handle) and ONE armour_ik call -> (waypoint configurations, the launches' ms)."""
     h0 = hl[0]
     robot, host = h0.robot, h0.host
     qs = np.stack([np.asarray(q, dtype=np.float64) for q in qs])
     obstacles = np.stack([h.obstacles for h in hl])
     z = ik.end_effector(robot, qs, h0.ik_options.get("tool")).reshape(-1, 3)
     seeds = np.array([call_seed(h.seed, h.world, h.calls) for h in hl], dtype=np.uint64)
-    chains = [_chain(h, z[k]) for k, h in enumerate(hl)]
-    res = plan_workspace_trees(obstacles, z, np.stack([h.goal_point for h in hl]), seeds, init=chains if any(c is not None for c in chains) else None,
-                               host=host, **h0.options)
+    if h0.mode == "keep":
+        res = _grow_kept(hl, z)
+    else:
+        chains = [_chain(h, z[k]) for k, h in enumerate(hl)]
+        res = plan_workspace_trees(obstacles, z, np.stack([h.goal_point for h in hl]), seeds, init=chains if any(c is not None for c in chains) else None,
+                                   host=host, **h0.options)
     points = np.stack([z[k] if p is None else waypoint_along_points(p, z[k], la) for k, (p, la) in enumerate(zip(res.paths, lookaheads))])
     goals = np.stack([h.goal for h in hl])
     sol = ik.solve_ik(robot, points, 0.5 * (qs + goals) if h0.ik_reference == "mid" else qs, obstacles, np.arange(len(hl)), seeds, host=host, **h0.ik_options)
@@ -210,6 +334,37 @@ def workspace_hlps(worlds, robot, seed=0, lookahead=0.1, mode="new", ik_referenc
         def get_waypoint(self, q_cur, _joint_space_lookahead):
             return _waypoints([self], [q_cur], [lookahead])[0][0]
 
-    return hlp_factory(worlds, lambda i, obstacles, goal: _Metres(robot, obstacles, goal, seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference,
-                                                                  ik_options=ik_options, **options),
+    # mode='keep': the factory owns the trees.  Batched: ONE WorkspaceTrees for all the worlds (world i is its tree i), made at the first call
+    # and grown on the live worlds alone; per world: a one-world handle each, made at that world's first call.  make.close() frees them.
+    shared = {}
+
+    def handle(key, indices):
+        if key not in shared:
+            lb, ub = workspace_box(robot, (ik_options or {}).get("tool"))
+            o = dict(options)
+            o.setdefault("lb", lb)
+            o.setdefault("ub", ub)
+            probs = [p for _, p in worlds]
+            O = max([np.asarray(p["obstacles"]).reshape(-1, 12).shape[0] for p in probs] + [1])
+            obstacles = np.stack([pad_obstacles(np.asarray(probs[i]["obstacles"], dtype=np.float64).reshape(-1, 12), O) for i in indices])
+            points = [ik.end_effector(robot, np.asarray(probs[i]["goal"], dtype=np.float64), (ik_options or {}).get("tool")) for i in indices]
+            shared[key] = keep_trees(obstacles, points, [call_seed(seed, i, 0) for i in indices], host, o)
+        return shared[key]
+
+    def keep(i):
+        if mode != "keep":
+            return {}
+        return dict(trees=lambda: handle("trees", range(len(worlds))), slot=i) if batched else dict(trees=lambda: handle(i, [i]), slot=0)
+
+    make = hlp_factory(worlds, lambda i, obstacles, goal: _Metres(robot, obstacles, goal, seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference,
+                                                                  ik_options=ik_options, **keep(i), **options),
                        lambda hl, qs, _joint_space_lookaheads: _waypoints(hl, qs, [lookahead] * len(hl)), batched)
+    make.shared = shared                  # 'keep': {'trees': the one handle} (batched) or {world: its handle}, once called
+
+    def close():
+        for t in shared.values():
+            t.close()
+        shared.clear()
+
+    make.close = close
+    return make

@@ -1091,6 +1091,57 @@ int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int3
                              int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path,
                              int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* margin);
 
+/* ---- resident workspace trees: the same trees kept between calls and grown in instalments (ws_tree.hip) ---- */
+/* The reference's grow_tree_mode = 'keep' (RRT_HLP.m:99-117; the mode of kinova_run_hard_scenarios.m): the tree planted at the first call
+ * stays and every later call grows it further, so the path is an anytime RRT* path.  An ArmourWsTrees holds the trees of W worlds whose
+ * obstacles, goals, seeds and parameters are fixed at create; a grow runs further iterations of armour_ws_tree_plan's loop on the worlds it
+ * lists; a read returns stored trees.
+ * The defining property.  For any world, let its grows have had the iteration counts n_1, n_2, ..., n_k, the first of them having planted
+ *   it from the point s.  Then the stored tree (read), the cumulative iterations and rewires, and the last grow's status, points, path,
+ *   path_cost and goal_dist equal BIT FOR BIT what armour_ws_tree_plan / _host return for starts = s, no chain and max_iterations = sum n,
+ *   on a host handle and on the device: a world's whole state between iterations is its node arrays, its count, its iteration index and
+ *   its rewires, and the sample of iteration i is a function of (seed, i) alone.
+ * armour_ws_trees_create / _create_host: lb, ub, W, O, obstacles [W][O][12], goals [W][3], seeds [W] and the parameters are
+ *   armour_ws_tree_plan's and are refused by the same rules (ARMOUR_EINVAL; one copy of that code).  Every tree starts empty: count 0, 0
+ *   iterations done.  Neither touches a device: a device handle uploads its worlds and reserves W max_nodes nodes with the first grow that
+ *   launches.  _create_host makes the host form, whose grows run armour_ws_tree_plan_host's loop.
+ * armour_ws_trees_grow: slot l = 0 .. L - 1 serves world worlds[l]; every output is [L], in slot order.
+ *     the world's tree is empty: the point rule at starts[l]; not free -> START_BLOCKED, the tree stays empty, no iteration is consumed
+ *       (goal_dist = |goal - starts[l]|), and a later call may plant it from another point; free -> starts[l] is the root.
+ *     the world's tree is planted: starts[l] is not read.
+ *     then `iterations` further iterations of the loop, i continuing from the world's iterations done; the world stops when its tree holds
+ *       max_nodes nodes.  Then the best node and the path, as in armour_ws_tree_plan.
+ *   iterations [L] and rewires [L] returned are cumulative; count [L] (may be NULL) the tree's nodes.  iterations = 0 is allowed: it plants
+ *   the root, or returns the current path.  path [L][max_points][3] (may be NULL) and ARMOUR_ECAPACITY: armour_ws_tree_plan's rule, by slot.
+ *   ms (may be NULL): the device time of the launch, 0 on a host handle.  margin [L] (may be NULL): a host handle's, the smallest
+ *   |clearance| over THIS call's deciding checks.
+ *   ARMOUR_EINVAL before a device is touched: an index outside [0, W); a world listed twice (two blocks would write one tree);
+ *   iterations outside [0, ARMOUR_TREE_MAX_ITERATIONS]; max_points < 0; a world's iterations done + iterations beyond INT32_MAX; a start of
+ *   an empty tree that is absent or not finite; margin on a device handle.  L = 0 is a success that does nothing.
+ *   Device: ONE launch of grid L of the kernel of armour_ws_tree_plan in its resumed form -- block l takes w from the index list, loads
+ *   the world's count, iteration base and rewires, skips the start test when the tree is planted, and writes the three words back at the
+ *   end; nothing else differs, and the loop's first barrier orders the writes of the launch before as it orders an iteration's.  Nothing
+ *   but the index list and the starts is uploaded.
+ * armour_ws_trees_read: nodes [L][max_nodes][3], parent [L][max_nodes], node_cost [L][max_nodes], count [L] of the listed worlds (each may
+ *   be NULL; a world may be listed twice); only the first count rows of a slot are written.
+ * A handle is used by one thread at a time.  Out of scope: obstacles that change, re-rooting or pruning, a reset.  DESIGN.md 4.12g. */
+typedef struct ArmourWsTrees ArmourWsTrees;
+int armour_ws_trees_create(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* goals,
+                           const uint64_t* seeds, double step, double edge_step, double rewire_radius, double goal_rate, double buffer,
+                           double goal_tol, int32_t max_nodes, ArmourWsTrees** out);
+int armour_ws_trees_create_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* goals,
+                                const uint64_t* seeds, double step, double edge_step, double rewire_radius, double goal_rate, double buffer,
+                                double goal_tol, int32_t max_nodes, ArmourWsTrees** out);
+void armour_ws_trees_destroy(ArmourWsTrees* trees);
+int armour_ws_trees_grow(ArmourWsTrees* trees, int32_t L, const int32_t* worlds, const double* starts, int32_t iterations, int32_t max_points,
+                         int32_t* status, int32_t* iterations_done, int32_t* points, int32_t* rewires, double* path_cost, double* goal_dist,
+                         double* path, int32_t* count, double* ms, double* margin);
+int armour_ws_trees_read(ArmourWsTrees* trees, int32_t L, const int32_t* worlds, double* nodes, int32_t* parent, double* node_cost,
+                         int32_t* count);
+/* Test hook: sets the iterations that world `world` counts as done (>= 0), so that a test reaches the INT32_MAX rule of a grow without
+ * running 2^31 iterations.  ARMOUR_ESTATE once a device handle has launched (its state is on the device then). */
+int armour_debug_ws_trees_set_iterations(ArmourWsTrees* trees, int32_t world, int32_t done);
+
 /* ---- path audit: executed pieces of Bezier plans checked against worlds' obstacles on the device (path_audit.hip) ---- */
 /* The world's half of the safety claim (KSI/kinova_world_static.m collision_check after every move of KSI/simulator_armtd.m): did the path
  * the arm was sent along touch an obstacle?  P pieces are audited in one launch.  Piece p is the plan of armour_desired_trajectory

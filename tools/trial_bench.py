@@ -22,7 +22,10 @@ and prints ONE JSON line.
   the file already holds is kept for comparison;
 * --hlp workspace: the same worlds once more with the reference's own high-level planner, the end-effector RRT* (armour_amd.ws_planner.
   workspace_hlps: a fresh workspace tree per world and iteration, all live worlds in one armour_ws_tree_plan call and one armour_ik call;
-  --tree-seed, --ws-iterations, --ws-nodes, --ws-lookahead in metres, --ws-buffer): `hlp_outcomes_workspace` holds the outcome counts beside
+  --tree-seed, --ws-iterations, --ws-nodes, --ws-lookahead in metres, --ws-buffer; --ws-mode keep: ONE resident tree per world, grown by
+  --ws-iterations at every call and bounded by --ws-nodes over the whole trial -- that run adds the row
+  `hlp_outcomes_workspace_keep["<iterations>_per_call"]` to the saved profile, beside the 'new' row, and measures nothing else again):
+  `hlp_outcomes_workspace` holds the outcome counts beside
   the straight-line run's, the worlds whose outcome differs, how many waypoints fell back to the goal configuration and `ms_per_batch`.  The
   sections of the other planners that profiles/trial_bench.json already holds are kept;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
@@ -133,11 +136,16 @@ def workspace_trials(robot, ws, straight, a):
     from armour_amd.trials import OUTCOMES, run_trials
     from armour_amd.ws_planner import EDGE_STEP, GOAL_RATE, GOAL_TOL, REWIRE_RADIUS, STEP, workspace_hlps
     options = dict(max_iterations=a.ws_iterations, max_nodes=a.ws_nodes, buffer=a.ws_buffer)
-    make = workspace_hlps(ws, robot, seed=a.tree_seed, lookahead=a.ws_lookahead, **options)
+    make = workspace_hlps(ws, robot, seed=a.tree_seed, lookahead=a.ws_lookahead, mode=a.ws_mode, **options)
     res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
     per_batch = lambda key: dict(mean=float(np.mean([b[key] for b in res["batches"]])), max=float(np.max([b[key] for b in res["batches"]])))
     count = lambda r: {o: sum(1 for w in r["worlds"] if w["outcome"] == o) for o in OUTCOMES}
     calls, fallbacks = int(sum(h.calls for h in make.hlps.values())), int(sum(h.fallbacks for h in make.hlps.values()))
+    if a.ws_mode == "keep":
+        options = dict(options, mode="keep", iterations_per_call=a.ws_iterations, tree_sizes_at_the_end=dict(
+            mean=float(np.mean([h.count for h in make.hlps.values()])), max=int(max(h.count for h in make.hlps.values())),
+            full=int(sum(h.count >= a.ws_nodes for h in make.hlps.values()))))
+        make.close()
     return dict(workspace=dict(options, seed=a.tree_seed, lookahead_m=a.ws_lookahead, step=STEP, edge_step=EDGE_STEP, rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE,
                                goal_tol=GOAL_TOL, hlp_calls=calls, goal_configuration_fallbacks=fallbacks),
                 straight=count(straight), workspace_outcomes=count(res), workspace_summary=res["summary"],
@@ -158,6 +166,7 @@ def main():
     ap.add_argument("--ws-nodes", type=int, default=1024)
     ap.add_argument("--ws-lookahead", type=float, default=0.1)
     ap.add_argument("--ws-buffer", type=float, default=0.0)
+    ap.add_argument("--ws-mode", choices=["new", "keep"], default="new")
     ap.add_argument("--tree-seed", type=int, default=0)
     ap.add_argument("--tree-iterations", type=int, default=2000)
     ap.add_argument("--tree-nodes", type=int, default=2048)
@@ -195,11 +204,25 @@ def main():
     if a.hlp == "tree":
         variant = a.tree_shortcut or a.tree_mode != "new"
         out["hlp_outcomes_tree_seed" if variant else "hlp_outcomes_tree"] = tree_trials(robot, ws, res, a)
+    if a.hlp == "workspace" and a.ws_mode == "keep":
+        # one row of a finished profile: the 'keep' run at this many iterations per call goes beside the 'new' row, and nothing else of the
+        # saved file is measured again
+        saved = json.load(open(saved_json))
+        row = workspace_trials(robot, ws, res, a)
+        row["new_mode_row"] = {k: saved["hlp_outcomes_workspace"][k] for k in ("workspace_outcomes", "hard_scenarios") if k in saved.get("hlp_outcomes_workspace", {})}
+        if "ms_per_batch" in saved.get("hlp_outcomes_workspace", {}):
+            row["new_mode_row"]["hlp_ms_mean"] = saved["hlp_outcomes_workspace"]["ms_per_batch"]["hlp_ms"]["mean"]
+        saved.setdefault("hlp_outcomes_workspace_keep", {})["%d_per_call" % a.ws_iterations] = row
+        with open(saved_json, "w") as f:
+            json.dump(saved, f, indent=1, default=float)
+            f.write("\n")
+        print(json.dumps(dict(hlp_outcomes_workspace_keep=saved["hlp_outcomes_workspace_keep"]), default=float))
+        return
     if a.hlp == "workspace":
         out["hlp_outcomes_workspace"] = workspace_trials(robot, ws, res, a)
     if a.hlp in ("tree", "workspace") and os.path.exists(saved_json):
         saved = json.load(open(saved_json))
-        for key in ("hlp_outcomes", "hlp_outcomes_tree", "hlp_outcomes_tree_seed", "hlp_outcomes_workspace"):
+        for key in ("hlp_outcomes", "hlp_outcomes_tree", "hlp_outcomes_tree_seed", "hlp_outcomes_workspace", "hlp_outcomes_workspace_keep"):
             if key not in out and saved.get(key) is not None:
                 out[key] = saved[key]
     k_range, D = res["k_range"], res["duration"]

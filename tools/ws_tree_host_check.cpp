@@ -3,6 +3,8 @@
 // and without an initial chain, at the node cap and with every optional output absent, checks what every run must satisfy -- every parent
 // chain reaches the root within count steps, cost_k = cost_parent + |x_k - x_parent| bit for bit, the path runs from the start to a node
 // whose distance to the goal is goal_dist, the same seed gives the same bytes -- and the refusals, and prints what it found.
+// Then the resident trees' host handle (armour_ws_trees_create_host / _grow / _read / _destroy): instalments of a permuted subset and of
+// every world must leave each world with the bytes of one plan of its own sum; a blocked start, ECAPACITY by slot, the refusals.
 //   make -C armour_amd/csrc wshost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
 // It supplies the symbols ws_tree.hip takes from api.hip, so that nothing else of the library is linked.
 #include <cmath>
@@ -122,6 +124,90 @@ int main() {
         bare(0.1, 0.00001, 0.2, 0.1, 0.0, iters, cap) != ARMOUR_EINVAL) {
         printf("FAILED: a bad argument passed\n");
         return 1;
+    }
+    // ---- resident trees on the host handle: create_host / grow / read / destroy.  Three instalments (100 + 0 + 200; the second empty) of
+    // a subset in permuted order, then of everyone, must leave every world with the bytes of ONE plan of its own sum from the same start.
+    {
+        ArmourWsTrees* h = nullptr;
+        if (armour_ws_trees_create_host(lb, ub, W, O, obstacles.data(), goals.data(), seeds, 0.1, 0.01, 0.2, 0.1, 0.01, 0.01, cap, &h) != ARMOUR_OK || !h) {
+            printf("FAILED: create_host: %s\n", g_error);
+            return 1;
+        }
+        Out g;
+        auto grow = [&](int32_t L, const int32_t* worlds, const double* from, int32_t n, int32_t room) {
+            g.status.assign(W, -1); g.iterations.assign(W, -1); g.points.assign(W, -1); g.rewires.assign(W, -1); g.count.assign(W, -1);
+            g.path_cost.assign(W, -1.0); g.goal_dist.assign(W, -1.0); g.path.assign((size_t)W * (room > 0 ? room : 1) * 3, 0.0); g.margin.assign(W, 0.0);
+            double ms = -1.0;
+            const int rc = armour_ws_trees_grow(h, L, worlds, from, n, room, g.status.data(), g.iterations.data(), g.points.data(), g.rewires.data(), g.path_cost.data(),
+                                                g.goal_dist.data(), g.path.data(), g.count.data(), &ms, g.margin.data());
+            return ms == 0.0 || rc == ARMOUR_EINVAL ? rc : -100;
+        };
+        const int32_t two[2] = {2, 0}, all[3] = {0, 1, 2}, twice[2] = {1, 1}, outside[1] = {3};
+        const double inside[3] = {0.5, 0.35, 0.5}, nan3[3] = {NAN, 0.0, 0.0};
+        if (grow(1, all, inside, 50, cap) != ARMOUR_OK || g.status[0] != ARMOUR_WS_START_BLOCKED || g.count[0] != 0 || g.iterations[0] != 0) {
+            printf("FAILED: a blocked start planted a tree: %s\n", g_error);
+            return 1;
+        }
+        if (grow(2, two, starts.data(), 100, cap) != ARMOUR_OK || grow(2, two, nullptr, 0, cap) != ARMOUR_OK || grow(3, all, starts.data(), 200, cap) != ARMOUR_OK) {
+            printf("FAILED: grow: %s\n", g_error);
+            return 1;
+        }
+        Out nc;
+        if (run(&nc, cap, cap, false, 0.2) != ARMOUR_OK) { printf("FAILED: %s\n", g_error); return 1; }    // 300 iterations, no chain: worlds 0 and 2
+        Out one;                                                                                                 // world 1: 200 iterations
+        one.status.assign(W, 0); one.iterations.assign(W, 0); one.points.assign(W, 0); one.rewires.assign(W, 0); one.kept.assign(W, 0); one.count.assign(W, 0);
+        one.path_cost.assign(W, 0.0); one.goal_dist.assign(W, 0.0); one.path.assign((size_t)W * cap * 3, 0.0); one.nodes.assign((size_t)W * cap * 3, 0.0);
+        one.parent.assign((size_t)W * cap, -7); one.cost.assign((size_t)W * cap, 0.0);
+        if (armour_ws_tree_plan_host(lb, ub, W, O, obstacles.data(), starts.data(), goals.data(), seeds, 0, nullptr, nullptr, 0.1, 0.01, 0.2, 0.1, 0.01, 0.01, 200, cap, cap,
+                                     one.status.data(), one.iterations.data(), one.points.data(), one.rewires.data(), one.kept.data(), one.path_cost.data(),
+                                     one.goal_dist.data(), one.path.data(), one.count.data(), one.nodes.data(), one.parent.data(), one.cost.data(), nullptr) != ARMOUR_OK) {
+            printf("FAILED: %s\n", g_error);
+            return 1;
+        }
+        std::vector<double> rn((size_t)W * cap * 3, 0.0), rc_((size_t)W * cap, 0.0);
+        std::vector<int32_t> rp((size_t)W * cap, -7), rcount(W, -1);
+        if (armour_ws_trees_read(h, 3, all, rn.data(), rp.data(), rc_.data(), rcount.data()) != ARMOUR_OK) { printf("FAILED: read: %s\n", g_error); return 1; }
+        for (int w = 0; w < W; w++) {
+            const Out& ref = w == 1 ? one : nc;
+            const size_t c = (size_t)ref.count[w], row = (size_t)w * cap;
+            if (g.status[w] != ref.status[w] || g.iterations[w] != ref.iterations[w] || g.points[w] != ref.points[w] || g.rewires[w] != ref.rewires[w] ||
+                g.count[w] != ref.count[w] || rcount[w] != ref.count[w] || std::memcmp(&g.path_cost[w], &ref.path_cost[w], sizeof(double)) ||
+                std::memcmp(&g.goal_dist[w], &ref.goal_dist[w], sizeof(double)) ||
+                std::memcmp(&g.path[row * 3], &ref.path[row * 3], (size_t)ref.points[w] * 3 * sizeof(double)) || std::memcmp(&rn[row * 3], &ref.nodes[row * 3], c * 3 * sizeof(double)) ||
+                std::memcmp(&rp[row], &ref.parent[row], c * sizeof(int32_t)) || std::memcmp(&rc_[row], &ref.cost[row], c * sizeof(double)) || rp[row + c] != -7) {
+                printf("FAILED: world %d grown in instalments differs from one plan of %d iterations\n", w, ref.iterations[w]);
+                return 1;
+            }
+        }
+        // the refusals, and the read of a subset with every array absent but the counts
+        if (grow(2, twice, starts.data(), 1, cap) != ARMOUR_EINVAL || grow(1, outside, starts.data(), 1, cap) != ARMOUR_EINVAL || grow(1, all, starts.data(), -1, cap) != ARMOUR_EINVAL ||
+            grow(1, all, starts.data(), ARMOUR_TREE_MAX_ITERATIONS + 1, cap) != ARMOUR_EINVAL || grow(1, all, starts.data(), 1, -1) != ARMOUR_EINVAL ||
+            armour_ws_trees_read(h, 1, outside, nullptr, nullptr, nullptr, nullptr) != ARMOUR_EINVAL) {
+            printf("FAILED: a bad argument of grow or read passed\n");
+            return 1;
+        }
+        // too little room, no iterations, planted trees (their starts are not read): ECAPACITY with every world's own points complete
+        if (grow(3, all, nan3, 0, 2) != ARMOUR_ECAPACITY || g.points[0] != nc.points[0] || g.points[1] != one.points[1] || g.points[2] != nc.points[2]) {
+            printf("FAILED: ECAPACITY of a grow\n");
+            return 1;
+        }
+        int32_t c2[2] = {-1, -1};
+        if (armour_ws_trees_read(h, 2, two, nullptr, nullptr, nullptr, c2) != ARMOUR_OK || c2[0] != nc.count[2] || c2[1] != nc.count[0]) { printf("FAILED: read of a subset\n"); return 1; }
+        ArmourWsTrees* fresh = nullptr;
+        if (armour_ws_trees_create_host(lb, ub, W, O, obstacles.data(), goals.data(), seeds, 0.1, 0.01, 0.2, 0.1, 0.01, 0.01, cap, &fresh) != ARMOUR_OK ||
+            armour_ws_trees_grow(fresh, 1, all, nan3, 1, 0, g.status.data(), g.iterations.data(), g.points.data(), g.rewires.data(), g.path_cost.data(), g.goal_dist.data(), nullptr,
+                                 nullptr, nullptr, nullptr) != ARMOUR_EINVAL) {
+            printf("FAILED: the non-finite start of an empty tree passed\n");
+            return 1;
+        }
+        armour_ws_trees_destroy(fresh);
+        if (armour_ws_trees_create_host(lb, ub, W, O, obstacles.data(), goals.data(), seeds, 0.0, 0.01, 0.2, 0.1, 0.01, 0.01, cap, &fresh) != ARMOUR_EINVAL || fresh) {
+            printf("FAILED: a bad argument of create passed\n");
+            return 1;
+        }
+        armour_ws_trees_destroy(h);
+        armour_ws_trees_destroy(nullptr);
+        printf("ws trees host check ok: 100 + 0 + 200 / 200 / 100 + 0 + 200 iterations in instalments equal one plan each: %d / %d / %d nodes\n", rcount[0], rcount[1], rcount[2]);
     }
     printf("ws tree host check ok: %d / %d / %d nodes, %d / %d / %d rewires, path costs %.4f %.4f %.4f, chains kept %d %d %d, margins %.3g %.3g %.3g\n", a.count[0],
            a.count[1], a.count[2], a.rewires[0], a.rewires[1], a.rewires[2], a.path_cost[0], a.path_cost[1], a.path_cost[2], a.kept[0], a.kept[1], a.kept[2], a.margin[0],
