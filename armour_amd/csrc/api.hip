@@ -223,35 +223,17 @@ extern "C" int armour_create(const ArmourRobot* robot, const ArmourParams* param
     h->ub = armour_ultimate_bound(robot);
     h->device = device;
     h->T = params->num_time_steps; h->J = robot->num_joints; h->n = robot->num_factors;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { armour_set_error("hipStreamCreate failed: %s", hipGetErrorString(e)); delete h; return ARMOUR_EDEVICE; }
+    if (const int rc = h->stream.create(); rc != ARMOUR_OK) { delete h; return rc; }
     *out = h;
     return ARMOUR_OK;
-}
-
-double* armour_handle_pinned(ArmourPlanner* h, int slot, size_t bytes) {
-    if (h->solve_pin[slot] && h->solve_pin_bytes[slot] >= bytes) return static_cast<double*>(h->solve_pin[slot]);
-    if (h->solve_pin[slot]) { armour_free_pinned(h->solve_pin[slot]); h->solve_pin[slot] = nullptr; h->solve_pin_bytes[slot] = 0; }
-    void* p = nullptr;
-    if (armour_alloc_pinned(bytes, &p) != ARMOUR_OK) return nullptr;
-    h->solve_pin[slot] = p; h->solve_pin_bytes[slot] = bytes;
-    return static_cast<double*>(p);
-}
-
-static void drop_step_graphs(ArmourPlanner* h) {
-    for (auto& g : h->step_graphs) (void)hipGraphExecDestroy(g.exec);
-    h->step_graphs.clear();
 }
 
 extern "C" void armour_destroy(ArmourPlanner* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    drop_step_graphs(h);
-    for (void* pin : h->solve_pin) armour_free_pinned(pin);
-    armour_p1_free(h);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;   // (its DevBuf members free the device buffers)
+    armour_p1_free(h);   // (the arena pool's user count)
+    delete h;   // (its members release the graphs, the buffers and the stream)
 }
 
 // mode ARMTD: `qdd0` carries k_range [B][n] (the curve has no initial acceleration) and the third row of d_bez holds it
@@ -273,7 +255,7 @@ static int begin_problem_set(ArmourPlanner* h, int B, int O, const double* q0, c
     h->bounds_on_device = false; h->bounds_on_host = false;
     h->tables_from_host = false;
     h->stats_fresh = false;
-    drop_step_graphs(h);  // they bake in the tables of the previous problem set
+    h->step_graphs.clear();  // they bake in the tables of the previous problem set
     int rc = ensure_capacity(h, B, O);
     if (rc != ARMOUR_OK) return rc;
     h->B = B; h->O = O; h->Q = h->J * h->T * O;
@@ -591,10 +573,9 @@ static int steps_graph(ArmourPlanner* h, const double* d_k, int steps, double* d
     if (h->step_graphs.size() >= 4) {  // keep the four most recently used
         size_t lru = 0;
         for (size_t i = 1; i < h->step_graphs.size(); i++) if (h->step_graphs[i].last_use < h->step_graphs[lru].last_use) lru = i;
-        (void)hipGraphExecDestroy(h->step_graphs[lru].exec);
         h->step_graphs.erase(h->step_graphs.begin() + lru);
     }
-    h->step_graphs.push_back({d_k, steps, d_g, d_jac, exec, h->graph_clock});
+    h->step_graphs.push_back({d_k, steps, d_g, d_jac, GraphExec(exec), h->graph_clock});
     *out = exec;
     return ARMOUR_OK;
 }
@@ -851,9 +832,10 @@ extern "C" int armour_eval_violations(ArmourPlanner* h, const double* k, ArmourV
     const size_t bn = (size_t)h->B * h->n;
     ARMOUR_TRY(h->d_viol.reserve((size_t)h->B));
     // page-locked staging on both sides: the two copies are asynchronous and ordered with the launches on the handle's stream
-    double* hk = armour_handle_pinned(h, 6, bn * sizeof(double));
-    ArmourViolation* hv = reinterpret_cast<ArmourViolation*>(armour_handle_pinned(h, 7, (size_t)h->B * sizeof(ArmourViolation)));
-    if (!hk || !hv) return ARMOUR_EDEVICE;
+    ARMOUR_TRY(h->h_viol_k.reserve(bn));
+    ARMOUR_TRY(h->h_viol.reserve((size_t)h->B));
+    double* hk = h->h_viol_k;
+    ArmourViolation* hv = h->h_viol;
     memcpy(hk, k, bn * sizeof(double));
     HIPCHK(hipMemcpyAsync(h->d_k, hk, bn * sizeof(double), hipMemcpyHostToDevice, h->stream));
     // The relevant-rows form (ARMOUR_OPT_CULL_ROWS) holds for k inside [-1, 1]^n -- its mask says "never violated for a k of the box" (relevance.hip).

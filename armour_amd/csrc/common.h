@@ -95,12 +95,26 @@ struct P2Tables {
 #define ARMOUR_MODE_ARMOUR 0
 #define ARMOUR_MODE_ARMTD 1
 
-// device buffers of the device-resident armour_solve (solver_device.hip), grown on demand and kept across solves
+// buffers of the device-resident armour_solve (solver_device.hip), grown on demand and kept across solves
 struct SolveDeviceWork {
     DevBuf<unsigned char> ctl;        // one block: control words | goals | SolveArgs (one copy per solve)
     DevBuf<unsigned char> blk_word;
     int words_clean = 0;              // the last launch ended normally: every block has cleared its flag word
     DevBuf<unsigned char> blk_rows, qp_rows, flags;
+    // page-locked
+    PinBuf<ArmourSolveResult> h_res;  // [B]: the kernel writes the results straight into it
+    PinBuf<unsigned char> h_ctl;      // the control block's mirror
+    PinBuf<long long> h_stamps;       // ARMOUR_SOLVE_TIMING: the kernel's phase stamps [B][64]
+};
+
+// page-locked mirrors of the host-driven armour_solve (solver.hip), grown on demand and kept across solves
+struct SolveHostWork {
+    PinBuf<double> k;                 // [B][n] the point evaluated: armour_eval_g_jac_device reads it in place
+    PinBuf<double> g, jac;            // the whole linearisation, which only the row-buffer overflow fallback brings over
+    // written by the scan kernel, per segment of a problem's rows:
+    PinBuf<long long> viol_seg;       // [B][nseg] violations
+    PinBuf<int> count;                // [B][nseg] candidate rows found
+    PinBuf<unsigned char> rows;       // [B][nseg][cap_rows] SolveRow records
 };
 
 // One set of row lists of the current problem set (relevance.hip): a mask [B][m], the listed collision rows of every problem in ascending
@@ -119,13 +133,15 @@ struct RelLists {
     double ms = 0;
 };
 
+struct P1Work;   // p1_reach.hip
+
 struct ArmourPlanner {
     ArmourRobot robot;
     ArmourParams params;
     ArmourLimits lim;
     ArmourUltimateBound ub;
     int device = 0;
-    hipStream_t stream = nullptr;
+    DevStream stream;
     int T = 0, J = 0, n = 0;
     // current problem set
     int B = 0, O = 0, Q = 0, m = 0;
@@ -138,9 +154,6 @@ struct ArmourPlanner {
     int row0 = 0;                   // rows before the collision block (n*T torque rows, or 0 in ARMTD mode)
     std::vector<double> h_krange;   // ARMTD mode: [B][n] acceleration range of each problem's JRS tables
     DevBuf<double> d_jrs;           // ARMTD mode: [B][n][6][T] c/g/r of cos, then of sin (the order of armtd.in)
-    // page-locked host scratch of armour_solve (k, g, jac mirrors), grown on demand and kept across solves
-    void* solve_pin[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // k, g, jac mirrors; violation sums, row counts, compact rows; [6] k and [7] records of armour_eval_violations; [8] the reach-set build's read-back, [9] its status words
-    size_t solve_pin_bytes[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool stats_fresh = false;       // armour_p1_build has read the table statistics back itself (armour_refresh_table_stats has nothing to do)
     int opt_p1_build = 0;           // ARMOUR_OPT_P1_BUILD: 0 automatic, 1 per time step, 2 time-vectorised
     double opt_p1_work_mb = 0;      // ARMOUR_OPT_P1_WORK_MEMORY_MB: cap on the time-vectorised build's arena, MiB (0: none)
@@ -150,10 +163,13 @@ struct ArmourPlanner {
     int tune(int option) const { return (int)tuning[option - ARMOUR_OPT_FIRST_TUNING]; }
     double tune_f(int option) const { return tuning[option - ARMOUR_OPT_FIRST_TUNING]; }
     DevBuf<ArmourViolation> d_viol;   // [B] records of armour_eval_violations
+    PinBuf<double> h_viol_k;          // its page-locked staging: k [B][n] in,
+    PinBuf<ArmourViolation> h_viol;   // the records [B] out
     RelLists rel, rel2;      // the relevance lists and the solver's (rel2.mask is filled together with rel.mask)
     int rel2_tq_cap = 0;
     DevBuf<unsigned char> d_sweep;   // armour_sweep's device block: candidates | cost coefficients | records | best (sweep.hip)
     SolveDeviceWork solve_dev;
+    SolveHostWork solve_host;
     DevBuf<double> d_bounds;         // [2][B][m] g_l, g_u for the solver's device-side scan (uploaded on the first solve of a problem set)
     bool bounds_on_device = false, bounds_on_host = false;
     bool tables_from_host = false;   // armour_debug_load_tables: plane normals are the caller's, not necessarily unit vectors (relevance.hip)
@@ -203,10 +219,10 @@ struct ArmourPlanner {
     int build_info[4] = {0, 0, 0, 0};          // armour_get_build_info: kernel of the last reach-set build, waves per block, sort-buffer entries, launches
     int max_link = 0, max_torque = 0;          // largest monomial counts in the current tables (LDS sizing of P2)
     long long sum_link = 0, sum_torque = 0;
-    // P1 workspace (p1_reach.hip)
-    void* p1 = nullptr;
+    // P1 workspace (p1_reach.hip: made by the first build, released by armour_p1_free)
+    P1Work* p1 = nullptr;
     // instantiated graphs of armour_eval_g_jac_device_steps, valid for one problem set (api.hip)
-    struct StepsGraph { const double* d_k; int steps; double* d_g; double* d_jac; hipGraphExec_t exec; unsigned long long last_use; };
+    struct StepsGraph { const double* d_k; int steps; double* d_g; double* d_jac; GraphExec exec; unsigned long long last_use; };
     std::vector<StepsGraph> step_graphs;
     unsigned long long graph_clock = 0;
 };
@@ -233,8 +249,6 @@ slv::RowLimits armour_row_limits(const ArmourPlanner* h);
     if (!(h)->ready) { armour_set_error("no problem set: call armour_set_problems first"); return ARMOUR_ESTATE; }
 // joint ix = b * n + i's coefficients c0, c1, c2 of the cost's plan point (solver_common.h slv::plan_point): what armour_eval_f and the sweep's cost read
 void armour_plan_coeffs(const ArmourPlanner* h, size_t ix, double c[3]);
-// page-locked scratch slot of the handle with at least `bytes` bytes (registered for the zero-copy eval path); nullptr on failure
-double* armour_handle_pinned(ArmourPlanner* h, int slot, size_t bytes);
 int armour_p2_slice_links_launch(const P2Tables& tb, const double* d_k, double* d_centers, hipStream_t stream);
 P2Tables armour_make_tables(const ArmourPlanner* h);
 // g_l / g_u of the current problem set in h->d_bounds ([2][B][m]): filled by a kernel once per problem set (api.hip)

@@ -157,8 +157,7 @@ struct CtlCache {
     DevStream stream;
     DevBuf<CtlArgs> d_args;
     DevBuf<double> d_buf;
-    double* h_pin = nullptr; size_t h_cap = 0;   // doubles
-    ~CtlCache() { if (h_pin) (void)hipHostFree(h_pin); }
+    PinBuf<double> h_pin;
 };
 thread_local CtlCache g_ctl;
 
@@ -224,12 +223,8 @@ extern "C" int armour_robust_controller(const ArmourRobot* robot, double model_u
     const double* in[5] = {q, qd, q_des, qd_des, qdd_des};
     double* out[3] = {u, tau, v};
     const bool staged = 5 * bn <= kStagedDoubles;
-    if (staged && total > c.h_cap) {
-        if (c.h_pin) { (void)hipHostFree(c.h_pin); c.h_pin = nullptr; c.h_cap = 0; }
-        HIPCHK(hipHostMalloc((void**)&c.h_pin, total * sizeof(double), hipHostMallocDefault));
-        c.h_cap = total;
-    }
     if (staged) {
+        ARMOUR_TRY(c.h_pin.reserve(total));
         for (int k = 0; k < 5; k++) memcpy(c.h_pin + (size_t)k * bn, in[k], bn * sizeof(double));
         HIPCHK(hipMemcpyAsync(d_in, c.h_pin, 5 * bn * sizeof(double), hipMemcpyHostToDevice, c.stream));
     } else {

@@ -1,5 +1,5 @@
-// Host-side owners of what every entry point holds on the device -- buffers, a stream, a pair of timing events -- and the
-// argument checks the entries share.  Host code only: nothing here is seen by a kernel.
+// Host-side owners of what every entry point holds on the device -- buffers, page-locked host buffers, a stream, a pair of timing
+// events, an instantiated graph -- and the argument checks the entries share.  Host code only: nothing here is seen by a kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -66,7 +66,39 @@ struct DevBuf {
     }
 };
 
-// a non-blocking stream of the one-shot entries and of the handles that are not planners
+// An owning page-locked host buffer under the same reserve() contract.  From armour_alloc_pinned (api.hip): allocated with the default flags, so
+// that kernels may write it in place, and listed in the registry of page-locked ranges the synchronous evaluation consults.  Only a unit
+// that instantiates a PinBuf refers to those two functions.
+template <class T>
+struct PinBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~PinBuf() { release(); }
+    operator T*() const { return p; }
+    template <class U> U* as() const { return reinterpret_cast<U*>(p); }   // a block of bytes that holds records
+    void release() {
+        if (p) armour_free_pinned(p);
+        p = nullptr; cap = 0;
+    }
+    int reserve(size_t need) {
+        if (p && need <= cap) return ARMOUR_OK;
+        release();
+        const size_t count = need ? need : 1;
+        void* q = nullptr;
+        ARMOUR_TRY(armour_alloc_pinned(count * sizeof(T), &q));
+        p = static_cast<T*>(q);
+        cap = count;
+        return ARMOUR_OK;
+    }
+};
+
+// a non-blocking stream of the one-shot entries, of the planner handle and of the handles that are not planners
 struct DevStream {
     hipStream_t s = nullptr;
     DevStream() = default;
@@ -110,6 +142,24 @@ struct EventPair {
         HIPCHK(hipEventElapsedTime(&f, e0, e1));
         *ms = f;
         return ARMOUR_OK;
+    }
+};
+
+// an instantiated graph: move-only, so that a vector of them destroys what it erases or clears
+struct GraphExec {
+    hipGraphExec_t g = nullptr;
+    GraphExec() = default;
+    explicit GraphExec(hipGraphExec_t g_) : g(g_) {}
+    GraphExec(GraphExec&& o) noexcept : g(o.g) { o.g = nullptr; }
+    GraphExec& operator=(GraphExec&& o) noexcept {
+        if (this != &o) { release(); g = o.g; o.g = nullptr; }
+        return *this;
+    }
+    ~GraphExec() { release(); }
+    operator hipGraphExec_t() const { return g; }
+    void release() {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
     }
 };
 

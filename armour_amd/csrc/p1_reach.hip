@@ -1793,13 +1793,18 @@ static std::mutex g_p1_launch_mu;
 // twice in twelve builds, when the runtime has to get the memory back from the driver.)
 struct TvArenaPool {
     std::mutex mu;
-    unsigned char* ptr = nullptr;
+    unsigned char* ptr = nullptr;   // raw on purpose: the pool is a global, and an owner here would call hipFree during static destruction
     size_t bytes = 0;
     int users = 0;   // live handles of the device that have built something: the last one to go frees the arena
 };
 constexpr int kMaxPoolDevices = 64;
 TvArenaPool g_tv_pool[kMaxPoolDevices];
 
+#endif  // P1_TV_VARIANT
+}  // namespace
+
+#ifndef P1_TV_VARIANT
+// the handle's reach-set workspace (common.h: ArmourPlanner::p1)
 struct P1Work {
     DevBuf<unsigned char> arena;
     DevBuf<unsigned> d_status;
@@ -1810,10 +1815,11 @@ struct P1Work {
     DevBuf<long long> d_phase;   // ARMOUR_P1_TRACE: [1024][8] phase clocks of the last launch's blocks (P1Cfg::phase_log), allocated on first use
     DevBuf<unsigned char> d_xch; int xch_epoch = 0;   // a time step on two CUs: kXchBytes per item, flags tagged with the launch's epoch (cleared when allocated and when the epoch wraps)
     EventPair ev_chain, ev_planes;   // around the reach-set kernel | around the half-space kernels
+    // page-locked: the block through which a build of up to 4 MiB of read-back brings home what the host keeps | the per-step kernel's status words
+    PinBuf<unsigned char> h_readback;
+    PinBuf<unsigned> h_status;
 };
-
 #endif  // P1_TV_VARIANT
-}  // namespace
 
 // ---- launch of THIS translation unit's time-vectorised kernel (rows of tv::GR doubles; pz_tv.h).  p1_reach.hip holds the 64-double rows,
 // p1_reach_tv50.hip the same source with rows of 50 (BASELINE's T = 100 makes groups of 50 time steps): armour_p1_build picks by group size.
@@ -1846,7 +1852,7 @@ __attribute__((visibility("hidden"))) hipError_t armour_p1_tv_launch_g50(int nw_
 constexpr int kTvNarrowRows = P1_TV_NARROW;   // the row width of that unit (its TV_GROW; development builds pass both)
 
 void armour_p1_free(ArmourPlanner* h) {
-    P1Work* wk = (P1Work*)h->p1;
+    P1Work* wk = h->p1;
     if (!wk) return;
     {   // the device's last handle takes the shared work slots with it
         TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices];
@@ -1878,18 +1884,18 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
     const size_t smem = p1_wave_lds(cap_key, cap_raw) + p1_shared_lds(ci_doubles(L));
     if (smem > (size_t)160 * 1024) { armour_set_error("armour_debug_pz_op: sort buffers of %d keys / %d raw terms do not fit the LDS", cap_key, cap_raw); return ARMOUR_EINVAL; }
     HIPCHK(hipFuncSetAttribute((const void*)armour_p1_pzop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    unsigned char* arena = nullptr;
-    HIPCHK(hipMalloc((void**)&arena, L.total));
+    DevBuf<unsigned char> arena;
+    ARMOUR_TRY(arena.reserve(L.total));
     PzOpArgs a;
     memset(&a, 0, sizeof(a));
     a.op = op; a.nops = nops; a.r = r; a.out_cap = out_cap;
-    std::vector<void*> dev;
+    std::vector<DevBuf<unsigned char>> dev;   // the operands, the outputs, the argument block
+    int up_rc = ARMOUR_OK;                    // the first allocation that failed: nothing is launched then
     auto up = [&](const void* src, size_t bytes) -> void* {
-        void* d = nullptr;
-        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) return nullptr;
-        dev.push_back(d);
-        if (bytes && src) (void)hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
-        return d;
+        dev.emplace_back();
+        if (const int rc = dev.back().reserve(bytes ? bytes : 8); rc != ARMOUR_OK) { if (up_rc == ARMOUR_OK) up_rc = rc; return nullptr; }
+        if (bytes && src) (void)hipMemcpy(dev.back(), src, bytes, hipMemcpyHostToDevice);
+        return dev.back();
     };
     for (int o = 0; o < nops; o++) {
         a.sz[o] = sz[o]; a.cnt[o] = cnt[o];
@@ -1909,6 +1915,7 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
     cf.arena_bytes = L.total; cf.arena = arena;
     cf.rb = h->robot; cf.pr = h->params; cf.ub = h->ub;
     const PzOpArgs* d_args = (const PzOpArgs*)up(&a, sizeof(a));
+    ARMOUR_TRY(up_rc);
     hipLaunchKernelGGL(armour_p1_pzop_kernel, dim3(1), dim3(WAVE), smem, h->stream, cf, d_args);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1917,8 +1924,6 @@ int armour_p1_debug_pz_op(ArmourPlanner* h, int op, int nops, const int* sz, con
         (void)hipMemcpy(out_coef, a.out_coef, (size_t)out_cap * 9 * 8, hipMemcpyDeviceToHost);
         (void)hipMemcpy(out_misc, a.out_misc, 64 * 8, hipMemcpyDeviceToHost);
     }
-    for (void* d : dev) (void)hipFree(d);
-    (void)hipFree(arena);
     if (e != hipSuccess) { armour_set_error("armour_debug_pz_op: %s", hipGetErrorString(e)); return ARMOUR_EDEVICE; }
     return ARMOUR_OK;
 }
@@ -2335,11 +2340,10 @@ static int build_time_vectorised(ArmourPlanner* h, P1Work* wk, int cus, float* t
 
 int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     if (!h->p1) {
-        P1Work* nw = new P1Work();
-        h->p1 = nw;
+        h->p1 = new P1Work();
         { TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices]; std::lock_guard<std::mutex> lk(pool.mu); pool.users++; }
     }
-    P1Work* wk = (P1Work*)h->p1;
+    P1Work* wk = h->p1;
     const int B = h->B, T = h->T, J = h->J, n = h->n, O = h->O;
     int rc;
     ARMOUR_TRY(wk->d_status.reserve(ST_WORDS + 64));
@@ -2365,8 +2369,8 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     float total_ms = 0;
     h->build_info[0] = h->build_info[1] = h->build_info[2] = h->build_info[3] = 0;
     unsigned st[ST_WORDS];
-    unsigned* st_pin = reinterpret_cast<unsigned*>(armour_handle_pinned(h, 9, 64));   // (the status words of the per-step kernel come back through it)
-    if (!st_pin) { armour_set_error("page-locked status block"); return ARMOUR_EDEVICE; }
+    ARMOUR_TRY(wk->h_status.reserve(16));   // (the status words of the per-step kernel come back through it)
+    unsigned* st_pin = wk->h_status;
     if (h->no_torque()) {  // no torque tables in these modes: empty PZs, zero radius (RT/armour_main.cu:172-175: the radius stays zero)
         HIPCHK(hipMemsetAsync(h->d_tq_count, 0, (size_t)B * n * T * sizeof(int), h->stream));
         HIPCHK(hipMemsetAsync(wk->d_torque_radius, 0, (size_t)B * n * T * sizeof(double), h->stream));
@@ -2398,7 +2402,11 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     const size_t n_tr = (size_t)B * n * T, n_lg = (size_t)B * T * J * 18, n_lc = (size_t)B * J * T, n_tc = (size_t)B * n * T;
     const size_t off_lg = n_tr * sizeof(double), off_lc = off_lg + n_lg * sizeof(double), off_tc = off_lc + n_lc * sizeof(int),
                  off_ps = (off_tc + n_tc * sizeof(int) + 7) & ~(size_t)7, off_mg = off_ps + (size_t)B * sizeof(unsigned long long), rb_bytes = off_mg + (size_t)B * sizeof(unsigned long long);
-    unsigned char* rb = rb_bytes <= ((size_t)4 << 20) ? reinterpret_cast<unsigned char*>(armour_handle_pinned(h, 8, rb_bytes)) : nullptr;
+    unsigned char* rb = nullptr;
+    if (rb_bytes <= ((size_t)4 << 20)) {
+        ARMOUR_TRY(wk->h_readback.reserve(rb_bytes));
+        rb = wk->h_readback;
+    }
     for (bool again = true; again;) {   // again: step_pass_verdict
         const bool chain = n_items > 0;
         if (chain && ((rc = plan_step_launch(h, cus, cap_raw, d_items, n_items, false, &plan)) != ARMOUR_OK || (rc = queue_step_launch(h, wk, plan, st_pin)) != ARMOUR_OK)) return rc;
@@ -2463,7 +2471,7 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
 // into `d_full` ([B][5][36][Q] doubles, device): the same kernel code as the build's, with nothing left out.  For armour_get_hyperplanes
 // (parity tests, diagnostics); the product path reads the lean table.
 int armour_p1_full_planes(ArmourPlanner* h, double* d_full) {
-    P1Work* wk = (P1Work*)h->p1;
+    P1Work* wk = h->p1;
     if (!wk || !wk->d_link_gens || !wk->d_obstacles || h->O <= 0) { armour_set_error("no reach sets on the device to rebuild the half-space table from"); return ARMOUR_ESTATE; }
     const int Q = h->J * h->T * h->O, nbx = (Q + 63) / 64;
     hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, h->B), dim3(256), 0, h->stream, h->B, h->T, h->J, h->O,

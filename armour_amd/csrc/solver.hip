@@ -546,10 +546,11 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     ARMOUR_TRY(w.blk_rows.reserve((size_t)p.Bs * p.nb * p.cap_blk * sizeof(SolveRow)));
     ARMOUR_TRY(w.qp_rows.reserve((size_t)p.Bs * p.cap_rows * sizeof(SolveRow)));
     ARMOUR_TRY(w.flags.reserve((size_t)p.Bs * 8 * (p.cap_rows + 2 * NV)));   // (active / excluded) x the four QP attempts
-    s.hres = reinterpret_cast<ArmourSolveResult*>(armour_handle_pinned(h, 1, (size_t)B * sizeof(ArmourSolveResult)));
-    s.hblock = reinterpret_cast<unsigned char*>(armour_handle_pinned(h, 2, s.block_bytes));
-    if (!s.hres || !s.hblock) return ARMOUR_EDEVICE;
-    SolveCtl* hctl = reinterpret_cast<SolveCtl*>(s.hblock);
+    ARMOUR_TRY(w.h_res.reserve((size_t)B));
+    ARMOUR_TRY(w.h_ctl.reserve(s.block_bytes));
+    s.hres = w.h_res;
+    s.hblock = w.h_ctl;
+    SolveCtl* hctl = w.h_ctl.as<SolveCtl>();
     memset(s.hres, 0, (size_t)B * sizeof(ArmourSolveResult));
     memset(hctl, 0, (size_t)B * sizeof(SolveCtl));
     for (int b = 0; b < B; b++) {   // phase 0: CMD_EVAL_GJ at the start point (zeros, or armour_solve_from's)
@@ -582,9 +583,11 @@ static int stage_device_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, c
     const double no_budget_s = std::max(5.0, 1.0 + 50.0 * (double)std::max(1, opt.max_iterations) * (1.0 + std::max(0, opt.max_line_search)) * p.tiles_per_block * 4e-6);
     s.hard_s = hard_cap_s > 0 ? hard_cap_s : (a.budget_ticks >= 0 ? a.budget_ticks / plan.ticks_per_ms * 1e-3 + 1.0 : no_budget_s);
     a.hard_ticks = std::max<long long>(1, (long long)(s.hard_s * 1e3 * plan.ticks_per_ms));
-    const bool timing = armour_trace_solve();
-    s.hstamps = timing ? reinterpret_cast<long long*>(armour_handle_pinned(h, 0, (size_t)B * 64 * sizeof(long long) + (size_t)B * n * sizeof(double))) : nullptr;
-    if (s.hstamps) memset(s.hstamps, 0, (size_t)B * 64 * sizeof(long long));
+    if (armour_trace_solve()) {
+        ARMOUR_TRY(w.h_stamps.reserve((size_t)B * 64));
+        s.hstamps = w.h_stamps;
+        memset(s.hstamps, 0, (size_t)B * 64 * sizeof(long long));
+    }
     a.stamps = s.hstamps;
     return ARMOUR_OK;
 }
@@ -687,8 +690,9 @@ static int setup_host_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, con
     int rc;
     s.h = h; s.opt = opt; s.B = B; s.n = n; s.m = m;
     // (the page-locked mirrors are kept across solves; armour_eval_g_jac_device reads k from hk in place)
-    s.hk = armour_handle_pinned(h, 0, (size_t)B * n * sizeof(double));
-    if (!s.hk) return ARMOUR_EDEVICE;
+    SolveHostWork& w = h->solve_host;
+    ARMOUR_TRY(w.k.reserve((size_t)B * n));
+    s.hk = w.k;
     s.xl.resize(n); s.xu.resize(n);
     if ((rc = armour_upload_bounds(h)) != ARMOUR_OK) return rc;   // (d_bounds: once per problem set, on the device)
     if (!h->bounds_on_host) {  // this form's own host copy, once per problem set
@@ -700,10 +704,10 @@ static int setup_host_solve(ArmourPlanner* h, const ArmourSolveOptions& opt, con
     // rows a segment may hand back (its slice of the page-locked buffer): everything if the batch is small
     s.cap_rows = (int)std::max<size_t>(64, std::min<size_t>(2 * kScanRowsPerBlock, ((size_t)128 << 20) / ((size_t)B * s.nseg * sizeof(SolveRow))));
     if (h->tune(ARMOUR_OPT_SOLVE_ROW_CAP) > 0) s.cap_rows = std::max(1, h->tune(ARMOUR_OPT_SOLVE_ROW_CAP));  // tests: force the overflow fallback
-    s.hviol_seg = reinterpret_cast<long long*>(armour_handle_pinned(h, 3, (size_t)B * s.nseg * sizeof(long long)));
-    s.hcount = reinterpret_cast<int*>(armour_handle_pinned(h, 4, (size_t)B * s.nseg * sizeof(int)));
-    s.hrows = reinterpret_cast<SolveRow*>(armour_handle_pinned(h, 5, (size_t)B * s.nseg * s.cap_rows * sizeof(SolveRow)));
-    if (!s.hviol_seg || !s.hcount || !s.hrows) return ARMOUR_EDEVICE;
+    ARMOUR_TRY(w.viol_seg.reserve((size_t)B * s.nseg));
+    ARMOUR_TRY(w.count.reserve((size_t)B * s.nseg));
+    ARMOUR_TRY(w.rows.reserve((size_t)B * s.nseg * s.cap_rows * sizeof(SolveRow)));
+    s.hviol_seg = w.viol_seg; s.hcount = w.count; s.hrows = w.rows.as<SolveRow>();
     s.viol.resize(B); s.f.resize(B); s.gradf.resize((size_t)B * n);
     // constant diagonal Hessian of the cost (solver_common.h)
     s.Hd.assign((size_t)B * NV, 1e-12);
@@ -746,9 +750,9 @@ static int evaluate(HostSolve& s, Scan mode) {
     bool overflow = false;
     for (size_t i = 0; i < (size_t)B * nseg; i++) overflow = overflow || s.hcount[i] > s.cap_rows;
     if (overflow) {  // more candidate rows than the buffer holds: bring the whole linearisation over, as before
-        s.hg = armour_handle_pinned(h, 1, bm * sizeof(double));
-        s.hj = armour_handle_pinned(h, 2, bm * n * sizeof(double));
-        if (!s.hg || !s.hj) return ARMOUR_EDEVICE;
+        ARMOUR_TRY(h->solve_host.g.reserve(bm));
+        ARMOUR_TRY(h->solve_host.jac.reserve(bm * n));
+        s.hg = h->solve_host.g; s.hj = h->solve_host.jac;
         HIPCHK(hipMemcpyAsync(s.hg, h->d_g, bm * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(s.hj, h->d_jac, bm * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if ((r = armour_spin_on_stream(h->stream)) != ARMOUR_OK) return r;
