@@ -32,7 +32,8 @@ namespace {
 // EX: every wave holds exactly PPW live planes and the block slices in one pass: the PZ-table loads are issued first and
 // the plane loads, a fixed number, after them, so the slicing (waiting for the tables with vmcnt(#plane loads)) runs while
 // the planes are still in flight; the barriers before the scan wait for LDS traffic only.
-template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX>
+// ROUNDS: slicing rounds of an EX collision block (p2_tiles.h load_pass_uncond), chosen by armour_p2_launch.
+template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS>
 __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE(DFC, MULTI)))) void armour_p2_eval_kernel(P2Tables tb, const double* __restrict__ k_all,
                                                                   double* __restrict__ g_all, double* __restrict__ jac_all,
                                                                   P2Launch lp) {
@@ -57,10 +58,10 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE
     if ((P2_ABLATE & 4) && role >= lp.nbc + lp.nbt) return;
 #endif
 #ifdef P2_TIMELINE
-    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw, t_entry);
+    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw, t_entry);
     else
 #endif
-    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
+    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
     else if (role < lp.nbc + lp.nbt) torque_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
     else limit_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
 }
@@ -189,11 +190,19 @@ int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const uns
     if (rc != ARMOUR_OK) return rc;
     if (skip_collision_blocks) lp.role0 = lp.nbc;   // the torque blocks and the limit block only
     dim3 grid(lp.nbc + lp.nbt + 1 - lp.role0, tb.B), block(P2_BLOCK);
+    // EX launches: a block has at most max_pairs * 3 * strideL slicing tasks; where one round of P2_BLOCK threads holds them all, the kernel
+    // without the second round (a host decision from the plan's own values; the rows are the same doubles either way)
+    bool one_round = exact && (long long)lp.max_pairs * 3 * lp.strideL <= P2_BLOCK;
+#if defined(P2_ABLATE) && (P2_ABLATE & (64 | 128))   // development only: the two bound builds are measured on the two-round kernel
+    one_round = false;
+#endif
 #define P2_LAUNCH_M(G, J, M)                                                                                                                      \
     do {                                                                                                                                          \
-        if (dfc && exact && !(M)) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);      \
+        if (dfc && exact && !(M) && one_round) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true, 1>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        else if (dfc && exact && !(M)) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);      \
         else if (dfc && six) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, true, true, 6, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);                \
         else if (dfc) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, true, true, 9, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);              \
+        else if (tb.ll_shared && exact && !(M) && one_round) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true, 1>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared && exact && !(M)) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared && six) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, false, true, 6, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, false, true, 9, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \

@@ -230,7 +230,11 @@ __device__ inline void load_pass(const P2Tables& tb, const P2Launch& lp, int b, 
 // The same registers through UNCONDITIONAL loads with clamped indices (threads without a task re-read task 0's entry) and no
 // select on a loaded value (the compiler would sink the load into the branch): a fixed number of loads, so that loads issued
 // after them can stay in flight while these are waited for (vmcnt counts in order and takes an immediate).
+// ROUNDS: 2, or 1 for launches in which no block has a task beyond the first round (armour_p2_launch: max_pairs * 3 * strideL <= P2_BLOCK;
+// the headline has 150) -- the second round's three clamped loads, its index arithmetic and its predicated-off terms are then dead code.
+template <int ROUNDS>
 __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, int b, int lt_first, int pc, PassRegs& pr) {
+    static_assert(ROUNDS == 1 || ROUNDS == P2_TASK_ROUNDS, "one slicing round or all of them");
     const int tid = threadIdx.x;
     const int per_pair = lp.strideL * P2_SL, per_pair3 = lp.strideL * 3;
     const int ntask = pc * per_pair3;
@@ -241,8 +245,18 @@ __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, 
     const char* co_b = reinterpret_cast<const char*>(tb.link_coeff) + (size_t)(uint32_t)b * lp.ex_co_bytes;
     const char* cen_b = reinterpret_cast<const char*>(tb.link_center) + (size_t)(uint32_t)b * lp.ex_cen_bytes;
     const char* ind_b = reinterpret_cast<const char*>(tb.link_indep) + (size_t)(uint32_t)b * lp.ex_cen_bytes;
+    // (A round beyond ROUNDS is a round without a live task, as constants: the monomial-term loop keeps its P2_TASK_ROUNDS trips and the
+    //  compiler drops the dead one.  Written as a shorter loop here and there, the kernel has the same loads and registers but another
+    //  instruction order in all three roles, and the headline launch is 3 % slower with it -- no faster than with both rounds -- on three
+    //  boxes, although its collision blocks alone time the same: profiles/p2_vector_loads.txt.)
+#if defined(P2_ABLATE) && (P2_ABLATE & 128)   // development only (wrong rows where a block has second-round tasks): the second round's loads are not issued
+    constexpr int live_rounds = 1;
+#else
+    constexpr int live_rounds = ROUNDS;
+#endif
 #pragma unroll
     for (int r = 0; r < P2_TASK_ROUNDS; r++) {
+        if (r >= live_rounds) { pr.tkey[r] = 0; pr.tco[r] = 0.0; pr.tcnt[r] = -1; pr.tdst[r] = 0; continue; }
         const int task = tid + r * P2_BLOCK;
         const bool valid = task < ntask;
         const int tk = valid ? task : 0;
@@ -266,7 +280,8 @@ __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, 
 // EX: every wave holds exactly PPW live planes and the block slices in one pass: the PZ-table loads are issued first and
 // the plane loads, a fixed number, after them, so the slicing (waiting for the tables with vmcnt(#plane loads)) runs while
 // the planes are still in flight; the barriers before the scan wait for LDS traffic only.
-template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX>
+// ROUNDS (EX only): slicing rounds a thread loads and evaluates, see load_pass_uncond; the other kernels keep P2_TASK_ROUNDS.
+template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS>
 __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Launch& lp, const int b, const int role, const double* __restrict__ k0,
                                    const double k_first, double* __restrict__ g0_in, double* __restrict__ jac0_in, unsigned char* smem_raw
 #ifdef P2_TIMELINE
@@ -331,7 +346,8 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     const int npairs = fast_div(q_end - 1, lp.magic_O) - lt_first + 1;
     const bool single_pass = npairs <= lp.pair_chunk;
     PassRegs pr;
-    if (EX) load_pass_uncond(tb, lp, b, lt_first, npairs, pr);
+    static_assert(EX || ROUNDS == P2_TASK_ROUNDS, "only the EX kernels have a one-round form");
+    if (EX) load_pass_uncond<ROUNDS>(tb, lp, b, lt_first, npairs, pr);
     // EX launches (armour_p2_plan: ex_layout_ok): waves 0 and 1 hold six planes with an obstacle generator each -- {Ax,Ay}, {Az,delta}:
     // twelve 16-B loads; waves 2 and 3 six CONSECUTIVE link x link planes each, starting at an even p - 21: their 18 normal components
     // are 144 contiguous, 16-B aligned bytes of the (link, time step) record -- nine loads whose 64 lanes touch 64/O + 1 records -- and
@@ -379,7 +395,14 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
         const char* plb = reinterpret_cast<const char*>(tb.planes) + (size_t)(uint32_t)b * lp.ex_planes_bytes;
         const char* llb = reinterpret_cast<const char*>(tb.planes_ll) + (size_t)(uint32_t)b * lp.ex_ll_bytes;
         const __amdgpu_buffer_rsrc_t rs_pl = table_rsrc(plb, lp.ex_planes_bytes);
+#if defined(P2_ABLATE) && (P2_ABLATE & 64)
+        // development only (wrong rows; no address changes): the link x link waves read their nine normal registers through a resource of
+        // length 0 -- every lane is out of range, the loads return zeros and fetch nothing, and stay nine instructions, so the vmcnt of the
+        // slicing is the shipped one (profiles/p2_vector_loads.txt).
+        const __amdgpu_buffer_rsrc_t rs_a = table_rsrc(ll_wave ? llb : plb, ll_wave ? 0u : lp.ex_planes_bytes);
+#else
         const __amdgpu_buffer_rsrc_t rs_a = table_rsrc(ll_wave ? llb : plb, ll_wave ? lp.ex_ll_bytes : lp.ex_planes_bytes);
+#endif
         const uint32_t vq = (uint32_t)q * 16u, va = ll_wave ? (uint32_t)q_lt * (uint32_t)(ARMOUR_LL_RECORD * sizeof(double)) : vq;
 #pragma unroll
         for (int j = 0; j < 12; j++) raw[j] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(j < 9 ? rs_a : rs_pl, j < 9 ? va : vq, (int)so[j], 0));

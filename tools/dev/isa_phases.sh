@@ -1,6 +1,7 @@
 #!/bin/bash
 # dev only: static instruction counts between the P2_TIMELINE stamps of the headline instantiation of the one-point fused kernel
-# (armour_p2_eval_kernel<true, true, false, false, true, 6, true>: g and jac, one point, d read, compact link x link normals, six slots, EX).
+# (armour_p2_eval_kernel<true, true, false, false, true, 6, true, 1>: g and jac, one point, d read, compact link x link normals, six slots, EX,
+# one slicing round).
 #   bash tools/dev/isa_phases.sh [CSRC]      CSRC: another checkout's armour_amd/csrc (default: this checkout's)
 # Stretches are what lies between two stamps in the assembly, in file order (the collision path is laid out in program order); the first
 # stamp is the kernel's entry stamp, the second P2_STAMP(0).  Also printed: the kernel's registers, scratch and occupancy.
@@ -15,7 +16,7 @@ python3 - "$TMP/p2_tl.s" <<'PY'
 import re, sys
 from collections import Counter
 L = open(sys.argv[1]).read().split('\n')
-HEAD = 'armour_p2_eval_kernelILb1ELb1ELb0ELb0ELb1ELi6ELb1EE'
+HEAD = 'armour_p2_eval_kernelILb1ELb1ELb0ELb0ELb1ELi6ELb1ELi1EE'
 a = next(i for i, l in enumerate(L) if l.startswith('_ZN') and ':' in l and HEAD in l.split(':')[0])
 b = next(i for i in range(a, len(L)) if L[i].startswith('.Lfunc_end'))
 K = L[a:b]
@@ -34,6 +35,13 @@ for nme, (x, y) in zip(names, zip(st[:-1], st[1:])):
     print(f"{nme:9s} {len(seg):4d}  SALU {c['s']:3d} VALU {c['v']:3d} loads {loads:2d} (vector {sum(v for k, v in op.items() if re.match(r'(global|buffer|flat)_load', k)):2d})"
           f" LDS {c['ds']:2d} v_cndmask {sum(v for k, v in op.items() if k.startswith('v_cndmask')):3d} s_waitcnt {op['s_waitcnt']:2d} branches {sum(v for k, v in op.items() if 'branch' in k):2d}  {u64}")
 print(f"collision path, stamp 0 -> 6: {total - len(ins(K[st[0] + 1:st[1]]))} instructions; whole kernel {len(ins(K))}")
+# a fingerprint of the compiler's output for this kernel: the headline's speed has moved by 3 % with the instruction order alone
+# (profiles/p2_vector_loads.txt), so compare this line before and after a toolchain change or an edit to any of the three roles
+import hashlib
+body = [re.sub(r'\.?LBB\d+_\d+', 'L', s) for s in ins(K) if not s.startswith('s_memrealtime')]
+vloads = sum(1 for s in body if re.match(r'(global|buffer|flat)_load', s))
+waits = [int(m.group(1)) for m in (re.search(r'vmcnt\((\d+)\)', s) for s in body if s.startswith('s_waitcnt')) if m]
+print(f"fingerprint: vector loads {vloads}, s_waitcnt vmcnt {waits}, sha1 of the instruction stream {hashlib.sha1(chr(10).join(body).encode()).hexdigest()[:12]}")
 tail = '\n'.join(L[b:b + 80])
 for key in ('NumSgprs', 'NumVgprs', 'NumAgprs', 'ScratchSize', 'Occupancy', 'LDSByteSize'):
     m = re.search(r';\s*' + key + r':\s*(\d+)', tail)
