@@ -158,6 +158,7 @@ OPT_P1_TV_AUX3 = 119
 OPT_P1_FULL_PLANES = 120
 OPT_P1_TV_ROW_WIDTH = 122   # 0 automatic | 50 | 64 doubles per row of the time-vectorised kernel's work slots
 OPT_P2_EX = 130
+OPT_P2_NO_ZERO_TEST = 134   # 0: the EX kernels keep the scan's zero-normal test (armour_debug_p2_zero_plan says which form a handle takes)
 OPT_STEPS_GRAPH_MIN = 131
 OPT_PINNED_MODE = 132
 OPT_CULL_ROWS = 133   # 1: armour_eval_violations* evaluate only the rows that can be violated for some k (armour_get_row_relevance)
@@ -198,7 +199,7 @@ EXPORTS = [
     "armour_ws_trees_create", "armour_ws_trees_create_host", "armour_ws_trees_destroy", "armour_ws_trees_grow", "armour_ws_trees_read",
     "armour_debug_ws_trees_set_iterations",
     "armour_debug_block_steps", "armour_debug_block_split", "armour_debug_block_owner",
-    "armour_debug_p2_plan", "armour_debug_p2_plan_shape",
+    "armour_debug_p2_plan", "armour_debug_p2_plan_shape", "armour_debug_p2_zero_plan", "armour_debug_p2_zero_plan_shape",
 ]
 
 _lib = None
@@ -370,6 +371,9 @@ def load():
     if hasattr(L, "armour_debug_p2_plan"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
         L.armour_debug_p2_plan.argtypes = [vp, ip, C.POINTER(C.c_uint32)]
         L.armour_debug_p2_plan_shape.argtypes = [C.c_int32] * 8 + [C.POINTER(C.c_uint64), ip, C.POINTER(C.c_uint32)]
+    if hasattr(L, "armour_debug_p2_zero_plan"):
+        L.armour_debug_p2_zero_plan.argtypes = [vp, ip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.armour_debug_p2_zero_plan_shape.argtypes = [C.c_int32] * 8 + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), ip]
     L.armour_track_options_default.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions)]
     L.armour_track_options_default.restype = None
     L.armour_track.argtypes = [C.POINTER(ArmourRobot), C.POINTER(ArmourTrackOptions), C.c_int32, dp, dp, dp, dp, dp, dp, dp, dp,

@@ -102,7 +102,7 @@ static int ensure_capacity(ArmourPlanner* h, int B, int O) {
     ARMOUR_TRY(h->d_planes.reserve((size_t)nb * armour_planes_per_problem(h->J * h->T * no)));
     ARMOUR_TRY(h->d_planes_ll.reserve((size_t)nb * armour_planes_ll_per_problem(h->J * h->T)));
     ARMOUR_TRY(h->d_obs_center.reserve((size_t)nb * 3 * (no > 0 ? no : 1)));
-    ARMOUR_TRY(h->d_plane_skip.reserve((size_t)nb));
+    ARMOUR_TRY(h->d_plane_skip.reserve(2 * (size_t)nb));   // plane_skip | plane_zero
     ARMOUR_TRY(h->d_bez.reserve((size_t)nb * 3 * h->n));
     const size_t mmax = (size_t)h->n * h->T + (size_t)h->J * h->T * no + 4 * h->n;
     ARMOUR_TRY(h->d_k.reserve((size_t)nb * h->n));
@@ -150,7 +150,7 @@ const TuningSpec kTuning[] = {
     {ARMOUR_OPT_P1_TV_MIN_GROUPS, 31, 1, 1e6}, {ARMOUR_OPT_P1_TV_WAVES, 0, 0, 8}, {ARMOUR_OPT_P1_TV_FREE, 1, 0, 1}, {ARMOUR_OPT_P1_TV_SPLIT_FK, -1, -1, 1},
     {ARMOUR_OPT_P1_TV_DEDICATED, 1, 0, 1}, {ARMOUR_OPT_P1_TV_HELP_SHIFT, 0, 0, 3}, {ARMOUR_OPT_P1_TV_HELPERS, 1, 0, 31}, {ARMOUR_OPT_P1_TV_HELP_MIN, 192, 1, 1e6},
     {ARMOUR_OPT_P1_TV_HELP_N, 1, 0, 1}, {ARMOUR_OPT_P1_TV_AUX3, 1, 0, 1}, {ARMOUR_OPT_P1_TV_ROW_WIDTH, 0, 0, 64}, {ARMOUR_OPT_P1_FULL_PLANES, 0, 0, 1},
-    {ARMOUR_OPT_P2_EX, 1, 0, 1}, {ARMOUR_OPT_STEPS_GRAPH_MIN, 2, 0, 1e6}, {ARMOUR_OPT_PINNED_MODE, 0, 0, 2}, {ARMOUR_OPT_CULL_ROWS, 0, 0, 1},
+    {ARMOUR_OPT_P2_EX, 1, 0, 1}, {ARMOUR_OPT_P2_NO_ZERO_TEST, 1, 0, 1}, {ARMOUR_OPT_STEPS_GRAPH_MIN, 2, 0, 1e6}, {ARMOUR_OPT_PINNED_MODE, 0, 0, 2}, {ARMOUR_OPT_CULL_ROWS, 0, 0, 1},
     {ARMOUR_OPT_SOLVE_SUB_TILES, 48, 1, 1e6}, {ARMOUR_OPT_SOLVE_DEVICE, 1, 0, 2}, {ARMOUR_OPT_SOLVE_CUT_TILES, 156, 1, 1e6}, {ARMOUR_OPT_SOLVE_BLOCKS, 0, 0, 1e6},
     {ARMOUR_OPT_SOLVE_SUB_BATCH, 0, 0, 1e6}, {ARMOUR_OPT_SOLVE_ROW_CAP, 0, 0, 1e7}, {ARMOUR_OPT_SOLVE_HARD_CAP_S, 0, 0, 1e6}, {ARMOUR_OPT_SOLVE_WAVES_PER_SIMD, 0, 0, 2}, {ARMOUR_OPT_SOLVE_CULL, -1, -1, 1},
 };
@@ -294,7 +294,13 @@ int armour_refresh_table_stats(ArmourPlanner* h) {
     for (int v : tc) { st += v; if (v > mt) mt = v; }
     h->sum_link = sl; h->sum_torque = st; h->max_link = ml; h->max_torque = mt;
     h->h_plane_skip.assign((size_t)h->B, 0ull);
-    if (h->O > 0) HIPCHK(hipMemcpy(h->h_plane_skip.data(), h->d_plane_skip, (size_t)h->B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    h->h_plane_zero.assign((size_t)h->B, ~0ull);   // masks that are not the build's (loaded tables): every plane may be zero somewhere
+    if (h->O > 0 && h->plane_zero_built) {         // plane_skip | plane_zero of the build, one copy
+        std::vector<unsigned long long> both(2 * (size_t)h->B);
+        HIPCHK(hipMemcpy(both.data(), h->d_plane_skip, both.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::copy(both.begin(), both.begin() + h->B, h->h_plane_skip.begin());
+        std::copy(both.begin() + h->B, both.end(), h->h_plane_zero.begin());
+    } else if (h->O > 0) HIPCHK(hipMemcpy(h->h_plane_skip.data(), h->d_plane_skip, (size_t)h->B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (h->O > 0 && armour_trace_p1()) {   // development: which planes the collision rows never need (p1_reach.hip, armour_p1_planes_kernel)
         unsigned long long all_and = ~0ull, all_or = 0ull;
         for (unsigned long long v : h->h_plane_skip) { all_and &= v; all_or |= v; }
@@ -419,6 +425,7 @@ extern "C" int armour_debug_load_tables(ArmourPlanner* h, int32_t B, int32_t O, 
         h->planes_lean = 0; h->planes_have_d = 1;
     }
     HIPCHK(hipMemset(h->d_plane_skip, 0, (size_t)B * sizeof(unsigned long long)));  // loaded tables: evaluate every plane
+    h->plane_zero_built = false;                                                    // ... and keep the scan's zero-normal test
 #undef UP
     h->h_torque_radius.assign(torque_radius, torque_radius + (size_t)B * n * T);
     h->h_link_gens.assign((size_t)B * T * J * 18, 0.0);
@@ -536,14 +543,14 @@ extern "C" int armour_eval_g_jac_device(ArmourPlanner* h, const double* d_k, dou
     NEED_READY(h);
     if (!d_k) { armour_set_error("d_k is null"); return ARMOUR_EINVAL; }
     const P2Tables tb = armour_make_tables(h);
-    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream);
+    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream);
 }
 
 static int enqueue_steps(ArmourPlanner* h, const double* d_k, int steps, double* d_g, double* d_jac, hipStream_t st) {
     const P2Tables tb = armour_make_tables(h);
     const size_t stride = (size_t)h->B * h->n;
     for (int s = 0; s < steps; s++) {
-        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k + (size_t)s * stride, d_g, d_jac, st);
+        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), d_k + (size_t)s * stride, d_g, d_jac, st);
         if (rc != ARMOUR_OK) return rc;
     }
     return ARMOUR_OK;
@@ -618,7 +625,7 @@ extern "C" int armour_eval_g_jac_device_multi(ArmourPlanner* h, const double* d_
     if (points == 0) return ARMOUR_OK;
     const P2Tables tb = armour_make_tables(h);
     const long long bn = (long long)h->B * h->n, bm = (long long)h->B * h->m;
-    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream,
+    return armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), d_k, d_g, d_jac, stream ? (hipStream_t)stream : h->stream,
                             points, bn, bm, bm * h->n);
 }
 
@@ -645,14 +652,14 @@ extern "C" int armour_eval_g_jac(ArmourPlanner* h, const double* k, double* g, d
     const int pinned_mode = h->tune(ARMOUR_OPT_PINNED_MODE);
     const bool all_pinned = in_pinned(k, bn * sizeof(double)) && in_pinned(g, bm * sizeof(double)) && in_pinned(jac, bm * h->n * sizeof(double));
     if (all_pinned && pinned_mode == 1) {
-        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), k, g, jac, h->stream);
+        int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), k, g, jac, h->stream);
         if (rc != ARMOUR_OK) return rc;
         return armour_spin_on_stream(h->stream);
     }
     const double* k_dev = h->d_k;
     if (all_pinned && pinned_mode == 2) k_dev = k;
     else HIPCHK(hipMemcpyAsync(h->d_k, k, bn * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), k_dev, g ? h->d_g : nullptr, jac ? h->d_jac : nullptr, h->stream);
+    int rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), k_dev, g ? h->d_g : nullptr, jac ? h->d_jac : nullptr, h->stream);
     if (rc != ARMOUR_OK) return rc;
     if (g && jac && jac == g + bm) {   // the caller's g and jac are one block (as the device copies are): one transfer instead of two
         HIPCHK(hipMemcpyAsync(g, h->d_g, bm * (1 + (size_t)h->n) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -811,7 +818,7 @@ static int eval_violations_device_impl(ArmourPlanner* h, const double* d_k, Armo
     if (allow_cull && h->tune(ARMOUR_OPT_CULL_ROWS)) return armour_eval_violations_culled(h, d_k, d_out, st);   // the relevant rows only: relevance.hip
     const P2Tables tb = armour_make_tables(h);
     // g only (the Jacobian tile, 7/8 of the output bytes, is neither computed nor written), into the handle's own g buffer
-    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, h->d_g, nullptr, st);
+    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), d_k, h->d_g, nullptr, st);
     if (rc != ARMOUR_OK) return rc;
     ViolArgs a;
     a.rule = armour_row_rule(h);

@@ -179,6 +179,10 @@ struct ArmourPlanner {
     DevBuf<double> d_tr_stage;   // the same on the device, for the kernel that fills the bounds (armour_upload_bounds)
     std::vector<double> h_link_gens;                  // [B][T][J][18]
     std::vector<unsigned long long> h_plane_skip;     // [B] host copy of d_plane_skip
+    std::vector<unsigned long long> h_plane_zero;     // [B] bit p set: plane p has the zero normal in at least one row of the problem (bits of skipped planes carry no meaning); all ones when the masks are not the build's
+    bool plane_zero_built = false;                    // d_plane_skip + B holds the last build's plane_zero (p1_reach.hip queue_planes); false for loaded tables
+    // what armour_p2_plan may conclude from: the zero-normal masks, or null with ARMOUR_OPT_P2_NO_ZERO_TEST = 0 (the scan keeps its test)
+    const unsigned long long* p2_zero() const { return (tune(ARMOUR_OPT_P2_NO_ZERO_TEST) && h_plane_zero.size() >= (size_t)B) ? h_plane_zero.data() : nullptr; }
     std::vector<double> h_bez;                        // [B][3][n] host copy of d_bez (one-problem launches pass it in the kernel arguments)
     std::vector<double> h_prune_margin;               // [B] how close the last build's simplify() verdicts came to flipping (armour_get_prune_margin)
     // device tables (sized for allocB x allocO)
@@ -201,7 +205,7 @@ struct ArmourPlanner {
     double planes_ms = 0;   // device time of the half-space kernels of the last build
     DevBuf<double> d_planes_ll;
     int ll_shared = 0;  // the link x link normals of the loaded table are identical over the obstacles (always so for tables built by P1)
-    DevBuf<unsigned long long> d_plane_skip;
+    DevBuf<unsigned long long> d_plane_skip;   // [2][B]: plane_skip, then plane_zero of the same build
     DevBuf<double> d_bez;
     // staging for the host-pointer API
     DevBuf<double> d_k;
@@ -233,7 +237,7 @@ bool armour_trace_p1();      // ARMOUR_P1_TRACE
 bool armour_trace_solve();   // ARMOUR_SOLVE_TIMING
 
 // p2_eval.hip
-int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, const double* d_k, double* d_g, double* d_jac, hipStream_t stream,
+int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const unsigned long long* h_zero, const double* h_bez, const double* d_k, double* d_g, double* d_jac, hipStream_t stream,
                      int steps = 1, long long k_stride = 0, long long g_stride = 0, long long j_stride = 0, bool skip_collision_blocks = false);
 // relevance.hip
 int armour_relevance_build(ArmourPlanner* h, bool for_solver);   // (relevance.hip; for_solver: also the lists armour_solve's culled device form walks)

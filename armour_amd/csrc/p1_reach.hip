@@ -1375,7 +1375,7 @@ __device__ inline void pair_normal(const double* ga, const double* gb, double& C
 template <int GRP, bool LEAN>
 __device__ inline void planes_of_group(const double (&G)[9][3], const double (&c)[3], bool in, int Q, int q, int o, int lt, int JT,
                                        double* __restrict__ out, double* __restrict__ ll, unsigned long long (&Sg)[ARMOUR_NPLANES][64], unsigned long long (&sig)[9], int lane,
-                                       unsigned long long pre, bool store_d) {
+                                       unsigned long long pre, bool store_d, unsigned& zbits) {
 #pragma unroll
     for (int k = 0; k < 9; k++) {
         constexpr int p0 = GRP * 9;
@@ -1391,6 +1391,8 @@ __device__ inline void planes_of_group(const double (&G)[9][3], const double (&c
         double dl = 0.0;
 #pragma unroll
         for (int j = 0; j < 9; j++) dl += fabs(C0 * G[j][0] + C1 * G[j][1] + C2 * G[j][2]);
+        // plane_zero: the scan's own test (p2_tiles.h collision_block: nz) on the doubles stored below, so -0.0 counts as zero
+        if (in && !((C0 != 0.0) | (C1 != 0.0) | (C2 != 0.0))) zbits |= 1u << k;
         if (in) {
             // (layout: common.h armour_plane_index -- {Ax,Ay} and {Az,delta} are 16-B pairs, written as such)
             if (!LEAN || p < ARMOUR_FIRST_LL_PLANE) *reinterpret_cast<double2*>(out + armour_plane_index(Q, q, p, 0)) = make_double2(C0, C1);
@@ -1475,14 +1477,16 @@ __device__ inline unsigned planes_redundant(const unsigned long long (&Sg)[ARMOU
 // strict-> scan of :268-279 has already seen (d and delta follow the normal exactly), so skipping it changes
 // neither the maximum nor the winning normal.  The AND over all rows of a problem goes to plane_skip[b]; with
 // axis-aligned box obstacles that is 12 of the 36 planes (all obstacle x error-generator and error x error pairs).
+// Next to it plane_zero[b], an OR over the rows: bit p set when plane p has the zero normal in at least one row (all three stored components
+// == 0.0, the scan's own comparison) -- what armour_p2_plan needs to know to drop that test from the scan; bits of skipped planes carry no meaning.
 // Four threads per row (wave w of the 256-thread block builds planes 9w .. 9w+8 of the block's 64 rows); the signatures of the
 // normals go through LDS so that each thread can test its planes against all earlier planes of its row.
 template <bool LEAN>
 __global__ __launch_bounds__(256) void armour_p1_planes_kernel(int B, int T, int J, int O, const double* __restrict__ link_gens,
                                                                const double* __restrict__ obstacles, double* __restrict__ planes,
                                                                double* __restrict__ planes_ll, double* __restrict__ obs_center,
-                                                               unsigned long long* __restrict__ skip_part, const unsigned long long* __restrict__ pre_mask,
-                                                               const unsigned long long* __restrict__ live_mask, int store_d) {
+                                                               unsigned long long* __restrict__ skip_part, unsigned long long* __restrict__ zero_part,
+                                                               const unsigned long long* __restrict__ pre_mask, const unsigned long long* __restrict__ live_mask, int store_d) {
     __shared__ unsigned long long Sg[ARMOUR_NPLANES][64];  // [plane][row of the block]: signatures of the normals (18 KB; the normals themselves, 55 KB, held the kernel at two blocks per CU)
     const int Q = J * T * O;
     const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
@@ -1508,13 +1512,21 @@ __global__ __launch_bounds__(256) void armour_p1_planes_kernel(int B, int T, int
     // this wave's nine planes, with compile-time generator indices (see planes_of_group)
     double* ll = planes_ll ? planes_ll + (size_t)b * armour_planes_ll_per_problem(J * T) : nullptr;
     unsigned long long sig[9];
+    unsigned zbits = 0u;   // bit k: plane 9 grp + k of this row has the zero normal (planes of `pre` are not looked at: skipped everywhere)
     switch (grp) {
-        case 0: planes_of_group<0, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0); break;
-        case 1: planes_of_group<1, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0); break;
-        case 2: planes_of_group<2, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0); break;
-        default: planes_of_group<3, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0); break;
+        case 0: planes_of_group<0, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0, zbits); break;
+        case 1: planes_of_group<1, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0, zbits); break;
+        case 2: planes_of_group<2, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0, zbits); break;
+        default: planes_of_group<3, LEAN>(G, c, in, Q, q, o, lt, J * T, out, ll, Sg, sig, lane, pre, store_d != 0, zbits); break;
     }
     if (!skip_part) return;   // (the full table for armour_get_hyperplanes: the masks exist already)
+    // plane_zero[b] is an OR over the problem's rows of what plane_skip ANDs: this wave's nine bits of it, next to its skip word.  No row of
+    // a box world has a computed plane without a normal: one ballot says so and the exchange is skipped (wave-uniform).
+    if (__ballot(zbits != 0u) != 0ull) {
+#pragma unroll
+        for (int o2 = 32; o2 > 0; o2 >>= 1) zbits |= __shfl_xor(zbits, o2, 64);
+    }
+    if (lane == 0) zero_part[((size_t)b * gridDim.x + blockIdx.x) * 4 + grp] = (unsigned long long)zbits << (grp * 9);
     // plane_skip[b] is an AND over the problem's rows, so a plane that ONE row needs is settled: armour_p1_plane_sample_kernel ran the
     // exact test on a few rows of the problem beforehand.  If every plane is either redundant everywhere by class (`pre`) or known
     // to be needed (`live`) -- always so for box obstacles -- the result is `pre` and this block skips the signature exchange and the
@@ -1657,20 +1669,23 @@ __global__ __launch_bounds__(256) void armour_p1_plane_class_kernel(int T, int J
     if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = s[0] & s[1] & s[2] & s[3];
 }
 
-// plane_skip[b] = AND of the planes kernel's per-wave masks of problem b
-__global__ __launch_bounds__(256) void armour_p1_skip_reduce_kernel(const unsigned long long* __restrict__ part, int per_problem, unsigned long long* __restrict__ plane_skip) {
-    __shared__ unsigned long long s[4];
+// plane_skip[b] = AND of the planes kernel's per-wave skip masks of problem b; plane_zero[b] = OR of its per-wave zero-normal masks
+__global__ __launch_bounds__(256) void armour_p1_skip_reduce_kernel(const unsigned long long* __restrict__ part, const unsigned long long* __restrict__ zpart, int per_problem,
+                                                                    unsigned long long* __restrict__ plane_skip, unsigned long long* __restrict__ plane_zero) {
+    __shared__ unsigned long long s[4], sz[4];
     const int b = blockIdx.x;
-    unsigned long long v = ~0ull;
-    for (int i = threadIdx.x; i < per_problem; i += 256) v &= part[(size_t)b * per_problem + i];
+    unsigned long long v = ~0ull, z = 0ull;
+    for (int i = threadIdx.x; i < per_problem; i += 256) { v &= part[(size_t)b * per_problem + i]; z |= zpart[(size_t)b * per_problem + i]; }
 #pragma unroll
     for (int o2 = 32; o2 > 0; o2 >>= 1) {
         const unsigned lo = __shfl_xor((unsigned)v, o2, 64), hi = __shfl_xor((unsigned)(v >> 32), o2, 64);
         v &= ((unsigned long long)hi << 32) | lo;
+        const unsigned zlo = __shfl_xor((unsigned)z, o2, 64), zhi = __shfl_xor((unsigned)(z >> 32), o2, 64);
+        z |= ((unsigned long long)zhi << 32) | zlo;
     }
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = v; sz[threadIdx.x >> 6] = z; }
     __syncthreads();
-    if (threadIdx.x == 0) plane_skip[b] = s[0] & s[1] & s[2] & s[3];
+    if (threadIdx.x == 0) { plane_skip[b] = s[0] & s[1] & s[2] & s[3]; plane_zero[b] = sz[0] | sz[1] | sz[2] | sz[3]; }
 }
 
 
@@ -2170,10 +2185,11 @@ static int queue_planes(ArmourPlanner* h, P1Work* wk) {
     const int B = h->B, T = h->T, J = h->J, O = h->O, Q = J * T * O;
     ARMOUR_TRY(wk->ev_planes.record_start(h->stream));
     const int nbx = (Q + 63) / 64, nbc = (Q + 255) / 256;
-    // [B][nbx][4] per-wave masks of the planes kernel | [B][nbc] per-block masks of the class pre-pass | [B] its result | [B] planes a sampled row needs
+    // [B][nbx][4] per-wave skip masks of the planes kernel | the same of its zero-normal masks | [B][nbc] per-block masks of the class pre-pass | [B] its result | [B] planes a sampled row needs
     const size_t part_words = (size_t)B * nbx * 4, pre_words = (size_t)B * nbc;
-    ARMOUR_TRY(wk->d_skip_part.reserve(part_words + pre_words + 2 * (size_t)B));
-    unsigned long long* d_pre_part = wk->d_skip_part + part_words;
+    ARMOUR_TRY(wk->d_skip_part.reserve(2 * part_words + pre_words + 2 * (size_t)B));
+    unsigned long long* d_zero_part = wk->d_skip_part + part_words;
+    unsigned long long* d_pre_part = d_zero_part + part_words;
     unsigned long long* d_pre = d_pre_part + pre_words;
     unsigned long long* d_live = d_pre + B;
     // The table holds what the fused evaluation reads and nothing else (planes_of_group): ARMOUR_OPT_P1_FULL_PLANES = 1 builds
@@ -2187,12 +2203,14 @@ static int queue_planes(ArmourPlanner* h, P1Work* wk) {
         hipLaunchKernelGGL(armour_p1_plane_class_kernel, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
         hipLaunchKernelGGL(armour_p1_plane_sample_kernel, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
         hipLaunchKernelGGL(armour_p1_planes_kernel<true>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
-                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_pre, d_live, store_d);
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_zero_part, d_pre, d_live, store_d);
     } else {
         hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
-                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, nullptr, nullptr, 1);
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_zero_part, nullptr, nullptr, 1);
     }
-    hipLaunchKernelGGL(armour_p1_skip_reduce_kernel, dim3(B), dim3(256), 0, h->stream, wk->d_skip_part, nbx * 4, h->d_plane_skip);
+    // (plane_zero lies behind plane_skip in one allocation: the build's read-back fetches both with the copy it made for one)
+    hipLaunchKernelGGL(armour_p1_skip_reduce_kernel, dim3(B), dim3(256), 0, h->stream, wk->d_skip_part, d_zero_part, nbx * 4, h->d_plane_skip, h->d_plane_skip + B);
+    h->plane_zero_built = true;
     h->ll_shared = 1; h->d_from_center = 1;
     h->planes_lean = lean ? 1 : 0; h->planes_have_d = (!lean || store_d) ? 1 : 0;
     HIPCHK(hipGetLastError());
@@ -2401,7 +2419,7 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     // is rare: everything is queued again behind the next one.
     const size_t n_tr = (size_t)B * n * T, n_lg = (size_t)B * T * J * 18, n_lc = (size_t)B * J * T, n_tc = (size_t)B * n * T;
     const size_t off_lg = n_tr * sizeof(double), off_lc = off_lg + n_lg * sizeof(double), off_tc = off_lc + n_lc * sizeof(int),
-                 off_ps = (off_tc + n_tc * sizeof(int) + 7) & ~(size_t)7, off_mg = off_ps + (size_t)B * sizeof(unsigned long long), rb_bytes = off_mg + (size_t)B * sizeof(unsigned long long);
+                 off_ps = (off_tc + n_tc * sizeof(int) + 7) & ~(size_t)7, off_mg = off_ps + 2 * (size_t)B * sizeof(unsigned long long), rb_bytes = off_mg + (size_t)B * sizeof(unsigned long long);
     unsigned char* rb = nullptr;
     if (rb_bytes <= ((size_t)4 << 20)) {
         ARMOUR_TRY(wk->h_readback.reserve(rb_bytes));
@@ -2422,7 +2440,7 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
             HIPCHK(hipMemcpyAsync(rb + off_lg, wk->d_link_gens, n_lg * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipMemcpyAsync(rb + off_lc, h->d_link_count, n_lc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipMemcpyAsync(rb + off_tc, h->d_tq_count, n_tc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            if (O > 0) HIPCHK(hipMemcpyAsync(rb + off_ps, h->d_plane_skip, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            if (O > 0) HIPCHK(hipMemcpyAsync(rb + off_ps, h->d_plane_skip, 2 * (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));   // plane_skip | plane_zero
             HIPCHK(hipMemcpyAsync(rb + off_mg, wk->d_margin, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         }
         // (unconditional: the bounds kernel above and the blocking copies below are ordered against h->stream -- a non-blocking stream -- by this
@@ -2455,6 +2473,8 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
         h->sum_link = sl; h->sum_torque = st2; h->max_link = ml; h->max_torque = mt;
         h->h_plane_skip.assign((size_t)B, 0ull);
         if (O > 0) memcpy(h->h_plane_skip.data(), rb + off_ps, (size_t)B * sizeof(unsigned long long));
+        h->h_plane_zero.assign((size_t)B, ~0ull);
+        if (O > 0) memcpy(h->h_plane_zero.data(), rb + off_ps + (size_t)B * sizeof(unsigned long long), (size_t)B * sizeof(unsigned long long));
         h->stats_fresh = !armour_trace_p1();   // (the trace line of armour_refresh_table_stats wants its own pass)
         armour_margin_from_words(h, reinterpret_cast<const unsigned long long*>(rb + off_mg));
     } else {
@@ -2475,7 +2495,7 @@ int armour_p1_full_planes(ArmourPlanner* h, double* d_full) {
     if (!wk || !wk->d_link_gens || !wk->d_obstacles || h->O <= 0) { armour_set_error("no reach sets on the device to rebuild the half-space table from"); return ARMOUR_ESTATE; }
     const int Q = h->J * h->T * h->O, nbx = (Q + 63) / 64;
     hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, h->B), dim3(256), 0, h->stream, h->B, h->T, h->J, h->O,
-                       wk->d_link_gens, wk->d_obstacles, d_full, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
+                       wk->d_link_gens, wk->d_obstacles, d_full, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return ARMOUR_OK;

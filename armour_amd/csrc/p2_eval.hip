@@ -33,7 +33,10 @@ namespace {
 // the plane loads, a fixed number, after them, so the slicing (waiting for the tables with vmcnt(#plane loads)) runs while
 // the planes are still in flight; the barriers before the scan wait for LDS traffic only.
 // ROUNDS: slicing rounds of an EX collision block (p2_tiles.h load_pass_uncond), chosen by armour_p2_launch.
-template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS>
+// NONZERO: an EX collision block's scan without the zero-normal test (p2_tiles.h collision_block), chosen by armour_p2_launch from the plan's verdict.
+// ONE: the launch has one problem (grid.y = 1, armour_p2_launch: tb.B == 1): b is the constant 0 and the seven `b * bytes + base` chains of a
+// block's first stretch fold away.  The headline's instantiations only.
+template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS, bool NONZERO = false, bool ONE = false>
 __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE(DFC, MULTI)))) void armour_p2_eval_kernel(P2Tables tb, const double* __restrict__ k_all,
                                                                   double* __restrict__ g_all, double* __restrict__ jac_all,
                                                                   P2Launch lp) {
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE
     //  (problem, row block) pairs so that neighbouring blocks, which share their (link, time step) records, share an L2 -- configs[2]
     //  539 us against 500: what a block streams is 30 KB of its own rows and 3 KB of shared records, and eight XCDs that each walk one
     //  contiguous stretch of the table concentrate on fewer HBM channels at a time, like the tiled table layout of round 2.)
-    const int b = blockIdx.y, role = blockIdx.x + lp.role0;
+    const int b = ONE ? 0 : blockIdx.y, role = blockIdx.x + lp.role0;
     const int n = tb.n, m = tb.m;   // (read together: one scalar load of the kernel argument block instead of two dependent ones)
     const double* k0 = k_all + (size_t)b * n;
     double* g0 = WANT_G ? g_all + (size_t)b * m : nullptr;
@@ -58,10 +61,10 @@ __global__ __launch_bounds__(P2_BLOCK) __attribute__((amdgpu_waves_per_eu(P2_WPE
     if ((P2_ABLATE & 4) && role >= lp.nbc + lp.nbt) return;
 #endif
 #ifdef P2_TIMELINE
-    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw, t_entry);
+    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS, NONZERO>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw, t_entry);
     else
 #endif
-    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
+    if (role < lp.nbc) collision_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX, ROUNDS, NONZERO>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
     else if (role < lp.nbc + lp.nbt) torque_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
     else limit_block<WANT_G, WANT_J, MULTI, DFC, LL, PPW, EX>(tb, lp, b, role, k0, k_first, g0, jac0, smem_raw);
 }
@@ -107,8 +110,18 @@ bool armour_p2_ex_layout_ok(unsigned long long skip) {
     return true;
 }
 
+// May an EX launch drop the scan's zero-normal test?  Only when no problem has a live plane that is zero in some row: zero[b] (plane_zero of the
+// build, p1_reach.hip; null: unknown, as all ones) has no bit outside skip[b] among the 36 planes.  Bits of skipped planes carry no meaning.
+bool armour_p2_nonzero_ok(bool exact, int B, const unsigned long long* h_skip, const unsigned long long* h_zero) {
+    if (!exact || !h_skip || !h_zero) return false;
+    for (int b = 0; b < B; b++)
+        if (h_zero[b] & ~h_skip[b] & ((1ull << ARMOUR_NPLANES) - 1ull)) return false;
+    return true;
+}
+
 int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, int steps, long long k_stride,
-                   long long g_stride, long long j_stride, P2Launch* lp_out, size_t* smem_out, bool* dfc_out, bool* six_out, bool* exact_out) {
+                   long long g_stride, long long j_stride, P2Launch* lp_out, size_t* smem_out, bool* dfc_out, bool* six_out, bool* exact_out,
+                   const unsigned long long* h_zero, bool* nonzero_out) {
     P2Launch lp;
     lp.role0 = 0;
     lp.nbc = (tb.Q + P2_ROWS - 1) / P2_ROWS;
@@ -177,16 +190,17 @@ int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsig
         }
     }
     *lp_out = lp; *smem_out = smem; *dfc_out = dfc; *six_out = six; *exact_out = exact;
+    if (nonzero_out) *nonzero_out = armour_p2_nonzero_ok(exact, tb.B, h_skip, h_zero);
     return ARMOUR_OK;
 }
 
-int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, const double* d_k, double* d_g, double* d_jac,
+int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const unsigned long long* h_zero, const double* h_bez, const double* d_k, double* d_g, double* d_jac,
                      hipStream_t stream, int steps, long long k_stride, long long g_stride, long long j_stride, bool skip_collision_blocks) {
     if (!d_g && !d_jac) return ARMOUR_OK;
     P2Launch lp;
     size_t smem = 0;
-    bool dfc, six, exact;
-    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, steps, k_stride, g_stride, j_stride, &lp, &smem, &dfc, &six, &exact);
+    bool dfc, six, exact, nonzero;
+    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, steps, k_stride, g_stride, j_stride, &lp, &smem, &dfc, &six, &exact, h_zero, &nonzero);
     if (rc != ARMOUR_OK) return rc;
     if (skip_collision_blocks) lp.role0 = lp.nbc;   // the torque blocks and the limit block only
     dim3 grid(lp.nbc + lp.nbt + 1 - lp.role0, tb.B), block(P2_BLOCK);
@@ -198,11 +212,16 @@ int armour_p2_launch(const P2Tables& tb, int max_link, int max_torque, const uns
 #endif
 #define P2_LAUNCH_M(G, J, M)                                                                                                                      \
     do {                                                                                                                                          \
-        if (dfc && exact && !(M) && one_round) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true, 1>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        if (dfc && exact && !(M) && one_round && nonzero) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true, 1, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        else if (dfc && exact && !(M) && one_round) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true, 1>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        else if (dfc && exact && !(M) && nonzero) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true, P2_TASK_ROUNDS, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (dfc && exact && !(M)) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, true, true, 6, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);      \
         else if (dfc && six) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, true, true, 6, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);                \
         else if (dfc) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, true, true, 9, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp);              \
+        else if (tb.ll_shared && exact && !(M) && one_round && nonzero && tb.B == 1) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true, 1, true, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        else if (tb.ll_shared && exact && !(M) && one_round && nonzero) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true, 1, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared && exact && !(M) && one_round) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true, 1>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
+        else if (tb.ll_shared && exact && !(M) && nonzero) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true, P2_TASK_ROUNDS, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared && exact && !(M)) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, false, false, true, 6, true>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared && six) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, false, true, 6, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
         else if (tb.ll_shared) hipLaunchKernelGGL((armour_p2_eval_kernel<G, J, M, false, true, 9, false>), grid, block, smem, stream, tb, d_k, d_g, d_jac, lp); \
@@ -227,7 +246,7 @@ static int p2_plan_report(const P2Tables& tb, int max_link, int max_torque, cons
     P2Launch lp;
     size_t smem = 0;
     bool dfc, six, exact;
-    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact);
+    const int rc = armour_p2_plan(tb, max_link, max_torque, h_skip, h_bez, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact, nullptr, nullptr);
     if (rc != ARMOUR_OK) return rc;
     const size_t at_lp = (sizeof(P2Tables) + 3 * sizeof(void*) + alignof(P2Launch) - 1) / alignof(P2Launch) * alignof(P2Launch);   // (tb, k, g, jac, lp)
     verdict[0] = dfc; verdict[1] = six; verdict[2] = exact; verdict[3] = (int32_t)(at_lp + sizeof(P2Launch)); verdict[4] = lp.ex_shared; verdict[5] = lp.skip_by_value;
@@ -243,6 +262,46 @@ static int p2_plan_report(const P2Tables& tb, int max_link, int max_torque, cons
 extern "C" int armour_debug_p2_plan(ArmourPlanner* h, int32_t* verdict, uint32_t* fields) {
     NEED_READY(h);
     return p2_plan_report(armour_make_tables(h), h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), verdict, fields);
+}
+
+// the zero-normal verdict of the same launch and the two masks it rests on (include/armour_hip.h)
+extern "C" int armour_debug_p2_zero_plan(ArmourPlanner* h, int32_t* nonzero, uint64_t* skip, uint64_t* zero) {
+    NEED_READY(h);
+    if (!nonzero || !skip || !zero) { armour_set_error("armour_debug_p2_zero_plan: null output"); return ARMOUR_EINVAL; }
+    P2Launch lp;
+    size_t smem = 0;
+    bool dfc, six, exact, nz;
+    const int rc = armour_p2_plan(armour_make_tables(h), h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact, h->p2_zero(), &nz);
+    if (rc != ARMOUR_OK) return rc;
+    *nonzero = nz ? 1 : 0;
+    for (int b = 0; b < h->B; b++) {
+        skip[b] = (uint64_t)h->h_plane_skip[b] & ((1ull << ARMOUR_NPLANES) - 1ull);
+        zero[b] = (uint64_t)(b < (int)h->h_plane_zero.size() ? h->h_plane_zero[b] : ~0ull) & ((1ull << ARMOUR_NPLANES) - 1ull);
+    }
+    return ARMOUR_OK;
+}
+
+// the plan of a table shape with given (skip, zero) masks: host only, no handle, no device -- {EX launch, zero-normal test dropped}
+extern "C" int armour_debug_p2_zero_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,
+                                               const uint64_t* skip, const uint64_t* zero, int32_t* verdict) {
+    if (B < 1 || T < 1 || J < 1 || n < 1 || n > ARMOUR_MAX_FACTORS || O < 1 || capL < 1 || max_link < 1 || !skip || !zero || !verdict || (long long)J * T * O >= (1ll << 31)) {
+        armour_set_error("armour_debug_p2_zero_plan_shape: bad shape or null argument");
+        return ARMOUR_EINVAL;
+    }
+    static const double none = 0.0;
+    std::vector<unsigned long long> h_skip(skip, skip + B), h_zero(zero, zero + B);
+    P2Tables tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.B = B; tb.T = T; tb.J = J; tb.n = n; tb.O = O; tb.Q = J * T * O; tb.row0 = n * T; tb.m = tb.row0 + tb.Q + 4 * n;
+    tb.capL = capL; tb.capT = 1; tb.ll_shared = 1; tb.ex_allowed = 1; tb.mode = ARMOUR_MODE_ARMOUR;
+    tb.obs_center = recompute_d ? &none : nullptr;
+    P2Launch lp;
+    size_t smem = 0;
+    bool dfc, six, exact, nz;
+    const int rc = armour_p2_plan(tb, max_link, 1, h_skip.data(), nullptr, 1, 0, 0, 0, &lp, &smem, &dfc, &six, &exact, h_zero.data(), &nz);
+    if (rc != ARMOUR_OK) return rc;
+    verdict[0] = exact ? 1 : 0; verdict[1] = nz ? 1 : 0;
+    return ARMOUR_OK;
 }
 
 extern "C" int armour_debug_p2_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,

@@ -281,7 +281,9 @@ __device__ inline void load_pass_uncond(const P2Tables& tb, const P2Launch& lp, 
 // the plane loads, a fixed number, after them, so the slicing (waiting for the tables with vmcnt(#plane loads)) runs while
 // the planes are still in flight; the barriers before the scan wait for LDS traffic only.
 // ROUNDS (EX only): slicing rounds a thread loads and evaluates, see load_pass_uncond; the other kernels keep P2_TASK_ROUNDS.
-template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS>
+// NONZERO (EX only): no live plane of any problem of the launch has the zero normal in any row (armour_p2_plan, from the build's plane_zero): the
+// scan's zero-normal test is the constant true.
+template <bool WANT_G, bool WANT_J, bool MULTI, bool DFC, bool LL, int PPW, bool EX, int ROUNDS = P2_TASK_ROUNDS, bool NONZERO = false>
 __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Launch& lp, const int b, const int role, const double* __restrict__ k0,
                                    const double k_first, double* __restrict__ g0_in, double* __restrict__ jac0_in, unsigned char* smem_raw
 #ifdef P2_TIMELINE
@@ -347,6 +349,7 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
     const bool single_pass = npairs <= lp.pair_chunk;
     PassRegs pr;
     static_assert(EX || ROUNDS == P2_TASK_ROUNDS, "only the EX kernels have a one-round form");
+    static_assert(EX || !NONZERO, "only the EX kernels have a form without the zero-normal test");
     if (EX) load_pass_uncond<ROUNDS>(tb, lp, b, lt_first, npairs, pr);
     // EX launches (armour_p2_plan: ex_layout_ok): waves 0 and 1 hold six planes with an obstacle generator each -- {Ax,Ay}, {Az,delta}:
     // twelve 16-B loads; waves 2 and 3 six CONSECUTIVE link x link planes each, starting at an even p - 21: their 18 normal components
@@ -523,7 +526,7 @@ __device__ __forceinline__ void collision_block(const P2Tables& tb, const P2Laun
         int best = (wv == 0 && plane0_live) ? 0 : -2;
 #pragma unroll
         for (int i = 0; i < PPW; i++) {
-            const bool nz = (a0[i] != 0.0) | (a1[i] != 0.0) | (a2[i] != 0.0);  // A_elt.norm() > 0 (RT/CollisionChecking.cu:252)
+            const bool nz = NONZERO || ((a0[i] != 0.0) | (a1[i] != 0.0) | (a2[i] != 0.0));  // A_elt.norm() > 0 (RT/CollisionChecking.cu:252)
             const double dot = a0[i] * x0 + a1[i] * x1 + a2[i] * x2;
             const double pos_res = nz ? dot - (dd[i] + dl[i]) : -100000000.0;
             const double neg_res = nz ? -dot - (-dd[i] + dl[i]) : -100000000.0;

@@ -461,7 +461,7 @@ int armour_eval_violations_culled(ArmourPlanner* h, const double* d_k, ArmourVio
     int rc = armour_relevance_build(h, false);
     if (rc != ARMOUR_OK) return rc;
     const P2Tables tb = armour_make_tables(h);
-    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->h_bez.data(), d_k, h->d_g, nullptr, st, 1, 0, 0, 0, /*skip_collision_blocks=*/true);
+    rc = armour_p2_launch(tb, h->max_link, h->max_torque, h->h_plane_skip.data(), h->p2_zero(), h->h_bez.data(), d_k, h->d_g, nullptr, st, 1, 0, 0, 0, /*skip_collision_blocks=*/true);
     if (rc != ARMOUR_OK) return rc;
     RelTables a;
     a.tb = tb;

@@ -65,7 +65,8 @@ struct SolvePlan {
 };
 
 int armour_p2_plan(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, const double* h_bez, int steps, long long k_stride,
-                   long long g_stride, long long j_stride, p2::P2Launch* lp_out, size_t* smem_out, bool* dfc_out, bool* six_out, bool* exact_out);
+                   long long g_stride, long long j_stride, p2::P2Launch* lp_out, size_t* smem_out, bool* dfc_out, bool* six_out, bool* exact_out,
+                   const unsigned long long* h_zero = nullptr, bool* nonzero_out = nullptr);
 // b_launch: problems per launch the occupancy choice is made for (the whole batch, or a sub-batch of it)
 // n_tiles_override > 0: the tiles a problem of the launch has at most (the culled form's count, from the row lists)
 int armour_solve_device_capacity(const P2Tables& tb, int max_link, int max_torque, const unsigned long long* h_skip, int device, int b_launch, int waves_per_simd, SolvePlan* plan,

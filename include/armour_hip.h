@@ -150,6 +150,7 @@ void armour_free_pinned(void* p);
 #define ARMOUR_OPT_P1_FULL_PLANES 120         /* 0 (default) the lean half-space table | 1 every plane and component resident (armour_get_hyperplanes builds it on demand otherwise) */
 /* fused evaluation (p2_eval.hip) and its host entries (api.hip) */
 #define ARMOUR_OPT_P2_EX 130                  /* 1 (default) | 0: the fixed-load-count kernels for problems with exactly 24 live planes */
+#define ARMOUR_OPT_P2_NO_ZERO_TEST 134         /* 1 (default) | 0: EX launches whose problems have no live plane with a zero normal in any row (plane_zero of the build) take the kernels without the scan's zero-normal test; same rows bit for bit */
 #define ARMOUR_OPT_STEPS_GRAPH_MIN 131        /* default 2: armour_eval_g_jac_device_steps submits >= this many steps as one graph; 0 never */
 #define ARMOUR_OPT_CULL_ROWS 133              /* 0 (default) | 1: armour_eval_violations* evaluate the rows that can be violated for some k only (armour_get_row_relevance): same L1 violation, counts and verdict bit for bit; `worst` is the full evaluation's whenever a row is violated.
                                                 * PRECONDITION: k inside [-1, 1]^n (the mask is a statement about the box).  armour_eval_violations (host k) takes every row when a component
@@ -653,6 +654,15 @@ int armour_debug_get_row_lists(ArmourPlanner* h, int32_t which, int32_t* rows, i
 int armour_debug_p2_plan(ArmourPlanner* h, int32_t* verdict, uint32_t* fields);
 int armour_debug_p2_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,
                                const uint64_t* skip, int32_t* verdict, uint32_t* fields);
+/* armour_debug_p2_zero_plan: does that launch take the EX kernel WITHOUT the scan's zero-normal test (*nonzero = 1), and the two masks [B] the
+ * verdict rests on: skip (armour_get_plane_skip) and zero -- bit p set: plane p has a normal with three components == 0.0 (so -0.0 counts) in at
+ * least one row of the problem; bits of skipped planes carry no meaning; all ones when the masks are not a build's (loaded tables).  The verdict
+ * is on only for an EX launch with zero[b] & ~skip[b] empty for every problem and ARMOUR_OPT_P2_NO_ZERO_TEST = 1.
+ * armour_debug_p2_zero_plan_shape (host only, no handle, no device): the plan of armour_debug_p2_plan_shape's table shape with the masks skip [B]
+ * and zero [B]; verdict [2] = {the exact-layout (EX) kernel, the one without the zero-normal test}. */
+int armour_debug_p2_zero_plan(ArmourPlanner* h, int32_t* nonzero, uint64_t* skip, uint64_t* zero);
+int armour_debug_p2_zero_plan_shape(int32_t B, int32_t T, int32_t J, int32_t n, int32_t O, int32_t capL, int32_t max_link, int32_t recompute_d,
+                                    const uint64_t* skip, const uint64_t* zero, int32_t* verdict);
 
 /* ---- test hooks: the block steps under the per-world planner kernels (armour_tree_plan, armour_path_shortcut, armour_ik, armour_ws_tree_plan) ---- */
 /* armour_debug_block_steps: ONE block of 256 lanes runs each cooperative step once on the caller's per-lane values (all [256]) and touches no

@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev only: static instruction counts between the P2_TIMELINE stamps of the headline instantiation of the one-point fused kernel
-# (armour_p2_eval_kernel<true, true, false, false, true, 6, true, 1>: g and jac, one point, d read, compact link x link normals, six slots, EX,
-# one slicing round).
+# (armour_p2_eval_kernel<true, true, false, false, true, 6, true, 1, true, true>: g and jac, one point, d read, compact link x link normals, six slots, EX,
+# one slicing round, no zero-normal test, one problem).
 #   bash tools/dev/isa_phases.sh [CSRC]      CSRC: another checkout's armour_amd/csrc (default: this checkout's)
 # Stretches are what lies between two stamps in the assembly, in file order (the collision path is laid out in program order); the first
 # stamp is the kernel's entry stamp, the second P2_STAMP(0).  Also printed: the kernel's registers, scratch and occupancy.
@@ -16,7 +16,7 @@ python3 - "$TMP/p2_tl.s" <<'PY'
 import re, sys
 from collections import Counter
 L = open(sys.argv[1]).read().split('\n')
-HEAD = 'armour_p2_eval_kernelILb1ELb1ELb0ELb0ELb1ELi6ELb1ELi1EE'
+HEAD = 'armour_p2_eval_kernelILb1ELb1ELb0ELb0ELb1ELi6ELb1ELi1ELb1ELb1EE'
 a = next(i for i, l in enumerate(L) if l.startswith('_ZN') and ':' in l and HEAD in l.split(':')[0])
 b = next(i for i in range(a, len(L)) if L[i].startswith('.Lfunc_end'))
 K = L[a:b]
