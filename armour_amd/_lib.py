@@ -188,6 +188,7 @@ EXPORTS = [
     "armour_roadmap_create", "armour_roadmap_destroy", "armour_roadmap_get_sizes", "armour_roadmap_check", "armour_roadmap_plan",
     "armour_track_options_default", "armour_track", "armour_track_auto_steps",
     "armour_path_audit", "armour_path_audit_host", "armour_path_audit_items",
+    "armour_set_problems_moving", "armour_path_audit_moving", "armour_path_audit_moving_host",
     "armour_solve_from", "armour_sweep", "armour_sweep_tile",
     "armour_self_pairs_default", "armour_self_check", "armour_self_check_host", "armour_self_edges_host", "armour_roadmap_check_self",
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
@@ -263,6 +264,8 @@ def load():
     L.armour_free_pinned.argtypes = [vp]
     L.armour_free_pinned.restype = None
     L.armour_set_problems.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp]
+    if hasattr(L, "armour_set_problems_moving"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        L.armour_set_problems_moving.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp]
     L.armour_set_problems_armtd.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
     L.armour_get_sizes.argtypes = [vp, ip, ip, ip]
     L.armour_get_bounds.argtypes = [vp, dp, dp, dp, dp]
@@ -382,6 +385,10 @@ def load():
     audit = [C.POINTER(ArmourRobot), C.c_int32, C.c_int32, dp, C.c_int32, ip, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp, C.c_double, ip, dp, dp]
     L.armour_path_audit.argtypes = audit + [dp]
     L.armour_path_audit_host.argtypes = audit
+    audit_moving = [C.POINTER(ArmourRobot), C.c_int32, C.c_int32, dp, dp, C.c_int32, ip, dp, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp, C.c_double, ip, dp, dp]
+    if hasattr(L, "armour_path_audit_moving"):
+        L.armour_path_audit_moving.argtypes = audit_moving + [dp]
+        L.armour_path_audit_moving_host.argtypes = audit_moving
     L.armour_path_audit_items.argtypes = [C.POINTER(ArmourRobot), C.c_int32, dp, dp, dp, dp, dp, C.c_double, dp, dp, C.c_double, C.POINTER(C.c_int64)]
     rp = C.POINTER(ArmourRobot)
     L.armour_self_pairs_default.argtypes = [rp, u8p]

@@ -336,6 +336,22 @@ extern "C" int armour_set_problems(ArmourPlanner* h, int32_t B, int32_t O, const
     return ARMOUR_OK;
 }
 
+// armour_set_problems with per-interval obstacle frames [B][T][O][12]: the same build, the half-space rows of interval t from frame t (p1_reach.hip, queue_planes)
+extern "C" int armour_set_problems_moving(ArmourPlanner* h, int32_t B, int32_t O, const double* q0, const double* qd0,
+                                          const double* qdd0, const double* q_des, const double* obstacle_frames) {
+    int rc = begin_problem_set(h, B, O, q0, qd0, qdd0, q_des);
+    if (rc != ARMOUR_OK) return rc;
+    if (O > 0 && !obstacle_frames) { armour_set_error("obstacle_frames is null but O=%d", O); return ARMOUR_EINVAL; }
+    const size_t cnt = (size_t)B * h->T * O * 12;
+    if (const size_t i = first_nonfinite(obstacle_frames, cnt); i < cnt) { armour_set_error("non-finite obstacle frame entry %zu", i); return ARMOUR_EINVAL; }
+    rc = armour_p1_build(h, obstacle_frames, h->T);
+    if (rc != ARMOUR_OK) return rc;
+    rc = armour_refresh_table_stats(h);
+    if (rc != ARMOUR_OK) return rc;
+    h->ready = true;
+    return ARMOUR_OK;
+}
+
 extern "C" int armour_set_problems_armtd(ArmourPlanner* h, int32_t B, int32_t O, const double* q0, const double* qd0, const double* q_des,
                                          const double* jrs, const double* k_range, const double* obstacles) {
     if (!jrs || !k_range) { armour_set_error("null argument"); return ARMOUR_EINVAL; }

@@ -264,7 +264,7 @@ void armour_build_stamp(const char* name);
 int armour_bounds_launch(ArmourPlanner* h, const double* d_torque_radius);   // the same kernel queued on the handle's stream (the reach-set build calls it)
 
 // p1_reach.hip
-int armour_p1_build(ArmourPlanner* h, const double* obstacles);  // h->mode selects the ARMOUR or the ARMTD chain
+int armour_p1_build(ArmourPlanner* h, const double* obstacles, int frames = 1);  // h->mode selects the ARMOUR or the ARMTD chain; frames: 1, obstacles [B][O][12], or T, [B][T][O][12] (armour_set_problems_moving)
 void armour_p1_free(ArmourPlanner* h);
 int armour_p1_full_planes(ArmourPlanner* h, double* d_full);
 

@@ -1481,7 +1481,10 @@ __device__ inline unsigned planes_redundant(const unsigned long long (&Sg)[ARMOU
 // == 0.0, the scan's own comparison) -- what armour_p2_plan needs to know to drop that test from the scan; bits of skipped planes carry no meaning.
 // Four threads per row (wave w of the 256-thread block builds planes 9w .. 9w+8 of the block's 64 rows); the signatures of the
 // normals go through LDS so that each thread can test its planes against all earlier planes of its row.
-template <bool LEAN>
+// MOVING: the obstacles are per-interval frames [B][T][O][12] (armour_set_problems_moving) and row (l, t, o) is built from frame t; otherwise
+// [B][O][12] and the address below is the static one, token for token (a template parameter, not a stride argument: the static kernels keep
+// their instruction streams and register counts).
+template <bool LEAN, bool MOVING>
 __global__ __launch_bounds__(256) void armour_p1_planes_kernel(int B, int T, int J, int O, const double* __restrict__ link_gens,
                                                                const double* __restrict__ obstacles, double* __restrict__ planes,
                                                                double* __restrict__ planes_ll, double* __restrict__ obs_center,
@@ -1494,7 +1497,7 @@ __global__ __launch_bounds__(256) void armour_p1_planes_kernel(int B, int T, int
     const bool in = q < Q;
     const int qc = in ? q : Q - 1;
     const int o = qc % O, lt = qc / O, l = lt / T, t = lt - l * T;
-    const double* ob = obstacles + ((size_t)b * O + o) * 12;
+    const double* ob = MOVING ? obstacles + ((((size_t)b * T + t) * O) + o) * 12 : obstacles + ((size_t)b * O + o) * 12;
     const double* lg = link_gens + (((size_t)b * T + t) * J + l) * 18;
     // planes that are redundant in every row of this problem by the class of their generators (wave-uniform)
     const unsigned long long pre = LEAN ? uniform_u64(pre_mask[b]) : 0ull;
@@ -1567,6 +1570,7 @@ __global__ __launch_bounds__(256) void armour_p1_planes_kernel(int B, int T, int
 // for bit as the planes kernel computes (pair_normal), compared as canonical triples, no hashing.  The same block ANDs the class
 // pre-pass's per-block words of the problem into pre_mask[b] (one launch less in front of the planes kernel).
 constexpr int kPlaneSamples = 16;
+template <bool MOVING>
 __global__ __launch_bounds__(64 * kPlaneSamples) void armour_p1_plane_sample_kernel(int T, int J, int O, const double* __restrict__ link_gens,
                                                                                     const double* __restrict__ obstacles, const unsigned long long* __restrict__ pre_part, int n_part,
                                                                                     unsigned long long* __restrict__ pre_mask, unsigned long long* __restrict__ live_mask) {
@@ -1576,7 +1580,7 @@ __global__ __launch_bounds__(64 * kPlaneSamples) void armour_p1_plane_sample_ker
     {
         const int q = (int)(((long long)sidx * Q) / kPlaneSamples + (sidx * 7) % O) % Q;
         const int o = q % O, lt = q / O, l = lt / T, t = lt - l * T;
-        const double* ob = obstacles + ((size_t)b * O + o) * 12;
+        const double* ob = MOVING ? obstacles + ((((size_t)b * T + t) * O) + o) * 12 : obstacles + ((size_t)b * O + o) * 12;
         const double* lg = link_gens + (((size_t)b * T + t) * J + l) * 18;
         unsigned long long cb[3] = {0ull, 0ull, 0ull};
         if (p < ARMOUR_NPLANES) {
@@ -1614,6 +1618,7 @@ __global__ __launch_bounds__(64 * kPlaneSamples) void armour_p1_plane_sample_ker
 // earlier pair of the same class repeats bit for bit.  One thread per row, integer logic on nine class codes; the result is a
 // subset of what the signature test of armour_p1_planes_kernel finds (that test still produces plane_skip), known BEFORE the planes are
 // computed, so that the lean kernel neither computes nor stores those planes.
+template <bool MOVING>
 __global__ __launch_bounds__(256) void armour_p1_plane_class_kernel(int T, int J, int O, const double* __restrict__ link_gens,
                                                                     const double* __restrict__ obstacles, unsigned long long* __restrict__ part) {
     __shared__ unsigned long long s[4];
@@ -1622,7 +1627,7 @@ __global__ __launch_bounds__(256) void armour_p1_plane_class_kernel(int T, int J
     unsigned long long m = ~0ull;
     if (q < Q) {
         const int o = q % O, lt = q / O, l = lt / T, t = lt - l * T;
-        const double* ob = obstacles + ((size_t)b * O + o) * 12;
+        const double* ob = MOVING ? obstacles + ((((size_t)b * T + t) * O) + o) * 12 : obstacles + ((size_t)b * O + o) * 12;
         const double* lg = link_gens + (((size_t)b * T + t) * J + l) * 18;
         int cls[9];     // 0: zero vector; 1..3: only component x / y / z is non-zero; 4: anything else
         double mag[9];  // |the one non-zero component|
@@ -1823,7 +1828,8 @@ TvArenaPool g_tv_pool[kMaxPoolDevices];
 struct P1Work {
     DevBuf<unsigned char> arena;
     DevBuf<unsigned> d_status;
-    DevBuf<double> d_link_gens, d_torque_radius, d_obstacles;
+    DevBuf<double> d_link_gens, d_torque_radius, d_obstacles;   // d_obstacles: [B][obs_frames][O][12]
+    int obs_frames = 1;   // 1: one zonotope per obstacle (static build); T: one per plan interval (moving build), row (l, t, o) reads frame t
     DevBuf<int> d_retry;  // [1 + B*T]: count, then item indices
     DevBuf<unsigned long long> d_skip_part;  // [B][blocks per problem][4 waves]: the planes kernel's masks before the AND
     DevBuf<unsigned long long> d_margin;   // [B]: the prune margin word of every problem (P1Cfg::margin)
@@ -2198,20 +2204,30 @@ static int queue_planes(ArmourPlanner* h, P1Work* wk) {
     const bool lean = !full_env;
     // (round 4, one box, interleaved: configs[4] -- one problem, 90 000 rows, a 60 MB table -- 13.1 us with d recomputed against 15.8 stored;
     //  configs[1] -- 14 000 rows, L2-resident -- 5.05 against 5.02: the launch that streams its table from beyond L2 wants the fewer bytes)
-    const int store_d = (B >= 8 || (long long)B * Q >= ARMOUR_RECOMPUTE_D_ROWS) ? 0 : 1;
-    if (lean) {
-        hipLaunchKernelGGL(armour_p1_plane_class_kernel, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
-        hipLaunchKernelGGL(armour_p1_plane_sample_kernel, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
-        hipLaunchKernelGGL(armour_p1_planes_kernel<true>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+    // A moving build (per-interval frames) has no one centre per obstacle to recompute d from: d is stored at every batch size, obs_center is not written.
+    const bool moving = wk->obs_frames > 1;
+    const int store_d = (moving || !(B >= 8 || (long long)B * Q >= ARMOUR_RECOMPUTE_D_ROWS)) ? 1 : 0;
+    if (moving && lean) {
+        hipLaunchKernelGGL(armour_p1_plane_class_kernel<true>, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
+        hipLaunchKernelGGL(armour_p1_plane_sample_kernel<true>, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
+        hipLaunchKernelGGL((armour_p1_planes_kernel<true, true>), dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, nullptr, wk->d_skip_part, d_zero_part, d_pre, d_live, store_d);
+    } else if (moving) {
+        hipLaunchKernelGGL((armour_p1_planes_kernel<false, true>), dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+                           wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, nullptr, wk->d_skip_part, d_zero_part, nullptr, nullptr, 1);
+    } else if (lean) {
+        hipLaunchKernelGGL(armour_p1_plane_class_kernel<false>, dim3(nbc, B), dim3(256), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part);
+        hipLaunchKernelGGL(armour_p1_plane_sample_kernel<false>, dim3(B), dim3(64 * kPlaneSamples), 0, h->stream, T, J, O, wk->d_link_gens, wk->d_obstacles, d_pre_part, nbc, d_pre, d_live);
+        hipLaunchKernelGGL((armour_p1_planes_kernel<true, false>), dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
                            wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_zero_part, d_pre, d_live, store_d);
     } else {
-        hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
+        hipLaunchKernelGGL((armour_p1_planes_kernel<false, false>), dim3(nbx, B), dim3(256), 0, h->stream, B, T, J, O,
                            wk->d_link_gens, wk->d_obstacles, h->d_planes, h->d_planes_ll, h->d_obs_center, wk->d_skip_part, d_zero_part, nullptr, nullptr, 1);
     }
     // (plane_zero lies behind plane_skip in one allocation: the build's read-back fetches both with the copy it made for one)
     hipLaunchKernelGGL(armour_p1_skip_reduce_kernel, dim3(B), dim3(256), 0, h->stream, wk->d_skip_part, d_zero_part, nbx * 4, h->d_plane_skip, h->d_plane_skip + B);
     h->plane_zero_built = true;
-    h->ll_shared = 1; h->d_from_center = 1;
+    h->ll_shared = 1; h->d_from_center = moving ? 0 : 1;
     h->planes_lean = lean ? 1 : 0; h->planes_have_d = (!lean || store_d) ? 1 : 0;
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(wk->ev_planes.record_stop(h->stream));
@@ -2356,7 +2372,7 @@ static int build_time_vectorised(ArmourPlanner* h, P1Work* wk, int cus, float* t
     return ARMOUR_OK;   // (pool_release: every launch above has been waited for)
 }
 
-int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
+int armour_p1_build(ArmourPlanner* h, const double* obstacles, int frames) {
     if (!h->p1) {
         h->p1 = new P1Work();
         { TvArenaPool& pool = g_tv_pool[h->device % kMaxPoolDevices]; std::lock_guard<std::mutex> lk(pool.mu); pool.users++; }
@@ -2368,8 +2384,9 @@ int armour_p1_build(ArmourPlanner* h, const double* obstacles) {
     ARMOUR_TRY(wk->d_link_gens.reserve((size_t)B * T * J * 18));
     ARMOUR_TRY(wk->d_torque_radius.reserve((size_t)B * n * T));
     ARMOUR_TRY(wk->d_margin.reserve((size_t)B));
-    ARMOUR_TRY(wk->d_obstacles.reserve((size_t)B * O * 12));
-    if (O > 0) HIPCHK(hipMemcpyAsync(wk->d_obstacles, obstacles, (size_t)B * O * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    wk->obs_frames = frames;
+    ARMOUR_TRY(wk->d_obstacles.reserve((size_t)B * frames * O * 12));
+    if (O > 0) HIPCHK(hipMemcpyAsync(wk->d_obstacles, obstacles, (size_t)B * frames * O * 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     armour_build_stamp("buffers+obstacles");
 
     hipDeviceProp_t prop;
@@ -2494,8 +2511,12 @@ int armour_p1_full_planes(ArmourPlanner* h, double* d_full) {
     P1Work* wk = h->p1;
     if (!wk || !wk->d_link_gens || !wk->d_obstacles || h->O <= 0) { armour_set_error("no reach sets on the device to rebuild the half-space table from"); return ARMOUR_ESTATE; }
     const int Q = h->J * h->T * h->O, nbx = (Q + 63) / 64;
-    hipLaunchKernelGGL(armour_p1_planes_kernel<false>, dim3(nbx, h->B), dim3(256), 0, h->stream, h->B, h->T, h->J, h->O,
-                       wk->d_link_gens, wk->d_obstacles, d_full, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
+    if (wk->obs_frames > 1)   // a moving build: the frames are in d_obstacles
+        hipLaunchKernelGGL((armour_p1_planes_kernel<false, true>), dim3(nbx, h->B), dim3(256), 0, h->stream, h->B, h->T, h->J, h->O,
+                           wk->d_link_gens, wk->d_obstacles, d_full, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
+    else
+        hipLaunchKernelGGL((armour_p1_planes_kernel<false, false>), dim3(nbx, h->B), dim3(256), 0, h->stream, h->B, h->T, h->J, h->O,
+                           wk->d_link_gens, wk->d_obstacles, d_full, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return ARMOUR_OK;

@@ -190,6 +190,76 @@ __host__ __device__ inline bool config_free(const RmRobot& rb, double (&q)[ARMOU
     return free_;
 }
 
+// ---- obstacles in linear motion (include/armour_hip.h, armour_path_audit_moving).  New names beside the static rule: pair_separated,
+// config_free and stage_obstacles* above are what the static audit and the roadmap compile, untouched.
+constexpr int RM_MOV_STRIDE = RM_OBS_STRIDE + 4;   // doubles per staged moving obstacle: the static 27 (pose at world time 0), then v[3], |v|_2
+
+__host__ __device__ inline double velocity_norm(const double* v) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
+
+// stage_obstacles for moving obstacles on the host: staged[o][RM_MOV_STRIDE] from obstacles [count][12] and velocity [count][3]
+inline void stage_obstacles_moving(const double* obstacles, const double* velocity, size_t count, double* staged) {
+    for (size_t o = 0; o < count; o++) {
+        double* st = staged + o * RM_MOV_STRIDE;
+        std::memcpy(st, obstacles + o * ARMOUR_OBS_DOUBLES, ARMOUR_OBS_DOUBLES * sizeof(double));
+        obstacle_normals(obstacles + o * ARMOUR_OBS_DOUBLES, st + ARMOUR_OBS_DOUBLES);
+        for (int i = 0; i < 3; i++) st[RM_OBS_STRIDE + i] = velocity[3 * o + i];
+        st[RM_OBS_STRIDE + 3] = velocity_norm(velocity + 3 * o);
+    }
+}
+
+// the same on the device: a block of BLOCK lanes stages its world's O obstacles Zw and velocities Vw into LDS, s_obs [O][RM_MOV_STRIDE], and meets at the barrier
+template <int BLOCK>
+__device__ inline void stage_obstacles_moving_lds(const double* __restrict__ Zw, const double* __restrict__ Vw, int O, double* s_obs) {
+    for (int i = threadIdx.x; i < O * ARMOUR_OBS_DOUBLES; i += BLOCK)
+        s_obs[(i / ARMOUR_OBS_DOUBLES) * RM_MOV_STRIDE + i % ARMOUR_OBS_DOUBLES] = Zw[i];
+    for (int o = threadIdx.x; o < O; o += BLOCK) {
+        double* st = s_obs + (size_t)o * RM_MOV_STRIDE;
+        obstacle_normals(Zw + (size_t)o * ARMOUR_OBS_DOUBLES, st + 12);
+        const double* v = Vw + (size_t)o * 3;
+        st[RM_OBS_STRIDE] = v[0]; st[RM_OBS_STRIDE + 1] = v[1]; st[RM_OBS_STRIDE + 2] = v[2];
+        st[RM_OBS_STRIDE + 3] = velocity_norm(v);
+    }
+    __syncthreads();
+}
+
+// config_free against obstacles staged with stride RM_MOV_STRIDE, each at its pose of world time tau: the pair test of link box l and
+// obstacle o with the box centre x - v_o tau (A meets B + d exactly when A - d meets B) and every half-size h_l + (r_l + |v_o| half).
+// half = 0 with r = 0 is the sample test; the tube test passes the sub-interval's half width, over which the obstacle leaves its
+// midpoint pose by at most |v_o| half.  q and r are consumed as config_free consumes them.
+__host__ __device__ inline bool config_free_moving(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], const double* obs, int O,
+                                                   double tau, double half, bool full, double* clearance) {
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+    double cl = INFINITY;
+    bool free_ = true;
+    for (int l = 0; l < rb.J; l++) {
+        link_frame(rb, l, q[0], R, p);
+        double x[3], u[3][3];
+        const double rl = r[0];
+#pragma unroll
+        for (int j = 0; j + 1 < ARMOUR_MAX_FACTORS; j++) q[j] = q[j + 1];
+#pragma unroll
+        for (int j = 0; j + 1 < ARMOUR_MAX_JOINTS; j++) r[j] = r[j + 1];
+        link_box(rb, l, R, p, x, u);
+        for (int o = 0; o < O; o++) {
+            const double* ob = obs + (size_t)o * RM_MOV_STRIDE;
+            const double* v = ob + RM_OBS_STRIDE;
+            const double grow = rl + v[3] * half;
+            double xs[3], s[3], val;
+            for (int i = 0; i < 3; i++) xs[i] = x[i] - v[i] * tau;
+            for (int k = 0; k < 3; k++) s[k] = rb.h[l][k] + grow;
+            const bool sep = pair_separated(xs, u, s, ob, full, &val);
+            if (!full) {
+                if (!sep) return false;
+            } else {
+                cl = fmin(cl, val);
+                free_ = free_ && sep;
+            }
+        }
+    }
+    if (full) *clearance = cl;
+    return free_;
+}
+
 inline void fill_rm_robot(const ArmourRobot* robot, const uint8_t* continuous, RmRobot* rb) {
     std::memset(rb, 0, sizeof(*rb));
     rb->J = robot->num_joints;

@@ -5,6 +5,8 @@
     res.t_hit          # [P]: the first colliding sample time of a verdict-1 piece, NaN otherwise
     res.clearance      # [P]: the minimum sample clearance (with clearance=True)
 
+audit_moving(robot, obstacles, velocity, world_of_piece, t_world, ...) is the same audit against obstacles in linear motion.
+
 `host=True` runs the library's host restatement of the same rule (no GPU needed; for tests).  The rule, its bound and the proof sketch are
 stated in include/armour_hip.h and DESIGN.md.
 """
@@ -67,6 +69,21 @@ def audit(robot, obstacles, world_of_piece, q0, qd0, qdd0, k, k_range, duration,
         wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
         return [W, O, _dp(obs) if obs.size else None, P, wp.ctypes.data_as(C.POINTER(C.c_int32))]
     return _audit(("armour_path_audit", "armour_path_audit_host"), lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, clearance, host)
+
+
+def audit_moving(robot, obstacles, velocity, world_of_piece, t_world, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, clearance=False,
+                 host=False):
+    """audit against obstacles in linear motion (armour_path_audit_moving): obstacles [W,O,12] (or [O,12]) are the poses at world time 0, velocity
+    [W,O,3] (or [O,3]) the constant velocities, t_world [P] (or a scalar) the world time of every piece's plan time 0.  t_hit is a plan time."""
+    obs, W, O = _lib.as_worlds(obstacles)
+    vel = np.ascontiguousarray(np.asarray(velocity, dtype=np.float64).reshape(W, O, 3))
+
+    def lead(P):
+        wp = np.ascontiguousarray(np.broadcast_to(np.asarray(world_of_piece, dtype=np.int32), (P,)))
+        tw = np.ascontiguousarray(np.broadcast_to(np.asarray(t_world, dtype=np.float64), (P,)))
+        return [W, O, _dp(obs) if obs.size else None, _dp(vel) if vel.size else None, P, wp.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tw)]
+    return _audit(("armour_path_audit_moving", "armour_path_audit_moving_host"), lead, robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube, step, clearance,
+                  host)
 
 
 def audit_self(robot, q0, qd0, qdd0, k, k_range, duration, ta, tb, tube=None, step=0.02, pairs=None, shrink=None, clearance=False, host=False):

@@ -351,6 +351,26 @@ class ArmourNLP:
         self._after_set(B, O)
         return self
 
+    def set_parameters_moving(self, q0, qd0, qdd0, q_des, obstacle_frames):
+        """set_parameters against moving obstacles (armour_set_problems_moving): obstacle_frames [T,O,12] for one problem or [B,T,O,12], frame t =
+        one zonotope per obstacle that covers all it can occupy during plan interval t (armour_amd.worlds.moving_frames builds them for boxes in
+        linear motion; covering is the caller's duty).  The half-space rows of interval t are built from frame t; everything else as set_parameters."""
+        q0, qd0, qdd0, q_des = [np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (q0, qd0, qdd0, q_des)]
+        fr = np.asarray(obstacle_frames, dtype=np.float64)
+        B = q0.shape[0]
+        if fr.ndim not in (3, 4) or fr.shape[-1] != 12 or fr.shape[-3] != self.T or (fr.ndim == 4 and fr.shape[0] != B) or (fr.ndim == 3 and B != 1):
+            raise ValueError(f"expected obstacle_frames of shape ({self.T},O,12) or ({B},{self.T},O,12), got {fr.shape}")
+        fr = np.ascontiguousarray(fr.reshape(B, self.T, -1, 12))
+        O = fr.shape[2]
+        for a in (q0, qd0, qdd0, q_des):
+            if a.shape != (B, self.n):
+                raise ValueError(f"expected shape ({B},{self.n}), got {a.shape}")
+        self._obs = fr
+        check(self.L.armour_set_problems_moving(self.h, B, O, _dp(q0), _dp(qd0), _dp(qdd0), _dp(q_des), _dp(fr) if O else None))
+        self.problem = dict(q0=q0.copy(), qd0=qd0.copy(), qdd0=qdd0.copy(), q_des=q_des.copy())
+        self._after_set(B, O)
+        return self
+
     def set_parameters_armtd(self, q0, qd0, q_des, jrs, k_range, obstacles):
         """ARMTD comparison mode (CMP/armtd_main.cu:36-216, the reference's second planner): constant-acceleration
         trajectory, cos/sin JRS from offline tables, no torque rows (m = J*T*O + 4n).  jrs: [n,6,T] (or [B,n,6,T]) --

@@ -78,6 +78,31 @@ def random_k(seed, count, n=7):
     return np.random.default_rng(10_000 + seed).uniform(-1.0, 1.0, (count, n))
 
 
+def moving_frames(obstacles, velocity, T, duration=1.0, t_world=0.0):
+    """Per-interval obstacle frames [T,O,12] for ArmourNLP.set_parameters_moving from axis-aligned boxes in linear motion: obstacles [O,12]
+    (centre, then a diagonal generator block: the poses at world time 0), velocity [O,3]; t_world = the world time of plan time 0.  Plan interval
+    t is [t D, (t + 1) D], D = duration / T.  Frame t has the centre c + v (t_world + (t + 1/2) D) and the half-sizes h_i + |v_i| D / 2: the
+    axis-aligned cover of box (+) the segment swept during the interval -- sound, and still three generators.  A box that is not axis-aligned
+    raises ValueError (a three-generator cover of a rotated swept box is not provided)."""
+    obs = np.asarray(obstacles, dtype=np.float64).reshape(-1, 12)
+    vel = np.asarray(velocity, dtype=np.float64).reshape(-1, 3)
+    if vel.shape[0] != obs.shape[0]:
+        raise ValueError(f"expected velocity of shape ({obs.shape[0]},3), got {vel.shape}")
+    G = obs[:, 3:].reshape(-1, 3, 3)            # G[o, g] = generator g
+    off = G[:, ~np.eye(3, dtype=bool)]
+    if np.any(off != 0.0):
+        raise ValueError("moving_frames takes axis-aligned boxes: generator g of every obstacle must lie on axis g (a diagonal generator block)")
+    T = int(T)
+    D = float(duration) / T
+    frames = np.repeat(obs[None], T, axis=0)
+    tm = float(t_world) + (np.arange(T) + 0.5) * D
+    frames[:, :, 0:3] = obs[:, 0:3] + tm[:, None, None] * vel      # (zero velocity: c + 0 = c, h + 0 = h, the static obstacle bit for bit)
+    for i in range(3):
+        h = obs[:, 3 + 4 * i]
+        frames[:, :, 3 + 4 * i] = np.copysign(np.abs(h) + np.abs(vel[:, i]) * D / 2, h)
+    return frames
+
+
 def load_scene_csv(path):
     """Saved random scene of the reference (kinova_src/saved_worlds/random/*.csv, load_saved_world.m:4-13):
     row 1 start, row 2 goal, row 3 NaN, rows 4.. = [cx cy cz sx sy sz NaN] boxes."""

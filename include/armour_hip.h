@@ -190,6 +190,23 @@ int armour_get_option(ArmourPlanner* h, int32_t option, double* value);
 int armour_set_problems(ArmourPlanner* h, int32_t B, int32_t O, const double* q0, const double* qd0,
                         const double* qdd0, const double* q_des, const double* obstacles);
 
+/* armour_set_problems against MOVING obstacles: obstacle_frames is host [B][T][O][12] (T = num_time_steps), one zonotope per obstacle and plan
+ * interval in the layout of armour_set_problems (centre, then 3 generators).  The half-space rows (l, t, .) -- the rows that say "link l's
+ * occupancy over plan interval t does not meet the obstacle" -- are built from frame t instead of from one zonotope for every t; nothing else
+ * of the build changes (reach sets, torque rows and limit rows do not read obstacles).
+ * THE FRAME CONTRACT.  Plan interval t is the plan times [t D, (t + 1) D] with D = duration / T.  Frame t of problem b must cover everything
+ * obstacle o can occupy at any time of that interval.  COVERING IS THE CALLER'S DUTY: the library takes a frame as given, exactly as it takes a
+ * static obstacle as given, and its guarantee is the reference's per interval -- the link's occupancy over interval t does not meet frame t.
+ * (armour_amd.worlds.moving_frames builds sound frames for axis-aligned boxes in linear motion.)
+ * Arguments as armour_set_problems: a null obstacle_frames with O > 0 and non-finite entries are refused (ARMOUR_EINVAL), ArmourLimits.max_obstacles
+ * means what it means there, and the handle stays usable after a refusal.  A table built from frames has no one centre per obstacle, so its d
+ * column is stored at every batch size and the evaluations read it (a static batch of >= 8 problems recomputes d from the centres); the next
+ * armour_set_problems on the handle restores the static forms, and the other way round.  Every consumer of the tables (evaluation, masks,
+ * armour_solve*, armour_sweep, armour_eval_violations, armour_get_hyperplanes) works as after armour_set_problems.  Not available: the ARMTD
+ * mode, armour_batch_* and the file protocol, whose obstacles stay static. */
+int armour_set_problems_moving(ArmourPlanner* h, int32_t B, int32_t O, const double* q0, const double* qd0,
+                               const double* qdd0, const double* q_des, const double* obstacle_frames);
+
 /* ARMTD comparison mode: the same handle and the same callback surface for the reference's second
  * planner, kinova_planner_realtime_armtd_comparison ("CMP").  Replaces CMP/armtd_main.cu:36-216: constant-acceleration
  * trajectory q(t) = q0 + qd0 t + k t^2/2 (CMP/Trajectory.h:6-15), cos/sin JRS taken from the caller's offline tables and
@@ -1195,6 +1212,32 @@ int armour_path_audit_host(const ArmourRobot* robot, int32_t W, int32_t O, const
                            const double* q0, const double* qd0, const double* qdd0, const double* k, const double* k_range, double duration,
                            const double* ta, const double* tb, const double* tube, double step, int32_t* verdict, double* t_hit,
                            double* clearance);
+/* armour_path_audit against obstacles in LINEAR MOTION.  obstacles [W][O][12] is every obstacle's pose at world time 0, velocity [W][O][3]
+ * its constant velocity (finite), t_world [P] the world time of piece p's plan time 0 (finite): at world time w obstacle o is its zonotope
+ * translated by v_o w.  Pieces, v_j, S, the midpoints t_s and the sub-interval half width half = (tb - ta) / (2S) are the static audit's
+ * (armour_path_audit_items stays valid); verdicts, t_hit (a PLAN time), clearance and ms as there.
+ * For item (p, s) and obstacle o, with tau = t_world[p] + t_s:
+ * Sample test (exact).  The node rule's pair test of link box l against the staged obstacle o with the box centre x replaced by x - v_o tau
+ *   (component-wise x[i] - v[i] * tau): the obstacle at its pose of world time tau.
+ * Tube test (conservative).  The same shifted centre, and every half-size of link l enlarged by r_l + |v_o|_2 half, with
+ *   |v_o|_2 = sqrt((v0^2 + v1^2) + v2^2) computed once per obstacle when it is staged.
+ * Soundness.  Inside the sub-interval the obstacle is displaced from its midpoint pose by at most |v_o| half.  A meets B + d exactly when
+ * A - d meets B, so testing the link box shifted by -v_o tau against the obstacle at its pose of time 0 is testing the box against the
+ * obstacle at tau, and a displacement d of the obstacle with |d| <= rho is a displacement -d of the box; a box whose half-sizes grow by rho
+ * contains the box (+) a ball of radius rho.  So if the box with half-sizes h_l + r_l + |v_o| half about the shifted midpoint centre is
+ * separated from obstacle o, no configuration within e of the plan touches the obstacle at any time of the sub-interval (the static argument
+ * supplies r_l).  Monotonicity carries over: the shift is the same in both tests and only the half-sizes grow, so a separated tube test still
+ * implies a separated sample test bit for bit.  With zero velocities the results are armour_path_audit's bit for bit, for any t_world.
+ * The device stages RM_OBS_STRIDE + 4 doubles per obstacle (the static 27, then v and |v|): 248 B of LDS each. */
+int armour_path_audit_moving(const ArmourRobot* robot, int32_t W, int32_t O, const double* obstacles, const double* velocity, int32_t P,
+                             const int32_t* world_of_piece, const double* t_world, const double* q0, const double* qd0, const double* qdd0,
+                             const double* k, const double* k_range, double duration, const double* ta, const double* tb, const double* tube,
+                             double step, int32_t* verdict, double* t_hit, double* clearance, double* ms);
+/* the same rule by the same functions in a host loop (for tests; runs without a GPU) */
+int armour_path_audit_moving_host(const ArmourRobot* robot, int32_t W, int32_t O, const double* obstacles, const double* velocity, int32_t P,
+                                  const int32_t* world_of_piece, const double* t_world, const double* q0, const double* qd0, const double* qdd0,
+                                  const double* k, const double* k_range, double duration, const double* ta, const double* tb, const double* tube,
+                                  double step, int32_t* verdict, double* t_hit, double* clearance);
 /* items [P] = S of every piece: the work items an audit at `step` takes (host arithmetic) */
 int armour_path_audit_items(const ArmourRobot* robot, int32_t P, const double* q0, const double* qd0, const double* qdd0, const double* k,
                             const double* k_range, double duration, const double* ta, const double* tb, double step, int64_t* items);
