@@ -193,6 +193,7 @@ EXPORTS = [
     "armour_self_pairs_default", "armour_self_check", "armour_self_check_host", "armour_self_edges_host", "armour_roadmap_check_self",
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
     "armour_roadmap_field", "armour_roadmap_descend",
+    "armour_roadmap_check_moving", "armour_roadmap_check_moving_host",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
@@ -334,6 +335,9 @@ def load():
     L.armour_roadmap_destroy.restype = None
     L.armour_roadmap_get_sizes.argtypes = [vp, ip, ip, C.POINTER(C.c_int64)]
     L.armour_roadmap_check.argtypes = [vp, C.c_int32, C.c_int32, dp, u8p, u8p, dp, dp]
+    if hasattr(L, "armour_roadmap_check_moving"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        L.armour_roadmap_check_moving.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, u8p, u8p, dp, dp]
+        L.armour_roadmap_check_moving_host.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, u8p, u8p, dp]
     L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
     L.armour_roadmap_field.argtypes = [vp, dp, C.c_int32, dp, ip, ip, ip, dp]
     L.armour_roadmap_descend.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, dp, ip, dp]

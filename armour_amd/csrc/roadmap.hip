@@ -22,14 +22,20 @@ constexpr int RM_BLOCK = 256;                 // four waves; a block serves one 
 
 // One launch: grid (ceil((N + M) / RM_BLOCK), W); item i < N is node i, item N + k is edge sub-segment k (edge sample_edge[k],
 // sub-segment k - edge_off[e]).  edge_free must hold 1 on entry; a colliding sub-segment stores 0 (no atomics: every writer writes 0).
+// MOVING (armour_roadmap_check_moving): the window rule -- velocity [W][O][3], mid / half [W] as the host computed them, the obstacles staged
+// with RM_MOV_STRIDE.  The static instantiation reads none of the three and keeps the static rule's calls as they were.
+template <bool MOVING>
 __global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int32_t N, int64_t M, const double* __restrict__ nodes,
                                                                   const int32_t* __restrict__ edges, const int64_t* __restrict__ edge_off,
                                                                   const int32_t* __restrict__ sample_edge, const double* __restrict__ obstacles,
-                                                                  int32_t O, int32_t E, uint8_t* __restrict__ node_free,
-                                                                  uint8_t* __restrict__ edge_free, double* __restrict__ clearance) {
-    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+                                                                  const double* __restrict__ velocity, const double* __restrict__ mid,
+                                                                  const double* __restrict__ half, int32_t O, int32_t E,
+                                                                  uint8_t* __restrict__ node_free, uint8_t* __restrict__ edge_free,
+                                                                  double* __restrict__ clearance) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE], MOVING: [O][RM_MOV_STRIDE]
     const int w = blockIdx.y;
-    stage_obstacles_lds<RM_BLOCK>(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    if constexpr (MOVING) stage_obstacles_moving_lds<RM_BLOCK>(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, velocity + (size_t)w * O * 3, O, s_obs);
+    else stage_obstacles_lds<RM_BLOCK>(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
     const int64_t item = (int64_t)blockIdx.x * RM_BLOCK + threadIdx.x;
     if (item >= (int64_t)N + M) return;
     double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
@@ -49,7 +55,9 @@ __global__ __launch_bounds__(RM_BLOCK) void roadmap_check_kernel(RmRobot rb, int
     }
     const bool full = is_node && clearance != nullptr;   // node clearance: no early exit
     double cl;
-    const bool ok = config_free(rb, q, r, s_obs, O, full, &cl);
+    bool ok;
+    if constexpr (MOVING) ok = config_free_moving(rb, q, r, s_obs, O, mid[w], half[w], full, &cl);
+    else ok = config_free(rb, q, r, s_obs, O, full, &cl);
     if (is_node) {
         node_free[(size_t)w * N + item] = ok ? 1 : 0;
         if (full) clearance[(size_t)w * N + item] = cl;
@@ -64,12 +72,14 @@ namespace rmhost {
 
 double wrapped_distance(const RmRobot& rb, const double* a, const double* b) { return wrapped_norm(rb, a, b); }
 
-bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b) {
+bool edge_free(const ArmourRoadmap* rm, const WorldView& v, const double* a, const double* b) {
     const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
     double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
     for (int64_t s = 0; s < S; s++) {
         edge_sample(rm->rb, a, b, s, S, q, r);
-        if (!config_free(rm->rb, q, r, obs, rm->O, false, nullptr)) return false;
+        const bool ok = v.moving ? config_free_moving(rm->rb, q, r, v.obs, rm->O, v.mid, v.half, false, nullptr)
+                                 : config_free(rm->rb, q, r, v.obs, rm->O, false, nullptr);
+        if (!ok) return false;
     }
     // with the self masks switched on (armour_roadmap_use_self) the same edge passes the self edge rule as well
     return !rm->self_on || self_edge_free(rm->rb, rm->self_table, rm->edge_step, a, b);
@@ -77,7 +87,10 @@ bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, cons
 
 void world_view(const ArmourRoadmap* rm, int32_t w, WorldView* v) {
     const int N = rm->N, E = rm->E;
-    v->obs = rm->obs.data() + (size_t)w * rm->O * RM_OBS_STRIDE;
+    v->moving = rm->moving;
+    v->obs = rm->obs.data() + (size_t)w * rm->O * (rm->moving ? RM_MOV_STRIDE : RM_OBS_STRIDE);
+    v->mid = rm->moving ? rm->mid[w] : 0.0;
+    v->half = rm->moving ? rm->half[w] : 0.0;
     v->nf = rm->node_free.data() + (size_t)w * N;
     v->ef = rm->edge_free.data() + (size_t)w * E;
     // free in both masks when the self masks are on
@@ -100,7 +113,7 @@ void connect(const ArmourRoadmap* rm, const WorldView& v, const double* q, int32
     std::partial_sort(cand.begin(), cand.begin() + k, cand.end());
     out->clear();
     for (size_t c = 0; c < k; c++)
-        if (edge_free(rm, v.obs, q, &rm->nodes[(size_t)cand[c].second * n])) out->push_back(cand[c]);
+        if (edge_free(rm, v, q, &rm->nodes[(size_t)cand[c].second * n])) out->push_back(cand[c]);
 }
 
 }  // namespace rmhost
@@ -182,29 +195,79 @@ extern "C" int armour_roadmap_get_sizes(const ArmourRoadmap* rm, int32_t* N, int
     return ARMOUR_OK;
 }
 
-extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
-                                    double* node_clearance, double* ms) {
-    if (!rm) { armour_set_error("armour_roadmap_check: null handle"); return ARMOUR_EINVAL; }
-    ARMOUR_TRY(armour_check_world_counts("armour_roadmap_check", W, O, obstacles));
+// the motion of a moving check as the caller passed it (null: a static check)
+struct Motion {
+    const double *velocity, *t_from, *t_to;
+};
+
+// the argument rules of the three check entries, before a device is touched
+static int check_check_args(const char* who, const ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const Motion* mv) {
+    if (!rm) { armour_set_error("%s: null handle", who); return ARMOUR_EINVAL; }
+    ARMOUR_TRY(armour_check_world_counts(who, W, O, obstacles));
     const size_t nobs = (size_t)W * O * ARMOUR_OBS_DOUBLES;
-    if (const size_t i = first_nonfinite(obstacles, nobs); i < nobs) { armour_set_error("armour_roadmap_check: obstacle %zu is not finite", i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
+    if (const size_t i = first_nonfinite(obstacles, nobs); i < nobs) { armour_set_error("%s: obstacle %zu is not finite", who, i / ARMOUR_OBS_DOUBLES); return ARMOUR_EINVAL; }
+    if (!mv) return ARMOUR_OK;
+    if ((W > 0 && O > 0 && !mv->velocity) || (W > 0 && (!mv->t_from || !mv->t_to))) { armour_set_error("%s: null velocity or window", who); return ARMOUR_EINVAL; }
+    if (!finite_all(mv->velocity, (size_t)W * O * 3) || !finite_all(mv->t_from, (size_t)W) || !finite_all(mv->t_to, (size_t)W)) {
+        armour_set_error("%s: a velocity or a window is not finite", who);
+        return ARMOUR_EINVAL;
+    }
+    for (int32_t w = 0; w < W; w++)
+        if (mv->t_from[w] > mv->t_to[w]) { armour_set_error("%s: world %d: t_from = %g > t_to = %g", who, w, mv->t_from[w], mv->t_to[w]); return ARMOUR_EINVAL; }
+    return ARMOUR_OK;
+}
+
+// What a check leaves on the host for the searches: the obstacles as the kernel staged them and, after a moving check, every world's window
+// as the two numbers the rule reads.  Called before the launch, so that the kernel is given these mid and half.
+static void keep_worlds(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const Motion* mv) {
+    rm->moving = mv != nullptr;
+    rm->obs.resize((size_t)W * O * (mv ? RM_MOV_STRIDE : RM_OBS_STRIDE));
+    if (mv) stage_obstacles_moving(obstacles, mv->velocity, (size_t)W * O, rm->obs.data());
+    else stage_obstacles(obstacles, (size_t)W * O, rm->obs.data());
+    rm->mid.resize(mv ? (size_t)W : 0);
+    rm->half.resize(mv ? (size_t)W : 0);
+    for (int32_t w = 0; mv && w < W; w++) {
+        rm->mid[w] = 0.5 * (mv->t_from[w] + mv->t_to[w]);
+        rm->half[w] = 0.5 * (mv->t_to[w] - mv->t_from[w]);
+    }
+}
+
+// the device entry of both checks (mv null: the static one)
+static int check_on_device(const char* who, ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const Motion* mv, uint8_t* node_free,
+                           uint8_t* edge_free, double* node_clearance, double* ms) {
+    ARMOUR_TRY(check_check_args(who, rm, W, O, obstacles, mv));
+    if (rm->device < 0) { armour_set_error("%s: the handle was made by armour_roadmap_create_host and holds nothing on a device", who); return ARMOUR_EDEVICE; }
+    const size_t nobs = (size_t)W * O * ARMOUR_OBS_DOUBLES;
     HIPCHK(hipSetDevice(rm->device));
     rm->field_valid = false;   // the fields of armour_roadmap_field belong to the check they were computed from
     rm->W = -1;                // from here on d_edge_free is rewritten: a check that fails below leaves no worlds, not the last check's host masks
+    keep_worlds(rm, W, O, obstacles, mv);
     const size_t WN = (size_t)W * rm->N, WE = (size_t)W * rm->E;
     ARMOUR_TRY(rm->d_node_free.reserve(WN));
     ARMOUR_TRY(rm->d_edge_free.reserve(WE));
     if (node_clearance) ARMOUR_TRY(rm->d_clear.reserve(WN));
     ARMOUR_TRY(rm->d_obs.upload(obstacles, nobs, rm->stream));
+    if (mv) {
+        ARMOUR_TRY(rm->d_vel.upload(mv->velocity, (size_t)W * O * 3, rm->stream));
+        ARMOUR_TRY(rm->d_mid.upload(rm->mid.data(), (size_t)W, rm->stream));
+        ARMOUR_TRY(rm->d_half.upload(rm->half.data(), (size_t)W, rm->stream));
+    }
     if (WE) HIPCHK(hipMemsetAsync(rm->d_edge_free, 1, WE, rm->stream));
     const int64_t items = (int64_t)rm->N + rm->M;
     ARMOUR_TRY(rm->ev.record_start(rm->stream));
     if (W > 0 && items > 0) {
         const dim3 grid((unsigned)((items + RM_BLOCK - 1) / RM_BLOCK), (unsigned)W);
-        const size_t lds = (size_t)O * RM_OBS_STRIDE * sizeof(double);
-        hipLaunchKernelGGL(roadmap_check_kernel, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes, rm->d_edges,
-                           rm->d_edge_off, rm->d_sample_edge, rm->d_obs, O, rm->E, rm->d_node_free, rm->d_edge_free,
-                           node_clearance ? rm->d_clear : nullptr);
+        if (mv) {
+            const size_t lds = (size_t)O * RM_MOV_STRIDE * sizeof(double);
+            hipLaunchKernelGGL(roadmap_check_kernel<true>, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes, rm->d_edges,
+                               rm->d_edge_off, rm->d_sample_edge, rm->d_obs, rm->d_vel, rm->d_mid, rm->d_half, O, rm->E, rm->d_node_free, rm->d_edge_free,
+                               node_clearance ? rm->d_clear : nullptr);
+        } else {
+            const size_t lds = (size_t)O * RM_OBS_STRIDE * sizeof(double);
+            hipLaunchKernelGGL(roadmap_check_kernel<false>, grid, dim3(RM_BLOCK), lds, rm->stream, rm->rb, rm->N, rm->M, rm->d_nodes, rm->d_edges,
+                               rm->d_edge_off, rm->d_sample_edge, rm->d_obs, nullptr, nullptr, nullptr, O, rm->E, rm->d_node_free, rm->d_edge_free,
+                               node_clearance ? rm->d_clear : nullptr);
+        }
         HIPCHK(hipGetLastError());
     }
     ARMOUR_TRY(rm->ev.record_stop(rm->stream));
@@ -217,9 +280,61 @@ extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, con
     if (ms) ARMOUR_TRY(rm->ev.elapsed_ms(ms));
     if (node_free && WN) std::memcpy(node_free, rm->node_free.data(), WN);
     if (edge_free && WE) std::memcpy(edge_free, rm->edge_free.data(), WE);
-    // the obstacles as the kernel staged them, for the host checks of armour_roadmap_plan
-    rm->obs.resize((size_t)W * O * RM_OBS_STRIDE);
-    stage_obstacles(obstacles, (size_t)W * O, rm->obs.data());
+    rm->W = W;
+    rm->O = O;
+    return ARMOUR_OK;
+}
+
+extern "C" int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
+                                    double* node_clearance, double* ms) {
+    return check_on_device("armour_roadmap_check", rm, W, O, obstacles, nullptr, node_free, edge_free, node_clearance, ms);
+}
+
+extern "C" int armour_roadmap_check_moving(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity, const double* t_from,
+                                           const double* t_to, uint8_t* node_free, uint8_t* edge_free, double* node_clearance, double* ms) {
+    const Motion mv{velocity, t_from, t_to};
+    return check_on_device("armour_roadmap_check_moving", rm, W, O, obstacles, &mv, node_free, edge_free, node_clearance, ms);
+}
+
+// the window rule by the kernel's functions in a host loop, on a handle of armour_roadmap_create_host; it leaves the host state of a device check
+extern "C" int armour_roadmap_check_moving_host(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                                const double* t_from, const double* t_to, uint8_t* node_free, uint8_t* edge_free,
+                                                double* node_clearance) {
+    const char* who = "armour_roadmap_check_moving_host";
+    const Motion mv{velocity, t_from, t_to};
+    ARMOUR_TRY(check_check_args(who, rm, W, O, obstacles, &mv));
+    if (rm->device >= 0) { armour_set_error("%s: the handle holds a device; make one with armour_roadmap_create_host", who); return ARMOUR_EINVAL; }
+    rm->field_valid = false;
+    rm->W = -1;
+    keep_worlds(rm, W, O, obstacles, &mv);
+    const int n = rm->rb.n, N = rm->N, E = rm->E;
+    rm->node_free.assign((size_t)W * N, 0);
+    rm->edge_free.assign((size_t)W * E, 1);
+    double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
+    for (int32_t w = 0; w < W; w++) {
+        const double* obs = rm->obs.data() + (size_t)w * O * RM_MOV_STRIDE;
+        for (int i = 0; i < N; i++) {
+            for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < n ? rm->nodes[(size_t)i * n + j] : 0.0;
+            for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
+            double cl;
+            const bool full = node_clearance != nullptr;
+            rm->node_free[(size_t)w * N + i] = config_free_moving(rm->rb, q, r, obs, O, rm->mid[w], rm->half[w], full, &cl) ? 1 : 0;
+            if (full) node_clearance[(size_t)w * N + i] = cl;
+        }
+        for (int e = 0; e < E; e++) {
+            const double *a = &rm->nodes[(size_t)rm->edges[2 * e] * n], *b = &rm->nodes[(size_t)rm->edges[2 * e + 1] * n];
+            const int64_t S = edge_segments(rm->rb, a, b, rm->edge_step);
+            for (int64_t s = 0; s < S; s++) {
+                edge_sample(rm->rb, a, b, s, S, q, r);
+                if (!config_free_moving(rm->rb, q, r, obs, O, rm->mid[w], rm->half[w], false, nullptr)) {
+                    rm->edge_free[(size_t)w * E + e] = 0;
+                    break;
+                }
+            }
+        }
+    }
+    if (node_free && W && N) std::memcpy(node_free, rm->node_free.data(), (size_t)W * N);
+    if (edge_free && W && E) std::memcpy(edge_free, rm->edge_free.data(), (size_t)W * E);
     rm->W = W;
     rm->O = O;
     return ARMOUR_OK;
@@ -251,7 +366,7 @@ extern "C" int armour_roadmap_plan(ArmourRoadmap* rm, int32_t w, const double* q
         for (size_t i = 0; i < seq.size(); i++) std::memcpy(path + i * n, node(seq[i]), n * sizeof(double));
         return ARMOUR_OK;
     };
-    if (rmhost::edge_free(rm, view.obs, q_start, q_goal)) return emit({N, N + 1});
+    if (rmhost::edge_free(rm, view, q_start, q_goal)) return emit({N, N + 1});
     // graph: roadmap nodes 0..N-1, start N, goal N+1
     std::vector<std::vector<std::pair<int, double>>> adj((size_t)N + 2);
     for (int e = 0; e < rm->E; e++) {

@@ -236,7 +236,7 @@ extern "C" int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double
     rmhost::world_view(rm, w, &view);
     std::vector<int> seq;   // the roadmap nodes between start and goal
     double total;
-    if (rmhost::edge_free(rm, view.obs, q_start, goal)) {
+    if (rmhost::edge_free(rm, view, q_start, goal)) {
         total = rmhost::wrapped_distance(rm->rb, q_start, goal);
     } else {
         std::vector<std::pair<double, int>> joined;

@@ -58,6 +58,7 @@ struct ArmourRoadmap {
     std::vector<double> nodes;           // [N][n]
     std::vector<int32_t> edges;          // [E][2]
     DevBuf<double> d_nodes, d_obs, d_clear;
+    DevBuf<double> d_vel, d_mid, d_half;  // the last moving check: velocity [W][O][3], the windows' midpoints and half widths [W]
     DevBuf<int32_t> d_edges, d_sample_edge;
     DevBuf<int64_t> d_edge_off;
     DevBuf<uint8_t> d_node_free, d_edge_free;
@@ -65,7 +66,10 @@ struct ArmourRoadmap {
     EventPair ev;
     // the last check, on the host
     int32_t W = -1, O = 0;
-    std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them
+    std::vector<double> obs;             // [W][O][RM_OBS_STRIDE], staged as the kernel stages them ([W][O][RM_MOV_STRIDE] when `moving`)
+    // the last check was armour_roadmap_check_moving: every later test of geometry for its worlds uses the window rule
+    bool moving = false;
+    std::vector<double> mid, half;       // [W]: 0.5 (t_from + t_to), 0.5 (t_to - t_from), the numbers the kernels are given
     std::vector<uint8_t> node_free, edge_free;
     // the self-collision masks (armour_roadmap_check_self, self_check.hip): world-independent, kept until the next self check
     bool self_on = false, self_checked = false;
@@ -91,16 +95,20 @@ struct ArmourRoadmap {
 namespace rmhost {
 
 double wrapped_distance(const rmgeo::RmRobot& rb, const double* a, const double* b);
-// the edge rule on the host, for an edge that is not in the roadmap (with the self masks on: the self edge rule as well)
-bool edge_free(const ArmourRoadmap* rm, const double* obs, const double* a, const double* b);
-
 // World w of the last check as a search reads it: its staged obstacles and its node / edge masks, ANDed with the self masks when those are on.
+// After a moving check: moving = true, the obstacles staged with RM_MOV_STRIDE, and the world's window as mid and half.
 struct WorldView {
     const double* obs = nullptr;
+    bool moving = false;
+    double mid = 0.0, half = 0.0;
     const uint8_t *nf = nullptr, *ef = nullptr;
     std::vector<uint8_t> both_n, both_e;
 };
 void world_view(const ArmourRoadmap* rm, int32_t w, WorldView* v);
+
+// the edge rule on the host in the world of `v` (the window rule after a moving check), for an edge that is not in the roadmap (with the self
+// masks on: the self edge rule as well).  The one place where the host searches choose between the static and the moving rule.
+bool edge_free(const ArmourRoadmap* rm, const WorldView& v, const double* a, const double* b);
 
 // q's connect_k nearest free nodes by wrapped_distance(q, node) (ties: the smaller index), in that order, those whose connecting edge is free:
 // (distance, node)

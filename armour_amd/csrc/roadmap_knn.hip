@@ -187,18 +187,24 @@ __global__ __launch_bounds__(KT_BLOCK) void knn_merge_kernel(int32_t P, int32_t 
 // grid Q, dynamic LDS [O][RM_OBS_STRIDE] doubles: query i's candidates c < count[i] are the edges q[i] -> nodes[index[i][c]], candidate
 // c = k (with target) the edge q[i] -> target[i].  An item is (candidate, sub-segment); a candidate found colliding is skipped by the items
 // that have not started (s_ok: every writer writes 0).  on / shrink: the self table, null with the self masks off.
+// MOVING (after armour_roadmap_check_moving): the window rule of roadmap.hip's moving check -- dynamic LDS [O][RM_MOV_STRIDE], velocity
+// [W][O][3], mid / half [W] of the last check.  The static instantiation reads none of the three.
+template <bool MOVING>
 __global__ __launch_bounds__(CE_BLOCK) void connect_edges_kernel(RmRobot rb, double edge_step, int32_t k, const double* __restrict__ nodes,
                                                                   const double* __restrict__ q, const double* __restrict__ target,
-                                                                  const int32_t* __restrict__ world, const double* __restrict__ obstacles, int32_t O,
+                                                                  const int32_t* __restrict__ world, const double* __restrict__ obstacles,
+                                                                  const double* __restrict__ velocity, const double* __restrict__ mid,
+                                                                  const double* __restrict__ half, int32_t O,
                                                                   const int32_t* __restrict__ index, const int32_t* __restrict__ count,
                                                                   const uint8_t* __restrict__ on, const double* __restrict__ shrink, int32_t rows,
                                                                   uint8_t* __restrict__ ok /* [Q][k + 1] */) {
-    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE], MOVING: [O][RM_MOV_STRIDE]
     __shared__ int s_off[ARMOUR_ROADMAP_KNN_MAX + 2];
     __shared__ int s_ok[ARMOUR_ROADMAP_KNN_MAX + 1];
     const int n = rb.n, t = threadIdx.x, i = blockIdx.x;
     const double* a = q + (size_t)i * n;
-    stage_obstacles_lds<CE_BLOCK>(obstacles + (size_t)world[i] * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    if constexpr (MOVING) stage_obstacles_moving_lds<CE_BLOCK>(obstacles + (size_t)world[i] * O * ARMOUR_OBS_DOUBLES, velocity + (size_t)world[i] * O * 3, O, s_obs);
+    else stage_obstacles_lds<CE_BLOCK>(obstacles + (size_t)world[i] * O * ARMOUR_OBS_DOUBLES, O, s_obs);
     const int cands = count[i], C = k + 1;
     auto end_of = [&](int c) -> const double* {
         if (c < cands) return nodes + (size_t)index[(size_t)i * k + c] * n;
@@ -228,7 +234,9 @@ __global__ __launch_bounds__(CE_BLOCK) void connect_edges_kernel(RmRobot rb, dou
         const int64_t s = item - s_off[c], S = s_off[c + 1] - s_off[c];
         double x[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
         edge_sample(rb, a, b, s, S, x, r);
-        bool free_ = config_free(rb, x, r, s_obs, O, false, nullptr);
+        bool free_;
+        if constexpr (MOVING) free_ = config_free_moving(rb, x, r, s_obs, O, mid[world[i]], half[world[i]], false, nullptr);
+        else free_ = config_free(rb, x, r, s_obs, O, false, nullptr);
         for (int row = 0; free_ && on && row < rows; row++) {
             double delta[ARMOUR_MAX_FACTORS], cl;
             int which;
@@ -351,10 +359,13 @@ int connect_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* world, const doub
     }
     const int C = kk + 1;
     ARMOUR_TRY(rm->d_kok.reserve((size_t)Q * C));
-    const size_t lds = (size_t)rm->O * RM_OBS_STRIDE * sizeof(double);
-    hipLaunchKernelGGL(connect_edges_kernel, dim3((unsigned)Q), dim3(CE_BLOCK), lds, rm->stream, rm->rb, rm->edge_step, kk, rm->d_nodes, rm->d_kq,
-                       target ? rm->d_ktarget.p : nullptr, rm->d_kmask, rm->d_obs, rm->O, rm->d_kidx, rm->d_kcount, rm->self_on ? rm->d_self_on.p : nullptr,
-                       rm->self_on ? rm->d_self_shrink.p : nullptr, rm->self_on ? rm->self_table.rows : 0, rm->d_kok);
+    // the one place where the batched joins choose between the static and the window rule: the last check's
+    const size_t lds = (size_t)rm->O * (rm->moving ? RM_MOV_STRIDE : RM_OBS_STRIDE) * sizeof(double);
+    const double* none = nullptr;
+    hipLaunchKernelGGL(rm->moving ? connect_edges_kernel<true> : connect_edges_kernel<false>, dim3((unsigned)Q), dim3(CE_BLOCK), lds, rm->stream, rm->rb,
+                       rm->edge_step, kk, rm->d_nodes, rm->d_kq, target ? rm->d_ktarget.p : nullptr, rm->d_kmask, rm->d_obs, rm->moving ? rm->d_vel.p : none,
+                       rm->moving ? rm->d_mid.p : none, rm->moving ? rm->d_half.p : none, rm->O, rm->d_kidx, rm->d_kcount,
+                       rm->self_on ? rm->d_self_on.p : nullptr, rm->self_on ? rm->d_self_shrink.p : nullptr, rm->self_on ? rm->self_table.rows : 0, rm->d_kok);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(rm->ev.record_stop(rm->stream));
     std::vector<int32_t> h_idx((size_t)Q * kk);

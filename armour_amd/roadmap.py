@@ -14,6 +14,8 @@ configurations + an adjacency list in, node feasibility / link_c / the collision
     index, dist, count = rm.knn(queries, k=8)               # [Q,n] -> each query's k nearest nodes in the order (distance, index), one call
     rm = Roadmap(robot, *device_roadmap(robot, 200000, 0.3, 16, 0, lb, ub, cont), continuous=cont)    # the edges by that search
     paths = rm.descend_many(worlds, starts)                 # descend() for Q queries with one device call
+    v = rm.check_moving(obstacles, velocity, t_from, t_to)  # check() against obstacles in linear motion over a time window per world
+    res = run_trials(worlds, hlp=moving_field_hlps(rm, worlds, velocities), velocities=velocities)   # whole trials in moving worlds
 
 The node and edge rules (exact node test, conservative edge test with enlarged boxes) are stated in include/armour_hip.h and DESIGN.md.
 """
@@ -71,7 +73,8 @@ class Roadmap:
     """A roadmap on one device: nodes [N,n], edges [E,2], the edge rule's step (radians per sub-segment)."""
 
     def __init__(self, robot, nodes, edges, continuous=None, edge_step=0.05, device=0, host=False):
-        """host=True: a handle that holds nothing on a device (armour_roadmap_create_host); it serves knn(host=True) and nothing else."""
+        """host=True: a handle that holds nothing on a device (armour_roadmap_create_host); it serves knn(host=True), check_moving(host=True)
+        and plan() after that check, and nothing else."""
         self.L = _lib.load()
         self.robot = robot
         self.n = robot.num_factors
@@ -113,6 +116,29 @@ class Roadmap:
         check(self.L.armour_roadmap_check(self.h, W, O, _dp(obs) if obs.size else None, nf.ctypes.data_as(u8), ef.ctypes.data_as(u8),
                                           _dp(cl) if clearance else None, C.byref(ms)))
         self.W = W              # (a check that fails after its arguments passed leaves the library without worlds: field() is ESTATE)
+        out = dict(node_free=nf.astype(bool), edge_free=ef.astype(bool), ms=ms.value)
+        if clearance:
+            out["node_clearance"] = cl
+        return out
+
+    def check_moving(self, obstacles, velocity, t_from, t_to, clearance=False, host=False):
+        """check() over a time window per world against obstacles in linear motion (armour_roadmap_check_moving): obstacles [W,O,12] (or
+        [O,12]) are the poses at world time 0, velocity [W,O,3] (or [O,3]) the constant velocities, t_from / t_to [W] (or scalars, for every
+        world) the windows in world time.  Returns the dict check() returns (ms = 0 on the host).  Until the next check, plan / descend /
+        connect_many / descend_many join points to the roadmap by the window rule.  host=True: the library's host loop, on a Roadmap(host=True)."""
+        obs, W, O = _lib.as_worlds(obstacles)
+        vel = np.ascontiguousarray(np.asarray(velocity, dtype=np.float64).reshape(W, O, 3))
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_from, dtype=np.float64), (W,)))
+        t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_to, dtype=np.float64), (W,)))
+        nf = np.zeros((W, self.N), dtype=np.uint8)
+        ef = np.zeros((W, self.E), dtype=np.uint8)
+        cl = np.zeros((W, self.N)) if clearance else None
+        ms = C.c_double(0.0)
+        u8 = C.POINTER(C.c_uint8)
+        args = (self.h, W, O, _dp(obs) if obs.size else None, _dp(vel) if vel.size else None, _dp(t0), _dp(t1), nf.ctypes.data_as(u8), ef.ctypes.data_as(u8),
+                _dp(cl) if clearance else None)
+        check(self.L.armour_roadmap_check_moving_host(*args) if host else self.L.armour_roadmap_check_moving(*args, C.byref(ms)))
+        self.W = W
         out = dict(node_free=nf.astype(bool), edge_free=ef.astype(bool), ms=ms.value)
         if clearance:
             out["node_clearance"] = cl
@@ -353,4 +379,55 @@ def field_hlps(roadmap, worlds, connect_k=8, batched=False):
 
     if batched:
         make.get_waypoints = get_waypoints
+    return make
+
+
+def moving_field_hlps(roadmap, worlds, velocities, horizon=None, connect_k=8):
+    """field_hlps(batched=True) for worlds whose obstacles move: `velocities` is a list of [O_w, 3], one per world (padded with zeros as the
+    obstacles are padded with pad_obstacles).  The factory carries set_world_times(t_world [W]), which run_trials(velocities=...) calls
+    before every waypoint query, and get_waypoints(indices, qs, lookaheads), which does per call ONE check_moving of all W worlds on the
+    windows [t_world[w], t_world[w] + horizon], ONE field and ONE descend_many, with field_hlps' fall-back to the straight-line waypoint.
+    horizon=None: the plan's duration (planner.default_params), the span the half-space tables of the same iteration cover.  Worlds that have
+    finished keep their last clock, so a world's index is its index in the trial.  The factory's last_check is the dict the last check_moving
+    returned (None before the first call)."""
+    probs = [p for _, p in worlds]
+    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
+    vel = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
+    if len(vel) != len(obs) or any(v.shape[0] != o.shape[0] for v, o in zip(vel, obs)):
+        raise ValueError("moving_field_hlps: one velocity per obstacle of every world")
+    O = max([o.shape[0] for o in obs] + [1])
+    obs_p = np.stack([pad_obstacles(o, O) for o in obs])
+    vel_p = np.stack([np.concatenate([v, np.zeros((O - v.shape[0], 3))]) for v in vel])
+    goals = np.stack([np.asarray(p["goal"], dtype=np.float64) for p in probs])
+    if horizon is None:
+        from .planner import default_params
+        horizon = default_params(1).duration
+    state = dict(t_world=np.zeros(len(probs)))
+
+    class _One:
+        """One world's view of the factory, for a caller that asks world by world: each question is a get_waypoints of its own."""
+
+        def __init__(self, i):
+            self.i = int(i)
+
+        def get_waypoint(self, q_cur, lookahead):
+            return get_waypoints([self.i], [np.asarray(q_cur, dtype=np.float64)], [lookahead])[0]
+
+    def make(i, world):
+        return _One(i)
+
+    def set_world_times(t_world):
+        state["t_world"] = np.array(np.broadcast_to(np.asarray(t_world, dtype=np.float64), (len(probs),)))
+
+    def get_waypoints(indices, qs, lookaheads):
+        cont = roadmap.continuous.astype(bool)
+        make.last_check = roadmap.check_moving(obs_p, vel_p, state["t_world"], state["t_world"] + float(horizon))
+        roadmap.field(goals, connect_k=connect_k)
+        paths = roadmap.descend_many(indices, qs, connect_k=connect_k)
+        return [straight_line_waypoint(q, goals[i], la) if path is None else waypoint_along(path, q, la, cont)
+                for i, q, la, (path, _) in zip(indices, qs, lookaheads, paths)]
+
+    make.last_check = None
+    make.set_world_times = set_world_times
+    make.get_waypoints = get_waypoints
     return make

@@ -18,6 +18,8 @@ it yields none, KSI/uarmtd_planner.m:241-245), armour_set_problems + armour_solv
   * goal check as KSI/kinova_world_static.m:417-425: |angdiff(q, goal)|_2 <= goal_radius at the piece's end or at one of `goal_nodes`
     evenly spaced nodes on it, in closed form on the host;
   * the iteration cap ends the trial `iteration_limit`.
+With velocities (obstacles in linear motion) every world has a clock: the tables are built from worlds.moving_frames at the world's clock, the
+executed piece goes to armour_path_audit_moving with the world time of its plan time 0, and the clock advances by the executed window.
 A world that ends leaves the next batch.  With per_step_build=True (ARMOUR_OPT_P1_BUILD held to the per-step kernel) a world's record does
 not depend on which other worlds share its batch -- the header's own contract.
 """
@@ -26,11 +28,12 @@ import time
 import numpy as np
 
 from . import _lib, scenes
-from .path_audit import FREE, HIT, UNDECIDED, audit, audit_self
+from .path_audit import FREE, HIT, UNDECIDED, audit, audit_moving, audit_self
 from .planner import ArmourNLP, default_params, desired_trajectory, kinova_robot
 
 OUTCOMES = ("goal", "collision", "stuck", "iteration_limit")
 SELF_OUTCOME = "self_collision"   # only with run_trials(self_check="stop")
+STRUCK_OUTCOME = "struck_at_rest"  # only with run_trials(velocities=...): a moving obstacle ran into an arm that stood still
 
 
 def bezier_q(q0, qd0, qdd0, k, k_range, duration, t):
@@ -70,6 +73,7 @@ class DevicePlanner:
 
     def __init__(self, robot=None, T=128, max_batch=128, max_obstacles=16, per_step_build=False, device=0, solve_options=None, rescue_candidates=0):
         self.robot = robot if robot is not None else kinova_robot()
+        self.T = int(T)
         self.params = default_params(T)
         n = self.robot.num_factors
         self.k_range = np.array(self.params.k_range[:n])
@@ -86,6 +90,14 @@ class DevicePlanner:
         """[B, n] x 4 and [B, O, 12] -> (results [B] of dict(k_opt, feasible, iterations, time_ms, ...), build_ms, solve_ms) -- the two times
         are the batch's: device time of the reach-set build and wall time of the solve."""
         self.nlp.set_parameters(q0, qd0, qdd0, q_des, obstacles)
+        return self._solve()
+
+    def plan_moving(self, q0, qd0, qdd0, q_des, frames):
+        """plan() against moving obstacles: frames [B, T, O, 12] as worlds.moving_frames builds them (ArmourNLP.set_parameters_moving)."""
+        self.nlp.set_parameters_moving(q0, qd0, qdd0, q_des, frames)
+        return self._solve()
+
+    def _solve(self):
         build_ms = self.nlp.build_ms
         t0 = time.perf_counter()
         if self.rescue_candidates > 0:
@@ -108,7 +120,8 @@ def _world_record(world):
 
 def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, stop_threshold=4, max_iterations=300, audit_step=0.01, tube=None,
                tracked=False, track_samples=1, track_dt=1e-3, track_seed=0, goal_nodes=10, T=128, per_step_build=False, solve_options=None,
-               backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0, self_check=None, self_pairs=None, self_shrink=None):
+               backend=None, audit_on_host=False, clearance=True, device=0, rescue_candidates=0, self_check=None, self_pairs=None, self_shrink=None,
+               velocities=None):
     """Run every world of `worlds` ([(name, problem)] as scenes.reference_worlds() gives them; a problem holds q0 = the start at rest, goal,
     obstacles [O, 12] and lookahead) to its end.  hlp: "straight" or a factory (world index, world record) -> object with
     get_waypoint(q_cur, lookahead) (e.g. a RoadmapHLP; None = no waypoint: the goal is used); a factory that also has
@@ -123,6 +136,16 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
     iteration for the executed pieces, with the world audit's tube and step and the table self_pairs / self_shrink; every record carries
     `self_verdict`, `self_t_hit` and `self_clearance`, the summary counts `self_hit_pieces` and `self_undecided_pieces`) or "stop" (as "record",
     and verdict 1 ends the world with the outcome `self_collision`, after a world collision and before the goal check).
+    velocities: None (default: static worlds, today's path) or a list of [O_w, 3], every obstacle's constant velocity; `obstacles` are then the
+    poses at world time 0.  Every world has a clock t_world that starts at 0.  A factory that has set_world_times(t_world [W]) is given all
+    worlds' clocks before the waypoint query (roadmap.moving_field_hlps).  The backend is asked plan_moving(q0, qd0, qdd0, q_des, frames
+    [B, T, O, 12]) with frames[b] = worlds.moving_frames(obstacles_w, velocity_w, backend.T, duration, t_world_w), and the state keeps with a
+    plan the world time of its plan time 0.  The executed pieces go to audit_moving: a `plan` or `stay` piece with t_world = the clock, a
+    `brake` piece with the stored world time of its plan (its window [t_plan, duration] belongs to the plan made one iteration earlier, whose
+    frames covered that span).  The clock then advances by the executed window: t_plan, duration - t_plan for a `brake`.  Every record carries
+    `t_world`, the clock at which the iteration planned.  A proved hit on a `stay` piece -- a moving obstacle ran into an arm that stood still,
+    which no planner can prevent -- ends the world `struck_at_rest` (counted in the summary only with velocities); on a `plan` or `brake` piece
+    it stays `collision`.
     Returns dict(worlds, summary, ...)."""
     if self_check not in (None, "record", "stop"):
         raise ValueError(f"unknown self_check {self_check!r}")
@@ -137,6 +160,14 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
     k_range, D, t_plan = np.asarray(backend.k_range, dtype=np.float64), float(backend.duration), float(backend.t_plan)
     O = max([w["obstacles"].shape[0] for w in ws] + [1])
     obstacles = np.stack([scenes.pad_obstacles(w["obstacles"], O) for w in ws]) if W else np.zeros((0, O, 12))
+    moving = velocities is not None
+    if moving:
+        from .worlds import moving_frames
+        vel = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
+        if len(vel) != W or any(v.shape[0] != w["obstacles"].shape[0] for v, w in zip(vel, ws)):
+            raise ValueError("run_trials: velocities holds one [O_w, 3] per world")
+        velocity = np.stack([np.concatenate([v, np.zeros((O - v.shape[0], 3))]) for v in vel]) if W else np.zeros((0, O, 3))
+        t_world = np.zeros(W)
     if isinstance(tube, str):
         if tube != "ultimate_bound":
             raise ValueError(f"unknown tube {tube!r}")
@@ -162,6 +193,8 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
             break
         # 1. waypoints
         t_hlp = time.perf_counter()
+        if moving and hasattr(hlp, "set_world_times"):
+            hlp.set_world_times(t_world.copy())
         if batch_hlp is not None:      # one call for all live worlds
             wps = batch_hlp(list(live), [st[i]["q"].copy() for i in live], [ws[i]["lookahead"] for i in live])
         else:
@@ -170,10 +203,14 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
         hlp_ms = (time.perf_counter() - t_hlp) * 1e3
         q0, qd0, qdd0, q_des = (np.stack(a) for a in ([st[i]["q"] for i in live], [st[i]["qd"] for i in live], [st[i]["qdd"] for i in live], q_des))
         # 2. one batch
-        res, build_ms, solve_ms = backend.plan(q0, qd0, qdd0, q_des, obstacles[live])
+        if moving:
+            frames = np.stack([moving_frames(obstacles[i], velocity[i], backend.T, D, t_world[i]) for i in live])
+            res, build_ms, solve_ms = backend.plan_moving(q0, qd0, qdd0, q_des, frames)
+        else:
+            res, build_ms, solve_ms = backend.plan(q0, qd0, qdd0, q_des, obstacles[live])
         batches.append(dict(iteration=it, live=len(live), hlp_ms=hlp_ms, build_ms=build_ms, solve_ms=solve_ms))
         # 3 / 4. what every world executes: (plan q0, qd0, qdd0, k, ta, tb) and its next state
-        pieces = []
+        pieces, piece_t0 = [], []   # piece_t0 (moving worlds): the world time of every piece's plan time 0
         for b, i in enumerate(live):
             s, r = st[i], res[b]
             rec = dict(iteration=it, q0=q0[b].copy(), qd0=qd0[b].copy(), qdd0=qdd0[b].copy(), q_des=q_des[b].copy(), k_opt=np.array(r["k_opt"], dtype=np.float64),
@@ -184,6 +221,8 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
                 piece, kind = plan + (0.0, t_plan), "plan"
                 s["q"], s["qd"], s["qdd"] = desired_trajectory(*plan, t_plan, k_range=k_range, duration=D)
                 s["plan"], s["at_rest"], s["fails"] = plan, False, 0
+                if moving:
+                    s["plan_t_world"] = float(t_world[i])
             else:
                 s["fails"] += 1
                 if s["plan"] is not None and not s["at_rest"]:
@@ -193,13 +232,21 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
                 else:
                     piece, kind = (s["q"].copy(), z.copy(), z.copy(), z.copy(), 0.0, t_plan), "stay"
             rec.update(executed=kind, piece=piece, fails=s["fails"])
+            if moving:
+                rec["t_world"] = float(t_world[i])
+                piece_t0.append(s["plan_t_world"] if kind == "brake" else float(t_world[i]))
+                t_world[i] += (D - t_plan) if kind == "brake" else t_plan
             pieces.append(piece)
             s["records"].append(rec)
         # 5. one audit call for all live worlds
         cols = [np.stack([p[c] for p in pieces]) for c in range(4)]
         ta, tb = np.array([p[4] for p in pieces]), np.array([p[5] for p in pieces])
-        au = audit(robot, obstacles[live], np.arange(len(live), dtype=np.int32), *cols, k_range, D, ta, tb, tube=tube_e, step=audit_step,
-                   clearance=clearance, host=audit_on_host)
+        if moving:
+            au = audit_moving(robot, obstacles[live], velocity[live], np.arange(len(live), dtype=np.int32), np.array(piece_t0), *cols, k_range, D, ta, tb,
+                              tube=tube_e, step=audit_step, clearance=clearance, host=audit_on_host)
+        else:
+            au = audit(robot, obstacles[live], np.arange(len(live), dtype=np.int32), *cols, k_range, D, ta, tb, tube=tube_e, step=audit_step,
+                       clearance=clearance, host=audit_on_host)
         batches[-1]["audit_ms"] = au.ms
         if self_check is not None:
             sa = audit_self(robot, *cols, k_range, D, ta, tb, tube=tube_e, step=audit_step, pairs=self_pairs, shrink=self_shrink, clearance=clearance,
@@ -233,7 +280,7 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
             nodes = bezier_q(p[0], p[1], p[2], p[3], k_range, D, np.linspace(p[4], p[5], goal_nodes + 1))
             rec["goal_reached"] = goal_reached(nodes, ws[i]["goal"], goal_radius)
             if au.verdict[b] == HIT:
-                s["outcome"] = "collision"
+                s["outcome"] = STRUCK_OUTCOME if moving and rec["executed"] == "stay" else "collision"
             elif self_check == "stop" and sa.verdict[b] == HIT:
                 s["outcome"] = SELF_OUTCOME
             elif rec["goal_reached"]:
@@ -260,6 +307,8 @@ def run_trials(worlds, robot=None, *, hlp="straight", goal_radius=np.pi / 30, st
         summary.update(self_hit_pieces=sum(1 for v in sv if v == HIT), self_undecided_pieces=sum(1 for v in sv if v == UNDECIDED))
         if self_check == "stop":
             summary[SELF_OUTCOME] = sum(1 for s in st if s["outcome"] == SELF_OUTCOME)
+    if moving:
+        summary[STRUCK_OUTCOME] = sum(1 for s in st if s["outcome"] == STRUCK_OUTCOME)
     if tracked:
         ub, qe, qde = ultimate_bound(robot)
         trk = [r["tracking"] for s in st for r in s["records"]]

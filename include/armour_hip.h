@@ -748,6 +748,35 @@ int armour_roadmap_get_sizes(const ArmourRoadmap* rm, int32_t* N, int32_t* E, in
  * launch.  The handle keeps every world's verdicts and obstacles for armour_roadmap_plan. */
 int armour_roadmap_check(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, uint8_t* node_free, uint8_t* edge_free,
                          double* node_clearance, double* ms);
+/* armour_roadmap_check against obstacles in LINEAR MOTION, over a time window per world.  obstacles [W][O][12] is every obstacle's pose at
+ * world time 0, velocity [W][O][3] its constant velocity, t_from / t_to [W] the window of world w in world time (t_from <= t_to).
+ * Window rule.  The host computes once per world mid[w] = 0.5 * (t_from[w] + t_to[w]) and half[w] = 0.5 * (t_to[w] - t_from[w]) and hands
+ *   these two numbers to the kernel, so host and device judge by the same doubles.  A node is FREE in the window when the node rule's pair
+ *   tests pass with, for obstacle o, the box centre x - v_o mid (component-wise x[i] - v[i] * mid) and every half-size h_l + |v_o|_2 half
+ *   (|v_o|_2 = sqrt((v0^2 + v1^2) + v2^2), computed once per obstacle when it is staged); its clearance is the minimum of those pair
+ *   values.  An edge is FREE when every sub-segment of the edge rule passes the same tests with the half-sizes h_l + (r_l + |v_o|_2 half).
+ *   Sub-segment counts and offsets are the static check's (armour_roadmap_get_sizes stays valid).
+ * Soundness.  Within [t_from, t_to] obstacle o leaves its pose of time mid by at most |v_o| half.  A meets B + d exactly when A - d meets B,
+ *   and a box whose half-sizes grow by rho contains the box (+) a ball of radius rho.  So no configuration on a free node or edge meets an
+ *   obstacle at ANY time of the window, whatever the time at which the arm passes it (the static argument supplies r_l).
+ * With zero velocities the masks and clearances are armour_roadmap_check's bit for bit, for any window (x - 0 * mid = x,
+ *   h + (r + 0 * half) = h + r); t_from == t_to is the verdict at an instant.
+ * State.  The handle keeps the obstacles, velocities and windows: until the next check, armour_roadmap_plan, armour_roadmap_descend,
+ *   armour_roadmap_connect_batch, armour_roadmap_descend_batch and the seeds of armour_roadmap_field test the edges that join a point to the
+ *   roadmap by the window rule of the point's world.  armour_roadmap_check returns the handle to the static rule.  Either check ends the
+ *   field.  armour_roadmap_knn and the self masks read masks only.
+ * Device.  One launch for all W worlds; RM_OBS_STRIDE + 4 doubles of LDS per obstacle (248 B: 62 KB per block at the cap).
+ * ARMOUR_EINVAL before a device is touched: armour_roadmap_check's refusals; a null or non-finite velocity, t_from or t_to;
+ * t_from[w] > t_to[w]. */
+int armour_roadmap_check_moving(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                const double* t_from, const double* t_to, uint8_t* node_free, uint8_t* edge_free,
+                                double* node_clearance, double* ms);
+/* the same rule by the same functions in a host loop, for a handle of armour_roadmap_create_host (any other: ARMOUR_EINVAL); runs without
+ * a GPU.  It leaves the host state of the device entry -- W, O, the masks, the staged obstacles and the windows -- so armour_roadmap_plan
+ * works on that handle afterwards. */
+int armour_roadmap_check_moving_host(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                     const double* t_from, const double* t_to, uint8_t* node_free, uint8_t* edge_free,
+                                     double* node_clearance);
 /* Host search over world w of the last check: the direct start -> goal edge if it is free; else start and goal are joined to their
  * connect_k nearest free nodes (wrapped joint distance) by edges checked with the edge rule, and A* runs over the free edges with
  * wrapped-distance weights.  path [max_points][n] = start, nodes..., goal; *points = 0 when there is no path.  ARMOUR_ESTATE before
@@ -811,8 +840,9 @@ int armour_roadmap_descend(ArmourRoadmap* rm, int32_t w, const double* q_start, 
  * Device: Q >= ARMOUR_ROADMAP_KNN_MANY queries take one lane per query (the nodes cut into up to 16 slices when the queries alone do
  *   not fill the device); fewer take one block per (query, 256 nodes).  Every shape writes sorted partial lists and a second launch
  *   merges them by rank.  DESIGN.md 4.12b.
- * armour_roadmap_knn_host is the same rule in a host loop and touches no device; a handle of armour_roadmap_create_host serves it
- * (and nothing that needs the device: those entries return ARMOUR_EDEVICE on it). */
+ * armour_roadmap_knn_host is the same rule in a host loop and touches no device; a handle of armour_roadmap_create_host serves it,
+ * armour_roadmap_check_moving_host and armour_roadmap_plan after that check (and nothing that needs the device: those entries return
+ * ARMOUR_EDEVICE on it). */
 #define ARMOUR_ROADMAP_KNN_MAX 64
 #define ARMOUR_ROADMAP_KNN_MANY 2048
 int armour_roadmap_create_host(const ArmourRobot* robot, int32_t N, const double* nodes, int32_t E, const int32_t* edges,

@@ -1,6 +1,7 @@
 // Build check of the roadmap search's host half (armour_amd/csrc/roadmap_knn.hip, roadmap_field.hip) under the host sanitizers: a program
 // of its own that calls armour_roadmap_knn_host on a host handle (armour_roadmap_create_host) and the descend walk on a hand-built field,
-// compares the search with a plain sort, and prints what it found.
+// compares the search with a plain sort, runs the window rule's host twin (armour_roadmap_check_moving_host) and armour_roadmap_plan after it
+// on a three-node roadmap, and prints what it found.
 //   make -C armour_amd/csrc knnhost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
 // It supplies the symbol the roadmap units take from api.hip, so that nothing else of the library is linked.
 #include <algorithm>
@@ -71,6 +72,34 @@ int main() {
         return 1;
     }
     armour_roadmap_destroy(rm);
+    // the window rule on the host: a box that reaches the end of the arm at t = 2 leaves the edge 0 -> 1 free in [0, 1] and blocks it in [0, 3]
+    {
+        std::vector<double> three((size_t)3 * n, 0.0);
+        three[1] = three[n + 1] = three[2 * n + 1] = 0.6;
+        three[n] = 0.5;
+        three[2 * n] = 0.25;
+        three[2 * n + 1] = -0.6;
+        const int32_t edges[6] = {0, 1, 0, 2, 2, 1};
+        const double box[24] = {0.0, 0.0, 3.5, 0.05, 0, 0, 0, 0.05, 0, 0, 0, 0.05,      // falls onto the arm's top at 1 m/s
+                                50.0, 0.0, 0.0, 0.05, 0, 0, 0, 0.05, 0, 0, 0, 0.05};     // far away, at rest
+        const double vel[6] = {0.0, 0.0, -1.0, 0.0, 0.0, 0.0}, from[1] = {0.0}, early[1] = {1.0}, late[1] = {3.0};
+        uint8_t nf[3], ef[3];
+        double cl[3], path[5 * ARMOUR_MAX_FACTORS];
+        int32_t points = 0;
+        CHECK(armour_roadmap_create_host(&robot, 3, three.data(), 3, edges, nullptr, 0.1, &rm));
+        CHECK(armour_roadmap_check_moving_host(rm, 1, 2, box, vel, from, early, nf, ef, cl));
+        CHECK(armour_roadmap_plan(rm, 0, three.data(), three.data() + n, 2, 5, path, &points));
+        if (!ef[0] || points != 2) { printf("FAILED: window [0, 1]: edge %d, %d points\n", ef[0], points); return 1; }
+        CHECK(armour_roadmap_check_moving_host(rm, 1, 2, box, vel, from, late, nf, ef, nullptr));
+        CHECK(armour_roadmap_plan(rm, 0, three.data(), three.data() + n, 2, 5, path, &points));
+        if (ef[0] || points == 2) { printf("FAILED: window [0, 3]: edge %d, %d points\n", ef[0], points); return 1; }
+        if (armour_roadmap_check_moving_host(rm, 1, 2, box, vel, late, from, nf, ef, nullptr) != ARMOUR_EINVAL ||
+            armour_roadmap_check_moving_host(rm, 1, 2, box, nullptr, from, late, nf, ef, nullptr) != ARMOUR_EINVAL) {
+            printf("FAILED: a bad window or a null velocity passed\n");
+            return 1;
+        }
+        armour_roadmap_destroy(rm);
+    }
     // the descend walk on a chain 4 -> 3 -> 2 -> 1 -> 0 -> goal, joined at 4 (far) and 2 (near), and on successors that never arrive
     const double cost[5] = {1.0, 2.0, 3.0, 4.0, 5.0};
     const int32_t next[5] = {ARMOUR_ROADMAP_NEXT_GOAL, 0, 1, 2, 3}, loop[5] = {1, 0, 1, 2, 3};
@@ -83,6 +112,6 @@ int main() {
         printf("FAILED: the empty join or the walk without an end\n");
         return 1;
     }
-    printf("knn host check ok: %d result lists equal a plain sort, the walk gives 2 1 0 and refuses a cycle\n", checked);
+    printf("knn host check ok: %d result lists equal a plain sort, the window rule frees and blocks the edge, the walk gives 2 1 0 and refuses a cycle\n", checked);
     return 0;
 }

@@ -1,6 +1,7 @@
 """Moving obstacles measured (armour_set_problems_moving, armour_path_audit_moving); writes profiles/moving_bench.json.
 
   python tools/moving_bench.py [--parent-lib PATH] [--rounds 3] [--out profiles/moving_bench.json]
+  python tools/moving_bench.py --roadmap [--parent-lib PATH] [--rounds 3] [--out profiles/moving_roadmap_bench.json]
 
   static build    wall ms of set_parameters and the device ms of its kernels, B = 1 and B = 128, O = 20, T = 100; with --parent-lib (a libarmour_hip.so
                   of the parent commit) the parent's library and this one alternate, a fresh process per run (the library is chosen by
@@ -11,6 +12,14 @@
                   device events around 40 asynchronous evaluations on one stream, after 5 warm-up calls.
   audit           items/s of armour_path_audit_moving against armour_path_audit on the same random pieces over the reference's worlds (median
                   device ms of 10 launches, verdict and clearance mode, steps 0.01 and 0.002).
+
+--roadmap measures the roadmap's window rule instead (armour_roadmap_check_moving) and writes profiles/moving_roadmap_bench.json:
+  static check    kernel ms (median of 10 launches) of armour_roadmap_check on the two roadmaps tools/roadmap_bench.py measures (20 000 nodes, radius
+                  0.3 and 1.5, edge step 0.05; the edges by roadmap.device_roadmap, which equal uniform_roadmap's) against the 107 reference worlds
+                  and the first alone; with --parent-lib the parent's library and this one alternate as above, and the parent's spread is taken the
+                  same way.
+  moving check    the same launches of armour_roadmap_check_moving on the window [0, 1] at zero velocity and at 0.2 .. 1.0 m/s, in checks/s beside
+                  the static column of the same process, with the free nodes and edges each form finds.
 
 Every run needs the GPU; without one the tool fails."""
 import argparse
@@ -131,6 +140,79 @@ def worker_audit(P=4096, launches=10):
     return out
 
 
+ROADMAPS = (("radius_0.3", 0.3), ("radius_1.5", 1.5))
+
+
+def worker_roadmap(moving, N=20000, k_max=16, edge_step=0.05, launches=10):
+    """Per roadmap and W: kernel ms and checks/s of the static check (and, where the library has the entry, of the moving check at v = 0 and at 0.2 .. 1.0 m/s)."""
+    from armour_amd.planner import kinova_robot
+    from armour_amd.roadmap import Roadmap, device_roadmap
+    from armour_amd.scenes import as_batch, reference_worlds
+    robot = kinova_robot()
+    n = robot.num_factors
+    cont = np.array(robot.continuous[:n]).astype(bool)
+    lb, ub = np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n])
+    obs = np.ascontiguousarray(as_batch(reference_worlds())["obstacles"])
+    vel = _velocity(10, obs.shape[:2])
+    out = {}
+    for key, radius in ROADMAPS:
+        nodes, edges = device_roadmap(robot, N, radius, k_max, 0, lb, ub, cont)
+        rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8), edge_step=edge_step)
+        row = dict(N=rm.N, E=rm.E, edge_samples=rm.edge_samples, O=int(obs.shape[1]))
+        for W in (obs.shape[0], 1):
+            kinds = [("static", lambda: rm.check(obs[:W]))]
+            if moving:
+                kinds += [("moving_zero_velocity", lambda: rm.check_moving(obs[:W], np.zeros_like(vel[:W]), 0.0, 1.0)),
+                          ("moving", lambda: rm.check_moving(obs[:W], vel[:W], 0.0, 1.0))]
+            items = (rm.N + rm.edge_samples) * W
+            cell = dict(items=items)
+            for kind, call in kinds:
+                runs = [call() for _ in range(launches + 2)][2:]
+                ms = _median([r["ms"] for r in runs])
+                cell[kind] = dict(kernel_ms=ms, checks_per_s=items / (ms * 1e-3), free_nodes=int(runs[-1]["node_free"].sum()), free_edges=int(runs[-1]["edge_free"].sum()))
+            if moving:
+                cell["moving_zero_velocity_over_static"] = cell["moving_zero_velocity"]["checks_per_s"] / cell["static"]["checks_per_s"]
+                cell["moving_over_static"] = cell["moving"]["checks_per_s"] / cell["static"]["checks_per_s"]
+            row[f"W={W}"] = cell
+        rm.close()
+        out[key] = row
+    return out
+
+
+def main_roadmap(a):
+    runs = {"parent": [], "new": []}
+    for _ in range(a.rounds):
+        if a.parent_lib:
+            runs["parent"].append(_child("roadmap_static", os.path.abspath(a.parent_lib)))
+        runs["new"].append(_child("roadmap"))
+    doc = dict(what="tools/moving_bench.py --roadmap on one MI355X in one visit (see the tool's docstring): kernel ms are medians of 10 launches per process, "
+                    "the lists hold one entry per round; window [0, 1], velocities of 0.2 .. 1.0 m/s.", rounds=a.rounds)
+    for key, _ in ROADMAPS:
+        last = runs["new"][-1][key]
+        row = {k: last[k] for k in ("N", "E", "edge_samples", "O")}
+        for W in [k for k in last if k.startswith("W=")]:
+            new = [r[key][W]["static"]["kernel_ms"] for r in runs["new"]]
+            cell = dict(items=last[W]["items"], static_new_kernel_ms=new, static_new_median=_median(new))
+            if runs["parent"]:
+                par = [r[key][W]["static"]["kernel_ms"] for r in runs["parent"]]
+                cell.update(static_parent_kernel_ms=par, static_parent_median=_median(par), parent_spread=max(par) - min(par),
+                            new_over_parent=_median(new) / _median(par), within_parent_spread=bool(_median(new) <= _median(par) + (max(par) - min(par))))
+            for kind in ("static", "moving_zero_velocity", "moving"):
+                cell[kind] = dict(kernel_ms=_median([r[key][W][kind]["kernel_ms"] for r in runs["new"]]),
+                                  checks_per_s=_median([r[key][W][kind]["checks_per_s"] for r in runs["new"]]),
+                                  free_nodes=last[W][kind]["free_nodes"], free_edges=last[W][kind]["free_edges"])
+            cell["moving_zero_velocity_over_static"] = _median([r[key][W]["moving_zero_velocity_over_static"] for r in runs["new"]])
+            cell["moving_over_static"] = _median([r[key][W]["moving_over_static"] for r in runs["new"]])
+            row[W] = cell
+        doc[key] = row
+    out = a.out or os.path.join(ROOT, "profiles", "moving_roadmap_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc, indent=1))
+
+
 def _child(what, lib=None):
     env = dict(os.environ)
     if lib:
@@ -146,15 +228,20 @@ def main():
     ap.add_argument("--worker")
     ap.add_argument("--parent-lib")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "moving_bench.json"))
+    ap.add_argument("--roadmap", action="store_true")
+    ap.add_argument("--out")
     a = ap.parse_args()
     if a.worker:
         from armour_amd import _lib
         if not _lib.load().armour_device_available():
             raise SystemExit("moving_bench: no HIP device visible (nothing here can be measured without one)")
-        res = {"build_static": lambda: worker_build(False), "build": lambda: worker_build(True), "eval": worker_eval, "audit": worker_audit}[a.worker]()
+        res = {"build_static": lambda: worker_build(False), "build": lambda: worker_build(True), "eval": worker_eval, "audit": worker_audit,
+               "roadmap_static": lambda: worker_roadmap(False), "roadmap": lambda: worker_roadmap(True)}[a.worker]()
         print(json.dumps(res))
         return
+    if a.roadmap:
+        return main_roadmap(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "moving_bench.json")
     runs = {"parent": [], "new": []}
     for _ in range(a.rounds):
         if a.parent_lib:

@@ -28,6 +28,11 @@ and prints ONE JSON line.
   `hlp_outcomes_workspace` holds the outcome counts beside
   the straight-line run's, the worlds whose outcome differs, how many waypoints fell back to the goal configuration and `ms_per_batch`.  The
   sections of the other planners that profiles/trial_bench.json already holds are kept;
+* --moving: a run of its own that writes profiles/trial_moving_bench.json and leaves profiles/trial_bench.json alone: the same worlds with every
+  obstacle in linear motion (seeded velocities, --moving-seed, speeds --moving-speed LO HI in m/s; run_trials(velocities=...)) under the
+  straight-line planner and under armour_amd.roadmap.moving_field_hlps (device_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0): one
+  check_moving, one field and one descend_many per iteration): outcome counts of both, `struck_at_rest` among them, the pieces by kind and
+  verdict, and hlp / build / solve / audit ms per batch iteration.  Records, not pass criteria;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -112,6 +117,34 @@ def roadmap_field_trials(robot, ws, straight, a):
                 changed={w["name"]: [s["outcome"], w["outcome"]] for s, w in zip(straight["worlds"], res["worlds"]) if s["outcome"] != w["outcome"]})
 
 
+def moving_trials(robot, ws, a):
+    """The worlds with moving obstacles under the straight-line planner and under moving_field_hlps: outcomes, pieces by kind and verdict, ms per batch."""
+    from armour_amd.roadmap import Roadmap, device_roadmap, moving_field_hlps
+    from armour_amd.trials import OUTCOMES, STRUCK_OUTCOME, run_trials
+    n = robot.num_factors
+    cont = np.array(robot.continuous[:n]).astype(bool)
+    lo, hi = a.moving_speed
+    vel = []
+    for i, (_, p) in enumerate(ws):
+        rng = np.random.default_rng([a.moving_seed, i])
+        v = rng.normal(size=(np.asarray(p["obstacles"]).reshape(-1, 12).shape[0], 3))
+        vel.append(v / np.linalg.norm(v, axis=-1, keepdims=True) * rng.uniform(lo, hi, (v.shape[0], 1)))
+    nodes, edges = device_roadmap(robot, a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
+    rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
+    out = dict(tool="trial_bench --moving", T=a.T, worlds=len(ws), max_iterations=a.max_iterations, seed=a.moving_seed, speed=[lo, hi],
+               roadmap=dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius))
+    for key, hlp in (("straight", "straight"), ("moving_field", moving_field_hlps(rm, ws, vel))):
+        res = run_trials(ws, hlp=hlp, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0], velocities=vel)
+        recs = [r for w in res["worlds"] for r in w["records"]]
+        per_batch = lambda k: dict(mean=float(np.mean([b[k] for b in res["batches"]])), max=float(np.max([b[k] for b in res["batches"]])))
+        out[key] = dict(outcomes={o: sum(1 for w in res["worlds"] if w["outcome"] == o) for o in OUTCOMES + (STRUCK_OUTCOME,)}, summary=res["summary"],
+                        pieces={kind: {str(v): sum(1 for r in recs if r["executed"] == kind and r["audit_verdict"] == v) for v in (0, 1, 2)}
+                                for kind in ("plan", "brake", "stay")},
+                        ms_per_batch={k: per_batch(k) for k in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0])
+    rm.close()
+    return out
+
+
 def tree_trials(robot, ws, straight, a):
     """The worlds once more under tree_hlps; outcome counts under both HLPs and the worlds that end differently."""
     from armour_amd.tree_planner import tree_hlps
@@ -175,6 +208,9 @@ def main():
     ap.add_argument("--roadmap-nodes", type=int, default=20000)
     ap.add_argument("--roadmap-radius", type=float, default=1.5)
     ap.add_argument("--batched", action="store_true")
+    ap.add_argument("--moving", action="store_true")
+    ap.add_argument("--moving-seed", type=int, default=2)
+    ap.add_argument("--moving-speed", type=float, nargs=2, default=[0.05, 0.2])
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
@@ -186,6 +222,13 @@ def main():
     from armour_amd.trials import run_trials
     robot = kinova_robot()
     ws = scenes.reference_worlds()
+    if a.moving:
+        out = moving_trials(robot, ws, a)
+        with open(os.path.join(ROOT, "profiles", "trial_moving_bench.json"), "w") as f:
+            json.dump(out, f, indent=1, default=float)
+            f.write("\n")
+        print(json.dumps(out, default=float))
+        return
     res = run_trials(ws, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0])
     s = res["summary"]
     its = np.array([w["iterations"] for w in res["worlds"]])
