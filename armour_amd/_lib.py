@@ -194,6 +194,7 @@ EXPORTS = [
     "armour_roadmap_use_self", "armour_path_audit_self", "armour_path_audit_self_host",
     "armour_roadmap_field", "armour_roadmap_descend",
     "armour_roadmap_check_moving", "armour_roadmap_check_moving_host",
+    "armour_roadmap_check_slices", "armour_roadmap_check_slices_host", "armour_roadmap_arrival", "armour_roadmap_arrival_host",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
@@ -338,6 +339,14 @@ def load():
     if hasattr(L, "armour_roadmap_check_moving"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
         L.armour_roadmap_check_moving.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, u8p, u8p, dp, dp]
         L.armour_roadmap_check_moving_host.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, u8p, u8p, dp]
+    if hasattr(L, "armour_roadmap_check_slices"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        u64p = C.POINTER(C.c_uint64)
+        slices = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_double, C.c_int32, C.c_int32, ip, dp, dp, u64p, u64p, u64p, dp]
+        arrival = [vp, C.c_double, C.c_int32, ip, ip, ip, dp, u64p, u64p, u64p, u64p, ip, ip, ip, ip, ip]
+        L.armour_roadmap_check_slices.argtypes = slices + [dp]
+        L.armour_roadmap_check_slices_host.argtypes = slices
+        L.armour_roadmap_arrival.argtypes = arrival + [dp]
+        L.armour_roadmap_arrival_host.argtypes = arrival
     L.armour_roadmap_plan.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, ip]
     L.armour_roadmap_field.argtypes = [vp, dp, C.c_int32, dp, ip, ip, ip, dp]
     L.armour_roadmap_descend.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_int32, dp, ip, dp]

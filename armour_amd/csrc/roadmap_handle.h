@@ -89,6 +89,22 @@ struct ArmourRoadmap {
     DevBuf<double> d_kq, d_kdist, d_pdist, d_ktarget, d_self_shrink;
     DevBuf<int32_t> d_kmask, d_kexcl, d_kidx, d_kcount, d_pidx, d_pcount;
     DevBuf<uint8_t> d_self_node_free, d_self_on, d_kok;
+    // the time slices (armour_roadmap_check_slices / armour_roadmap_arrival, roadmap_slices.hip): state of their own, beside the last check's.
+    // sl_W < 0: no sliced check yet.  The device keeps the tables of a device handle; the host keeps them on a host handle, and on a device
+    // handle when the caller asked for them (sl_on_host).
+    int32_t sl_W = -1, sl_O = 0, sl_K = 0;
+    double sl_dt = 0.0;
+    bool sl_on_host = false;
+    std::vector<double> sl_t0;                      // [W]
+    std::vector<uint64_t> sl_node, sl_edge;         // [W][N], [W][E]
+    DevBuf<uint64_t> d_sl_node, d_sl_edge, d_sl_extra, d_sl_reach, d_sl_xmask, d_sl_ends;
+    DevBuf<double> d_sl_obs, d_sl_vel, d_sl_mid, d_sl_half, d_sl_xq;
+    DevBuf<int32_t> d_sl_xitem, d_sl_xoff, d_sl_row_off, d_sl_col, d_sl_eid, d_sl_steps, d_sl_xu, d_sl_xv, d_sl_xsteps, d_sl_out, d_sl_path, d_sl_status;
+    // the roadmap's edge lengths and CSR rows in the field's order (neighbour ascending, then edge id), built on first use; on the device
+    // as well (d_sl_row_off / d_sl_col / d_sl_eid) once sl_csr_on_device
+    bool sl_csr_ready = false, sl_csr_on_device = false;
+    std::vector<double> sl_len;                     // [E]
+    std::vector<int32_t> sl_row_off, sl_col, sl_eid;
 };
 
 // ---- what armour_roadmap_plan (roadmap.hip) and the field entries (roadmap_field.hip) share; defined in roadmap.hip

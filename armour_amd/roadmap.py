@@ -16,6 +16,10 @@ configurations + an adjacency list in, node feasibility / link_c / the collision
     paths = rm.descend_many(worlds, starts)                 # descend() for Q queries with one device call
     v = rm.check_moving(obstacles, velocity, t_from, t_to)  # check() against obstacles in linear motion over a time window per world
     res = run_trials(worlds, hlp=moving_field_hlps(rm, worlds, velocities), velocities=velocities)   # whole trials in moving worlds
+    s = rm.check_slices(obstacles, velocity, t0, dt, K)     # the window rule on K consecutive slices of every world's clock, one launch
+    a = rm.arrival(step_len, ...)                           # earliest arrival over (node, slice) states of those tables, waiting allowed
+    plans = rm.plan_slices(starts, goals, obstacles, velocity, t0, dt, K, speed)   # knn + check_slices + arrival -> timed polylines
+    res = run_trials(worlds, hlp=spacetime_hlps(rm, worlds, velocities, speed), velocities=velocities)
 
 The node and edge rules (exact node test, conservative edge test with enlarged boxes) are stated in include/armour_hip.h and DESIGN.md.
 """
@@ -207,6 +211,131 @@ class Roadmap:
         check(self.L.armour_roadmap_descend(self.h, int(w), _dp(s), int(connect_k), cap, _dp(path), C.byref(pts), C.byref(length)))
         return (path[:pts.value].copy() if pts.value else None), length.value
 
+
+    def check_slices(self, obstacles, velocity, t0, dt, K, extra_world=None, extra_a=None, extra_b=None, host=False, tables=True):
+        """The window rule of check_moving on K <= 64 consecutive slices [t0[w] + k dt, t0[w] + (k + 1) dt] of every world's clock in one
+        launch (armour_roadmap_check_slices): obstacles [W,O,12] / velocity [W,O,3] as check_moving takes them, t0 [W] (or a scalar).  Extra
+        edges: extra_world [Q], extra_a / extra_b [Q,n], judged by the edge rule in their world (a == b: the node rule).  Returns dict
+        node_slices [W,N] uint64, edge_slices [W,E] uint64 (bit k: free in slice k; None with tables=False, which leaves them on the device
+        for arrival()), extra_slices [Q] uint64, slice_times [W,K+1], ms.  The last check's state (plan, field, descend) is untouched.
+        host=True: the library's host loop, on a Roadmap(host=True)."""
+        obs, W, O = _lib.as_worlds(obstacles)
+        vel = np.ascontiguousarray(np.asarray(velocity, dtype=np.float64).reshape(W, O, 3))
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(t0, dtype=np.float64), (W,)))
+        K = int(K)
+        if extra_world is None:
+            Q, xw, xa, xb = 0, None, None, None
+        else:
+            xa = np.ascontiguousarray(extra_a, dtype=np.float64).reshape(-1, self.n)
+            xb = np.ascontiguousarray(extra_b, dtype=np.float64).reshape(-1, self.n)
+            Q = xa.shape[0]
+            xw = np.ascontiguousarray(np.broadcast_to(np.asarray(extra_world, dtype=np.int32), (Q,)))
+            if xb.shape[0] != Q:
+                raise ValueError("Roadmap.check_slices: extra_a and extra_b differ in length")
+        keep = tables or host
+        ns = np.zeros((W, self.N), dtype=np.uint64) if keep else None
+        es = np.zeros((W, self.E), dtype=np.uint64) if keep else None
+        xs = np.zeros(Q, dtype=np.uint64)
+        times = np.zeros((W, max(K, 0) + 1))
+        ms = C.c_double(0.0)
+        u64, i32 = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+        p64 = lambda a: None if a is None else a.ctypes.data_as(u64)
+        args = (self.h, W, O, _dp(obs) if obs.size else None, _dp(vel) if vel.size else None, _dp(t), float(dt), K, Q,
+                None if xw is None else xw.ctypes.data_as(i32), _dp(xa), _dp(xb), p64(ns), p64(es), p64(xs), _dp(times))
+        check(self.L.armour_roadmap_check_slices_host(*args) if host else self.L.armour_roadmap_check_slices(*args, C.byref(ms)))
+        self.slices_W, self.slices_K = W, K
+        return dict(node_slices=ns, edge_slices=es, extra_slices=xs, slice_times=times, ms=ms.value)
+
+    def arrival(self, step_len, start_mask, goal_mask, x_world=None, x_u=None, x_v=None, x_len=None, x_mask=None, host=False, reach=True):
+        """Earliest arrival over (node, slice) states of the last check_slices (armour_roadmap_arrival), all its worlds in one launch: node N
+        is the start with mask start_mask[w] | 1, node N + 1 the goal with mask goal_mask[w]; the extra edges (x_world sorted, x_u / x_v in
+        [0, N + 2), x_len in radians, x_mask) join them to the roadmap; an edge of length len takes max(1, ceil(len / step_len)) slices and
+        every slice of a traversal must be free; waiting at a node is allowed while it stays free.  Returns dict reach [W,N+2] uint64 (None
+        with reach=False), goal_slice [W] (-1: not reached within the slices), path_len [W], path_node / path_slice [W,64] (-1 padded: the
+        visits from the start on, a node with the slice at which it is reached, the start with the slice at which it is left), sweeps [W],
+        ms.  host=True: the library's host loop after check_slices(host=True)."""
+        W = getattr(self, "slices_W", None)
+        if W is None:           # no sliced check to take W from: the library says so (ESTATE)
+            check(self.L.armour_roadmap_arrival_host(self.h, float(step_len), 0, *([None] * 13)) if host else
+                  self.L.armour_roadmap_arrival(self.h, float(step_len), 0, *([None] * 14)))
+            raise RuntimeError("armour_roadmap_arrival accepted a roadmap without a sliced check")
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(start_mask, dtype=np.uint64), (W,)))
+        gm = np.ascontiguousarray(np.broadcast_to(np.asarray(goal_mask, dtype=np.uint64), (W,)))
+        i32, u64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        if x_world is None:
+            X, xw, xu, xv, xl, xm = 0, None, None, None, None, None
+        else:
+            xw, xu, xv = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (x_world, x_u, x_v))
+            xl = np.ascontiguousarray(x_len, dtype=np.float64).reshape(-1)
+            xm = np.ascontiguousarray(x_mask, dtype=np.uint64).reshape(-1)
+            X = xw.size
+            if not (xu.size == xv.size == xl.size == xm.size == X):
+                raise ValueError("Roadmap.arrival: the extra edges' arrays differ in length")
+        ip = lambda a: None if a is None else a.ctypes.data_as(i32)
+        up = lambda a: None if a is None else a.ctypes.data_as(u64)
+        rows = np.zeros((W, self.N + 2), dtype=np.uint64) if reach else None
+        goal_slice, path_len, sweeps = (np.zeros(W, dtype=np.int32) for _ in range(3))
+        path_node, path_slice = np.full((W, 64), -1, dtype=np.int32), np.full((W, 64), -1, dtype=np.int32)
+        ms = C.c_double(0.0)
+        args = (self.h, float(step_len), X, ip(xw), ip(xu), ip(xv), _dp(xl), up(xm), up(sm), up(gm), up(rows), ip(goal_slice), ip(path_len), ip(path_node),
+                ip(path_slice), ip(sweeps))
+        check(self.L.armour_roadmap_arrival_host(*args) if host else self.L.armour_roadmap_arrival(*args, C.byref(ms)))
+        return dict(reach=rows, goal_slice=goal_slice, path_len=path_len, path_node=path_node, path_slice=path_slice, sweeps=sweeps, ms=ms.value)
+
+    def plan_slices(self, starts, goals, obstacles, velocity, t0, dt, K, speed, connect_k=8, host=False):
+        """Timed paths through moving worlds, one per world: starts / goals [W,n], the worlds as check_slices takes them, `speed` the arm's
+        nominal joint-space speed in rad/s (an edge of length len takes max(1, ceil(len / (speed dt))) slices).  Four steps: ONE knn of all
+        starts and goals with no mask; ONE check_slices whose extra edges are start -> node and goal -> node for the connect_k nearest,
+        start -> goal, and the degenerate edges start -> start and goal -> goal for the two masks; ONE arrival; then per world the timed
+        polyline.  Returns a list of W dicts: path [P,n] (start, nodes..., goal; None when the goal is not reached within the K slices),
+        node [P] (N: the start, N + 1: the goal), slice [P], time [P] (slice_times at those slices: when each point is reached, for the
+        start when it is left), goal_slice; and keeps the raw results in self.last_slices / self.last_arrival."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, self.n)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, self.n)
+        W, N, k = s.shape[0], self.N, min(int(connect_k), self.N)
+        if g.shape[0] != W:
+            raise ValueError("Roadmap.plan_slices: one goal per start")
+        if k > 0:
+            index, dist, count = self.knn(np.concatenate([s, g]), k, host=host)
+        else:
+            index, dist, count = np.zeros((2 * W, 0), dtype=np.int32), np.zeros((2 * W, 0)), np.zeros(2 * W, dtype=np.int32)
+        per = 2 * k + 3                                  # a world's extra edges: k from the start, k from the goal, start -> goal, the two masks
+        cont = self.continuous.astype(bool)
+        xw = np.repeat(np.arange(W, dtype=np.int32), per)
+        xa, xb = np.zeros((W * per, self.n)), np.zeros((W * per, self.n))
+        xu, xv, xl = np.zeros(W * per, dtype=np.int32), np.zeros(W * per, dtype=np.int32), np.zeros(W * per)
+        used = np.zeros(W * per, dtype=bool)
+        for w in range(W):
+            base = w * per
+            for side, (q, end) in enumerate(((s[w], N), (g[w], N + 1))):
+                for c in range(int(count[side * W + w])):
+                    i = base + side * k + c
+                    v = int(index[side * W + w, c])
+                    xa[i], xb[i], xu[i], xv[i], xl[i], used[i] = q, self.nodes[v], end, v, dist[side * W + w, c], True
+                for c in range(int(count[side * W + w]), k):     # (fewer than k nodes: a slot that joins nothing, judged and dropped)
+                    xa[base + side * k + c] = xb[base + side * k + c] = q
+            i = base + 2 * k
+            xa[i], xb[i], xu[i], xv[i], used[i] = s[w], g[w], N, N + 1, True
+            d = wrapped_diff(s[w], g[w], cont)
+            xl[i] = np.sqrt((d * d).sum())
+            xa[i + 1] = xb[i + 1] = s[w]
+            xa[i + 2] = xb[i + 2] = g[w]
+        sl = self.check_slices(obstacles, velocity, t0, dt, K, extra_world=xw, extra_a=xa, extra_b=xb, host=host, tables=False)
+        xm = sl["extra_slices"]
+        masks = xm.reshape(W, per)
+        ar = self.arrival(float(speed) * float(dt), masks[:, 2 * k + 1], masks[:, 2 * k + 2], x_world=xw[used], x_u=xu[used], x_v=xv[used], x_len=xl[used],
+                          x_mask=xm[used], host=host, reach=False)
+        self.last_slices, self.last_arrival = sl, ar
+        out = []
+        for w in range(W):
+            P = int(ar["path_len"][w])
+            if P == 0:
+                out.append(dict(path=None, node=None, slice=None, time=None, goal_slice=int(ar["goal_slice"][w])))
+                continue
+            node, sli = ar["path_node"][w, :P].copy(), ar["path_slice"][w, :P].copy()
+            pts = np.stack([s[w] if v == N else g[w] if v == N + 1 else self.nodes[v] for v in node])
+            out.append(dict(path=pts, node=node, slice=sli, time=sl["slice_times"][w, sli], goal_slice=int(ar["goal_slice"][w])))
+        return out
 
     def knn(self, queries, k, radius=np.inf, worlds=None, exclude=None, host=False):
         """queries [Q,n] -> (index [Q,k] int32, dist [Q,k], count [Q]): each query's first k candidates in the order (wrapped distance, node
@@ -428,6 +557,82 @@ def moving_field_hlps(roadmap, worlds, velocities, horizon=None, connect_k=8):
                 for i, q, la, (path, _) in zip(indices, qs, lookaheads, paths)]
 
     make.last_check = None
+    make.set_world_times = set_world_times
+    make.get_waypoints = get_waypoints
+    return make
+
+
+def spacetime_hlps(roadmap, worlds, velocities, speed, dt=0.25, K=32, connect_k=8):
+    """moving_field_hlps with a search over (node, time slice) states in place of one window per world: `worlds` and `velocities` as
+    moving_field_hlps takes them, `speed` the arm's nominal joint-space speed in rad/s.  The factory carries set_world_times(t_world [W]),
+    which run_trials(velocities=...) calls before every waypoint query, and get_waypoints(indices, qs, lookaheads), which does per call ONE
+    Roadmap.plan_slices of all W worlds from the worlds' current configurations at the worlds' clocks (K slices of dt seconds ahead).
+    Waypoint rule: the polyline is the current configuration followed by the path's nodes up to the first node at which the path waits at
+    least one planning period (planner.default_params t_plan), or up to the goal; when that wait is at the start itself the waypoint is the
+    current configuration (stand still: "wait until the box has passed"), otherwise waypoint_along(polyline, q, lookahead); with no path
+    within the K slices it falls back to the straight-line waypoint, as field_hlps does.  The search only proposes waypoints: safety rests on
+    the solver's tables and the moving audit.  `speed`, dt = 0.25 and K = 32 are starting values that nobody has tuned.  Worlds that have
+    finished keep their last clock and configuration.  The factory's last_check is the dict the last check_slices returned, last_plans the
+    list plan_slices returned (None before the first call)."""
+    probs = [p for _, p in worlds]
+    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for p in probs]
+    vel = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
+    if len(vel) != len(obs) or any(v.shape[0] != o.shape[0] for v, o in zip(vel, obs)):
+        raise ValueError("spacetime_hlps: one velocity per obstacle of every world")
+    O = max([o.shape[0] for o in obs] + [1])
+    obs_p = np.stack([pad_obstacles(o, O) for o in obs])
+    vel_p = np.stack([np.concatenate([v, np.zeros((O - v.shape[0], 3))]) for v in vel])
+    goals = np.stack([np.asarray(p["goal"], dtype=np.float64) for p in probs])
+    from .planner import default_params
+    period = float(default_params(1).t_plan)
+    step_len = float(speed) * float(dt)
+    state = dict(t_world=np.zeros(len(probs)), q=np.stack([np.asarray(p["q0"], dtype=np.float64) for p in probs]))
+
+    class _One:
+        """One world's view of the factory, for a caller that asks world by world: each question is a get_waypoints of its own."""
+
+        def __init__(self, i):
+            self.i = int(i)
+
+        def get_waypoint(self, q_cur, lookahead):
+            return get_waypoints([self.i], [np.asarray(q_cur, dtype=np.float64)], [lookahead])[0]
+
+    def make(i, world):
+        return _One(i)
+
+    def set_world_times(t_world):
+        state["t_world"] = np.array(np.broadcast_to(np.asarray(t_world, dtype=np.float64), (len(probs),)))
+
+    def hop_slices(a, b):
+        d = wrapped_diff(a, b, cont)
+        return max(1, int(np.ceil(np.sqrt((d * d).sum()) / step_len)))
+
+    def get_waypoints(indices, qs, lookaheads):
+        for i, q in zip(indices, qs):
+            state["q"][i] = np.asarray(q, dtype=np.float64)
+        plans = roadmap.plan_slices(state["q"], goals, obs_p, vel_p, state["t_world"], dt, K, speed, connect_k=connect_k)
+        make.last_check, make.last_plans = roadmap.last_slices, plans
+        out = []
+        for i, q, la in zip(indices, qs, lookaheads):
+            plan = plans[i]
+            if plan["path"] is None:
+                out.append(straight_line_waypoint(q, goals[i], la))
+                continue
+            path, sli = plan["path"], plan["slice"]
+            if sli[0] * float(dt) >= period:             # the path leaves the start a planning period from now, or later
+                out.append(np.array(q, dtype=np.float64))
+                continue
+            last = 1
+            while last < path.shape[0] - 1:              # the wait at path[last]: from its arrival to the departure of the next hop
+                leave = sli[last + 1] - hop_slices(path[last], path[last + 1])
+                if (leave - sli[last]) * float(dt) >= period:
+                    break
+                last += 1
+            out.append(waypoint_along(path[:last + 1], q, la, cont))
+        return out
+
+    cont = roadmap.continuous.astype(bool)
+    make.last_check = make.last_plans = None
     make.set_world_times = set_world_times
     make.get_waypoints = get_waypoints
     return make

@@ -867,6 +867,67 @@ int armour_roadmap_connect_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* wo
 int armour_roadmap_descend_batch(ArmourRoadmap* rm, int32_t Q, const int32_t* world, const double* q_start, int32_t connect_k,
                                  int32_t seq_capacity, int32_t* seq_off, int32_t* seq, uint8_t* status, double* length);
 
+/* Time slices (roadmap_slices.hip): the window rule of armour_roadmap_check_moving on K consecutive windows of every world's clock in ONE
+ * launch, and an earliest-arrival search over (node, slice) states on the result.  DESIGN.md 4.16a.
+ *
+ * Slices.  The boundaries of world w are t_k = t0[w] + (double)k * dt, k = 0..K, computed once on the host and returned in slice_times
+ *   [W][K + 1].  Slice k is the window [t_k, t_k+1]; the host computes mid_k = 0.5 * (t_k + t_k+1) and half_k = 0.5 * (t_k+1 - t_k) from those
+ *   doubles and hands [W][K] of each to the kernel, so the device, the host twin and armour_roadmap_check_moving on
+ *   (slice_times[w][k], slice_times[w][k + 1]) judge by the same numbers.
+ * Outputs, each may be NULL.  Bit k of node_slices[w][v] is node_free[w][v] of armour_roadmap_check_moving on slice k, bit k of
+ *   edge_slices[w][e] is edge_free[w][e] on it; bits >= K are 0.  There is no clearance.  Extra edge i (Q of them; Q = 0 with null arrays
+ *   is allowed) joins extra_a[i] to extra_b[i] ([Q][n]) in world extra_world[i] and is judged by the edge rule with the handle's edge_step:
+ *   extra_slices[i].  a == b gives S = 1 and r = 0, the node rule on that configuration.  *ms: device time of the launches.
+ * State.  The handle keeps the slice tables with their W, O, K, dt and t0 as state of their own, on the device (and on the host when both
+ *   node_slices and edge_slices were asked for); the last check's masks, obstacles, windows and field are not touched, so
+ *   armour_roadmap_plan and armour_roadmap_descend answer after a sliced check as before it.  The self masks are not read.
+ * Device.  A block serves one world (obstacles, mid and half in LDS: 248 B per obstacle + 16 B per slice, 63 KB at both caps); a lane is a
+ *   node, an edge sub-segment or an extra sub-segment, walks its links once and keeps the slices still free in a 64-bit mask.
+ * ARMOUR_EINVAL before a device is touched: armour_roadmap_check_moving's refusals (t0 in place of the windows); K < 1 or
+ *   K > ARMOUR_ROADMAP_SLICES_MAX; dt not finite or <= 0, or a last boundary that is not finite; Q < 0 or a null extra array with Q > 0; an
+ *   extra_world outside [0, W); an extra configuration that is not finite.
+ * armour_roadmap_check_slices_host: the same function in a host loop, for a handle of armour_roadmap_create_host (any other: ARMOUR_EINVAL). */
+#define ARMOUR_ROADMAP_SLICES_MAX 64
+int armour_roadmap_check_slices(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                const double* t0, double dt, int32_t K, int32_t Q, const int32_t* extra_world, const double* extra_a,
+                                const double* extra_b, uint64_t* node_slices, uint64_t* edge_slices, uint64_t* extra_slices,
+                                double* slice_times, double* ms);
+int armour_roadmap_check_slices_host(ArmourRoadmap* rm, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                     const double* t0, double dt, int32_t K, int32_t Q, const int32_t* extra_world, const double* extra_a,
+                                     const double* extra_b, uint64_t* node_slices, uint64_t* edge_slices, uint64_t* extra_slices,
+                                     double* slice_times);
+/* Earliest arrival over the slice tables of the last armour_roadmap_check_slices, all W worlds in one launch.
+ *
+ * Graph of world w: the roadmap's N nodes with mask node_slices[w][v]; node N, the start, with mask start_mask[w] | 1 (the arm is where it
+ *   is in slice 0); node N + 1, the goal, with mask goal_mask[w]; the roadmap's edges with edge_slices[w][e]; and the world's extra edges
+ *   (x_u, x_v, x_len, x_mask)[i], X in all, sorted by x_world, ends in [0, N + 2).  Only the low K bits of a mask given here are read.
+ * Steps: steps(len) = max(1, ceil(len / step_len)), step_len in radians (nominal speed x dt), evaluated on the host for the roadmap's edge
+ *   lengths (armour_roadmap_field's len[e]) and for x_len; the device sees int32.  An edge with steps > K is unusable.
+ * Operators on 64-bit masks (no implementation shifts by 64): avail(m, c) = AND over i < c of (m >> i) -- every slice of a traversal is free;
+ *   fill(x, m) = the least y that holds x & m with ((y << 1) & m) inside y -- waiting at a node while it stays free.
+ * reach [W][N + 2] is the LEAST family of masks with reach[N] holding fill(1, start_mask | 1), every reach[v] closed under fill(., mask[v]),
+ *   and for every usable edge (u, v) of c steps and mask m, in both directions, reach[v] holding ((reach[u] & avail(m, c)) << c) & mask[v].
+ *   All operators are monotone on a finite lattice: the least fixed point is unique and any in-place sweep order ends at it.  A move
+ *   advances the slice, so sweeps that close the waits end within K + 1 sweeps; more is ARMOUR_ESTATE.
+ * goal_slice[w]: the lowest set bit of reach[N + 1], -1 if none.
+ * Path: the backward walk from (N + 1, goal_slice).  At (v, k), v != N: the first usable incident edge with c <= k and bit k - c set in
+ *   reach[u] and in avail(m, c) -- the roadmap's edges in row order (neighbour ascending, then edge id), then the world's extras in list
+ *   order -- leads to (u, k - c); else (v, k - 1), a wait.  The walk stops at node N.  path_node / path_slice [W][64] list the visits from the
+ *   start onward, path_len[w] of them (0: no path), -1 behind them: a node with the slice at which it is reached, the start with the slice at
+ *   which the path leaves it.  Waits are implicit; slices increase strictly, so 64 entries suffice.
+ * Every output may be NULL.  ARMOUR_ESTATE before a sliced check, and while armour_roadmap_use_self is on: the self masks are not part of
+ *   the space-time search.  ARMOUR_EINVAL: step_len not finite or <= 0, extras not sorted by world or out of range, a negative or
+ *   non-finite x_len.  armour_roadmap_arrival_host: the same functions world after world on the host, for a handle of
+ *   armour_roadmap_create_host after armour_roadmap_check_slices_host; reach, goal_slice and the paths are the device's, sweeps may differ. */
+int armour_roadmap_arrival(ArmourRoadmap* rm, double step_len, int32_t X, const int32_t* x_world, const int32_t* x_u, const int32_t* x_v,
+                           const double* x_len, const uint64_t* x_mask, const uint64_t* start_mask, const uint64_t* goal_mask,
+                           uint64_t* reach, int32_t* goal_slice, int32_t* path_len, int32_t* path_node, int32_t* path_slice,
+                           int32_t* sweeps, double* ms);
+int armour_roadmap_arrival_host(ArmourRoadmap* rm, double step_len, int32_t X, const int32_t* x_world, const int32_t* x_u, const int32_t* x_v,
+                                const double* x_len, const uint64_t* x_mask, const uint64_t* start_mask, const uint64_t* goal_mask,
+                                uint64_t* reach, int32_t* goal_slice, int32_t* path_len, int32_t* path_node, int32_t* path_slice,
+                                int32_t* sweeps);
+
 /* ---- batched tree planner: bidirectional RRT-Connect for W worlds in one launch (tree_plan.hip) ---- */
 /* The reference's single-query high-level planners (RRT_HLP, RRT_connect_HLP, robot_arm_RRT_HLP with HLP_grow_tree_mode = 'new'): a fresh
  * pair of trees per query, grown where the query is, with no graph built beforehand.  Everything geometric is the roadmap's, reused as it

@@ -33,6 +33,9 @@ and prints ONE JSON line.
   straight-line planner and under armour_amd.roadmap.moving_field_hlps (device_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0): one
   check_moving, one field and one descend_many per iteration): outcome counts of both, `struck_at_rest` among them, the pieces by kind and
   verdict, and hlp / build / solve / audit ms per batch iteration.  Records, not pass criteria;
+* --moving --spacetime: the same moving worlds under armour_amd.roadmap.spacetime_hlps (one plan_slices per iteration: --spacetime-K slices of
+  --spacetime-dt seconds) at each of --spacetime-speeds rad/s, written to profiles/trial_spacetime_bench.json: the record layout of --moving per
+  speed, and the share of waypoint queries for which the search found a path within its slices.  Records, not pass criteria;
 * --kernel-stats: a `rocprofv3 --kernel-trace --stats` summary of the audit kernel in profiles/trial_kernel_stats.csv, taken in a run of
   its own: a fresh child process under a time limit that only repeats the W = 107 audit.
 """
@@ -145,6 +148,46 @@ def moving_trials(robot, ws, a):
     return out
 
 
+def spacetime_trials(robot, ws, a):
+    """--moving --spacetime: the moving worlds under armour_amd.roadmap.spacetime_hlps at each of --spacetime-speeds (the velocities, the roadmap
+    and the record layout of moving_trials; --spacetime-dt, --spacetime-K).  The outcomes are records, not pass criteria."""
+    from armour_amd.roadmap import Roadmap, device_roadmap, spacetime_hlps
+    from armour_amd.trials import OUTCOMES, STRUCK_OUTCOME, run_trials
+    n = robot.num_factors
+    cont = np.array(robot.continuous[:n]).astype(bool)
+    lo, hi = a.moving_speed
+    vel = []
+    for i, (_, p) in enumerate(ws):
+        rng = np.random.default_rng([a.moving_seed, i])
+        v = rng.normal(size=(np.asarray(p["obstacles"]).reshape(-1, 12).shape[0], 3))
+        vel.append(v / np.linalg.norm(v, axis=-1, keepdims=True) * rng.uniform(lo, hi, (v.shape[0], 1)))
+    nodes, edges = device_roadmap(robot, a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
+    rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
+    out = dict(tool="trial_bench --moving --spacetime", T=a.T, worlds=len(ws), max_iterations=a.max_iterations, seed=a.moving_seed, speed=[lo, hi],
+               dt=a.spacetime_dt, K=a.spacetime_K, roadmap=dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius))
+    for speed in a.spacetime_speeds:
+        make = spacetime_hlps(rm, ws, vel, speed, dt=a.spacetime_dt, K=a.spacetime_K)
+        found = []
+        inner = make.get_waypoints
+
+        def counting(indices, qs, lookaheads, inner=inner, make=make, found=found):
+            wps = inner(indices, qs, lookaheads)
+            found.append((sum(make.last_plans[i]["path"] is not None for i in indices), len(indices)))
+            return wps
+
+        make.get_waypoints = counting
+        res = run_trials(ws, hlp=make, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0], velocities=vel)
+        recs = [r for w in res["worlds"] for r in w["records"]]
+        per_batch = lambda k: dict(mean=float(np.mean([b[k] for b in res["batches"]])), max=float(np.max([b[k] for b in res["batches"]])))
+        out["speed_%g" % speed] = dict(outcomes={o: sum(1 for w in res["worlds"] if w["outcome"] == o) for o in OUTCOMES + (STRUCK_OUTCOME,)}, summary=res["summary"],
+                                       pieces={kind: {str(v): sum(1 for r in recs if r["executed"] == kind and r["audit_verdict"] == v) for v in (0, 1, 2)}
+                                               for kind in ("plan", "brake", "stay")},
+                                       paths_found_share=float(sum(f for f, _ in found)) / max(1, sum(q for _, q in found)),
+                                       ms_per_batch={k: per_batch(k) for k in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0])
+    rm.close()
+    return out
+
+
 def tree_trials(robot, ws, straight, a):
     """The worlds once more under tree_hlps; outcome counts under both HLPs and the worlds that end differently."""
     from armour_amd.tree_planner import tree_hlps
@@ -211,6 +254,10 @@ def main():
     ap.add_argument("--moving", action="store_true")
     ap.add_argument("--moving-seed", type=int, default=2)
     ap.add_argument("--moving-speed", type=float, nargs=2, default=[0.05, 0.2])
+    ap.add_argument("--spacetime", action="store_true")
+    ap.add_argument("--spacetime-speeds", type=float, nargs="+", default=[0.5, 1.0, 2.0])
+    ap.add_argument("--spacetime-dt", type=float, default=0.25)
+    ap.add_argument("--spacetime-K", type=int, default=32)
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
@@ -223,8 +270,8 @@ def main():
     robot = kinova_robot()
     ws = scenes.reference_worlds()
     if a.moving:
-        out = moving_trials(robot, ws, a)
-        with open(os.path.join(ROOT, "profiles", "trial_moving_bench.json"), "w") as f:
+        out = spacetime_trials(robot, ws, a) if a.spacetime else moving_trials(robot, ws, a)
+        with open(os.path.join(ROOT, "profiles", "trial_spacetime_bench.json" if a.spacetime else "trial_moving_bench.json"), "w") as f:
             json.dump(out, f, indent=1, default=float)
             f.write("\n")
         print(json.dumps(out, default=float))
