@@ -197,6 +197,7 @@ EXPORTS = [
     "armour_roadmap_check_slices", "armour_roadmap_check_slices_host", "armour_roadmap_arrival", "armour_roadmap_arrival_host",
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
+    "armour_tree_plan_moving", "armour_tree_plan_moving_host", "armour_path_shortcut_moving", "armour_path_shortcut_moving_host",
     "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
     "armour_ws_tree_plan", "armour_ws_tree_plan_host",
     "armour_ws_trees_create", "armour_ws_trees_create_host", "armour_ws_trees_destroy", "armour_ws_trees_grow", "armour_ws_trees_read",
@@ -363,6 +364,9 @@ def load():
     short = [C.POINTER(ArmourRobot), u8p, C.c_int32, C.c_int32, dp, C.c_int32, dp, ip, C.c_double, C.c_int32, C.c_int32, ip, ip, ip, ip, dp, dp, dp, dp]
     L.armour_path_shortcut.argtypes = short       # (the last pointer: ms)
     L.armour_path_shortcut_host.argtypes = short  # (the last pointer: margin [W])
+    if hasattr(L, "armour_tree_plan_moving"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        L.armour_tree_plan_moving.argtypes = L.armour_tree_plan_moving_host.argtypes = tree[:7] + [dp, dp, dp] + tree[7:]         # velocity, t_from, t_to
+        L.armour_path_shortcut_moving.argtypes = L.armour_path_shortcut_moving_host.argtypes = short[:5] + [dp, dp, dp] + short[5:]
     ik = [C.POINTER(ArmourRobot), u8p, dp, dp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, ip, dp, dp, C.POINTER(C.c_uint64), C.c_double, C.c_double,
           C.c_double, C.c_int32, ip, ip, dp, dp, dp, ip, ip, dp]
     L.armour_ik.argtypes = ik                     # (the last pointer: ms)

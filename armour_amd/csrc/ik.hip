@@ -308,7 +308,7 @@ extern "C" int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuou
     ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
     ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
-    for_each_staged(N, O, obstacles, world, [&](int32_t t, const double* obs, int count) { ik_target_host(rb, ar, t, obs, count, margin ? margin + t : nullptr); });
+    for_each_staged(N, O, obstacles, world, [&](int32_t t, const Rule<false>& staged, int count) { ik_target_host(rb, ar, t, staged.obs, count, margin ? margin + t : nullptr); });
     return ARMOUR_OK;
 }
 

@@ -1,5 +1,6 @@
 // Path shortening (include/armour_hip.h, armour_path_shortcut): W polylines in W worlds are validated, pruned and refined in ONE launch, a
-// block per world.  The rule reuses the tree planner's definitions as they stand (tree_block.h: the wrapped difference, S of a prefix, one
+// block per world (armour_path_shortcut_moving: the same against obstacles in linear motion, by the window rule; tree_block.h Rule<MOVING>).
+// The rule reuses the tree planner's definitions as they stand (tree_block.h: the wrapped difference, S of a prefix, one
 // sub-segment's enlarged test); what is new -- the midpoint, the bitwise comparison of two points and the order of the passes -- is written
 // once below as __host__ __device__ code, run by the kernel's lanes and by armour_path_shortcut_host's loop.
 //
@@ -106,7 +107,8 @@ __device__ __forceinline__ bool load_edge(const RmRobot& rb, const EdgeSet& es, 
 //   refine    goes through the whole list and leaves the verdicts in sh.hit.
 // TP_NONE / C when the list ends without such a candidate.  A candidate with a hit is not tested further.  The caller has put a barrier after
 // the last write of pts; on return every lane is past the last read of pts, and (refine) sh.hit is complete.
-__device__ inline int run_edges(const RmRobot& rb, ShortShared& sh, const EdgeSet es, int C, const double* pts, double edge_step, const double* s_obs, int O) {
+template <class R>
+__device__ inline int run_edges(const RmRobot& rb, ShortShared& sh, const EdgeSet es, int C, const double* pts, double edge_step, const R& rule, int O) {
     const int t = threadIdx.x;
     for (int k = t; k < C; k += TP_BLOCK) sh.hit[k] = 0;
     __syncthreads();
@@ -129,7 +131,7 @@ __device__ inline int run_edges(const RmRobot& rb, ShortShared& sh, const EdgeSe
         if (t < per * sp.G && item < T) {
             const int k = item_owner(sh.end, nw, item), start = k ? sh.end[k - 1] : 0, done = k ? 0 : sbase;
             load_edge(rb, es, pts, cbase + k, a, b);
-            if (!segment_free(rb, a, b, item - start + done, sh.end[k] - start + done, s_obs + (size_t)sp.o0 * RM_OBS_STRIDE, sp.o1 - sp.o0)) sh.hit[cbase + k] = 1;
+            if (!segment_free(rb, a, b, item - start + done, sh.end[k] - start + done, rule.from(sp.o0), sp.o1 - sp.o0)) sh.hit[cbase + k] = 1;
         }
         __syncthreads();
         const int in_chunk = item_owner(sh.end, nw, per - 1) + 1;   // the candidates with an item in this chunk: 1 + the number of ends < per
@@ -153,14 +155,15 @@ __device__ inline int run_edges(const RmRobot& rb, ShortShared& sh, const EdgeSe
 }
 
 // prune of the list pts [count][n], in place: the kept points move to the front (slot o <= the anchor's successor, never above a candidate)
-__device__ inline int block_prune(const RmRobot& rb, ShortShared& sh, double* pts, int count, double edge_step, const double* s_obs, int O) {
+template <class R>
+__device__ inline int block_prune(const RmRobot& rb, ShortShared& sh, double* pts, int count, double edge_step, const R& rule, int O) {
     const int t = threadIdx.x, n = rb.n, last = count - 1;
     int o = 1, i = 0;
     while (i < last) {                                      // the anchor moves forward every time
         const int C = last - i - 1;                         // candidates last, last - 1, ..., i + 2; i + 1 is an edge of the list: known free
         int j = i + 1;
         if (C > 0) {
-            const int k = run_edges(rb, sh, EdgeSet{SC_PRUNE, i, last}, C, pts, edge_step, s_obs, O);
+            const int k = run_edges(rb, sh, EdgeSet{SC_PRUNE, i, last}, C, pts, edge_step, rule, O);
             if (k < C) j = last - k;
         }
         if (t < n) pts[o * n + t] = pts[j * n + t];
@@ -172,9 +175,10 @@ __device__ inline int block_prune(const RmRobot& rb, ShortShared& sh, double* pt
 }
 
 // refine of the list pts [count][n], in place; the caller has checked 2 count - 1 <= the rows of pts.  Returns the new count.
-__device__ inline int block_refine(const RmRobot& rb, ShortShared& sh, double* pts, int count, double edge_step, const double* s_obs, int O) {
+template <class R>
+__device__ inline int block_refine(const RmRobot& rb, ShortShared& sh, double* pts, int count, double edge_step, const R& rule, int O) {
     const int t = threadIdx.x, n = rb.n;
-    run_edges(rb, sh, EdgeSet{SC_REFINE, 0, 0}, 2 * (count - 1), pts, edge_step, s_obs, O);
+    run_edges(rb, sh, EdgeSet{SC_REFINE, 0, 0}, 2 * (count - 1), pts, edge_step, rule, O);
     // point k goes to k + the number of midpoints inserted before it: lane t scans the pairs SC_PER_LANE t ...
     int before[SC_PER_LANE], mine = 0;
 #pragma unroll
@@ -233,30 +237,40 @@ __device__ inline double block_length(const RmRobot& rb, ShortShared& sh, const 
 }
 
 // grid W, dynamic LDS: the world's obstacles [O][RM_OBS_STRIDE], then its list [max(max_in, max_points)][n]
-__global__ __launch_bounds__(TP_BLOCK) void path_shortcut_kernel(RmRobot rb, ShortcutArgs ar) {
+// MOVING (armour_path_shortcut_moving): the window rule -- the obstacles are [O][RM_MOV_STRIDE], mv.velocity [W][O][3], mv.mid / mv.half [W], this
+// world's two kept in registers.  The static instantiation reads nothing of mv and keeps the static rule's calls as they were.
+template <bool MOVING>
+__global__ __launch_bounds__(TP_BLOCK) void path_shortcut_kernel(RmRobot rb, ShortcutArgs ar, MovingArgs mv) {
     extern __shared__ double s_dyn[];
     __shared__ ShortShared sh;
     const int w = blockIdx.x, t = threadIdx.x, n = rb.n, O = ar.O;
     double* s_obs = s_dyn;
-    double* pts = s_dyn + (size_t)O * RM_OBS_STRIDE;
+    double* pts = s_dyn + (size_t)O * Rule<MOVING>::STRIDE;
+    Rule<MOVING> rule{s_obs};
+    if constexpr (MOVING) {
+        rule.mid = mv.mid[w];
+        rule.half = mv.half[w];
+    }
     int count = ar.counts[w];
     const double* in = ar.paths + (size_t)w * ar.max_in * n;
     for (int i = t; i < count * n; i += TP_BLOCK) pts[i] = in[i];
-    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);   // (ends in a barrier: pts is written too)
+    // (either ends in a barrier: pts is written too)
+    if constexpr (MOVING) stage_obstacles_moving_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, mv.velocity + (size_t)w * O * 3, O, s_obs);
+    else stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
     const double length_in = block_length(rb, sh, pts, count);
     int status = ARMOUR_SHORTCUT_OK, first_bad = -1, passes_done = 0;
     double length_out = 0.0;
-    const int bad = run_edges(rb, sh, EdgeSet{SC_VALIDATE, 0, 0}, count - 1, pts, ar.edge_step, s_obs, O);
+    const int bad = run_edges(rb, sh, EdgeSet{SC_VALIDATE, 0, 0}, count - 1, pts, ar.edge_step, rule, O);
     if (bad != TP_NONE) {
         status = ARMOUR_SHORTCUT_INVALID;
         first_bad = bad;
         count = 0;
     } else {
-        count = block_prune(rb, sh, pts, count, ar.edge_step, s_obs, O);
+        count = block_prune(rb, sh, pts, count, ar.edge_step, rule, O);
         passes_done = 1;
         for (int p = 1; p < ar.passes && 2 * count - 1 <= ar.max_points; p++) {
-            count = block_refine(rb, sh, pts, count, ar.edge_step, s_obs, O);
-            count = block_prune(rb, sh, pts, count, ar.edge_step, s_obs, O);
+            count = block_refine(rb, sh, pts, count, ar.edge_step, rule, O);
+            count = block_prune(rb, sh, pts, count, ar.edge_step, rule, O);
             passes_done = p + 1;
         }
         length_out = block_length(rb, sh, pts, count);
@@ -282,13 +296,15 @@ double length_host(const RmRobot& rb, const std::vector<double>& pts, int count)
     return acc;
 }
 
-bool free_host(const HostWorld& hw, const double* a, const double* b) {
+template <class R>
+bool free_host(const HostWorld<R>& hw, const double* a, const double* b) {
     int S;
     return hw.prefix(a, b, &S) == S;
 }
 
 // prune: the candidates of an anchor in descending j, each with prefix; i + 1 is taken untested
-void prune_host(const HostWorld& hw, std::vector<double>& pts, int* count) {
+template <class R>
+void prune_host(const HostWorld<R>& hw, std::vector<double>& pts, int* count) {
     const int n = hw.rb.n, last = *count - 1;
     int o = 1, i = 0;
     while (i < last) {
@@ -302,7 +318,8 @@ void prune_host(const HostWorld& hw, std::vector<double>& pts, int* count) {
 }
 
 // refine: a -> mid is tested first, mid -> b only when it is free
-void refine_host(const HostWorld& hw, std::vector<double>& pts, int* count) {
+template <class R>
+void refine_host(const HostWorld<R>& hw, std::vector<double>& pts, int* count) {
     const int n = hw.rb.n;
     std::vector<double> next;
     next.reserve((size_t)(2 * *count - 1) * n);
@@ -323,11 +340,12 @@ void refine_host(const HostWorld& hw, std::vector<double>& pts, int* count) {
     pts.swap(next);
 }
 
-void shortcut_world_host(const RmRobot& rb, const ShortcutArgs& ar, int w, const double* obs, double* margin) {
+template <class R>
+void shortcut_world_host(const RmRobot& rb, const ShortcutArgs& ar, int w, const R& rule, double* margin) {
     const int n = rb.n;
     int count = ar.counts[w];
     if (margin) *margin = INFINITY;
-    const HostWorld hw{rb, obs, ar.O, ar.edge_step, margin};
+    const HostWorld<R> hw{rb, rule, ar.O, ar.edge_step, margin};
     const double* in = ar.paths + (size_t)w * ar.max_in * n;
     std::vector<double> pts(in, in + (size_t)count * n);
     ar.length_in[w] = length_host(rb, pts, count);
@@ -389,49 +407,49 @@ int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continu
     return check_joint_spans(who, *rb, extent, ar.edge_step);
 }
 
-}  // namespace
-
-extern "C" int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
-                                         const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
-                                         int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out,
-                                         double* margin) {
-    const char* who = "armour_path_shortcut_host";
+// the host twin of both rules (mv null: the static one)
+int shortcut_on_host(const char* who, const ArmourRobot* robot, const uint8_t* continuous, const ShortcutCall& ar, const Motion* mv, double* margin) {
     RmRobot rb;
-    ShortcutCall ar{};
-    ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.max_in = max_in; ar.paths = paths; ar.counts = counts; ar.edge_step = edge_step; ar.passes = passes;
-    ar.max_points = max_points; ar.status = status; ar.points = points; ar.first_bad = first_bad; ar.passes_done = passes_done; ar.out = out;
-    ar.length_in = length_in; ar.length_out = length_out;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, ar));
-    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) { shortcut_world_host(rb, ar, w, obs, margin ? margin + w : nullptr); });
-    return armour_check_path_capacity(who, W, points, max_points, true);
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    auto world = [&](int32_t w, const auto& rule, int) { shortcut_world_host(rb, ar, w, rule, margin ? margin + w : nullptr); };
+    if (mv) for_each_staged<true>(ar.W, ar.O, ar.obstacles, nullptr, world, mv->velocity, mid.data(), half.data());
+    else for_each_staged(ar.W, ar.O, ar.obstacles, nullptr, world);
+    return armour_check_path_capacity(who, ar.W, ar.points, ar.max_points, true);
 }
 
-extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
-                                    const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
-                                    int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, double* ms) {
-    const char* who = "armour_path_shortcut";
+// the device entry of both rules (mv null: the static one)
+int shortcut_on_device(const char* who, const char* host_form, const ArmourRobot* robot, const uint8_t* continuous, const ShortcutCall& ar, const Motion* mv, double* ms) {
     RmRobot rb;
-    ShortcutCall ar{};
-    ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.max_in = max_in; ar.paths = paths; ar.counts = counts; ar.edge_step = edge_step; ar.passes = passes;
-    ar.max_points = max_points; ar.status = status; ar.points = points; ar.first_bad = first_bad; ar.passes_done = passes_done; ar.out = out;
-    ar.length_in = length_in; ar.length_out = length_out;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, ar));
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    const int32_t W = ar.W, O = ar.O, max_in = ar.max_in, max_points = ar.max_points;
+    double* out = ar.out;
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
-    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_path_shortcut_host is the host form)", who); return ARMOUR_EDEVICE; }
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (%s is the host form)", who, host_form); return ARMOUR_EDEVICE; }
     const int n = rb.n;
     const size_t rows = (size_t)std::max(max_in, max_points), out_len = out ? (size_t)W * max_points * n : 0;
-    const size_t lds = ((size_t)O * RM_OBS_STRIDE + rows * n) * sizeof(double);
+    const size_t lds = ((size_t)O * (mv ? RM_MOV_STRIDE : RM_OBS_STRIDE) + rows * n) * sizeof(double);
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_paths, d_path_out;
+    DevBuf<double> d_obs, d_paths, d_path_out, d_vel, d_mid, d_half;
     DevBuf<int32_t> d_counts;
     DevColumns<double> len;                               // length_in | length_out [W] each
     DevColumns<int32_t> res;                              // status | points | first_bad | passes_done [W] each
     ARMOUR_TRY(st.create());
-    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
-    ARMOUR_TRY(d_paths.upload(paths, (size_t)W * max_in * n, st));
-    ARMOUR_TRY(d_counts.upload(counts, (size_t)W, st));
+    ARMOUR_TRY(d_obs.upload(ar.obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_paths.upload(ar.paths, (size_t)W * max_in * n, st));
+    ARMOUR_TRY(d_counts.upload(ar.counts, (size_t)W, st));
+    MovingArgs dmv{};
+    if (mv) {
+        ARMOUR_TRY(d_vel.upload(mv->velocity, (size_t)W * O * 3, st));
+        ARMOUR_TRY(d_mid.upload(mid.data(), (size_t)W, st));
+        ARMOUR_TRY(d_half.upload(half.data(), (size_t)W, st));
+        dmv = MovingArgs{d_vel, d_mid, d_half};
+    }
     ARMOUR_TRY(res.reserve(4, (size_t)W));
     ARMOUR_TRY(len.reserve(2, (size_t)W));
     if (out) ARMOUR_TRY(d_path_out.reserve(out_len));
@@ -440,24 +458,77 @@ extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* con
     dev.status = res.column(0); dev.points = res.column(1); dev.first_bad = res.column(2); dev.passes_done = res.column(3);
     dev.length_in = len.column(0); dev.length_out = len.column(1);
     dev.out = out ? d_path_out.p : nullptr;
-    // beside the kernel's static 21.6 KB: at the caps 55 KB of obstacles and 56 KB of path, which a block may have once it asks
-    if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(path_shortcut_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // beside the kernel's static 21.6 KB: at the caps 54 KB (static) or 62 KB (moving) of obstacles and up to 64 KB of path, which a block may
+    // have once it asks, as far as the device grants it
+    const void* kernel = mv ? reinterpret_cast<const void*>(path_shortcut_kernel<true>) : reinterpret_cast<const void*>(path_shortcut_kernel<false>);
+    ARMOUR_TRY(grant_dynamic_lds(who, kernel, lds));
     ARMOUR_TRY(ev.record_start(st));
-    hipLaunchKernelGGL(path_shortcut_kernel, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev);
+    if (mv) hipLaunchKernelGGL(path_shortcut_kernel<true>, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
+    else hipLaunchKernelGGL(path_shortcut_kernel<false>, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
     ARMOUR_TRY(res.fetch(st));
     ARMOUR_TRY(len.fetch(st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    int32_t* const ints[4] = {status, points, first_bad, passes_done};
+    int32_t* const ints[4] = {ar.status, ar.points, ar.first_bad, ar.passes_done};
     for (int k = 0; k < 4; k++) res.copy_out(k, ints[k]);
-    len.copy_out(0, length_in);
-    len.copy_out(1, length_out);
+    len.copy_out(0, ar.length_in);
+    len.copy_out(1, ar.length_out);
     // only the rows that were written come back (the rest of the caller's array is left as it was)
     for (int32_t w = 0; out && w < W; w++)
-        if (points[w] > 0 && points[w] <= max_points)
-            HIPCHK(hipMemcpyAsync(out + (size_t)w * max_points * n, d_path_out + (size_t)w * max_points * n, (size_t)points[w] * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (ar.points[w] > 0 && ar.points[w] <= max_points)
+            HIPCHK(hipMemcpyAsync(out + (size_t)w * max_points * n, d_path_out + (size_t)w * max_points * n, (size_t)ar.points[w] * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    return armour_check_path_capacity(who, W, points, max_points, true);
+    return armour_check_path_capacity(who, W, ar.points, max_points, true);
+}
+
+// an entry's arguments into the call record (the moving entries' three go beside it, in a Motion)
+ShortcutCall shortcut_call(int32_t W, int32_t O, const double* obstacles, int32_t max_in, const double* paths, const int32_t* counts, double edge_step, int32_t passes,
+                           int32_t max_points, int32_t* status, int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in,
+                           double* length_out) {
+    ShortcutCall ar{};
+    ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.max_in = max_in; ar.paths = paths; ar.counts = counts; ar.edge_step = edge_step; ar.passes = passes;
+    ar.max_points = max_points; ar.status = status; ar.points = points; ar.first_bad = first_bad; ar.passes_done = passes_done; ar.out = out;
+    ar.length_in = length_in; ar.length_out = length_out;
+    return ar;
+}
+
+}  // namespace
+
+extern "C" int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
+                                         const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
+                                         int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out,
+                                         double* margin) {
+    const ShortcutCall ar = shortcut_call(W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out, length_in,
+                                          length_out);
+    return shortcut_on_host("armour_path_shortcut_host", robot, continuous, ar, nullptr, margin);
+}
+
+extern "C" int armour_path_shortcut_moving_host(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles,
+                                                const double* velocity, const double* t_from, const double* t_to, int32_t max_in, const double* paths,
+                                                const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status, int32_t* points,
+                                                int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, double* margin) {
+    const ShortcutCall ar = shortcut_call(W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out, length_in,
+                                          length_out);
+    const Motion mv{velocity, t_from, t_to};
+    return shortcut_on_host("armour_path_shortcut_moving_host", robot, continuous, ar, &mv, margin);
+}
+
+extern "C" int armour_path_shortcut(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, int32_t max_in,
+                                    const double* paths, const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
+                                    int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, double* ms) {
+    const ShortcutCall ar = shortcut_call(W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out, length_in,
+                                          length_out);
+    return shortcut_on_device("armour_path_shortcut", "armour_path_shortcut_host", robot, continuous, ar, nullptr, ms);
+}
+
+extern "C" int armour_path_shortcut_moving(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                           const double* t_from, const double* t_to, int32_t max_in, const double* paths, const int32_t* counts, double edge_step,
+                                           int32_t passes, int32_t max_points, int32_t* status, int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out,
+                                           double* length_in, double* length_out, double* ms) {
+    const ShortcutCall ar = shortcut_call(W, O, obstacles, max_in, paths, counts, edge_step, passes, max_points, status, points, first_bad, passes_done, out, length_in,
+                                          length_out);
+    const Motion mv{velocity, t_from, t_to};
+    return shortcut_on_device("armour_path_shortcut_moving", "armour_path_shortcut_moving_host", robot, continuous, ar, &mv, ms);
 }

@@ -7,6 +7,8 @@
 // order key_less, the obstacle split and the owner of a work item.  path_shortcut.hip and ik.hip take all they need from here; tree_plan.hip
 // takes block_first and ws_tree.hip block_any / block_scan / block_argmin, and each of the two keeps the rest inline, where the shared form
 // measured slower.  The argument rules and the staging loop of all four kernels' host entries are here as well.
+// The tree planner and the shortener judge by the static rule or, in their moving entries, by the window rule: both reach
+// the rule and the stride of a staged obstacle through Rule<MOVING> below and nowhere else.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -40,19 +42,51 @@ __host__ __device__ inline int prefix_segments(const RmRobot& rb, const double* 
     const int64_t S = edge_segments(rb, a, b, edge_step);
     return S > ARMOUR_TREE_MAX_SEGMENTS ? ARMOUR_TREE_MAX_SEGMENTS : (int)S;
 }
-// sub-segment s of S of the edge a -> b against the staged obstacles: the edge rule's enlarged test, verdict mode
-__host__ __device__ inline bool segment_free(const RmRobot& rb, const double* a, const double* b, int s, int S, const double* obs, int O) {
+// The rule a step judges a configuration by, with the staged obstacles it judges it against: the ONE place from which the two kernels and the
+// two host twins reach config_free / config_free_moving and the stride of a staged obstacle.  Rule<false>: the static rule (stride
+// RM_OBS_STRIDE).  Rule<true>: the window rule of armour_roadmap_check_moving (stride RM_MOV_STRIDE) with the world's mid and half.
+// from(o0) is the view of the obstacles o0, o0 + 1, ...: what the obstacle split hands a lane.
+template <bool MOVING>
+struct Rule;
+template <>
+struct Rule<false> {
+    static constexpr int STRIDE = RM_OBS_STRIDE;
+    const double* obs;
+    __host__ __device__ Rule from(int o0) const { return Rule{obs + (size_t)o0 * STRIDE}; }
+    __host__ __device__ bool config(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], int O, bool full, double* clearance) const {
+        return config_free(rb, q, r, obs, O, full, clearance);
+    }
+};
+template <>
+struct Rule<true> {
+    static constexpr int STRIDE = RM_MOV_STRIDE;
+    const double* obs;
+    double mid, half;
+    __host__ __device__ Rule from(int o0) const { return Rule{obs + (size_t)o0 * STRIDE, mid, half}; }
+    __host__ __device__ bool config(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], int O, bool full, double* clearance) const {
+        return config_free_moving(rb, q, r, obs, O, mid, half, full, clearance);
+    }
+};
+// what a moving kernel reads besides the static one's arguments (device pointers): velocity [W][O][3], mid / half [W]
+struct MovingArgs {
+    const double *velocity, *mid, *half;
+};
+
+// sub-segment s of S of the edge a -> b against O staged obstacles: the edge rule's enlarged test, verdict mode
+template <class R>
+__host__ __device__ inline bool segment_free(const RmRobot& rb, const double* a, const double* b, int s, int S, const R& rule, int O) {
     double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
     edge_sample(rb, a, b, s, S, q, r);
-    return config_free(rb, q, r, obs, O, false, nullptr);
+    return rule.config(rb, q, r, O, false, nullptr);
 }
-__host__ __device__ inline bool node_free(const RmRobot& rb, const double* x, const double* obs, int O) {
+template <class R>
+__host__ __device__ inline bool node_free(const RmRobot& rb, const double* x, const R& rule, int O) {
     double q[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
 #pragma unroll
     for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
 #pragma unroll
     for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
-    return config_free(rb, q, r, obs, O, false, nullptr);
+    return rule.config(rb, q, r, O, false, nullptr);
 }
 
 // ---- the block's cooperative steps: TP_BLOCK lanes, ordered by __syncthreads() alone.  Every result is the same in all lanes.
@@ -156,16 +190,17 @@ __host__ __device__ inline int item_owner(const int* end, int n, int item) {
 }
 
 // ---- the host twins' steps: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
+template <class R>
 struct HostWorld {
     const RmRobot& rb;
-    const double* obs;
+    R rule;
     int O;
     double edge_step;
     double* margin;
 
     void note(double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS]) const {
         double cl;
-        config_free(rb, q, r, obs, O, true, &cl);
+        rule.config(rb, q, r, O, true, &cl);
         *margin = std::fmin(*margin, std::fabs(cl));
     }
     bool node(const double* x) const {
@@ -174,7 +209,7 @@ struct HostWorld {
             for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) q[j] = j < rb.n ? x[j] : 0.0;
             note(q, r);
         }
-        return node_free(rb, x, obs, O);
+        return node_free(rb, x, rule, O);
     }
     int prefix(const double* a, const double* b, int* S_out) const {
         const int S = prefix_segments(rb, a, b, edge_step);
@@ -185,7 +220,7 @@ struct HostWorld {
                 edge_sample(rb, a, b, s, S, q, r);
                 note(q, r);
             }
-            if (!segment_free(rb, a, b, s, S, obs, O)) return s;
+            if (!segment_free(rb, a, b, s, S, rule, O)) return s;
         }
         return S;
     }
@@ -204,15 +239,61 @@ inline int check_joint_spans(const char* who, const RmRobot& rb, const double* e
     }
     return ARMOUR_OK;
 }
+// the motion of a moving entry as the caller passed it: velocity [W][O][3], t_from / t_to [W] (an entry hands a null Motion* for a static call)
+struct Motion {
+    const double *velocity, *t_from, *t_to;
+};
+// The refusals that the moving entries add to those of their static forms, before a device is touched (armour_roadmap_check_moving's); fills
+// mid / half [W], the two numbers per world that the rule reads, for the kernel and the host twin alike
+inline int check_windows(const char* who, int32_t W, int32_t O, const Motion& mv, std::vector<double>* mid, std::vector<double>* half) {
+    const double *velocity = mv.velocity, *t_from = mv.t_from, *t_to = mv.t_to;
+    if ((W > 0 && O > 0 && !velocity) || (W > 0 && (!t_from || !t_to))) { armour_set_error("%s: null velocity or window", who); return ARMOUR_EINVAL; }
+    if (!finite_all(velocity, (size_t)W * O * 3) || !finite_all(t_from, (size_t)W) || !finite_all(t_to, (size_t)W)) {
+        armour_set_error("%s: a velocity or a window is not finite", who);
+        return ARMOUR_EINVAL;
+    }
+    mid->resize((size_t)W);
+    half->resize((size_t)W);
+    for (int32_t w = 0; w < W; w++) {
+        if (t_from[w] > t_to[w]) { armour_set_error("%s: world %d: t_from = %g > t_to = %g", who, w, t_from[w], t_to[w]); return ARMOUR_EINVAL; }
+        (*mid)[w] = 0.5 * (t_from[w] + t_to[w]);
+        (*half)[w] = 0.5 * (t_to[w] - t_from[w]);
+    }
+    return ARMOUR_OK;
+}
+// The dynamic LDS of a launch against what the device grants a block: above 48 KB a kernel has it once it asks, above the device's limit
+// (with the kernel's static LDS beside it) the entry refuses instead of launching
+inline int grant_dynamic_lds(const char* who, const void* kernel, size_t lds) {
+    if (lds <= 48 * 1024) return ARMOUR_OK;
+    int dev = 0, limit = 0;
+    hipFuncAttributes fa{};
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    HIPCHK(hipFuncGetAttributes(&fa, kernel));
+    if (lds + fa.sharedSizeBytes > (size_t)limit) {
+        armour_set_error("%s: %zu B of dynamic LDS beside %zu B static, the device grants a block %d B", who, lds, (size_t)fa.sharedSizeBytes, limit);
+        return ARMOUR_ECAPACITY;
+    }
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return ARMOUR_OK;
+}
 // Item i of `count` (a world, or a target in world world[i]; -1: no obstacles) with its world's obstacles staged as the kernels stage them:
-// run(i, staged obstacles, their number)
-template <class F>
-inline void for_each_staged(int32_t count, int32_t O, const double* obstacles, const int32_t* world, F&& run) {
-    std::vector<double> obs((size_t)O * RM_OBS_STRIDE);
+// run(i, the rule over the staged obstacles, their number).  MOVING: velocity [W][O][3], mid / half [W] of check_windows.
+template <bool MOVING = false, class F>
+inline void for_each_staged(int32_t count, int32_t O, const double* obstacles, const int32_t* world, F&& run, const double* velocity = nullptr,
+                            const double* mid = nullptr, const double* half = nullptr) {
+    std::vector<double> obs((size_t)O * Rule<MOVING>::STRIDE);
     for (int32_t i = 0; i < count; i++) {
         const int32_t w = world ? world[i] : i;
-        if (w >= 0) stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
-        run(i, obs.data(), w < 0 ? 0 : O);
+        Rule<MOVING> rule{obs.data()};
+        if constexpr (MOVING) {
+            if (w >= 0) stage_obstacles_moving(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, velocity + (size_t)w * O * 3, (size_t)O, obs.data());
+            rule.mid = w >= 0 ? mid[w] : 0.0;
+            rule.half = w >= 0 ? half[w] : 0.0;
+        } else {
+            if (w >= 0) stage_obstacles(obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, (size_t)O, obs.data());
+        }
+        run(i, rule, w < 0 ? 0 : O);
     }
 }
 

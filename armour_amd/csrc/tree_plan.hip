@@ -1,5 +1,6 @@
 // Batched tree planner (include/armour_hip.h, armour_tree_plan): bidirectional RRT-Connect for W worlds in ONE launch, a block per world,
-// the whole loop inside the block.  The rule is the roadmap's, reused as it stands: the node rule (config_free), the edge rule's sub-segments
+// the whole loop inside the block (armour_tree_plan_moving: the same against obstacles in linear motion, by the window rule; tree_block.h
+// Rule<MOVING>).  The rule is the roadmap's, reused as it stands: the node rule (config_free), the edge rule's sub-segments
 // (edge_segments / edge_sample) and the wrapped distance (wrapped_sq); what is new here -- the counter hash, the steer and cut steps and the
 // order (distance, index) -- is written once below as __host__ __device__ code, run by the kernel's lanes and by armour_tree_plan_host's loop.
 //
@@ -86,8 +87,10 @@ __device__ inline void block_nearest(const RmRobot& rb, TreeShared& sh, const do
 // at most TP_BLOCK / 2 sub-segments (every extend step; most joins) gives each sub-segment G = min(O, TP_BLOCK / S) lanes, lane g of them
 // testing the obstacles [g O / G, (g + 1) O / G): tree_block.h's obstacle_split, which says why it is sound.  Lanes are in ascending order
 // of sub-segment, so the first colliding lane names the first colliding sub-segment.  The caller has put a barrier after the last write of
-// sh.a / sh.b; on return every lane is past the last read of them, and sh.words is released.
-__device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edge_step, const double* s_obs, int O, int* S_out) {
+// sh.a / sh.b; on return every lane is past the last read of them, and sh.words is released.  A lane's slice is rule.from(o0): the offset is in
+// the stride of the rule's staging.
+template <class R>
+__device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edge_step, const R& rule, int O, int* S_out) {
     const int t = threadIdx.x;
     const int S = prefix_segments(rb, sh.a, sh.b, edge_step);
     *S_out = S;
@@ -98,7 +101,7 @@ __device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edg
     int m = S;
     for (int base = 0; base < S; base += per) {
         const int s = base + t / G;
-        const bool hit = t < per * G && s < S && !segment_free(rb, sh.a, sh.b, s, S, s_obs + (size_t)o0 * RM_OBS_STRIDE, o1 - o0);
+        const bool hit = t < per * G && s < S && !segment_free(rb, sh.a, sh.b, s, S, rule.from(o0), o1 - o0);
         const int f = block_first(sh.words, hit);           // (released: the next chunk, or the next prefix, may write the words)
         if (f != TP_NONE) { m = base + f / G; break; }
     }
@@ -106,11 +109,21 @@ __device__ inline int block_prefix(const RmRobot& rb, TreeShared& sh, double edg
 }
 
 // grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The trees of world w: nodes [w][2][max_nodes][n], parent [w][2][max_nodes], count [w][2].
-__global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArgs ar) {
-    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+// MOVING (armour_tree_plan_moving): the window rule -- dynamic LDS [O][RM_MOV_STRIDE], mv.velocity [W][O][3], mv.mid / mv.half [W], this world's
+// two kept in registers.  The static instantiation reads nothing of mv and keeps the static rule's calls as they were.
+template <bool MOVING>
+__global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArgs ar, MovingArgs mv) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE], MOVING: [O][RM_MOV_STRIDE]
     __shared__ TreeShared sh;
     const int w = blockIdx.x, t = threadIdx.x, n = rb.n, O = ar.O, cap = ar.max_nodes;
-    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    Rule<MOVING> rule{s_obs};
+    if constexpr (MOVING) {
+        rule.mid = mv.mid[w];
+        rule.half = mv.half[w];
+        stage_obstacles_moving_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, mv.velocity + (size_t)w * O * 3, O, s_obs);
+    } else {
+        stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    }
     const double* start = ar.starts + (size_t)w * n;
     const double* goal = ar.goals + (size_t)w * n;
     const uint64_t seed = ar.seeds[w];
@@ -120,7 +133,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArg
     int status = ARMOUR_TREE_NOT_FOUND, iterations = 0, points = 0;
 
     // the node rule at start and goal (lanes 0 and 1), and the direct edge
-    if (t < 2) sh.flag[t] = node_free(rb, t == 0 ? start : goal, s_obs, O) ? 1 : 0;
+    if (t < 2) sh.flag[t] = node_free(rb, t == 0 ? start : goal, rule, O) ? 1 : 0;
     if (t < ARMOUR_MAX_FACTORS) {
         sh.a[t] = t < n ? start[t] : 0.0;
         sh.b[t] = t < n ? goal[t] : 0.0;
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArg
         status = ARMOUR_TREE_GOAL_BLOCKED;
     } else {
         int S;
-        const int m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+        const int m = block_prefix(rb, sh, ar.edge_step, rule, O, &S);
         if (m == S) {
             status = ARMOUR_TREE_FOUND;
             points = 2;
@@ -173,7 +186,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArg
             __syncthreads();
             // ---- extend: the free prefix of nearest -> qn
             int S;
-            int m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+            int m = block_prefix(rb, sh, ar.edge_step, rule, O, &S);
             if (m == 0) continue;
             if (t < n) {
                 if (m < S) sh.b[t] = cut_joint(rb, t, sh.a[t], sh.b[t], m, S);
@@ -188,7 +201,7 @@ __global__ __launch_bounds__(TP_BLOCK) void tree_plan_kernel(RmRobot rb, TreeArg
             block_nearest(rb, sh, nodes[b], cnt[b], &acc, &vb);
             if (t < ARMOUR_MAX_FACTORS) sh.a[t] = t < n ? nodes[b][(size_t)vb * n + t] : 0.0;
             __syncthreads();
-            m = block_prefix(rb, sh, ar.edge_step, s_obs, O, &S);
+            m = block_prefix(rb, sh, ar.edge_step, rule, O, &S);
             if (m == S) {
                 // joined: the start tree's chain root -> ..., then the goal tree's chain ... -> root.  The walks are bounded by the counts.
                 const int join[2] = {a == 0 ? joined_a : vb, a == 0 ? vb : joined_a};
@@ -238,13 +251,14 @@ int nearest_host(const RmRobot& rb, const double* nodes, int cnt, const double* 
 }
 
 // world w of the host twin; the trees go to nodes [2][max_nodes][n] / parent [2][max_nodes] (the caller's rows or scratch)
-void plan_world_host(const RmRobot& rb, const TreeArgs& ar, int w, const double* obs, double* nodes0, int32_t* parent0, double* margin) {
+template <class R>
+void plan_world_host(const RmRobot& rb, const TreeArgs& ar, int w, const R& rule, double* nodes0, int32_t* parent0, double* margin) {
     const int n = rb.n, cap = ar.max_nodes;
     const double* start = ar.starts + (size_t)w * n;
     const double* goal = ar.goals + (size_t)w * n;
     const uint64_t seed = ar.seeds[w];
     if (margin) *margin = INFINITY;
-    const HostWorld hw{rb, obs, ar.O, ar.edge_step, margin};
+    const HostWorld<R> hw{rb, rule, ar.O, ar.edge_step, margin};
     double* nodes[2] = {nodes0, nodes0 + (size_t)cap * n};
     int32_t* parent[2] = {parent0, parent0 + cap};
     int cnt[2] = {0, 0};
@@ -359,56 +373,59 @@ int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continu
     return ARMOUR_OK;
 }
 
-}  // namespace
-
-extern "C" int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
-                                     const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
-                                     int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
-                                     double* path, int32_t* count, double* nodes, int32_t* parent, double* margin) {
-    const char* who = "armour_tree_plan_host";
+// the host twin of both rules (mv null: the static one)
+int plan_on_host(const char* who, const ArmourRobot* robot, const uint8_t* continuous, TreeCall& ar, const Motion* mv, double* margin) {
     RmRobot rb;
-    TreeCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds;
-    ar.step = step; ar.edge_step = edge_step; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points;
-    ar.status = status; ar.iterations = iterations; ar.points = points; ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
     const int n = rb.n;
+    const int32_t max_nodes = ar.max_nodes;
+    double* nodes = ar.nodes;
+    int32_t* parent = ar.parent;
     std::vector<double> own_nodes(nodes ? 0 : (size_t)2 * max_nodes * n);
     std::vector<int32_t> own_parent(parent ? 0 : (size_t)2 * max_nodes);
-    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) {
-        plan_world_host(rb, ar, w, obs, nodes ? nodes + (size_t)w * 2 * max_nodes * n : own_nodes.data(), parent ? parent + (size_t)w * 2 * max_nodes : own_parent.data(),
+    auto world = [&](int32_t w, const auto& rule, int) {
+        plan_world_host(rb, ar, w, rule, nodes ? nodes + (size_t)w * 2 * max_nodes * n : own_nodes.data(), parent ? parent + (size_t)w * 2 * max_nodes : own_parent.data(),
                         margin ? margin + w : nullptr);
-    });
-    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
+    };
+    if (mv) for_each_staged<true>(ar.W, ar.O, ar.obstacles, nullptr, world, mv->velocity, mid.data(), half.data());
+    else for_each_staged(ar.W, ar.O, ar.obstacles, nullptr, world);
+    return armour_check_path_capacity(who, ar.W, ar.points, ar.max_points, ar.path != nullptr);
 }
 
-extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
-                                const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
-                                int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path,
-                                int32_t* count, double* nodes, int32_t* parent, double* ms) {
-    const char* who = "armour_tree_plan";
+// the device entry of both rules (mv null: the static one)
+int plan_on_device(const char* who, const char* host_form, const ArmourRobot* robot, const uint8_t* continuous, TreeCall& ar, const Motion* mv, double* ms) {
     RmRobot rb;
-    TreeCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds;
-    ar.step = step; ar.edge_step = edge_step; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points;
-    ar.status = status; ar.iterations = iterations; ar.points = points; ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    const int32_t W = ar.W, O = ar.O, max_nodes = ar.max_nodes, max_points = ar.max_points;
+    int32_t *status = ar.status, *iterations = ar.iterations, *points = ar.points, *count = ar.count, *parent = ar.parent;
+    double *path = ar.path, *nodes = ar.nodes;
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
-    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (%s is the host form)", who, host_form); return ARMOUR_EDEVICE; }
     const int n = rb.n;
     const size_t Wn = (size_t)W * n, trees = (size_t)W * 2 * max_nodes, path_len = path ? (size_t)W * max_points * n : 0;
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_starts, d_goals, d_nodes, d_path;
+    DevBuf<double> d_obs, d_starts, d_goals, d_nodes, d_path, d_vel, d_mid, d_half;
     DevBuf<uint64_t> d_seeds;
     DevBuf<int32_t> d_parent;
     DevColumns<int32_t> out;                              // status | iterations | points [W] each, then count [W][2]
     ARMOUR_TRY(st.create());
-    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
-    ARMOUR_TRY(d_starts.upload(starts, Wn, st));
-    ARMOUR_TRY(d_goals.upload(goals, Wn, st));
-    ARMOUR_TRY(d_seeds.upload(seeds, (size_t)W, st));
+    ARMOUR_TRY(d_obs.upload(ar.obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_starts.upload(ar.starts, Wn, st));
+    ARMOUR_TRY(d_goals.upload(ar.goals, Wn, st));
+    ARMOUR_TRY(d_seeds.upload(ar.seeds, (size_t)W, st));
+    MovingArgs dmv{};
+    if (mv) {
+        ARMOUR_TRY(d_vel.upload(mv->velocity, (size_t)W * O * 3, st));
+        ARMOUR_TRY(d_mid.upload(mid.data(), (size_t)W, st));
+        ARMOUR_TRY(d_half.upload(half.data(), (size_t)W, st));
+        dmv = MovingArgs{d_vel, d_mid, d_half};
+    }
     ARMOUR_TRY(d_nodes.reserve(trees * n));
     ARMOUR_TRY(d_parent.reserve(trees));
     ARMOUR_TRY(out.reserve(5, (size_t)W));
@@ -417,8 +434,13 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
     dev.obstacles = d_obs; dev.starts = d_starts; dev.goals = d_goals; dev.seeds = d_seeds;
     dev.status = out.column(0); dev.iterations = out.column(1); dev.points = out.column(2); dev.count = out.column(3);
     dev.parent = d_parent; dev.nodes = d_nodes; dev.path = path ? d_path.p : nullptr;
+    // at the cap of 256 obstacles 54 KB (static) or 62 KB (moving) of dynamic LDS: above 48 KB, which a block may have once it asks
+    const size_t lds = (size_t)O * (mv ? RM_MOV_STRIDE : RM_OBS_STRIDE) * sizeof(double);
+    const void* kernel = mv ? reinterpret_cast<const void*>(tree_plan_kernel<true>) : reinterpret_cast<const void*>(tree_plan_kernel<false>);
+    ARMOUR_TRY(grant_dynamic_lds(who, kernel, lds));
     ARMOUR_TRY(ev.record_start(st));
-    hipLaunchKernelGGL(tree_plan_kernel, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, rb, dev);
+    if (mv) hipLaunchKernelGGL(tree_plan_kernel<true>, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
+    else hipLaunchKernelGGL(tree_plan_kernel<false>, dim3((unsigned)W), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
     ARMOUR_TRY(out.fetch(st));
@@ -441,4 +463,57 @@ extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continu
     }
     HIPCHK(hipStreamSynchronize(st));
     return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
+}
+
+// an entry's arguments into the call record (the moving entries' three go beside it, in a Motion)
+TreeCall tree_call(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds,
+                   double step, double edge_step, int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                   double* path, int32_t* count, double* nodes, int32_t* parent) {
+    TreeCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds;
+    ar.step = step; ar.edge_step = edge_step; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points;
+    ar.status = status; ar.iterations = iterations; ar.points = points; ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent;
+    return ar;
+}
+
+}  // namespace
+
+extern "C" int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                     const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                                     int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
+                                     double* path, int32_t* count, double* nodes, int32_t* parent, double* margin) {
+    TreeCall ar = tree_call(lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status, iterations, points, path, count,
+                            nodes, parent);
+    return plan_on_host("armour_tree_plan_host", robot, continuous, ar, nullptr, margin);
+}
+
+extern "C" int armour_tree_plan_moving_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                            const double* obstacles, const double* velocity, const double* t_from, const double* t_to, const double* starts,
+                                            const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations, int32_t max_nodes,
+                                            int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path, int32_t* count, double* nodes,
+                                            int32_t* parent, double* margin) {
+    TreeCall ar = tree_call(lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status, iterations, points, path, count,
+                            nodes, parent);
+    const Motion mv{velocity, t_from, t_to};
+    return plan_on_host("armour_tree_plan_moving_host", robot, continuous, ar, &mv, margin);
+}
+
+extern "C" int armour_tree_plan(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
+                                int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path,
+                                int32_t* count, double* nodes, int32_t* parent, double* ms) {
+    TreeCall ar = tree_call(lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status, iterations, points, path, count,
+                            nodes, parent);
+    return plan_on_device("armour_tree_plan", "armour_tree_plan_host", robot, continuous, ar, nullptr, ms);
+}
+
+extern "C" int armour_tree_plan_moving(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                       const double* obstacles, const double* velocity, const double* t_from, const double* t_to, const double* starts,
+                                       const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations, int32_t max_nodes,
+                                       int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path, int32_t* count, double* nodes,
+                                       int32_t* parent, double* ms) {
+    TreeCall ar = tree_call(lb, ub, W, O, obstacles, starts, goals, seeds, step, edge_step, max_iterations, max_nodes, max_points, status, iterations, points, path, count,
+                            nodes, parent);
+    const Motion mv{velocity, t_from, t_to};
+    return plan_on_device("armour_tree_plan_moving", "armour_tree_plan_moving_host", robot, continuous, ar, &mv, ms);
 }

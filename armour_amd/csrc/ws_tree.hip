@@ -580,8 +580,8 @@ extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int3
     const size_t cap = (size_t)max_nodes;
     std::vector<double> own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);
     std::vector<int32_t> own_parent(parent ? 0 : cap);
-    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const double* obs, int) {
-        plan_world_host(ar, w, w, obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
+    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const Rule<false>& staged, int) {
+        plan_world_host(ar, w, w, staged.obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
                         node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr, nullptr);
     });
     return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
@@ -800,9 +800,9 @@ extern "C" int armour_ws_trees_grow(ArmourWsTrees* h, int32_t L, const int32_t* 
         ar.starts = starts; ar.goals = h->goals.data(); ar.seeds = h->seeds.data();
         ar.status = status; ar.iterations = iterations_done; ar.points = points; ar.rewires = rewires; ar.chain_kept = kept.data(); ar.count = count;
         ar.path_cost = path_cost; ar.goal_dist = goal_dist; ar.path = path;
-        for_each_staged(L, O, h->obstacles.data(), worlds, [&](int32_t l, const double* obs, int) {
+        for_each_staged(L, O, h->obstacles.data(), worlds, [&](int32_t l, const Rule<false>& staged, int) {
             const size_t row = (size_t)worlds[l] * cap;
-            plan_world_host(ar, l, worlds[l], obs, &h->nodes[row * 3], &h->parent[row], &h->node_cost[row], &h->node_len[row], margin ? margin + l : nullptr,
+            plan_world_host(ar, l, worlds[l], staged.obs, &h->nodes[row * 3], &h->parent[row], &h->node_cost[row], &h->node_len[row], margin ? margin + l : nullptr,
                             &h->state[(size_t)worlds[l] * WS_STATE]);
         });
         return armour_check_path_capacity(who, L, points, max_points, path != nullptr);

@@ -998,6 +998,33 @@ int armour_tree_plan_host(const ArmourRobot* robot, const uint8_t* continuous, c
                           const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds, double step, double edge_step,
                           int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points,
                           double* path, int32_t* count, double* nodes, int32_t* parent, double* margin);
+/* armour_tree_plan against obstacles in LINEAR MOTION, over a time window per world: the static entry with velocity [W][O][3], t_from and
+ * t_to [W] after obstacles, which are the poses at world time 0 (armour_roadmap_check_moving's arguments).
+ * The rule is armour_roadmap_check_moving's window rule and nothing else changes.  The host computes once per world mid[w] = 0.5 * (t_from[w]
+ *   + t_to[w]) and half[w] = 0.5 * (t_to[w] - t_from[w]) and hands these two doubles to the kernel.  The node rule at start and goal and every
+ *   sub-segment test of every prefix are the static ones with, for obstacle o, the box centre x - v_o mid[w] and every half-size
+ *   h_l + (r_l + |v_o|_2 half[w]) (r_l = 0 for a node).  S, the sub-segment midpoints and enlargements, prefix, nearest, the steer step, the
+ *   counter hash, the order of the loop and the path are word for word the static entry's.
+ * Soundness.  Within [t_from, t_to] obstacle o leaves its pose of time mid by at most |v_o| half, so the static argument holds with the
+ *   window in place of the instant: no configuration on a returned path meets an obstacle at ANY time of the window, whatever the time at
+ *   which the arm passes it.  The trees do not carry time; a path is not a schedule.
+ * With zero velocities every output is armour_tree_plan's bit for bit, for any window; t_from == t_to judges at an instant.
+ * ARMOUR_EINVAL before a device is touched: armour_tree_plan's refusals; a null or non-finite velocity, t_from or t_to; t_from[w] > t_to[w].
+ *   O = 0 with null obstacles and velocity is served as the static entry serves it.
+ * Device: the static launch with RM_OBS_STRIDE + 4 doubles of LDS per obstacle (248 B: 62 KB per block at the cap, which the entry asks the
+ *   runtime for); ARMOUR_ECAPACITY, without a launch, when the device grants a block less dynamic LDS than that beside the kernel's static.
+ * armour_tree_plan_moving_host is the same functions in a loop and touches no device; margin [W] as armour_tree_plan_host's, of the
+ *   window rule's clearances. */
+int armour_tree_plan_moving(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                            const double* obstacles, const double* velocity, const double* t_from, const double* t_to, const double* starts,
+                            const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations, int32_t max_nodes,
+                            int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path, int32_t* count,
+                            double* nodes, int32_t* parent, double* ms);
+int armour_tree_plan_moving_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, int32_t W, int32_t O,
+                                 const double* obstacles, const double* velocity, const double* t_from, const double* t_to, const double* starts,
+                                 const double* goals, const uint64_t* seeds, double step, double edge_step, int32_t max_iterations,
+                                 int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, double* path,
+                                 int32_t* count, double* nodes, int32_t* parent, double* margin);
 
 /* ---- path shortening: W polylines in W worlds validated, pruned and refined in one launch (path_shortcut.hip) ---- */
 /* What a user of a sampling planner expects back, and what the reference's HLPs need to reuse their last path (HLP_grow_tree_mode =
@@ -1050,6 +1077,30 @@ int armour_path_shortcut_host(const ArmourRobot* robot, const uint8_t* continuou
                               int32_t max_in, const double* paths, const int32_t* counts, double edge_step, int32_t passes,
                               int32_t max_points, int32_t* status, int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out,
                               double* length_in, double* length_out, double* margin);
+/* armour_path_shortcut against obstacles in LINEAR MOTION, over a time window per world: the static entry with velocity [W][O][3], t_from
+ * and t_to [W] after obstacles (the poses at world time 0).  An edge is FREE when every sub-segment passes the window rule's test, exactly
+ * as armour_tree_plan_moving's prefix judges it (mid[w] and half[w] computed once on the host); validate, prune, refine, the midpoint, the
+ * lengths and the order of the passes are word for word the static entry's.  Soundness: every segment of an output path is an edge whose
+ * every sub-segment separated under the window rule, so no configuration on the output meets an obstacle at ANY time of [t_from, t_to],
+ * whatever the time at which the arm passes it.  A path that was free in an earlier window can be INVALID in a later one: that is how a
+ * planner that keeps its path learns that the world has moved over it.
+ * With zero velocities every output column is armour_path_shortcut's bit for bit, for any window.
+ * ARMOUR_EINVAL before a device is touched: armour_path_shortcut's refusals; a null or non-finite velocity, t_from or t_to;
+ *   t_from[w] > t_to[w].  O = 0 with null obstacles and velocity is served as the static entry serves it.
+ * Device: the static launch; dynamic LDS = O * 248 B of obstacles (62 KB at the cap) + max(max_in, max_points) * n * 8 B of path (up to
+ *   64 KB) beside the kernel's static 21.6 KB, which the entry asks the runtime for; ARMOUR_ECAPACITY, without a launch, when the sum
+ *   exceeds what the device grants a block.
+ * armour_path_shortcut_moving_host is the same functions in a loop and touches no device; margin [W] as armour_path_shortcut_host's, of
+ *   the window rule's clearances. */
+int armour_path_shortcut_moving(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles,
+                                const double* velocity, const double* t_from, const double* t_to, int32_t max_in, const double* paths,
+                                const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status, int32_t* points,
+                                int32_t* first_bad, int32_t* passes_done, double* out, double* length_in, double* length_out, double* ms);
+int armour_path_shortcut_moving_host(const ArmourRobot* robot, const uint8_t* continuous, int32_t W, int32_t O, const double* obstacles,
+                                     const double* velocity, const double* t_from, const double* t_to, int32_t max_in, const double* paths,
+                                     const int32_t* counts, double edge_step, int32_t passes, int32_t max_points, int32_t* status,
+                                     int32_t* points, int32_t* first_bad, int32_t* passes_done, double* out, double* length_in,
+                                     double* length_out, double* margin);
 
 /* ---- batched collision-aware inverse kinematics for workspace goals (ik.hip) ---- */
 /* The reference's end-effector planner (arm_end_effector_RRT_star_HLP) takes its goal and waypoints as points of the workspace and turns

@@ -3,7 +3,8 @@
 // points, the straight segment through the wall (invalid) and a two-point path in an empty world -- checks what every run must satisfy
 // (the ends are kept, one pass returns a subsequence, the output is not longer, every output edge is free by the node rule at the
 // midpoints of its sub-segments, rows of an invalid world and rows past `points` are untouched, the same call twice gives the same bytes)
-// and the refusals, and prints what it found.
+// and the refusals, and prints what it found.  Then armour_path_shortcut_moving_host: at zero velocity against the static call, and with
+// the wall arriving.
 //   make -C armour_amd/csrc shortcuthost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
 // It supplies the symbols path_shortcut.hip takes from api.hip, so that nothing else of the library is linked.
 #include <cmath>
@@ -144,6 +145,55 @@ int main() {
             const int rc = run(&c, 1, a.points[0] - 1 < 2 ? 2 : a.points[0] - 1);
             if (a.points[0] > 2 && (rc != ARMOUR_ECAPACITY || c.points != a.points || c.out[0] != SENTINEL)) { printf("FAILED: capacity: rc %d\n", rc); return 1; }
         }
+    }
+    // moving obstacles.  Zero velocity on any window is the static call bit for bit, every column; then the wall 1 m further out at t = 0
+    // and moving in at 0.5 m/s: the straight segment of world 2 is free while the window ends before the wall is near and invalid in a
+    // window about its arrival, where the detour of world 0 is still shortened
+    {
+        auto run_moving = [&](Out* o, const double* obs, const double* vel, const double* t_from, const double* t_to) {
+            o->status.assign(W, -1); o->points.assign(W, -1); o->first_bad.assign(W, -9); o->passes_done.assign(W, -1);
+            o->out.assign((size_t)W * max_points * n, SENTINEL); o->length_in.assign(W, -1.0); o->length_out.assign(W, -1.0); o->margin.assign(W, 0.0);
+            return armour_path_shortcut_moving_host(&robot, nullptr, W, O, obs, vel, t_from, t_to, max_in, paths.data(), counts.data(), edge_step, 2, max_points,
+                                                    o->status.data(), o->points.data(), o->first_bad.data(), o->passes_done.data(), o->out.data(), o->length_in.data(),
+                                                    o->length_out.data(), o->margin.data());
+        };
+        Out a, b;
+        const std::vector<double> zero((size_t)W * O * 3, 0.0);
+        const double t_from[W] = {-3.0, 0.25, 7.0, 0.0}, t_to[W] = {4.0, 0.25, 11.5, 0.0};
+        if (run(&a, 2, max_points) != ARMOUR_OK || run_moving(&b, obstacles.data(), zero.data(), t_from, t_to) != ARMOUR_OK) { printf("FAILED: %s\n", g_error); return 1; }
+        if (a.status != b.status || a.points != b.points || a.first_bad != b.first_bad || a.passes_done != b.passes_done || a.length_in != b.length_in ||
+            a.length_out != b.length_out || a.margin != b.margin || std::memcmp(a.out.data(), b.out.data(), a.out.size() * sizeof(double))) {
+            printf("FAILED: zero velocity is not the static call\n");
+            return 1;
+        }
+        const double out_dir[3] = {x[0] / std::hypot(x[0], x[1]), x[1] / std::hypot(x[0], x[1]), 0.0};
+        std::vector<double> away = obstacles, vel((size_t)W * O * 3, 0.0);
+        for (int w = 0; w < 3; w++)
+            for (int i = 0; i < 3; i++) {
+                away[(size_t)w * 12 + i] += 1.0 * out_dir[i];
+                vel[(size_t)w * 3 + i] = -0.5 * out_dir[i];
+            }
+        const double early_from[W] = {0.0, 0.0, 0.0, 0.0}, early_to[W] = {0.2, 0.2, 0.2, 0.2}, late_from[W] = {1.4, 1.4, 1.4, 1.4}, late_to[W] = {1.6, 1.6, 1.6, 1.6};
+        Out early, late;
+        if (run_moving(&early, away.data(), vel.data(), early_from, early_to) != ARMOUR_OK || run_moving(&late, away.data(), vel.data(), late_from, late_to) != ARMOUR_OK) {
+            printf("FAILED: the moving call: %s\n", g_error);
+            return 1;
+        }
+        if (early.status[2] != ARMOUR_SHORTCUT_OK || early.points[2] != 2 || early.points[0] != 2 || late.status[2] != ARMOUR_SHORTCUT_INVALID || late.first_bad[2] != 0 ||
+            late.status[0] != ARMOUR_SHORTCUT_OK || late.points[0] < 3 || late.points[0] >= counts[0] || !(late.margin[0] > 0.0)) {
+            printf("FAILED: the arriving wall: early status %d with %d / %d points, late status %d / %d with %d points\n", early.status[2], early.points[2], early.points[0],
+                   late.status[2], late.status[0], late.points[0]);
+            return 1;
+        }
+        const double reversed[W] = {0.0, 1.7, 0.0, 0.0};
+        vel[4] = NAN;
+        if (run_moving(&b, away.data(), nullptr, late_from, late_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), vel.data(), late_from, late_to) != ARMOUR_EINVAL ||
+            run_moving(&b, away.data(), zero.data(), reversed, late_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), zero.data(), late_from, nullptr) != ARMOUR_EINVAL) {
+            printf("FAILED: a bad velocity or window passed\n");
+            return 1;
+        }
+        printf("moving: zero velocity equals the static call; the arriving wall: the straight segment is free on [0, 0.2] and invalid on [1.4, 1.6], the detour %d -> %d points\n",
+               counts[0], late.points[0]);
     }
     // refusals
     Out r;

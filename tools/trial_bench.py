@@ -30,9 +30,11 @@ and prints ONE JSON line.
   sections of the other planners that profiles/trial_bench.json already holds are kept;
 * --moving: a run of its own that writes profiles/trial_moving_bench.json and leaves profiles/trial_bench.json alone: the same worlds with every
   obstacle in linear motion (seeded velocities, --moving-seed, speeds --moving-speed LO HI in m/s; run_trials(velocities=...)) under the
-  straight-line planner and under armour_amd.roadmap.moving_field_hlps (device_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0): one
-  check_moving, one field and one descend_many per iteration): outcome counts of both, `struck_at_rest` among them, the pieces by kind and
-  verdict, and hlp / build / solve / audit ms per batch iteration.  Records, not pass criteria;
+  straight-line planner, under armour_amd.roadmap.moving_field_hlps (device_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0): one
+  check_moving, one field and one descend_many per iteration) and under armour_amd.tree_planner.moving_tree_hlps (the --tree-* options; no
+  roadmap: at most three launches per iteration): outcome counts of each, `struck_at_rest` among them, the pieces by kind and verdict, and
+  hlp / build / solve / audit ms per batch iteration.  --moving-planners runs some of the three rows and keeps the file's others.
+  Records, not pass criteria;
 * --moving --spacetime: the same moving worlds under armour_amd.roadmap.spacetime_hlps (one plan_slices per iteration: --spacetime-K slices of
   --spacetime-dt seconds) at each of --spacetime-speeds rad/s, written to profiles/trial_spacetime_bench.json: the record layout of --moving per
   speed, and the share of waypoint queries for which the search found a path within its slices.  Records, not pass criteria;
@@ -132,11 +134,20 @@ def moving_trials(robot, ws, a):
         rng = np.random.default_rng([a.moving_seed, i])
         v = rng.normal(size=(np.asarray(p["obstacles"]).reshape(-1, 12).shape[0], 3))
         vel.append(v / np.linalg.norm(v, axis=-1, keepdims=True) * rng.uniform(lo, hi, (v.shape[0], 1)))
-    nodes, edges = device_roadmap(robot, a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
-    rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
-    out = dict(tool="trial_bench --moving", T=a.T, worlds=len(ws), max_iterations=a.max_iterations, seed=a.moving_seed, speed=[lo, hi],
-               roadmap=dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius))
-    for key, hlp in (("straight", "straight"), ("moving_field", moving_field_hlps(rm, ws, vel))):
+    out = dict(tool="trial_bench --moving", T=a.T, worlds=len(ws), max_iterations=a.max_iterations, seed=a.moving_seed, speed=[lo, hi])
+    rm = None
+    if "moving_field" in a.moving_planners:
+        nodes, edges = device_roadmap(robot, a.roadmap_nodes, a.roadmap_radius, 16, 0, np.array(robot.state_limits_lb[:n]), np.array(robot.state_limits_ub[:n]), cont)
+        rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
+        out["roadmap"] = dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius)
+    from armour_amd.tree_planner import moving_tree_hlps
+    planners = dict(straight=lambda: "straight", moving_field=lambda: moving_field_hlps(rm, ws, vel),
+                    moving_tree=lambda: moving_tree_hlps(ws, robot, vel, seed=a.tree_seed, shortcut=a.tree_shortcut, mode=a.tree_mode, max_iterations=a.tree_iterations,
+                                                         max_nodes=a.tree_nodes))
+    if "moving_tree" in a.moving_planners:
+        out["tree"] = dict(seed=a.tree_seed, shortcut=a.tree_shortcut, mode=a.tree_mode, max_iterations=a.tree_iterations, max_nodes=a.tree_nodes)
+    for key in a.moving_planners:
+        hlp = planners[key]()
         res = run_trials(ws, hlp=hlp, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0], velocities=vel)
         recs = [r for w in res["worlds"] for r in w["records"]]
         per_batch = lambda k: dict(mean=float(np.mean([b[k] for b in res["batches"]])), max=float(np.max([b[k] for b in res["batches"]])))
@@ -144,7 +155,8 @@ def moving_trials(robot, ws, a):
                         pieces={kind: {str(v): sum(1 for r in recs if r["executed"] == kind and r["audit_verdict"] == v) for v in (0, 1, 2)}
                                 for kind in ("plan", "brake", "stay")},
                         ms_per_batch={k: per_batch(k) for k in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0])
-    rm.close()
+    if rm is not None:
+        rm.close()
     return out
 
 
@@ -254,6 +266,7 @@ def main():
     ap.add_argument("--moving", action="store_true")
     ap.add_argument("--moving-seed", type=int, default=2)
     ap.add_argument("--moving-speed", type=float, nargs=2, default=[0.05, 0.2])
+    ap.add_argument("--moving-planners", nargs="+", choices=["straight", "moving_field", "moving_tree"], default=["straight", "moving_field", "moving_tree"])
     ap.add_argument("--spacetime", action="store_true")
     ap.add_argument("--spacetime-speeds", type=float, nargs="+", default=[0.5, 1.0, 2.0])
     ap.add_argument("--spacetime-dt", type=float, default=0.25)
@@ -271,7 +284,11 @@ def main():
     ws = scenes.reference_worlds()
     if a.moving:
         out = spacetime_trials(robot, ws, a) if a.spacetime else moving_trials(robot, ws, a)
-        with open(os.path.join(ROOT, "profiles", "trial_spacetime_bench.json" if a.spacetime else "trial_moving_bench.json"), "w") as f:
+        path = os.path.join(ROOT, "profiles", "trial_spacetime_bench.json" if a.spacetime else "trial_moving_bench.json")
+        if not a.spacetime and os.path.exists(path):      # the rows of the planners that this run left out are kept
+            with open(path) as f:
+                out = dict(json.load(f), **out)
+        with open(path, "w") as f:
             json.dump(out, f, indent=1, default=float)
             f.write("\n")
         print(json.dumps(out, default=float))
