@@ -198,8 +198,8 @@ EXPORTS = [
     "armour_roadmap_create_host", "armour_roadmap_knn", "armour_roadmap_knn_host", "armour_roadmap_connect_batch", "armour_roadmap_descend_batch",
     "armour_tree_plan", "armour_tree_plan_host", "armour_path_shortcut", "armour_path_shortcut_host",
     "armour_tree_plan_moving", "armour_tree_plan_moving_host", "armour_path_shortcut_moving", "armour_path_shortcut_moving_host",
-    "armour_ik", "armour_ik_host", "armour_ik_end_effector_host",
-    "armour_ws_tree_plan", "armour_ws_tree_plan_host",
+    "armour_ik", "armour_ik_host", "armour_ik_end_effector_host", "armour_ik_moving", "armour_ik_moving_host",
+    "armour_ws_tree_plan", "armour_ws_tree_plan_host", "armour_ws_tree_plan_moving", "armour_ws_tree_plan_moving_host",
     "armour_ws_trees_create", "armour_ws_trees_create_host", "armour_ws_trees_destroy", "armour_ws_trees_grow", "armour_ws_trees_read",
     "armour_debug_ws_trees_set_iterations",
     "armour_debug_block_steps", "armour_debug_block_split", "armour_debug_block_owner",
@@ -376,6 +376,9 @@ def load():
         dp, dp, dp, ip, dp, ip, dp, dp]
     L.armour_ws_tree_plan.argtypes = ws           # (the last pointer: ms)
     L.armour_ws_tree_plan_host.argtypes = ws      # (the last pointer: margin [W])
+    if hasattr(L, "armour_ws_tree_plan_moving"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
+        L.armour_ik_moving.argtypes = L.armour_ik_moving_host.argtypes = ik[:10] + [dp, dp, dp] + ik[10:]                         # velocity, t_from, t_to
+        L.armour_ws_tree_plan_moving.argtypes = L.armour_ws_tree_plan_moving_host.argtypes = ws[:5] + [dp, dp, dp] + ws[5:]
     if hasattr(L, "armour_ws_trees_create"):   # (absent from a library of an earlier commit selected with ARMOUR_HIP_LIB for a comparison)
         trees = [dp, dp, C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_uint64)] + [C.c_double] * 6 + [C.c_int32, C.POINTER(vp)]
         L.armour_ws_trees_create.argtypes = trees

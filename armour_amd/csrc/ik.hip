@@ -1,6 +1,6 @@
 // Batched collision-aware inverse kinematics for workspace goals (include/armour_hip.h, armour_ik): N targets x S seeds in ONE launch, a
 // block per target.  An item (target, seed) is a damped least-squares iteration on the end-effector point; a converged item is judged by the
-// node rule against its target's world, and the free item nearest to q_ref is picked.  Everything geometric is the roadmap's, reused as it
+// node rule (armour_ik_moving: the window rule, through tree_block.h's Rule<MOVING>) against its target's world, and the free item nearest to q_ref is picked.  Everything geometric is the roadmap's, reused as it
 // stands (link_frame, config_free, wrapped_sq, key_less, the staged obstacles) and the start points come from the tree planner's counter
 // hash; what is new -- the end-effector point with its Jacobian, the step and the pick -- is written once below as __host__ __device__ code,
 // run by the kernel's lanes and by armour_ik_host's loop.
@@ -132,14 +132,17 @@ __host__ __device__ inline bool ik_iterate(const RmRobot& rb, const IkArgs& ar, 
     }
 }
 
-// The node rule at q against `count` staged obstacles: verdict mode, no enlargement (q is copied: config_free consumes its arguments)
-__host__ __device__ inline bool ik_free(const RmRobot& rb, const double (&q)[ARMOUR_MAX_FACTORS], const double* obs, int count) {
+// The node rule at q against the `count` staged obstacles of the rule's view (tree_block.h, Rule<MOVING>: the static rule, or the window rule
+// of the target's world): verdict mode, no enlargement (q is copied: the rule consumes its arguments).  clearance (host twin's margin): the
+// full form.
+template <class R>
+__host__ __device__ inline bool ik_free(const RmRobot& rb, const double (&q)[ARMOUR_MAX_FACTORS], const R& rule, int count, double* clearance = nullptr) {
     double x[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS];
 #pragma unroll
     for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) x[j] = q[j];
 #pragma unroll
     for (int l = 0; l < ARMOUR_MAX_JOINTS; l++) r[l] = 0.0;
-    return config_free(rb, x, r, obs, count, false, nullptr);
+    return rule.config(rb, x, r, count, clearance != nullptr, clearance);
 }
 
 struct IkShared {
@@ -149,14 +152,23 @@ struct IkShared {
     uint8_t conv[TP_BLOCK], hit[TP_BLOCK];
 };
 
-// grid N, dynamic LDS [O][RM_OBS_STRIDE] doubles
-__global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar) {
-    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+// grid N, dynamic LDS [O][Rule<MOVING>::STRIDE] doubles.  MOVING (armour_ik_moving): the window rule of the target's world -- mv.velocity
+// [W][O][3], mv.mid / mv.half [W], read only for world >= 0.  The static instantiation reads nothing of mv.
+template <bool MOVING>
+__global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar, MovingArgs mv) {
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE], MOVING: [O][RM_MOV_STRIDE]
     __shared__ IkShared sh;
     const int tg = blockIdx.x, t = threadIdx.x, n = rb.n, S = ar.S;
     const int w = ar.world[tg];
-    const int O = w < 0 ? 0 : ar.O;                        // world -1: no obstacles
-    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)(w < 0 ? 0 : w) * ar.O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    const int O = w < 0 ? 0 : ar.O;                        // world -1: no obstacles (and no window)
+    Rule<MOVING> rule{s_obs};
+    if constexpr (MOVING) {
+        rule.mid = w < 0 ? 0.0 : mv.mid[w < 0 ? 0 : w];
+        rule.half = w < 0 ? 0.0 : mv.half[w < 0 ? 0 : w];
+        stage_obstacles_moving_lds<TP_BLOCK>(ar.obstacles + (size_t)(w < 0 ? 0 : w) * ar.O * ARMOUR_OBS_DOUBLES, mv.velocity + (size_t)(w < 0 ? 0 : w) * ar.O * 3, O, s_obs);
+    } else {
+        stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)(w < 0 ? 0 : w) * ar.O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    }
     const double* q_ref = ar.q_ref + (size_t)tg * n;
     const size_t item = (size_t)tg * S + (t < S ? t : 0);
 
@@ -194,7 +206,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar) {
             double x[ARMOUR_MAX_FACTORS];
 #pragma unroll
             for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) x[j] = S <= IK_SPLIT_SEEDS ? sh.q[j][it] : q[j];   // (above the split: it == t)
-            if (!ik_free(rb, x, s_obs + (size_t)o0 * RM_OBS_STRIDE, o1 - o0)) sh.hit[it] = 1;           // every writer stores the same value
+            if (!ik_free(rb, x, rule.from(o0), o1 - o0)) sh.hit[it] = 1;                                 // every writer stores the same value
         }
     }
     __syncthreads();
@@ -224,8 +236,9 @@ __global__ __launch_bounds__(TP_BLOCK) void ik_kernel(RmRobot rb, IkArgs ar) {
     }
 }
 
-// target tg of the host twin: the same functions in a loop; obs = the target's world, staged as the kernel stages it
-void ik_target_host(const RmRobot& rb, const IkArgs& ar, int tg, const double* obs, int O, double* margin) {
+// target tg of the host twin: the same functions in a loop; rule = the target's world, staged as the kernel stages it, with its rule
+template <class R>
+void ik_target_host(const RmRobot& rb, const IkArgs& ar, int tg, const R& rule, int O, double* margin) {
     const int n = rb.n, S = ar.S;
     const double* q_ref = ar.q_ref + (size_t)tg * n;
     double bd = INFINITY, m = INFINITY;
@@ -240,11 +253,10 @@ void ik_target_host(const RmRobot& rb, const IkArgs& ar, int tg, const double* o
         bool free_ = false;
         if (conv) {
             some = true;
-            free_ = ik_free(rb, q, obs, O);
+            free_ = ik_free(rb, q, rule, O);
             if (margin) {
-                double x[ARMOUR_MAX_FACTORS], r[ARMOUR_MAX_JOINTS] = {}, cl;
-                for (int j = 0; j < ARMOUR_MAX_FACTORS; j++) x[j] = q[j];
-                config_free(rb, x, r, obs, O, true, &cl);
+                double cl;
+                ik_free(rb, q, rule, O, &cl);
                 m = std::fmin(m, std::fabs(cl));
             }
         }
@@ -295,51 +307,51 @@ int check_args(const char* who, const ArmourRobot* robot, const uint8_t* continu
     return ARMOUR_OK;
 }
 
-}  // namespace
-
-extern "C" int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
-                              int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds,
-                              double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err,
-                              int32_t* iterations, int32_t* flags, double* margin) {
-    const char* who = "armour_ik_host";
+// the host twin of both rules (mv null: the static one)
+int solve_on_host(const char* who, const ArmourRobot* robot, const uint8_t* continuous, IkCall& ar, const Motion* mv, double* margin) {
     RmRobot rb;
-    IkCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.tool_in = tool; ar.N = N; ar.S = S; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.world = world; ar.targets = targets;
-    ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
-    ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
-    for_each_staged(N, O, obstacles, world, [&](int32_t t, const Rule<false>& staged, int count) { ik_target_host(rb, ar, t, staged.obs, count, margin ? margin + t : nullptr); });
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    auto target = [&](int32_t t, const auto& rule, int count) { ik_target_host(rb, ar, t, rule, count, margin ? margin + t : nullptr); };
+    if (mv) for_each_staged<true>(ar.N, ar.O, ar.obstacles, ar.world, target, mv->velocity, mid.data(), half.data());
+    else for_each_staged(ar.N, ar.O, ar.obstacles, ar.world, target);
     return ARMOUR_OK;
 }
 
-extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S, int32_t W,
-                         int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds, double lambda,
-                         double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err,
-                         int32_t* iterations, int32_t* flags, double* ms) {
-    const char* who = "armour_ik";
+// the device entry of both rules (mv null: the static one)
+int solve_on_device(const char* who, const char* host_form, const ArmourRobot* robot, const uint8_t* continuous, IkCall& ar, const Motion* mv, double* ms) {
     RmRobot rb;
-    IkCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.tool_in = tool; ar.N = N; ar.S = S; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.world = world; ar.targets = targets;
-    ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
-    ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
     ARMOUR_TRY(check_args(who, robot, continuous, &rb, &ar));
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    const int32_t N = ar.N, S = ar.S, W = ar.W, O = ar.O;
+    int32_t *best = ar.best, *iterations = ar.iterations, *flags = ar.flags;
+    double *q_best = ar.q_best, *q = ar.q, *err = ar.err;
     if (ms) *ms = 0.0;
     if (N == 0) return ARMOUR_OK;
-    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ik_host is the host form)", who); return ARMOUR_EDEVICE; }
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (%s is the host form)", who, host_form); return ARMOUR_EDEVICE; }
     const int n = rb.n;
     const size_t items = (size_t)N * S;
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_targets, d_ref, d_qbest, d_q, d_err;
+    DevBuf<double> d_obs, d_targets, d_ref, d_qbest, d_q, d_err, d_vel, d_mid, d_half;
     DevBuf<uint64_t> d_seeds;
     DevBuf<int32_t> d_world, d_items;                      // d_items: iterations | flags [N][S] each, either may be absent
     DevColumns<int32_t> out;                               // status | best [N] each
     ARMOUR_TRY(st.create());
-    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
-    ARMOUR_TRY(d_targets.upload(targets, (size_t)N * 3, st));
-    ARMOUR_TRY(d_ref.upload(q_ref, (size_t)N * n, st));
-    ARMOUR_TRY(d_seeds.upload(seeds, (size_t)N, st));
-    ARMOUR_TRY(d_world.upload(world, (size_t)N, st));
+    ARMOUR_TRY(d_obs.upload(ar.obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_targets.upload(ar.targets, (size_t)N * 3, st));
+    ARMOUR_TRY(d_ref.upload(ar.q_ref, (size_t)N * n, st));
+    ARMOUR_TRY(d_seeds.upload(ar.seeds, (size_t)N, st));
+    ARMOUR_TRY(d_world.upload(ar.world, (size_t)N, st));
+    MovingArgs dmv{};
+    if (mv) {
+        ARMOUR_TRY(d_vel.upload(mv->velocity, (size_t)W * O * 3, st));
+        ARMOUR_TRY(d_mid.upload(mid.data(), (size_t)W, st));
+        ARMOUR_TRY(d_half.upload(half.data(), (size_t)W, st));
+        dmv = MovingArgs{d_vel, d_mid, d_half};
+    }
     ARMOUR_TRY(d_qbest.reserve((size_t)N * n));
     ARMOUR_TRY(out.reserve(2, (size_t)N));
     if (q) ARMOUR_TRY(d_q.reserve(items * n));
@@ -352,8 +364,13 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
     dev.err = err ? d_err.p : nullptr;
     dev.iterations = iterations ? d_items.p : nullptr;
     dev.flags = flags ? d_items + items : nullptr;
+    // at the cap of 256 obstacles 54 KB (static) or 62 KB (moving) of dynamic LDS: above 48 KB, which a block may have once it asks
+    const size_t lds = (size_t)O * (mv ? Rule<true>::STRIDE : Rule<false>::STRIDE) * sizeof(double);
+    const void* kernel = mv ? reinterpret_cast<const void*>(ik_kernel<true>) : reinterpret_cast<const void*>(ik_kernel<false>);
+    ARMOUR_TRY(grant_dynamic_lds(who, kernel, lds));
     ARMOUR_TRY(ev.record_start(st));
-    hipLaunchKernelGGL(ik_kernel, dim3((unsigned)N), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, rb, dev);
+    if (mv) hipLaunchKernelGGL(ik_kernel<true>, dim3((unsigned)N), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
+    else hipLaunchKernelGGL(ik_kernel<false>, dim3((unsigned)N), dim3(TP_BLOCK), lds, st, rb, dev, dmv);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
     ARMOUR_TRY(out.fetch(st));
@@ -363,13 +380,61 @@ extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, co
     if (flags) HIPCHK(hipMemcpyAsync(flags, d_items + items, items * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    out.copy_out(0, status);
+    out.copy_out(0, ar.status);
     out.copy_out(1, best);
     // only the rows that were written come back (a target without a pick leaves the caller's row as it was)
     for (int32_t t = 0; t < N; t++)
         if (best[t] >= 0) HIPCHK(hipMemcpyAsync(q_best + (size_t)t * n, d_qbest + (size_t)t * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return ARMOUR_OK;
+}
+
+// an entry's arguments into the call record (the moving entries' three go beside it, in a Motion)
+IkCall ik_call(const double* lb, const double* ub, const double* tool, int32_t N, int32_t S, int32_t W, int32_t O, const double* obstacles, const int32_t* world,
+               const double* targets, const double* q_ref, const uint64_t* seeds, double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status,
+               int32_t* best, double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags) {
+    IkCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.tool_in = tool; ar.N = N; ar.S = S; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.world = world; ar.targets = targets;
+    ar.q_ref = q_ref; ar.seeds = seeds; ar.lambda = lambda; ar.e_max = e_max; ar.tol = tol; ar.max_iterations = max_iterations; ar.status = status; ar.best = best;
+    ar.q_best = q_best; ar.q = q; ar.err = err; ar.iterations = iterations; ar.flags = flags;
+    return ar;
+}
+
+}  // namespace
+
+extern "C" int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
+                              int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds,
+                              double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err,
+                              int32_t* iterations, int32_t* flags, double* margin) {
+    IkCall ar = ik_call(lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best, q_best, q, err, iterations, flags);
+    return solve_on_host("armour_ik_host", robot, continuous, ar, nullptr, margin);
+}
+
+extern "C" int armour_ik_moving_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
+                                     int32_t W, int32_t O, const double* obstacles, const double* velocity, const double* t_from, const double* t_to,
+                                     const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds, double lambda, double e_max, double tol,
+                                     int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags,
+                                     double* margin) {
+    IkCall ar = ik_call(lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best, q_best, q, err, iterations, flags);
+    const Motion mv{velocity, t_from, t_to};
+    return solve_on_host("armour_ik_moving_host", robot, continuous, ar, &mv, margin);
+}
+
+extern "C" int armour_ik(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S, int32_t W,
+                         int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds, double lambda,
+                         double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err,
+                         int32_t* iterations, int32_t* flags, double* ms) {
+    IkCall ar = ik_call(lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best, q_best, q, err, iterations, flags);
+    return solve_on_device("armour_ik", "armour_ik_host", robot, continuous, ar, nullptr, ms);
+}
+
+extern "C" int armour_ik_moving(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N, int32_t S,
+                                int32_t W, int32_t O, const double* obstacles, const double* velocity, const double* t_from, const double* t_to, const int32_t* world,
+                                const double* targets, const double* q_ref, const uint64_t* seeds, double lambda, double e_max, double tol, int32_t max_iterations,
+                                int32_t* status, int32_t* best, double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags, double* ms) {
+    IkCall ar = ik_call(lb, ub, tool, N, S, W, O, obstacles, world, targets, q_ref, seeds, lambda, e_max, tol, max_iterations, status, best, q_best, q, err, iterations, flags);
+    const Motion mv{velocity, t_from, t_to};
+    return solve_on_device("armour_ik_moving", "armour_ik_moving_host", robot, continuous, ar, &mv, ms);
 }
 
 extern "C" int armour_ik_end_effector_host(const ArmourRobot* robot, int32_t N, const double* q, const double* tool, double* p, double* jac) {

@@ -8,7 +8,9 @@
 // takes block_first and ws_tree.hip block_any / block_scan / block_argmin, and each of the two keeps the rest inline, where the shared form
 // measured slower.  The argument rules and the staging loop of all four kernels' host entries are here as well.
 // The tree planner and the shortener judge by the static rule or, in their moving entries, by the window rule: both reach
-// the rule and the stride of a staged obstacle through Rule<MOVING> below and nowhere else.
+// the rule and the stride of a staged obstacle through Rule<MOVING> below and nowhere else.  So do the inverse kinematics (its free test is
+// Rule::config) and the workspace trees (ws_tree.hip), whose test of an axis-aligned box against one staged obstacle is Rule::box
+// (DESIGN.md 4.16c).
 #pragma once
 #include <climits>
 #include <cmath>
@@ -46,8 +48,16 @@ __host__ __device__ inline int prefix_segments(const RmRobot& rb, const double* 
 // two host twins reach config_free / config_free_moving and the stride of a staged obstacle.  Rule<false>: the static rule (stride
 // RM_OBS_STRIDE).  Rule<true>: the window rule of armour_roadmap_check_moving (stride RM_MOV_STRIDE) with the world's mid and half.
 // from(o0) is the view of the obstacles o0, o0 + 1, ...: what the obstacle split hands a lane.
+// box(x, h, o, ...): the workspace trees' test, the axis-aligned box (centre x, axes e_0 e_1 e_2, half-sizes h) against staged obstacle o of
+// the view, pair_separated's verdict or (full) clearance.  Rule<true>: the box over the world's window, centre x - v_o mid and every
+// half-size h_i + |v_o| half -- the obstacle leaves its mid pose by at most |v_o| half in the 2-norm, which the growth along every axis
+// covers; v = 0 leaves x and h as they are, bit for bit.
 template <bool MOVING>
 struct Rule;
+__host__ __device__ inline bool box_separated(const double* x, const double* h, const double* ob, bool full, double* value) {
+    const double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    return pair_separated(x, E, h, ob, full, value);
+}
 template <>
 struct Rule<false> {
     static constexpr int STRIDE = RM_OBS_STRIDE;
@@ -55,6 +65,9 @@ struct Rule<false> {
     __host__ __device__ Rule from(int o0) const { return Rule{obs + (size_t)o0 * STRIDE}; }
     __host__ __device__ bool config(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], int O, bool full, double* clearance) const {
         return config_free(rb, q, r, obs, O, full, clearance);
+    }
+    __host__ __device__ bool box(const double (&x)[3], const double (&h)[3], int o, bool full, double* value) const {
+        return box_separated(x, h, obs + (size_t)o * STRIDE, full, value);
     }
 };
 template <>
@@ -65,6 +78,15 @@ struct Rule<true> {
     __host__ __device__ Rule from(int o0) const { return Rule{obs + (size_t)o0 * STRIDE, mid, half}; }
     __host__ __device__ bool config(const RmRobot& rb, double (&q)[ARMOUR_MAX_FACTORS], double (&r)[ARMOUR_MAX_JOINTS], int O, bool full, double* clearance) const {
         return config_free_moving(rb, q, r, obs, O, mid, half, full, clearance);
+    }
+    __host__ __device__ bool box(const double (&x)[3], const double (&h)[3], int o, bool full, double* value) const {
+        const double* ob = obs + (size_t)o * STRIDE;
+        const double* v = ob + RM_OBS_STRIDE;
+        const double grow = v[3] * half;
+        double xs[3], s[3];
+        for (int i = 0; i < 3; i++) xs[i] = x[i] - v[i] * mid;
+        for (int i = 0; i < 3; i++) s[i] = h[i] + grow;
+        return box_separated(xs, s, ob, full, value);
     }
 };
 // what a moving kernel reads besides the static one's arguments (device pointers): velocity [W][O][3], mid / half [W]

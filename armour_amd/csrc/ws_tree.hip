@@ -5,6 +5,9 @@
 // and the cost of a node -- is written once below as __host__ __device__ code, run by the kernel's lanes and by armour_ws_tree_plan_host's loop.
 // The resident trees (armour_ws_trees_*, at the end of this file) are the same run resumed: the kernel's RESUMED form and the host loop with a
 // world's state go on from the tree, the iteration index and the rewire count that a handle keeps between calls.
+// The moving entries (armour_ws_tree_plan_moving) run the same loop with every box judged over its world's window: kernel and twin reach the
+// box test and the stride of a staged obstacle through tree_block.h's Rule<MOVING> and nowhere else.  The resident trees
+// stay static.
 //
 // Nothing but __syncthreads() orders the block: a tree's nodes live in global memory, written and read by this block alone (keeping them
 // in LDS was measured and is a few per cent faster only where it fits, up to ~1700 nodes: DESIGN.md 4.12f); every decision
@@ -73,28 +76,30 @@ __host__ __device__ inline void ws_sub_box(const double* a, const double (&D)[3]
         h[i] = buf + fabs(D[i]) / two_S;
     }
 }
-// the box (x, e_0 e_1 e_2, h) against the staged obstacles [o0, o1): true when every one separates (verdict mode)
-__host__ __device__ inline bool ws_box_free(const double (&x)[3], const double (&h)[3], const double* obs, int o0, int o1) {
-    const double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+// the box (x, e_0 e_1 e_2, h) against the staged obstacles [o0, o1) of the rule's view: true when every one separates (verdict mode).
+// The rule (tree_block.h, Rule<MOVING>::box) is the static test or the window's, and holds the stride of the staging.
+template <class R>
+__host__ __device__ inline bool ws_box_free(const double (&x)[3], const double (&h)[3], const R& rule, int o0, int o1) {
     for (int o = o0; o < o1; o++)
-        if (!pair_separated(x, E, h, obs + (size_t)o * RM_OBS_STRIDE, false, nullptr)) return false;
+        if (!rule.box(x, h, o, false, nullptr)) return false;
     return true;
 }
 // min over the obstacles of the pair clearance of that box (+inf without obstacles): what the host twin's margin is made of
-inline double ws_box_clearance(const double (&x)[3], const double (&h)[3], const double* obs, int O) {
-    const double E[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+template <class R>
+inline double ws_box_clearance(const double (&x)[3], const double (&h)[3], const R& rule, int O) {
     double cl = INFINITY;
     for (int o = 0; o < O; o++) {
         double v;
-        pair_separated(x, E, h, obs + (size_t)o * RM_OBS_STRIDE, true, &v);
+        rule.box(x, h, o, true, &v);
         cl = std::fmin(cl, v);
     }
     return cl;
 }
-__host__ __device__ inline bool ws_sub_free(const double* a, const double (&D)[3], int s, int S, double buf, const double* obs, int o0, int o1) {
+template <class R>
+__host__ __device__ inline bool ws_sub_free(const double* a, const double (&D)[3], int s, int S, double buf, const R& rule, int o0, int o1) {
     double x[3], h[3];
     ws_sub_box(a, D, s, S, buf, x, h);
-    return ws_box_free(x, h, obs, o0, o1);
+    return ws_box_free(x, h, rule, o0, o1);
 }
 // the sample of iteration i
 __host__ __device__ inline void ws_sample(const WsArgs& a, uint64_t seed, int i, const double* goal, double (&qr)[3]) {
@@ -125,23 +130,34 @@ struct WsShared {
 };
 
 // the edge a -> a + D of S sub-segments, dealt to the lanes in chunks of TP_BLOCK: free when every sub-segment separates
-__device__ inline bool block_edge_free(WsShared& sh, const double* a, const double (&D)[3], int S, double buf, const double* s_obs, int O) {
+template <class R>
+__device__ inline bool block_edge_free(WsShared& sh, const double* a, const double (&D)[3], int S, double buf, const R& rule, int O) {
     bool hit = false;
-    for (int s = threadIdx.x; s < S; s += TP_BLOCK) hit = hit || !ws_sub_free(a, D, s, S, buf, s_obs, 0, O);
+    for (int s = threadIdx.x; s < S; s += TP_BLOCK) hit = hit || !ws_sub_free(a, D, s, S, buf, rule, 0, O);
     return !block_any(sh.any, hit);
 }
 
-// grid W, dynamic LDS [O][RM_OBS_STRIDE] doubles.  The tree of world w: nodes [w][max_nodes][3], parent / node_cost / node_len [w][max_nodes].
+// grid W, dynamic LDS [O][Rule<MOVING>::STRIDE] doubles.  The tree of world w: nodes [w][max_nodes][3], parent / node_cost / node_len [w][max_nodes].
 // RESUMED (armour_ws_trees_grow; grid L): slot l = blockIdx.x serves world w = worlds[l] -- the start and every output are slot l's, the
 // obstacles, the goal, the seed and the tree world w's -- and the tree goes on from state[w]: a planted tree (count > 0) skips the start test,
 // iteration i of this launch is iteration base + i of the world, and the state is written back at the end.  Not resumed, l = w, base = 0 and
 // every `RESUMED` below is a constant: the plan kernel is the code it was.
-template <bool RESUMED>
-__global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
-    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE]
+// MOVING (armour_ws_tree_plan_moving; never RESUMED): the window rule -- dynamic LDS [O][RM_MOV_STRIDE], mv.velocity [W][O][3], mv.mid / mv.half
+// [W], this world's two kept in registers.  The static instantiations read nothing of mv.  Every box test below goes through `rule`.
+template <bool RESUMED, bool MOVING>
+__global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar, MovingArgs mv) {
+    static_assert(!(RESUMED && MOVING), "the resident trees stay static");
+    extern __shared__ double s_obs[];   // [O][RM_OBS_STRIDE], MOVING: [O][RM_MOV_STRIDE]
     __shared__ WsShared sh;
     const int l = blockIdx.x, w = RESUMED ? ar.worlds[l] : l, t = threadIdx.x, O = ar.O, cap = ar.max_nodes;
-    stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    Rule<MOVING> rule{s_obs};
+    if constexpr (MOVING) {
+        rule.mid = mv.mid[w];
+        rule.half = mv.half[w];
+        stage_obstacles_moving_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, mv.velocity + (size_t)w * O * 3, O, s_obs);
+    } else {
+        stage_obstacles_lds<TP_BLOCK>(ar.obstacles + (size_t)w * O * ARMOUR_OBS_DOUBLES, O, s_obs);
+    }
     for (int c = t; c < cap; c += TP_BLOCK) sh.free_[c] = 0;
     const uint64_t seed = ar.seeds[w];
     const double buf = ar.buffer, rr2 = ar.rewire_radius * ar.rewire_radius;
@@ -173,7 +189,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
     bool hit = false;
     if (!planted) {
         const double h[3] = {buf, buf, buf};
-        for (int o = t; o < O; o += TP_BLOCK) hit = hit || !ws_box_free(start, h, s_obs, o, o + 1);
+        for (int o = t; o < O; o += TP_BLOCK) hit = hit || !ws_box_free(start, h, rule, o, o + 1);
     }
     if (planted || !block_any(sh.any, hit)) {
         if (!planted) {
@@ -189,7 +205,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
 #pragma unroll
             for (int j = 0; j < 3; j++) x[j] = ar.init[((size_t)w * ar.max_init + c) * 3 + j];
             const double d = sqrt(ws_diff(prev, x, D));
-            if (!block_edge_free(sh, prev, D, ws_segments(d, ar.edge_step), buf, s_obs, O)) break;
+            if (!block_edge_free(sh, prev, D, ws_segments(d, ar.edge_step), buf, rule, O)) break;
             prev_cost = prev_cost + d;
             if (t < 3) nx[(size_t)cnt * 3 + t] = pick3(x, t);
             if (t == 0) { par[cnt] = cnt - 1; nlen[cnt] = d; ncost[cnt] = prev_cost; }
@@ -257,7 +273,7 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
                         const int first = lo ? sh.end[lo - 1] : 0;
                         const double* xc = nx + (size_t)sh.cand[lo] * 3;
                         ws_diff(xc, qn, D);
-                        if (!ws_sub_free(xc, D, it - first, sh.end[lo] - first, buf, s_obs, o0, o1)) sh.hit[lo] = 1;   // every lane that stores, stores this 1
+                        if (!ws_sub_free(xc, D, it - first, sh.end[lo] - first, buf, rule, o0, o1)) sh.hit[lo] = 1;   // every lane that stores, stores this 1
                     }
                 }
                 __syncthreads();
@@ -364,19 +380,20 @@ __global__ __launch_bounds__(TP_BLOCK) void ws_tree_kernel(WsArgs ar) {
 }
 
 // ---- the host twin: the same functions in a loop.  margin (may be null): min |clearance| over the checks that decide.
+template <class R>
 struct WsHost {
-    const double* obs;
+    R rule;
     int O;
     double buf, edge_step;
     double* margin;
 
     void note(const double (&x)[3], const double (&h)[3]) const {
-        if (margin) *margin = std::fmin(*margin, std::fabs(ws_box_clearance(x, h, obs, O)));
+        if (margin) *margin = std::fmin(*margin, std::fabs(ws_box_clearance(x, h, rule, O)));
     }
     bool point(const double* p) const {
         const double x[3] = {p[0], p[1], p[2]}, h[3] = {buf, buf, buf};
         note(x, h);
-        return ws_box_free(x, h, obs, 0, O);
+        return ws_box_free(x, h, rule, 0, O);
     }
     // prefix(a, b): sub-segments in ascending order up to the first that does not separate; free when m == S
     bool edge(const double* a, const double* b) const {
@@ -386,7 +403,7 @@ struct WsHost {
             double x[3], h[3];
             ws_sub_box(a, D, s, S, buf, x, h);
             note(x, h);
-            if (!ws_box_free(x, h, obs, 0, O)) return false;
+            if (!ws_box_free(x, h, rule, 0, O)) return false;
         }
         return true;
     }
@@ -394,14 +411,15 @@ struct WsHost {
 
 // slot l = world w of the host twin (the plan entry: l = w); the tree goes to nx [max_nodes][3] / par / ncost / nlen [max_nodes] (the caller's
 // rows or scratch).  state (null: the plan entry): world w's WS_STATE words of a handle -- the run resumes the tree they describe, as the
-// kernel's resumed form does, and writes them back.
-void plan_world_host(const WsArgs& ar, int l, int w, const double* obs, double* nx, int32_t* par, double* ncost, double* nlen, double* margin, int32_t* state) {
+// kernel's resumed form does, and writes them back.  rule: the world's staged obstacles with the static rule or its window's; O their number.
+template <class R>
+void plan_world_host(const WsArgs& ar, int l, int w, const R& rule, double* nx, int32_t* par, double* ncost, double* nlen, double* margin, int32_t* state) {
     const int cap = ar.max_nodes;
     const double* goal = ar.goals + (size_t)w * 3;
     const uint64_t seed = ar.seeds[w];
     const double rr2 = ar.rewire_radius * ar.rewire_radius;
     if (margin) *margin = INFINITY;
-    const WsHost hw{obs, ar.O, ar.buffer, ar.edge_step, margin};
+    const WsHost<R> hw{rule, ar.O, ar.buffer, ar.edge_step, margin};
     double D[3];
     int cnt = state ? state[0] : 0, rewires = state ? state[2] : 0, kept = 0;
     const int base = state ? state[1] : 0;
@@ -561,64 +579,60 @@ int check_args(const char* who, WsCall* ar) {
     return ARMOUR_OK;
 }
 
-}  // namespace
-
-extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
-                                        const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
-                                        double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
-                                        int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
-                                        double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost,
-                                        double* margin) {
-    const char* who = "armour_ws_tree_plan_host";
-    WsCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds; ar.max_init = max_init;
-    ar.init = init; ar.init_count = init_count; ar.step = step; ar.edge_step = edge_step; ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate;
-    ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points; ar.status = status;
-    ar.iterations = iterations; ar.points = points; ar.rewires = rewires; ar.chain_kept = chain_kept; ar.path_cost = path_cost; ar.goal_dist = goal_dist;
-    ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent; ar.node_cost = node_cost;
+// the host twin of both rules (mv null: the static one)
+int plan_on_host(const char* who, WsCall& ar, const Motion* mv, double* margin) {
     ARMOUR_TRY(check_args(who, &ar));
-    const size_t cap = (size_t)max_nodes;
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    const size_t cap = (size_t)ar.max_nodes;
+    double *nodes = ar.nodes, *node_cost = ar.node_cost;
+    int32_t* parent = ar.parent;
     std::vector<double> own_nodes(nodes ? 0 : cap * 3), own_cost(node_cost ? 0 : cap), len(cap);
     std::vector<int32_t> own_parent(parent ? 0 : cap);
-    for_each_staged(W, O, obstacles, nullptr, [&](int32_t w, const Rule<false>& staged, int) {
-        plan_world_host(ar, w, w, staged.obs, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
+    auto world = [&](int32_t w, const auto& rule, int) {
+        plan_world_host(ar, w, w, rule, nodes ? nodes + (size_t)w * cap * 3 : own_nodes.data(), parent ? parent + (size_t)w * cap : own_parent.data(),
                         node_cost ? node_cost + (size_t)w * cap : own_cost.data(), len.data(), margin ? margin + w : nullptr, nullptr);
-    });
-    return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
+    };
+    if (mv) for_each_staged<true>(ar.W, ar.O, ar.obstacles, nullptr, world, mv->velocity, mid.data(), half.data());
+    else for_each_staged(ar.W, ar.O, ar.obstacles, nullptr, world);
+    return armour_check_path_capacity(who, ar.W, ar.points, ar.max_points, ar.path != nullptr);
 }
 
-extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
-                                   const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
-                                   double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
-                                   int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
-                                   double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* ms) {
-    const char* who = "armour_ws_tree_plan";
-    WsCall ar{};
-    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds; ar.max_init = max_init;
-    ar.init = init; ar.init_count = init_count; ar.step = step; ar.edge_step = edge_step; ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate;
-    ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points; ar.status = status;
-    ar.iterations = iterations; ar.points = points; ar.rewires = rewires; ar.chain_kept = chain_kept; ar.path_cost = path_cost; ar.goal_dist = goal_dist;
-    ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent; ar.node_cost = node_cost;
+// the device entry of both rules (mv null: the static one)
+int plan_on_device(const char* who, const char* host_form, WsCall& ar, const Motion* mv, double* ms) {
     ARMOUR_TRY(check_args(who, &ar));
+    std::vector<double> mid, half;
+    if (mv) ARMOUR_TRY(check_windows(who, ar.W, ar.O, *mv, &mid, &half));
+    const int32_t W = ar.W, O = ar.O, max_nodes = ar.max_nodes, max_points = ar.max_points, max_init = ar.max_init;
+    const double* init = ar.init;
+    int32_t *points = ar.points, *parent = ar.parent;
+    double *path = ar.path, *nodes = ar.nodes, *node_cost = ar.node_cost;
     if (ms) *ms = 0.0;
     if (W == 0) return ARMOUR_OK;
-    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (armour_ws_tree_plan_host is the host form)", who); return ARMOUR_EDEVICE; }
+    if (!armour_device_available()) { armour_set_error("%s: no HIP device visible (%s is the host form)", who, host_form); return ARMOUR_EDEVICE; }
     const size_t cap = (size_t)max_nodes, rows = (size_t)W * cap, path_len = path ? (size_t)W * max_points * 3 : 0;
     DevStream st;
     EventPair ev;
-    DevBuf<double> d_obs, d_starts, d_goals, d_init, d_nodes, d_cost, d_len, d_path;
+    DevBuf<double> d_obs, d_starts, d_goals, d_init, d_nodes, d_cost, d_len, d_path, d_vel, d_mid, d_half;
     DevBuf<uint64_t> d_seeds;
     DevBuf<int32_t> d_init_count, d_parent;
     DevColumns<int32_t> out;                                // status | iterations | points | rewires | chain_kept | count [W] each
     DevColumns<double> real;                                // path_cost | goal_dist [W] each
     ARMOUR_TRY(st.create());
-    ARMOUR_TRY(d_obs.upload(obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
-    ARMOUR_TRY(d_starts.upload(starts, (size_t)W * 3, st));
-    ARMOUR_TRY(d_goals.upload(goals, (size_t)W * 3, st));
-    ARMOUR_TRY(d_seeds.upload(seeds, (size_t)W, st));
+    ARMOUR_TRY(d_obs.upload(ar.obstacles, (size_t)W * O * ARMOUR_OBS_DOUBLES, st));
+    ARMOUR_TRY(d_starts.upload(ar.starts, (size_t)W * 3, st));
+    ARMOUR_TRY(d_goals.upload(ar.goals, (size_t)W * 3, st));
+    ARMOUR_TRY(d_seeds.upload(ar.seeds, (size_t)W, st));
     if (init) {
         ARMOUR_TRY(d_init.upload(init, (size_t)W * max_init * 3, st));
-        ARMOUR_TRY(d_init_count.upload(init_count, (size_t)W, st));
+        ARMOUR_TRY(d_init_count.upload(ar.init_count, (size_t)W, st));
+    }
+    MovingArgs dmv{};
+    if (mv) {
+        ARMOUR_TRY(d_vel.upload(mv->velocity, (size_t)W * O * 3, st));
+        ARMOUR_TRY(d_mid.upload(mid.data(), (size_t)W, st));
+        ARMOUR_TRY(d_half.upload(half.data(), (size_t)W, st));
+        dmv = MovingArgs{d_vel, d_mid, d_half};
     }
     ARMOUR_TRY(d_nodes.reserve(rows * 3));
     ARMOUR_TRY(d_cost.reserve(rows));
@@ -634,19 +648,24 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
     dev.chain_kept = out.column(4); dev.count = out.column(5);
     dev.path_cost = real.column(0); dev.goal_dist = real.column(1);
     dev.parent = d_parent; dev.nodes = d_nodes; dev.node_cost = d_cost; dev.node_len = d_len; dev.path = path ? d_path.p : nullptr;
+    // at the cap of 256 obstacles 54 KB (static) or 62 KB (moving) of dynamic LDS: above 48 KB, which a block may have once it asks
+    const size_t lds = (size_t)O * (mv ? Rule<true>::STRIDE : Rule<false>::STRIDE) * sizeof(double);
+    const void* kernel = mv ? reinterpret_cast<const void*>(ws_tree_kernel<false, true>) : reinterpret_cast<const void*>(ws_tree_kernel<false, false>);
+    ARMOUR_TRY(grant_dynamic_lds(who, kernel, lds));
     ARMOUR_TRY(ev.record_start(st));
-    hipLaunchKernelGGL(ws_tree_kernel<false>, dim3((unsigned)W), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, dev);
+    if (mv) hipLaunchKernelGGL((ws_tree_kernel<false, true>), dim3((unsigned)W), dim3(TP_BLOCK), lds, st, dev, dmv);
+    else hipLaunchKernelGGL((ws_tree_kernel<false, false>), dim3((unsigned)W), dim3(TP_BLOCK), lds, st, dev, dmv);
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(ev.record_stop(st));
     ARMOUR_TRY(out.fetch(st));
     ARMOUR_TRY(real.fetch(st));
     HIPCHK(hipStreamSynchronize(st));
     if (ms) ARMOUR_TRY(ev.elapsed_ms(ms));
-    int32_t* const ints[6] = {status, iterations, points, rewires, chain_kept, count};
+    int32_t* const ints[6] = {ar.status, ar.iterations, points, ar.rewires, ar.chain_kept, ar.count};
     for (int k = 0; k < 6; k++) out.copy_out(k, ints[k]);
     const int32_t* h_count = out.fetched(5);
-    real.copy_out(0, path_cost);
-    real.copy_out(1, goal_dist);
+    real.copy_out(0, ar.path_cost);
+    real.copy_out(1, ar.goal_dist);
     // the trees and the paths: only the rows that were written come back (the rest of the caller's arrays is left as it was)
     for (int32_t w = 0; w < W; w++) {
         const size_t c = (size_t)h_count[w], row = (size_t)w * cap;
@@ -658,6 +677,67 @@ extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W
     }
     HIPCHK(hipStreamSynchronize(st));
     return armour_check_path_capacity(who, W, points, max_points, path != nullptr);
+}
+
+// an entry's arguments into the call record (the moving entries' three go beside it, in a Motion)
+WsCall ws_call(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals, const uint64_t* seeds,
+               int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step, double rewire_radius, double goal_rate, double buffer,
+               double goal_tol, int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires,
+               int32_t* chain_kept, double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost) {
+    WsCall ar{};
+    ar.box_lb = lb; ar.box_ub = ub; ar.W = W; ar.O = O; ar.obstacles = obstacles; ar.starts = starts; ar.goals = goals; ar.seeds = seeds; ar.max_init = max_init;
+    ar.init = init; ar.init_count = init_count; ar.step = step; ar.edge_step = edge_step; ar.rewire_radius = rewire_radius; ar.goal_rate = goal_rate;
+    ar.buffer = buffer; ar.goal_tol = goal_tol; ar.max_iterations = max_iterations; ar.max_nodes = max_nodes; ar.max_points = max_points; ar.status = status;
+    ar.iterations = iterations; ar.points = points; ar.rewires = rewires; ar.chain_kept = chain_kept; ar.path_cost = path_cost; ar.goal_dist = goal_dist;
+    ar.path = path; ar.count = count; ar.nodes = nodes; ar.parent = parent; ar.node_cost = node_cost;
+    return ar;
+}
+
+}  // namespace
+
+extern "C" int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
+                                        const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                                        double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
+                                        int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
+                                        double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost,
+                                        double* margin) {
+    WsCall ar = ws_call(lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                        max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent, node_cost);
+    return plan_on_host("armour_ws_tree_plan_host", ar, nullptr, margin);
+}
+
+extern "C" int armour_ws_tree_plan_moving_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                               const double* t_from, const double* t_to, const double* starts, const double* goals, const uint64_t* seeds,
+                                               int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step, double rewire_radius,
+                                               double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes, int32_t max_points,
+                                               int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost,
+                                               double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* margin) {
+    WsCall ar = ws_call(lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                        max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent, node_cost);
+    const Motion mv{velocity, t_from, t_to};
+    return plan_on_host("armour_ws_tree_plan_moving_host", ar, &mv, margin);
+}
+
+extern "C" int armour_ws_tree_plan(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* starts, const double* goals,
+                                   const uint64_t* seeds, int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                                   double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
+                                   int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
+                                   double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* ms) {
+    WsCall ar = ws_call(lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                        max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent, node_cost);
+    return plan_on_device("armour_ws_tree_plan", "armour_ws_tree_plan_host", ar, nullptr, ms);
+}
+
+extern "C" int armour_ws_tree_plan_moving(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                          const double* t_from, const double* t_to, const double* starts, const double* goals, const uint64_t* seeds,
+                                          int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step, double rewire_radius,
+                                          double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes, int32_t max_points,
+                                          int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost,
+                                          double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* ms) {
+    WsCall ar = ws_call(lb, ub, W, O, obstacles, starts, goals, seeds, max_init, init, init_count, step, edge_step, rewire_radius, goal_rate, buffer, goal_tol,
+                        max_iterations, max_nodes, max_points, status, iterations, points, rewires, chain_kept, path_cost, goal_dist, path, count, nodes, parent, node_cost);
+    const Motion mv{velocity, t_from, t_to};
+    return plan_on_device("armour_ws_tree_plan_moving", "armour_ws_tree_plan_moving_host", ar, &mv, ms);
 }
 
 // ---- resident trees (include/armour_hip.h, armour_ws_trees_*): the trees of W worlds kept between calls and grown in instalments by the
@@ -802,7 +882,7 @@ extern "C" int armour_ws_trees_grow(ArmourWsTrees* h, int32_t L, const int32_t* 
         ar.path_cost = path_cost; ar.goal_dist = goal_dist; ar.path = path;
         for_each_staged(L, O, h->obstacles.data(), worlds, [&](int32_t l, const Rule<false>& staged, int) {
             const size_t row = (size_t)worlds[l] * cap;
-            plan_world_host(ar, l, worlds[l], staged.obs, &h->nodes[row * 3], &h->parent[row], &h->node_cost[row], &h->node_len[row], margin ? margin + l : nullptr,
+            plan_world_host(ar, l, worlds[l], staged, &h->nodes[row * 3], &h->parent[row], &h->node_cost[row], &h->node_len[row], margin ? margin + l : nullptr,
                             &h->state[(size_t)worlds[l] * WS_STATE]);
         });
         return armour_check_path_capacity(who, L, points, max_points, path != nullptr);
@@ -821,8 +901,10 @@ extern "C" int armour_ws_trees_grow(ArmourWsTrees* h, int32_t L, const int32_t* 
     ar.chain_kept = h->out.column(4); ar.count = h->out.column(5);
     ar.path_cost = h->real.column(0); ar.goal_dist = h->real.column(1);
     ar.parent = h->d_parent; ar.nodes = h->d_nodes; ar.node_cost = h->d_cost; ar.node_len = h->d_len; ar.path = path ? h->d_path.p : nullptr;
+    const size_t lds = (size_t)O * Rule<false>::STRIDE * sizeof(double);
+    ARMOUR_TRY(grant_dynamic_lds(who, reinterpret_cast<const void*>(ws_tree_kernel<true, false>), lds));
     ARMOUR_TRY(h->ev.record_start(st));
-    hipLaunchKernelGGL(ws_tree_kernel<true>, dim3((unsigned)L), dim3(TP_BLOCK), (size_t)O * RM_OBS_STRIDE * sizeof(double), st, ar);
+    hipLaunchKernelGGL((ws_tree_kernel<true, false>), dim3((unsigned)L), dim3(TP_BLOCK), lds, st, ar, MovingArgs{});
     HIPCHK(hipGetLastError());
     ARMOUR_TRY(h->ev.record_stop(st));
     ARMOUR_TRY(h->out.fetch(st));

@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from ._lib import _dp, check
 from .scenes import pad_obstacles, straight_line_waypoint
-from .tree_planner import call_seed, sampling_box
+from .tree_planner import _motion, call_seed, sampling_box
 
 NONE_CONVERGED, FOUND, ALL_BLOCKED = _lib.IK_NONE_CONVERGED, _lib.IK_FOUND, _lib.IK_ALL_BLOCKED
 CONVERGED_BIT, FREE_BIT = 1, 2
@@ -55,17 +55,21 @@ def end_effector(robot, Q, tool=None, jacobian=False):
 
 
 def solve_ik(robot, targets, q_ref, obstacles=None, world=None, seeds=0, S=32, tool=None, lb=None, ub=None, continuous=None, lam=0.05, e_max=0.1, tol=1e-9,
-             max_iterations=200, host=False, details=False):
+             max_iterations=200, host=False, details=False, velocity=None, t_from=None, t_to=None):
     """targets [N,3], q_ref [N,n] (or [n] for all), obstacles [W,O,12] (or [O,12]: W = 1; None: no obstacles), world [N] (the world of every
     target, -1: none; default: target i in world i when W == N, else world 0), seeds [N] (uint64, or one for all) -> IKSolutions.  S start
     points per target: q_ref, then S - 1 points of the box lb / ub (default: tree_planner.sampling_box).  host=True: the same rule in the
-    library's host loop (no device), which also reports `margin`."""
+    library's host loop (no device), which also reports `margin`.
+    velocity [W,O,3] with t_from / t_to ([W] or scalars): the obstacles move in a line from their poses `obstacles` of world time 0, and the
+    free test of a target is armour_ik_moving's, free at every time of the window of the target's world; all three None (the default): the
+    static entry."""
     L = _lib.load()
     n = robot.num_factors
     tg = np.ascontiguousarray(np.asarray(targets, dtype=np.float64).reshape(-1, 3))
     N = tg.shape[0]
     ref = np.ascontiguousarray(np.broadcast_to(np.asarray(q_ref, dtype=np.float64), (N, n)))
     obs, W, O = _lib.as_worlds(np.zeros((0, 0, 12)) if obstacles is None else obstacles)
+    motion = _motion("solve_ik", W, O, velocity, t_from, t_to)
     if world is None:
         world = np.full(N, -1) if W == 0 else (np.arange(N) if W == N else np.zeros(N))
     wd = np.ascontiguousarray(np.broadcast_to(np.asarray(world, dtype=np.int32), (N,)))
@@ -83,9 +87,12 @@ def solve_ik(robot, targets, q_ref, obstacles=None, world=None, seeds=0, S=32, t
     iterations, flags = np.zeros((N, rows), dtype=np.int32), np.zeros((N, rows), dtype=np.int32)
     margin = np.zeros(N) if host else None
     ms = C.c_double()
-    fn = L.armour_ik_host if host else L.armour_ik
+    if motion is None:
+        fn, mv = L.armour_ik_host if host else L.armour_ik, ()
+    else:
+        fn, mv = L.armour_ik_moving_host if host else L.armour_ik_moving, motion[0]
     check(fn(C.byref(robot), None if cont is None else cont.ctypes.data_as(u8), _dp(lb), _dp(ub), _dp(_tool(tool)), N, S, W, O, _dp(obs) if obs.size else None,
-             wd.ctypes.data_as(i32), _dp(tg), _dp(ref), sd.ctypes.data_as(C.POINTER(C.c_uint64)), float(lam), float(e_max), float(tol), int(max_iterations),
+             *mv, wd.ctypes.data_as(i32), _dp(tg), _dp(ref), sd.ctypes.data_as(C.POINTER(C.c_uint64)), float(lam), float(e_max), float(tol), int(max_iterations),
              status.ctypes.data_as(i32), best.ctypes.data_as(i32), _dp(q_best), _dp(q_all) if details else None, _dp(err) if details else None,
              iterations.ctypes.data_as(i32) if details else None, flags.ctypes.data_as(i32) if details else None, _dp(margin) if host else C.byref(ms)))
     out = IKSolutions(status=status, best=best, q=q_best, margin=margin, ms=0.0 if host else ms.value)

@@ -14,6 +14,14 @@ are solved by one armour_ik call:
     res = trees.grow(worlds, starts, 100)                                  # 100 more iterations for the listed worlds -> WorkspacePlans
     out = run_trials(worlds, hlp=workspace_hlps(worlds, robot, mode='keep', max_iterations=100, max_nodes=4096))
 
+Obstacles in linear motion: plan_workspace_trees and ik.solve_ik take velocity, t_from and t_to and then judge every box, and every inverse-
+kinematics solution, by the window rule (armour_ws_tree_plan_moving, armour_ik_moving: free at every time of the world's window);
+WorkspaceTreeHLP takes a velocity and a horizon and keeps a world clock (set_world_time), and moving_workspace_hlps is workspace_hlps for
+run_trials(velocities=...).  The resident trees stay static:
+
+    res = plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, velocity=vel, t_from=t, t_to=t + horizon)     # vel [W,O,3]
+    out = run_trials(worlds, hlp=moving_workspace_hlps(worlds, robot, velocities, mode="seed"), velocities=velocities)
+
 The rule (point and edge tests, samples, parent choice, rewiring, cost re-derivation, best node), its two deliberate departures from the
 reference, the soundness arguments and the limits are stated in include/armour_hip.h; DESIGN.md 4.12f, and 4.12g for the resident trees.
 """
@@ -25,7 +33,7 @@ from . import _lib
 from ._lib import _dp, check
 from . import ik
 from .scenes import pad_obstacles
-from .tree_planner import call_seed, hlp_factory
+from .tree_planner import _motion, call_seed, hlp_factory
 
 PARTIAL, REACHED, START_BLOCKED = _lib.WS_PARTIAL, _lib.WS_REACHED, _lib.WS_START_BLOCKED
 
@@ -53,14 +61,18 @@ def workspace_box(robot, tool=None):
 
 
 def plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, step=STEP, edge_step=EDGE_STEP, rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE, buffer=0.0,
-                         goal_tol=GOAL_TOL, max_iterations=MAX_ITERATIONS, max_nodes=MAX_NODES, init=None, host=False, trees=False, max_points=None):
+                         goal_tol=GOAL_TOL, max_iterations=MAX_ITERATIONS, max_nodes=MAX_NODES, init=None, host=False, trees=False, max_points=None, velocity=None,
+                         t_from=None, t_to=None):
     """obstacles [W,O,12] (or [O,12]: W = 1), starts / goals [W,3] (points of the workspace), seeds [W] (uint64), lb / ub [3] (the sampling box)
     -> WorkspacePlans.  edge_step and goal_rate default to the reference's (arm_end_effector_RRT_star_HLP.m:5, RRT_star_HLP.m:24); step,
     rewire_radius and goal_tol are arm-sized (see STEP above).  rewire_radius = 0 is plain RRT.  init: None, or W entries, each None or a
     chain [C,3] offered before the loop (the reference's 'seed' mode).  max_points: the path rows to reserve (default: max_nodes, which a
-    path cannot exceed).  host=True: the same rule in the library's host loop (no device), which also reports `margin`."""
+    path cannot exceed).  host=True: the same rule in the library's host loop (no device), which also reports `margin`.
+    velocity [W,O,3] with t_from / t_to ([W] or scalars): the obstacles move in a line from their poses `obstacles` of world time 0, and
+    every box test is armour_ws_tree_plan_moving's window rule on [t_from[w], t_to[w]]; all three None (the default): the static entry."""
     L = _lib.load()
     obs, W, O = _lib.as_worlds(obstacles)
+    motion = _motion("plan_workspace_trees", W, O, velocity, t_from, t_to)
     s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(W, 3))
     g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(W, 3))
     sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (W,)))
@@ -86,8 +98,11 @@ def plan_workspace_trees(obstacles, starts, goals, seeds, lb, ub, step=STEP, edg
     nodes, parent, node_cost = np.zeros((W, rows, 3)), np.zeros((W, rows), dtype=np.int32), np.zeros((W, rows))
     margin = np.zeros(W) if host else None
     ms = C.c_double()
-    fn = L.armour_ws_tree_plan_host if host else L.armour_ws_tree_plan
-    check(fn(_dp(lb), _dp(ub), W, O, _dp(obs) if obs.size else None, _dp(s), _dp(g), sd.ctypes.data_as(C.POINTER(C.c_uint64)), max_init, _dp(chain),
+    if motion is None:
+        fn, mv = L.armour_ws_tree_plan_host if host else L.armour_ws_tree_plan, ()
+    else:
+        fn, mv = L.armour_ws_tree_plan_moving_host if host else L.armour_ws_tree_plan_moving, motion[0]
+    check(fn(_dp(lb), _dp(ub), W, O, _dp(obs) if obs.size else None, *mv, _dp(s), _dp(g), sd.ctypes.data_as(C.POINTER(C.c_uint64)), max_init, _dp(chain),
              None if chain_count is None else chain_count.ctypes.data_as(i32), float(step), float(edge_step), float(rewire_radius), float(goal_rate), float(buffer),
              float(goal_tol), int(max_iterations), cap, max_points, status.ctypes.data_as(i32), iterations.ctypes.data_as(i32), points.ctypes.data_as(i32),
              rewires.ctypes.data_as(i32), chain_kept.ctypes.data_as(i32), _dp(path_cost), _dp(goal_dist), _dp(path), count.ctypes.data_as(i32),
@@ -223,18 +238,38 @@ class WorkspaceTreeHLP:
         at the first waypoint) and `slot` this world's index there -- made from this world's padded obstacles, goal POINT and
         call_seed(seed, world, 0), as workspace_hlps does for all its worlds at once; whoever made the handle closes it.  mode='keep'
         without `trees` is a ValueError.
+    velocity [O,3] (default None: a static world, today's calls): the obstacles move in a line from their poses `world_obstacles` of world
+      time 0.  Both launches of a call -- the tree (with its 'seed' chain) and the inverse kinematics -- then judge by the window rule on
+      [t, t + horizon], t the world time of the last set_world_time (0 before the first) and horizon the plan's duration unless given.  With
+      mode='seed' the chain ends at its first edge that the new window blocks.  A waypoint without a solution free over the window falls
+      back to the goal configuration.  mode='keep' with a velocity is a ValueError: the resident trees stay static.
     plan_options go to plan_workspace_trees (step, edge_step, rewire_radius, goal_rate, buffer, goal_tol, max_iterations, max_nodes; lb /
     ub default to workspace_box); ik_options go to ik.solve_ik (S, lam, e_max, tol, max_iterations, tool)."""
 
     def __init__(self, robot, world_obstacles, goal, seed=0, world=0, host=False, mode="new", ik_reference="mid", ik_options=None, trees=None, slot=0,
-                 **plan_options):
+                 velocity=None, horizon=None, **plan_options):
         if mode not in ("new", "seed", "keep") or ik_reference not in ("mid", "current"):
             raise ValueError(f"mode = {mode!r} ('new', 'seed' or 'keep'), ik_reference = {ik_reference!r} ('mid' or 'current')")
+        if velocity is None and horizon is not None:
+            raise ValueError("horizon belongs to a moving world: give a velocity")
+        if mode == "keep" and velocity is not None:
+            raise ValueError("mode = 'keep' is for static worlds: a kept tree's edges were proved against windows that have passed")
         if (mode == "keep") != (trees is not None):
             raise ValueError("mode = 'keep' takes the WorkspaceTrees that holds this world's tree (trees=, slot=), and no other mode does")
         self.robot, self.goal, self.seed, self.world, self.host = robot, np.asarray(goal, dtype=np.float64), int(seed), int(world), bool(host)
         self.mode, self.ik_reference = mode, ik_reference
         self.obstacles = np.asarray(world_obstacles, dtype=np.float64).reshape(-1, 12)
+        self.velocity, self.horizon, self.t_world = None, None, 0.0
+        if velocity is not None:
+            self.velocity = np.asarray(velocity, dtype=np.float64).reshape(-1, 3)
+            if self.velocity.shape[0] != self.obstacles.shape[0]:
+                raise ValueError("WorkspaceTreeHLP: one velocity per obstacle")
+            if horizon is None:
+                from .planner import default_params
+                horizon = default_params(1).duration
+            self.horizon = float(horizon)
+            if not self.horizon >= 0.0:
+                raise ValueError(f"horizon = {horizon} (>= 0)")
         self.ik_options = dict(ik_options or {})
         self.options = dict(plan_options)
         lb, ub = workspace_box(robot, self.ik_options.get("tool"))
@@ -250,6 +285,12 @@ class WorkspaceTreeHLP:
         if callable(self.trees):
             self.trees = self.trees()
         return self.trees
+
+    def set_world_time(self, t):
+        """The world time at which the next call plans (a moving world): its window is [t, t + horizon]."""
+        if self.velocity is None:
+            raise ValueError("set_world_time belongs to a moving world: give a velocity")
+        self.t_world = float(t)
 
     def get_waypoint(self, q_cur, lookahead):
         return _waypoints([self], [q_cur], [lookahead])[0][0]
@@ -291,9 +332,16 @@ def _chain(h, z):
 
 def _waypoints(hl, qs, lookaheads):
     """One call of each of the HLPs `hl` (one robot, one obstacle count, the same options) from qs: ONE armour_ws_tree_plan call (mode 'keep': one
-    armour_ws_trees_grow call on the shared handle) and ONE armour_ik call -> (waypoint configurations, the launches' ms)."""
+    armour_ws_trees_grow call on the shared handle) and ONE armour_ik call -> (waypoint configurations, the launches' ms).  Moving worlds (all
+    or none of hl): both launches get the window [t_world, t_world + horizon] of each world."""
     h0 = hl[0]
     robot, host = h0.robot, h0.host
+    if any((h.velocity is None) != (h0.velocity is None) for h in hl):
+        raise ValueError("static and moving worlds cannot share a launch")
+    motion = {}
+    if h0.velocity is not None:
+        t = np.array([h.t_world for h in hl])
+        motion = dict(velocity=np.stack([h.velocity for h in hl]), t_from=t, t_to=t + np.array([h.horizon for h in hl]))
     qs = np.stack([np.asarray(q, dtype=np.float64) for q in qs])
     obstacles = np.stack([h.obstacles for h in hl])
     z = ik.end_effector(robot, qs, h0.ik_options.get("tool")).reshape(-1, 3)
@@ -303,10 +351,10 @@ def _waypoints(hl, qs, lookaheads):
     else:
         chains = [_chain(h, z[k]) for k, h in enumerate(hl)]
         res = plan_workspace_trees(obstacles, z, np.stack([h.goal_point for h in hl]), seeds, init=chains if any(c is not None for c in chains) else None,
-                                   host=host, **h0.options)
+                                   host=host, **h0.options, **motion)
     points = np.stack([z[k] if p is None else waypoint_along_points(p, z[k], la) for k, (p, la) in enumerate(zip(res.paths, lookaheads))])
     goals = np.stack([h.goal for h in hl])
-    sol = ik.solve_ik(robot, points, 0.5 * (qs + goals) if h0.ik_reference == "mid" else qs, obstacles, np.arange(len(hl)), seeds, host=host, **h0.ik_options)
+    sol = ik.solve_ik(robot, points, 0.5 * (qs + goals) if h0.ik_reference == "mid" else qs, obstacles, np.arange(len(hl)), seeds, host=host, **h0.ik_options, **motion)
     out = []
     for k, h in enumerate(hl):
         found = res.paths[k] is not None and sol.status[k] == ik.FOUND
@@ -367,4 +415,45 @@ def workspace_hlps(worlds, robot, seed=0, lookahead=0.1, mode="new", ik_referenc
         shared.clear()
 
     make.close = close
+    return make
+
+
+def moving_workspace_hlps(worlds, robot, velocities, horizon=None, seed=0, lookahead=0.1, mode="new", ik_reference="mid", host=False, ik_options=None, **options):
+    """workspace_hlps(batched=True) for worlds whose obstacles move: `velocities` is a list of [O_w, 3], one per world (padded with zeros as the
+    obstacles are padded with pad_obstacles).  The factory carries set_world_times(t_world [W]), which run_trials(velocities=...) calls
+    before every waypoint query and which sets the clock of every object made so far (and of those made later), and
+    get_waypoints(indices, qs, lookaheads) as workspace_hlps': ONE armour_ws_tree_plan_moving call and ONE armour_ik_moving call for all live
+    worlds, each world judged by the window rule on [t_world[w], t_world[w] + horizon]; make.last_ms is their sum.  horizon=None: the plan's
+    duration (planner.default_params).  mode: 'new' or 'seed' ('keep' is a ValueError: the resident trees stay static).  The planner only
+    proposes waypoints: safety rests on the solver's tables and the moving audit.  Zero velocities give workspace_hlps' waypoints.  Worlds
+    that have finished keep their last clock."""
+    obs = [np.asarray(p["obstacles"], dtype=np.float64).reshape(-1, 12) for _, p in worlds]
+    vel = [np.asarray(v, dtype=np.float64).reshape(-1, 3) for v in velocities]
+    if len(vel) != len(obs) or any(v.shape[0] != o.shape[0] for v, o in zip(vel, obs)):
+        raise ValueError("moving_workspace_hlps: one velocity per obstacle of every world")
+    if mode == "keep":
+        raise ValueError("mode = 'keep' is for static worlds: a kept tree's edges were proved against windows that have passed")
+    O = max([o.shape[0] for o in obs] + [1])
+    vel_p = [np.concatenate([v, np.zeros((O - v.shape[0], 3))]) for v in vel]
+    if horizon is None:
+        from .planner import default_params
+        horizon = default_params(1).duration
+    lookahead = float(lookahead)
+    state = dict(t_world=np.zeros(len(obs)))
+
+    def build(i, obstacles, goal):
+        h = WorkspaceTreeHLP(robot, obstacles, goal, seed=seed, world=i, host=host, mode=mode, ik_reference=ik_reference, ik_options=ik_options,
+                             velocity=vel_p[i], horizon=horizon, **options)
+        h.set_world_time(state["t_world"][i])
+        return h
+
+    make = hlp_factory(worlds, build, lambda hl, qs, _joint_space_lookaheads: _waypoints(hl, qs, [lookahead] * len(hl)), True)
+
+    def set_world_times(t_world):
+        state["t_world"] = np.array(np.broadcast_to(np.asarray(t_world, dtype=np.float64), (len(obs),)))
+        for i, h in make.hlps.items():
+            h.set_world_time(state["t_world"][i])
+
+    make.set_world_times = set_world_times
+    make.last_ms = 0.0
     return make

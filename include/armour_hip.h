@@ -1166,6 +1166,30 @@ int armour_ik_host(const ArmourRobot* robot, const uint8_t* continuous, const do
                    int32_t S, int32_t W, int32_t O, const double* obstacles, const int32_t* world, const double* targets, const double* q_ref,
                    const uint64_t* seeds, double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best,
                    double* q_best, double* q, double* err, int32_t* iterations, int32_t* flags, double* margin);
+/* armour_ik against obstacles in LINEAR MOTION, over a time window per world: the static entry with velocity [W][O][3], t_from and t_to [W]
+ * after obstacles, which are the poses at world time 0 (armour_roadmap_check_moving's arguments).
+ * The rule.  The free test of a converged item of target t is the node rule over the window of the target's world w = world[t]:
+ *   armour_roadmap_check_moving's window rule at (mid[w], half[w]) = (0.5 (t_from[w] + t_to[w]), 0.5 (t_to[w] - t_from[w])), computed once on
+ *   the host -- for obstacle o the box centre x - v_o mid[w] and every half-size h_l + |v_o|_2 half[w].  world[t] = -1 has no obstacles and
+ *   reads no window.  The start points, the damped least-squares iteration, convergence and the pick are word for word the static entry's.
+ * Soundness.  Within [t_from, t_to] obstacle o leaves its pose of time mid by at most |v_o| half, so a configuration that is IK_FOUND meets no
+ *   obstacle of its world at ANY time of the window.
+ * With zero velocities every output is armour_ik's bit for bit, for any window; t_from == t_to judges at an instant.
+ * ARMOUR_EINVAL before a device is touched: armour_ik's refusals; a null or non-finite velocity, t_from or t_to; t_from[w] > t_to[w].  N = 0
+ *   and W = 0 are served as the static entry serves them.
+ * Device: the static launch with RM_OBS_STRIDE + 4 doubles of LDS per obstacle (62 KB per block at the cap, which the entry asks the runtime
+ *   for); ARMOUR_ECAPACITY, without a launch, when the device grants a block less.
+ * armour_ik_moving_host is the same functions in a loop and touches no device; margin [N] as armour_ik_host's, of the window rule's clearances. */
+int armour_ik_moving(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N,
+                     int32_t S, int32_t W, int32_t O, const double* obstacles, const double* velocity, const double* t_from, const double* t_to,
+                     const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds, double lambda, double e_max,
+                     double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best, double* q, double* err,
+                     int32_t* iterations, int32_t* flags, double* ms);
+int armour_ik_moving_host(const ArmourRobot* robot, const uint8_t* continuous, const double* lb, const double* ub, const double* tool, int32_t N,
+                          int32_t S, int32_t W, int32_t O, const double* obstacles, const double* velocity, const double* t_from,
+                          const double* t_to, const int32_t* world, const double* targets, const double* q_ref, const uint64_t* seeds,
+                          double lambda, double e_max, double tol, int32_t max_iterations, int32_t* status, int32_t* best, double* q_best,
+                          double* q, double* err, int32_t* iterations, int32_t* flags, double* margin);
 int armour_ik_end_effector_host(const ArmourRobot* robot, int32_t N, const double* q, const double* tool, double* p, double* jac);
 
 /* ---- batched workspace RRT*: the end-effector planner's tree for W worlds in one launch (ws_tree.hip) ---- */
@@ -1259,6 +1283,39 @@ int armour_ws_tree_plan_host(const double* lb, const double* ub, int32_t W, int3
                              int32_t max_iterations, int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations,
                              int32_t* points, int32_t* rewires, int32_t* chain_kept, double* path_cost, double* goal_dist, double* path,
                              int32_t* count, double* nodes, int32_t* parent, double* node_cost, double* margin);
+/* armour_ws_tree_plan against obstacles in LINEAR MOTION, over a time window per world: the static entry with velocity [W][O][3], t_from and
+ * t_to [W] after obstacles, which are the poses at world time 0 (armour_roadmap_check_moving's arguments).
+ * The rule.  The host computes once per world mid[w] = 0.5 * (t_from[w] + t_to[w]) and half[w] = 0.5 * (t_to[w] - t_from[w]).  Every box the
+ *   static rule tests -- the point rule's box at the start, every sub-segment box of the edge rule (centre x, axes e_0 e_1 e_2, half-sizes h)
+ *   -- is tested against obstacle o as the box of centre x - v_o mid[w] and half-sizes h_i + |v_o|_2 half[w], each product and sum rounded on
+ *   its own.  The samples, nearest, the steer step, the near set, the parent choice, rewiring, the cost re-derivation, the best node, the path
+ *   and the initial chain (which ends at its first edge that the window blocks) are word for word the static entry's.
+ * Soundness.  Within [t_from, t_to] obstacle o leaves its pose of time mid by at most |v_o| half in the 2-norm, and growing the box by that
+ *   amount along every axis covers it: no point of a returned path, grown by the buffer, meets an obstacle at ANY time of the window,
+ *   whatever the time at which the end effector passes it.  The trees do not carry time; a path is not a schedule.
+ * With zero velocities every output is armour_ws_tree_plan's bit for bit, for any window; t_from == t_to judges at an instant.
+ * ARMOUR_EINVAL before a device is touched: armour_ws_tree_plan's refusals; a null or non-finite velocity, t_from or t_to;
+ *   t_from[w] > t_to[w].  W = 0 is served as the static entry serves it.
+ * Device: the static launch with RM_OBS_STRIDE + 4 doubles of LDS per obstacle (62 KB per block at the cap, which the entry asks the runtime
+ *   for); ARMOUR_ECAPACITY, without a launch, when the device grants a block less.
+ * armour_ws_tree_plan_moving_host is the same functions in a loop and touches no device; margin [W] as armour_ws_tree_plan_host's, of the
+ *   window rule's clearances.
+ * The resident trees below (armour_ws_trees_*) stay static: a kept tree's edges were proved against the world as it stood, and a window that
+ *   has passed proves nothing about the next. */
+int armour_ws_tree_plan_moving(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                               const double* t_from, const double* t_to, const double* starts, const double* goals, const uint64_t* seeds,
+                               int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                               double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations, int32_t max_nodes,
+                               int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires, int32_t* chain_kept,
+                               double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes, int32_t* parent,
+                               double* node_cost, double* ms);
+int armour_ws_tree_plan_moving_host(const double* lb, const double* ub, int32_t W, int32_t O, const double* obstacles, const double* velocity,
+                                    const double* t_from, const double* t_to, const double* starts, const double* goals, const uint64_t* seeds,
+                                    int32_t max_init, const double* init, const int32_t* init_count, double step, double edge_step,
+                                    double rewire_radius, double goal_rate, double buffer, double goal_tol, int32_t max_iterations,
+                                    int32_t max_nodes, int32_t max_points, int32_t* status, int32_t* iterations, int32_t* points, int32_t* rewires,
+                                    int32_t* chain_kept, double* path_cost, double* goal_dist, double* path, int32_t* count, double* nodes,
+                                    int32_t* parent, double* node_cost, double* margin);
 
 /* ---- resident workspace trees: the same trees kept between calls and grown in instalments (ws_tree.hip) ---- */
 /* The reference's grow_tree_mode = 'keep' (RRT_HLP.m:99-117; the mode of kinova_run_hard_scenarios.m): the tree planted at the first call

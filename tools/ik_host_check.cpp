@@ -3,7 +3,8 @@
 // that holds the whole last link, one out of reach -- and armour_ik_end_effector_host, checks what every run must satisfy -- a found
 // configuration reaches its target by the entry's own forward kinematics, stays inside the box on the non-continuous joints, is the flagged
 // item with the smallest (distance, seed), the same call twice gives the same bytes, the Jacobian matches central differences -- and the
-// refusals, and prints what it found.
+// refusals, and prints what it found.  Then the moving twin (armour_ik_moving_host): zero velocity against the static call for two sets of
+// windows, the blocking box arriving on its target, the refusals.
 //   make -C armour_amd/csrc ikhost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
 // It supplies the symbols ik.hip takes from api.hip, so that nothing else of the library is linked.
 #include <cmath>
@@ -143,6 +144,50 @@ int main() {
         !refused(S, 0.05, 0.1, 1e-9, ARMOUR_IK_MAX_ITERATIONS + 1, 0) || !refused(S, 0.05, 0.1, 1e-9, 200, W) || !refused(S, 0.05, 0.1, 1e-9, 200, -2)) {
         printf("FAILED: a bad argument passed\n");
         return 1;
+    }
+    // ---- moving obstacles (armour_ik_moving_host): zero velocity against the static call `a`, for two sets of windows; the blocking cube
+    // of world 1 starting 2 m above the target and coming down at 1 m/s (FOUND on [0, 0.5], ALL_BLOCKED about t = 2); the refusals
+    {
+        Out m;
+        auto run_moving = [&](Out* o, const double* obs, const double* vel, const double* t0, const double* t1) {
+            o->status.assign(N, -7); o->best.assign(N, -7); o->iterations.assign((size_t)N * S, -7); o->flags.assign((size_t)N * S, -7);
+            o->q_best.assign((size_t)N * n, -7.0); o->q.assign((size_t)N * S * n, 0.0); o->err.assign((size_t)N * S, 0.0); o->margin.assign(N, 0.0);
+            return armour_ik_moving_host(&robot, nullptr, lb.data(), ub.data(), tool, N, S, W, O, obs, vel, t0, t1, world, targets.data(), refs.data(), seeds, 0.05, 0.1,
+                                         1e-9, 200, o->status.data(), o->best.data(), o->q_best.data(), o->q.data(), o->err.data(), o->iterations.data(), o->flags.data(),
+                                         o->margin.data());
+        };
+        const double zero[W * O * 3] = {0, 0, 0, 0, 0, 0};
+        const double windows[2][2][W] = {{{0.0, 0.0}, {0.0, 0.0}}, {{-3.0, 7.0}, {4.0, 11.5}}};
+        for (int k = 0; k < 2; k++) {
+            if (run_moving(&m, obstacles, zero, windows[k][0], windows[k][1]) != ARMOUR_OK) { printf("FAILED: moving, zero velocity: %s\n", g_error); return 1; }
+            if (m.status != a.status || m.best != a.best || m.iterations != a.iterations || m.flags != a.flags || std::memcmp(m.q.data(), a.q.data(), a.q.size() * sizeof(double)) ||
+                std::memcmp(m.q_best.data(), a.q_best.data(), a.q_best.size() * sizeof(double)) || std::memcmp(m.err.data(), a.err.data(), a.err.size() * sizeof(double)) ||
+                std::memcmp(m.margin.data(), a.margin.data(), a.margin.size() * sizeof(double))) {
+                printf("FAILED: zero velocity differs from the static entry (windows %d)\n", k);
+                return 1;
+            }
+        }
+        double lifted[W * O * 12];
+        std::memcpy(lifted, obstacles, sizeof(lifted));
+        lifted[12 + 2] += 2.0;
+        const double vel[W * O * 3] = {0, 0, 0, 0, 0, -1.0};
+        const double e0[W] = {0.0, 0.0}, e1[W] = {0.5, 0.5}, l0[W] = {0.0, 1.9}, l1[W] = {0.5, 2.1};
+        if (run_moving(&m, lifted, vel, e0, e1) != ARMOUR_OK || m.status[2] != ARMOUR_IK_FOUND || m.best[2] < 0 || m.status[1] != a.status[1]) {
+            printf("FAILED: the early window: status %d, best %d: %s\n", m.status[2], m.best[2], g_error);
+            return 1;
+        }
+        if (run_moving(&m, lifted, vel, l0, l1) != ARMOUR_OK || m.status[2] != ARMOUR_IK_ALL_BLOCKED || m.status[1] != a.status[1] || !(m.margin[2] > 0.0)) {
+            printf("FAILED: the late window: status %d: %s\n", m.status[2], g_error);
+            return 1;
+        }
+        const double nanv[W * O * 3] = {0, NAN, 0, 0, 0, 0}, inf2[W] = {0.5, INFINITY};
+        if (run_moving(&m, lifted, nullptr, e0, e1) != ARMOUR_EINVAL || run_moving(&m, lifted, nanv, e0, e1) != ARMOUR_EINVAL || run_moving(&m, lifted, vel, nullptr, e1) != ARMOUR_EINVAL ||
+            run_moving(&m, lifted, vel, e0, nullptr) != ARMOUR_EINVAL || run_moving(&m, lifted, vel, e0, inf2) != ARMOUR_EINVAL || run_moving(&m, lifted, vel, l1, l0) != ARMOUR_EINVAL ||
+            run_moving(&m, nullptr, vel, e0, e1) != ARMOUR_EINVAL) {
+            printf("FAILED: a bad argument of the moving entry passed\n");
+            return 1;
+        }
+        printf("ik moving host check ok: zero velocity equals the static call for two sets of windows; the arriving cube blocks its target late\n");
     }
     printf("ik host check ok: %d of %d items converged, picks %d %d %d %d, margins %.3g %.3g, Jacobian within %.2g of central differences\n", converged, N * S, a.best[0],
            a.best[1], a.best[2], a.best[3], a.margin[1], a.margin[2], worst_fd);

@@ -32,8 +32,10 @@ and prints ONE JSON line.
   obstacle in linear motion (seeded velocities, --moving-seed, speeds --moving-speed LO HI in m/s; run_trials(velocities=...)) under the
   straight-line planner, under armour_amd.roadmap.moving_field_hlps (device_roadmap(--roadmap-nodes, --roadmap-radius, 16, seed 0): one
   check_moving, one field and one descend_many per iteration) and under armour_amd.tree_planner.moving_tree_hlps (the --tree-* options; no
-  roadmap: at most three launches per iteration): outcome counts of each, `struck_at_rest` among them, the pieces by kind and verdict, and
-  hlp / build / solve / audit ms per batch iteration.  --moving-planners runs some of the three rows and keeps the file's others.
+  roadmap: at most three launches per iteration) and -- the row `moving_workspace`, run when named in --moving-planners -- under
+  armour_amd.ws_planner.moving_workspace_hlps (the --ws-* options, mode 'new': one armour_ws_tree_plan_moving and one armour_ik_moving call per
+  iteration): outcome counts of each, `struck_at_rest` among them, the pieces by kind and verdict, and
+  hlp / build / solve / audit ms per batch iteration.  --moving-planners runs some of the four rows and keeps the file's others.
   Records, not pass criteria;
 * --moving --spacetime: the same moving worlds under armour_amd.roadmap.spacetime_hlps (one plan_slices per iteration: --spacetime-K slices of
   --spacetime-dt seconds) at each of --spacetime-speeds rad/s, written to profiles/trial_spacetime_bench.json: the record layout of --moving per
@@ -141,9 +143,14 @@ def moving_trials(robot, ws, a):
         rm = Roadmap(robot, nodes, edges, continuous=cont.astype(np.uint8))
         out["roadmap"] = dict(N=int(nodes.shape[0]), E=int(edges.shape[0]), radius=a.roadmap_radius)
     from armour_amd.tree_planner import moving_tree_hlps
-    planners = dict(straight=lambda: "straight", moving_field=lambda: moving_field_hlps(rm, ws, vel),
+    from armour_amd.ws_planner import moving_workspace_hlps
+    planners = dict(moving_workspace=lambda: moving_workspace_hlps(ws, robot, vel, seed=a.tree_seed, lookahead=a.ws_lookahead, max_iterations=a.ws_iterations,
+                                                                   max_nodes=a.ws_nodes, buffer=a.ws_buffer),
+                    straight=lambda: "straight", moving_field=lambda: moving_field_hlps(rm, ws, vel),
                     moving_tree=lambda: moving_tree_hlps(ws, robot, vel, seed=a.tree_seed, shortcut=a.tree_shortcut, mode=a.tree_mode, max_iterations=a.tree_iterations,
                                                          max_nodes=a.tree_nodes))
+    if "moving_workspace" in a.moving_planners:
+        out["workspace"] = dict(seed=a.tree_seed, lookahead_m=a.ws_lookahead, max_iterations=a.ws_iterations, max_nodes=a.ws_nodes, buffer=a.ws_buffer, mode="new")
     if "moving_tree" in a.moving_planners:
         out["tree"] = dict(seed=a.tree_seed, shortcut=a.tree_shortcut, mode=a.tree_mode, max_iterations=a.tree_iterations, max_nodes=a.tree_nodes)
     for key in a.moving_planners:
@@ -151,7 +158,8 @@ def moving_trials(robot, ws, a):
         res = run_trials(ws, hlp=hlp, T=a.T, max_iterations=a.max_iterations, audit_step=a.steps[0], velocities=vel)
         recs = [r for w in res["worlds"] for r in w["records"]]
         per_batch = lambda k: dict(mean=float(np.mean([b[k] for b in res["batches"]])), max=float(np.max([b[k] for b in res["batches"]])))
-        out[key] = dict(outcomes={o: sum(1 for w in res["worlds"] if w["outcome"] == o) for o in OUTCOMES + (STRUCK_OUTCOME,)}, summary=res["summary"],
+        extra = dict(fallbacks=int(sum(h.fallbacks for h in hlp.hlps.values())), calls=int(sum(h.calls for h in hlp.hlps.values()))) if key == "moving_workspace" else {}
+        out[key] = dict(**extra, outcomes={o: sum(1 for w in res["worlds"] if w["outcome"] == o) for o in OUTCOMES + (STRUCK_OUTCOME,)}, summary=res["summary"],
                         pieces={kind: {str(v): sum(1 for r in recs if r["executed"] == kind and r["audit_verdict"] == v) for v in (0, 1, 2)}
                                 for kind in ("plan", "brake", "stay")},
                         ms_per_batch={k: per_batch(k) for k in ("hlp_ms", "build_ms", "solve_ms", "audit_ms")}, first_batch=res["batches"][0])
@@ -266,7 +274,8 @@ def main():
     ap.add_argument("--moving", action="store_true")
     ap.add_argument("--moving-seed", type=int, default=2)
     ap.add_argument("--moving-speed", type=float, nargs=2, default=[0.05, 0.2])
-    ap.add_argument("--moving-planners", nargs="+", choices=["straight", "moving_field", "moving_tree"], default=["straight", "moving_field", "moving_tree"])
+    ap.add_argument("--moving-planners", nargs="+", choices=["straight", "moving_field", "moving_tree", "moving_workspace"],
+                    default=["straight", "moving_field", "moving_tree"])
     ap.add_argument("--spacetime", action="store_true")
     ap.add_argument("--spacetime-speeds", type=float, nargs="+", default=[0.5, 1.0, 2.0])
     ap.add_argument("--spacetime-dt", type=float, default=0.25)

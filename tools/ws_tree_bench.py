@@ -2,6 +2,7 @@
 
     python tools/ws_tree_bench.py [--max-iterations 1000] [--max-nodes 1024] [--seed 7] [--reps 10] [--skip-cap] [--skip-host] [--instalments 10] [--out FILE]
     python tools/ws_tree_bench.py --ab PARENT_LIBRARY [--rounds 3] [--out profiles/ws_trees_bench.json]
+    python tools/ws_tree_bench.py --moving [--moving-seed 2] [--moving-speed 0.05 0.2] [--out profiles/ws_tree_moving_bench.json]
 
 * `batch`: the 107 reference worlds (scenes.reference_worlds; start and goal POINTS = the end effector of the start and of the goal
   configuration, O padded with scenes.FAR_BOX, every world with the seed --seed, the sampling box ws_planner.workspace_box, the planner's
@@ -21,6 +22,12 @@
   process of this tool per run with the library chosen by ARMOUR_HIP_LIB, parent, new, parent, new, ... for --rounds rounds; per shape the
   device ms of every run, the medians, the parent's own spread (max - min over its rounds), whether the new median lies within it, and
   whether the digests are equal; the last new run's `instalments` row.  Written to --out (default profiles/ws_trees_bench.json).
+--moving: a run of its own that writes profiles/ws_tree_moving_bench.json (or --out): the batch by the static entry, by
+  armour_ws_tree_plan_moving at zero velocity on the window [0, 1] (the like-for-like cost of the window rule: same worlds, same trees;
+  `ratio_v0` = static ms / moving ms, `v0_equals_static` = the digests are equal) and with every obstacle in linear motion (velocities from
+  the stream (--moving-seed, world), speeds --moving-speed LO HI in m/s, as tools/tree_bench.py --moving draws them) on the same window;
+  with --ab-static PARENT_LIBRARY also the static batch and one world of the parent commit's library against this one's, alternating in
+  fresh processes for --rounds rounds (the key `static_against_parent`).
 """
 import argparse
 import hashlib
@@ -35,6 +42,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 STATUS = ("partial", "reached", "start_blocked")
 FIELDS = ("status", "iterations", "count", "rewires", "chain_kept", "path_cost", "goal_dist", "nodes", "parent", "node_cost")
@@ -77,6 +85,30 @@ def measure(obs, starts, goals, seeds, box, options, reps, with_host=True):
                 path_points=[0 if p is None else int(len(p)) for p in dev.paths])
 
 
+def moving(a, obs, starts, goals, seeds, box, options, ws):
+    """--moving: see the module text"""
+    from tree_bench import seeded_velocities
+    lo, hi = a.moving_speed
+    window = dict(t_from=0.0, t_to=1.0)
+    legs = dict(static={}, moving_v0=dict(window, velocity=np.zeros(obs.shape[:2] + (3,))),
+                moving=dict(window, velocity=seeded_velocities(ws, obs.shape[1], a.moving_seed, lo, hi)))
+    keep = ("device_ms", "device_ms_min", "call_ms", "device_equals_host", "host_margin_min", "digest", "status_counts")
+    res = {k: measure(obs, starts, goals, seeds, box, dict(options, **kw), a.reps, not a.skip_host) for k, kw in legs.items()}
+    out = dict(tool="ws_tree_bench --moving", seed=a.seed, reps=a.reps, **options, worlds=int(obs.shape[0]), obstacles_per_world=int(obs.shape[1]), window=[0.0, 1.0],
+               moving_seed=a.moving_seed, speed=[lo, hi], **{k: {f: r[f] for f in keep} for k, r in res.items()})
+    out["ratio_v0"] = round(res["static"]["device_ms"] / res["moving_v0"]["device_ms"], 4)
+    out["v0_equals_static"] = bool(res["static"]["digest"] == res["moving_v0"]["digest"])
+    out["worlds_planned_differently_moving"] = int(sum(x != y for x, y in zip(res["static"]["tree_sizes"], res["moving"]["tree_sizes"])))
+    if a.ab_static:
+        a.ab, a.instalments = a.ab_static, 0
+        rows = ab(a, write=False)
+        out["static_against_parent"] = {k: rows[k] for k in ("batch", "one_world")}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def instalments(obs, starts, goals, seeds, box, options, reps, K, plan_row):
     """The batch on resident trees: K grows of max_iterations / K iterations each, on `reps` fresh handles"""
     from armour_amd import _lib
@@ -113,7 +145,7 @@ def instalments(obs, starts, goals, seeds, box, options, reps, K, plan_row):
 SHAPES = ("batch", "one_world", "at_the_cap")
 
 
-def ab(a):
+def ab(a, write=True):
     """--ab: parent, new, parent, new, ... in fresh processes; see the module text"""
     runs = {"parent": [], "new": []}
     with tempfile.TemporaryDirectory() as tmp:
@@ -126,17 +158,19 @@ def ab(a):
                     env["ARMOUR_HIP_LIB"] = os.path.abspath(a.ab)
                 cmd = [sys.executable, os.path.abspath(__file__), "--skip-host", "--out", out, "--max-iterations", str(a.max_iterations), "--max-nodes", str(a.max_nodes),
                        "--cap-iterations", str(a.cap_iterations), "--seed", str(a.seed), "--reps", str(a.reps),
-                       "--instalments", str(a.instalments if side == "new" and rnd == a.rounds - 1 else 0)]
+                       "--instalments", str(a.instalments if side == "new" and rnd == a.rounds - 1 else 0)] + (["--skip-cap"] if a.skip_cap else [])
                 subprocess.run(cmd, env=env, check=True, stdout=subprocess.DEVNULL, timeout=600)
                 runs[side].append(json.load(open(out)))
     rows = {}
-    for shape in SHAPES:
+    for shape in (s for s in SHAPES if s in runs["new"][0]):
         p, n = [r[shape]["device_ms"] for r in runs["parent"]], [r[shape]["device_ms"] for r in runs["new"]]
         pm, nm, spread = float(np.median(p)), float(np.median(n)), max(p) - min(p)
         digests = {r[shape]["digest"] for side in runs for r in runs[side]}
         rows[shape] = dict(parent_device_ms=p, new_device_ms=n, parent_median=pm, new_median=nm, parent_spread=round(spread, 4), new_over_parent=round(nm / pm, 4),
                            within_parent_spread=bool(nm <= pm + spread), digests_equal=len(digests) == 1, digest=runs["new"][-1][shape]["digest"],
                            parent_call_ms=[r[shape]["call_ms"] for r in runs["parent"]], new_call_ms=[r[shape]["call_ms"] for r in runs["new"]])
+    if not write:
+        return rows
     last = runs["new"][-1]
     out = dict(tool="ws_tree_bench --ab", what="armour_ws_tree_plan of the parent commit's library against this one on one MI355X in one visit: parent, new, parent, new, "
                "...; a fresh process per run, the library chosen by ARMOUR_HIP_LIB.  device ms = the median of `reps` launches per run; parent_spread = max - min of "
@@ -161,9 +195,13 @@ def main():
     ap.add_argument("--instalments", type=int, default=10)
     ap.add_argument("--ab")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--moving", action="store_true")
+    ap.add_argument("--moving-seed", type=int, default=2)
+    ap.add_argument("--moving-speed", type=float, nargs=2, default=[0.05, 0.2])
+    ap.add_argument("--ab-static")
     ap.add_argument("--out")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "ws_trees_bench.json" if a.ab else "ws_tree_bench.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "ws_tree_moving_bench.json" if a.moving else "ws_trees_bench.json" if a.ab else "ws_tree_bench.json")
     if a.ab:
         return ab(a)
     from armour_amd import _lib, ik, scenes
@@ -181,6 +219,8 @@ def main():
     options = dict(max_iterations=a.max_iterations, max_nodes=a.max_nodes)
     out = dict(tool="ws_tree_bench", robot="kinova_gen3_no_gripper", library=os.path.basename(_lib.LIB_PATH), seed=a.seed, reps=a.reps, step=STEP, edge_step=EDGE_STEP,
                rewire_radius=REWIRE_RADIUS, goal_rate=GOAL_RATE, goal_tol=GOAL_TOL, box=[list(box[0]), list(box[1])], **options)
+    if a.moving:
+        return moving(a, obs, starts, goals, seeds, box, options, ws)
     out["batch"] = dict(measure(obs, starts, goals, seeds, box, options, a.reps, not a.skip_host), names=names)
     w = names.index("hard_7_window")
     out["one_world"] = dict(measure(obs[w:w + 1], starts[w:w + 1], goals[w:w + 1], seeds[w:w + 1], box, options, a.reps, not a.skip_host), name=names[w])

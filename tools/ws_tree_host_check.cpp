@@ -5,6 +5,8 @@
 // whose distance to the goal is goal_dist, the same seed gives the same bytes -- and the refusals, and prints what it found.
 // Then the resident trees' host handle (armour_ws_trees_create_host / _grow / _read / _destroy): instalments of a permuted subset and of
 // every world must leave each world with the bytes of one plan of its own sum; a blocked start, ECAPACITY by slot, the refusals.
+// And the moving twin (armour_ws_tree_plan_moving_host): zero velocity against the static call for two sets of windows, a drifting wall, one
+// box that arrives at the start point, the refusals.
 //   make -C armour_amd/csrc wshost      (hipcc -Xarch_host -fsanitize=address,undefined; no GPU is used)
 // It supplies the symbols ws_tree.hip takes from api.hip, so that nothing else of the library is linked.
 #include <cmath>
@@ -208,6 +210,59 @@ int main() {
         armour_ws_trees_destroy(h);
         armour_ws_trees_destroy(nullptr);
         printf("ws trees host check ok: 100 + 0 + 200 / 200 / 100 + 0 + 200 iterations in instalments equal one plan each: %d / %d / %d nodes\n", rcount[0], rcount[1], rcount[2]);
+    }
+    // ---- moving obstacles (armour_ws_tree_plan_moving_host): zero velocity against the static call `a`, for two sets of windows; one box that
+    // arrives at the start point (free on [0, 1], START_BLOCKED on [0, 3]); the refusals
+    {
+        Out m;
+        auto run_moving = [&](Out* o, const double* vel, const double* t0, const double* t1) {
+            o->status.assign(W, -1); o->iterations.assign(W, -1); o->points.assign(W, -1); o->rewires.assign(W, -1); o->kept.assign(W, -1); o->count.assign(W, -1);
+            o->parent.assign((size_t)W * cap, -7); o->path_cost.assign(W, -1.0); o->goal_dist.assign(W, -1.0); o->path.assign((size_t)W * cap * 3, 0.0);
+            o->nodes.assign((size_t)W * cap * 3, 0.0); o->cost.assign((size_t)W * cap, 0.0); o->margin.assign(W, 0.0);
+            return armour_ws_tree_plan_moving_host(lb, ub, W, O, obstacles.data(), vel, t0, t1, starts.data(), goals.data(), seeds, max_init, &chains[0][0][0], chain_count,
+                                                   0.1, 0.01, 0.2, 0.1, 0.01, 0.01, iters, cap, cap, o->status.data(), o->iterations.data(), o->points.data(),
+                                                   o->rewires.data(), o->kept.data(), o->path_cost.data(), o->goal_dist.data(), o->path.data(), o->count.data(),
+                                                   o->nodes.data(), o->parent.data(), o->cost.data(), o->margin.data());
+        };
+        const std::vector<double> zero((size_t)W * O * 3, 0.0);
+        const double windows[2][2][W] = {{{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, {{-3.0, 0.25, 7.0}, {4.0, 0.25, 11.5}}};
+        for (int k = 0; k < 2; k++) {
+            if (run_moving(&m, zero.data(), windows[k][0], windows[k][1]) != ARMOUR_OK) { printf("FAILED: moving, zero velocity: %s\n", g_error); return 1; }
+            if (m.status != a.status || m.iterations != a.iterations || m.points != a.points || m.rewires != a.rewires || m.kept != a.kept || m.count != a.count ||
+                m.parent != a.parent || std::memcmp(m.path.data(), a.path.data(), a.path.size() * sizeof(double)) ||
+                std::memcmp(m.nodes.data(), a.nodes.data(), a.nodes.size() * sizeof(double)) || std::memcmp(m.cost.data(), a.cost.data(), a.cost.size() * sizeof(double)) ||
+                std::memcmp(m.path_cost.data(), a.path_cost.data(), W * sizeof(double)) || std::memcmp(m.goal_dist.data(), a.goal_dist.data(), W * sizeof(double)) ||
+                std::memcmp(m.margin.data(), a.margin.data(), W * sizeof(double))) {
+                printf("FAILED: zero velocity differs from the static entry (windows %d)\n", k);
+                return 1;
+            }
+        }
+        // a drifting wall and windows of three kinds: the trees must keep the static entry's invariants
+        std::vector<double> drift((size_t)W * O * 3, 0.0);
+        for (size_t i = 0; i < drift.size(); i += 3) { drift[i] = 0.01; drift[i + 1] = -0.02; drift[i + 2] = 0.005; }
+        const double d0[W] = {0.0, 1.25, -0.1}, d1[W] = {0.5, 1.25, 0.2};
+        if (run_moving(&m, drift.data(), d0, d1) != ARMOUR_OK || !check_trees(m, cap, cap)) { printf("FAILED: moving, drifting wall: %s\n", g_error); return 1; }
+        // one box 1 m above the start point, coming down at 0.5 m/s
+        std::vector<double> one_box;
+        box(&one_box, start[0], start[1], start[2] + 1.0, 0.05, 0.05, 0.05);
+        const double v[3] = {0.0, 0.0, -0.5}, from[1] = {0.0}, early[1] = {1.0}, late[1] = {3.0};
+        int32_t s1, i1, p1, r1, k1, c1;
+        double pc1, gd1, mg1;
+        auto arriving = [&](const double* vel, const double* t0, const double* t1, const double* obs) {
+            return armour_ws_tree_plan_moving_host(lb, ub, 1, 1, obs, vel, t0, t1, start, goal, seeds, 0, nullptr, nullptr, 0.1, 0.01, 0.2, 0.1, 0.0, 0.01, 40, cap, 0, &s1, &i1,
+                                                   &p1, &r1, &k1, &pc1, &gd1, nullptr, &c1, nullptr, nullptr, nullptr, &mg1);
+        };
+        if (arriving(v, from, early, one_box.data()) != ARMOUR_OK || s1 == ARMOUR_WS_START_BLOCKED || c1 < 2) { printf("FAILED: the early window: status %d, %d nodes\n", s1, c1); return 1; }
+        if (arriving(v, from, late, one_box.data()) != ARMOUR_OK || s1 != ARMOUR_WS_START_BLOCKED || c1 != 0 || !(mg1 > 0.0)) { printf("FAILED: the late window: status %d, %d nodes\n", s1, c1); return 1; }
+        const double nanv[3] = {0.0, NAN, 0.0}, inf1[1] = {INFINITY};
+        if (arriving(nullptr, from, early, one_box.data()) != ARMOUR_EINVAL || arriving(nanv, from, early, one_box.data()) != ARMOUR_EINVAL ||
+            arriving(v, nullptr, early, one_box.data()) != ARMOUR_EINVAL || arriving(v, from, nullptr, one_box.data()) != ARMOUR_EINVAL ||
+            arriving(v, from, inf1, one_box.data()) != ARMOUR_EINVAL || arriving(v, late, early, one_box.data()) != ARMOUR_EINVAL ||
+            arriving(v, from, early, nullptr) != ARMOUR_EINVAL) {
+            printf("FAILED: a bad argument of the moving entry passed\n");
+            return 1;
+        }
+        printf("ws tree moving host check ok: zero velocity equals the static call for two sets of windows; drifting wall %d / %d / %d nodes\n", m.count[0], m.count[1], m.count[2]);
     }
     printf("ws tree host check ok: %d / %d / %d nodes, %d / %d / %d rewires, path costs %.4f %.4f %.4f, chains kept %d %d %d, margins %.3g %.3g %.3g\n", a.count[0],
            a.count[1], a.count[2], a.rewires[0], a.rewires[1], a.rewires[2], a.path_cost[0], a.path_cost[1], a.path_cost[2], a.kept[0], a.kept[1], a.kept[2], a.margin[0],
