@@ -224,8 +224,12 @@ Q_A = np.array([0.3, 0.6, -0.2, 1.2, 0.1, 0.6, 0.0])
 
 
 def blocking_box(g, p):
-    """a cube about the point p that holds the whole last link, wherever it points, when the last frame's origin is at p"""
-    r = np.sqrt(dot3(g["c"][-1], g["c"][-1])) + np.sqrt(dot3(g["h"][-1], g["h"][-1])) + 0.01
+    """a cube about the point p that holds the whole last link that has a box (the last link itself on the Kinova arms; the Fetch presets end
+    in links without one), wherever it points, when the last frame's origin is at p"""
+    l = max(i for i in range(g["J"]) if np.any(g["h"][i] != 0.0))
+    r = np.sqrt(dot3(g["c"][l], g["c"][l])) + np.sqrt(dot3(g["h"][l], g["h"][l])) + 0.01
+    for i in range(l + 1, g["J"]):
+        r = r + np.sqrt(dot3(g["trans"][i], g["trans"][i]))
     return np.array([p[0], p[1], p[2], r, 0, 0, 0, r, 0, 0, 0, r])
 
 

@@ -158,9 +158,20 @@ def edge_free_np(g, a, b, Z, edge_step):
 
 
 # ----------------------------------------------------------------------------------------------------------- helpers
-def _robot(name):
+def _kinova8_robot():
+    """The Kinova with an eighth revolute joint and link (tests/test_key128.py): J = n = 8, no fixed joint."""
     from armour_amd import planner
-    return {"kinova": planner.kinova_robot, "gripper": planner.kinova_gripper_robot, "fetch": planner.fetch_robot}[name]()
+    from test_key128 import make_eight_factor_arm
+    return make_eight_factor_arm(planner.kinova_robot())
+
+
+def _robot(name):
+    """The preset `name`.  "fetch8" (n = 8, J = 9) and "kinova8" (n = J = 8) exist in the 8-factor ABI only (ARMOUR_KEY128=1)."""
+    from armour_amd import _lib, planner
+    presets = {"kinova": planner.kinova_robot, "gripper": planner.kinova_gripper_robot, "fetch": planner.fetch_robot}
+    if _lib.MAXF == 8:
+        presets.update(fetch8=planner.fetch8_robot, kinova8=_kinova8_robot)
+    return presets[name]()
 
 
 def _fetch8_dict():
@@ -389,7 +400,8 @@ def test_stationary_reach_set_agrees_with_the_node_check():
 def _wall_world(g):
     """A start / goal pair of the Kinova whose straight segment hits a wall, and a hand-placed free detour chain.  The wall is a thin
     box through the end of the forearm at the segment's middle; the detour folds the elbow, swings the base and unfolds."""
-    start = np.array([0.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0])
+    start = np.zeros(g["n"])                                   # (an arm with more factors than the Kinova: its further joints at zero)
+    start[:7] = [0.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0]
     goal = start.copy()
     goal[0] = 2.0
     mid = 0.5 * (start + goal)

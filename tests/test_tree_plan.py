@@ -121,7 +121,7 @@ def assert_equals_restatement(res, w, ref):
     assert list(res.count[w]) == list(ref["count"])
     for k in range(2):
         c = ref["count"][k]
-        assert _same_bits(res.nodes[w, k, :c], np.reshape(ref["nodes"][k], (c, -1)))
+        assert _same_bits(res.nodes[w, k, :c], np.reshape(ref["nodes"][k], (c, res.nodes.shape[-1])))       # (c = 0: a run that grew no tree)
         assert list(res.parent[w, k, :c]) == list(ref["parent"][k])
     assert (res.paths[w] is None) == (ref["path"] is None)
     if ref["path"] is not None:
@@ -181,15 +181,17 @@ def test_host_twin_equals_the_numpy_restatement_on_the_wall_world(kinova, seed):
     assert abs(res.margin[0] - ref["margin"]) <= 1e-12
 
 
-def _fetch_world():
-    robot = _robot("fetch")
+def _fetch_world(name="fetch"):
+    """name "fetch8" (the 8-factor ABI's preset): the same arm behind a torso yaw joint, so every joint and link index moves up by one"""
+    robot = _robot(name)
     g = geometry(robot_dict(robot))
     lb, ub, _ = _limits(robot)
+    up = robot.num_factors - 7
     start = np.zeros(robot.num_factors)
-    start[1], start[3] = 0.4, 0.8
+    start[1 + up], start[3 + up] = 0.4, 0.8
     goal = start.copy()
-    goal[0] = 1.2
-    c = link_boxes(g, (0.5 * (start + goal))[None])[2][0, 5]
+    goal[up] = 1.2
+    c = link_boxes(g, (0.5 * (start + goal))[None])[2][0, 5 + up]
     wall = np.array([[c[0], c[1], c[2], 0.05, 0, 0, 0, 0.05, 0, 0, 0, 0.10]])
     return dict(robot=robot, g=g, lb=lb, ub=ub, start=start, goal=goal, wall=wall)
 

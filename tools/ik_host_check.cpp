@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../armour_amd/csrc/roadmap_handle.h"
-#include "../include/armour_robot_kinova.h"
+#include "host_check_robot.h"
 
 static char g_error[512];
 void armour_set_error(const char* fmt, ...) {
@@ -30,17 +30,17 @@ using namespace rmgeo;
 
 int main() {
     ArmourRobot robot;
-    armour_fill_kinova_gen3_no_gripper(&robot);
+    host_check_robot(&robot);
     RmRobot rb;
     fill_rm_robot(&robot, nullptr, &rb);
     const int n = rb.n, N = 4, S = 16, W = 2, O = 1;
-    const double q_goal[7] = {0.3, 0.6, -0.2, 1.2, 0.1, 0.6, 0.0}, q_ref[7] = {0.0, 0.3, 0.0, 0.9, 0.0, 0.4, 0.0}, tool[3] = {0.0, 0.0, 0.0};
-    double pg[3], jac[3 * 7];
+    const double *q_goal = HC_IK_GOAL, *q_ref = HC_IK_REF, tool[3] = {0.0, 0.0, 0.0};
+    double pg[3], jac[3 * ARMOUR_MAX_FACTORS];
     if (armour_ik_end_effector_host(&robot, 1, q_goal, tool, pg, jac) != ARMOUR_OK) { printf("FAILED: %s\n", g_error); return 1; }
     // the Jacobian against central differences of the point
     double worst_fd = 0.0;
     for (int j = 0; j < n; j++) {
-        double qa[7], qb[7], pa[3], pb[3];
+        double qa[ARMOUR_MAX_FACTORS], qb[ARMOUR_MAX_FACTORS], pa[3], pb[3];
         std::memcpy(qa, q_goal, sizeof(qa));
         std::memcpy(qb, q_goal, sizeof(qb));
         qa[j] -= 1e-6; qb[j] += 1e-6;
@@ -51,8 +51,11 @@ int main() {
         for (int r = 0; r < 3; r++) worst_fd = std::fmax(worst_fd, std::fabs(jac[r * n + j] - (pb[r] - pa[r]) / 2e-6));
     }
     if (!(worst_fd <= 1e-8)) { printf("FAILED: the Jacobian is %g away from central differences\n", worst_fd); return 1; }
-    // world 0: a box far below the base; world 1: a cube about the target that holds the whole last link
-    const double rr = std::sqrt(dot3(rb.c[rb.J - 1], rb.c[rb.J - 1])) + std::sqrt(dot3(rb.h[rb.J - 1], rb.h[rb.J - 1])) + 0.01;
+    // world 0: a box far below the base; world 1: a cube about the target that holds the whole last link that has a box (fetch8 ends in one without)
+    int boxed = rb.J - 1;
+    while (boxed > 0 && dot3(rb.h[boxed], rb.h[boxed]) == 0.0) boxed--;
+    double rr = std::sqrt(dot3(rb.c[boxed], rb.c[boxed])) + std::sqrt(dot3(rb.h[boxed], rb.h[boxed])) + 0.01;
+    for (int l = boxed + 1; l < rb.J; l++) rr += std::sqrt(dot3(rb.trans[l], rb.trans[l]));
     const double obstacles[W * O * 12] = {0, 0, -50, 0.005, 0, 0, 0, 0.005, 0, 0, 0, 0.005, pg[0], pg[1], pg[2], rr, 0, 0, 0, rr, 0, 0, 0, rr};
     const int32_t world[N] = {-1, 0, 1, 0};
     std::vector<double> targets, refs, lb(n), ub(n);

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../armour_amd/csrc/roadmap_handle.h"
-#include "../include/armour_robot_kinova.h"
+#include "host_check_robot.h"
 
 static char g_error[512];
 void armour_set_error(const char* fmt, ...) {
@@ -29,7 +29,7 @@ void armour_set_error(const char* fmt, ...) {
 
 int main() {
     ArmourRobot robot;
-    armour_fill_kinova_gen3_no_gripper(&robot);
+    host_check_robot(&robot);
     const int n = robot.num_factors, N = 301, Q = 67;
     uint64_t seed = 2024;
     auto unit = [&]() { seed = seed * 6364136223846793005ull + 1442695040888963407ull; return (double)(seed >> 11) / 9007199254740992.0; };

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../armour_amd/csrc/roadmap_handle.h"
-#include "../include/armour_robot_kinova.h"
+#include "host_check_robot.h"
 
 static char g_error[512];
 void armour_set_error(const char* fmt, ...) {
@@ -32,26 +32,26 @@ static const double SENTINEL = -7.25;
 
 int main() {
     ArmourRobot robot;
-    armour_fill_kinova_gen3_no_gripper(&robot);
+    host_check_robot(&robot);
     RmRobot rb;
     fill_rm_robot(&robot, nullptr, &rb);
     const int n = rb.n, W = 4, O = 1;
     const double edge_step = 0.05;
-    const double start[7] = {0.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0}, goal[7] = {2.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0};
-    // the wall: a thin box through the centre of link 5 halfway along the straight segment
+    const double *start = HC_START, *goal = HC_GOAL;
+    // the wall: a thin box through the centre of link 5 (fetch8: 6) halfway along the straight segment
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0}, x[3], u[3][3];
-    for (int l = 0; l <= 5; l++) link_frame(rb, l, 0.5 * (start[l] + goal[l]), R, p);
-    link_box(rb, 5, R, p, x, u);
-    const double wall[12] = {x[0], x[1], x[2], 0.06, 0, 0, 0, 0.06, 0, 0, 0, 0.12}, far_box[12] = {0, 0, -50, 0.005, 0, 0, 0, 0.005, 0, 0, 0, 0.005};
+    for (int l = 0; l <= HC_WALL_LINK; l++) link_frame(rb, l, l < n ? 0.5 * (start[l] + goal[l]) : 0.0, R, p);
+    link_box(rb, HC_WALL_LINK, R, p, x, u);
+    const double wall[12] = {x[0], x[1], x[2], HC_WALL_HALF[0], 0, 0, 0, HC_WALL_HALF[1], 0, 0, 0, HC_WALL_HALF[2]}, far_box[12] = {0, 0, -50, 0.005, 0, 0, 0, 0.005, 0, 0, 0, 0.005};
     // the detour: halfway, with the shoulder swung 2 rad back; each leg cut into 8 pieces
-    double corner[7];
+    double corner[ARMOUR_MAX_FACTORS];
     for (int j = 0; j < n; j++) corner[j] = 0.5 * (start[j] + goal[j]);
-    corner[1] -= 2.0;
+    corner[HC_SWING_JOINT] += HC_SWING;
     std::vector<std::vector<double>> in(W);
     auto push = [&](std::vector<double>& v, const double* q) { v.insert(v.end(), q, q + n); };
     for (int leg = 0; leg < 2; leg++)
         for (int k = 0; k < 8; k++) {
-            double q[7];
+            double q[ARMOUR_MAX_FACTORS];
             const double* a = leg ? corner : start;
             const double* b = leg ? goal : corner;
             for (int j = 0; j < n; j++) q[j] = a[j] + (k / 8.0) * (b[j] - a[j]);
@@ -173,7 +173,8 @@ int main() {
                 away[(size_t)w * 12 + i] += 1.0 * out_dir[i];
                 vel[(size_t)w * 3 + i] = -0.5 * out_dir[i];
             }
-        const double early_from[W] = {0.0, 0.0, 0.0, 0.0}, early_to[W] = {0.2, 0.2, 0.2, 0.2}, late_from[W] = {1.4, 1.4, 1.4, 1.4}, late_to[W] = {1.6, 1.6, 1.6, 1.6};
+        const double early_from[W] = {0.0, 0.0, 0.0, 0.0}, early_to[W] = {0.2, 0.2, 0.2, 0.2}, late_from[W] = {HC_LATE[0], HC_LATE[0], HC_LATE[0], HC_LATE[0]},
+                     late_to[W] = {HC_LATE[1], HC_LATE[1], HC_LATE[1], HC_LATE[1]};
         Out early, late;
         if (run_moving(&early, away.data(), vel.data(), early_from, early_to) != ARMOUR_OK || run_moving(&late, away.data(), vel.data(), late_from, late_to) != ARMOUR_OK) {
             printf("FAILED: the moving call: %s\n", g_error);
@@ -185,15 +186,15 @@ int main() {
                    late.status[2], late.status[0], late.points[0]);
             return 1;
         }
-        const double reversed[W] = {0.0, 1.7, 0.0, 0.0};
+        const double reversed[W] = {0.0, HC_LATE[1] + 0.1, 0.0, 0.0};
         vel[4] = NAN;
         if (run_moving(&b, away.data(), nullptr, late_from, late_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), vel.data(), late_from, late_to) != ARMOUR_EINVAL ||
             run_moving(&b, away.data(), zero.data(), reversed, late_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), zero.data(), late_from, nullptr) != ARMOUR_EINVAL) {
             printf("FAILED: a bad velocity or window passed\n");
             return 1;
         }
-        printf("moving: zero velocity equals the static call; the arriving wall: the straight segment is free on [0, 0.2] and invalid on [1.4, 1.6], the detour %d -> %d points\n",
-               counts[0], late.points[0]);
+        printf("moving: zero velocity equals the static call; the arriving wall: the straight segment is free on [0, 0.2] and invalid on [%g, %g], the detour %d -> %d points\n",
+               HC_LATE[0], HC_LATE[1], counts[0], late.points[0]);
     }
     // refusals
     Out r;

@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "../armour_amd/csrc/roadmap_handle.h"
-#include "../include/armour_robot_kinova.h"
+#include "host_check_robot.h"
 
 static char g_error[512];
 void armour_set_error(const char* fmt, ...) {
@@ -28,16 +28,16 @@ using namespace rmgeo;
 
 int main() {
     ArmourRobot robot;
-    armour_fill_kinova_gen3_no_gripper(&robot);
+    host_check_robot(&robot);
     RmRobot rb;
     fill_rm_robot(&robot, nullptr, &rb);
     const int n = rb.n, W = 3, O = 1, cap = 512, max_points = 2 * cap;
-    const double start[7] = {0.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0}, goal[7] = {2.0, 0.6, 0.0, 1.2, 0.0, 0.6, 0.0};
-    // the wall: a thin box through the centre of link 5 halfway along the straight segment
+    const double *start = HC_START, *goal = HC_GOAL;
+    // the wall: a thin box through the centre of link 5 (fetch8: 6) halfway along the straight segment
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0}, x[3], u[3][3];
-    for (int l = 0; l <= 5; l++) link_frame(rb, l, 0.5 * (start[l] + goal[l]), R, p);
-    link_box(rb, 5, R, p, x, u);
-    const double wall[12] = {x[0], x[1], x[2], 0.06, 0, 0, 0, 0.06, 0, 0, 0, 0.12}, far_box[12] = {0, 0, -50, 0.005, 0, 0, 0, 0.005, 0, 0, 0, 0.005};
+    for (int l = 0; l <= HC_WALL_LINK; l++) link_frame(rb, l, l < n ? 0.5 * (start[l] + goal[l]) : 0.0, R, p);
+    link_box(rb, HC_WALL_LINK, R, p, x, u);
+    const double wall[12] = {x[0], x[1], x[2], HC_WALL_HALF[0], 0, 0, 0, HC_WALL_HALF[1], 0, 0, 0, HC_WALL_HALF[2]}, far_box[12] = {0, 0, -50, 0.005, 0, 0, 0, 0.005, 0, 0, 0, 0.005};
     std::vector<double> obstacles, starts, goals, lb(n), ub(n);
     for (int w = 0; w < W; w++) {
         obstacles.insert(obstacles.end(), w < 2 ? wall : far_box, (w < 2 ? wall : far_box) + 12);
@@ -142,7 +142,7 @@ int main() {
             away[(size_t)w * 12 + i] += 1.0 * out_dir[i];
             vel[(size_t)w * 3 + i] = -0.5 * out_dir[i];
         }
-    const double m_from[W] = {0.0, 1.4, 0.0}, m_to[W] = {0.2, 1.6, 1.0};
+    const double m_from[W] = {0.0, HC_LATE[0], 0.0}, m_to[W] = {0.2, HC_LATE[1], 1.0};
     if (run_moving(&b, away.data(), vel.data(), m_from, m_to) != ARMOUR_OK) { printf("FAILED: the moving call: %s\n", g_error); return 1; }
     if (b.status[0] != ARMOUR_TREE_FOUND || b.points[0] != 2 || b.iterations[0] != 0 || b.status[1] != ARMOUR_TREE_FOUND || b.points[1] <= 2 || b.iterations[1] < 1 ||
         !(b.margin[0] > 0.0) || !(b.margin[1] > 0.0)) {
@@ -168,7 +168,7 @@ int main() {
             }
     }
     const int grown_points = b.points[1], grown_iterations = b.iterations[1];
-    const double reversed[W] = {0.0, 1.7, 0.0}, nan_t[W] = {0.0, NAN, 0.0};
+    const double reversed[W] = {0.0, HC_LATE[1] + 0.1, 0.0}, nan_t[W] = {0.0, NAN, 0.0};
     vel[4] = INFINITY;
     if (run_moving(&b, away.data(), nullptr, m_from, m_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), vel.data(), m_from, m_to) != ARMOUR_EINVAL ||
         run_moving(&b, away.data(), zero.data(), reversed, m_to) != ARMOUR_EINVAL || run_moving(&b, away.data(), zero.data(), m_from, nan_t) != ARMOUR_EINVAL ||
@@ -176,8 +176,8 @@ int main() {
         printf("FAILED: a bad velocity or window passed\n");
         return 1;
     }
-    printf("moving: zero velocity equals the static call; the arriving wall: direct edge on [0, 0.2], %d points after %d iterations on [1.4, 1.6], %d edges free over it\n",
-           grown_points, grown_iterations, moving_edges);
+    printf("moving: zero velocity equals the static call; the arriving wall: direct edge on [0, 0.2], %d points after %d iterations on [%g, %g], %d edges free over it\n",
+           grown_points, grown_iterations, HC_LATE[0], HC_LATE[1], moving_edges);
     printf("tree host check ok: wall world found after %d / %d iterations with %d / %d points, %d path edges free by the rule, margins %.3g %.3g %.3g\n",
            a.iterations[0], a.iterations[1], a.points[0], a.points[1], edges, a.margin[0], a.margin[1], a.margin[2]);
     return 0;
